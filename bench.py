@@ -42,6 +42,29 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 1 << 21    # --dump-outputs: cells written of a larger field (2 x 16 MB: values + cell numbers), a fixed seeded sample
+DUMP_SEED = 20240611
+
+
+def field_sample(name, psi, budget=DUMP_SAMPLE):
+    """{name: psi at the sampled cells, name_cells: those cells (as float64)}; the whole field if it fits the budget.  psi: torch 1-D"""
+    import torch
+    n = int(psi.shape[0])
+    if n <= budget:
+        return {name: psi.double().cpu().numpy()}
+    cells = np.sort(np.random.default_rng(DUMP_SEED).choice(n, budget, replace=False))
+    vals = psi[torch.from_numpy(cells).to(psi.device)].double().cpu().numpy()
+    return {name: vals, name + "_cells": cells.astype(np.float64)}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
+
+
 def parts_for(n):
     return {1: (1, 1, 1), 2: (1, 1, 2), 4: (1, 2, 2), 8: (2, 2, 2)}.get(n) or (1, 1, n)
 
@@ -131,6 +154,8 @@ def bench_gamg(args, eng, syn, ctx, dev, json_fd):
         h = perf["history"]
         above = h > 1e-12                     # (past ~70 cycles the residual sits at the rounding floor; the cycles cost the same)
         assert perf["nIterations"] == K and np.all(np.diff(h)[above[1:]] < 0), perf
+    if args.dump_outputs:                 # the last timed solve: its solution and residual history
+        dump_outputs(args.dump_outputs, {**field_sample("psi", psi), "history": perf["history"]})
     elapsed = float(np.median(rep_s))
     levels = [(G.level_sizes(l)["n_coarse"], G.level_sizes(l)["n_coarse_faces"]) for l in range(G.n_levels)]
     ctl = dict(nPostSweeps=2, postSweepsLevelMultiplier=1, maxPostSweeps=4, nFinestSweeps=2)
@@ -209,6 +234,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)   # median of 5 repeats of the timed region
     ap.add_argument("--solver", choices=["pcg", "gamg"], default="pcg")   # gamg: BASELINE config 3 (a second mode, 1 GPU; a step = one V-cycle)
     ap.add_argument("--no-supplements", action="store_true")   # skip config.supplements (configs 3 and 4/5 on the same box, N = 1 only)
+    # after the timed steps: the solution (a fixed sample of its cells past 2^21) and the residual history the timed solve produced,
+    # as DIR/<name>.npy (float64, < 64 MB); the ranks of a decomposed run write their sub-domain's solution as psi_rank<r>
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
     args = ap.parse_args()
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: become the launcher (one rank per GPU, as the driver's
@@ -315,8 +343,13 @@ def main():
             a_ms = mat.pcg_iterate(K, time_amul=True, event_stride=ev_stride)  # HIP events around every 4th Amul launch of the timed region
             torch.cuda.synchronize()
             rep_s.append(time.perf_counter() - t0); rep_amul_ms.append(a_ms)
-        perf = mat.pcg_end(None, history_len=W + R * K + 2)
+        psi_out = torch.empty(N, dtype=torch.float64, device=dev) if args.dump_outputs else None   # (the solution in cell order)
+        perf = mat.pcg_end(psi_out, history_len=W + R * K + 2)
         assert perf["nIterations"] == W + R * K, perf          # every timed step really iterated (no device-side early exit)
+        if args.dump_outputs:
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, {**field_sample("psi", psi_out), "history": perf["history"]})
+            del psi_out
         fused_rp = ctx.stat(4) > 0
         if fused_rp:                                             # (csrc/pcg_fused.inc ran: three launches per iteration instead of five)
             host_loop += ": Amul, fold, then ONE launch for residual update + test + next direction (z = rD o rA stays on the chip)"
@@ -450,6 +483,9 @@ def main():
             solver.iterate(K); torch.cuda.synchronize()
         perf = solver.end()
         assert perf["nIterations"] == W + (R + 1) * K, perf
+        if args.dump_outputs:                 # each rank its sub-domain's solution (cell order), rank 0 also the residual history
+            part = field_sample("psi" if world == 1 else f"psi_rank{rank}", torch.from_numpy(solver.ops.solution()), DUMP_SAMPLE // world)
+            dump_outputs(args.dump_outputs, {**part, "history": perf["history"]} if rank == 0 else part)
         n_amul_cells, n_amul_faces = sub.n_cells, sub.n_faces + sum(len(i.face_cells) for i in sub.interfaces)
         # supplement (not `value`): the same solver with the per-GPU work held at the N = 1 size (weak scaling;
         # at 8 GPUs this is the 80 M-cell box of BASELINE config 5), so that the latency-bound strong-scaling number

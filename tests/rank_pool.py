@@ -89,9 +89,12 @@ def _collect():
 
 
 class RankPool:
-    def __init__(self, world, persistent=True):
+    def __init__(self, world, persistent=True, caller_rank0=False, timeout=600.0):
         # The ranks meet through a FileStore (no rendezvous port that is found free here and bound a moment later -- round 5's
         # EADDRINUSE, 2 of 58 pools).  gloo's own pair sockets can still fail to bind on a busy box: start again instead of failing the test.
+        # caller_rank0: rank 0 is THIS process (one process fewer with the GPU open), ranks 1 .. world-1 are started; its collectives
+        # give up after `timeout` seconds, so a rank that dies cannot hold the caller forever.
+        self.caller_rank0, self.timeout = caller_rank0, timeout
         for attempt in range(4):
             try:
                 self._start(world, persistent)
@@ -106,38 +109,72 @@ class RankPool:
         os.close(fd); os.unlink(store)                 # (the FileStore creates it; the name only has to be unique)
         self.store = store
         self.world, self.procs, self.conns = world, [], []
-        for r in range(world):
+        self.ranks = list(range(1 if self.caller_rank0 else 0, world))     # the ranks of the started processes, in procs / conns order
+        self.joined = False
+        for r in self.ranks:
             a, b = ctx.Pipe()
             p = ctx.Process(target=_rank_main, args=(r, world, store, b, persistent), daemon=True)
             p.start()
             b.close()
             self.procs.append(p); self.conns.append(a)
         try:
+            if self.caller_rank0:
+                self._join_caller()
             self._gather(180.0, "ready")
         except BaseException:
-            self._unlink_store()           # (kill() ran inside _gather; a rank that died before it could be killed leaves the file)
+            self.kill()           # (kill() ran inside _gather; a rank that died before it could be killed leaves the file)
             raise
 
-    def _gather(self, timeout, want):
+    def _join_caller(self):
+        import datetime
+        import torch.distributed as dist
+        dist.init_process_group("gloo", init_method=f"file://{self.store}", rank=0, world_size=self.world,
+                                timeout=datetime.timedelta(seconds=self.timeout))
+        self.joined = True
+
+    def _run_caller(self, module, fn, args):
+        """the job's rank 0 in this process, with the environment of a rank process (restored afterwards); its traceback or None"""
+        saved = dict(os.environ)
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ.pop("MASTER_PORT", None)
+        try:
+            for p in (ROOT, HERE):
+                if p not in sys.path:
+                    sys.path.insert(0, p)
+            getattr(importlib.import_module(module), fn)(0, self.world, *args)
+            _collect()
+            return None
+        except BaseException:
+            return traceback.format_exc()
+        finally:
+            for k in [k for k in os.environ if k not in saved]:
+                del os.environ[k]
+            for k, v in saved.items():
+                if os.environ.get(k) != v:
+                    os.environ[k] = v
+
+    def _gather(self, timeout, want, errors=None):
         deadline = time.monotonic() + timeout
-        errors, pending = [], set(range(self.world))
+        errors, pending = list(errors or []), set(range(len(self.conns)))
+        if errors:
+            deadline = time.monotonic() + 15.0
         while pending:
-            for r in sorted(pending):
-                c = self.conns[r]
+            for i in sorted(pending):
+                r, c = self.ranks[i], self.conns[i]
                 try:
                     if c.poll(0.05):
                         kind, payload = c.recv()
-                        pending.discard(r)
+                        pending.discard(i)
                         if kind != want:
                             errors.append(f"--- rank {r} ---\n{payload}")
                             deadline = min(deadline, time.monotonic() + 15.0)    # the others may be waiting for this rank: do not wait long
                 except (EOFError, OSError):
-                    pending.discard(r)
-                    errors.append(f"--- rank {r} ---\nprocess died (exit code {self.procs[r].exitcode})")
+                    pending.discard(i)
+                    errors.append(f"--- rank {r} ---\nprocess died (exit code {self.procs[i].exitcode})")
                     deadline = min(deadline, time.monotonic() + 15.0)
             if pending and time.monotonic() > deadline:
                 if not errors:
-                    errors.append(f"ranks {sorted(pending)} did not answer within {timeout:.0f} s")
+                    errors.append(f"ranks {[self.ranks[i] for i in sorted(pending)]} did not answer within {timeout:.0f} s")
                 break
         if errors:
             self.kill()
@@ -146,7 +183,8 @@ class RankPool:
     def run(self, module, fn, *args, timeout=600.0):
         for c in self.conns:
             c.send((module, fn, args))
-        self._gather(timeout, "ok")
+        err = self._run_caller(module, fn, args) if self.caller_rank0 else None
+        self._gather(timeout, "ok", [f"--- rank 0 (this process) ---\n{err}"] if err else None)
 
     def alive(self):
         return bool(self.procs) and all(p.is_alive() for p in self.procs)
@@ -170,6 +208,13 @@ class RankPool:
         for c in self.conns:
             c.close()
         self.procs, self.conns = [], []
+        if getattr(self, "joined", False):
+            import torch.distributed as dist
+            try:
+                dist.destroy_process_group()
+            except Exception:
+                pass
+            self.joined = False
         self._unlink_store()
 
     def _unlink_store(self):
@@ -177,6 +222,19 @@ class RankPool:
             os.unlink(getattr(self, "store", ""))
         except OSError:
             pass
+
+
+# GPU machines that are shared between users may cap the processes that have a device open at the same time: MAX_GPU_PROCESSES
+# (default 6; MI_TEST_MAX_GPU_PROCESSES where the cap differs).  The test process has the GPU open as well, so a job of exactly that
+# many ranks runs its rank 0 in the test process (run_ranks); a test with more ranks than the cap skips before it starts any.
+MAX_GPU_PROCESSES = int(os.environ.get("MI_TEST_MAX_GPU_PROCESSES", "6"))
+
+
+def skip_unless_gpu_processes(world):
+    """pytest.skip unless `world` ranks fit under MAX_GPU_PROCESSES (the test process counts as rank 0 where it has to)"""
+    import pytest
+    if world > MAX_GPU_PROCESSES:
+        pytest.skip(f"needs {world} rank processes with the GPU open at once, at most {MAX_GPU_PROCESSES} allowed here")
 
 
 def run_ranks(world, module, fn, *args, timeout=600.0, fresh=False):
@@ -190,8 +248,11 @@ def run_ranks(world, module, fn, *args, timeout=600.0, fresh=False):
     # the host transport (a hipMemcpy per callback) get slower and slower in a process that has served jobs before -- measured on the
     # GPU box: a 4-rank cyclicAMI case 127 s re-used against ~12 s fresh, a 2-rank one 79 s against 3.3 s
     # (profiles/r05_c_multiprocess_test_timing.md); the cause was not found within the round's GPU time.
-    if os.environ.get("MI_TEST_POOL", "0") != "1":
-        pool = RankPool(world, persistent=False)
+    caller = world + 1 > MAX_GPU_PROCESSES          # the test process + world ranks would exceed the cap: rank 0 runs here
+    if caller:
+        close_all()
+    if os.environ.get("MI_TEST_POOL", "0") != "1" or caller:
+        pool = RankPool(world, persistent=False, caller_rank0=caller, timeout=timeout)
         try:
             pool.run(module, fn, *args, timeout=timeout)
         finally:

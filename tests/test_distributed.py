@@ -10,7 +10,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from rank_pool import run_ranks
+from rank_pool import run_ranks, skip_unless_gpu_processes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -144,6 +144,7 @@ def test_distributed_pcg_real_engine_ranks_share_one_gpu(pkg, orc, tmp_path, par
     here (duplicate GPU), so all ranks must agree to fall back to the torch.distributed loop."""
     dims = (20, 16, 12)
     world = parts[0] * parts[1] * parts[2]
+    skip_unless_gpu_processes(world)
     run_ranks(world, "test_distributed", "_gpu_body", parts, dims, dict(kw), str(tmp_path), driver)
     case = pkg.synthetic.box_case(*dims)
     okw = dict(tolerance=kw["tolerance"], maxIter=kw["max_iter"], minIter=kw.get("min_iter", 0))
@@ -502,6 +503,7 @@ def test_cyclic_ami_side_split_over_ranks(pkg, orc, tmp_path, name, world, peer)
     derives each piece's coarse faces from what its own transport patch receives.  Amul bit-exact against the multi-domain oracle
     (whose split-side path equals the single-domain AMI bit for bit on every row off the processor cuts: tests/test_ami.py); Krylov
     solvers and GAMG against it to 1e-10, over the external transport and over peer windows."""
+    skip_unless_gpu_processes(world)
     spec = _windows_spec(NATIVE_SPECS[name]) if peer else NATIVE_SPECS[name]
     run_ranks(world, "test_distributed", "_native_body", spec, str(tmp_path), False, peer)
     _check_native(pkg, orc, spec, world, str(tmp_path))
@@ -514,6 +516,7 @@ def test_persistent_distributed_pcg_between_processes(pkg, orc, tmp_path, name, 
     hipIpc) run the whole PCG iteration -- halo stores into the neighbours' windows, flags, both all-reduces through the
     replicated window slots, rank-order sums -- inside their persistent cooperative kernels, which share the one GPU of this
     box (MI_PERSIST_GRID workgroups each).  Iteration counts, histories (1e-10) and solutions against the multi-domain oracle."""
+    skip_unless_gpu_processes(world)
     spec = NATIVE_SPECS[name]
     run_ranks(world, "test_distributed", "_native_body", spec, str(tmp_path), False, f"persist:{grid}")
     _check_native(pkg, orc, spec, world, str(tmp_path))

@@ -24,7 +24,7 @@ import torch.multiprocessing as mp
 
 import full_size_ref as fs
 from full_size_ref import check_bits, check_solution
-from rank_pool import run_ranks
+from rank_pool import run_ranks, skip_unless_gpu_processes
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -177,6 +177,7 @@ def _config5_recorded(rec):
 
 
 def test_config5_eight_engine_ranks_80M_cells(pkg, orc, tmp_path):
+    skip_unless_gpu_processes(8)
     rec = None if fs.live_oracle() else fs.Records()
     if _ram_gb() < (48 if rec else 96):
         pytest.skip("needs 48 GB of host memory for eight engine processes (96 with the live oracle's eight 10 M-cell domains next to them)")

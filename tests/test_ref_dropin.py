@@ -1,6 +1,6 @@
 """GPU (-m gpu): the REFERENCE's own solver classes running on top of the engine.
 
-tests/ref_dropin/ compiles the reference's PCG.C, PBiCG.C, PBiCGStab.C and smoothSolver.C from where
+oracle/Makefile `dropin` (sources in tests/ref_dropin/, output in oracle/_ref/) compiles the reference's PCG.C, PBiCG.C, PBiCGStab.C and smoothSolver.C from where
 they lie (in the build container, where /root/reference exists) with hipcc against a shim whose
 device primitives are this repo's C ABI: lduMatrix::Amul/Tmul/residual -> mi_amul/mi_tmul/mi_residual,
 preconditioner::precondition[T] -> mi_precondition, smoother::smooth -> mi_jacobi_smooth,
@@ -19,13 +19,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB = os.path.join(HERE, "ref_dropin", "_ref", "libref_dropin.so")
+LIB = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_dropin.so")
 
 
 @pytest.fixture(scope="module")
 def dropin(pkg):
     if not os.path.exists(LIB):
-        pytest.skip("tests/ref_dropin/_ref/libref_dropin.so not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/libref_dropin.so not built (needs /root/reference at build time)")
     pkg.engine.lib()  # torch's HIP runtime and the engine first
     lib = C.CDLL(LIB)
     lib.ref_dropin_solve.restype = None

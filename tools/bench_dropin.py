@@ -10,7 +10,7 @@ import __graft_entry__ as graft
 graft.build()
 pkg = graft.load_package()
 syn, eng = pkg.synthetic, pkg.engine
-lib = C.CDLL(os.path.join(ROOT, "tests", "ref_dropin", "_ref", "libref_dropin.so"))
+lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_dropin.so"))
 lib.ref_dropin_solve.restype = None; lib.ref_dropin_gamg_solve.restype = None; lib.ref_dropin_solve_order.restype = None
 dims = [int(v) for v in os.environ.get("DIMS", "216,216,216").split(",")]
 case = syn.box_case(*dims)
