@@ -530,6 +530,48 @@ typedef struct mi_fvm_terms {
 } mi_fvm_terms;
 int mi_fvm_assemble(mi_addr_t addr, const mi_fvm_terms *terms, double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev,
                     double *const *source_out_dev, double *sum_mag_off_diag_out_dev_or_null);
+/* ---- explicit correction of the corrected convection schemes linearUpwind and LUST ----
+ * `Gauss linearUpwind grad(U)` / `Gauss LUST grad(U)`: gaussConvectionScheme<Type>::fvmDiv (src/finiteVolume/finiteVolume/convectionSchemes/
+ * gaussConvectionScheme/gaussConvectionScheme.C:109-112) adds   fvm += fvc::surfaceIntegrate(faceFlux*correction(vf))   to the div matrix,
+ * i.e. source -= V*ivf (fvMatrix.C:1819-1826).  correction(vf) of linearUpwind (src/finiteVolume/interpolation/surfaceInterpolation/schemes/
+ * linearUpwind/linearUpwind.C:33-62,65-199), on internal face f and component r:
+ *     c = faceFlux[f] > 0 ? owner[f] : neighbour[f]     (STRICT; the weights use pos(), >= 0: at a zero flux the weight takes the owner,
+ *                                                         the correction the neighbour)
+ *     corr = (Cf[f] - C[c]) & grad_r[c]                 (the differences first; the dot product fma(dz, gz, fma(dx, gx, dy*gy)) as every
+ *                                                         face pass of this engine; for a vector field vector & tensor component r)
+ *     t_f  = faceFlux[f] * (scale*corr)                 (two stored fields, two roundings; scale 1: linearUpwind, 0.25: LUST, LUST.H:120-126)
+ * and the weights: upwind (mi_upwind_weights / div_weights_dev NULL) for linearUpwind (linearUpwind.H:53-55), mi_lust_weights for LUST.
+ * mi_div_correction: the correction's inputs; grad_dev[3*r + k] = d(vf_r)/dx_k, the cell gradient (e.g. mi_gauss_grad) of component r.
+ * mi_linear_upwind_correction: t_f for n_rhs <= 4 components in ONE face pass over the internal faces (the reference: the correction
+ *   field, [the scale,] the product, per component).  Then mi_surface_integrate(t, NULL, ivf) + the coupled patches' faces (below,
+ *   mi_patch_add) + mi_vec_div(ivf, V) + mi_vec_submul(V, ivf, source) is the unfused sequence (without coupled patches
+ *   mi_surface_integrate(t, V, ivf) divides in the same pass).
+ * mi_patch_linear_upwind_correction: the same on one COUPLED patch (processor, cyclic; linearUpwind.C:49-62, the functor the reference
+ *   runs): faceFlux > 0: (pCf - C[o]) & grad[o]; otherwise ((pCf - C[o]) - pd) & nbrGrad[i], o = faceCells[i], pd = patch().delta(),
+ *   nbrGrad = the gradient's patchNeighbourField (mi_matrix_patch_neighbour_field per component).  Arrays: patch_cf / c / patch_delta 3
+ *   component arrays each, grad / nbr_grad 3*n_rhs, out n_rhs.  Non-coupled patches contribute nothing.
+ * mi_lust_weights: LUST.H:104-110, w = 0.75*cd_weights + 0.25*pos(faceFlux): three field operations, no fma.
+ * mi_fvm_assemble_corrected: mi_fvm_assemble with that correction in the div term, in the same row pass: each block forms t_f of its own
+ *   faces once and stages it in LDS; per cell ivf_r = (sum_own t - sum_nei t)/V (mi_surface_integrate's order), and
+ *   source[r] = ((ddt source or 0.0) - V*ivf_r) before the su terms -- bit for bit the unfused sequence above placed after the ddt term.
+ *   corr NULL: mi_fvm_assemble.  Refused (MI_ERR_ARG) without a convection term, and when the addressing has coupled patches
+ *   (mi_addr_n_ext > 0): the reference adds those faces before the division by V, which only the unfused path reproduces.
+ * Every call here rejects missing arrays, unaligned face fields and outputs that alias an input.                                   */
+typedef struct mi_div_correction {
+    double scale;                                  /* 1: linearUpwind, 0.25: LUST */
+    const double *cf_dev[3];                       /* face centres Cf of the internal faces, component arrays (16-byte aligned) */
+    const double *c_dev[3];                        /* cell centres C */
+    const double *grad_dev[12];                    /* the first 3*n_rhs: grad_dev[3*r + k] = d(vf_r)/dx_k */
+} mi_div_correction;
+int mi_linear_upwind_correction(mi_addr_t addr, const mi_div_correction *corr, int32_t n_rhs, const double *face_flux_dev,
+                                double *const *out_dev);
+int mi_patch_linear_upwind_correction(mi_patch_t patch, double scale, int32_t n_rhs, const double *patch_flux_dev,
+                                      const double *const *patch_cf_dev, const double *const *c_dev, const double *const *patch_delta_dev,
+                                      const double *const *grad_dev, const double *const *nbr_grad_dev, double *const *out_dev);
+int mi_lust_weights(mi_ctx_t ctx, int64_t n_faces, const double *cd_weights_dev, const double *face_flux_dev, double *weights_out_dev);
+int mi_fvm_assemble_corrected(mi_addr_t addr, const mi_fvm_terms *terms, const mi_div_correction *corr_or_null,
+                              double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev,
+                              double *const *source_out_dev, double *sum_mag_off_diag_out_dev_or_null);
 /* fvMatrix::setReference (src/finiteVolume/fvMatrices/fvMatrix/fvMatrix.C:964-981; icoFoam.C:89, simpleFoam/pEqn.H:21: the pressure level of a
  * closed domain): source[celli] += diag[celli]*value; diag[celli] += diag[celli].  celli < 0 (the rank does not hold the cell): no-op. */
 int mi_fvm_set_reference(mi_addr_t addr, int32_t celli, double value, double *diag_dev, double *source_dev);

@@ -151,6 +151,28 @@ __global__ __launch_bounds__(BS) void k_row_pass(const RowPassArgs a)
 }
 
 
+// ---- explicit correction of the corrected convection schemes (linearUpwind, LUST) ---------------------------------------------
+// gaussConvectionScheme<Type>::fvmDiv adds fvc::surfaceIntegrate(faceFlux*correction(vf)) to the matrix (gaussConvectionScheme.C:109-112).
+// linearUpwind<Type>::correction (linearUpwind.C:33-47, functor on the internal faces): the cell is the owner when faceFlux > 0 -- STRICT,
+// while the weights use pos() (>= 0) -- the neighbour otherwise, and corr = (Cf - C[cell]) & grad[cell], the three differences formed
+// first.  For a vector field `vector & tensor` gives component r as the same scalar expression on component r's gradient; the dot
+// product is contracted as flux_face's and k_limited_linear_weights' are.  LUST scales it (0.25*correction, a stored field: rounded,
+// LUST.H:120-126); the face term faceFlux*(scale*corr) is a second stored field.  Gradients: grad[3*r + k] = d(vf_r)/dx_k.
+struct CorrIn {
+    const double *cf[3], *cc[3], *grad[12];
+    double scale;
+};
+__device__ __forceinline__ double lu_dot(double dx, double dy, double dz, double gx, double gy, double gz) { return fma(dz, gz, fma(dx, gx, dy * gy)); }
+__device__ __forceinline__ void lu_face(const CorrIn& q, int nRhs, const int32_t* lo, const int32_t* up, const double* flux, int f, double t[4])
+{
+    const double fl = flux[f];
+    const int c = fl > 0 ? lo[f] : up[f];
+    const double dx = q.cf[0][f] - q.cc[0][c], dy = q.cf[1][f] - q.cc[1][c], dz = q.cf[2][f] - q.cc[2][c];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (r < nRhs) t[r] = fl * (q.scale * lu_dot(dx, dy, dz, q.grad[3 * r][c], q.grad[3 * r + 1][c], q.grad[3 * r + 2][c]));
+}
+
 // ---- fused matrix assembly: [fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- explicit terms] in ONE row pass ----------
 // (SURVEY 8f rank 1; fvMatrix::operator+= / -= / == on fvMatrix.C:1693-2030, lduMatrix::operator+= / -= on lduMatrixOperations.C:235-396.)
 // The reference forms every scheme's matrix with its own passes and temporaries and then combines them coefficient array by
@@ -171,8 +193,12 @@ struct AsmArgs {
     const double* psiOld[4]; double* sourceOut[4]; const double* su[16]; int suMinus[4];   // su[k * nRhs + r]
     double *diagOut, *sumMagOut;
 };
-template <bool DIV, bool LAP, int BS, bool R16>
-__global__ __launch_bounds__(BS) void k_row_assemble(const AsmArgs a)
+struct AsmCorrArgs : AsmArgs { const int32_t *lo, *up; CorrIn corr; };   // CORR: caller-order face addressing and the correction's inputs
+// CORR: each own face's t_r = faceFlux*(scale*corr_r) is formed once in the face pass and staged in LDS after lB / uB / uL; every cell
+// forms its n_rhs surfaceIntegrate row sums in mi_surface_integrate's order, ivf = sum/V, and subtracts the rounded V*ivf from the source
+// right after the ddt part (the div matrix's own source, fvMatrix.C:1819-1826), before the explicit terms
+template <bool DIV, bool LAP, int BS, bool R16, bool CORR = false>
+__global__ __launch_bounds__(BS) void k_row_assemble(const typename std::conditional<CORR, AsmCorrArgs, AsmArgs>::type a)
 {
     extern __shared__ __attribute__((aligned(16))) double rp_smem[];
     const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
@@ -186,6 +212,7 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const AsmArgs a)
     double* sLB = rp_smem;                               // DIV: lB, uB; LAP: uL
     double* sUB = rp_smem + a.cap;
     double* sUL = rp_smem + (DIV ? 2 : 0) * a.cap;
+    double* sT = rp_smem + ((DIV ? 2 : 0) + (LAP ? 1 : 0)) * a.cap;   // CORR: t_r at sT[r * cap + j]
     const bool mag = a.sumMagOut != nullptr;
     struct FaceC { double lB, uB, uL; };
     auto face = [&](int f) -> FaceC {
@@ -203,6 +230,13 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const AsmArgs a)
         a.upperOut[f0 + j] = upperF(r);
         if (staged) { if (DIV) { sLB[j] = r.lB; sUB[j] = r.uB; } if (LAP) sUL[j] = r.uL; }
     }
+    if constexpr (CORR) if (staged) {                    // a loop of its own: fewer pointers live at once (no SGPR spills)
+        for (int j = tid; j < nf; j += BS) {
+            double t[4]; lu_face(a.corr, a.nRhs, a.lo, a.up, a.flux, f0 + j, t);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) if (q < a.nRhs) sT[q * a.cap + j] = t[q];
+        }
+    }
     int nb = 0, ne = 0, ob = 0, oe = 0;
     const int escBase = R16 ? a.escStart[lb] : 0;
     if (live) {
@@ -216,6 +250,19 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const AsmArgs a)
         if (!R16) return a.losort[j];
         const unsigned e = a.losort16[j];
         return (e & 0x8000u) ? a.esc[escBase + (int)(e & 0x7FFFu)] : f0 + (int)e;
+    };
+    // CORR: a face's t_r from LDS when the block staged it, else recomputed from the inputs (the cut faces after the barrier)
+    double sumC[4] = {0.0, 0.0, 0.0, 0.0};
+    auto corr_add = [&](int f, bool own) {
+        if constexpr (CORR) {
+            double t[4];
+            if (staged && f >= f0) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) if (q < a.nRhs) t[q] = sT[q * a.cap + f - f0];
+            } else lu_face(a.corr, a.nRhs, a.lo, a.up, a.flux, f, t);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) if (q < a.nRhs) sumC[q] += own ? t[q] : -t[q];
+        }
     };
     // cut neighbour-side faces are recomputed from the schemes' inputs (same roundings) before the barrier
     const int cnt = ne - nb;
@@ -251,11 +298,18 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const AsmArgs a)
     if (a.sp) { const double t = V * a.sp[c]; d = a.spMinus ? d - t : d + t; }
     a.diagOut[c] = d;
     if (mag) a.sumMagOut[c] = sumM;
-    for (int r = 0; r < a.nRhs; ++r) {
+    auto source = [&](int r, double vIvf) {
         double s = a.ddt ? ((a.rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue)) * a.psiOld[r][c]) * V : 0.0;
+        if (CORR) s = s - vIvf;
         for (int k = 0; k < a.nSu; ++k) { const double t = V * a.su[k * a.nRhs + r][c]; s = a.suMinus[k] ? s + t : s - t; }
         a.sourceOut[r][c] = s;
-    }
+    };
+    if constexpr (CORR) {   // the surfaceIntegrate row sums after the matrix's: own faces ascending, then losort order (as mi_surface_integrate)
+        for (int j = ob; j < oe; ++j) corr_add(j, true);
+        for (int j = nb; j < ne; ++j) corr_add(nei_face(j), false);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if (r < a.nRhs) { const double ivf = sumC[r] / V; source(r, V * ivf); }
+    } else for (int r = 0; r < a.nRhs; ++r) source(r, 0.0);
 }
 
 // linear-type face interpolation (surfaceInterpolationScheme.C:337-352)
@@ -455,6 +509,51 @@ __global__ void k_limited_linear_weights(const int32_t* __restrict__ lo, const i
         if (limOut) limOut[f] = lim;
         w[f] = fma(lim, cdw[f], (1.0 - lim) * (fl >= 0 ? 1.0 : 0.0));
     }
+}
+// faceFlux*correction(vf) of linearUpwind / LUST on the internal faces for n_rhs <= 4 components in one sweep (the reference: the
+// gradient, the correction field, [the 0.25 scale,] the product -- per component): faceFlux and Cf read once, C and the gradients gathered
+// at the upwind cell; XCD-aware chunks as k_limited_linear_weights
+struct CorrOut { double* out[4]; };
+__global__ void k_linear_upwind_corr(const int32_t* __restrict__ lo, const int32_t* __restrict__ up, const double* __restrict__ flux,
+                                     const CorrIn q, const CorrOut o, int nRhs, int nf, int xcd)
+{
+    int f0, f1; block_chunk(nf, xcd, f0, f1);
+    for (int f = f0 + threadIdx.x; f < f1; f += blockDim.x) {
+        double t[4]; lu_face(q, nRhs, lo, up, flux, f, t);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if (r < nRhs) o.out[r][f] = t[r];
+    }
+}
+// the same on one COUPLED patch (linearUpwind.C:49-62, the functor the reference runs): flux > 0: (pCf - C[o]) & grad[o]; otherwise
+// ((pCf - C[o]) - pd) & gradNbr[i], pd = patch().delta(), gradNbr the gradient's patchNeighbourField
+struct PatchCorrIn {
+    const double *pcf[3], *cc[3], *pd[3], *grad[12], *nbr[12];
+    double scale;
+};
+__global__ void k_patch_linear_upwind_corr(const int32_t* __restrict__ faceCells, const double* __restrict__ pflux, const PatchCorrIn q,
+                                           const CorrOut o, int nRhs, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = faceCells[i];
+    const double fl = pflux[i];
+    const bool own = fl > 0;
+    double dx = q.pcf[0][i] - q.cc[0][c], dy = q.pcf[1][i] - q.cc[1][c], dz = q.pcf[2][i] - q.cc[2][c];
+    if (!own) { dx = dx - q.pd[0][i]; dy = dy - q.pd[1][i]; dz = dz - q.pd[2][i]; }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (r < nRhs) {
+            const double gx = own ? q.grad[3 * r][c] : q.nbr[3 * r][i], gy = own ? q.grad[3 * r + 1][c] : q.nbr[3 * r + 1][i],
+                         gz = own ? q.grad[3 * r + 2][c] : q.nbr[3 * r + 2][i];
+            o.out[r][i] = fl * (q.scale * lu_dot(dx, dy, dz, gx, gy, gz));
+        }
+}
+// LUST weights (LUST.H:104-110): 0.75*w_linear + 0.25*pos(faceFlux) -- three field operations, three roundings (no fma)
+__global__ __launch_bounds__(RB) void k_lust_weights(const double* __restrict__ cdw, const double* __restrict__ flux, double* __restrict__ w, int64_t n)
+{
+    chunk_loop(n, [&](int64_t i) { const double2 c = ld2(cdw, i), f = ld2(flux, i);
+                                   st2(w, i, make_double2(0.75 * c.x + 0.25 * (f.x >= 0 ? 1.0 : 0.0), 0.75 * c.y + 0.25 * (f.y >= 0 ? 1.0 : 0.0))); },
+        [&](int64_t i) { w[i] = 0.75 * cdw[i] + 0.25 * (flux[i] >= 0 ? 1.0 : 0.0); });
 }
 // fvc::grad, Gauss (gaussGrad.C:27-90): the row pass above with four staged face arrays (Sf x3 + ssf) and three
 // accumulators; ssf is read once for the three components; every term is one fma, like the oracle.
@@ -786,9 +885,104 @@ extern "C" int mi_fvm_div(mi_addr_t a, const double* weights_dev, const double* 
 }
 
 
+namespace {
+// the correction's inputs for n_rhs components; every output must differ from every one of them (faces and cells of other blocks read
+// them while this call writes)
+int corr_in(const char* who, const mi_div_correction* k, int nRhs, CorrIn& q, const double* const* outs, int nOuts)
+{
+    if (!k || nRhs < 1 || nRhs > 4) return fail(MI_ERR_ARG, std::string(who) + ": a correction needs 1 to 4 components");
+    q = CorrIn{};
+    q.scale = k->scale;
+    for (int d = 0; d < 3; ++d) { q.cf[d] = k->cf_dev[d]; q.cc[d] = k->c_dev[d]; }
+    for (int j = 0; j < 3 * nRhs; ++j) q.grad[j] = k->grad_dev[j];
+    const double* in[18];
+    int m = 0;
+    for (int d = 0; d < 3; ++d) { in[m++] = q.cf[d]; in[m++] = q.cc[d]; }
+    for (int j = 0; j < 3 * nRhs; ++j) in[m++] = q.grad[j];
+    for (int j = 0; j < m; ++j) if (!in[j]) return fail(MI_ERR_ARG, std::string(who) + ": correction arrays missing (Cf, C and 3 gradient components per right-hand side)");
+    for (int d = 0; d < 3; ++d) if (!al16(q.cf[d])) return fail(MI_ERR_ARG, std::string(who) + ": face fields must be 16-byte aligned");
+    for (int o = 0; o < nOuts; ++o)
+        for (int j = 0; j < m; ++j)
+            if (outs[o] && outs[o] == in[j]) return fail(MI_ERR_ARG, std::string(who) + ": an output must not alias a correction input");
+    return MI_OK;
+}
+} // namespace
+
+extern "C" int mi_linear_upwind_correction(mi_addr_t a, const mi_div_correction* corr, int32_t n_rhs, const double* face_flux_dev, double* const* out_dev)
+{
+    const char* who = "mi_linear_upwind_correction";
+    if (!a) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!face_flux_dev) return fail(MI_ERR_ARG, std::string(who) + ": the correction of a convection scheme needs its faceFlux");
+    if (!al16(face_flux_dev)) return fail(MI_ERR_ARG, std::string(who) + ": face fields must be 16-byte aligned");
+    if (!out_dev || n_rhs < 1 || n_rhs > 4) return fail(MI_ERR_ARG, std::string(who) + ": 1 to 4 outputs needed");
+    CorrOut o{};
+    for (int r = 0; r < n_rhs; ++r) {
+        o.out[r] = out_dev[r];
+        if (!o.out[r]) return fail(MI_ERR_ARG, std::string(who) + ": null output");
+        if (o.out[r] == face_flux_dev) return fail(MI_ERR_ARG, std::string(who) + ": an output must not alias faceFlux");
+        for (int s = 0; s < r; ++s) if (o.out[s] == o.out[r]) return fail(MI_ERR_ARG, std::string(who) + ": the outputs must differ");
+    }
+    CorrIn q;
+    MICHK(corr_in(who, corr, n_rhs, q, o.out, n_rhs));
+    HIPCHK(hipSetDevice(a->ctx->device));
+    MICHK(ensure_caller_tables(a));
+    if (a->L.nFaces == 0) return MI_OK;
+    k_linear_upwind_corr<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, face_flux_dev, q, o, n_rhs, a->L.nFaces,
+                                                                            a->ctx->xcdRows);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+
+extern "C" int mi_patch_linear_upwind_correction(mi_patch_t p, double scale, int32_t n_rhs, const double* patch_flux_dev, const double* const* patch_cf_dev,
+                                                 const double* const* c_dev, const double* const* patch_delta_dev, const double* const* grad_dev,
+                                                 const double* const* nbr_grad_dev, double* const* out_dev)
+{
+    const char* who = "mi_patch_linear_upwind_correction";
+    if (!p || n_rhs < 1 || n_rhs > 4) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (p->nFaces == 0) return MI_OK;
+    if (!patch_flux_dev || !patch_cf_dev || !c_dev || !patch_delta_dev || !grad_dev || !nbr_grad_dev || !out_dev)
+        return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    PatchCorrIn q{};
+    q.scale = scale;
+    const double* in[31];
+    int m = 0;
+    in[m++] = patch_flux_dev;
+    for (int d = 0; d < 3; ++d) { in[m++] = q.pcf[d] = patch_cf_dev[d]; in[m++] = q.cc[d] = c_dev[d]; in[m++] = q.pd[d] = patch_delta_dev[d]; }
+    for (int j = 0; j < 3 * n_rhs; ++j) { in[m++] = q.grad[j] = grad_dev[j]; in[m++] = q.nbr[j] = nbr_grad_dev[j]; }
+    for (int j = 0; j < m; ++j) if (!in[j]) return fail(MI_ERR_ARG, std::string(who) + ": input arrays missing");
+    CorrOut o{};
+    for (int r = 0; r < n_rhs; ++r) {
+        o.out[r] = out_dev[r];
+        if (!o.out[r]) return fail(MI_ERR_ARG, std::string(who) + ": null output");
+        for (int j = 0; j < m; ++j) if (o.out[r] == in[j]) return fail(MI_ERR_ARG, std::string(who) + ": an output must not alias an input");
+        for (int s = 0; s < r; ++s) if (o.out[s] == o.out[r]) return fail(MI_ERR_ARG, std::string(who) + ": the outputs must differ");
+    }
+    HIPCHK(hipSetDevice(p->ctx->device));
+    k_patch_linear_upwind_corr<<<(p->nFaces + 255) / 256, 256, 0, p->ctx->stream>>>(p->faceCells.p, patch_flux_dev, q, o, n_rhs, p->nFaces);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+
+extern "C" int mi_lust_weights(mi_ctx_t c, int64_t n_faces, const double* cd_weights_dev, const double* face_flux_dev, double* weights_out_dev)
+{
+    if (!c || n_faces < 0 || !cd_weights_dev || !face_flux_dev || !weights_out_dev) return fail(MI_ERR_ARG, "mi_lust_weights: bad argument");
+    if (!al16(cd_weights_dev) || !al16(face_flux_dev) || !al16(weights_out_dev)) return fail(MI_ERR_ARG, "mi_lust_weights: arrays must be 16-byte aligned");
+    if (n_faces == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    k_lust_weights<<<RG, RB, 0, c->stream>>>(cd_weights_dev, face_flux_dev, weights_out_dev, n_faces);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+
 // [fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- explicit terms] in one row pass (k_row_assemble)
 extern "C" int mi_fvm_assemble(mi_addr_t a, const mi_fvm_terms* t, double* lower_out_dev, double* upper_out_dev, double* diag_out_dev,
                                double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
+{
+    return mi_fvm_assemble_corrected(a, t, nullptr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+}
+// ... with the explicit correction of linearUpwind / LUST in the div term (CORR)
+extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
+                                         double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
 {
     if (!a || !t || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: bad argument");
     const bool DIV = t->div_flux_dev != nullptr, LAP = t->lap_delta_coeffs_dev != nullptr;
@@ -806,10 +1000,26 @@ extern "C" int mi_fvm_assemble(mi_addr_t a, const mi_fvm_terms* t, double* lower
         if (q && (q == upper_out_dev || q == lower_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_assemble: a coefficient output must not alias an input (cut faces are recomputed from the inputs)");
     }
     if (lower_out_dev && lower_out_dev == upper_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: lower_out and upper_out must differ");
+    const bool CORR = corr != nullptr;
+    if (CORR) {
+        const char* who = "mi_fvm_assemble_corrected";
+        if (!DIV) return fail(MI_ERR_ARG, std::string(who) + ": a convection correction without a convection term (div_flux_dev is NULL)");
+        if (a->L.nExt > 0)
+            return fail(MI_ERR_ARG, std::string(who) + ": the addressing has coupled patches, whose correction faces the reference adds before the "
+                        "division by V -- use the unfused path (mi_linear_upwind_correction + mi_patch_linear_upwind_correction + mi_surface_integrate + "
+                        "mi_patch_add + mi_vec_div + mi_vec_submul)");
+        if (t->n_rhs < 1 || !t->vol_dev) return fail(MI_ERR_ARG, std::string(who) + ": the correction needs n_rhs >= 1 right-hand sides and the cell volumes");
+    }
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
+    AsmCorrArgs ra{};
+    if (CORR) {
+        const double* outs[8] = {lower_out_dev, upper_out_dev, diag_out_dev, sum_mag_off_diag_out_dev};
+        for (int r = 0; r < t->n_rhs; ++r) outs[4 + r] = source_out_dev[r];
+        MICHK(corr_in("mi_fvm_assemble_corrected", corr, t->n_rhs, ra.corr, outs, 4 + t->n_rhs));
+        ra.lo = a->lowerAddr.p; ra.up = a->upperAddr.p;
+    }
     if (a->L.nCells == 0) return MI_OK;
-    AsmArgs ra{};
     ra.flux = t->div_flux_dev; ra.w = t->div_weights_dev; ra.delta = t->lap_delta_coeffs_dev; ra.gam = t->lap_gamma_magsf_dev;
     ra.lowerOut = lower_out_dev; ra.upperOut = upper_out_dev; ra.diagOut = diag_out_dev; ra.sumMagOut = sum_mag_off_diag_out_dev;
     ra.ddt = t->ddt ? 1 : 0; ra.rdt = t->r_delta_t; ra.rhoValue = t->rho_value; ra.rho = t->rho_dev; ra.rhoOld = t->rho_old_dev; ra.vol = t->vol_dev;
@@ -827,22 +1037,25 @@ extern "C" int mi_fvm_assemble(mi_addr_t a, const mi_fvm_terms* t, double* lower
     ra.row16 = a->row16.p; ra.losort16 = a->losort16.p; ra.esc = a->rowEsc.p; ra.escStart = a->rowEscStart.p;
     const mi_addr_s::RowPlan& rp = a->rowPlan[0];
     ra.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
-    const int arrays = (DIV ? 2 : 0) + (LAP ? 1 : 0);
+    const int arrays = (DIV ? 2 : 0) + (LAP ? 1 : 0) + (CORR ? t->n_rhs : 0);
     ra.n = a->L.nCells; ra.cap = row_cap(rp, arrays); ra.xcd = a->ctx->xcdRows;
     const size_t lds = (size_t)arrays * ra.cap * sizeof(double);
     const bool r16 = a->row16.n > 0;
-#define MI_ASM_LAUNCH(D, L)                                                                                                      \
+    const AsmArgs& rb = ra;                        // the uncorrected kernels take the base arguments only
+#define MI_ASM_LAUNCH(D, L, K, ARGS)                                                                                             \
     do {                                                                                                                           \
-        if (r16) { if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, true>, ra, lds);                           \
-                   if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, true>, ra, lds);                           \
-                   return row_launch(a, rp, k_row_assemble<D, L, 1024, true>, ra, lds); }                                          \
-        if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, false>, ra, lds);                                     \
-        if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, false>, ra, lds);                                     \
-        return row_launch(a, rp, k_row_assemble<D, L, 1024, false>, ra, lds);                                                      \
+        if (r16) { if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, true, K>, ARGS, lds);                     \
+                   if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, true, K>, ARGS, lds);                     \
+                   return row_launch(a, rp, k_row_assemble<D, L, 1024, true, K>, ARGS, lds); }                                    \
+        if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, false, K>, ARGS, lds);                               \
+        if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, false, K>, ARGS, lds);                               \
+        return row_launch(a, rp, k_row_assemble<D, L, 1024, false, K>, ARGS, lds);                                                \
     } while (0)
-    if (DIV && LAP) MI_ASM_LAUNCH(true, true);
-    if (DIV) MI_ASM_LAUNCH(true, false);
-    MI_ASM_LAUNCH(false, true);
+    if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, ra);
+    if (CORR) MI_ASM_LAUNCH(true, false, true, ra);
+    if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, rb);
+    if (DIV) MI_ASM_LAUNCH(true, false, false, rb);
+    MI_ASM_LAUNCH(false, true, false, rb);
 #undef MI_ASM_LAUNCH
 }
 

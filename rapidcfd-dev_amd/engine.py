@@ -69,6 +69,7 @@ SYMBOLS = [
     "mi_patch_create", "mi_patch_destroy", "mi_patch_add", "mi_patch_add_product", "mi_patch_flux", "mi_relax",
     "mi_sngrad_correction_flux", "mi_patch_sngrad_correction_flux", "mi_patch_internal_field", "mi_vec_submul",
     "mi_comm_create_external", "mi_addr_create_ordered", "mi_addr_tile_starts", "mi_addr_is_ordered",
+    "mi_linear_upwind_correction", "mi_patch_linear_upwind_correction", "mi_lust_weights", "mi_fvm_assemble_corrected",
 ]
 
 
@@ -893,6 +894,14 @@ class Patch:
         """fvPatchField::patchInternalField: out[i] = psi[faceCells[i]]"""
         _chk(lib().mi_patch_internal_field(self.h, _ptr(psi), _ptr(out)))
 
+    def linear_upwind_correction(self, patch_flux, patch_cf, c, patch_delta, grad, nbr_grad, out, scale=1.0):
+        """patchFlux*correction(vf) of linearUpwind (scale 1) / LUST (scale 0.25) on a COUPLED patch (linearUpwind.C:49-62): grad and nbr_grad one
+        [gx, gy, gz] per component (cell gradients / their patchNeighbourField), out one patch array per component"""
+        n = len(out)
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_patch_linear_upwind_correction(self.h, C.c_double(scale), C.c_int32(n), _ptr(patch_flux), pv(patch_cf), pv(c), pv(patch_delta),
+                                                     pv([g for gr in grad for g in gr]), pv([g for gr in nbr_grad for g in gr]), pv(out)))
+
     def sngrad_correction_flux(self, corr_vecs, weights, grad, nbr_grad, gamma_magsf, out):
         """non-orthogonal correction flux on a COUPLED patch (gaussLaplacianSchemes.C:64-90 + surfaceInterpolationScheme.C:360-365)"""
         _chk(lib().mi_patch_sngrad_correction_flux(self.h, _ptr(corr_vecs[0]), _ptr(corr_vecs[1]), _ptr(corr_vecs[2]), _ptr(weights), _ptr(grad[0]),
@@ -911,6 +920,26 @@ class FvmTerms(C.Structure):
                 ("vol_dev", C.c_void_p), ("div_flux_dev", C.c_void_p), ("div_weights_dev", C.c_void_p), ("lap_delta_coeffs_dev", C.c_void_p),
                 ("lap_gamma_magsf_dev", C.c_void_p), ("sp_dev", C.c_void_p), ("sp_sign", C.c_double), ("n_rhs", C.c_int32),
                 ("psi_old_dev", C.POINTER(C.c_void_p)), ("n_su", C.c_int32), ("su_dev", C.POINTER(C.c_void_p)), ("su_sign", C.POINTER(C.c_double))]
+
+
+class DivCorrection(C.Structure):
+    """mi_div_correction (include/mi_ldu.h)"""
+    _fields_ = [("scale", C.c_double), ("cf_dev", C.c_void_p * 3), ("c_dev", C.c_void_p * 3), ("grad_dev", C.c_void_p * 12)]
+
+
+def div_correction(cf, c, grad, scale=1.0) -> DivCorrection:
+    """linearUpwind (scale 1) / LUST (scale 0.25) correction inputs: face centres cf and cell centres c as [x, y, z], grad one [gx, gy, gz]
+    per component"""
+    k = DivCorrection()
+    k.scale = float(scale)
+    if len(grad) > 4:
+        raise MiError("at most 4 components")
+    for d in range(3):
+        k.cf_dev[d] = _ptr(cf[d]).value; k.c_dev[d] = _ptr(c[d]).value
+    for r, g in enumerate(grad):
+        for d in range(3):
+            k.grad_dev[3 * r + d] = _ptr(g[d]).value
+    return k
 
 
 class Assembly:
@@ -982,6 +1011,17 @@ class Assembly:
         _chk(lib().mi_sngrad_correction_flux(self.addr.h, _ptr(corr_vecs[0]), _ptr(corr_vecs[1]), _ptr(corr_vecs[2]), _ptr(weights), _ptr(grad[0]),
                                              _ptr(grad[1]), _ptr(grad[2]), _ptr(gamma_magsf), _ptr(out)))
 
+    def linear_upwind_correction(self, face_flux, cf, c, grad, out, scale=1.0):
+        """faceFlux*correction(vf) of linearUpwind (scale 1) / LUST (scale 0.25) on the internal faces, one face pass for len(out) <= 4 components
+        (linearUpwind.C:33-47); grad one [gx, gy, gz] per component"""
+        k = div_correction(cf, c, grad, scale)
+        o = (C.c_void_p * max(len(out), 1))(*[_ptr(x) for x in out])
+        _chk(lib().mi_linear_upwind_correction(self.addr.h, C.byref(k), C.c_int32(len(out)), _ptr(face_flux), o))
+
+    def lust_weights(self, cd_weights, face_flux, w_out):
+        """LUST weights 0.75*cd_weights + 0.25*pos(faceFlux) (LUST.H:104-110)"""
+        _chk(lib().mi_lust_weights(self.addr.ctx.h, C.c_int64(face_flux.numel()), _ptr(cd_weights), _ptr(face_flux), _ptr(w_out)))
+
     def submul(self, x, y, inout):
         """inout -= x*y (source -= V*div(...))"""
         _chk(lib().mi_vec_submul(self.addr.ctx.h, C.c_int64(inout.numel()), _ptr(x), _ptr(y), _ptr(inout)))
@@ -993,7 +1033,9 @@ class Assembly:
         """[fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- su] in one row pass (mi_fvm_assemble).
         ddt = dict(r_delta_t=, vol=, psi_old=[...], rho=None | tensor, rho_old=None | tensor, rho_value=1.0); div = dict(flux=, weights=None (upwind) | tensor);
         laplacian = dict(delta_coeffs=, gamma_magsf=); sp = (field, sign); su = [(sign, [field per rhs]), ...]; vol is taken from ddt or the `vol` key of sp / su
-        through ddt["vol"] (pass ddt=dict(vol=...) with r_delta_t omitted for no time derivative)."""
+        through ddt["vol"] (pass ddt=dict(vol=...) with r_delta_t omitted for no time derivative).
+        div["correction"] = dict(scale=1.0 | 0.25, cf=[x, y, z], c=[x, y, z], grad=[[gx, gy, gz] per rhs]): the explicit correction of linearUpwind / LUST
+        in the same pass (mi_fvm_assemble_corrected)."""
         t = FvmTerms()
         n_rhs = len(sources_out)
         keep = []
@@ -1016,7 +1058,12 @@ class Assembly:
             sg = (C.c_double * len(su))(*[float(sign) for sign, _ in su]); keep.append(sg)
             t.su_dev = C.cast(sd, C.POINTER(C.c_void_p)); t.su_sign = C.cast(sg, C.POINTER(C.c_double))
         so = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in sources_out])
-        _chk(lib().mi_fvm_assemble(self.addr.h, C.byref(t), _ptr(lower_out), _ptr(upper_out), _ptr(diag_out), so, _ptr(sum_mag_out)))
+        corr = (div or {}).get("correction")
+        if corr is None:
+            _chk(lib().mi_fvm_assemble(self.addr.h, C.byref(t), _ptr(lower_out), _ptr(upper_out), _ptr(diag_out), so, _ptr(sum_mag_out)))
+        else:
+            k = div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))
+            _chk(lib().mi_fvm_assemble_corrected(self.addr.h, C.byref(t), C.byref(k), _ptr(lower_out), _ptr(upper_out), _ptr(diag_out), so, _ptr(sum_mag_out)))
 
     def fvc_div(self, face_flux, weights, vf, vol, face_out, div_out):
         """fvc::div(faceFlux, vf) (gaussConvectionScheme.C:117-140); weights None: upwind"""

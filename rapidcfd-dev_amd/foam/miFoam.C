@@ -756,6 +756,60 @@ void fvm::assemble(fvScalarMatrix& M, scalar rDeltaT, scalar rho, const scalargp
     double* so[1] = {M.source().data()};
     miCheck(mi_fvm_assemble(M.lduAddr().handle(), &t, faceFlux ? M.lower().data() : nullptr, M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble");
 }
+namespace {
+mi_div_correction divCorrection(const linearUpwindCorrection& corr, std::size_t nRhs)
+{
+    if (!corr.Cf || !corr.C || corr.grad.size() != nRhs) FatalErrorIn("linearUpwind::correction", "one gradient per component of the field is needed");
+    mi_div_correction k{};
+    k.scale = corr.scale;
+    for (int d = 0; d < 3; ++d) { k.cf_dev[d] = corr.Cf->component(d).data(); k.c_dev[d] = corr.C->component(d).data(); }
+    for (std::size_t r = 0; r < nRhs; ++r) {
+        if (!corr.grad[r]) FatalErrorIn("linearUpwind::correction", "null gradient");
+        for (int d = 0; d < 3; ++d) k.grad_dev[3 * r + d] = corr.grad[r]->component(d).data();
+    }
+    return k;
+}
+}
+void fvm::assemble(fvScalarMatrix& M, scalar rDeltaT, scalar rho, const scalargpuField& V, const scalargpuField& psiOld, const scalargpuField& faceFlux,
+                   const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const linearUpwindCorrection& corr,
+                   const scalargpuField* su)
+{
+    mi_fvm_terms t{};
+    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
+    t.div_flux_dev = faceFlux.data(); t.div_weights_dev = weights ? weights->data() : nullptr;
+    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
+    const double* po[1] = {psiOld.data()}; t.n_rhs = 1; t.psi_old_dev = po;
+    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
+    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
+    double* so[1] = {M.source().data()};
+    const mi_div_correction k = divCorrection(corr, 1);
+    miCheck(mi_fvm_assemble_corrected(M.lduAddr().handle(), &t, &k, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble (corrected convection)");
+}
+void fvm::assemble(fvVectorMatrix& M, scalar rDeltaT, scalar rho, const scalargpuField& V, const vectorgpuField& psiOld, const scalargpuField& faceFlux,
+                   const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const linearUpwindCorrection& corr)
+{
+    mi_fvm_terms t{};
+    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
+    t.div_flux_dev = faceFlux.data(); t.div_weights_dev = weights ? weights->data() : nullptr;
+    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
+    const double* po[3] = {psiOld.component(0).data(), psiOld.component(1).data(), psiOld.component(2).data()};
+    t.n_rhs = 3; t.psi_old_dev = po;
+    double* so[3] = {M.source().component(0).data(), M.source().component(1).data(), M.source().component(2).data()};
+    const mi_div_correction k = divCorrection(corr, 3);
+    miCheck(mi_fvm_assemble_corrected(M.lduAddr().handle(), &t, &k, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble (corrected convection)");
+}
+void fvc::linearUpwindCorrectionFlux(scalargpuField& out, const lduAddressing& a, const scalargpuField& faceFlux, const linearUpwindCorrection& corr)
+{
+    const mi_div_correction k = divCorrection(corr, 1);
+    double* o[1] = {out.data()};
+    miCheck(mi_linear_upwind_correction(a.handle(), &k, 1, faceFlux.data(), o), "linearUpwind::correction");
+}
+void fvc::linearUpwindCorrectionFlux(vectorgpuField& out, const lduAddressing& a, const scalargpuField& faceFlux, const linearUpwindCorrection& corr)
+{
+    const mi_div_correction k = divCorrection(corr, 3);
+    double* o[3] = {out.component(0).data(), out.component(1).data(), out.component(2).data()};
+    miCheck(mi_linear_upwind_correction(a.handle(), &k, 3, faceFlux.data(), o), "linearUpwind::correction");
+}
 void fvc::grad(vectorgpuField& g, const lduAddressing& a, const vectorgpuField& Sf, const scalargpuField& ssf, const scalargpuField& V)
 {
     miCheck(mi_gauss_grad(a.handle(), Sf.component(0).data(), Sf.component(1).data(), Sf.component(2).data(), ssf.data(), V.data(),
@@ -822,6 +876,10 @@ void fvPatchCells::patchInternalField(const scalargpuField& psi, scalargpuField&
 void upwindWeights(scalargpuField& w, const scalargpuField& faceFlux)
 {
     miCheck(mi_upwind_weights(miEngine::New().ctx, faceFlux.size(), faceFlux.data(), w.data()), "upwind::weights");
+}
+void LUSTWeights(scalargpuField& w, const scalargpuField& cdWeights, const scalargpuField& faceFlux)
+{
+    miCheck(mi_lust_weights(miEngine::New().ctx, faceFlux.size(), cdWeights.data(), faceFlux.data(), w.data()), "LUST::weights");
 }
 void limitedLinearWeights(scalargpuField& w, const lduAddressing& a, scalar k, const scalargpuField& cdWeights, const scalargpuField& faceFlux,
                           const scalargpuField& vf, const vectorgpuField& gradVf, const vectorgpuField& C)
