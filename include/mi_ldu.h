@@ -98,12 +98,14 @@ int mi_ctx_set_option(mi_ctx_t ctx, const char *name, int32_t value);
 /* which solver paths ran on this context (diagnostics, tests): launches of the persistent PCG kernel -- one per batch of
  * iterations -- on plain (MI_STAT_PERSIST_PCG) / communicator-attached (MI_STAT_PERSIST_DPCG) matrices; runs of the grid
  * barrier litmus that gates that kernel (MI_STAT_BARRIER_LITMUS); V-cycles of a decomposed case replayed as a hipGraph
- * (MI_STAT_GAMG_GRAPH_ATTACHED); launches of the fused residual / direction kernel of PCG (MI_STAT_PCG_FUSED_RP) */
+ * (MI_STAT_GAMG_GRAPH_ATTACHED); launches of the fused residual / direction kernel of PCG (MI_STAT_PCG_FUSED_RP); batches of
+ * PCG iterations that mi_pcg_solve replayed from a hipGraph (MI_STAT_PCG_GRAPH) */
 #define MI_STAT_PERSIST_PCG 0
 #define MI_STAT_PERSIST_DPCG 1
 #define MI_STAT_BARRIER_LITMUS 2
 #define MI_STAT_GAMG_GRAPH_ATTACHED 3
 #define MI_STAT_PCG_FUSED_RP 4
+#define MI_STAT_PCG_GRAPH 5
 int mi_ctx_stat(mi_ctx_t ctx, int32_t which, int64_t *out);
 const char *mi_last_error(void);
 /* 1 if a usable gfx950 device is visible to this process, else 0 */

@@ -98,7 +98,7 @@ struct mi_ctx_s {
     int pcgFuseTest = 0; // tests ("pcg_fuse_test"): workgroups of the fused launch that leave its barrier at once (pcg_fused.inc)
     int pcgFuseRP = -1; // MI_PCG_FUSE_RP: residual update + next direction update as one launch (pcg_fused.inc); 0 never, -1 (default) once the device has been asked
     int pcgPersist = 1; // MI_PCG_PERSIST: 0 never, 1 (default) whenever the tiles fit the CUs' registers (persist.inc)
-    int64_t stats[5] = {0, 0, 0, 0, 0}; // mi_ctx_stat
+    int64_t stats[6] = {0, 0, 0, 0, 0, 0}; // mi_ctx_stat
     int persistGrid = 0; // MI_PERSIST_GRID: workgroups of the persistent kernel (0: one per CU); MI_PERSIST_SHARED=1 lets ranks that share a device use it -- tests only: their grids must fit the device TOGETHER
     int persistShared = 0;
     int persistCoop = -1; // cooperative launch of the persistent kernel possible on this device AND its barrier litmus clean (-1: not asked yet)
@@ -329,10 +329,11 @@ extern "C" int mi_ctx_set_option(mi_ctx_t c, const char* name, int32_t value)
 }
 
 // which solver paths ran on this context: 0 / 1 = launches of the persistent PCG kernel (one per batch of iterations) on plain /
-// attached matrices, 2 = grid-barrier litmus runs (persist.inc), 3 = V-cycles of a decomposed case replayed as a hipGraph
+// attached matrices, 2 = grid-barrier litmus runs (persist.inc), 3 = V-cycles of a decomposed case replayed as a hipGraph,
+// 4 = launches of the fused residual / direction kernel of PCG (pcg_fused.inc), 5 = PCG batches replayed as a hipGraph (mi_pcg_solve)
 extern "C" int mi_ctx_stat(mi_ctx_t c, int32_t which, int64_t* out)
 {
-    if (!c || !out || which < 0 || which >= 5) return fail(MI_ERR_ARG, "mi_ctx_stat: bad argument");
+    if (!c || !out || which < 0 || which >= 6) return fail(MI_ERR_ARG, "mi_ctx_stat: bad argument");
     *out = c->stats[which];
     return MI_OK;
 }
@@ -1757,7 +1758,10 @@ extern "C" int mi_pcg_iterate_sampled(mi_matrix_t m, int32_t n_iters, int32_t ev
     if (!m || !m->pcgActive || n_iters < 0 || event_stride < 0) return fail(MI_ERR_STATE, "mi_pcg_iterate: no active PCG session");
     HIPCHK(hipSetDevice(m->addr->ctx->device));
     const int stride = amul_ms_sum ? (event_stride > 0 ? event_stride : 1) : 0;
-    if (!amul_ms_sum && pcg_persist_usable(m, m->pcgPrecond)) { // small matrix: the whole batch is ONE cooperative launch (persist.inc)
+    // small matrix: the whole batch is ONE cooperative launch (persist.inc) -- unless the previous batch ended in the fused launch,
+    // which has formed pA of the next iteration already: the persistent kernel would form it a second time.  Such a batch stays
+    // with pcg_enqueue, which starts from that pA.
+    if (!amul_ms_sum && !m->pcgPReady && pcg_persist_usable(m, m->pcgPrecond)) {
         const int rcP = pcg_persist_enqueue(m, n_iters, m->pcgPrecond);
         if (rcP != MI_ERR_UNSUPPORTED) {
             MICHK(rcP);
@@ -1834,6 +1838,7 @@ extern "C" int mi_pcg_solve(mi_matrix_t m, double* psi, const double* source, co
         }
         while (!c->hostState->done && m->pcgIt <= limit) {
             HIPCHK(hipGraphLaunch(m->pcgGraph, c->stream));
+            c->stats[5] += 1;   // mi_ctx_stat(5): PCG batches replayed as a hipGraph
             m->pcgIt += batch;
             MICHK(fetch_state(c));
         }

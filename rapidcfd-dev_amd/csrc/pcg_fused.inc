@@ -136,6 +136,7 @@ __device__ __forceinline__ void fused_close(PcgState* st, int it, double alpha, 
     st->finalResidual = q.res;
     if (it + 1 < histLen) hist[it + 1] = q.res;
     st->nIterations = it + 1;
+    st->it = it + 1;              // (k_pcg_final advances it too: the persistent kernel starts a later batch from it)
     st->converged = q.conv;
     if (q.cont) st->wArA[(it + 1) & 1] = q.wArA; else st->done = 1;
     st->pApplyItP1 = st->rItP1;   // psi is complete here: nothing is owed to a later pass (pcg_flush)
@@ -263,9 +264,13 @@ __global__ __launch_bounds__(RB) void k_pcg_fused_finish(FusedArgs a)
     __shared__ double red[RB / 64];
     const unsigned int b = blockIdx.x, tid = threadIdx.x;
     unsigned int* pend = a.bar + FUSED_PEND_AT;
+    PcgState* __restrict__ st = a.st;
+    // k_pcg_final's note, which the fused launch replaces: the k_pcg_update_p of this iteration (if one ran) has added the psi
+    // term iteration it - 1 owed.  fused_close records the same when the launch completes; this covers the launches that return
+    // at once (solve done, singular direction), where a deferred term added by that k_pcg_update_p would otherwise be flushed twice
+    if (b == 0 && tid == 0 && st->rItP1 >= a.it) st->pApplyItP1 = a.it;
     const bool mine = pend[b] != 0u, closing = b == 0 && pend[RG] != 0u;
     if (!mine && !closing) return;
-    PcgState* __restrict__ st = a.st;
     const int it = a.it;
     const double wApA = sum_partials(a.partial2, red);
     const double wArAold = st->wArA[it & 1];

@@ -235,7 +235,8 @@ class Context:
 
     def stat(self, which: int) -> int:
         """mi_ctx_stat: 0 = launches of the persistent PCG kernel on plain matrices, 1 = on communicator-attached ones,
-        2 = grid-barrier litmus runs, 3 = V-cycles of a decomposed case replayed as a hipGraph, 4 = launches of the fused residual / direction kernel of PCG"""
+        2 = grid-barrier litmus runs, 3 = V-cycles of a decomposed case replayed as a hipGraph, 4 = launches of the fused residual / direction kernel of PCG,
+        5 = batches of PCG iterations replayed as a hipGraph (mi_pcg_solve)"""
         v = C.c_int64(0)
         _chk(lib().mi_ctx_stat(self.h, C.c_int32(which), C.byref(v)))
         return int(v.value)
