@@ -466,6 +466,40 @@ int mi_limited_linear_weights(mi_addr_t addr, double k, const double *cd_weights
                               const double *phi_dev, const double *gradx_dev, const double *grady_dev,
                               const double *gradz_dev, const double *cx_dev, const double *cy_dev,
                               const double *cz_dev, double *weights_out_dev, double *limiter_out_dev_or_null);
+/* ---- the TVD/NVD limited schemes and their V and bounded forms (finiteVolume/Make/files:253-273, limitedSchemes/<scheme>/<scheme>.C) ----
+ * mi_limiter_parse: host only, no GPU.  Accepts exactly the names the reference registers -- limitedLinear vanLeer MUSCL Minmod SuperBee
+ *   UMIST vanAlbada OSPRE QUICK limitedCubic Gamma SFCD, each with a "V" form (limitedLinearV ... SFCDV: NVDVTVDV.H), and the bounded
+ *   forms of Limited.H / Limited01.H: limitedLimitedLinear k lo hi, limitedLinear01 k, limitedVanLeer lo hi, vanLeer01, limitedMUSCL lo hi,
+ *   MUSCL01, limitedLimitedCubic k lo hi, limitedCubic01 k, limitedGamma k lo hi, Gamma01 k.  limitedLinear, limitedCubic and Gamma read
+ *   k first.  Refused (MI_ERR_ARG): any other name, a missing or extra coefficient, k outside [0, 1] (limitedLinear.H:67-73,
+ *   limitedCubic.H:67-73, Gamma.H:66-72), lower > upper (Limited.H:54-64), a bounded V form.
+ * mi_limited_weights: LimitedSchemeCalcLimiterFunctor (LimitedScheme.C:32-57,88-136) + limitedSurfaceInterpolationSchemeWeightsFunctor
+ *   (limitedSurfaceInterpolationScheme.C:155-161) on the internal faces in ONE face pass: d = C[N] - C[P], the limiter of lim->kind over
+ *   NVDTVD.H (scalar: phi_dev[0], grad_dev[0..2]) or NVDVTVDV.H (vector_form: phi_dev[0..2], grad_dev[3*j + k] = d(phi_j)/dx_k), the
+ *   LimitedLimiter bounds (Limited.H:105-118; a zero flux is in neither branch), then w = lim*cdw + (1 - lim)*pos(faceFlux).  Contraction:
+ *   DESIGN 3.5b.  limiter_out may be NULL.  A vector field under a non-V scheme is limited on magSqr(U) (LimitFuncs.C:39-54): the caller
+ *   forms that scalar and its gradient.  mi_limited_linear_weights stays the limitedLinear-only call.
+ * mi_patch_limited_weights: the same on one COUPLED patch (LimitedScheme.C:145-195): phiP, gradcP through the patch's faceCells, phiN,
+ *   gradcN the patchNeighbourField (mi_matrix_patch_neighbour_field per component), d = patch().delta() (patch_delta_dev, 3 component
+ *   arrays), the patch's own CD weights and flux.  Non-coupled patches take limiter 1 (LimitedScheme.C:197-200): their weights ARE the
+ *   patch CD weights, no call is needed.
+ * Both refuse (MI_ERR_ARG, nothing launched): an invalid mi_limiter, missing arrays, unaligned face fields, outputs that alias an input. */
+enum { MI_LIM_LIMITED_LINEAR, MI_LIM_VAN_LEER, MI_LIM_MUSCL, MI_LIM_MINMOD, MI_LIM_SUPERBEE, MI_LIM_UMIST,
+       MI_LIM_VAN_ALBADA, MI_LIM_OSPRE, MI_LIM_QUICK, MI_LIM_LIMITED_CUBIC, MI_LIM_GAMMA, MI_LIM_SFCD };
+typedef struct mi_limiter {
+    int32_t kind;          /* MI_LIM_* */
+    int32_t vector_form;   /* 0: NVDTVD over a scalar (1 phi, 3 grad arrays); 1: NVDVTVDV, the "...V" schemes (3 phi, 9 grad: grad[3*j+k] = d(phi_j)/dx_k) */
+    int32_t bounded;       /* Limited.H: limitedX lo hi / X01; scalar form only */
+    double k, lower, upper;
+} mi_limiter;
+int mi_limiter_parse(const char *scheme, mi_limiter *out);
+int mi_limited_weights(mi_addr_t addr, const mi_limiter *lim, const double *cd_weights_dev, const double *face_flux_dev,
+                       const double *const *phi_dev, const double *const *grad_dev, const double *const *c_dev,
+                       double *weights_out_dev, double *limiter_out_dev_or_null);
+int mi_patch_limited_weights(mi_patch_t patch, const mi_limiter *lim, const double *patch_cd_weights_dev, const double *patch_flux_dev,
+                             const double *const *phi_dev, const double *const *nbr_phi_dev, const double *const *grad_dev,
+                             const double *const *nbr_grad_dev, const double *const *patch_delta_dev,
+                             double *weights_out_dev, double *limiter_out_dev_or_null);
 int mi_gauss_grad(mi_addr_t addr, const double *sfx_dev, const double *sfy_dev, const double *sfz_dev,
                   const double *ssf_dev, const double *vol_dev_or_null, double *gx_dev, double *gy_dev, double *gz_dev);
 int mi_vec_axpby(mi_ctx_t ctx, int64_t n, double a, const double *x_dev, double b, const double *y_dev, double *out_dev);

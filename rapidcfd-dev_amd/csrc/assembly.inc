@@ -555,6 +555,136 @@ __global__ __launch_bounds__(RB) void k_lust_weights(const double* __restrict__ 
                                    st2(w, i, make_double2(0.75 * c.x + 0.25 * (f.x >= 0 ? 1.0 : 0.0), 0.75 * c.y + 0.25 * (f.y >= 0 ? 1.0 : 0.0))); },
         [&](int64_t i) { w[i] = 0.75 * cdw[i] + 0.25 * (flux[i] >= 0 ? 1.0 : 0.0); });
 }
+// ---- the TVD/NVD limited schemes (limitedSchemes/*, DESIGN 3.5b) ------------------------------------------------------------------
+// LimitedSchemeCalcLimiterFunctor (LimitedScheme.C:41-55) for every limiter of the family over NVDTVD (a scalar) or NVDVTVDV (the "V"
+// schemes: a vector, its gradient grad[3*j + k] = d(phi_j)/dx_k), with the LimitedLimiter bounds (Limited.H:93-133, scalar form only),
+// then the weights lim*cdw + (1 - lim)*pos(flux) (limitedSurfaceInterpolationScheme.C:155-161).  One contraction rule throughout: a dot
+// product is lu_dot, of two products in a sum the first is fused; max / min are the reference's (s1 > s2) ? s1 : s2 / (s1 < s2) ? s1 : s2.
+enum { LIM_LINEAR, LIM_VANLEER, LIM_MUSCL, LIM_MINMOD, LIM_SUPERBEE, LIM_UMIST, LIM_VANALBADA, LIM_OSPRE, LIM_QUICK, LIM_CUBIC, LIM_GAMMA, LIM_SFCD, LIM_N };
+struct LimCoef { double twoByk, gammaK, lower, upper; int bounded; };
+__device__ __forceinline__ double rmax(double a, double b) { return a > b ? a : b; }
+__device__ __forceinline__ double rmin(double a, double b) { return a < b ? a : b; }
+__device__ __forceinline__ double rsign(double s) { return s >= 0 ? 1.0 : -1.0; }
+__device__ __forceinline__ double rstab(double s) { return s >= 0 ? s + 1e-15 : s - 1e-15; }   // stabilise(s, SMALL)
+// phi(p, j): component j at the owner side (p) or the neighbour side; grad(p, c): gradient component c there.  Only what KIND reads
+// is loaded: the scalar form gathers the gradient at the upwind cell only, limitedCubic at both.
+template <int KIND, bool VEC, class PHI, class GRAD>
+__device__ __forceinline__ double lim_face(const LimCoef& L, double cdw, double fl, const PHI& phi, const GRAD& grad, double dx, double dy, double dz)
+{
+    constexpr int M = VEC ? 3 : 1;
+    double pP[M], pN[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) { pP[j] = phi(true, j); pN[j] = phi(false, j); }
+    if (!VEC && L.bounded && ((fl > 0 && (pP[0] < L.lower || pN[0] > L.upper)) || (fl < 0 && (pN[0] < L.lower || pP[0] > L.upper)))) return 0.0;
+    const bool up = fl > 0;                                       // strict (NVDTVD.H:110)
+    auto dg = [&](bool p, int j) { return lu_dot(dx, dy, dz, grad(p, 3 * j), grad(p, 3 * j + 1), grad(p, 3 * j + 2)); };   // d & grad(phi_j)
+    double gfV[3] = {0.0, 0.0, 0.0}, gradf, gradcf;
+    if (VEC) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) gfV[j] = pN[j] - pP[j];
+        gradf = lu_dot(gfV[0], gfV[1], gfV[2], gfV[0], gfV[1], gfV[2]);
+        gradcf = lu_dot(gfV[0], gfV[1], gfV[2], dg(up, 0), dg(up, 1), dg(up, 2));
+    } else {
+        gradf = pN[0] - pP[0];
+        gradcf = dg(up, 0);
+    }
+    if constexpr (KIND == LIM_GAMMA || KIND == LIM_SFCD) {         // NVDTVD.H:85-92 phict
+        const double phict = fabs(gradf) >= 1000 * fabs(gradcf) ? 1 - 0.5 * 1000 * rsign(gradcf) * rsign(gradf) : 1 - 0.5 * gradf / gradcf;
+        if constexpr (KIND == LIM_GAMMA) return rmin(rmax(phict / L.gammaK, 0.0), 1.0);   // Gamma.H:96
+        const double lp = rmin(rmax(phict, 0.0), 0.5);                                      // SFCD.H:81-82
+        return lp / (1 - lp);
+    }
+    if constexpr (KIND == LIM_QUICK) {                            // QUICK.H:80-99, QUICKV.H:80-101
+        const double q = 1 - cdw;
+        double phiCD, phiU;
+        if (VEC) {
+            double w[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) w[j] = fma(cdw, pP[j], q * pN[j]);
+            phiCD = lu_dot(gfV[0], gfV[1], gfV[2], w[0], w[1], w[2]);
+            phiU = up ? lu_dot(gfV[0], gfV[1], gfV[2], pP[0], pP[1], pP[2]) : lu_dot(gfV[0], gfV[1], gfV[2], pN[0], pN[1], pN[2]);
+        } else {
+            phiCD = fma(cdw, pP[0], q * pN[0]);
+            phiU = up ? pP[0] : pN[0];
+        }
+        const double phif = 0.5 * fma(up ? q : -cdw, gradcf, phiCD + phiU);   // gradcf: (gradfV &) (d & gradc[upwind])
+        return rmax(rmin((phif - phiU) / rstab(phiCD - phiU), 2.0), 0.0);
+    }
+    const double r = fabs(gradcf) >= 1000 * fabs(gradf) ? 2 * 1000 * rsign(gradcf) * rsign(gradf) - 1 : fma(2.0, gradcf / gradf, -1.0);   // NVDTVD.H:119-126
+    if constexpr (KIND == LIM_LINEAR) return rmax(rmin(L.twoByk * r, 1.0), 0.0);                      // limitedLinear.H:96
+    if constexpr (KIND == LIM_VANLEER) return (r + fabs(r)) / (1 + fabs(r));                          // vanLeer.H:81
+    if constexpr (KIND == LIM_MUSCL) return rmax(rmin(rmin(2 * r, 0.5 * r + 0.5), 2.0), 0.0);         // MUSCL.H:80
+    if constexpr (KIND == LIM_MINMOD) return rmax(rmin(r, 1.0), 0.0);                                 // Minmod.H:80
+    if constexpr (KIND == LIM_SUPERBEE) return rmax(rmax(rmin(2 * r, 1.0), rmin(r, 2.0)), 0.0);       // SuperBee.H:81
+    if constexpr (KIND == LIM_UMIST) return rmax(rmin(rmin(rmin(2 * r, fma(0.75, r, 0.25)), 0.25 * r + 0.75), 2.0), 0.0);   // UMIST.H:80
+    if constexpr (KIND == LIM_VANALBADA) return r * (r + 1) / fma(r, r, 1.0);                         // vanAlbada.H:81
+    if constexpr (KIND == LIM_OSPRE) { const double rr = r * (r + 1); return 1.5 * rr / (rr + 1); }   // OSPRE.H:81-82
+    if constexpr (KIND == LIM_CUBIC) {                            // limitedCubic.H:91-127, limitedCubicV.H:91-124
+        const double twor = L.twoByk * r, q = 1 - cdw;
+        double phif, phiCD, fU;
+        if (VEC) {
+            double fV[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) fV[j] = fma(cdw, pP[j], (1.0 - cdw) * pN[j]);
+            const double fP = lu_dot(fV[0], fV[1], fV[2], pP[0], pP[1], pP[2]), fN = lu_dot(fV[0], fV[1], fV[2], pN[0], pN[1], pN[2]);
+            const double tN = lu_dot(fV[0], fV[1], fV[2], dg(false, 0), dg(false, 1), dg(false, 2));
+            const double tP = lu_dot(fV[0], fV[1], fV[2], dg(true, 0), dg(true, 1), dg(true, 2));
+            fU = up ? fP : fN;
+            phif = fma(cdw, fP - 0.25 * tN, q * (fN + 0.25 * tP));
+            phiCD = fma(cdw, fP, q * fN);
+        } else {
+            fU = up ? pP[0] : pN[0];
+            phif = fma(cdw, pP[0] - 0.25 * dg(false, 0), q * (pN[0] + 0.25 * dg(true, 0)));
+            phiCD = fma(cdw, pP[0], q * pN[0]);
+        }
+        const double cubic = (phif - fU) / rstab(phiCD - fU);
+        return rmax(rmin(rmin(twor, cubic), 2.0), 0.0);
+    }
+    return 0.0;
+}
+struct LimArgs {
+    const int32_t *lo, *up;
+    const double *cdw, *flux, *phi[3], *grad[9], *cc[3];
+    double *w, *limOut;
+    LimCoef k;
+    int nf, xcd;
+};
+// the internal faces: XCD-aware chunks as k_limited_linear_weights; cdw and flux streamed, phi / grad / C gathered; d = C[N] - C[P]
+template <int KIND, bool VEC>
+__global__ void k_limited_weights(const LimArgs a)
+{
+    int f0, f1; block_chunk(a.nf, a.xcd, f0, f1);
+    for (int f = f0 + threadIdx.x; f < f1; f += blockDim.x) {
+        const int P = a.lo[f], N = a.up[f];
+        const double fl = a.flux[f], cdw = a.cdw[f];
+        const double dx = a.cc[0][N] - a.cc[0][P], dy = a.cc[1][N] - a.cc[1][P], dz = a.cc[2][N] - a.cc[2][P];
+        const double lim = lim_face<KIND, VEC>(a.k, cdw, fl, [&](bool p, int j) { return a.phi[j][p ? P : N]; },
+                                               [&](bool p, int c) { return a.grad[c][p ? P : N]; }, dx, dy, dz);
+        if (a.limOut) a.limOut[f] = lim;
+        a.w[f] = fma(lim, cdw, (1.0 - lim) * (fl >= 0 ? 1.0 : 0.0));
+    }
+}
+struct PatchLimArgs {
+    const int32_t* fc;
+    const double *cdw, *flux, *phi[3], *nphi[3], *grad[9], *ngrad[9], *pd[3];
+    double *w, *limOut;
+    LimCoef k;
+    int n;
+};
+// one COUPLED patch (LimitedScheme.C:145-195): phiP / gradcP through faceCells, phiN / gradcN the caller's patchNeighbourField,
+// d = pd - (0,0,0) = pd
+template <int KIND, bool VEC>
+__global__ void k_patch_limited_weights(const PatchLimArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int o = a.fc[i];
+    const double fl = a.flux[i], cdw = a.cdw[i];
+    const double lim = lim_face<KIND, VEC>(a.k, cdw, fl, [&](bool p, int j) { return p ? a.phi[j][o] : a.nphi[j][i]; },
+                                           [&](bool p, int c) { return p ? a.grad[c][o] : a.ngrad[c][i]; }, a.pd[0][i], a.pd[1][i], a.pd[2][i]);
+    if (a.limOut) a.limOut[i] = lim;
+    a.w[i] = fma(lim, cdw, (1.0 - lim) * (fl >= 0 ? 1.0 : 0.0));
+}
 // fvc::grad, Gauss (gaussGrad.C:27-90): the row pass above with four staged face arrays (Sf x3 + ssf) and three
 // accumulators; ssf is read once for the three components; every term is one fma, like the oracle.
 struct GradArgs {
@@ -1401,6 +1531,163 @@ extern "C" int mi_limited_linear_weights(mi_addr_t a, double k, const double* cd
     const double twoByk = 2.0 / (k > 1e-15 ? k : 1e-15);
     k_limited_linear_weights<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, twoByk, cd_weights_dev, face_flux_dev,
         phi_dev, gradx_dev, grady_dev, gradz_dev, cx_dev, cy_dev, cz_dev, weights_out_dev, limiter_out_dev_or_null, a->L.nFaces, a->ctx->xcdRows);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+// ---- the limited schemes: parse (host only) and the two face passes -------------------------------------------------------------
+namespace {
+struct LimName { const char* name; int kind, vec, bounded, hasK; double lower, upper; };   // bounded 1: "lo hi" read; 2: Limited01 (0, 1)
+// the names the reference registers (finiteVolume/Make/files:253-273 and the make* macros of limitedSchemes/*/*.C)
+const LimName kLimNames[] = {
+    {"limitedLinear", MI_LIM_LIMITED_LINEAR, 0, 0, 1, 0, 0}, {"limitedLinearV", MI_LIM_LIMITED_LINEAR, 1, 0, 1, 0, 0},
+    {"limitedLimitedLinear", MI_LIM_LIMITED_LINEAR, 0, 1, 1, 0, 0}, {"limitedLinear01", MI_LIM_LIMITED_LINEAR, 0, 2, 1, 0, 1},
+    {"vanLeer", MI_LIM_VAN_LEER, 0, 0, 0, 0, 0}, {"vanLeerV", MI_LIM_VAN_LEER, 1, 0, 0, 0, 0},
+    {"limitedVanLeer", MI_LIM_VAN_LEER, 0, 1, 0, 0, 0}, {"vanLeer01", MI_LIM_VAN_LEER, 0, 2, 0, 0, 1},
+    {"MUSCL", MI_LIM_MUSCL, 0, 0, 0, 0, 0}, {"MUSCLV", MI_LIM_MUSCL, 1, 0, 0, 0, 0},
+    {"limitedMUSCL", MI_LIM_MUSCL, 0, 1, 0, 0, 0}, {"MUSCL01", MI_LIM_MUSCL, 0, 2, 0, 0, 1},
+    {"Minmod", MI_LIM_MINMOD, 0, 0, 0, 0, 0}, {"MinmodV", MI_LIM_MINMOD, 1, 0, 0, 0, 0},
+    {"SuperBee", MI_LIM_SUPERBEE, 0, 0, 0, 0, 0}, {"SuperBeeV", MI_LIM_SUPERBEE, 1, 0, 0, 0, 0},
+    {"UMIST", MI_LIM_UMIST, 0, 0, 0, 0, 0}, {"UMISTV", MI_LIM_UMIST, 1, 0, 0, 0, 0},
+    {"vanAlbada", MI_LIM_VAN_ALBADA, 0, 0, 0, 0, 0}, {"vanAlbadaV", MI_LIM_VAN_ALBADA, 1, 0, 0, 0, 0},
+    {"OSPRE", MI_LIM_OSPRE, 0, 0, 0, 0, 0}, {"OSPREV", MI_LIM_OSPRE, 1, 0, 0, 0, 0},
+    {"QUICK", MI_LIM_QUICK, 0, 0, 0, 0, 0}, {"QUICKV", MI_LIM_QUICK, 1, 0, 0, 0, 0},
+    {"limitedCubic", MI_LIM_LIMITED_CUBIC, 0, 0, 1, 0, 0}, {"limitedCubicV", MI_LIM_LIMITED_CUBIC, 1, 0, 1, 0, 0},
+    {"limitedLimitedCubic", MI_LIM_LIMITED_CUBIC, 0, 1, 1, 0, 0}, {"limitedCubic01", MI_LIM_LIMITED_CUBIC, 0, 2, 1, 0, 1},
+    {"Gamma", MI_LIM_GAMMA, 0, 0, 1, 0, 0}, {"GammaV", MI_LIM_GAMMA, 1, 0, 1, 0, 0},
+    {"limitedGamma", MI_LIM_GAMMA, 0, 1, 1, 0, 0}, {"Gamma01", MI_LIM_GAMMA, 0, 2, 1, 0, 1},
+    {"SFCD", MI_LIM_SFCD, 0, 0, 0, 0, 0}, {"SFCDV", MI_LIM_SFCD, 1, 0, 0, 0, 0},
+};
+bool lim_has_k(int kind) { return kind == MI_LIM_LIMITED_LINEAR || kind == MI_LIM_LIMITED_CUBIC || kind == MI_LIM_GAMMA; }
+// the constructors' checks (limitedLinear.H:67-73, limitedCubic.H:67-73, Gamma.H:66-72, Limited.H:54-64) on a caller-filled mi_limiter
+int lim_check(const char* who, const mi_limiter* l, LimCoef& c)
+{
+    if (!l || l->kind < 0 || l->kind >= LIM_N || (l->vector_form != 0 && l->vector_form != 1) || (l->bounded != 0 && l->bounded != 1))
+        return fail(MI_ERR_ARG, std::string(who) + ": invalid mi_limiter");
+    if (lim_has_k(l->kind) && !(l->k >= 0 && l->k <= 1)) return fail(MI_ERR_ARG, std::string(who) + ": coefficient k should be >= 0 and <= 1");
+    if (l->bounded && l->vector_form) return fail(MI_ERR_ARG, std::string(who) + ": the bounded (Limited) form exists for scalar fields only");
+    if (l->bounded && !(l->lower <= l->upper)) return fail(MI_ERR_ARG, std::string(who) + ": lower bound is higher than the upper bound");
+    c = LimCoef{};
+    c.twoByk = 2.0 / (l->k > 1e-15 ? l->k : 1e-15);                          // 2.0/max(k, SMALL)
+    c.gammaK = l->k / 2.0 > 1e-15 ? l->k / 2.0 : 1e-15;                      // Gamma.H:76 max(k/2, SMALL)
+    c.lower = l->lower; c.upper = l->upper; c.bounded = l->bounded;
+    return MI_OK;
+}
+#define MI_LIM_CASES(KERNEL, ARGS)                                                                                                       \
+    template <int KIND, bool VEC> void launch_##KERNEL(dim3 g, dim3 b, hipStream_t s, const ARGS& a) { KERNEL<KIND, VEC><<<g, b, 0, s>>>(a); } \
+    void dispatch_##KERNEL(int kind, bool vec, dim3 g, dim3 b, hipStream_t s, const ARGS& a)                                             \
+    {                                                                                                                                    \
+        typedef void (*F)(dim3, dim3, hipStream_t, const ARGS&);                                                                         \
+        static const F tab[2][LIM_N] = {                                                                                                 \
+            {launch_##KERNEL<0, false>, launch_##KERNEL<1, false>, launch_##KERNEL<2, false>, launch_##KERNEL<3, false>,                 \
+             launch_##KERNEL<4, false>, launch_##KERNEL<5, false>, launch_##KERNEL<6, false>, launch_##KERNEL<7, false>,                 \
+             launch_##KERNEL<8, false>, launch_##KERNEL<9, false>, launch_##KERNEL<10, false>, launch_##KERNEL<11, false>},              \
+            {launch_##KERNEL<0, true>, launch_##KERNEL<1, true>, launch_##KERNEL<2, true>, launch_##KERNEL<3, true>,                     \
+             launch_##KERNEL<4, true>, launch_##KERNEL<5, true>, launch_##KERNEL<6, true>, launch_##KERNEL<7, true>,                     \
+             launch_##KERNEL<8, true>, launch_##KERNEL<9, true>, launch_##KERNEL<10, true>, launch_##KERNEL<11, true>}};                \
+        tab[vec ? 1 : 0][kind](g, b, s, a);                                                                                              \
+    }
+MI_LIM_CASES(k_limited_weights, LimArgs)
+MI_LIM_CASES(k_patch_limited_weights, PatchLimArgs)
+#undef MI_LIM_CASES
+// every output must differ from every input (other faces read the inputs while the pass writes) and from the other output
+int lim_outputs(const char* who, const double* const* in, int m, double* w, double* limOut)
+{
+    for (int j = 0; j < m; ++j) if (!in[j]) return fail(MI_ERR_ARG, std::string(who) + ": input arrays missing");
+    if (!w) return fail(MI_ERR_ARG, std::string(who) + ": the weights output is missing");
+    if (w == limOut) return fail(MI_ERR_ARG, std::string(who) + ": weights_out and limiter_out must differ");
+    for (int j = 0; j < m; ++j)
+        if (in[j] == w || (limOut && in[j] == limOut)) return fail(MI_ERR_ARG, std::string(who) + ": an output must not alias an input");
+    return MI_OK;
+}
+} // namespace
+
+extern "C" int mi_limiter_parse(const char* scheme, mi_limiter* out)
+{
+    if (!scheme || !out) return fail(MI_ERR_ARG, "mi_limiter_parse: bad argument");
+    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
+    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
+    for (const char* c = scheme; *c;) {
+        while (*c && sp(*c)) ++c;
+        const char* b = c;
+        while (*c && !sp(*c)) ++c;
+        if (c > b) tok.emplace_back(b, c);
+    }
+    if (tok.empty()) return fail(MI_ERR_ARG, "mi_limiter_parse: empty scheme");
+    const std::string& name = tok[0];
+    const LimName* e = nullptr;
+    for (const LimName& x : kLimNames) if (name == x.name) e = &x;
+    if (!e) return fail(MI_ERR_ARG, "mi_limiter_parse: unknown limited scheme '" + name + "'");
+    const int want = (e->hasK ? 1 : 0) + (e->bounded == 1 ? 2 : 0);   // LimitedLimiter: the limiter's own coefficient first, then lower, upper
+    const int got = (int)tok.size() - 1;
+    if (got > want) return fail(MI_ERR_ARG, "mi_limiter_parse: '" + name + "' takes " + std::to_string(want) + " coefficient(s): extra '" + tok[want + 1] + "'");
+    double v[3] = {0, 0, 0};
+    for (int j = 0; j < got; ++j) {
+        char* end = nullptr;
+        v[j] = std::strtod(tok[j + 1].c_str(), &end);
+        if (end == tok[j + 1].c_str() || *end != '\0') return fail(MI_ERR_ARG, "mi_limiter_parse: '" + tok[j + 1] + "' is not a number");
+    }
+    if (got < want) return fail(MI_ERR_ARG, "mi_limiter_parse: '" + name + "' takes " + std::to_string(want) + " coefficient(s), " + std::to_string(got) + " given");
+    mi_limiter l{};
+    l.kind = e->kind; l.vector_form = e->vec; l.bounded = e->bounded ? 1 : 0;
+    l.k = e->hasK ? v[0] : 0.0;
+    l.lower = e->bounded == 2 ? 0.0 : e->bounded == 1 ? v[e->hasK ? 1 : 0] : 0.0;
+    l.upper = e->bounded == 2 ? 1.0 : e->bounded == 1 ? v[e->hasK ? 2 : 1] : 0.0;
+    LimCoef c;
+    MICHK(lim_check("mi_limiter_parse", &l, c));
+    *out = l;
+    return MI_OK;
+}
+
+extern "C" int mi_limited_weights(mi_addr_t a, const mi_limiter* lim, const double* cd_weights_dev, const double* face_flux_dev,
+                                  const double* const* phi_dev, const double* const* grad_dev, const double* const* c_dev,
+                                  double* weights_out_dev, double* limiter_out_dev_or_null)
+{
+    const char* who = "mi_limited_weights";
+    if (!a || !phi_dev || !grad_dev || !c_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    LimArgs q{};
+    MICHK(lim_check(who, lim, q.k));
+    const int m = lim->vector_form ? 3 : 1;
+    const double* in[17];
+    int n = 0;
+    in[n++] = q.cdw = cd_weights_dev; in[n++] = q.flux = face_flux_dev;
+    for (int j = 0; j < m; ++j) in[n++] = q.phi[j] = phi_dev[j];
+    for (int j = 0; j < 3 * m; ++j) in[n++] = q.grad[j] = grad_dev[j];
+    for (int d = 0; d < 3; ++d) in[n++] = q.cc[d] = c_dev[d];
+    MICHK(lim_outputs(who, in, n, weights_out_dev, limiter_out_dev_or_null));
+    if (!al16(cd_weights_dev) || !al16(face_flux_dev) || !al16(weights_out_dev) || (limiter_out_dev_or_null && !al16(limiter_out_dev_or_null)))
+        return fail(MI_ERR_ARG, std::string(who) + ": face fields must be 16-byte aligned");
+    HIPCHK(hipSetDevice(a->ctx->device));
+    MICHK(ensure_caller_tables(a));
+    if (a->L.nFaces == 0) return MI_OK;
+    q.lo = a->lowerAddr.p; q.up = a->upperAddr.p; q.w = weights_out_dev; q.limOut = limiter_out_dev_or_null;
+    q.nf = a->L.nFaces; q.xcd = a->ctx->xcdRows;
+    dispatch_k_limited_weights(lim->kind, lim->vector_form != 0, dim3(grid_for(a->L.nFaces)), dim3(256), a->ctx->stream, q);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+
+extern "C" int mi_patch_limited_weights(mi_patch_t p, const mi_limiter* lim, const double* patch_cd_weights_dev, const double* patch_flux_dev,
+                                        const double* const* phi_dev, const double* const* nbr_phi_dev, const double* const* grad_dev,
+                                        const double* const* nbr_grad_dev, const double* const* patch_delta_dev,
+                                        double* weights_out_dev, double* limiter_out_dev_or_null)
+{
+    const char* who = "mi_patch_limited_weights";
+    if (!p) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    PatchLimArgs q{};
+    MICHK(lim_check(who, lim, q.k));
+    if (p->nFaces == 0) return MI_OK;
+    if (!phi_dev || !nbr_phi_dev || !grad_dev || !nbr_grad_dev || !patch_delta_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    const int m = lim->vector_form ? 3 : 1;
+    const double* in[29];
+    int n = 0;
+    in[n++] = q.cdw = patch_cd_weights_dev; in[n++] = q.flux = patch_flux_dev;
+    for (int j = 0; j < m; ++j) { in[n++] = q.phi[j] = phi_dev[j]; in[n++] = q.nphi[j] = nbr_phi_dev[j]; }
+    for (int j = 0; j < 3 * m; ++j) { in[n++] = q.grad[j] = grad_dev[j]; in[n++] = q.ngrad[j] = nbr_grad_dev[j]; }
+    for (int d = 0; d < 3; ++d) in[n++] = q.pd[d] = patch_delta_dev[d];
+    MICHK(lim_outputs(who, in, n, weights_out_dev, limiter_out_dev_or_null));
+    HIPCHK(hipSetDevice(p->ctx->device));
+    q.fc = p->faceCells.p; q.w = weights_out_dev; q.limOut = limiter_out_dev_or_null; q.n = p->nFaces;
+    dispatch_k_patch_limited_weights(lim->kind, lim->vector_form != 0, dim3((p->nFaces + 255) / 256), dim3(256), p->ctx->stream, q);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }

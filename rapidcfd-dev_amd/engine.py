@@ -70,6 +70,7 @@ SYMBOLS = [
     "mi_sngrad_correction_flux", "mi_patch_sngrad_correction_flux", "mi_patch_internal_field", "mi_vec_submul",
     "mi_comm_create_external", "mi_addr_create_ordered", "mi_addr_tile_starts", "mi_addr_is_ordered",
     "mi_linear_upwind_correction", "mi_patch_linear_upwind_correction", "mi_lust_weights", "mi_fvm_assemble_corrected",
+    "mi_limiter_parse", "mi_limited_weights", "mi_patch_limited_weights",
 ]
 
 
@@ -903,6 +904,14 @@ class Patch:
         _chk(lib().mi_patch_linear_upwind_correction(self.h, C.c_double(scale), C.c_int32(n), _ptr(patch_flux), pv(patch_cf), pv(c), pv(patch_delta),
                                                      pv([g for gr in grad for g in gr]), pv([g for gr in nbr_grad for g in gr]), pv(out)))
 
+    def limited_weights(self, lim, patch_cd_weights, patch_flux, phi, nbr_phi, grad, nbr_grad, patch_delta, w_out, limiter_out=None):
+        """a limited scheme's weights on a COUPLED patch (LimitedScheme.C:145-195): phi / nbr_phi 1 or 3 arrays (cell field, its
+        patchNeighbourField), grad / nbr_grad 3 or 9 (grad[3*j + k] = d(phi_j)/dx_k), patch_delta [x, y, z]; lim a Limiter or a scheme name"""
+        lim = limiter(lim) if isinstance(lim, str) else lim
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_patch_limited_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), pv(phi), pv(nbr_phi), pv(grad),
+                                            pv(nbr_grad), pv(patch_delta), _ptr(w_out), _ptr(limiter_out)))
+
     def sngrad_correction_flux(self, corr_vecs, weights, grad, nbr_grad, gamma_magsf, out):
         """non-orthogonal correction flux on a COUPLED patch (gaussLaplacianSchemes.C:64-90 + surfaceInterpolationScheme.C:360-365)"""
         _chk(lib().mi_patch_sngrad_correction_flux(self.h, _ptr(corr_vecs[0]), _ptr(corr_vecs[1]), _ptr(corr_vecs[2]), _ptr(weights), _ptr(grad[0]),
@@ -941,6 +950,21 @@ def div_correction(cf, c, grad, scale=1.0) -> DivCorrection:
         for d in range(3):
             k.grad_dev[3 * r + d] = _ptr(g[d]).value
     return k
+
+
+class Limiter(C.Structure):
+    """mi_limiter (include/mi_ldu.h)"""
+    _fields_ = [("kind", C.c_int32), ("vector_form", C.c_int32), ("bounded", C.c_int32), ("k", C.c_double), ("lower", C.c_double), ("upper", C.c_double)]
+
+
+LIMITER_KINDS = ("limitedLinear", "vanLeer", "MUSCL", "Minmod", "SuperBee", "UMIST", "vanAlbada", "OSPRE", "QUICK", "limitedCubic", "Gamma", "SFCD")
+
+
+def limiter(scheme: str) -> Limiter:
+    """mi_limiter_parse: "vanLeer", "limitedLinearV 1", "limitedCubic01 0.5", "limitedVanLeer -1 2" ... (host only, no GPU)"""
+    out = Limiter()
+    _chk(lib().mi_limiter_parse(scheme.encode(), C.byref(out)))
+    return out
 
 
 class Assembly:
@@ -1018,6 +1042,14 @@ class Assembly:
         k = div_correction(cf, c, grad, scale)
         o = (C.c_void_p * max(len(out), 1))(*[_ptr(x) for x in out])
         _chk(lib().mi_linear_upwind_correction(self.addr.h, C.byref(k), C.c_int32(len(out)), _ptr(face_flux), o))
+
+    def limited_weights(self, lim, cd_weights, face_flux, phi, grad, centres, w_out, limiter_out=None):
+        """a limited scheme's weights on the internal faces in one face pass (mi_limited_weights): lim a Limiter or a scheme name, phi 1 or 3
+        cell arrays, grad 3 or 9 (grad[3*j + k] = d(phi_j)/dx_k), centres [x, y, z]"""
+        lim = limiter(lim) if isinstance(lim, str) else lim
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_limited_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), pv(phi), pv(grad), pv(centres), _ptr(w_out),
+                                      _ptr(limiter_out)))
 
     def lust_weights(self, cd_weights, face_flux, w_out):
         """LUST weights 0.75*cd_weights + 0.25*pos(faceFlux) (LUST.H:104-110)"""

@@ -889,6 +889,72 @@ void limitedLinearWeights(scalargpuField& w, const lduAddressing& a, scalar k, c
                                       C.component(2).data(), w.data(), nullptr), "limitedLinear::weights");
 }
 
+limitedScheme limitedScheme::New(const std::string& scheme)
+{
+    mi_limiter l{};
+    miCheck(mi_limiter_parse(scheme.c_str(), &l), "limitedSurfaceInterpolationScheme::New");
+    return limitedScheme(l);
+}
+namespace {
+struct limitedArrays
+{
+    const double* phi[3]; const double* grad[9]; int m = 0;
+    limitedArrays(const scalargpuField& vf, const vectorgpuField& g) : m(1)
+    {
+        phi[0] = vf.data();
+        for (int k = 0; k < 3; ++k) grad[k] = g.component(k).data();
+    }
+    limitedArrays(const vectorgpuField& vf, const vectorgpuField* const g[3]) : m(3)
+    {
+        for (int j = 0; j < 3; ++j) {
+            phi[j] = vf.component(j).data();
+            for (int k = 0; k < 3; ++k) grad[3 * j + k] = g[j]->component(k).data();
+        }
+    }
+};
+const double* const* comps(const vectorgpuField& v, const double* (&out)[3])
+{
+    for (int k = 0; k < 3; ++k) out[k] = v.component(k).data();
+    return out;
+}
+void limitedCall(scalargpuField& w, const lduAddressing& a, const limitedScheme& s, const scalargpuField& cdWeights, const scalargpuField& faceFlux,
+                 const limitedArrays& q, const vectorgpuField& C, scalargpuField* limiter)
+{
+    const double* c[3];
+    miCheck(mi_limited_weights(a.handle(), &s.data(), cdWeights.data(), faceFlux.data(), q.phi, q.grad, comps(C, c), w.data(),
+                               limiter ? limiter->data() : nullptr), "LimitedScheme::weights");
+}
+void patchLimitedCall(scalargpuField& w, const fvPatchCells& p, const limitedScheme& s, const scalargpuField& pCdWeights, const scalargpuField& pFaceFlux,
+                      const limitedArrays& own, const limitedArrays& nbr, const vectorgpuField& pDelta, scalargpuField* limiter)
+{
+    const double* d[3];
+    miCheck(mi_patch_limited_weights(p.handle(), &s.data(), pCdWeights.data(), pFaceFlux.data(), own.phi, nbr.phi, own.grad, nbr.grad,
+                                     comps(pDelta, d), w.data(), limiter ? limiter->data() : nullptr), "LimitedScheme::weights (coupled patch)");
+}
+} // namespace
+void limitedWeights(scalargpuField& w, const lduAddressing& a, const limitedScheme& s, const scalargpuField& cdWeights, const scalargpuField& faceFlux,
+                    const scalargpuField& vf, const vectorgpuField& gradVf, const vectorgpuField& C, scalargpuField* limiter)
+{
+    limitedCall(w, a, s, cdWeights, faceFlux, limitedArrays(vf, gradVf), C, limiter);
+}
+void limitedWeights(scalargpuField& w, const lduAddressing& a, const limitedScheme& s, const scalargpuField& cdWeights, const scalargpuField& faceFlux,
+                    const vectorgpuField& vf, const vectorgpuField* const gradVf[3], const vectorgpuField& C, scalargpuField* limiter)
+{
+    limitedCall(w, a, s, cdWeights, faceFlux, limitedArrays(vf, gradVf), C, limiter);
+}
+void patchLimitedWeights(scalargpuField& w, const fvPatchCells& p, const limitedScheme& s, const scalargpuField& pCdWeights, const scalargpuField& pFaceFlux,
+                         const scalargpuField& vf, const scalargpuField& nbrVf, const vectorgpuField& gradVf, const vectorgpuField& nbrGradVf,
+                         const vectorgpuField& pDelta, scalargpuField* limiter)
+{
+    patchLimitedCall(w, p, s, pCdWeights, pFaceFlux, limitedArrays(vf, gradVf), limitedArrays(nbrVf, nbrGradVf), pDelta, limiter);
+}
+void patchLimitedWeights(scalargpuField& w, const fvPatchCells& p, const limitedScheme& s, const scalargpuField& pCdWeights, const scalargpuField& pFaceFlux,
+                         const vectorgpuField& vf, const vectorgpuField& nbrVf, const vectorgpuField* const gradVf[3],
+                         const vectorgpuField* const nbrGradVf[3], const vectorgpuField& pDelta, scalargpuField* limiter)
+{
+    patchLimitedCall(w, p, s, pCdWeights, pFaceFlux, limitedArrays(vf, gradVf), limitedArrays(nbrVf, nbrGradVf), pDelta, limiter);
+}
+
 // ---- Pstream: the parallel run as this path sees it -------------------------------------------------------------
 namespace {
 struct PstreamState { bool par = false; int rank = 0, n = 1; mi_comm_t red = nullptr, halo = nullptr; };
