@@ -502,6 +502,43 @@ int mi_patch_limited_weights(mi_patch_t patch, const mi_limiter *lim, const doub
                              double *weights_out_dev, double *limiter_out_dev_or_null);
 int mi_gauss_grad(mi_addr_t addr, const double *sfx_dev, const double *sfy_dev, const double *sfz_dev,
                   const double *ssf_dev, const double *vol_dev_or_null, double *gx_dev, double *gy_dev, double *gz_dev);
+/* ---- the limited gradient schemes (finiteVolume/gradSchemes/limitedGradSchemes: cellLimitedGrad, cellMDLimitedGrad, faceLimitedGrad, faceMDLimitedGrad) ----
+ * mi_grad_limiter_parse: host only, no GPU.  Accepts exactly `cellLimited|cellMDLimited|faceLimited|faceMDLimited Gauss linear <k>` (the
+ *   constructors read the base scheme through gradScheme::New, then readScalar: cellLimitedGrad.H:88-107 and its siblings).  Refused
+ *   (MI_ERR_ARG): any other name, a base other than Gauss, an interpolation other than linear, a limited scheme over a limited scheme, a
+ *   missing or extra token, k outside [0, 1].  identity = k < SMALL (1e-15): the basic scheme's gradient is returned unchanged.
+ * mi_grad_boundary_create: the boundary as the limiters see it, built once per mesh on the host: n_patches patches in the reference's
+ *   order, patch p with patch_sizes[p] faces whose cells are face_cells_host[p], of kind patch_kinds[p] (MI_GRAD_PATCH_*: coupled,
+ *   fixesValue() or any other; an empty patch has zero faces).  Boundary face fields are the patch-ordered concatenation of every patch's
+ *   faces (nb = sum of patch_sizes).
+ * mi_limited_grad: limits the internal field of a Gauss linear gradient in place (grad_inout_dev[3*j + k] = d(vf_j)/dx_k, from
+ *   mi_gauss_grad + the boundary faces + the division by V), for n_comp = 1 (scalar) or 3 (vector) components, in ONE row pass:
+ *   cellLimited (cellLimitedGrads.C:47-199 scalar, :201-364 vector; limitFace cellLimitedGrad.H:136-171), cellMDLimited
+ *   (cellMDLimitedGrads.C; cellMDLimitedGrad.H:136-180), faceLimited (faceLimitedGrads.C:47-177 scalar, :183-340 vector; faceLimitedGrad.H:140-156,
+ *   including the vector form's unexpanded bounds on the neighbour side of an internal face, :241-254) and faceMDLimited (faceMDLimitedGrads.C).
+ *   c_dev: cell centres [x, y, z]; cf_dev: internal face centres; bvalue_dev[j]: per boundary face the patchNeighbourField (coupled
+ *   patches, e.g. mi_matrix_patch_neighbour_field) or the boundary value (the others); bcf_dev: boundary face centres.  The cell kinds
+ *   read every patch, the face kinds the coupled and fixesValue patches only.  boundary NULL: no boundary faces.  limiter_out: n_comp
+ *   cell arrays for cellLimited, 1 for faceLimited, NULL for the MD kinds (or NULL).  Each cell's faces are visited in the reference's
+ *   order and every expression is rounded as the reference's host loops round it.  With lim->identity nothing is written
+ *   and nothing launched.  Refused (MI_ERR_ARG, nothing launched): an invalid mi_grad_limiter, n_comp not 1 or 3, a boundary built for
+ *   another addressing, NULL boundary arrays while the boundary has faces, limiter_out for an MD kind, missing arrays, an output that
+ *   aliases an input or another output.  The gradient's boundary values stay the caller's (as for mi_gauss_grad). */
+enum { MI_GRAD_CELL_LIMITED, MI_GRAD_CELL_MD_LIMITED, MI_GRAD_FACE_LIMITED, MI_GRAD_FACE_MD_LIMITED };
+enum { MI_GRAD_PATCH_OTHER, MI_GRAD_PATCH_COUPLED, MI_GRAD_PATCH_FIXES_VALUE };
+typedef struct mi_grad_limiter {
+    int32_t kind;          /* MI_GRAD_* */
+    int32_t identity;      /* k < SMALL */
+    double k;
+} mi_grad_limiter;
+typedef struct mi_grad_boundary_s *mi_grad_boundary_t;
+int mi_grad_limiter_parse(const char *scheme, mi_grad_limiter *out);
+int mi_grad_boundary_create(mi_addr_t addr, int32_t n_patches, const int32_t *patch_sizes, const int32_t *const *face_cells_host,
+                            const int32_t *patch_kinds, mi_grad_boundary_t *out);
+int mi_grad_boundary_destroy(mi_grad_boundary_t boundary);
+int mi_limited_grad(mi_addr_t addr, const mi_grad_limiter *lim, mi_grad_boundary_t boundary_or_null, int32_t n_comp,
+                    const double *const *vf_dev, const double *const *c_dev, const double *const *cf_dev, const double *const *bvalue_dev,
+                    const double *const *bcf_dev, double *const *grad_inout_dev, double *const *limiter_out_dev_or_null);
 int mi_vec_axpby(mi_ctx_t ctx, int64_t n, double a, const double *x_dev, double b, const double *y_dev, double *out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),

@@ -2494,6 +2494,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "pcg_fused.inc"
 #include "gamg_engine.inc"
 #include "assembly.inc"
+#include "limited_grad.inc"
 
 mi_matrix_s::~mi_matrix_s()
 {

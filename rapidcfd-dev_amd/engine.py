@@ -71,6 +71,7 @@ SYMBOLS = [
     "mi_comm_create_external", "mi_addr_create_ordered", "mi_addr_tile_starts", "mi_addr_is_ordered",
     "mi_linear_upwind_correction", "mi_patch_linear_upwind_correction", "mi_lust_weights", "mi_fvm_assemble_corrected",
     "mi_limiter_parse", "mi_limited_weights", "mi_patch_limited_weights",
+    "mi_grad_limiter_parse", "mi_grad_boundary_create", "mi_grad_boundary_destroy", "mi_limited_grad",
 ]
 
 
@@ -967,6 +968,46 @@ def limiter(scheme: str) -> Limiter:
     return out
 
 
+class GradLimiter(C.Structure):
+    """mi_grad_limiter (include/mi_ldu.h)"""
+    _fields_ = [("kind", C.c_int32), ("identity", C.c_int32), ("k", C.c_double)]
+
+
+GRAD_LIMITER_KINDS = ("cellLimited", "cellMDLimited", "faceLimited", "faceMDLimited")
+GRAD_PATCH_KINDS = {"other": 0, "coupled": 1, "fixesValue": 2}
+
+
+def grad_limiter(scheme: str) -> GradLimiter:
+    """mi_grad_limiter_parse: "cellLimited Gauss linear 1", "faceMDLimited Gauss linear 0.5" ... (host only, no GPU)"""
+    out = GradLimiter()
+    _chk(lib().mi_grad_limiter_parse(scheme.encode(), C.byref(out)))
+    return out
+
+
+class GradBoundary:
+    """The boundary of a limited gradient (mi_grad_boundary_create): the patches in order, each its faceCells and a kind ("coupled",
+    "fixesValue", "other"); boundary face fields are the patch-ordered concatenation of their faces (n_faces)."""
+
+    def __init__(self, addr: Addressing, face_cells: Sequence, kinds: Sequence):
+        fcs = [np.ascontiguousarray(f, dtype=np.int32) for f in face_cells]
+        n = len(fcs)
+        if len(kinds) != n:
+            raise MiError("one kind per patch")
+        I32 = C.POINTER(C.c_int32)
+        sizes = (C.c_int32 * max(n, 1))(*[f.shape[0] for f in fcs])
+        ptrs = (I32 * max(n, 1))(*[f.ctypes.data_as(I32) for f in fcs])
+        kd = (C.c_int32 * max(n, 1))(*[GRAD_PATCH_KINDS[k] if isinstance(k, str) else int(k) for k in kinds])
+        self.addr = addr
+        self.n_faces = int(sum(f.shape[0] for f in fcs))
+        self.h = C.c_void_p()
+        _chk(lib().mi_grad_boundary_create(addr.h, C.c_int32(n), sizes, ptrs, kd, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().mi_grad_boundary_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Assembly:
     """fvm::div / fvm::laplacian / negSumDiag / relax ... on caller-order arrays of an Addressing."""
 
@@ -1050,6 +1091,16 @@ class Assembly:
         pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
         _chk(lib().mi_limited_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), pv(phi), pv(grad), pv(centres), _ptr(w_out),
                                       _ptr(limiter_out)))
+
+    def limited_grad(self, lim, vf, centres, cf, grad, boundary=None, bvalue=None, bcf=None, limiter_out=None):
+        """limits a Gauss linear gradient in place (mi_limited_grad): lim a GradLimiter or a scheme ("cellLimited Gauss linear 1"), vf 1 or 3
+        cell arrays, centres / cf / bcf [x, y, z] (cells, internal faces, boundary faces), grad 3 or 9 (grad[3*j + k] = d(vf_j)/dx_k),
+        boundary a GradBoundary (or None), bvalue one boundary-face array per component; limiter_out n_comp arrays (cellLimited), 1
+        (faceLimited) or None"""
+        lim = grad_limiter(lim) if isinstance(lim, str) else lim
+        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_limited_grad(self.addr.h, C.byref(lim), boundary.h if boundary is not None else None, C.c_int32(len(vf)), pv(vf),
+                                   pv(centres), pv(cf), pv(bvalue), pv(bcf), pv(grad), pv(limiter_out)))
 
     def lust_weights(self, cd_weights, face_flux, w_out):
         """LUST weights 0.75*cd_weights + 0.25*pos(faceFlux) (LUST.H:104-110)"""

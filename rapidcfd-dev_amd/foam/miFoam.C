@@ -1019,4 +1019,52 @@ label Pstream::returnReduceSum(label v)
     return (label)(t.asHost()[0] + 0.5);
 }
 
+// ---- the limited gradient schemes -------------------------------------------------------------------------------------------------
+fv::limitedGradScheme fv::limitedGradScheme::New(const std::string& scheme)
+{
+    mi_grad_limiter l{};
+    miCheck(mi_grad_limiter_parse(scheme.c_str(), &l), "gradScheme::New");
+    return limitedGradScheme(l);
+}
+gradBoundary::gradBoundary(const lduAddressing& a, const std::vector<labelList>& faceCells, const std::vector<patchKind>& kinds) : h_(nullptr)
+{
+    if (faceCells.size() != kinds.size()) FatalErrorIn("gradBoundary", "one kind per patch");
+    std::vector<int32_t> sizes, kd;
+    std::vector<const int32_t*> ptrs;
+    for (size_t p = 0; p < faceCells.size(); ++p) {
+        sizes.push_back((int32_t)faceCells[p].size()); ptrs.push_back(faceCells[p].data()); kd.push_back((int32_t)kinds[p]);
+    }
+    miCheck(mi_grad_boundary_create(a.handle(), (int32_t)sizes.size(), sizes.data(), ptrs.data(), kd.data(), &h_), "gradBoundary");
+}
+gradBoundary::~gradBoundary() { if (h_) mi_grad_boundary_destroy(h_); }
+void fvc::limitedGrad(vectorgpuField& g, const lduAddressing& a, const fv::limitedGradScheme& s, const gradBoundary* b, const scalargpuField& vf,
+                      const vectorgpuField& C, const vectorgpuField& Cf, const scalargpuField* bValue, const vectorgpuField* bCf, scalargpuField* limiter)
+{
+    const double* v[1] = {vf.data()};
+    const double* c[3] = {C.component(0).data(), C.component(1).data(), C.component(2).data()};
+    const double* cf[3] = {Cf.component(0).data(), Cf.component(1).data(), Cf.component(2).data()};
+    const double* bv[1] = {bValue ? bValue->data() : nullptr};
+    const double* bcf[3] = {nullptr, nullptr, nullptr};
+    if (bCf) for (int d = 0; d < 3; ++d) bcf[d] = bCf->component(d).data();
+    double* gr[3] = {g.component(0).data(), g.component(1).data(), g.component(2).data()};
+    double* lim[1] = {limiter ? limiter->data() : nullptr};
+    miCheck(mi_limited_grad(a.handle(), &s.data(), b ? b->handle() : nullptr, 1, v, c, cf, bValue ? bv : nullptr, bCf ? bcf : nullptr, gr,
+                            limiter ? lim : nullptr), "fvc::grad (limited)");
+}
+void fvc::limitedGrad(vectorgpuField* const g[3], const lduAddressing& a, const fv::limitedGradScheme& s, const gradBoundary* b, const vectorgpuField& vf,
+                      const vectorgpuField& C, const vectorgpuField& Cf, const vectorgpuField* bValue, const vectorgpuField* bCf, vectorgpuField* limiter)
+{
+    const double *v[3], *c[3], *cf[3], *bv[3] = {nullptr, nullptr, nullptr}, *bcf[3] = {nullptr, nullptr, nullptr};
+    double *gr[9], *lim[3] = {nullptr, nullptr, nullptr};
+    for (int d = 0; d < 3; ++d) {
+        v[d] = vf.component(d).data(); c[d] = C.component(d).data(); cf[d] = Cf.component(d).data();
+        if (bValue) bv[d] = bValue->component(d).data();
+        if (bCf) bcf[d] = bCf->component(d).data();
+        if (limiter) lim[d] = limiter->component(d).data();
+        for (int k = 0; k < 3; ++k) gr[3 * d + k] = g[d]->component(k).data();
+    }
+    miCheck(mi_limited_grad(a.handle(), &s.data(), b ? b->handle() : nullptr, 3, v, c, cf, bValue ? bv : nullptr, bCf ? bcf : nullptr, gr,
+                            limiter ? lim : nullptr), "fvc::grad (limited)");
+}
+
 } // namespace Foam
