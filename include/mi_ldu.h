@@ -82,7 +82,8 @@ typedef struct {
 
 /* ---- context (replaces src/OpenFOAM/device/DeviceConfig.{H,C}, DeviceStream) ---- */
 /* stream: a hipStream_t created by the caller (e.g. torch's current stream) or NULL
- * for the engine's own stream.                                                     */
+ * for the engine's own stream.  MI_PCG_BATCH (iterations per batch of the device-resident
+ * Krylov loops, default 16) below 1 is taken as 1.                                  */
 int mi_ctx_create(int device, void *hip_stream, mi_ctx_t *out);
 int mi_ctx_destroy(mi_ctx_t ctx);
 int mi_ctx_synchronize(mi_ctx_t ctx);
@@ -99,13 +100,23 @@ int mi_ctx_set_option(mi_ctx_t ctx, const char *name, int32_t value);
  * iterations -- on plain (MI_STAT_PERSIST_PCG) / communicator-attached (MI_STAT_PERSIST_DPCG) matrices; runs of the grid
  * barrier litmus that gates that kernel (MI_STAT_BARRIER_LITMUS); V-cycles of a decomposed case replayed as a hipGraph
  * (MI_STAT_GAMG_GRAPH_ATTACHED); launches of the fused residual / direction kernel of PCG (MI_STAT_PCG_FUSED_RP); batches of
- * PCG iterations that mi_pcg_solve replayed from a hipGraph (MI_STAT_PCG_GRAPH) */
+ * PCG iterations that mi_pcg_solve replayed from a hipGraph (MI_STAT_PCG_GRAPH); solves of one PBiCG loop per call --
+ * mi_pbicg_solve or mi_pbicg_solve_multi -- through the multi-vector solver (MI_STAT_PBICG_MULTI), through the device loop
+ * pbicg_solve_device (MI_STAT_PBICG_DEVICE, once per component) and host-stepped (MI_STAT_PBICG_HOST_STEPPED); PBiCGStab solves
+ * through the device loop (MI_STAT_PBICGSTAB_DEVICE) and host-stepped (MI_STAT_PBICGSTAB_HOST_STEPPED); PBiCGStab solves of either
+ * loop that ended at the mid-iteration exit, converged on the residual of sA (MI_STAT_PBICGSTAB_MID_EXIT) */
 #define MI_STAT_PERSIST_PCG 0
 #define MI_STAT_PERSIST_DPCG 1
 #define MI_STAT_BARRIER_LITMUS 2
 #define MI_STAT_GAMG_GRAPH_ATTACHED 3
 #define MI_STAT_PCG_FUSED_RP 4
 #define MI_STAT_PCG_GRAPH 5
+#define MI_STAT_PBICG_MULTI 6
+#define MI_STAT_PBICG_DEVICE 7
+#define MI_STAT_PBICG_HOST_STEPPED 8
+#define MI_STAT_PBICGSTAB_DEVICE 9
+#define MI_STAT_PBICGSTAB_HOST_STEPPED 10
+#define MI_STAT_PBICGSTAB_MID_EXIT 11
 int mi_ctx_stat(mi_ctx_t ctx, int32_t which, int64_t *out);
 const char *mi_last_error(void);
 /* 1 if a usable gfx950 device is visible to this process, else 0 */

@@ -98,7 +98,7 @@ struct mi_ctx_s {
     int pcgFuseTest = 0; // tests ("pcg_fuse_test"): workgroups of the fused launch that leave its barrier at once (pcg_fused.inc)
     int pcgFuseRP = -1; // MI_PCG_FUSE_RP: residual update + next direction update as one launch (pcg_fused.inc); 0 never, -1 (default) once the device has been asked
     int pcgPersist = 1; // MI_PCG_PERSIST: 0 never, 1 (default) whenever the tiles fit the CUs' registers (persist.inc)
-    int64_t stats[6] = {0, 0, 0, 0, 0, 0}; // mi_ctx_stat
+    int64_t stats[12] = {}; // mi_ctx_stat
     int persistGrid = 0; // MI_PERSIST_GRID: workgroups of the persistent kernel (0: one per CU); MI_PERSIST_SHARED=1 lets ranks that share a device use it -- tests only: their grids must fit the device TOGETHER
     int persistShared = 0;
     int persistCoop = -1; // cooperative launch of the persistent kernel possible on this device AND its barrier litmus clean (-1: not asked yet)
@@ -280,7 +280,9 @@ extern "C" int mi_ctx_create(int device, void* hip_stream, mi_ctx_t* out)
     c->persistShared = env_int("MI_PERSIST_SHARED", 0);
     c->fuseFinal = env_int("MI_PCG_FUSE_FINAL", 0); // measured: no gain (332.0 vs 332.3 us/iter), kept as an option
     c->amulBS = env_int("MI_AMUL_BS", 0); // 0 = choose per launch from the LDS footprint
-    c->pcgBatch = env_int("MI_PCG_BATCH", 16); c->pcgGraph = env_int("MI_PCG_GRAPH", -1); c->pbicgHostStepped = env_int("MI_PBICG_HOST_STEPPED", 0);
+    c->pcgBatch = env_int("MI_PCG_BATCH", 16);
+    if (c->pcgBatch < 1) c->pcgBatch = 1;   // every batched loop advances by the batch length: 0 or less would never end
+    c->pcgGraph = env_int("MI_PCG_GRAPH", -1); c->pbicgHostStepped = env_int("MI_PBICG_HOST_STEPPED", 0);
     c->gamgDeviceInvert = env_int("MI_GAMG_DEVICE_INVERT", -1); c->gamgAlwaysAgglomerate = env_int("MI_GAMG_ALWAYS_AGGLOMERATE", 0); c->gamgGraph = env_int("MI_GAMG_GRAPH", 1); c->gamgFuse = env_int("MI_GAMG_FUSE", 1);
     if (c->amulBS != 256 && c->amulBS != 512 && c->amulBS != 1024) c->amulBS = 0;
     *out = c;
@@ -330,10 +332,12 @@ extern "C" int mi_ctx_set_option(mi_ctx_t c, const char* name, int32_t value)
 
 // which solver paths ran on this context: 0 / 1 = launches of the persistent PCG kernel (one per batch of iterations) on plain /
 // attached matrices, 2 = grid-barrier litmus runs (persist.inc), 3 = V-cycles of a decomposed case replayed as a hipGraph,
-// 4 = launches of the fused residual / direction kernel of PCG (pcg_fused.inc), 5 = PCG batches replayed as a hipGraph (mi_pcg_solve)
+// 4 = launches of the fused residual / direction kernel of PCG (pcg_fused.inc), 5 = PCG batches replayed as a hipGraph (mi_pcg_solve),
+// PBiCG loops through 6 = the multi-vector solver (multi.inc), 7 = pbicg_solve_device, 8 = the host-stepped loop; PBiCGStab solves
+// through 9 = the device loop, 10 = the host-stepped loop; 11 = PBiCGStab solves that ended at the mid-iteration exit
 extern "C" int mi_ctx_stat(mi_ctx_t c, int32_t which, int64_t* out)
 {
-    if (!c || !out || which < 0 || which >= 6) return fail(MI_ERR_ARG, "mi_ctx_stat: bad argument");
+    if (!c || !out || which < 0 || which >= (int32_t)(sizeof(c->stats) / sizeof(c->stats[0]))) return fail(MI_ERR_ARG, "mi_ctx_stat: bad argument");
     *out = c->stats[which];
     return MI_OK;
 }
@@ -2085,6 +2089,7 @@ int pbicg_solve_device(mi_matrix_s* m, double* psi_io, const double* source, con
     MICHK(tile_op<OP_AMUL>(m, true, psi, nullptr, nullptr, wT, 0.0));
     k_sub<<<RG, RB, 0, s>>>(rT, src, wT, n);
     MICHK(fetch_state(c));
+    c->stats[7] += 1;   // mi_ctx_stat(7): solves of pbicg_solve_device
     const int batch = m->addr->ctx->pcgBatch;
     int it = 0, nb = batch < 2 ? batch : 2;   // growing batches, as in mi_pcg_solve
     while (!c->hostState->done && it <= ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0)) {
@@ -2132,6 +2137,7 @@ extern "C" int mi_pbicg_solve(mi_matrix_t m, double* psi_io, const double* sourc
     k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
     k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
     HostPerf hp; Table<double> hist;
+    a->ctx->stats[8] += 1;   // mi_ctx_stat(8): host-stepped PBiCG solves
     MICHK(host_prologue(m, ctl, psi, src, wA, rA, pA, hp, hist));
     MICHK(tile_op<OP_AMUL>(m, true, psi, nullptr, nullptr, wT, 0.0));
     k_sub<<<RG, RB, 0, s>>>(rT, src, wT, n);
@@ -2221,6 +2227,7 @@ int pbicgstab_solve_device(mi_matrix_s* m, double* psi_io, const double* source,
     MICHK(solve_prologue(m, ctl, psi, src, yA, rA, pA, histLen));
     HIPCHK(hipMemcpyAsync(rA0, rA, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
     MICHK(fetch_state(c));
+    c->stats[9] += 1;   // mi_ctx_stat(9): PBiCGStab solves of the device loop
     const int batch = m->addr->ctx->pcgBatch;
     int it = 0, nb = batch < 2 ? batch : 2;   // growing batches, as in mi_pcg_solve
     while (!c->hostState->done && it <= ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0)) {
@@ -2230,6 +2237,9 @@ int pbicgstab_solve_device(mi_matrix_s* m, double* psi_io, const double* source,
         MICHK(peer_check(m));
         nb = nb * 2 > batch ? batch : nb * 2;
     }
+    // mi_ctx_stat(11): k_stab_mid_final ended the solve -- it counts the half iteration but leaves st->it where the last
+    // k_pcg_final (or k_solve_init) put it, one behind nIterations; every other exit leaves them equal or unconverged
+    if (c->hostState->converged && c->hostState->it + 1 == c->hostState->nIterations) c->stats[11] += 1;
     k_scatter_perm<<<RG, RB, 0, s>>>(psi, a->perm(), psi_io, a->L.nCells);
     HIPCHK(hipGetLastError());
     if (perf) fill_perf(*c->hostState, perf);
@@ -2258,6 +2268,7 @@ extern "C" int mi_pbicgstab_solve(mi_matrix_t m, double* psi_io, const double* s
     k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
     k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
     HostPerf hp; Table<double> hist;
+    a->ctx->stats[10] += 1;   // mi_ctx_stat(10): host-stepped PBiCGStab solves
     MICHK(host_prologue(m, ctl, psi, src, yA, rA, pA, hp, hist));
     if (hp.minIter > 0 || !hp.checkConvergence()) {
         HIPCHK(hipMemcpyAsync(rA0, rA, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
@@ -2287,6 +2298,7 @@ extern "C" int mi_pbicgstab_solve(mi_matrix_t m, double* psi_io, const double* s
                 k_xpsy<<<RG, RB, 0, s>>>(psi, psi, alpha, yA, n);
                 hp.nIterations++;
                 hist.push_back(hp.finalResidual);
+                a->ctx->stats[11] += 1;   // mi_ctx_stat(11): the mid-iteration exit
                 return finish_host(m, hp, hist, psi, psi_io, perf, hist_host, hist_len);
             }
             MICHK(precond_engine(m, precond, false, sA, zA));

@@ -1536,9 +1536,11 @@ __device__ __forceinline__ void solve_init_body(PcgState* __restrict__ st, const
     if (histLen > 0) hist[0] = res;
     st->nIterations = 0; st->singular = 0; st->it = 0;
     st->wArA[0] = SP_GREAT; st->wArA[1] = SP_GREAT;
-    const bool conv = sp_converged(st, res);
+    // `minIter_ > 0 || !checkConvergence(...)` (PCG.C:121 and siblings): with minIter the test is never made, so converged stays
+    // false until a later test -- a solve that then ends at a singular exit reports it unconverged
+    const bool conv = st->minIter <= 0 && sp_converged(st, res);
     st->converged = conv;
-    st->done = (st->minIter > 0 || !conv) ? 0 : 1;
+    st->done = conv ? 1 : 0;
 }
 template <bool DIST = false>
 __global__ __launch_bounds__(RB) void k_solve_init(PcgState* __restrict__ st, const double* __restrict__ partialNF,

@@ -226,6 +226,7 @@ extern "C" int mi_pbicg_solve_multi(mi_matrix_t m, int32_t nrhs, const double* c
     hipStream_t s = c->stream;
     const int64_t n = a->L.nCells;
     const int histLen = ctl->maxIter + 2;
+    c->stats[6] += 1;   // mi_ctx_stat(6): solves through the multi-vector loop below
     // per component: 8 engine-order vectors (+ diagonal, 1/diagonal, sumA when the diagonals differ), a device state, 4 RG partial slots, a history
     double *psi[3], *src[3], *pA[3], *wA[3], *rA[3], *pT[3], *wT[3], *rT[3], *dgE[3] = {nullptr, nullptr, nullptr}, *rDc[3] = {nullptr, nullptr, nullptr}, *sumAc[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < nrhs; ++k) {

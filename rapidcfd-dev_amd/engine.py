@@ -238,7 +238,9 @@ class Context:
     def stat(self, which: int) -> int:
         """mi_ctx_stat: 0 = launches of the persistent PCG kernel on plain matrices, 1 = on communicator-attached ones,
         2 = grid-barrier litmus runs, 3 = V-cycles of a decomposed case replayed as a hipGraph, 4 = launches of the fused residual / direction kernel of PCG,
-        5 = batches of PCG iterations replayed as a hipGraph (mi_pcg_solve)"""
+        5 = batches of PCG iterations replayed as a hipGraph (mi_pcg_solve), PBiCG loops run through 6 = the multi-vector solver,
+        7 = pbicg_solve_device (once per component), 8 = the host-stepped loop (MI_PBICG_HOST_STEPPED), PBiCGStab solves through
+        9 = the device loop, 10 = the host-stepped loop, 11 = PBiCGStab solves that ended at the mid-iteration exit"""
         v = C.c_int64(0)
         _chk(lib().mi_ctx_stat(self.h, C.c_int32(which), C.byref(v)))
         return int(v.value)
