@@ -104,7 +104,9 @@ int mi_ctx_set_option(mi_ctx_t ctx, const char *name, int32_t value);
  * mi_pbicg_solve or mi_pbicg_solve_multi -- through the multi-vector solver (MI_STAT_PBICG_MULTI), through the device loop
  * pbicg_solve_device (MI_STAT_PBICG_DEVICE, once per component) and host-stepped (MI_STAT_PBICG_HOST_STEPPED); PBiCGStab solves
  * through the device loop (MI_STAT_PBICGSTAB_DEVICE) and host-stepped (MI_STAT_PBICGSTAB_HOST_STEPPED); PBiCGStab solves of either
- * loop that ended at the mid-iteration exit, converged on the residual of sA (MI_STAT_PBICGSTAB_MID_EXIT) */
+ * loop that ended at the mid-iteration exit, converged on the residual of sA (MI_STAT_PBICGSTAB_MID_EXIT).  (The device loops
+ * share one host frame in csrc/engine.hip -- stage_in, drive_batches, finish_device -- around the bodies they enqueue:
+ * bicg_enqueue for pbicg_solve_device, stab_enqueue for pbicgstab_solve_device, the in-line body of mi_pbicg_solve_multi.) */
 #define MI_STAT_PERSIST_PCG 0
 #define MI_STAT_PERSIST_DPCG 1
 #define MI_STAT_BARRIER_LITMUS 2

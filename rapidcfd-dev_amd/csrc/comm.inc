@@ -653,7 +653,7 @@ extern "C" int mi_matrix_patch_neighbour_field(mi_matrix_t m, const double* psi,
         MICHK(a->ifaceNbrCaller.upload(nb, s));
     }
     double* v0;
-    MICHK(m->vec(0, &v0));
+    MICHK(m->vec(WV_OP_X, &v0));
     if (comm_remote(m) || !a->ami.empty()) k_gather_perm<<<RG, RB, 0, s>>>(psi, a->perm(), v0, a->L.nCells);
     if (!a->ami.empty() && !(a->amiRemote && comm_remote(m))) MICHK(ami_fill(m, v0)); // cyclicAMI: interpolated (and transformed) partner values
     if (comm_remote(m)) {
@@ -748,70 +748,34 @@ int pcg_solve_attached(mi_matrix_s* m, double* psi_io, const double* source, con
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int64_t n = a->L.nCells;
-    double *psi, *src, *pA, *wA, *rA;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &wA)); MICHK(m->vec(7, &rA));
-    k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
+    PcgVecs v;
+    MICHK(stage_in(m, v, psi_io, source));
+    double *psi = v.psi, *src = v.src, *pA = v.pA, *wA = v.wA, *rA = v.rA;
     // (cyclicAMI / transformed patches: the phase pipeline below does not interpolate them; the tile-operator pipeline does)
     if ((precond == MI_PRECOND_DIAGONAL || precond == MI_PRECOND_NONE) && !comm_any_ami(m) && !comm_any_factor(m)) {
         if (m->dscal.n < 8) { MICHK(m->dscal.alloc(8)); HIPCHK(hipMemsetAsync(m->dscal.p, 0, 8 * sizeof(double), s)); }
         if (m->sendBuf.n < (size_t)std::max(a->L.nExt, 1)) MICHK(m->sendBuf.alloc((size_t)std::max(a->L.nExt, 1)));
-        const int histLen = ctl->maxIter + 2;
-        MICHK(mi_dpcg_set_buffers(m, psi, src, pA, wA, rA, m->dscal.p, m->sendBuf.p, ctl, precond, histLen));
+        MICHK(mi_dpcg_set_buffers(m, psi, src, pA, wA, rA, m->dscal.p, m->sendBuf.p, ctl, precond, ctl->maxIter + 2));
         MICHK(dpcg_prologue(m));
         MICHK(fetch_state(c));
-        const int batch = m->addr->ctx->pcgBatch;
-        while (!c->hostState->done && m->dpc->it <= ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0)) {
-            MICHK(mi_dpcg_comm_iterate(m, batch, 0));
-            MICHK(fetch_state(c));
-            MICHK(peer_check(m));
-        }
-        if (dpcg_fused_usable(m)) MICHK(dpcg_fused_flush(m));
-        if (perf) fill_perf(*c->hostState, perf);
-        MICHK(copy_hist(m, hist_host, hist_len, c->hostState->nIterations));
-        k_scatter_perm<<<RG, RB, 0, s>>>(psi, a->perm(), psi_io, a->L.nCells);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
+        // full batches from the start; mi_dpcg_comm_iterate counts the iterations in m->dpc->it
+        MICHK(drive_batches(m, ctl, m->dpc->it, c->pcgBatch, [m](int nb) { return mi_dpcg_comm_iterate(m, nb, 0); }));
+        MICHK(finish_device(m, psi, psi_io, perf, hist_host, hist_len, dpcg_flush_if_fused));
         m->dp = mi_dpcg_s();
         return MI_OK;
     }
     if (c->pbicgHostStepped == 0) {
         // AINV (= DIC): the single-GPU device-resident pipeline (pcg_enqueue: AINV tile pass with the fused wA.rA sum, Amul with
         // the fused wA.pA sum, one vector pass), its sums all-reduced on the device (globalize); the host polls `done` per batch
-        const int histLen = ctl->maxIter + 2;
-        MICHK(solve_prologue(m, ctl, psi, src, wA, rA, pA, histLen));
-        // diagonal / none on this pipeline (a case with cyclicAMI or transformed patches): the wArA partials of iteration 0, as
-        // mi_pcg_begin forms them (later iterations get them from k_pcg_update_psi_r); global like every other sum
-        if (precond == MI_PRECOND_DIAGONAL) {
-            MICHK(ensure_rD(m));
-            k_pcg_precond_dot<true><<<RG, RB, 0, s>>>(c->state.p, m->rD.p, rA, wA, n, c->partial.p);
-            MICHK(globalize(m, c->partial.p));
-        } else if (precond == MI_PRECOND_NONE) {
-            k_pcg_precond_dot<false><<<RG, RB, 0, s>>>(c->state.p, nullptr, rA, wA, n, c->partial.p);
-            MICHK(globalize(m, c->partial.p));
-        }
-        HIPCHK(hipGetLastError());
+        MICHK(solve_prologue(m, ctl, psi, src, wA, rA, ctl->maxIter + 2));
+        MICHK(pcg_first_dot(m, precond, v));   // (diagonal / none on this pipeline: a case with cyclicAMI or transformed patches)
         MICHK(fetch_state(c));
-        const int batch = c->pcgBatch;
-        const int limit = ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0);
-        int it = 0, nb = batch < 2 ? batch : 2;
-        while (!c->hostState->done && it <= limit) {
-            MICHK(pcg_enqueue(m, it, nb, precond, 0));
-            it += nb;
-            MICHK(fetch_state(c));
-            MICHK(peer_check(m));
-            nb = nb * 2 > batch ? batch : nb * 2;
-        }
-        MICHK(pcg_flush(m));
-        k_scatter_perm<<<RG, RB, 0, s>>>(psi, a->perm(), psi_io, a->L.nCells);
-        HIPCHK(hipGetLastError());
-        if (perf) fill_perf(*c->hostState, perf);
-        MICHK(copy_hist(m, hist_host, hist_len, c->hostState->nIterations));
-        HIPCHK(hipStreamSynchronize(s));
-        return MI_OK;
+        int it = 0;
+        MICHK(drive_batches(m, ctl, it, 2, [&](int nb) { it += nb; return pcg_enqueue(m, it - nb, nb, precond, 0); }));
+        return finish_device(m, psi, psi_io, perf, hist_host, hist_len, pcg_flush);
     }
     HostPerf hp; Table<double> hist;
-    MICHK(host_prologue(m, ctl, psi, src, wA, rA, pA, hp, hist));
+    MICHK(host_prologue(m, ctl, psi, src, wA, rA, hp, hist));
     double wArA = SP_GREAT, wArAold = wArA;
     if (hp.minIter > 0 || !hp.checkConvergence()) {
         do {

@@ -153,6 +153,27 @@ struct mi_addr_s {
 
 struct mi_dpcg_s { double *psi = nullptr, *src = nullptr, *pA = nullptr, *wA = nullptr, *rA = nullptr, *scal = nullptr, *send = nullptr; int precond = 0; };
 
+// The work vectors of a matrix (mi_matrix_s::work, taken with vec() / vecs()) by name.  The numbers are fixed: a slot's buffer is
+// allocated when it is first taken, so they decide allocation order and footprint.  Names that share a number overlap, and may:
+//  - WV_OP_*: operator-level calls (caller_op, mi_precondition, mi_jacobi_smooth, mi_matrix_set_ext, the patch neighbour field, the peer
+//    windows' self-test).  Each use ends inside one extern "C" call.  WV_OP_X also keeps the ext tail mi_matrix_set_ext places: no solver takes 0 .. 2.
+//  - WV_NF_*: mi_norm_factor; WV_NF_PSI is the solvers' WV_PSI.  A one-call solver gathers psi afresh (stage_in); only a PCG session
+//    (mi_pcg_begin .. mi_pcg_end) keeps anything there between calls, and solver_entry refuses mi_norm_factor and every solver meanwhile.
+//  - WV_PSI .. WV_STAB_RES1: the solvers (GAMG: 3 .. 8, its own names).  Each stages psi and source in and rebuilds every other vector, and
+//    none runs while another does (one stream per context, the session check above): PCG's wA is PBiCGStab's yA, PBiCG's pT .. rT its
+//    AyA .. zA, mi_smooth_solve's second psi.  The persistent and fused PCG kernels and mi_bench_amul use PCG's names.
+//  - ranges of their own: WV_BENCH_ZERO, never written (psi0 = 0 of mi_bench_pcg_iters); WV_MULTI + WV_MULTI_STRIDE k + j, component k of
+//    mi_pbicg_solve_multi (j: psi, src, pA, wA, rA, pT, wT, rT, diag, 1 / diag, sumA).
+enum WorkVec : size_t {
+    WV_OP_X = 0, WV_OP_Y = 1, WV_OP_B = 2,
+    WV_NF_APSI = 0, WV_NF_SUMA = 1, WV_NF_SRC = 2, WV_NF_PSI = 3,
+    WV_PSI = 3, WV_SRC = 4, WV_PA = 5, WV_WA = 6, WV_RA = 7,                                 // every solver (PcgVecs)
+    WV_PT = 8, WV_WT = 9, WV_RT = 10,                                                        // PBiCG (BicgVecs)
+    WV_STAB_YA = 6, WV_STAB_AYA = 8, WV_STAB_SA = 9, WV_STAB_ZA = 10, WV_STAB_TA = 11, WV_STAB_RA0 = 12,   // PBiCGStab (StabVecs)
+    WV_STAB_RES1 = 13,                                                                       // ... its host-stepped loop only
+    WV_SMOOTH_PSI2 = 8, WV_BENCH_ZERO = 14, WV_MULTI = 16, WV_MULTI_STRIDE = 11
+};
+
 struct mi_matrix_s {
     mi_addr_s* addr = nullptr;
     mi_dpcg_s dp; // buffers of a distributed PCG session (owned by the caller)
@@ -195,7 +216,18 @@ struct mi_matrix_s {
         *out = work[k]->p;
         return MI_OK;
     }
+    struct Slot { size_t k; double** out; };
+    int vecs(std::initializer_list<Slot> slots) { for (const Slot& v : slots) MICHK(vec(v.k, v.out)); return MI_OK; }   // several, in the order given
 };
+
+// the way into an extern "C" solver: arguments, bound coefficients, no PCG session open on the context (it owns the work vectors and the PcgState)
+static int solver_entry(const char* fn, const mi_matrix_s* m, bool args_ok, bool check_session = true)
+{
+    if (!m || !args_ok) return fail(MI_ERR_ARG, std::string(fn) + ": bad argument");
+    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
+    if (check_session && m->addr->ctx->session) return fail(MI_ERR_STATE, std::string(fn) + ": a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
+    return MI_OK;
+}
 
 // communicator hooks (comm.inc): with a communicator attached to the matrix every operator that reads the
 // coupled-patch neighbour values exchanges them itself and every global sum is all-reduced over the ranks
@@ -1176,13 +1208,13 @@ extern "C" int mi_matrix_set_ext(mi_matrix_t m, const double* ext)
     if (!ext) return fail(MI_ERR_ARG, "mi_matrix_set_ext: ext is NULL");
     HIPCHK(hipSetDevice(m->addr->ctx->device));
     double* v0;
-    MICHK(m->vec(0, &v0));
+    MICHK(m->vec(WV_OP_X, &v0));
     HIPCHK(hipMemcpyAsync(v0 + m->addr->L.nCells, ext, sizeof(double) * (size_t)nExt, hipMemcpyDeviceToDevice, m->addr->ctx->stream));
     return MI_OK;
 }
 
 namespace {
-// caller-order wrapper: x -> engine (work 0, keeps the ext tail), op -> work 1, -> caller
+// caller-order wrapper: x -> engine (WV_OP_X, keeps the ext tail), op -> WV_OP_Y, -> caller
 template <int OP>
 int caller_op(mi_matrix_s* m, bool trans, const double* x, const double* b, double* y)
 {
@@ -1194,14 +1226,14 @@ int caller_op(mi_matrix_s* m, bool trans, const double* x, const double* b, doub
         // ordered addressing: no permutation passes.  The input only has to be copied when the operator reads an ext
         // region (coupled patches whose neighbour values live behind the n_cells owned values of an engine vector).
         const double* xin = x;
-        if (x && a->L.nExt > 0) { MICHK(m->vec(0, &v0)); HIPCHK(hipMemcpyAsync(v0, x, sizeof(double) * (size_t)a->L.nCells, hipMemcpyDeviceToDevice, s)); xin = v0; }
+        if (x && a->L.nExt > 0) { MICHK(m->vec(WV_OP_X, &v0)); HIPCHK(hipMemcpyAsync(v0, x, sizeof(double) * (size_t)a->L.nCells, hipMemcpyDeviceToDevice, s)); xin = v0; }
         return tile_op<OP>(m, trans, xin, b, nullptr, y, 0.0);
     }
     constexpr bool fusable = (OP == OP_AMUL || OP == OP_RESIDUAL || OP == OP_H || OP == OP_SUMA || OP == OP_H1);
     if (fusable && a->ctx->fusePerm && !comm_remote(m) && a->ami.empty() && !a->compact) {
         // the permutation folded into the tile kernel: it gathers x[e2c] while staging and stores y[e2c] -- no separate passes.
-        // (The ext tail, if the mesh has coupled patches whose values the caller placed with mi_matrix_set_ext, lives in work 0.)
-        MICHK(m->vec(0, &v0));
+        // (The ext tail, if the mesh has coupled patches whose values the caller placed with mi_matrix_set_ext, lives in WV_OP_X.)
+        MICHK(m->vec(WV_OP_X, &v0));
         if (a->haloSrc.n != a->haloCell.n) {
             Table<int32_t> hc(a->haloCell.n), src(a->haloCell.n);
             HIPCHK(hipMemcpy(hc.data(), a->haloCell.p, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost));
@@ -1214,9 +1246,9 @@ int caller_op(mi_matrix_s* m, bool trans, const double* x, const double* b, doub
         m->callerX = nullptr; m->callerB = nullptr; m->callerY = nullptr;
         return rc;
     }
-    MICHK(m->vec(0, &v0)); MICHK(m->vec(1, &v1));
+    MICHK(m->vec(WV_OP_X, &v0)); MICHK(m->vec(WV_OP_Y, &v1));
     if (x) k_gather_perm<<<RG, RB, 0, s>>>(x, a->perm(), v0, a->L.nCells);
-    if (b) { MICHK(m->vec(2, &v2)); k_gather_perm<<<RG, RB, 0, s>>>(b, a->perm(), v2, a->L.nCells); }
+    if (b) { MICHK(m->vec(WV_OP_B, &v2)); k_gather_perm<<<RG, RB, 0, s>>>(b, a->perm(), v2, a->L.nCells); }
     MICHK(tile_op<OP>(m, trans, v0, v2, nullptr, v1, 0.0));
     k_scatter_perm<<<RG, RB, 0, s>>>(v1, a->perm(), y, a->L.nCells);
     HIPCHK(hipGetLastError());
@@ -1294,7 +1326,7 @@ extern "C" int mi_precondition(mi_matrix_t m, int kind, int transpose, const dou
         MICHK(ensure_rD(m));
         if (kind == MI_PRECOND_DIAGONAL && aligned16(rA) && aligned16(wA)) { k_mul<<<RG, RB, 0, s>>>(wA, m->rD.p, rA, a->L.nCells); HIPCHK(hipGetLastError()); return MI_OK; }
         // (the AINV tile pass stages x[haloCell] for every halo entry, ext entries included -- their values are never used, but
-        //  the caller's rA ends at n_cells: with an ext region the input goes through work vector 0 below, as caller_op does)
+        //  the caller's rA ends at n_cells: with an ext region the input goes through WV_OP_X below, as caller_op does)
         if (kind == MI_PRECOND_AINV && a->L.nExt == 0) return launch_tile<OP_AINV>(m, transpose != 0, rA, nullptr, m->rD.p, wA, 0.0, 0);
     }
     if (!a->identity && wA != rA && a->ctx->fusePerm) { // no permutation passes for the two preconditioners that are pointwise
@@ -1306,7 +1338,7 @@ extern "C" int mi_precondition(mi_matrix_t m, int kind, int transpose, const dou
             return MI_OK;
         }
     }
-    MICHK(m->vec(0, &v0)); MICHK(m->vec(1, &v1));
+    MICHK(m->vec(WV_OP_X, &v0)); MICHK(m->vec(WV_OP_Y, &v1));
     k_gather_perm<<<RG, RB, 0, s>>>(rA, a->perm(), v0, a->L.nCells);
     if (kind == MI_PRECOND_NONE) {
         HIPCHK(hipMemcpyAsync(v1, v0, sizeof(double) * (size_t)a->L.nCells, hipMemcpyDeviceToDevice, s));
@@ -1329,7 +1361,7 @@ extern "C" int mi_jacobi_smooth(mi_matrix_t m, double omega, double* psi, const 
     HIPCHK(hipSetDevice(a->ctx->device));
     hipStream_t s = a->ctx->stream;
     double *v0, *v1, *v2;
-    MICHK(m->vec(0, &v0)); MICHK(m->vec(1, &v1)); MICHK(m->vec(2, &v2));
+    MICHK(m->vec(WV_OP_X, &v0)); MICHK(m->vec(WV_OP_Y, &v1)); MICHK(m->vec(WV_OP_B, &v2));
     if (a->identity && a->L.nExt == 0) { // ordered addressing, no ext region: ping-pong between the caller's psi and one work vector
         double *cur = psi, *nxt = v1;
         for (int sw = 0; sw < n_sweeps; ++sw) { MICHK(tile_op<OP_JACOBI>(m, false, cur, source, nullptr, nxt, omega)); double* t = cur; cur = nxt; nxt = t; }
@@ -1411,7 +1443,7 @@ extern "C" int mi_jacobi_smooth_engine(mi_matrix_t m, double omega, double* psi_
     HIPCHK(hipSetDevice(a->ctx->device));
     hipStream_t s = a->ctx->stream;
     double* scratch;
-    MICHK(m->vec(1, &scratch));
+    MICHK(m->vec(WV_OP_Y, &scratch));
     double *cur = psi_e, *nxt = scratch;
     for (int sw = 0; sw < n_sweeps; ++sw) {
         if (a->L.nExt > 0 && sw > 0 && !comm_remote(m))
@@ -1449,29 +1481,25 @@ int norm_factor_engine(mi_matrix_s* m, const double* psi_e, const double* src_e,
 } // namespace
 extern "C" int mi_norm_factor(mi_matrix_t m, const double* psi, const double* source, const double* Apsi, double* out)
 {
-    if (!m || !psi || !source || !Apsi || !out) return fail(MI_ERR_ARG, "mi_norm_factor: bad argument");
-    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
-    if (m->addr->ctx->session) return fail(MI_ERR_STATE, "mi_norm_factor: a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
+    MICHK(solver_entry("mi_norm_factor", m, psi && source && Apsi && out));
     mi_addr_s* a = m->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
     hipStream_t s = a->ctx->stream;
     const int64_t n = a->L.nCells;
-    double *v0, *v1, *v2, *v3;
-    MICHK(m->vec(0, &v0)); MICHK(m->vec(1, &v1)); MICHK(m->vec(2, &v2)); MICHK(m->vec(3, &v3));
-    k_gather_perm<<<RG, RB, 0, s>>>(Apsi, a->perm(), v0, n);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), v2, n);
-    k_gather_perm<<<RG, RB, 0, s>>>(psi, a->perm(), v3, n);
-    return norm_factor_engine(m, v3, v2, v0, v1, out);
+    double *ApsiE, *sumA, *srcE, *psiE;
+    MICHK(m->vecs({{WV_NF_APSI, &ApsiE}, {WV_NF_SUMA, &sumA}, {WV_NF_SRC, &srcE}, {WV_NF_PSI, &psiE}}));
+    k_gather_perm<<<RG, RB, 0, s>>>(Apsi, a->perm(), ApsiE, n);
+    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), srcE, n);
+    k_gather_perm<<<RG, RB, 0, s>>>(psi, a->perm(), psiE, n);
+    return norm_factor_engine(m, psiE, srcE, ApsiE, sumA, out);
 }
 extern "C" int mi_norm_factor_engine(mi_matrix_t m, const double* psi_e, const double* source_e, const double* Apsi_e, double* out)
 {
-    if (!m || !psi_e || !source_e || !Apsi_e || !out) return fail(MI_ERR_ARG, "mi_norm_factor_engine: bad argument");
-    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
-    if (m->addr->ctx->session) return fail(MI_ERR_STATE, "mi_norm_factor_engine: a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
+    MICHK(solver_entry("mi_norm_factor_engine", m, psi_e && source_e && Apsi_e && out));
     HIPCHK(hipSetDevice(m->addr->ctx->device));
-    double* v1;
-    MICHK(m->vec(1, &v1));
-    return norm_factor_engine(m, psi_e, source_e, Apsi_e, v1, out);
+    double* sumA;
+    MICHK(m->vec(WV_NF_SUMA, &sumA));
+    return norm_factor_engine(m, psi_e, source_e, Apsi_e, sumA, out);
 }
 
 namespace {
@@ -1509,9 +1537,9 @@ int reduce_sync_fwd(mi_matrix_s* m, const double* a, double* out) { return reduc
 
 // common start of every solver (PCG.C:91-121 and siblings): given psi_e, src_e:
 //   wA = A psi ; rA = src - wA ; normFactor ; initial residual ; convergence test.
-// Leaves the result in the device PcgState; tmp is scratch (the reference passes pA).
+// Leaves the result in the device PcgState.
 int solve_prologue(mi_matrix_s* m, const mi_solver_controls* ctl, const double* psi_e, const double* src_e,
-                   double* wA, double* rA, double* tmp, int histLen)
+                   double* wA, double* rA, int histLen)
 {
     mi_addr_s* a = m->addr;
     mi_ctx_s* c = a->ctx;
@@ -1524,7 +1552,6 @@ int solve_prologue(mi_matrix_s* m, const mi_solver_controls* ctl, const double* 
     h.tolerance = ctl->tolerance; h.relTol = ctl->relTol; h.maxIter = ctl->maxIter; h.minIter = ctl->minIter;
     *c->hostState = h;
     HIPCHK(hipMemcpyAsync(c->state.p, c->hostState, sizeof(PcgState), hipMemcpyHostToDevice, s));
-    (void)tmp;
     if (c->fusePrologue) {
         // ONE pass over the coefficients: wA = A psi, rA = source - wA and -- when the coefficients were re-bound since the last solve, as in
         // every equation of a time step -- sumA (OP_PROLOGUE: the Amul's and the sumA pass's chains side by side, same bits); then the
@@ -1588,20 +1615,84 @@ int fetch_state(mi_ctx_s* c)
     return MI_OK;
 }
 
-void fill_perf(const PcgState& h, mi_solver_perf* p)
+template <class State>   // PcgState, or the host-stepped loops' HostPerf
+void fill_perf(const State& h, mi_solver_perf* p)
 {
     p->initialResidual = h.initialResidual; p->finalResidual = h.finalResidual; p->normFactor = h.normFactor;
     p->nIterations = h.nIterations; p->converged = h.converged; p->singular = h.singular; p->reserved = 0;
 }
 
-int copy_hist(mi_matrix_s* m, double* hist_host, int len, int nIter)
+// residual history -> host: entries 0 .. nIter, as many as both buffers hold (sync = false: the caller synchronises the stream)
+int copy_hist(hipStream_t s, const double* hist_dev, int dev_len, double* hist_host, int len, int nIter, bool sync = true)
 {
     if (!hist_host || len <= 0) return MI_OK;
-    int cnt = nIter + 1; if (cnt > len) cnt = len; if (cnt > m->histLen) cnt = m->histLen;
+    int cnt = nIter + 1; if (cnt > len) cnt = len; if (cnt > dev_len) cnt = dev_len;
     if (cnt > 0) {
-        HIPCHK(hipMemcpyAsync(hist_host, m->hist.p, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, m->addr->ctx->stream));
-        HIPCHK(hipStreamSynchronize(m->addr->ctx->stream));
+        HIPCHK(hipMemcpyAsync(hist_host, hist_dev, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
+        if (sync) HIPCHK(hipStreamSynchronize(s));
     }
+    return MI_OK;
+}
+int copy_hist(mi_matrix_s* m, double* hist_host, int len, int nIter) { return copy_hist(m->addr->ctx->stream, m->hist.p, m->histLen, hist_host, len, nIter); }
+
+// ---- the frame every solver shares (solver_entry: above): the work vectors by name (numbers and overlaps: WorkVec) ...
+struct PcgVecs { double *psi, *src, *pA, *wA, *rA; };
+struct BicgVecs : PcgVecs { double *pT, *wT, *rT; };
+struct StabVecs { double *psi, *src, *pA, *yA, *rA, *AyA, *sA, *zA, *tA, *rA0; };
+int work_vecs(mi_matrix_s* m, PcgVecs& v) { return m->vecs({{WV_PSI, &v.psi}, {WV_SRC, &v.src}, {WV_PA, &v.pA}, {WV_WA, &v.wA}, {WV_RA, &v.rA}}); }
+int work_vecs(mi_matrix_s* m, BicgVecs& v) { MICHK(work_vecs(m, static_cast<PcgVecs&>(v))); return m->vecs({{WV_PT, &v.pT}, {WV_WT, &v.wT}, {WV_RT, &v.rT}}); }
+int work_vecs(mi_matrix_s* m, StabVecs& v) { return m->vecs({{WV_PSI, &v.psi}, {WV_SRC, &v.src}, {WV_PA, &v.pA}, {WV_STAB_YA, &v.yA}, {WV_RA, &v.rA},
+                                                             {WV_STAB_AYA, &v.AyA}, {WV_STAB_SA, &v.sA}, {WV_STAB_ZA, &v.zA}, {WV_STAB_TA, &v.tA}, {WV_STAB_RA0, &v.rA0}}); }
+// ... the way into a solve: the work vectors, then the caller's psi and source in engine order
+template <class Vecs>
+int stage_in(mi_matrix_s* m, Vecs& v, const double* psi, const double* source)
+{
+    mi_addr_s* a = m->addr;
+    MICHK(work_vecs(m, v));
+    k_gather_perm<<<RG, RB, 0, a->ctx->stream>>>(psi, a->perm(), v.psi, a->L.nCells);
+    k_gather_perm<<<RG, RB, 0, a->ctx->stream>>>(source, a->perm(), v.src, a->L.nCells);
+    return MI_OK;
+}
+
+// tile launches of a device-resident loop read PcgState::done and exit past convergence while one of these lives
+struct GateDone { mi_matrix_s* m; explicit GateDone(mi_matrix_s* mm) : m(mm) { m->gateDone = true; } ~GateDone() { m->gateDone = false; } };
+// iteration bodies run for it = 0 .. maxIter inclusive at most (nIterations++ < maxIter, PCG.C:197-204), or minIter more if that is above maxIter
+int iter_limit(const mi_solver_controls* ctl) { return ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0); }
+
+// The host side of every device-resident solver loop: enqueue a batch of iteration bodies (enqueue(nb) also advances `it` by nb),
+// fetch the state, check the peer windows (none without a communicator), until done() or `it` passes the limit.  Batches grow first,
+// 2 first ... up to MI_PCG_BATCH: a solve that converges in a few iterations (every momentum predictor) does not pay for a full batch
+// of launches that exit at their first instruction.  The caller has fetched the state the prologue left, or done() says no until fetch() ran.
+template <class Enqueue, class Fetch, class Done>
+int drive_batches(mi_matrix_s* m, const mi_solver_controls* ctl, const int& it, int first, Enqueue enqueue, Fetch fetch, Done done)
+{
+    const int batch = m->addr->ctx->pcgBatch, limit = iter_limit(ctl);
+    int nb = batch < first ? batch : first;
+    while (!done() && it <= limit) {
+        MICHK(enqueue(nb));
+        MICHK(fetch());
+        MICHK(peer_check(m));
+        nb = nb * 2 > batch ? batch : nb * 2;
+    }
+    return MI_OK;
+}
+template <class Enqueue>   // ... polling the context's one PcgState
+int drive_batches(mi_matrix_s* m, const mi_solver_controls* ctl, const int& it, int first, Enqueue enqueue)
+{
+    mi_ctx_s* c = m->addr->ctx;
+    return drive_batches(m, ctl, it, first, enqueue, [c] { return fetch_state(c); }, [c] { return c->hostState->done != 0; });
+}
+
+// ... and the way out (finish_host is the host-stepped loops'): what the last iteration still owes (flush), psi back in caller order, the state the loop fetched, the history
+int finish_device(mi_matrix_s* m, const double* psi_e, double* psi_out, mi_solver_perf* perf, double* hist_host, int hist_len, int (*flush)(mi_matrix_s*) = nullptr)
+{
+    mi_addr_s* a = m->addr; mi_ctx_s* c = a->ctx;
+    if (flush) MICHK(flush(m));
+    k_scatter_perm<<<RG, RB, 0, c->stream>>>(psi_e, a->perm(), psi_out, a->L.nCells);
+    HIPCHK(hipGetLastError());
+    if (perf) fill_perf(*c->hostState, perf);
+    MICHK(copy_hist(m, hist_host, hist_len, c->hostState->nIterations));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return MI_OK;
 }
 
@@ -1638,15 +1729,16 @@ int pcg_enqueue(mi_matrix_s* m, int it0, int count, int precond, int evStride) /
     mi_ctx_s* c = a->ctx;
     hipStream_t s = c->stream;
     const int64_t n = a->L.nCells;
-    double *psi, *src, *pA, *wA, *rA;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &wA)); MICHK(m->vec(7, &rA));
+    PcgVecs v;
+    MICHK(work_vecs(m, v));
+    double *psi = v.psi, *pA = v.pA, *wA = v.wA, *rA = v.rA;
     double* P1 = c->partial.p; double* P2 = c->partial.p + RG; double* P3 = c->partial.p + 2 * RG;
     if (precond != MI_PRECOND_NONE) MICHK(ensure_rD(m));
     if (m->tilePartial.n < (size_t)a->L.nTiles) MICHK(m->tilePartial.alloc((size_t)a->L.nTiles));
     const bool fuse = c->fuseFinal && precond != MI_PRECOND_AINV;
     const int defer = (c->deferPsi && !fuse) ? 1 : 0; // (the fused convergence test has no per-iteration k_pcg_final to record the added psi term)
     double* psiD = defer ? psi : nullptr;
-    struct Gate { mi_matrix_s* m; explicit Gate(mi_matrix_s* mm) : m(mm) { m->gateDone = true; } ~Gate() { m->gateDone = false; } } gate(m);
+    GateDone gate(m);
     // round 6: k_pcg_update_psi_r(it) + k_pcg_final(it) + k_pcg_update_p(it + 1) as one launch that keeps rD o rA on the chip
     // (pcg_fused.inc).  Not under graph capture (it0 < 0: the launch carries the iteration number and its barrier generation).
     bool fusedRP = it0 >= 0 && pcg_fused_rp_usable(m, precond);
@@ -1703,13 +1795,25 @@ int pcg_enqueue(mi_matrix_s* m, int it0, int count, int precond, int evStride) /
     return MI_OK;
 }
 
+// diagonal / none: the wArA partials of iteration 0 (later iterations get them from k_pcg_update_psi_r), global like every other sum
+int pcg_first_dot(mi_matrix_s* m, int precond, const PcgVecs& v)
+{
+    mi_ctx_s* c = m->addr->ctx;
+    if (precond != MI_PRECOND_DIAGONAL && precond != MI_PRECOND_NONE) return MI_OK;
+    if (precond == MI_PRECOND_DIAGONAL) MICHK(ensure_rD(m));
+    if (precond == MI_PRECOND_DIAGONAL) k_pcg_precond_dot<true><<<RG, RB, 0, c->stream>>>(c->state.p, m->rD.p, v.rA, v.wA, m->addr->L.nCells, c->partial.p);
+    else k_pcg_precond_dot<false><<<RG, RB, 0, c->stream>>>(c->state.p, nullptr, v.rA, v.wA, m->addr->L.nCells, c->partial.p);
+    HIPCHK(hipGetLastError());
+    return globalize(m, c->partial.p);
+}
+
 // end of a pcg_enqueue-driven solve: the psi term the last iteration still owes (deferred psi update)
 int pcg_flush(mi_matrix_s* m)
 {
     mi_ctx_s* c = m->addr->ctx;
     if (!c->deferPsi) return MI_OK;
     double *psi, *pA;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(5, &pA));
+    MICHK(m->vecs({{WV_PSI, &psi}, {WV_PA, &pA}}));
     k_pcg_flush_psi<<<RG, RB, 0, c->stream>>>(c->state.p, pA, psi, m->addr->L.nCells);
     k_pcg_flush_mark<<<1, 1, 0, c->stream>>>(c->state.p);
     HIPCHK(hipGetLastError());
@@ -1729,20 +1833,10 @@ extern "C" int mi_pcg_begin(mi_matrix_t m, const double* psi0, const double* sou
         return fail(MI_ERR_STATE, "mi_pcg_begin: another matrix has a PCG session open on this context (one session per context: it owns the solver scratch)");
     mi_addr_s* a = m->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
-    hipStream_t s = a->ctx->stream;
-    double *psi, *src, *pA, *wA, *rA;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &wA)); MICHK(m->vec(7, &rA));
-    k_gather_perm<<<RG, RB, 0, s>>>(psi0, a->perm(), psi, a->L.nCells);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
-    MICHK(solve_prologue(m, ctl, psi, src, wA, rA, pA, history_len));
-    // wArA partials of iteration 0 (later iterations get them from k_pcg_update_psi_r)
-    if (precond == MI_PRECOND_DIAGONAL) {
-        MICHK(ensure_rD(m));
-        k_pcg_precond_dot<true><<<RG, RB, 0, s>>>(a->ctx->state.p, m->rD.p, rA, wA, a->L.nCells, a->ctx->partial.p);
-    } else if (precond == MI_PRECOND_NONE) {
-        k_pcg_precond_dot<false><<<RG, RB, 0, s>>>(a->ctx->state.p, nullptr, rA, wA, a->L.nCells, a->ctx->partial.p);
-    }
-    HIPCHK(hipGetLastError());
+    PcgVecs v;
+    MICHK(stage_in(m, v, psi0, source));
+    MICHK(solve_prologue(m, ctl, v.psi, v.src, v.wA, v.rA, history_len));
+    MICHK(pcg_first_dot(m, precond, v));
     m->pcgIt = 0; m->pcgPrecond = precond; m->pcgActive = true; m->pcgPReady = false; a->ctx->session = m;
     return MI_OK;
 }
@@ -1791,7 +1885,7 @@ extern "C" int mi_pcg_end(mi_matrix_t m, double* psi_out, mi_solver_perf* perf, 
     mi_addr_s* a = m->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
     double* psi;
-    MICHK(m->vec(3, &psi));
+    MICHK(m->vec(WV_PSI, &psi));
     MICHK(pcg_flush(m));
     if (psi_out) k_scatter_perm<<<RG, RB, 0, a->ctx->stream>>>(psi, a->perm(), psi_out, a->L.nCells);
     HIPCHK(hipGetLastError());
@@ -1805,17 +1899,12 @@ extern "C" int mi_pcg_end(mi_matrix_t m, double* psi_out, mi_solver_perf* perf, 
 extern "C" int mi_pcg_solve(mi_matrix_t m, double* psi, const double* source, const mi_solver_controls* ctl,
                             int precond, mi_solver_perf* perf, double* hist_host, int32_t hist_len)
 {
-    if (!m || !psi || !source || !ctl) return fail(MI_ERR_ARG, "mi_pcg_solve: bad argument");
-    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
+    MICHK(solver_entry("mi_pcg_solve", m, psi && source && ctl, !(m && comm_attached(m))));   // (the attached solve never opens a session)
     if (comm_attached(m)) return pcg_solve_attached(m, psi, source, ctl, precond, perf, hist_host, hist_len);
-    const int histLen = ctl->maxIter + 2;
-    if (m->addr->ctx->session) return fail(MI_ERR_STATE, "mi_pcg_solve: a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
-    MICHK(mi_pcg_begin(m, psi, source, ctl, precond, histLen));
+    MICHK(mi_pcg_begin(m, psi, source, ctl, precond, ctl->maxIter + 2));
     mi_ctx_s* c = m->addr->ctx;
     struct SessionGuard { mi_matrix_s* m; ~SessionGuard() { if (m->pcgActive) { m->pcgActive = false; m->addr->ctx->session = nullptr; } } } sessionGuard{m};
     MICHK(fetch_state(c));
-    const int batch = m->addr->ctx->pcgBatch;
-    const int limit = ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0);
     // Launch-bound regime (small meshes: a 32^3 cavity iteration is five ~5 us launches): one batch of iterations is
     // captured ONCE into a hipGraph -- the iteration counter lives in PcgState, so the kernel arguments never change --
     // and replayed until the device reports done.  Same kernels, same order: results are bit-identical.
@@ -1823,7 +1912,8 @@ extern "C" int mi_pcg_solve(mi_matrix_t m, double* psi, const double* source, co
     const bool useGraph = !pcg_persist_usable(m, precond) && (precond == MI_PRECOND_DIAGONAL || precond == MI_PRECOND_NONE) && !c->fuseFinal &&
                           (wantGraph == 1 || (wantGraph < 0 && m->addr->L.nCells <= 4000000));
     if (useGraph && !c->hostState->done) {
-        double* psiE; MICHK(m->vec(3, &psiE));
+        const int batch = c->pcgBatch, limit = iter_limit(ctl);
+        double* psiE; MICHK(m->vec(WV_PSI, &psiE));
         auto& K = m->pcgGraphKey;
         if (!m->pcgGraph || K.precond != precond || K.batch != batch || K.histLen != m->histLen || K.hist != m->hist.p || K.psi != psiE) {
             if (m->pcgGraph) { (void)hipGraphExecDestroy(m->pcgGraph); m->pcgGraph = nullptr; }
@@ -1848,15 +1938,8 @@ extern "C" int mi_pcg_solve(mi_matrix_t m, double* psi, const double* source, co
         }
         return mi_pcg_end(m, psi, perf, hist_host, hist_len);
     }
-    // bodies run for it = 0 .. maxIter inclusive at most (nIterations++ < maxIter, PCG.C:197-204)
-    // batches grow 2, 4, 8 ... batch: a solve that converges in a few iterations (every momentum predictor) does not pay
-    // for a full batch of launches that exit at their first instruction; a long solve polls `done` 3 times more in total
-    int nb = batch < 2 ? batch : 2;
-    while (!c->hostState->done && m->pcgIt <= limit) {
-        MICHK(mi_pcg_iterate(m, nb, nullptr));
-        MICHK(fetch_state(c));
-        nb = nb * 2 > batch ? batch : nb * 2;
-    }
+    // batches of 2, 4, 8 ... through mi_pcg_iterate: the persistent kernel and the fused launch keep their hand-over rules (pcgIt, pcgPReady)
+    MICHK(drive_batches(m, ctl, m->pcgIt, 2, [m](int nb) { return mi_pcg_iterate(m, nb, nullptr); }));
     return mi_pcg_end(m, psi, perf, hist_host, hist_len);
 }
 
@@ -1980,6 +2063,7 @@ struct HostPerf {
     double initialResidual = 0, finalResidual = 0, normFactor = 0;
     int nIterations = 0, converged = 0, singular = 0;
     double tolerance, relTol; int maxIter, minIter;
+    void controls(const mi_solver_controls* ctl) { tolerance = ctl->tolerance; relTol = ctl->relTol; maxIter = ctl->maxIter; minIter = ctl->minIter; }
     bool checkConvergence()
     {
         converged = (finalResidual < tolerance) || (relTol > SP_SMALL && finalResidual < relTol * initialResidual);
@@ -1995,25 +2079,24 @@ int finish_host(mi_matrix_s* m, const HostPerf& hp, const Table<double>& hist, d
     k_scatter_perm<<<RG, RB, 0, a->ctx->stream>>>(psi_e, a->perm(), psi_out, a->L.nCells);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(a->ctx->stream));
-    if (perf) {
-        perf->initialResidual = hp.initialResidual; perf->finalResidual = hp.finalResidual; perf->normFactor = hp.normFactor;
-        perf->nIterations = hp.nIterations; perf->converged = hp.converged; perf->singular = hp.singular; perf->reserved = 0;
-    }
+    if (perf) fill_perf(hp, perf);
     if (hist_host) for (int i = 0; i < hist_len && i < (int)hist.size(); ++i) hist_host[i] = hist[(size_t)i];
     return MI_OK;
 }
 
 int host_prologue(mi_matrix_s* m, const mi_solver_controls* ctl, const double* psi_e, const double* src_e,
-                  double* wA, double* rA, double* tmp, HostPerf& hp, Table<double>& hist)
+                  double* wA, double* rA, HostPerf& hp, Table<double>& hist)
 {
-    MICHK(solve_prologue(m, ctl, psi_e, src_e, wA, rA, tmp, 1));
+    MICHK(solve_prologue(m, ctl, psi_e, src_e, wA, rA, 1));
     MICHK(fetch_state(m->addr->ctx));
     const PcgState& h = *m->addr->ctx->hostState;
-    hp.tolerance = ctl->tolerance; hp.relTol = ctl->relTol; hp.maxIter = ctl->maxIter; hp.minIter = ctl->minIter;
+    hp.controls(ctl);
     hp.normFactor = h.normFactor; hp.initialResidual = h.initialResidual; hp.finalResidual = h.finalResidual;
     hist.clear(); hist.push_back(hp.initialResidual);
     return MI_OK;
 }
+// (the GAMG solve loop still hands over a scratch vector in seventh place: the text of gamg_engine.inc is hashed into the traffic record)
+int host_prologue(mi_matrix_s* m, const mi_solver_controls* ctl, const double* psi_e, const double* src_e, double* wA, double* rA, double*, HostPerf& hp, Table<double>& hist) { return host_prologue(m, ctl, psi_e, src_e, wA, rA, hp, hist); }
 } // namespace
 
 namespace {
@@ -2023,9 +2106,9 @@ int tile_pair(mi_matrix_s* m, bool ainv, const double* x0, const double* x1, dou
 int multi_exchange(mi_matrix_s* m, int nv, double* const* xs);   // multi.inc: one halo exchange for several operand vectors
 // enqueue PBiCG iteration bodies it0 .. it0+count-1 (no host sync): precondition both residuals (+ fused sum wA.rT),
 // update pA/pT, Amul, Tmul, sum wA.pT, update psi/rA/rT (+ sum|rA|), convergence test
-int bicg_enqueue(mi_matrix_s* m, int it0, int count, int precond, double* psi, double* pA, double* wA, double* rA,
-                 double* pT, double* wT, double* rT)
+int bicg_enqueue(mi_matrix_s* m, int it0, int count, int precond, const BicgVecs& v)
 {
+    double *psi = v.psi, *pA = v.pA, *wA = v.wA, *rA = v.rA, *pT = v.pT, *wT = v.wT, *rT = v.rT;
     mi_addr_s* a = m->addr;
     mi_ctx_s* c = a->ctx;
     hipStream_t s = c->stream;
@@ -2033,7 +2116,7 @@ int bicg_enqueue(mi_matrix_s* m, int it0, int count, int precond, double* psi, d
     double* P1 = c->partial.p; double* P2 = c->partial.p + RG; double* P3 = c->partial.p + 2 * RG;
     if (precond != MI_PRECOND_NONE) MICHK(ensure_rD(m));
     if (m->tilePartial.n < (size_t)a->L.nTiles) MICHK(m->tilePartial.alloc((size_t)a->L.nTiles));
-    struct Gate { mi_matrix_s* m; explicit Gate(mi_matrix_s* mm) : m(mm) { m->gateDone = true; } ~Gate() { m->gateDone = false; } } gate(m);
+    GateDone gate(m);
     for (int it = it0; it < it0 + count; ++it) {
         // the plain and the transposed pass share one staging of the coefficients; on a decomposed case (round 4) pA and pT also
         // share ONE halo exchange (cyclicAMI patches are interpolated per operand inside tile_op: they keep the separate passes)
@@ -2079,32 +2162,16 @@ int pbicg_solve_device(mi_matrix_s* m, double* psi_io, const double* source, con
     mi_ctx_s* c = a->ctx;
     hipStream_t s = c->stream;
     const int64_t n = a->L.nCells;
-    double *psi, *src, *pA, *wA, *rA, *pT, *wT, *rT;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &wA)); MICHK(m->vec(7, &rA));
-    MICHK(m->vec(8, &pT)); MICHK(m->vec(9, &wT)); MICHK(m->vec(10, &rT));
-    k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
-    const int histLen = ctl->maxIter + 2;
-    MICHK(solve_prologue(m, ctl, psi, src, wA, rA, pA, histLen));     // wA = A psi, rA = src - wA, normFactor, first test
-    MICHK(tile_op<OP_AMUL>(m, true, psi, nullptr, nullptr, wT, 0.0));
-    k_sub<<<RG, RB, 0, s>>>(rT, src, wT, n);
+    BicgVecs v;
+    MICHK(stage_in(m, v, psi_io, source));
+    MICHK(solve_prologue(m, ctl, v.psi, v.src, v.wA, v.rA, ctl->maxIter + 2));     // wA = A psi, rA = src - wA, normFactor, first test
+    MICHK(tile_op<OP_AMUL>(m, true, v.psi, nullptr, nullptr, v.wT, 0.0));
+    k_sub<<<RG, RB, 0, s>>>(v.rT, v.src, v.wT, n);
     MICHK(fetch_state(c));
     c->stats[7] += 1;   // mi_ctx_stat(7): solves of pbicg_solve_device
-    const int batch = m->addr->ctx->pcgBatch;
-    int it = 0, nb = batch < 2 ? batch : 2;   // growing batches, as in mi_pcg_solve
-    while (!c->hostState->done && it <= ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0)) {
-        MICHK(bicg_enqueue(m, it, nb, precond, psi, pA, wA, rA, pT, wT, rT));
-        it += nb;
-        MICHK(fetch_state(c));
-        MICHK(peer_check(m));
-        nb = nb * 2 > batch ? batch : nb * 2;
-    }
-    k_scatter_perm<<<RG, RB, 0, s>>>(psi, a->perm(), psi_io, a->L.nCells);
-    HIPCHK(hipGetLastError());
-    if (perf) fill_perf(*c->hostState, perf);
-    MICHK(copy_hist(m, hist_host, hist_len, c->hostState->nIterations));
-    HIPCHK(hipStreamSynchronize(s));
-    return MI_OK;
+    int it = 0;
+    MICHK(drive_batches(m, ctl, it, 2, [&](int nb) { it += nb; return bicg_enqueue(m, it - nb, nb, precond, v); }));
+    return finish_device(m, v.psi, psi_io, perf, hist_host, hist_len);
 }
 } // namespace
 
@@ -2116,9 +2183,7 @@ bool pbicg_single_via_multi(const mi_matrix_s* m);   // multi.inc
 extern "C" int mi_pbicg_solve(mi_matrix_t m, double* psi_io, const double* source, const mi_solver_controls* ctl,
                               int precond, mi_solver_perf* perf, double* hist_host, int32_t hist_len)
 {
-    if (!m || !psi_io || !source || !ctl) return fail(MI_ERR_ARG, "mi_pbicg_solve: bad argument");
-    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
-    if (m->addr->ctx->session) return fail(MI_ERR_STATE, "mi_pbicg_solve: a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
+    MICHK(solver_entry("mi_pbicg_solve", m, psi_io && source && ctl));
     mi_addr_s* a = m->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
     if (m->addr->ctx->pbicgHostStepped == 0) { // also with a communicator attached: the loop all-reduces its sums on the device (globalize)
@@ -2131,14 +2196,12 @@ extern "C" int mi_pbicg_solve(mi_matrix_t m, double* psi_io, const double* sourc
     }
     hipStream_t s = a->ctx->stream;
     const int64_t n = a->L.nCells;
-    double *psi, *src, *pA, *wA, *rA, *pT, *wT, *rT;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &wA)); MICHK(m->vec(7, &rA));
-    MICHK(m->vec(8, &pT)); MICHK(m->vec(9, &wT)); MICHK(m->vec(10, &rT));
-    k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
+    BicgVecs v;
+    MICHK(stage_in(m, v, psi_io, source));
+    double *psi = v.psi, *src = v.src, *pA = v.pA, *wA = v.wA, *rA = v.rA, *pT = v.pT, *wT = v.wT, *rT = v.rT;
     HostPerf hp; Table<double> hist;
     a->ctx->stats[8] += 1;   // mi_ctx_stat(8): host-stepped PBiCG solves
-    MICHK(host_prologue(m, ctl, psi, src, wA, rA, pA, hp, hist));
+    MICHK(host_prologue(m, ctl, psi, src, wA, rA, hp, hist));
     MICHK(tile_op<OP_AMUL>(m, true, psi, nullptr, nullptr, wT, 0.0));
     k_sub<<<RG, RB, 0, s>>>(rT, src, wT, n);
     double wArT = SP_GREAT, wArTold = wArT;
@@ -2175,15 +2238,15 @@ extern "C" int mi_pbicg_solve(mi_matrix_t m, double* psi_io, const double* sourc
 }
 
 namespace {
-int stab_enqueue(mi_matrix_s* m, int it0, int count, int precond, bool quirk, double* psi, double* pA, double* yA, double* rA,
-                 double* AyA, double* sA, double* zA, double* tA, double* rA0)
+int stab_enqueue(mi_matrix_s* m, int it0, int count, int precond, bool quirk, const StabVecs& v)
 {
+    double *psi = v.psi, *pA = v.pA, *yA = v.yA, *rA = v.rA, *AyA = v.AyA, *sA = v.sA, *zA = v.zA, *tA = v.tA, *rA0 = v.rA0;
     mi_addr_s* a = m->addr;
     mi_ctx_s* c = a->ctx;
     hipStream_t s = c->stream;
     const int64_t n = a->L.nCells;
     double* P1 = c->partial.p; double* P2 = c->partial.p + RG; double* P3 = c->partial.p + 2 * RG; double* P4 = c->partial.p + 3 * RG;
-    struct Gate { mi_matrix_s* m; explicit Gate(mi_matrix_s* mm) : m(mm) { m->gateDone = true; } ~Gate() { m->gateDone = false; } } gate(m);
+    GateDone gate(m);
     for (int it = it0; it < it0 + count; ++it) {
         k_reduce<RED_PROD><<<RG, RB, 0, s>>>(rA0, rA, n, P1);
         MICHK(globalize(m, P1));
@@ -2217,59 +2280,39 @@ int pbicgstab_solve_device(mi_matrix_s* m, double* psi_io, const double* source,
     hipStream_t s = c->stream;
     const int64_t n = a->L.nCells;
     if (c->partial.n < (size_t)4 * RG) return fail(MI_ERR_STATE, "partial buffer too small");
-    double *psi, *src, *pA, *yA, *rA, *AyA, *sA, *zA, *tA, *rA0;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &yA)); MICHK(m->vec(7, &rA));
-    MICHK(m->vec(8, &AyA)); MICHK(m->vec(9, &sA)); MICHK(m->vec(10, &zA)); MICHK(m->vec(11, &tA)); MICHK(m->vec(12, &rA0));
-    k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
+    StabVecs v;
+    MICHK(stage_in(m, v, psi_io, source));
     if (precond != MI_PRECOND_NONE) MICHK(ensure_rD(m));
-    const int histLen = ctl->maxIter + 2;
-    MICHK(solve_prologue(m, ctl, psi, src, yA, rA, pA, histLen));
-    HIPCHK(hipMemcpyAsync(rA0, rA, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    MICHK(solve_prologue(m, ctl, v.psi, v.src, v.yA, v.rA, ctl->maxIter + 2));
+    HIPCHK(hipMemcpyAsync(v.rA0, v.rA, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
     MICHK(fetch_state(c));
     c->stats[9] += 1;   // mi_ctx_stat(9): PBiCGStab solves of the device loop
-    const int batch = m->addr->ctx->pcgBatch;
-    int it = 0, nb = batch < 2 ? batch : 2;   // growing batches, as in mi_pcg_solve
-    while (!c->hostState->done && it <= ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0)) {
-        MICHK(stab_enqueue(m, it, nb, precond, replicate_quirk != 0, psi, pA, yA, rA, AyA, sA, zA, tA, rA0));
-        it += nb;
-        MICHK(fetch_state(c));
-        MICHK(peer_check(m));
-        nb = nb * 2 > batch ? batch : nb * 2;
-    }
+    int it = 0;
+    MICHK(drive_batches(m, ctl, it, 2, [&](int nb) { it += nb; return stab_enqueue(m, it - nb, nb, precond, replicate_quirk != 0, v); }));
     // mi_ctx_stat(11): k_stab_mid_final ended the solve -- it counts the half iteration but leaves st->it where the last
     // k_pcg_final (or k_solve_init) put it, one behind nIterations; every other exit leaves them equal or unconverged
     if (c->hostState->converged && c->hostState->it + 1 == c->hostState->nIterations) c->stats[11] += 1;
-    k_scatter_perm<<<RG, RB, 0, s>>>(psi, a->perm(), psi_io, a->L.nCells);
-    HIPCHK(hipGetLastError());
-    if (perf) fill_perf(*c->hostState, perf);
-    MICHK(copy_hist(m, hist_host, hist_len, c->hostState->nIterations));
-    HIPCHK(hipStreamSynchronize(s));
-    return MI_OK;
+    return finish_device(m, v.psi, psi_io, perf, hist_host, hist_len);
 }
 } // namespace
 
 extern "C" int mi_pbicgstab_solve(mi_matrix_t m, double* psi_io, const double* source, const mi_solver_controls* ctl,
                                   int precond, int replicate_quirk, mi_solver_perf* perf, double* hist_host, int32_t hist_len)
 {
-    if (!m || !psi_io || !source || !ctl) return fail(MI_ERR_ARG, "mi_pbicgstab_solve: bad argument");
-    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
-    if (m->addr->ctx->session) return fail(MI_ERR_STATE, "mi_pbicgstab_solve: a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
+    MICHK(solver_entry("mi_pbicgstab_solve", m, psi_io && source && ctl));
     mi_addr_s* a = m->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
     if (m->addr->ctx->pbicgHostStepped == 0)
         return pbicgstab_solve_device(m, psi_io, source, ctl, precond, replicate_quirk, perf, hist_host, hist_len);
     hipStream_t s = a->ctx->stream;
     const int64_t n = a->L.nCells;
-    double *psi, *src, *pA, *yA, *rA, *AyA, *sA, *zA, *tA, *rA0, *res1;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &yA)); MICHK(m->vec(7, &rA));
-    MICHK(m->vec(8, &AyA)); MICHK(m->vec(9, &sA)); MICHK(m->vec(10, &zA)); MICHK(m->vec(11, &tA)); MICHK(m->vec(12, &rA0));
-    MICHK(m->vec(13, &res1));
-    k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
+    StabVecs v; double* res1;
+    MICHK(stage_in(m, v, psi_io, source));
+    MICHK(m->vec(WV_STAB_RES1, &res1));
+    double *psi = v.psi, *src = v.src, *pA = v.pA, *yA = v.yA, *rA = v.rA, *AyA = v.AyA, *sA = v.sA, *zA = v.zA, *tA = v.tA, *rA0 = v.rA0;
     HostPerf hp; Table<double> hist;
     a->ctx->stats[10] += 1;   // mi_ctx_stat(10): host-stepped PBiCGStab solves
-    MICHK(host_prologue(m, ctl, psi, src, yA, rA, pA, hp, hist));
+    MICHK(host_prologue(m, ctl, psi, src, yA, rA, hp, hist));
     if (hp.minIter > 0 || !hp.checkConvergence()) {
         HIPCHK(hipMemcpyAsync(rA0, rA, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
         double rA0rA = 0, alpha = 0, omega = 0;
@@ -2321,20 +2364,16 @@ extern "C" int mi_pbicgstab_solve(mi_matrix_t m, double* psi_io, const double* s
 extern "C" int mi_smooth_solve(mi_matrix_t m, double* psi_io, const double* source, const mi_solver_controls* ctl,
                                double omega, int32_t n_sweeps, mi_solver_perf* perf, double* hist_host, int32_t hist_len)
 {
-    if (!m || !psi_io || !source || !ctl || n_sweeps == 0) return fail(MI_ERR_ARG, "mi_smooth_solve: bad argument");
-    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
-    if (m->addr->ctx->session) return fail(MI_ERR_STATE, "mi_smooth_solve: a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
+    MICHK(solver_entry("mi_smooth_solve", m, psi_io && source && ctl && n_sweeps != 0));
     mi_addr_s* a = m->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
-    hipStream_t s = a->ctx->stream;
-    double *psi, *src, *tmp, *wA, *rA, *psi2;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(4, &src)); MICHK(m->vec(5, &tmp)); MICHK(m->vec(6, &wA)); MICHK(m->vec(7, &rA));
-    MICHK(m->vec(8, &psi2));
-    k_gather_perm<<<RG, RB, 0, s>>>(psi_io, a->perm(), psi, a->L.nCells);
-    k_gather_perm<<<RG, RB, 0, s>>>(source, a->perm(), src, a->L.nCells);
+    PcgVecs v; double* psi2;   // (pA stays unused: the slot is taken as before)
+    MICHK(stage_in(m, v, psi_io, source));
+    MICHK(m->vec(WV_SMOOTH_PSI2, &psi2));
+    double *src = v.src, *rA = v.rA;
     HostPerf hp; Table<double> hist;
-    hp.tolerance = ctl->tolerance; hp.relTol = ctl->relTol; hp.maxIter = ctl->maxIter; hp.minIter = ctl->minIter;
-    double *cur = psi, *nxt = psi2;
+    hp.controls(ctl);
+    double *cur = v.psi, *nxt = psi2;
     auto sweeps = [&](int cnt) -> int {
         for (int sw = 0; sw < cnt; ++sw) {
             MICHK(tile_op<OP_JACOBI>(m, false, cur, src, nullptr, nxt, omega));
@@ -2346,7 +2385,7 @@ extern "C" int mi_smooth_solve(mi_matrix_t m, double* psi_io, const double* sour
         MICHK(sweeps(-n_sweeps));
         hp.nIterations -= n_sweeps;
     } else {
-        MICHK(host_prologue(m, ctl, psi, src, wA, rA, tmp, hp, hist));
+        MICHK(host_prologue(m, ctl, v.psi, src, v.wA, rA, hp, hist));
         if (hp.minIter > 0 || !hp.checkConvergence()) {
             do {
                 MICHK(sweeps(n_sweeps));
@@ -2390,7 +2429,7 @@ extern "C" int mi_bench_amul(mi_matrix_t m, int32_t reps, float* ms_out)
     mi_ctx_s* c = m->addr->ctx;
     HIPCHK(hipSetDevice(c->device));
     double *x, *y;
-    MICHK(m->vec(5, &x)); MICHK(m->vec(6, &y));
+    MICHK(m->vecs({{WV_PA, &x}, {WV_WA, &y}}));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     for (int i = 0; i < reps; ++i) MICHK(launch_tile<OP_AMUL>(m, false, x, nullptr, nullptr, y, 0.0, 0));
     HIPCHK(hipEventRecord(c->ev1, c->stream));
@@ -2406,7 +2445,7 @@ extern "C" int mi_bench_pcg_iters(mi_matrix_t m, const double* source, int32_t i
     HIPCHK(hipSetDevice(c->device));
     mi_solver_controls ctl; ctl.tolerance = 0; ctl.relTol = 0; ctl.maxIter = iters + 16; ctl.minIter = 0;
     double* zero;
-    MICHK(m->vec(14, &zero));
+    MICHK(m->vec(WV_BENCH_ZERO, &zero));
     // psi0 = 0 in caller order == 0 in engine order
     MICHK(mi_pcg_begin(m, zero, source, &ctl, precond, 1));
     HIPCHK(hipEventRecord(c->ev0, c->stream));

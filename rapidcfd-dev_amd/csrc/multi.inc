@@ -206,8 +206,7 @@ extern "C" int mi_pbicg_solve_multi(mi_matrix_t m, int32_t nrhs, const double* c
 {
     if (!m || nrhs < 1 || nrhs > 3 || !psi_io || !source || !ctl) return fail(MI_ERR_ARG, "mi_pbicg_solve_multi: bad argument (1 <= nrhs <= 3)");
     for (int c = 0; c < nrhs; ++c) if (!psi_io[c] || !source[c] || (diag_dev && !diag_dev[c])) return fail(MI_ERR_ARG, "mi_pbicg_solve_multi: NULL component");
-    if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound");
-    if (m->addr->ctx->session) return fail(MI_ERR_STATE, "mi_pbicg_solve_multi: a PCG session (mi_pcg_begin) is active on this context; call mi_pcg_end first");
+    MICHK(solver_entry("mi_pbicg_solve_multi", m, true));
     if (precond != MI_PRECOND_NONE && precond != MI_PRECOND_DIAGONAL && precond != MI_PRECOND_AINV) return fail(MI_ERR_ARG, "unknown preconditioner kind");
     mi_addr_s* a = m->addr;
     mi_ctx_s* c = a->ctx;
@@ -231,8 +230,9 @@ extern "C" int mi_pbicg_solve_multi(mi_matrix_t m, int32_t nrhs, const double* c
     double *psi[3], *src[3], *pA[3], *wA[3], *rA[3], *pT[3], *wT[3], *rT[3], *dgE[3] = {nullptr, nullptr, nullptr}, *rDc[3] = {nullptr, nullptr, nullptr}, *sumAc[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < nrhs; ++k) {
         double** vs[8] = {&psi[k], &src[k], &pA[k], &wA[k], &rA[k], &pT[k], &wT[k], &rT[k]};
-        for (int j = 0; j < 8; ++j) MICHK(m->vec((size_t)(16 + 11 * k + j), vs[j]));
-        if (diag_dev) { MICHK(m->vec((size_t)(16 + 11 * k + 8), &dgE[k])); MICHK(m->vec((size_t)(16 + 11 * k + 9), &rDc[k])); MICHK(m->vec((size_t)(16 + 11 * k + 10), &sumAc[k])); }
+        const size_t v0 = WV_MULTI + WV_MULTI_STRIDE * (size_t)k;
+        for (size_t j = 0; j < 8; ++j) MICHK(m->vec(v0 + j, vs[j]));
+        if (diag_dev) MICHK(m->vecs({{v0 + 8, &dgE[k]}, {v0 + 9, &rDc[k]}, {v0 + 10, &sumAc[k]}}));
     }
     if (m->mstate.n < 3) MICHK(m->mstate.alloc(3));
     if (m->mpartial.n < (size_t)3 * 4 * RG) MICHK(m->mpartial.alloc((size_t)3 * 4 * RG));
@@ -345,19 +345,15 @@ extern "C" int mi_pbicg_solve_multi(mi_matrix_t m, int32_t nrhs, const double* c
     auto fetch = [&]() -> int {
         HIPCHK(hipMemcpyAsync(m->mhostState, m->mstate.p, sizeof(PcgState) * (size_t)nrhs, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (att) MICHK(peer_check(m));   // a window wait that ran out of polls voids the sums
         return MI_OK;
     };
     auto all_done = [&]() { for (int k = 0; k < nrhs; ++k) if (!m->mhostState[k].done) return false; return true; };
     // (no host read before the first iteration is enqueued: a component that the prologue finds converged gates itself)
     // ---- iterations: every component runs ITS loop (its scalars, its test); what they share is the pass over the matrix
-    const int batch = c->pcgBatch;
-    const int limit = ctl->maxIter + (ctl->minIter > ctl->maxIter ? ctl->minIter : 0);
-    // (batches grow 1, 2, 4 ...: the momentum predictor of a time step usually needs ONE iteration per component)
-    int it = 0, nb = 1;
+    int it = 0;
     Fold3 f1, f2;
     for (int k = 0; k < 3; ++k) { f1.in[k] = m->mtilePartial.p + (size_t)(k < nrhs ? k : 0) * (size_t)a->L.nTiles; f1.out[k] = P1[k < nrhs ? k : 0]; f2.in[k] = f1.in[k]; f2.out[k] = P2[k < nrhs ? k : 0]; }
-    while (!all_done() && it <= limit) {
+    auto enqueue = [&](int nb) -> int {
         for (int j = 0; j < nb; ++j, ++it) {
             if (precond == MI_PRECOND_AINV) { // DILU: precondition(wA, rA), preconditionT(wT, rT) and sum wA.rT of all components in one pass
                 MultiIO io;
@@ -387,16 +383,15 @@ extern "C" int mi_pbicg_solve_multi(mi_matrix_t m, int32_t nrhs, const double* c
             for (int k = 0; k < nrhs; ++k) k_pcg_final<false><<<1, RB, 0, s>>>(st[k], it, P3[k], hist[k], histLen);
         }
         HIPCHK(hipGetLastError());
-        MICHK(fetch());
-        nb = nb * 2 > batch ? batch : nb * 2;
-    }
+        return MI_OK;
+    };
+    // (batches grow 1, 2, 4 ...: the momentum predictor of a time step usually needs ONE iteration per component.  After every fetch
+    //  drive_batches checks the peer windows: a window wait that ran out of polls voids the sums)
+    MICHK(drive_batches(m, ctl, it, 1, enqueue, fetch, all_done));
     for (int k = 0; k < nrhs; ++k) {
         k_scatter_perm<<<RG, RB, 0, s>>>(psi[k], a->perm(), psi_io[k], a->L.nCells);
         if (perf) fill_perf(m->mhostState[k], perf + k);
-        if (hist_host && hist_len > 0) {
-            int cnt = m->mhostState[k].nIterations + 1; if (cnt > hist_len) cnt = hist_len; if (cnt > histLen) cnt = histLen;
-            if (cnt > 0) HIPCHK(hipMemcpyAsync(hist_host + (size_t)k * (size_t)hist_len, hist[k], sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
-        }
+        if (hist_host) MICHK(copy_hist(s, hist[k], histLen, hist_host + (size_t)k * (size_t)hist_len, hist_len, m->mhostState[k].nIterations, false));
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));

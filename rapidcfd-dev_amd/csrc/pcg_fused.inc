@@ -348,7 +348,7 @@ int pcg_fused_rp_launch(mi_matrix_s* m, int it, int precond)
     A.st = c->state.p; A.it = it;
     A.partial1 = c->partial.p; A.partial2 = c->partial.p + RG; A.partial3 = c->partial.p + 2 * RG;
     double *psi, *pA, *wA, *rA;
-    MICHK(m->vec(3, &psi)); MICHK(m->vec(5, &pA)); MICHK(m->vec(6, &wA)); MICHK(m->vec(7, &rA));
+    MICHK(m->vecs({{WV_PSI, &psi}, {WV_PA, &pA}, {WV_WA, &wA}, {WV_RA, &rA}}));
     A.wA = wA; A.rD = m->rD.p; A.pA = pA; A.psi = psi; A.rA = rA; A.n = a->L.nCells;
     A.hist = m->hist.p; A.histLen = m->histLen;
     A.bar = m->fusedBar.p; A.gen = m->fusedGen;

@@ -761,7 +761,7 @@ extern "C" int mi_matrix_peer_halo_auto(mi_matrix_t m, int32_t* enabled_out)
     // agreement: the function is called collectively from mi_matrix_attach_comm, and a rank that returned early would leave
     // the others blocked in their next all-reduce (ADVICE r03).  Collective calls are issued by every rank regardless.
     double *v0 = nullptr, *v1 = nullptr;
-    if (ok && (m->vec(0, &v0) != MI_OK || m->vec(1, &v1) != MI_OK)) ok = false;
+    if (ok && (m->vec(WV_OP_X, &v0) != MI_OK || m->vec(WV_OP_Y, &v1) != MI_OK)) ok = false;
     if (ok && m->sendBuf.n < (size_t)std::max(L.nExt, 1) && m->sendBuf.alloc((size_t)std::max(L.nExt, 1)) != MI_OK) ok = false;
     MICHK(comm_agree(base, ok, &all));      // also: every window is mapped before anyone writes into it
     if (!all) return MI_OK;

@@ -704,7 +704,7 @@ int persist_enqueue(mi_matrix_s* m, int n_iters, int precond, bool dist)
     hipStream_t s = c->stream;
     double *psi, *pA, *rA;
     if (dist) { psi = m->dp.psi; pA = m->dp.pA; rA = m->dp.rA; }
-    else { MICHK(m->vec(3, &psi)); MICHK(m->vec(5, &pA)); MICHK(m->vec(7, &rA)); }
+    else { MICHK(m->vecs({{WV_PSI, &psi}, {WV_PA, &pA}, {WV_RA, &rA}})); }
     if (precond != MI_PRECOND_NONE) MICHK(ensure_rD(m));
     const int G = persist_grid(c);
     const size_t scratch = (size_t)3 * (size_t)G + 16 + BAR_WORDS / 2;
@@ -730,7 +730,7 @@ int persist_enqueue(mi_matrix_s* m, int n_iters, int precond, bool dist)
     P.st = c->state.p; P.psi = psi; P.rA = rA; P.pA = pA; P.rD = m->rD.p; P.P1 = c->partial.p;
     P.pB = pA; P.Z = nullptr; P.zpMaxTiles = env_int("MI_PERSIST_ZP", 1);
     if (!dist) {   // ZP: the second pA buffer (the Amul result vector of the five-launch pipeline, unused here) and z
-        MICHK(m->vec(6, &P.pB));
+        MICHK(m->vec(WV_WA, &P.pB));
         // (z is gathered like pA: halo entries of an un-attached matrix's processor patches index the ext region behind the
         //  owned cells, which reads as zero in every engine vector -- ADVICE r03: it used to be nCells long and uninitialised)
         const size_t zLen = (size_t)a->L.nCells + (size_t)a->L.nExt;

@@ -2,7 +2,8 @@
 
 mi_pbicg_solve takes one of three loops (engine.hip, multi.inc): the multi-vector solver with one right-hand side (M, the default),
 pbicg_solve_device (D: MI_PBICG_MULTI=0, compact rows, cyclicAMI patches) and the host-stepped loop (H: MI_PBICG_HOST_STEPPED=1).
-PBiCGStab has its device loop and a host-stepped twin; smoothSolver swaps two buffers after every Jacobi sweep.  Every run is held
+M, D and PBiCGStab's device loop are iteration bodies inside one host frame (engine.hip: stage_in, drive_batches, finish_device);
+M's first batch is 1 iteration, the others' 2.  PBiCGStab has its device loop (pbicgstab_solve_device) and a host-stepped twin; smoothSolver swaps two buffers after every Jacobi sweep.  Every run is held
 against the oracle (PBiCG.C, PBiCGStab.C, smoothSolver.C): iteration count and flags equal, the history through _check_hist,
 normFactor to 1e-13, psi to 1e-9 of max|psi_ref| -- smoothSolver's psi bit for bit.  The counters of mi_ctx_stat say which loop ran.
 
