@@ -786,14 +786,14 @@ int ensure_caller_tables(mi_addr_s* a)
         mi_addr_s::RowPlan& rp = a->rowPlan[k];
         rp = mi_addr_s::RowPlan();
         rp.tiles = tiles;
-        rp.capForced = env_int("MI_ROW_CAP", 0);
+        rp.capForced = sw::get(SW_ROW_CAP);
         if (tiles) {
             rp.bs = a->L.maxCells <= 256 ? 256 : a->L.maxCells <= 512 ? 512 : 1024;
             rp.blocks = a->L.nTiles;
             for (int32_t t = 0; t < a->L.nTiles; ++t)
                 rp.maxFaces = std::max(rp.maxFaces, os[(size_t)a->L.tileCellStart[(size_t)t + 1]] - os[(size_t)a->L.tileCellStart[t]]);
         } else {
-            const int bs = env_int(k == 0 ? "MI_ROW_BS" : "MI_GRAD_BS", k == 0 ? 1024 : 256);
+            const int bs = sw::get(k == 0 ? SW_ROW_BS : SW_GRAD_BS);
             rp.bs = bs <= 256 ? 256 : bs <= 512 ? 512 : 1024;
             rp.blocks = (n + rp.bs - 1) / rp.bs;
             for (int32_t c0 = 0; c0 < n; c0 += rp.bs) rp.maxFaces = std::max(rp.maxFaces, os[(size_t)std::min(c0 + rp.bs, n)] - os[c0]);
@@ -801,7 +801,7 @@ int ensure_caller_tables(mi_addr_s* a)
     }
     // block-local 16-bit row tables for the blocks of plan [0] (k_row_pass<..., R16>): usable when every block has < 32768 own
     // faces and cut faces and < 65536 neighbour-list entries (a 1024-cell block has ~3 000 / ~300 / ~3 000)
-    if (env_int("MI_ROW16", 1) != 0 && nf > 0) {
+    if (sw::get(SW_ROW16) != 0 && nf > 0) {
         const mi_addr_s::RowPlan& rp = a->rowPlan[0];
         const int nB = rp.blocks;
         auto block_cells = [&](int b, int32_t& c0, int32_t& c1) {

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(64) void k_peer_allreduce(const PeerAR A, double* _
     if (threadIdx.x == 0) for (int i = 0; i < n; ++i) p[i] = v[i];
 }
 namespace {
-const long long PEER_POLLS = (long long)env_int("MI_PEER_POLLS", 20000000);   // several seconds (tests shorten it)
+const long long PEER_POLLS = (long long)sw::get(SW_PEER_POLLS);   // several seconds (tests shorten it)
 PeerAR peer_ar(const mi_comm_s* c, long long maxPolls = PEER_POLLS)
 {
     return PeerAR{c->peerTable, c->window, c->epoch, c->peerStatus, c->nRanks, c->rank, maxPolls, (int32_t)peer_fused_off(c->nRanks), (int32_t)peer_rep_stride(c->nRanks)};
@@ -214,7 +214,7 @@ int alloc_ipc_window(size_t bytes, void** out, bool* fineGrained)
     void* w = nullptr;
     hipIpcMemHandle_t h;
     *fineGrained = false;
-    if (env_int("MI_PEER_FINEGRAINED", 1) && hipExtMallocWithFlags(&w, bytes, hipDeviceMallocFinegrained) == hipSuccess) {
+    if (sw::get(SW_PEER_FINEGRAINED) && hipExtMallocWithFlags(&w, bytes, hipDeviceMallocFinegrained) == hipSuccess) {
         if (hipIpcGetMemHandle(&h, w) == hipSuccess) *fineGrained = true;
         else { (void)hipFree(w); w = nullptr; (void)hipGetLastError(); }
     } else (void)hipGetLastError();
@@ -279,7 +279,7 @@ extern "C" int mi_comm_peer_connect(mi_comm_t c, const void* handles, int32_t n_
         if (!on_my_device(c->ctx, q)) oneDevice = false; else c->sharedDevice = true;
     }
     HIPCHK(hipMemcpy(c->peerTable, c->peerWindow.data(), sizeof(double*) * (size_t)c->nRanks, hipMemcpyHostToDevice));
-    if (!c->windowFineGrained && !oneDevice && !env_int("MI_PEER_ALLOW_COARSE", 0))
+    if (!c->windowFineGrained && !oneDevice && !sw::get(SW_PEER_ALLOW_COARSE))
         return fail(MI_ERR_UNSUPPORTED, "mi_comm_peer_connect: the window is ordinary (coarse-grained) device memory and a peer is on another device: "
                                         "not coherent while a kernel polls it; the communicator keeps its RCCL / external all-reduce");
     c->peerReady = true;
@@ -624,7 +624,7 @@ extern "C" int mi_matrix_attach_comm(mi_matrix_t m, mi_comm_t reduce, mi_comm_t 
         for (size_t q = 0; same && q < D.sends.size(); ++q) same = D.ph->patchRank[q] == D.sends[q].peer;
         if (!same) { delete D.ph; D.ph = nullptr; }
     }
-    if (!D.ph && reduce->peerReady && env_int("MI_PEER_HALO", 1)) {
+    if (!D.ph && reduce->peerReady && sw::get(SW_PEER_HALO)) {
         int32_t on = 0;
         MICHK(mi_matrix_peer_halo_auto(m, &on));
     }

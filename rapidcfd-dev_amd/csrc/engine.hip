@@ -7,6 +7,7 @@
 #include "kernels.hip.hpp"
 #include "tiling.hpp"
 #include "host_parallel.hpp"
+#include "switches.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -64,12 +65,6 @@ struct DevBuf {
     }
 };
 
-int env_int(const char* name, int def)
-{
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : def;
-}
-
 } // namespace
 
 struct mi_ctx_s {
@@ -84,35 +79,43 @@ struct mi_ctx_s {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t sideStream = nullptr;              // second stream (lazy): the GAMG coarsest-level inversion runs there beside the solve's prologue and first down-sweep
     hipEvent_t evSideGo = nullptr, evSideDone = nullptr;
-    int amulBS = 0;
-    int tileFlags = 0;
-    int xcdRows = 1;      // MI_XCD_ROWS: XCD-aware block mapping of the caller-order row passes
-    int persist = 0;      // MI_TILE_PERSIST: persistent tile launches (workgroups = resident slots, each walks a run of tiles)
     int nCU = 0;
-    bool coarseLevelBuild = false; // set by the GAMG hierarchy builder around its level addressings (tile size choice)
-    bool keepSlotTables = false;   // ... and: keep the host copies of slotFace / faceSlot (the builder derives its slot-to-slot children lists from them, then drops them)
-    int attachEvents = 1; // MI_EVENT_ATTACH=0: plain hipEventRecord pairs around the Amul launch instead of kernel-attached events (A/B hook)
-    int fusePerm = 1;  // MI_FUSE_PERM: caller-order operators gather / scatter through e2c inside the tile kernel (A/B hook)
-    int deferPsi = 1;  // MI_PCG_DEFER_PSI: psi += alpha pA rides in the next k_pcg_update_p (one vector read less per iteration; A/B hook)
-    int fuseFinal = 0; // MI_PCG_FUSE_FINAL: convergence test fused into the next update_p (A/B hook)
-    int pcgFuseTest = 0; // tests ("pcg_fuse_test"): workgroups of the fused launch that leave its barrier at once (pcg_fused.inc)
-    int pcgFuseRP = -1; // MI_PCG_FUSE_RP: residual update + next direction update as one launch (pcg_fused.inc); 0 never, -1 (default) once the device has been asked
-    int pcgPersist = 1; // MI_PCG_PERSIST: 0 never, 1 (default) whenever the tiles fit the CUs' registers (persist.inc)
+    bool keepSlotTables = false;   // set by the GAMG hierarchy builder around its level addressings: keep the host copies of slotFace / faceSlot (the builder derives its slot-to-slot children lists from them, then drops them)
+    // the switches of the context moment: mi_ctx_create fills every one from its row of switches.hpp (CTX_SWITCHES below), which says what it means
+    int tileFlags = 0, attachEvents = 0, persist = 0, xcdRows = 0, deferPsi = 0, fusePerm = 0, pairAT = 0, fusePrologue = 0, multiPipe = 0, winDirect = 0, gamgGraphAttached = 0;
+    int pcgPersist = 0, pcgFuseRP = 0, pcgFuseTest = 0, persistGrid = 0, persistShared = 0, fuseFinal = 0, amulBS = 0, pcgBatch = 0, pcgGraph = 0, pbicgHostStepped = 0;
+    int gamgDeviceInvert = 0, gamgAlwaysAgglomerate = 0, gamgGraph = 0, gamgFuse = 0;
     int64_t stats[12] = {}; // mi_ctx_stat
-    int persistGrid = 0; // MI_PERSIST_GRID: workgroups of the persistent kernel (0: one per CU); MI_PERSIST_SHARED=1 lets ranks that share a device use it -- tests only: their grids must fit the device TOGETHER
-    int persistShared = 0;
     int persistCoop = -1; // cooperative launch of the persistent kernel possible on this device AND its barrier litmus clean (-1: not asked yet)
     uint64_t faultEpoch = 0; // faults of the persistent kernel reported on this context so far (fetch_state); a matrix re-zeroes its barrier words when it has missed one
-    int winDirect = 1; // MI_WIN_DIRECT: tile operators of attached matrices read neighbour-rank values straight from the halo window (one launch for all tiles) instead of k_halo_pull + a second launch (A/B hook)
-    int gamgGraphAttached = 1; // MI_GAMG_GRAPH_ATTACHED: the V-cycle of a decomposed case replays as a hipGraph when every exchange of it is stream work (peer windows)
-    int multiPipe = 1; // MI_MULTI_PIPE: tile_kernel_multi_pipe (multi_pipe.inc) for the multi-vector passes of the Krylov iterations
-    int fusePrologue = 1; // MI_FUSE_PROLOGUE: A psi, source - A psi and sumA in one pass over the coefficients, the prologue's sums batched (A/B hook: 0 = the separate passes, same bits)
-    int pairAT = 1;    // MI_PBICG_PAIR: PBiCG's A p / A^T pT (and the DILU pair) in one pass over the coefficients (A/B hook)
     struct mi_matrix_s* session = nullptr; // matrix whose mi_pcg_begin/iterate/end session owns this context's solver scratch (partial, scalars, state)
-    int pcgBatch = 16, pcgGraph = -1, pbicgHostStepped = 0, gamgDeviceInvert = -1, gamgAlwaysAgglomerate = 0, gamgGraph = 1, gamgFuse = 1; // MI_* switches, read once per context
     std::set<const void*> ldsAttrSet;                         // kernels whose dynamic-LDS limit has been raised on THIS device
     std::map<std::pair<const void*, size_t>, int> occCache;  // (kernel, LDS bytes) -> resident workgroups per CU on this device
 };
+
+// the rows of switches.hpp that are read at mi_ctx_create (sw::CTX) and the members they fill; mi_ctx_set_option stores into the
+// same members by the rows' option names
+struct CtxSwitch { Switch id; int mi_ctx_s::*member; };
+static constexpr CtxSwitch CTX_SWITCHES[] = {
+    {SW_TILE_FLAGS, &mi_ctx_s::tileFlags}, {SW_EVENT_ATTACH, &mi_ctx_s::attachEvents}, {SW_TILE_PERSIST, &mi_ctx_s::persist}, {SW_XCD_ROWS, &mi_ctx_s::xcdRows},
+    {SW_PCG_DEFER_PSI, &mi_ctx_s::deferPsi}, {SW_FUSE_PERM, &mi_ctx_s::fusePerm}, {SW_PBICG_PAIR, &mi_ctx_s::pairAT}, {SW_FUSE_PROLOGUE, &mi_ctx_s::fusePrologue},
+    {SW_MULTI_PIPE, &mi_ctx_s::multiPipe}, {SW_WIN_DIRECT, &mi_ctx_s::winDirect}, {SW_GAMG_GRAPH_ATTACHED, &mi_ctx_s::gamgGraphAttached}, {SW_PCG_PERSIST, &mi_ctx_s::pcgPersist},
+    {SW_PCG_FUSE_RP, &mi_ctx_s::pcgFuseRP}, {SW_PCG_FUSE_TEST, &mi_ctx_s::pcgFuseTest}, {SW_PERSIST_GRID, &mi_ctx_s::persistGrid}, {SW_PERSIST_SHARED, &mi_ctx_s::persistShared},
+    {SW_PCG_FUSE_FINAL, &mi_ctx_s::fuseFinal}, {SW_AMUL_BS, &mi_ctx_s::amulBS}, {SW_PCG_BATCH, &mi_ctx_s::pcgBatch}, {SW_PCG_GRAPH, &mi_ctx_s::pcgGraph},
+    {SW_PBICG_HOST_STEPPED, &mi_ctx_s::pbicgHostStepped}, {SW_GAMG_DEVICE_INVERT, &mi_ctx_s::gamgDeviceInvert}, {SW_GAMG_ALWAYS_AGGLOMERATE, &mi_ctx_s::gamgAlwaysAgglomerate},
+    {SW_GAMG_GRAPH, &mi_ctx_s::gamgGraph}, {SW_GAMG_FUSE, &mi_ctx_s::gamgFuse},
+};
+constexpr bool ctx_switches_match_table()   // every sw::CTX row exactly once, no other row at all
+{
+    for (int s = 0; s < SW_COUNT; ++s) {
+        int n = 0;
+        for (const CtxSwitch& e : CTX_SWITCHES) n += e.id == s;
+        if (n != ((sw::table[s].when & sw::CTX) ? 1 : 0)) return false;
+    }
+    return true;
+}
+static_assert(ctx_switches_match_table(), "CTX_SWITCHES: exactly one entry for every sw::CTX row of switches.hpp");
+static void ctx_store(mi_ctx_s* c, const CtxSwitch& s, int value) { c->*s.member = s.id == SW_PCG_FUSE_RP ? (value != 0 ? -1 : 0) : value; }   // pcgFuseRP: 0 never, -1 not asked yet
 
 struct mi_addr_s {
     mi_ctx_s* ctx = nullptr;
@@ -295,28 +298,10 @@ extern "C" int mi_ctx_create(int device, void* hip_stream, mi_ctx_t* out)
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
         delete c; return fail(MI_ERR_DEVICE, "pinned host / event allocation failed");
     }
-    c->tileFlags = env_int("MI_TILE_FLAGS", 1); // bit0: coefficient segments are staged with non-temporal loads (read once per launch): Amul -4 % (profiles/r02_b_cache_policy_ab.md)
-    c->attachEvents = env_int("MI_EVENT_ATTACH", 1);
-    c->persist = env_int("MI_TILE_PERSIST", 0);
-    c->xcdRows = env_int("MI_XCD_ROWS", 1);
-    c->deferPsi = env_int("MI_PCG_DEFER_PSI", 1);
-    c->fusePerm = env_int("MI_FUSE_PERM", 1);
     { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess) c->nCU = pr.multiProcessorCount; }
-    c->pairAT = env_int("MI_PBICG_PAIR", 1);
-    c->fusePrologue = env_int("MI_FUSE_PROLOGUE", 1);
-    c->multiPipe = env_int("MI_MULTI_PIPE", 1);   // the multi-vector tile passes of the Krylov iterations as persistent pipelined workgroups (multi_pipe.inc): same bits, three-component PBiCG + DILU iteration 1 812 -> 1 643 us (profiles/r05_f_multi_pipe_ab.md)
-    c->winDirect = env_int("MI_WIN_DIRECT", 1); c->gamgGraphAttached = env_int("MI_GAMG_GRAPH_ATTACHED", 1);
-    c->pcgPersist = env_int("MI_PCG_PERSIST", 1);
-    c->pcgFuseRP = env_int("MI_PCG_FUSE_RP", 1) != 0 ? -1 : 0;
-    c->persistGrid = env_int("MI_PERSIST_GRID", 0);
-    c->persistShared = env_int("MI_PERSIST_SHARED", 0);
-    c->fuseFinal = env_int("MI_PCG_FUSE_FINAL", 0); // measured: no gain (332.0 vs 332.3 us/iter), kept as an option
-    c->amulBS = env_int("MI_AMUL_BS", 0); // 0 = choose per launch from the LDS footprint
-    c->pcgBatch = env_int("MI_PCG_BATCH", 16);
+    for (const CtxSwitch& s : CTX_SWITCHES) ctx_store(c, s, sw::get(s.id));
     if (c->pcgBatch < 1) c->pcgBatch = 1;   // every batched loop advances by the batch length: 0 or less would never end
-    c->pcgGraph = env_int("MI_PCG_GRAPH", -1); c->pbicgHostStepped = env_int("MI_PBICG_HOST_STEPPED", 0);
-    c->gamgDeviceInvert = env_int("MI_GAMG_DEVICE_INVERT", -1); c->gamgAlwaysAgglomerate = env_int("MI_GAMG_ALWAYS_AGGLOMERATE", 0); c->gamgGraph = env_int("MI_GAMG_GRAPH", 1); c->gamgFuse = env_int("MI_GAMG_FUSE", 1);
-    if (c->amulBS != 256 && c->amulBS != 512 && c->amulBS != 1024) c->amulBS = 0;
+    if (c->amulBS != 256 && c->amulBS != 512 && c->amulBS != 1024) c->amulBS = 0;   // 0 = choose per launch from the LDS footprint
     *out = c;
     return MI_OK;
 }
@@ -345,20 +330,12 @@ extern "C" int mi_ctx_synchronize(mi_ctx_t c)
     return MI_OK;
 }
 
-// run-time switches of a context (the environment variables of the same meaning are read once, at mi_ctx_create):
-//   "pcg_persist"  0 / 1: the persistent PCG kernel for matrices that fit the CUs' registers (MI_PCG_PERSIST)
-//   "fuse_prologue" 0 / 1: the solvers' prologue as one tile pass (A psi, source - A psi, sumA) + batched sums (MI_FUSE_PROLOGUE)
-//   "win_direct"   0 / 1: boundary tiles of attached matrices read the halo window themselves (MI_WIN_DIRECT)
-//   "gamg_graph_attached" 0 / 1: hipGraph replay of the V-cycle of a decomposed case (MI_GAMG_GRAPH_ATTACHED)
+// run-time switches of a context: the option names of switches.hpp, stored where mi_ctx_create stored the environment's value
 extern "C" int mi_ctx_set_option(mi_ctx_t c, const char* name, int32_t value)
 {
     if (!c || !name) return fail(MI_ERR_ARG, "mi_ctx_set_option: bad argument");
-    if (std::string(name) == "pcg_persist") { c->pcgPersist = value; return MI_OK; }
-    if (std::string(name) == "pcg_fuse_rp") { c->pcgFuseRP = value != 0 ? -1 : 0; return MI_OK; }
-    if (std::string(name) == "pcg_fuse_test") { c->pcgFuseTest = value; return MI_OK; }
-    if (std::string(name) == "fuse_prologue") { c->fusePrologue = value; return MI_OK; }             // MI_FUSE_PROLOGUE
-    if (std::string(name) == "win_direct") { c->winDirect = value; return MI_OK; }                     // MI_WIN_DIRECT
-    if (std::string(name) == "gamg_graph_attached") { c->gamgGraphAttached = value; return MI_OK; }   // MI_GAMG_GRAPH_ATTACHED
+    for (const CtxSwitch& s : CTX_SWITCHES)
+        if (sw::table[s.id].option && strcmp(name, sw::table[s.id].option) == 0) { ctx_store(c, s, value); return MI_OK; }
     return fail(MI_ERR_ARG, "mi_ctx_set_option: unknown option");
 }
 
@@ -377,10 +354,112 @@ extern "C" int mi_ctx_stat(mi_ctx_t c, int32_t which, int64_t* out)
 // ---------------------------------------------------------------------------
 // addressing
 // ---------------------------------------------------------------------------
+static int32_t tile_reorder() { return sw::get(SW_TILE_REORDER); }   // (on its own for mi_layout_build_host, which takes nothing else from the environment)
+// The tile-layout parameters of an addressing of n_cells cells (coarse: a level of a GAMG hierarchy on ctx; ctx is read for such a
+// level only): with tile_reorder() the only place where MI_TILE_CELLS, MI_TILE_SLOTS, MI_TILE_REORDER, MI_ENTRY16 and
+// MI_SMALL_TILES (switches.hpp) turn into a TileParams.
+// 1024 cells per tile; the coarse levels of a GAMG hierarchy are cut into enough tiles for every CU instead -- a shorter
+// staging / row chain per workgroup, down to 128-cell tiles: their tile kernels take 4.6-5.5 us instead of 7-8
+// (profiles/r02_gamg_rocprof_summary.md), 2.08 -> 2.02 ms per V-cycle on the 216^3 box.  The caller's own matrices keep 1024 (no
+// gain measured for small PCG cases, and the partial-sum grouping of the Krylov reductions stays what the parity tests pinned).
+static TileParams addr_tile_params(mi_ctx_t ctx, int32_t n_cells, bool coarse, bool ordered, int32_t n_tiles, const int32_t* tile_cell_start)
+{
+    TileParams prm;
+    prm.tileCells = sw::get(SW_TILE_CELLS);
+    if (prm.tileCells <= 0) {
+        int target = 1024;
+        if (coarse && sw::get(SW_SMALL_TILES)) target = (int)(((int64_t)n_cells / std::max(1, ctx->nCU) + 63) / 64 * 64);
+        prm.tileCells = std::min(1024, std::max(128, target));
+    }
+    prm.slotCap = sw::get(SW_TILE_SLOTS);
+    prm.reorder = tile_reorder();
+    prm.compact = sw::get(SW_ENTRY16) != 0;
+    prm.keepOrder = ordered; prm.givenTileStart = tile_cell_start; prm.nGivenTiles = n_tiles;
+    return prm;
+}
+// prebuilt != nullptr: the host layout was built elsewhere (the GAMG builder builds its levels' layouts on other threads while
+// it matches the next level) with addr_tile_params' parameters; it is moved from
+static int addr_create_impl(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces, const int32_t* lower, const int32_t* upper, int32_t n_patches,
+                            const int32_t* patch_sizes, const int32_t* const* patch_face_cells, const int32_t* const* patch_nbr_cells,
+                            bool coarse, bool ordered, int32_t n_tiles, const int32_t* tile_cell_start, mi_addr_t* out, TileLayout* prebuilt)
+{
+    if (!ctx || !out || (n_faces > 0 && (!lower || !upper)) || n_patches < 0)
+        return fail(MI_ERR_ARG, "mi_addr_create: bad argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    mi_addr_s* a = new mi_addr_s();
+    a->ctx = ctx;
+#ifdef MI_TIMING
+    auto ta__ = std::chrono::steady_clock::now();
+    auto ta_tick = [&](const char* what) { auto n = std::chrono::steady_clock::now(); if (n_cells > 1000000) fprintf(stderr, "[addr] %-28s %.4f s\n", what, std::chrono::duration<double>(n - ta__).count()); ta__ = n; };
+#endif
+    if (prebuilt) a->L = std::move(*prebuilt);
+    else {
+    const TileParams prm = addr_tile_params(ctx, n_cells, coarse, ordered, n_tiles, tile_cell_start);
+    const std::string err = build_tile_layout(n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, prm, a->L, patch_nbr_cells);
+    if (!err.empty()) { delete a; return fail(MI_ERR_LIMIT, "mi_addr_create: " + err); }
+    }
+#ifdef MI_TIMING
+    ta_tick("tile layout (host)");
+#endif
+    a->identity = true;
+    for (int32_t e = 0; e < n_cells; ++e) if (a->L.e2c[(size_t)e] != e) { a->identity = false; break; }
+    a->nLocalPatches = 0;
+    a->patchIsLocal.assign((size_t)std::max(n_patches, 0), 0);
+    if (patch_nbr_cells) for (int32_t p = 0; p < n_patches; ++p) if (patch_nbr_cells[p]) { a->nLocalPatches++; a->patchIsLocal[(size_t)p] = 1; }
+    TileLayout& L = a->L;
+    hipStream_t s = ctx->stream;
+    int r = MI_OK;
+#define UP(buf, vec) if (r == MI_OK) r = a->buf.upload(vec, s)
+    UP(e2c, L.e2c); UP(c2e, L.c2e); UP(tileCellStart, L.tileCellStart); UP(tileSlotStart, L.tileSlotStart); UP(tileIfaceSlot0, L.tileIfaceSlot0);
+    UP(tileHaloStart, L.tileHaloStart); UP(haloCell, L.haloCell); UP(tileSliceStart, L.tileSliceStart);
+    a->compact = L.compact;
+    if (L.compact) { UP(sliceEntryStart16, L.sliceEntryStart16); UP(entries16, L.entries16); UP(slotBase, L.slotBase); UP(tileSbStart, L.tileSbStart); }
+    else { UP(sliceEntryStart, L.sliceEntryStart); UP(entries, L.entries); }
+    UP(slotFace, L.slotFace);
+    UP(extSlot, L.extSlot); UP(interiorTiles, L.interiorTiles); UP(boundaryTiles, L.boundaryTiles);
+    UP(patchFaceCellsE, L.patchFaceCellsE); UP(faceSlot, L.faceSlot);
+#undef UP
+    if (r != MI_OK) { delete a; return r; }
+    if (hipStreamSynchronize(s) != hipSuccess) { delete a; return fail(MI_ERR_DEVICE, "upload failed"); }
+#ifdef MI_TIMING
+    ta_tick("uploads + synchronise");
+#endif
+    a->nInterior = (int32_t)L.interiorTiles.size();
+    a->nBoundary = (int32_t)L.boundaryTiles.size();
+    a->nEntries = (int64_t)(L.compact ? L.entries16.size() : L.entries.size()); // 32-bit words of row entries on the device
+    a->nHaloTot = (int64_t)L.haloCell.size();
+    a->lowerHost.resize((size_t)n_faces); a->upperHost.resize((size_t)n_faces);
+    mi::parallel_blocks(n_faces, 1 << 20, [&](int64_t b, int64_t e, int) {
+        std::memcpy(a->lowerHost.data() + b, lower + b, sizeof(int32_t) * (size_t)(e - b));
+        std::memcpy(a->upperHost.data() + b, upper + b, sizeof(int32_t) * (size_t)(e - b));
+    });
+    a->patchFaceCellsHost.resize((size_t)n_patches); a->patchNbrCellsHost.resize((size_t)n_patches);
+    for (int32_t p = 0; p < n_patches; ++p) {
+        a->patchFaceCellsHost[(size_t)p].assign(patch_face_cells[p], patch_face_cells[p] + patch_sizes[p]);
+        if (a->patchIsLocal[(size_t)p]) a->patchNbrCellsHost[(size_t)p].assign(patch_nbr_cells[p], patch_nbr_cells[p] + patch_sizes[p]);
+    }
+    // drop the big host tables that only the device needs (their memory goes back to the system on another thread)
+    {
+        Table<int32_t> slotFace, faceSlot;
+        if (!ctx->keepSlotTables) { slotFace.swap(L.slotFace); faceSlot.swap(L.faceSlot); }
+        mi::free_in_background(L.entries, L.entries16, L.sliceEntryStart16, L.slotBase, slotFace, L.haloCell, L.sliceEntryStart, faceSlot);
+        L.entries = Table<uint32_t>(); L.entries16 = Table<uint32_t>(); L.sliceEntryStart16 = Table<int32_t>(); L.slotBase = Table<uint16_t>();
+        L.haloCell = Table<int32_t>(); L.sliceEntryStart = Table<int32_t>();
+    }
+#ifdef MI_TIMING
+    ta_tick("host copies + frees");
+#endif
+    *out = a;
+    return MI_OK;
+}
+
 extern "C" int mi_addr_create_coupled(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces,
                                       const int32_t* lower, const int32_t* upper, int32_t n_patches,
                                       const int32_t* patch_sizes, const int32_t* const* patch_face_cells,
-                                      const int32_t* const* patch_nbr_cells, mi_addr_t* out);
+                                      const int32_t* const* patch_nbr_cells, mi_addr_t* out)
+{
+    return addr_create_impl(ctx, n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, patch_nbr_cells, false, false, 0, nullptr, out, nullptr);
+}
 
 extern "C" int mi_addr_create(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces,
                               const int32_t* lower, const int32_t* upper, int32_t n_patches,
@@ -388,18 +467,6 @@ extern "C" int mi_addr_create(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces,
                               mi_addr_t* out)
 {
     return mi_addr_create_coupled(ctx, n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, nullptr, out);
-}
-
-static int addr_create_impl(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces, const int32_t* lower, const int32_t* upper, int32_t n_patches,
-                            const int32_t* patch_sizes, const int32_t* const* patch_face_cells, const int32_t* const* patch_nbr_cells,
-                            bool ordered, int32_t n_tiles, const int32_t* tile_cell_start, mi_addr_t* out, TileLayout* prebuilt);
-
-extern "C" int mi_addr_create_coupled(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces,
-                                      const int32_t* lower, const int32_t* upper, int32_t n_patches,
-                                      const int32_t* patch_sizes, const int32_t* const* patch_face_cells,
-                                      const int32_t* const* patch_nbr_cells, mi_addr_t* out)
-{
-    return addr_create_impl(ctx, n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, patch_nbr_cells, false, 0, nullptr, out, nullptr);
 }
 
 // ORDERED addressing: the caller's numbering is kept (engine order == caller order, mi_addr_cell_perm is the identity), so the
@@ -410,7 +477,7 @@ extern "C" int mi_addr_create_ordered(mi_ctx_t ctx, int32_t n_cells, int32_t n_f
                                       const int32_t* const* patch_nbr_cells, int32_t n_tiles, const int32_t* tile_cell_start, mi_addr_t* out)
 {
     if (tile_cell_start && n_tiles <= 0) return fail(MI_ERR_ARG, "mi_addr_create_ordered: n_tiles must be positive when tile_cell_start is given");
-    return addr_create_impl(ctx, n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, patch_nbr_cells, true, n_tiles, tile_cell_start, out, nullptr);
+    return addr_create_impl(ctx, n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, patch_nbr_cells, false, true, n_tiles, tile_cell_start, out, nullptr);
 }
 
 // Renumber-at-bind (round 3): the mesh adopts the engine's cell order for its lifetime.  Host part (no device): the clustered layout
@@ -426,11 +493,8 @@ std::string adopt_engine_order(int32_t n_cells, int32_t n_faces, const int32_t* 
                                const int32_t* const* patch_face_cells, const int32_t* const* patch_nbr_cells, AdoptedMesh& M)
 {
     TileLayout L;
-    TileParams prm;
-    prm.tileCells = env_int("MI_TILE_CELLS", 0) > 0 ? env_int("MI_TILE_CELLS", 0) : 1024;
-    prm.slotCap = env_int("MI_TILE_SLOTS", 4094);
-    prm.reorder = env_int("MI_TILE_REORDER", -1);
-    prm.compact = false;
+    TileParams prm = addr_tile_params(nullptr, n_cells, false, false, 0, nullptr);   // (not a coarse level: no context needed)
+    prm.compact = false;   // whatever MI_ENTRY16 says: only the cell order and the tile starts are taken from this layout
     const std::string err = build_tile_layout(n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, prm, L, patch_nbr_cells);
     if (!err.empty()) return err;
     M.cellMap = L.e2c; M.tileStart = L.tileCellStart;
@@ -498,7 +562,7 @@ extern "C" int mi_addr_create_adopted(mi_ctx_t ctx, int32_t n_cells, int32_t n_f
         pfc[(size_t)p] = M.patchFaceCells[(size_t)p].data();
         if (patch_nbr_cells && patch_nbr_cells[p]) { pnb[(size_t)p] = M.patchNbrCells[(size_t)p].data(); anyNbr = true; }
     }
-    MICHK(addr_create_impl(ctx, n_cells, n_faces, M.lower.data(), M.upper.data(), n_patches, patch_sizes, pfc.data(), anyNbr ? pnb.data() : nullptr, true,
+    MICHK(addr_create_impl(ctx, n_cells, n_faces, M.lower.data(), M.upper.data(), n_patches, patch_sizes, pfc.data(), anyNbr ? pnb.data() : nullptr, false, true,
                            (int32_t)M.tileStart.size() - 1, M.tileStart.data(), out, nullptr));
     adopted_maps_out(M, cell_new_to_old_out, face_new_to_old_out, face_flipped_out, lower_out, upper_out);
     return MI_OK;
@@ -511,115 +575,6 @@ extern "C" int mi_addr_tile_starts(mi_addr_t a, int32_t* tile_cell_start_out)
     return MI_OK;
 }
 extern "C" int mi_addr_is_ordered(mi_addr_t a) { return a && a->identity ? 1 : 0; }
-
-// the tile-layout parameters of an addressing of n_cells cells on this context (coarse: a level of a GAMG hierarchy)
-static TileParams addr_tile_params(mi_ctx_t ctx, int32_t n_cells, bool coarse, bool ordered, int32_t n_tiles, const int32_t* tile_cell_start);
-// prebuilt != nullptr: the host layout was built elsewhere (the GAMG builder builds its levels' layouts on other threads while
-// it matches the next level) with addr_tile_params' parameters; it is moved from
-static int addr_create_impl(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces, const int32_t* lower, const int32_t* upper, int32_t n_patches,
-                            const int32_t* patch_sizes, const int32_t* const* patch_face_cells, const int32_t* const* patch_nbr_cells,
-                            bool ordered, int32_t n_tiles, const int32_t* tile_cell_start, mi_addr_t* out, TileLayout* prebuilt);
-static TileParams addr_tile_params(mi_ctx_t ctx, int32_t n_cells, bool coarse, bool ordered, int32_t n_tiles, const int32_t* tile_cell_start)
-{
-    TileParams prm;
-    prm.tileCells = env_int("MI_TILE_CELLS", 0);
-    if (prm.tileCells <= 0) {
-        const int target = (coarse && env_int("MI_SMALL_TILES", 1)) ? (int)(((int64_t)n_cells / std::max(1, ctx->nCU) + 63) / 64 * 64) : 1024;
-        prm.tileCells = std::min(1024, std::max(128, target));
-    }
-    prm.slotCap = env_int("MI_TILE_SLOTS", 4094);
-    prm.reorder = env_int("MI_TILE_REORDER", -1);
-    prm.compact = env_int("MI_ENTRY16", 0) != 0;
-    prm.keepOrder = ordered; prm.givenTileStart = tile_cell_start; prm.nGivenTiles = n_tiles;
-    return prm;
-}
-static int addr_create_impl(mi_ctx_t ctx, int32_t n_cells, int32_t n_faces, const int32_t* lower, const int32_t* upper, int32_t n_patches,
-                            const int32_t* patch_sizes, const int32_t* const* patch_face_cells, const int32_t* const* patch_nbr_cells,
-                            bool ordered, int32_t n_tiles, const int32_t* tile_cell_start, mi_addr_t* out, TileLayout* prebuilt)
-{
-    if (!ctx || !out || (n_faces > 0 && (!lower || !upper)) || n_patches < 0)
-        return fail(MI_ERR_ARG, "mi_addr_create: bad argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    mi_addr_s* a = new mi_addr_s();
-    a->ctx = ctx;
-    TileParams prm;
-    prm.tileCells = env_int("MI_TILE_CELLS", 0);
-    if (prm.tileCells <= 0) {
-        // 1024 cells per tile; the coarse levels of a GAMG hierarchy (ctx->coarseLevelBuild) are cut into enough tiles for
-        // every CU instead -- a shorter staging / row chain per workgroup, down to 128-cell tiles: their tile kernels take
-        // 4.6-5.5 us instead of 7-8 (profiles/r02_gamg_rocprof_summary.md), 2.08 -> 2.02 ms per V-cycle on the 216^3 box.
-        // The caller's own matrices keep 1024 (no gain measured for small PCG cases, and the partial-sum grouping of the
-        // Krylov reductions stays what the parity tests pinned).
-        const int target = (ctx->coarseLevelBuild && env_int("MI_SMALL_TILES", 1)) ? (int)(((int64_t)n_cells / std::max(1, ctx->nCU) + 63) / 64 * 64) : 1024;
-        prm.tileCells = std::min(1024, std::max(128, target));
-    }
-    prm.slotCap = env_int("MI_TILE_SLOTS", 4094);
-    prm.reorder = env_int("MI_TILE_REORDER", -1); // -1: Cuthill-McKee pre-ordering when the numbering has no locality (tiling.hpp)
-    prm.compact = env_int("MI_ENTRY16", 0) != 0; // opt-in: half the entry bytes, measured 2-4 % slower (profiles/r01_n_compact_entries_ab.md)
-    prm.keepOrder = ordered; prm.givenTileStart = tile_cell_start; prm.nGivenTiles = n_tiles;
-#ifdef MI_TIMING
-    auto ta__ = std::chrono::steady_clock::now();
-    auto ta_tick = [&](const char* what) { auto n = std::chrono::steady_clock::now(); if (n_cells > 1000000) fprintf(stderr, "[addr] %-28s %.4f s\n", what, std::chrono::duration<double>(n - ta__).count()); ta__ = n; };
-#endif
-    if (prebuilt) a->L = std::move(*prebuilt);
-    else {
-    const std::string err = build_tile_layout(n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, prm, a->L, patch_nbr_cells);
-    if (!err.empty()) { delete a; return fail(MI_ERR_LIMIT, "mi_addr_create: " + err); }
-    }
-#ifdef MI_TIMING
-    ta_tick("tile layout (host)");
-#endif
-    a->identity = true;
-    for (int32_t e = 0; e < n_cells; ++e) if (a->L.e2c[(size_t)e] != e) { a->identity = false; break; }
-    a->nLocalPatches = 0;
-    a->patchIsLocal.assign((size_t)std::max(n_patches, 0), 0);
-    if (patch_nbr_cells) for (int32_t p = 0; p < n_patches; ++p) if (patch_nbr_cells[p]) { a->nLocalPatches++; a->patchIsLocal[(size_t)p] = 1; }
-    TileLayout& L = a->L;
-    hipStream_t s = ctx->stream;
-    int r = MI_OK;
-#define UP(buf, vec) if (r == MI_OK) r = a->buf.upload(vec, s)
-    UP(e2c, L.e2c); UP(c2e, L.c2e); UP(tileCellStart, L.tileCellStart); UP(tileSlotStart, L.tileSlotStart); UP(tileIfaceSlot0, L.tileIfaceSlot0);
-    UP(tileHaloStart, L.tileHaloStart); UP(haloCell, L.haloCell); UP(tileSliceStart, L.tileSliceStart);
-    a->compact = L.compact;
-    if (L.compact) { UP(sliceEntryStart16, L.sliceEntryStart16); UP(entries16, L.entries16); UP(slotBase, L.slotBase); UP(tileSbStart, L.tileSbStart); }
-    else { UP(sliceEntryStart, L.sliceEntryStart); UP(entries, L.entries); }
-    UP(slotFace, L.slotFace);
-    UP(extSlot, L.extSlot); UP(interiorTiles, L.interiorTiles); UP(boundaryTiles, L.boundaryTiles);
-    UP(patchFaceCellsE, L.patchFaceCellsE); UP(faceSlot, L.faceSlot);
-#undef UP
-    if (r != MI_OK) { delete a; return r; }
-    if (hipStreamSynchronize(s) != hipSuccess) { delete a; return fail(MI_ERR_DEVICE, "upload failed"); }
-#ifdef MI_TIMING
-    ta_tick("uploads + synchronise");
-#endif
-    a->nInterior = (int32_t)L.interiorTiles.size();
-    a->nBoundary = (int32_t)L.boundaryTiles.size();
-    a->nEntries = (int64_t)(L.compact ? L.entries16.size() : L.entries.size()); // 32-bit words of row entries on the device
-    a->nHaloTot = (int64_t)L.haloCell.size();
-    a->lowerHost.resize((size_t)n_faces); a->upperHost.resize((size_t)n_faces);
-    mi::parallel_blocks(n_faces, 1 << 20, [&](int64_t b, int64_t e, int) {
-        std::memcpy(a->lowerHost.data() + b, lower + b, sizeof(int32_t) * (size_t)(e - b));
-        std::memcpy(a->upperHost.data() + b, upper + b, sizeof(int32_t) * (size_t)(e - b));
-    });
-    a->patchFaceCellsHost.resize((size_t)n_patches); a->patchNbrCellsHost.resize((size_t)n_patches);
-    for (int32_t p = 0; p < n_patches; ++p) {
-        a->patchFaceCellsHost[(size_t)p].assign(patch_face_cells[p], patch_face_cells[p] + patch_sizes[p]);
-        if (a->patchIsLocal[(size_t)p]) a->patchNbrCellsHost[(size_t)p].assign(patch_nbr_cells[p], patch_nbr_cells[p] + patch_sizes[p]);
-    }
-    // drop the big host tables that only the device needs (their memory goes back to the system on another thread)
-    {
-        Table<int32_t> slotFace, faceSlot;
-        if (!ctx->keepSlotTables) { slotFace.swap(L.slotFace); faceSlot.swap(L.faceSlot); }
-        mi::free_in_background(L.entries, L.entries16, L.sliceEntryStart16, L.slotBase, slotFace, L.haloCell, L.sliceEntryStart, faceSlot);
-        L.entries = Table<uint32_t>(); L.entries16 = Table<uint32_t>(); L.sliceEntryStart16 = Table<int32_t>(); L.slotBase = Table<uint16_t>();
-        L.haloCell = Table<int32_t>(); L.sliceEntryStart = Table<int32_t>();
-    }
-#ifdef MI_TIMING
-    ta_tick("host copies + frees");
-#endif
-    *out = a;
-    return MI_OK;
-}
 
 extern "C" int mi_addr_destroy(mi_addr_t a) { delete a; return MI_OK; }
 
@@ -2468,10 +2423,10 @@ extern "C" int mi_layout_build_host(int32_t n_cells, int32_t n_faces, const int3
 {
     if (!out) return fail(MI_ERR_ARG, "mi_layout_build_host: out is NULL");
     TileLayout* L = new TileLayout();
-    TileParams prm;
+    TileParams prm;   // the struct's own defaults, not addr_tile_params': the caps are this entry's arguments, and compact stays true whatever MI_ENTRY16 says (tests/test_layout.py reads the 16-bit tables here)
     if (tile_cells > 0) prm.tileCells = tile_cells;
     if (slot_cap > 0) prm.slotCap = slot_cap;
-    prm.reorder = env_int("MI_TILE_REORDER", -1);
+    prm.reorder = tile_reorder();
     const std::string err = build_tile_layout(n_cells, n_faces, lower, upper, n_patches, patch_sizes, patch_face_cells, prm, *L, patch_nbr_cells);
     if (!err.empty()) { delete L; return fail(MI_ERR_LIMIT, "mi_layout_build_host: " + err); }
     *out = L;

@@ -150,8 +150,8 @@ int32_t match_pairs(int32_t nFine, int32_t nFaces, const int32_t* lower, const i
 #endif
     std::atomic<bool> odd{false};
     parallel_blocks(nFaces, 1 << 18, [&](int64_t b, int64_t e, int) { bool any = false; for (int64_t f = b; f < e; ++f) any |= !(w[(size_t)f] > -1e20); if (any) odd = true; });
-    const bool parallel = !odd && host_threads() > 1 && nFine >= (1 << 15) && env_int_host("MI_MATCH_PARALLEL", 0) != 0;
-    const bool laterOnly = !odd && env_int_host("MI_MATCH_LATER_ONLY", 1) != 0;
+    const bool parallel = !odd && host_threads() > 1 && nFine >= (1 << 15) && sw::get(SW_MATCH_PARALLEL) != 0;
+    const bool laterOnly = !odd && sw::get(SW_MATCH_LATER_ONLY) != 0;
     sub("weights check");
     CellFaces F;
     if (laterOnly && forward && !parallel && owner_ranges(nFine, nFaces, lower, F.oS)) {

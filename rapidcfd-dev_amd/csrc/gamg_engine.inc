@@ -875,7 +875,7 @@ static int gamg_create_impl(mi_addr_t fine, const double* face_weights_host, int
         LevelMaps maps; bool haveMaps = false;
         std::mutex mu; std::condition_variable cv; bool layoutReady = false;   // (the next level's task waits for it)
     };
-    const bool wantDirect = env_int("MI_GAMG_DIRECT_SLOTS", 1) != 0 && dummy_levels == 0;
+    const bool wantDirect = sw::get(SW_GAMG_DIRECT_SLOTS) != 0 && dummy_levels == 0;
     Table<int32_t> fineFaceSlot;   // direct agglomeration tables: the finest level's faceSlot comes back from the device once
     if (wantDirect && fine->L.nFaces > 0) {
         fineFaceSlot.resize((size_t)fine->L.nFaces);
@@ -883,7 +883,7 @@ static int gamg_create_impl(mi_addr_t fine, const double* face_weights_host, int
     }
     Table<std::unique_ptr<LevelTask>> tasks;
     struct Joiner { Table<std::unique_ptr<LevelTask>>& t; ~Joiner() { for (auto& k : t) if (k && k->th.joinable()) k->th.join(); } } joiner{tasks};
-    const bool pipeline = env_int("MI_GAMG_PIPELINE", 1) != 0 && merge_levels == 1;
+    const bool pipeline = sw::get(SW_GAMG_PIPELINE) != 0 && merge_levels == 1;
     if (pipeline) H.onLevel = [&](int l) {
         GamgLevelHost& Lh = H.levels[(size_t)l];
         tasks.emplace_back(new LevelTask());
@@ -894,16 +894,14 @@ static int gamg_create_impl(mi_addr_t fine, const double* face_weights_host, int
             T->pfc[p] = Lh.patches[p].faceCells.data();
             T->pnb[p] = fine->patchIsLocal[(size_t)p] == 1 ? Lh.patches[p].nbrCells.data() : nullptr;
         }
-        c->coarseLevelBuild = true;
         const TileParams prm = addr_tile_params(c, Lh.nCoarse, true, false, 0, nullptr);
-        c->coarseLevelBuild = false;
         LevelTask* prevT = tasks.size() >= 2 ? tasks[tasks.size() - 2].get() : nullptr;
         const bool direct = wantDirect && fine->L.nFaces > 0;
         // MI_GAMG_INHERIT_TILES=1 (opt-in at the end of round 4: validated on the host -- tests/test_host_build.py,
         // tools/exp/inherit_tiles.cpp -- but not yet on the device): the level takes its tiles from its fine side's tiles instead
         // of clustering again (csrc/tiling.hpp inherit_tiles); on the 216^3 box the first two level layouts come out table for
         // table the same, without the clustering's sequential matching that is the critical path of this function.
-        const bool inherit = env_int("MI_GAMG_INHERIT_TILES", 0) != 0 && prm.tileCells == 1024;
+        const bool inherit = sw::get(SW_GAMG_INHERIT_TILES) != 0 && prm.tileCells == 1024;
         T->th = std::thread([T, prevT, &Lh, prm, nPatches, fine, direct, &fineFaceSlot, inherit] {
             TileParams lp = prm;
             Table<int32_t> inherited;
@@ -992,12 +990,8 @@ static int gamg_create_impl(mi_addr_t fine, const double* face_weights_host, int
                 if (T->err.empty()) T->err = "level tables were not built";
             }
             if (!T->err.empty()) { delete g; return fail(MI_ERR_LIMIT, "mi_gamg_create: " + T->err); }
-            r = addr_create_impl(c, L.nCoarse, L.nCoarseFaces, L.cLower.data(), L.cUpper.data(), nPatches, psz.data(), pfc.data(), pnb.data(), false, 0, nullptr, &ca, &T->L);
-        } else {
-        c->coarseLevelBuild = true;
-        r = mi_addr_create_coupled(c, L.nCoarse, L.nCoarseFaces, L.cLower.data(), L.cUpper.data(), nPatches, psz.data(), pfc.data(), pnb.data(), &ca);
-        c->coarseLevelBuild = false;
-        }
+            r = addr_create_impl(c, L.nCoarse, L.nCoarseFaces, L.cLower.data(), L.cUpper.data(), nPatches, psz.data(), pfc.data(), pnb.data(), true, false, 0, nullptr, &ca, &T->L);
+        } else r = addr_create_impl(c, L.nCoarse, L.nCoarseFaces, L.cLower.data(), L.cUpper.data(), nPatches, psz.data(), pfc.data(), pnb.data(), true, false, 0, nullptr, &ca, nullptr);
         if (r != MI_OK) { delete g; return r; }
         MI_TL("addressing on the device", l);
         for (const mi_addr_s::AmiPatch* q : fine->ami) {
@@ -1084,7 +1078,7 @@ static int gamg_create_impl(mi_addr_t fine, const double* face_weights_host, int
     }
     g->nGlobalCoarsest = g->rankOffset[(size_t)nRanks];
     if (g->nGlobalCoarsest > 4096) { delete g; return fail(MI_ERR_LIMIT, "coarsest level too large for the dense direct solve (nCellsInCoarsestLevel too big)"); }
-    if (reduce && nRanks > 1 && reduce->peerReady && env_int("MI_GAMG_GATHER_WIN", 1)) {
+    if (reduce && nRanks > 1 && reduce->peerReady && sw::get(SW_GAMG_GATHER_WIN)) {
         const int rg = gamg_gather_setup(g, reduce);   // collective; leaves g->gather == nullptr when any rank could not
         if (rg != MI_OK) { delete g; return rg; }
     }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "host_tables.hpp"
+#include "switches.hpp"
 
 namespace mi {
 // Host threads for the one-time layout build: plain std::thread workers pulling blocks of `grain` indices from an atomic
@@ -23,7 +24,7 @@ namespace mi {
 inline int host_threads()
 {
     static int n = [] {
-        const char* e = getenv("MI_HOST_THREADS");
+        const char* e = sw::text(SW_HOST_THREADS);
         if (e && *e) { const int v = atoi(e); return v < 1 ? 1 : (v > 64 ? 64 : v); }
         int v = (int)std::thread::hardware_concurrency();
         for (const char* name : {"LOCAL_WORLD_SIZE", "OMPI_COMM_WORLD_LOCAL_SIZE", "MV2_COMM_WORLD_LOCAL_SIZE", "SLURM_NTASKS_PER_NODE"}) {
@@ -34,7 +35,6 @@ inline int host_threads()
     }();
     return n;
 }
-inline int env_int_host(const char* name, int dflt) { const char* e = getenv(name); return (e && *e) ? atoi(e) : dflt; }
 // The workers are created once and shared by everything that runs at the same time (the hierarchy build of round 3 lays out
 // level l on other threads while level l + 1 is matched: with a team of threads per call the box ran 3 x 64 threads on 64
 // cores, and a 64-thread spawn per pass cost more than the pass): a call publishes its block counter, works on it itself,

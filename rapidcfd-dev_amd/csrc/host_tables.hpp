@@ -9,13 +9,15 @@
 #include <utility>
 #include <vector>
 
+#include "switches.hpp"
+
 namespace mi {
 // Large tables (>= 4 MiB) are placed on 2 MiB boundaries and advised to use transparent huge pages (round 6): a 10 M-cell layout first-touches
 // ~1 GB of fresh pages, a quarter of a million 4 KiB faults on the threads that fill the tables -- 0.4 s of the first mi_addr_create of a
 // process on the GPU box's host (profiles/r06_startup_timing.md).  No effect where THP is off; the tables' contents are what they were.
 inline void* host_table_alloc(size_t bytes)
 {
-    static const bool thp = [] { const char* e = std::getenv("MI_HOST_THP"); return !e || e[0] != '0'; }();   // MI_HOST_THP=0: plain malloc (A/B)
+    static const bool thp = [] { const char* e = sw::text(SW_HOST_THP); return !e || e[0] != '0'; }();   // MI_HOST_THP=0: plain malloc (A/B)
     if (thp && bytes >= ((size_t)4 << 20)) {
         void* p = nullptr;
         if (posix_memalign(&p, (size_t)2 << 20, bytes) == 0 && p) { (void)madvise(p, bytes, MADV_HUGEPAGE); return p; }

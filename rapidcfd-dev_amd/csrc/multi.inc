@@ -42,7 +42,7 @@ int launch_tile_multi_n(mi_matrix_s* m, const MultiIO& io, const MultiDiag& dg, 
     const int nOperands = OP == OP_SUMA ? 0 : 2 * NRHS, nRD = OP == OP_AINV ? (SRD ? 1 : NRHS) : 0;
     t.offLow = slots; t.offX = 2 * slots; t.offRD = 2 * slots + nOperands * xlen; t.offSB = xlen;
     const size_t lds = sizeof(double) * ((size_t)t.offRD + (size_t)nRD * (size_t)xlen);
-    if (env_int("MI_DEBUG_MULTI", 0)) fprintf(stderr, "[multi] OP %d NRHS %d SRD %d: slots %d xlen %d (maxCells %d maxHalo %d) lds %zu\n", OP, NRHS, (int)SRD, slots, xlen, L.maxCells, L.maxHalo, lds);
+    if (sw::get(SW_DEBUG_MULTI)) fprintf(stderr, "[multi] OP %d NRHS %d SRD %d: slots %d xlen %d (maxCells %d maxHalo %d) lds %zu\n", OP, NRHS, (int)SRD, slots, xlen, L.maxCells, L.maxHalo, lds);
     if (lds > 159 * 1024) return MI_ERR_LIMIT;     // (no message: the caller falls back to fewer operands per pass)
     MultiVec<NRHS> V;
     for (int k = 0; k < NRHS; ++k) {
@@ -93,7 +93,7 @@ int tile_multi(mi_matrix_s* m, int nrhs, const MultiIO& io, const MultiDiag& dg,
     if (!m->bound) return fail(MI_ERR_STATE, "matrix coefficients not bound (mi_matrix_set_coeffs)");
     if ((OP == OP_AMUL || OP == OP_PROLOGUE) && !a->ami.empty()) for (int v = 0; v < 2 * nrhs; ++v) MICHK(ami_fill(m, io.x[v]));
     *fused = true;
-    if (!a->compact && env_int("MI_MULTI_TILE", 1)) {
+    if (!a->compact && sw::get(SW_MULTI_TILE)) {
         static const int all[3] = {0, 1, 2};
         int rc = launch_tile_multi_group<OP>(m, nrhs, all, io, dg);
         if (rc == MI_ERR_LIMIT && nrhs == 3) {       // two components and one
@@ -108,7 +108,7 @@ int tile_multi(mi_matrix_s* m, int nrhs, const MultiIO& io, const MultiDiag& dg,
         if (rc != MI_ERR_LIMIT) return rc;
     }
     *fused = false;
-    if (env_int("MI_DEBUG_MULTI", 0)) fprintf(stderr, "[multi] OP %d: single-vector fall-back (compact %d)\n", OP, (int)a->compact);
+    if (sw::get(SW_DEBUG_MULTI)) fprintf(stderr, "[multi] OP %d: single-vector fall-back (compact %d)\n", OP, (int)a->compact);
     if (OP == OP_PROLOGUE) return MI_OK;   // (the caller runs the separate prologue passes)
     if (OP == OP_SUMA || dg.diag[0] != m->diagE.p) return fail(MI_ERR_LIMIT, "multi-vector tile pass: the tile image does not fit the LDS (per-component diagonals have no single-vector path)");
     for (int c = 0; c < nrhs; ++c) {   // (a finished component's single-vector passes are not gated: they only cost time)
@@ -197,7 +197,7 @@ namespace {
 // mi_pbicg_solve takes the multi-vector solver's route for its one right-hand side exactly when mi_pbicg_solve_multi would not hand it back
 bool pbicg_single_via_multi(const mi_matrix_s* m)
 {
-    if (env_int("MI_PBICG_MULTI", 1) == 0 || m->addr->compact || !m->addr->ami.empty()) return false;
+    if (sw::get(SW_PBICG_MULTI) == 0 || m->addr->compact || !m->addr->ami.empty()) return false;
     return !(comm_attached(m) && (comm_any_ami(m) || comm_any_compact(m)));
 }
 }
@@ -212,7 +212,7 @@ extern "C" int mi_pbicg_solve_multi(mi_matrix_t m, int32_t nrhs, const double* c
     mi_ctx_s* c = a->ctx;
     HIPCHK(hipSetDevice(c->device));
     const bool att = comm_attached(m);
-    if ((att && (comm_any_ami(m) || comm_any_compact(m))) || env_int("MI_PBICG_MULTI", 1) == 0) {
+    if ((att && (comm_any_ami(m) || comm_any_compact(m))) || sw::get(SW_PBICG_MULTI) == 0) {
         // component by component, as the reference (a decomposed matrix with cyclicAMI patches interpolates per operand inside
         // its tile operators; MI_PBICG_MULTI=0: A/B hook)
         if (diag_dev) return fail(MI_ERR_UNSUPPORTED, "mi_pbicg_solve_multi: per-component diagonals with MI_PBICG_MULTI=0 (or on an attached matrix with cyclicAMI patches): bind each diagonal and call mi_pbicg_solve");

@@ -38,6 +38,7 @@ constexpr int FUSED_LP = 2544;                   // pairs of z in LDS per workgr
 constexpr int FUSED_BAR_WORDS = BAR_LINE * (RG + 64) + RG + 64;   // + pending flag of every chunk, + workgroup 0's
 constexpr int FUSED_PEND_AT = BAR_LINE * (RG + 64);
 constexpr long long FUSED_WAIT_POLLS = 1000;     // a poll is a memory round trip (~1 us): the normal wait is a few tens
+static_assert(sw::table[SW_PCG_FUSE_POLLS].dflt == FUSED_WAIT_POLLS, "switches.hpp: the default of MI_PCG_FUSE_POLLS is FUSED_WAIT_POLLS");
 
 struct FusedArgs {
     PcgState* st;
@@ -352,11 +353,11 @@ int pcg_fused_rp_launch(mi_matrix_s* m, int it, int precond)
     A.wA = wA; A.rD = m->rD.p; A.pA = pA; A.psi = psi; A.rA = rA; A.n = a->L.nCells;
     A.hist = m->hist.p; A.histLen = m->histLen;
     A.bar = m->fusedBar.p; A.gen = m->fusedGen;
-    static const long long polls = (long long)env_int("MI_PCG_FUSE_POLLS", (int)FUSED_WAIT_POLLS);
+    static const long long polls = (long long)sw::get(SW_PCG_FUSE_POLLS);
     A.maxPolls = polls;
     A.testMode = c->pcgFuseTest;
     void* args[1] = {&A};
-    static const int coop = env_int("MI_PCG_FUSE_COOP", 0);   // 1 (A/B): hipLaunchCooperativeKernel -- ~22 us per launch on this runtime
+    static const int coop = sw::get(SW_PCG_FUSE_COOP);   // 1 (A/B): hipLaunchCooperativeKernel -- ~22 us per launch on this runtime
     if (coop) {
         if (hipLaunchCooperativeKernel(fn, dim3(RG), dim3(RB), args, (unsigned int)lds, s) != hipSuccess) {
             (void)hipGetLastError();

@@ -565,7 +565,7 @@ struct PeerHalo {
 };
 
 bool peer_halo_ready(const mi_matrix_s* m) { return m->dpc && m->dpc->ph && m->dpc->ph->ready; }
-bool peer_reduce_ready(const mi_matrix_s* m) { return m->dpc && m->dpc->reduce && m->dpc->reduce->peerReady && env_int("MI_PEER_GLOBALIZE", 1) != 0; }
+bool peer_reduce_ready(const mi_matrix_s* m) { return m->dpc && m->dpc->reduce && m->dpc->reduce->peerReady && sw::get(SW_PEER_GLOBALIZE) != 0; }
 int peer_globalize(mi_matrix_s* m, int n, double* const* P)
 {
     if (n < 1 || n > 6) return fail(MI_ERR_LIMIT, "peer_globalize: one to six sums");
@@ -756,7 +756,7 @@ extern "C" int mi_matrix_peer_halo_auto(mi_matrix_t m, int32_t* enabled_out)
         P->mapped[(size_t)e.peer] = q;
         if (!on_my_device(c, q)) oneDevice = false;
     }
-    if (ok && !P->fineGrained && !oneDevice && !env_int("MI_PEER_ALLOW_COARSE", 0)) ok = false;
+    if (ok && !P->fineGrained && !oneDevice && !sw::get(SW_PEER_ALLOW_COARSE)) ok = false;
     // From here to the end every LOCAL failure (an allocation, a copy) is folded into `ok` and the rank carries on to the next
     // agreement: the function is called collectively from mi_matrix_attach_comm, and a rank that returned early would leave
     // the others blocked in their next all-reduce (ADVICE r03).  Collective calls are issued by every rank regardless.
@@ -933,7 +933,7 @@ int dpcg_persist_enqueue(mi_matrix_s* m, int n_iters);
 // the fused iteration: three launches, no collective call
 bool dpcg_fused_usable(const mi_matrix_s* m)
 {
-    return peer_halo_ready(m) && m->dpc->reduce->peerReady && !m->asym && !comm_any_compact(m) && env_int("MI_DPCG_FUSED", 1) != 0;
+    return peer_halo_ready(m) && m->dpc->reduce->peerReady && !m->asym && !comm_any_compact(m) && sw::get(SW_DPCG_FUSED) != 0;
 }
 int dpcg_fused_iterate(mi_matrix_s* m, int32_t n_iters, int32_t record_amul_events)
 {
@@ -971,7 +971,7 @@ int dpcg_fused_iterate(mi_matrix_s* m, int32_t n_iters, int32_t record_amul_even
     //   3            both inside the passes: 62.2 us
     // (the phase loop over RCCL: 80.6 us.)  Ranks that share a device always take 5: there only single workgroups may wait
     // for another process.
-    const int want = env_int("MI_DPCG_FUSED", 1);
+    const int want = sw::get(SW_DPCG_FUSED);
     const int mode = (D.reduce->sharedDevice || (want != 3 && want != 4)) ? 5 : want;
     const PeerAR ar = peer_ar(D.reduce);
     const FusedCtl F{D.reduce->fusedEpoch, P->epoch, P->tickets + 1};

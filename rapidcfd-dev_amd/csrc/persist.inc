@@ -73,6 +73,7 @@ struct PersistArgs {
 constexpr int BAR_LINE = 16;                       // 32-bit words per slot (64 bytes)
 constexpr int BAR_WORDS = BAR_LINE * (1024 + 64);
 constexpr long long BAR_POLLS = 4000000ll;         // a few seconds
+static_assert(sw::table[SW_PERSIST_BAR_POLLS].dflt == BAR_POLLS, "switches.hpp: the default of MI_PERSIST_BAR_POLLS is BAR_POLLS");
 template <int NV, class Pre, class Root>
 __device__ __forceinline__ void grid_barrier(unsigned int* bar, unsigned int G, unsigned int& gen, bool& barDead, PcgState* st, double (&vals)[NV > 0 ? NV : 1], double* red16, Pre pre, Root root,
                                              long long maxPolls = BAR_POLLS, bool arrive = true)
@@ -667,14 +668,14 @@ bool persist_fits_layout(const mi_matrix_s* m)
                     const void* fn = persist_fn(tm, dist != 0);
                     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PERSIST_LDS_MAX) != hipSuccess) ok = false;
                     if (ok && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, fn, 1024, PERSIST_LDS_MAX) != hipSuccess || perCU < 1)) ok = false;
-                    if (!ok && env_int("MI_DEBUG_PERSIST", 0)) { fprintf(stderr, "[persist] instantiation TMAX %d DIST %d refused (LDS attribute / occupancy)\n", tm, dist); break; }
+                    if (!ok && sw::get(SW_DEBUG_PERSIST)) { fprintf(stderr, "[persist] instantiation TMAX %d DIST %d refused (LDS attribute / occupancy)\n", tm, dist); break; }
                 }
             // Ranks that SHARE a device (tests) would run their litmus grids side by side with the other processes' work, where a
             // short wait can run out for scheduling reasons alone; their grids are sized by hand anyway (MI_PERSIST_GRID).
-            if (ok && env_int("MI_PERSIST_LITMUS", 1) != 0 && !c->persistShared) {
+            if (ok && sw::get(SW_PERSIST_LITMUS) != 0 && !c->persistShared) {
                 bool clean = false;
                 if (persist_litmus(c, 64, &clean) != MI_OK || !clean) ok = false;
-                if (!ok && env_int("MI_DEBUG_PERSIST", 0)) fprintf(stderr, "[persist] the grid-barrier litmus failed: persistent kernels off on this context\n");
+                if (!ok && sw::get(SW_DEBUG_PERSIST)) fprintf(stderr, "[persist] the grid-barrier litmus failed: persistent kernels off on this context\n");
                 c->stats[2] += 1;   // mi_ctx_stat(2): barrier litmus runs on this context
             }
             c->persistCoop = ok ? 1 : 0;
@@ -728,7 +729,7 @@ int persist_enqueue(mi_matrix_s* m, int n_iters, int precond, bool dist)
     const int tmax = persist_tmax_for(P.tilesPerWG);
     const size_t lds = persist_lds(a, tmax, &t, &P.offPersist);
     P.st = c->state.p; P.psi = psi; P.rA = rA; P.pA = pA; P.rD = m->rD.p; P.P1 = c->partial.p;
-    P.pB = pA; P.Z = nullptr; P.zpMaxTiles = env_int("MI_PERSIST_ZP", 1);
+    P.pB = pA; P.Z = nullptr; P.zpMaxTiles = sw::get(SW_PERSIST_ZP);
     if (!dist) {   // ZP: the second pA buffer (the Amul result vector of the five-launch pipeline, unused here) and z
         MICHK(m->vec(WV_WA, &P.pB));
         // (z is gathered like pA: halo entries of an un-attached matrix's processor patches index the ext region behind the
@@ -744,7 +745,7 @@ int persist_enqueue(mi_matrix_s* m, int n_iters, int precond, bool dist)
     P.bar = reinterpret_cast<unsigned int*>(m->persistScratch.p + (((size_t)3 * (size_t)G + 15) & ~(size_t)15));
     P.hist = m->hist.p; P.histLen = m->histLen; P.nIt = n_iters; P.nTiles = a->L.nTiles;
     P.pmode = precond == MI_PRECOND_DIAGONAL ? 1 : 2;
-    P.barPolls = (long long)env_int("MI_PERSIST_BAR_POLLS", (int)BAR_POLLS); P.skipArrival = env_int("MI_PERSIST_SKIP_ARRIVAL", 0);
+    P.barPolls = (long long)sw::get(SW_PERSIST_BAR_POLLS); P.skipArrival = sw::get(SW_PERSIST_SKIP_ARRIVAL);
     if (dist) {
         PeerHalo* H = m->dpc->ph;
         PersistDist& d = P.d;

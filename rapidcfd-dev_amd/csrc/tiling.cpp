@@ -62,7 +62,7 @@ int32_t match_level(const Graph& g, int32_t cellCap, int32_t slotCap, Table<int3
     const int32_t n = g.n;
     match.resize((size_t)n);
     cmap.resize((size_t)n);
-    if (host_threads() > 1 && n >= (1 << 15) && env_int_host("MI_MATCH_PARALLEL", 0) != 0) {
+    if (host_threads() > 1 && n >= (1 << 15) && sw::get(SW_MATCH_PARALLEL) != 0) {
         ClusterGraph cg{n, true, &g, cellCap, slotCap};
         Table<uint8_t> proposer;
         greedy_match_parallel(cg, match, proposer);

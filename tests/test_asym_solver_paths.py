@@ -58,8 +58,9 @@ def _case(pkg, dims):
 
 
 def _ctx(pkg, monkeypatch, env=(), **opts):
-    """a context created under these switches; MI_MULTI_TILE and MI_PBICG_MULTI are read per call, so they stay set while the
-    caller solves on this context (the next _ctx sets every switch again)"""
+    """a context created under these switches.  csrc/switches.hpp says when each is read: most at mi_ctx_create, MI_ENTRY16 when the
+    addressing is created, MI_MULTI_TILE and MI_PBICG_MULTI on every call -- so they stay set while the caller solves on this
+    context (the next _ctx sets every switch again)"""
     for k, v in {**BASE_ENV, **dict(env)}.items():
         monkeypatch.setenv(k, v)
     ctx = pkg.engine.Context(0, torch.cuda.current_stream().cuda_stream)
