@@ -104,7 +104,8 @@ int mi_ctx_set_option(mi_ctx_t ctx, const char *name, int32_t value);
  * mi_pbicg_solve or mi_pbicg_solve_multi -- through the multi-vector solver (MI_STAT_PBICG_MULTI), through the device loop
  * pbicg_solve_device (MI_STAT_PBICG_DEVICE, once per component) and host-stepped (MI_STAT_PBICG_HOST_STEPPED); PBiCGStab solves
  * through the device loop (MI_STAT_PBICGSTAB_DEVICE) and host-stepped (MI_STAT_PBICGSTAB_HOST_STEPPED); PBiCGStab solves of either
- * loop that ended at the mid-iteration exit, converged on the residual of sA (MI_STAT_PBICGSTAB_MID_EXIT).  (The device loops
+ * loop that ended at the mid-iteration exit, converged on the residual of sA (MI_STAT_PBICGSTAB_MID_EXIT); tile launches that
+ * took the persistent walk of MI_TILE_PERSIST, fewer workgroups than tiles (MI_STAT_TILE_PERSIST).  (The device loops
  * share one host frame in csrc/engine.hip -- stage_in, drive_batches, finish_device -- around the bodies they enqueue:
  * bicg_enqueue for pbicg_solve_device, stab_enqueue for pbicgstab_solve_device, the in-line body of mi_pbicg_solve_multi.) */
 #define MI_STAT_PERSIST_PCG 0
@@ -119,6 +120,7 @@ int mi_ctx_set_option(mi_ctx_t ctx, const char *name, int32_t value);
 #define MI_STAT_PBICGSTAB_DEVICE 9
 #define MI_STAT_PBICGSTAB_HOST_STEPPED 10
 #define MI_STAT_PBICGSTAB_MID_EXIT 11
+#define MI_STAT_TILE_PERSIST 12
 int mi_ctx_stat(mi_ctx_t ctx, int32_t which, int64_t *out);
 const char *mi_last_error(void);
 /* 1 if a usable gfx950 device is visible to this process, else 0 */

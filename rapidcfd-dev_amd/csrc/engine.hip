@@ -85,7 +85,7 @@ struct mi_ctx_s {
     int tileFlags = 0, attachEvents = 0, persist = 0, xcdRows = 0, deferPsi = 0, fusePerm = 0, pairAT = 0, fusePrologue = 0, multiPipe = 0, winDirect = 0, gamgGraphAttached = 0;
     int pcgPersist = 0, pcgFuseRP = 0, pcgFuseTest = 0, persistGrid = 0, persistShared = 0, fuseFinal = 0, amulBS = 0, pcgBatch = 0, pcgGraph = 0, pbicgHostStepped = 0;
     int gamgDeviceInvert = 0, gamgAlwaysAgglomerate = 0, gamgGraph = 0, gamgFuse = 0;
-    int64_t stats[12] = {}; // mi_ctx_stat
+    int64_t stats[13] = {}; // mi_ctx_stat
     int persistCoop = -1; // cooperative launch of the persistent kernel possible on this device AND its barrier litmus clean (-1: not asked yet)
     uint64_t faultEpoch = 0; // faults of the persistent kernel reported on this context so far (fetch_state); a matrix re-zeroes its barrier words when it has missed one
     struct mi_matrix_s* session = nullptr; // matrix whose mi_pcg_begin/iterate/end session owns this context's solver scratch (partial, scalars, state)
@@ -871,7 +871,7 @@ int launch_tile_bs(mi_matrix_s* m, const TileArgs& args, int nTiles, size_t lds)
                 occ = nb > 0 ? nb : 1;                                                                                  \
             }                                                                                                           \
             const int slots = ((occ * cx->nCU * cx->persist) / 8) * 8;                                                  \
-            if (slots >= 8 && nTiles > 2 * slots) grid = slots;                                                         \
+            if (slots >= 8 && nTiles > 2 * slots) { grid = slots; cx->stats[12] += 1; } /* mi_ctx_stat(12): persistent walks */ \
         }                                                                                                               \
         if (m->kevStart) /* start/stop events stamped by the kernel's own begin/end: the profiler's clock */           \
             hipExtLaunchKernelGGL((tile_kernel<OP, ASYM, TRANS, BS, C16>), dim3(grid), dim3(BS), (uint32_t)lds, s, m->kevStart, m->kevStop, 0, args); \

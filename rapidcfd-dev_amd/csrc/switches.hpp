@@ -57,7 +57,7 @@ namespace mi {
     X(FUSE_PERM,               "MI_FUSE_PERM",               1,        CTX,           AB,        nullptr,               "caller-order operators gather / scatter through e2c inside the tile kernel") \
     X(DPCG_FUSED,              "MI_DPCG_FUSED",              1,        CALL,          AB,        nullptr,               "distributed PCG with the halo exchange and the sums inside its kernels (peer.inc)") \
     X(PBICG_HOST_STEPPED,      "MI_PBICG_HOST_STEPPED",      0,        CTX,           AB,        nullptr,               "1: PBiCG / PBiCGStab through their host-stepped loops instead of the device-resident ones") \
-    X(TILE_FLAGS,              "MI_TILE_FLAGS",              1,        CTX,           AB,        nullptr,               "bit0: coefficient segments are staged with non-temporal loads (read once per launch): Amul -4 % (profiles/r02_b_cache_policy_ab.md)") \
+    X(TILE_FLAGS,              "MI_TILE_FLAGS",              1,        CTX,           AB,        nullptr,               "bit0: coefficient segments are staged with non-temporal loads (read once per launch): Amul -4 % (profiles/r02_b_cache_policy_ab.md); bit1: non-temporal loads of the row entries; bit2: non-temporal stores of the result y; bit3: non-temporal loads of the diagonal (Amul); same bits in every combination") \
     X(TILE_PERSIST,            "MI_TILE_PERSIST",            0,        CTX,           AB,        nullptr,               "persistent tile launches: workgroups = resident slots, each walks a run of tiles") \
     X(XCD_ROWS,                "MI_XCD_ROWS",                1,        CTX,           AB,        nullptr,               "XCD-aware block mapping of the caller-order row passes") \
     X(SMALL_TILES,             "MI_SMALL_TILES",             1,        ADDR,          AB,        nullptr,               "coarse GAMG levels are cut into enough tiles for every CU, down to 128 cells (engine.hip: addr_tile_params)") \

@@ -240,7 +240,8 @@ class Context:
         2 = grid-barrier litmus runs, 3 = V-cycles of a decomposed case replayed as a hipGraph, 4 = launches of the fused residual / direction kernel of PCG,
         5 = batches of PCG iterations replayed as a hipGraph (mi_pcg_solve), PBiCG loops run through 6 = the multi-vector solver,
         7 = pbicg_solve_device (once per component), 8 = the host-stepped loop (MI_PBICG_HOST_STEPPED), PBiCGStab solves through
-        9 = the device loop (pbicgstab_solve_device), 10 = the host-stepped loop, 11 = PBiCGStab solves that ended at the mid-iteration exit.
+        9 = the device loop (pbicgstab_solve_device), 10 = the host-stepped loop, 11 = PBiCGStab solves that ended at the mid-iteration exit,
+        12 = tile launches that took the persistent walk (MI_TILE_PERSIST: fewer workgroups than tiles).
         (6, 7 and 9 are bodies enqueued by the one batch driver of csrc/engine.hip, drive_batches.)"""
         v = C.c_int64(0)
         _chk(lib().mi_ctx_stat(self.h, C.c_int32(which), C.byref(v)))

@@ -135,6 +135,35 @@ def test_engine_assembly_bit_exact(pkg, orc, dims):
 @pytest.mark.parametrize("mode", ["fixed256", "fixed1024", "tiles", "tiles_unstaged", "fixed_unstaged"])
 @pytest.mark.parametrize("name", ["box", "graph"])
 def test_row_passes_bit_exact_for_every_block_shape(pkg, orc, monkeypatch, name, mode):
+    _row_passes_bit_exact(pkg, orc, monkeypatch, name, mode, "default")
+
+
+# the forms of the row tables and of the block mapping that the defaults never take: (tables, mode)
+OTHER_TABLES = ([("row32", m) for m in ("fixed256", "fixed1024", "tiles", "tiles_unstaged", "fixed_unstaged")]
+                + [("noxcd", m) for m in ("fixed256", "tiles")])
+
+
+def _set_tables(monkeypatch, tables):
+    """before the context (MI_XCD_ROWS is read by mi_ctx_create) and before the first row pass (MI_ROW16: ensure_caller_tables)"""
+    monkeypatch.delenv("MI_ROW16", raising=False); monkeypatch.delenv("MI_XCD_ROWS", raising=False)
+    if tables == "row32":       # the 32-bit row tables: also what a block that does not fit 16 bits falls back to
+        monkeypatch.setenv("MI_ROW16", "0")
+    elif tables == "noxcd":     # blockIdx.x as it comes, in every row pass, face pass and gradient pass
+        monkeypatch.setenv("MI_XCD_ROWS", "0")
+    else:
+        assert tables == "default"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tables,mode", OTHER_TABLES)
+@pytest.mark.parametrize("name", ["box", "graph"])
+def test_row_passes_bit_exact_with_the_other_row_tables(pkg, orc, monkeypatch, name, mode, tables):
+    """the same statement with the 32-bit row tables (MI_ROW16=0) in every block shape, and without the XCD-aware block mapping
+    (MI_XCD_ROWS=0)"""
+    _row_passes_bit_exact(pkg, orc, monkeypatch, name, mode, tables)
+
+
+def _row_passes_bit_exact(pkg, orc, monkeypatch, name, mode, tables):
     """The row passes (row face ops, fvm::laplacian, fvm::div, surfaceIntegrate, Gauss grad) own blocks of consecutive cells:
     fixed ranges of 256 / 1024 cells in the caller's numbering, the layout's tiles under ordered addressing; neighbour-side
     faces inside the block come from LDS, cut faces are gathered / recomputed.  Same bits as the oracle in every shape,
@@ -142,6 +171,7 @@ def test_row_passes_bit_exact_for_every_block_shape(pkg, orc, monkeypatch, name,
     import torch
     from conftest import random_graph_case
     eng, syn = pkg.engine, pkg.synthetic
+    _set_tables(monkeypatch, tables)
     ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
     host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
@@ -466,6 +496,18 @@ def test_engine_scheme_front_end_bit_exact(pkg, orc, dims):
 @pytest.mark.parametrize("mode", ["fixed256", "fixed1024", "tiles", "tiles_unstaged"])
 @pytest.mark.parametrize("name", ["box", "graph"])
 def test_fused_assembly_equals_the_unfused_sequence_bit_for_bit(pkg, orc, monkeypatch, name, mode):
+    _fused_assembly_bit_exact(pkg, orc, monkeypatch, name, mode, "default")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tables,mode", [tm for tm in OTHER_TABLES if tm[1] != "fixed_unstaged"])
+@pytest.mark.parametrize("name", ["box", "graph"])
+def test_fused_assembly_bit_exact_with_the_other_row_tables(pkg, orc, monkeypatch, name, mode, tables):
+    """... and with the 32-bit row tables (MI_ROW16=0) / without the XCD-aware block mapping (MI_XCD_ROWS=0)"""
+    _fused_assembly_bit_exact(pkg, orc, monkeypatch, name, mode, tables)
+
+
+def _fused_assembly_bit_exact(pkg, orc, monkeypatch, name, mode, tables):
     """mi_fvm_assemble -- [fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- explicit terms] in ONE row pass -- against (a) the
     oracle's unfused sequence (tests/assembly_full_size.py: oracle_assemble) and (b) the engine's own scheme-by-scheme calls combined
     with mi_vec_axpby the way fvMatrix::operator+ / - combine them (fvMatrix.C:1693-2030), for three systems (momentum-like with three
@@ -476,6 +518,7 @@ def test_fused_assembly_equals_the_unfused_sequence_bit_for_bit(pkg, orc, monkey
     import assembly_full_size as afs
     from conftest import random_graph_case
     eng, syn = pkg.engine, pkg.synthetic
+    _set_tables(monkeypatch, tables)
     ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
     host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]

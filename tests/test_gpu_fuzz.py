@@ -1,7 +1,13 @@
 """GPU (-m gpu): randomised sweep of the tile engine against the oracle.  Ragged graphs (hub-free and hubby), symmetric and
 asymmetric coefficients, a random cyclic patch pair (partners in the same tile, in other tiles, repeated cells), tiny to
 normal tiles (many halos / cut faces), both row-entry formats: every operator of the SpMV family bit for bit, AINV and
-Jacobi bit for bit, patchNeighbourField, and a few Krylov iterations within the history bar."""
+Jacobi bit for bit, patchNeighbourField, and a few Krylov iterations within the history bar.
+
+The compact (16-bit) row entries exist only for layouts whose owners have at most eight own faces towards a tile and whose tiles
+have at most 4095 local cells; build_tile_layout drops them for the whole layout otherwise, without a word.  The shapes of CAPPED
+lose them on the plain random graph (an owner with nine or more faces), so their MI_ENTRY16=1 halves run on capped_graph_case --
+the same graph with every owner's faces beyond its first eight dropped -- and every MI_ENTRY16=1 case proves from the entry
+count that the compact form is what the kernels read (tests/test_layout.py pins both premises on the CPU)."""
 import copy
 
 import numpy as np
@@ -22,27 +28,67 @@ def host(t):
     return t.cpu().numpy()
 
 
-CASES = [(seed, n, extra, tile, sym, entry16)
-         for seed, n, extra, tile in [(1, 40, 1.0, 8), (2, 257, 2.0, 64), (3, 900, 3.0, 128), (4, 1500, 1.5, 1024), (5, 3000, 2.5, 256),
-                                      (6, 64, 6.0, 16), (7, 2200, 0.6, 96)]
-         for sym in (True, False) for entry16 in (0, 1)]
+def capped_graph_case(pkg, n=700, extra=2.5, seed=3, symmetric=True, cap=8):
+    """random_graph_case with every owner's faces beyond its first `cap` dropped (the faces are sorted by (owner, neighbour), so an
+    owner keeps its chain face and the graph stays connected), the coefficients rebuilt from the kept faces the same way: no
+    owner has more than eight own faces, so the rule-1 field k of the compact row entries stays within its three bits."""
+    syn = pkg.synthetic
+    base = random_graph_case(pkg, n, extra=extra, seed=seed, symmetric=symmetric)
+    lo, up = base.lower_addr, base.upper_addr
+    first = np.searchsorted(lo, lo, side="left")              # position of each owner's first face
+    keep = np.arange(lo.shape[0]) - first < cap
+    lo, up = lo[keep], up[keep]
+    nf = lo.shape[0]
+    c = syn.splitmix_uniform(seed + 1, 2 * nf)
+    upper = -(0.2 + c[:nf])
+    lower = None if symmetric else -(0.2 + c[nf:])
+    diag = np.zeros(n)
+    np.subtract.at(diag, lo, upper if symmetric else lower)
+    np.subtract.at(diag, up, upper)
+    diag += 0.05 + syn.splitmix_uniform(seed + 2, n)
+    source = syn.splitmix_uniform(seed + 3, n) - 0.5
+    return syn.LduCase(n, lo, up, diag, upper, lower, source)
 
 
-@pytest.mark.parametrize("seed,n,extra,tile,sym,entry16", CASES)
-def test_random_coupled_matrices_every_operator(pkg, orc, seed, n, extra, tile, sym, entry16, monkeypatch):
-    syn, eng = pkg.synthetic, pkg.engine
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    case = copy.copy(random_graph_case(pkg, n, extra=extra, seed=seed, symmetric=sym))
-    npair = max(1, n // 15)
+def cyclic_pair(pkg, case, seed, sym, div=15):
+    """the random cyclic patch pair of the sweep on a copy of `case`: (case with interfaces and a dominant diagonal, a, b)"""
+    syn = pkg.synthetic
+    n = case.n_cells
+    case = copy.copy(case)
+    npair = max(1, n // div)
     u = syn.splitmix_uniform(seed + 11, 2 * npair)
     a = (u[:npair] * n).astype(np.int32); b = (u[npair:] * n).astype(np.int32)
     kb = -(0.05 + 0.3 * syn.splitmix_uniform(seed + 12, npair))
     ki = kb if sym else -(0.05 + 0.3 * syn.splitmix_uniform(seed + 13, npair))
     case.interfaces = [syn.Interface(0, 1, a, kb, ki), syn.Interface(0, 0, b, kb, ki)]
     case.diag = case.diag + np.bincount(a, -kb, n) + np.bincount(b, -kb, n)      # keep the rows dominant
+    return case, a, b
+
+
+# shapes whose plain random graph loses the compact form (an owner with nine or more own faces): MI_ENTRY16=1 runs the capped graph
+CAPPED = {(3, 900, 3.0, 128), (4, 1500, 1.5, 1024), (5, 3000, 2.5, 256), (6, 64, 6.0, 16), (8, 5000, 3.0, 1024)}
+CASES = [(seed, n, extra, tile, sym, entry16)
+         for seed, n, extra, tile in [(1, 40, 1.0, 8), (2, 257, 2.0, 64), (3, 900, 3.0, 128), (4, 1500, 1.5, 1024), (5, 3000, 2.5, 256),
+                                      (6, 64, 6.0, 16), (7, 2200, 0.6, 96)]
+         for sym in (True, False) for entry16 in (0, 1)]
+CASES += [(8, 5000, 3.0, 1024, sym, 1) for sym in (True, False)]   # ragged 1024-cell tiles (up to 2561 local cells) in the compact form
+
+
+@pytest.mark.parametrize("seed,n,extra,tile,sym,entry16", CASES)
+def test_random_coupled_matrices_every_operator(pkg, orc, seed, n, extra, tile, sym, entry16, monkeypatch):
+    syn, eng = pkg.synthetic, pkg.engine
+    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
+    make = capped_graph_case if entry16 and (seed, n, extra, tile) in CAPPED else random_graph_case
+    case, a, b = cyclic_pair(pkg, make(pkg, n, extra=extra, seed=seed, symmetric=sym), seed, sym)
+    npair = a.shape[0]
     monkeypatch.setenv("MI_TILE_CELLS", str(tile))
     monkeypatch.setenv("MI_ENTRY16", str(entry16))
     addr = eng.Addressing(ctx, n, case.lower_addr, case.upper_addr, [a, b], [b, a])
+    if entry16:   # the compact form is what the kernels read: ceil(w / 2) words per row slot against w
+        monkeypatch.setenv("MI_ENTRY16", "0")
+        explicit = eng.Addressing(ctx, n, case.lower_addr, case.upper_addr, [a, b], [b, a])
+        assert addr.stats()["entries"] < explicit.stats()["entries"], "the layout dropped the compact row entries"
+        explicit.close()
     mat = eng.Matrix(addr)
     mat.set_coeffs(dev(case.diag), dev(case.upper), None if sym else dev(case.lower))
     for p, itf in enumerate(case.interfaces):

@@ -396,3 +396,63 @@ def test_box_addressing_equals_its_reference_form(pkg):
     for dims in [(1, 1, 1), (2, 1, 1), (1, 3, 1), (1, 1, 4), (5, 4, 3), (7, 1, 3), (1, 6, 5), (13, 11, 9), (40, 3, 2), (33, 32, 31)]:
         for a, b in zip(syn.box_addressing(*dims), syn.box_addressing_reference(*dims)):
             assert a.dtype == b.dtype and np.array_equal(a, b), dims
+
+
+# ---- the premises of the GPU sweeps that run the compact row entries and the slot cap (tests/test_gpu_fuzz.py, test_gpu_launch_forms.py) ----
+CAPPED_SHAPES = [(3, 900, 3.0, 128), (5, 3000, 2.5, 256), (6, 64, 6.0, 16), (4, 1500, 1.5, 1024), (8, 5000, 3.0, 1024)]
+
+
+def _fuzz_layout(pkg, make, seed, n, extra, tile, **kw):
+    from test_gpu_fuzz import cyclic_pair
+    case, a, b = cyclic_pair(pkg, make(pkg, n, extra=extra, seed=seed, symmetric=True), seed, True)
+    return case, pkg.engine.host_layout(n, case.lower_addr, case.upper_addr, [a, b], tile_cells=tile, patch_nbr_cells=[b, a], **kw)
+
+
+def _rule1_k(L):
+    """(the values of the field k among the rule-1 halves of the compact entries, pad entries left out; the most local cells of a tile)"""
+    ks, most = set(), 0
+    for t in range(L["tileCellStart"].shape[0] - 1):
+        local = int(L["tileCellStart"][t + 1] - L["tileCellStart"][t] + L["tileHaloStart"][t + 1] - L["tileHaloStart"][t])
+        most = max(most, local)
+        e0, e1 = L["sliceEntryStart16"][L["tileSliceStart"][t]], L["sliceEntryStart16"][L["tileSliceStart"][t + 1]]
+        w = L["entries16"][e0:e1]
+        h = np.concatenate([w & 0xFFFF, w >> 16]).astype(np.int64)
+        h = h[((h >> 15) == 1) & ((h & 0xFFF) != local)]
+        ks |= set(((h >> 12) & 7).tolist())
+    return ks, most
+
+
+@pytest.mark.parametrize("seed,n,extra,tile", CAPPED_SHAPES)
+def test_capped_graphs_keep_the_compact_entries_with_every_k(pkg, seed, n, extra, tile):
+    """no owner of capped_graph_case has more than eight own faces: the layout keeps the 16-bit entries, their rule-1 halves name
+    every k in 0..7, and interpreting them gives the bits of the explicit form -- with the sweep's cyclic patch pair in place"""
+    from test_gpu_fuzz import capped_graph_case
+    case, L = _fuzz_layout(pkg, capped_graph_case, seed, n, extra, tile)
+    assert np.bincount(case.lower_addr, minlength=n).max() == 8
+    assert L["entries16"].shape[0] > 0 and 2 * L["entries16"].shape[0] < L["entries"].shape[0] + 64 * L["tileSliceStart"][-1]
+    ks, most = _rule1_k(L)
+    assert ks == set(range(8))
+    if n == 5000:
+        assert 2048 < most <= 4095          # the twelfth bit of the local index is in use
+    x = pkg.synthetic.splitmix_uniform(seed + 7, n) - 0.5
+    bou = np.concatenate([i.bou_coeffs for i in case.interfaces])
+    explicit = _interpret(L, case, x, ext=np.zeros(len(bou)), bou=bou)
+    assert np.array_equal(_interpret(L, case, x, ext=np.zeros(len(bou)), bou=bou, compact=True), explicit)
+
+
+def test_an_owner_with_nine_faces_drops_the_compact_entries(pkg):
+    """... and the plain random graph of the same shape (an owner with 14 own faces) builds none, for the whole layout"""
+    case, L = _fuzz_layout(pkg, random_graph_case, 3, 900, 3.0, 128)
+    assert np.bincount(case.lower_addr, minlength=900).max() > 8
+    assert L["entries16"].shape[0] == 0 and L["entries"].shape[0] > 0
+
+
+def test_slot_cap_cuts_tiles_and_refuses_a_cell_that_cannot_fit(pkg):
+    """slot_cap (MI_TILE_SLOTS) on the ragged 900-cell graph at 128 cells per tile: 64 and 257 slots end the tiles before the cell
+    cap does, 1000 is above what 128 cells need; 16 is fewer slots than one cell's faces"""
+    for cap, tiles, cells in [(64, 113, 10), (257, 28, 40), (1000, 9, 128)]:
+        _, L = _fuzz_layout(pkg, random_graph_case, 3, 900, 3.0, 128, slot_cap=cap)
+        assert L["tileCellStart"].shape[0] - 1 == tiles and np.diff(L["tileCellStart"]).max() == cells
+        assert np.diff(L["tileSlotStart"]).max() <= cap + 2
+    with pytest.raises(pkg.engine.MiError, match="a single cell has more faces than a tile can hold"):
+        _fuzz_layout(pkg, random_graph_case, 3, 900, 3.0, 128, slot_cap=16)

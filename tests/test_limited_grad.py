@@ -551,8 +551,10 @@ def _check(eng, A, B, kind, k, M, vf, grad, bv, dev, host, tag=""):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["box", "skewed", "graph"])
-def test_every_kind_against_the_restatement(pkg, name):
+@pytest.mark.parametrize("name", ["box", "skewed", "graph", "skewed_noxcd"])
+def test_every_kind_against_the_restatement(pkg, monkeypatch, name):
+    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of the three-array gradient pass (MI_XCD_ROWS is read by mi_ctx_create)
+        monkeypatch.setenv("MI_XCD_ROWS", "0"); name = name[:-len("_noxcd")]
     eng, ctx, dev, host = _env(pkg)
     syn = pkg.synthetic
     M = box_mesh(syn, (13, 11, 9)) if name == "box" else skewed((9, 8, 7)) if name == "skewed" else graph_mesh(pkg)

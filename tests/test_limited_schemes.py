@@ -392,9 +392,11 @@ def _graded_box(pkg, dims):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["box", "graph"])
-def test_every_scheme_against_the_restatement(pkg, name):
+@pytest.mark.parametrize("name", ["box", "graph", "box_noxcd"])
+def test_every_scheme_against_the_restatement(pkg, monkeypatch, name):
     from conftest import random_graph_case
+    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of k_limited_weights (MI_XCD_ROWS is read by mi_ctx_create)
+        monkeypatch.setenv("MI_XCD_ROWS", "0"); name = name[:-len("_noxcd")]
     eng, ctx, dev, host, E = _env(pkg)
     if name == "box":
         case, Cc = _graded_box(pkg, (9, 8, 7))

@@ -165,8 +165,10 @@ def _grads(pkg, n, n_rhs, seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["box", "skewed", "graph"])
-def test_face_pass_and_lust_weights_against_the_restatement(pkg, name):
+@pytest.mark.parametrize("name", ["box", "skewed", "graph", "skewed_noxcd"])
+def test_face_pass_and_lust_weights_against_the_restatement(pkg, monkeypatch, name):
+    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of the face pass (MI_XCD_ROWS is read by mi_ctx_create)
+        monkeypatch.setenv("MI_XCD_ROWS", "0"); name = name[:-len("_noxcd")]
     eng, ctx, dev, host, E = _env(pkg)
     syn = pkg.synthetic
     n, lo, up, C, cf = _mesh(pkg, name)

@@ -98,3 +98,41 @@ def test_every_name_a_test_sets_is_known():
             n += 1
             assert name in t or any(fnmatch.fnmatchcase(name, p) for p in python_side), f"{os.path.basename(path)}: {name} is neither in csrc/switches.hpp nor a Python-side name of DESIGN.md's appendix"
     assert n > 100   # (the patterns still find the tests' settings)
+
+
+# rows of group USER or AB that no test sets to another value than the default, and why
+EXEMPT = {
+    "MI_HOST_THP": "read once per process (ONCE) and host allocation only: the tables hold the same values either way",
+    "MI_PCG_FUSE_COOP": "read once per process (ONCE): a test of it needs a process of its own",
+}
+
+
+def _values_given(text, name, option):
+    """what a test file gives a switch: the literal integers where the text has one ("MI_X", "0" / MI_X="0" / MI_X=0 /
+    set_option("opt", 0)), None where the value is an expression; an environment name that is only deleted does not count"""
+    found = []
+    pats = [r"""(?<!delenv\()["']%s["']\s*[,:]?\s*(?:str\()?["']?(-?\d+)?""" % name, r"""\b%s=(?!=)["']?(-?\d+)?""" % name]
+    if option:
+        pats.append(r"""set_option\(\s*["']%s["']\s*,\s*(-?\d+)?""" % option)
+    for pat in pats:
+        found += [int(v) if v else None for v in re.findall(pat, text)]
+    return found
+
+
+def test_every_same_bits_switch_is_exercised():
+    """every USER or AB row is given a value other than its default by some file under tests/ (by its environment name, quoted or
+    as a keyword, or by its option name in a set_option call), or stands in EXEMPT with the reason: a form that "gives the same
+    results either way" is a claim the suite has to run.  TRANSPORT and DIAG rows need several devices or inject faults."""
+    t = _table()
+    texts = {os.path.basename(p): _read(p) for p in sorted(glob.glob(os.path.join(ROOT, "tests", "*.py"))) if os.path.basename(p) != "test_switches.py"}
+    missing = []
+    for name, (dflt, _, group, option) in t.items():
+        if group not in ("USER", "AB"):
+            continue
+        given = [v for text in texts.values() for v in _values_given(text, name, option)]
+        exercised = any(v is None or v != dflt for v in given)
+        assert not (exercised and name in EXEMPT), f"{name} is exercised: take it out of EXEMPT"
+        if not exercised and name not in EXEMPT:
+            missing.append(name)
+    assert not missing, f"no test sets {missing} to another value than the default"
+    assert set(EXEMPT) <= set(t)
