@@ -660,6 +660,55 @@ int mi_lust_weights(mi_ctx_t ctx, int64_t n_faces, const double *cd_weights_dev,
 int mi_fvm_assemble_corrected(mi_addr_t addr, const mi_fvm_terms *terms, const mi_div_correction *corr_or_null,
                               double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev,
                               double *const *source_out_dev, double *sum_mag_off_diag_out_dev_or_null);
+/* ---- the backward time scheme: fvm::ddt, fvc::ddt, fvc::ddtCorr and the fused assembly ----
+ * backwardDdtScheme<Type> (src/finiteVolume/finiteVolume/ddtSchemes/backwardDdtScheme/backwardDdtScheme.C), the static-mesh branches.  The
+ * reference evaluates every expression below as field operators, one pass and one rounding per operator; the engine rounds every product,
+ * sum and difference exactly as parenthesised here (no contraction), so the results equal the reference's bit for bit.
+ * mi_ddt_backward_coeffs (host only, no device): backwardDdtScheme.C:472-479 with deltaT0_() of :57-69,
+ *     coefft = 1 + deltaT/(deltaT + deltaT0);  coefft00 = deltaT*deltaT/(deltaT0*(deltaT + deltaT0));  coefft0 = coefft + coefft00
+ *   coeffs_out = {coefft, coefft0, coefft00}.  n_old_times < 2 (the field has no old-old time yet): deltaT0 = GREAT = 1e15, which gives
+ *   coefft = coefft0 = 1 and a coefft00 that is tiny but NOT zero -- the old-old field is always read; on the first step pass the old
+ *   field for it (the reference creates oldTime().oldTime() as a copy).  MI_ERR_ARG: delta_t <= 0; delta_t0 <= 0 with n_old_times >= 2.
+ * mi_fvm_ddt_backward: fvmDdt(vf) :456-504, fvmDdt(dimensionedScalar rho, vf) :507-553, fvmDdt(volScalarField rho, vf) :558-607
+ *     rho_dev NULL:  diag = ((coefft*rDeltaT)*rho_value)*V;  source = ((rDeltaT*V)*rho_value)*((coefft0*psi0) - (coefft00*psi00))
+ *     rho_dev given: diag = ((coefft*rDeltaT)*rho)*V;        source = (rDeltaT*V)*(((coefft0*rho0)*psi0) - ((coefft00*rho00)*psi00))
+ *   (rho_value 1: fvm::ddt(vf)).  The three density arrays are given together or not at all.
+ * mi_fvc_ddt_backward: fvcDdt(vf) :196-207, fvcDdt(dimensionedScalar rho, vf) :268-280, fvcDdt(volScalarField rho, vf) :343-355
+ *     rho_dev NULL:  out = (rDeltaT*rho_value)*(((coefft*vf) - (coefft0*vf0)) + (coefft00*vf00))
+ *     rho_dev given: out = rDeltaT*((((coefft*rho)*vf) - ((coefft0*rho0)*vf0)) + ((coefft00*rho00)*vf00))
+ *   Both calls refuse (MI_ERR_ARG) a missing array, an unaligned array, and an output that is also an input or the other output.
+ * mi_ddt_phi_corr_backward: fvcDdtPhiCorr(U, phi) :724-765 and fvcDdtPhiCorr(rho, U, phi) :868-950 (first branch) with
+ *   ddtScheme<Type>::fvcDdtPhiCoeff (ddtSchemes/ddtScheme/ddtScheme.C:139-174), internal faces, ONE face pass:
+ *     W = (coefft0*U0) - (coefft00*U00)  [with density (coefft0*(rho0*U0)) - (coefft00*(rho00*U00))], a cell field, rounded per cell
+ *     k = 1 - min(|phi0 - flux(U0 or rho0*U0)|/(|phi0| + SMALL), 1)          (the OLD fields only)
+ *     out = (k*rDeltaT)*(((coefft0*phi0) - (coefft00*phi00)) - flux(W)),   flux(X) = Sf & interpolate(X) as mi_flux_div forms it
+ *   Each face gathers the old and old-old values of its two cells once and forms both fluxes from them.
+ * mi_fvm_assemble_backward: mi_fvm_assemble / mi_fvm_assemble_corrected (corr_or_null) with the backward time derivative in the same row
+ *   pass: terms->ddt != 0, terms->r_delta_t / rho_value / rho_dev / rho_old_dev / psi_old_dev keep their meaning, bw adds the coefficients
+ *   and the old-old fields.  diag's time part and the start of every source are mi_fvm_ddt_backward's expressions; everything else (face
+ *   terms, row sums, the correction, sp, su, sumMagOffDiag) is mi_fvm_assemble's -- so the outputs equal mi_fvm_ddt_backward + mi_fvm_div +
+ *   mi_fvm_laplacian + the mi_vec_axpby combinations bit for bit.  MI_ERR_ARG: bw NULL, terms->ddt == 0, rho_old_old_dev given without
+ *   rho_dev or the reverse, a missing old-old field; and every refusal of mi_fvm_assemble[_corrected].                                  */
+typedef struct mi_ddt_backward {
+    double coefft, coefft0, coefft00;              /* mi_ddt_backward_coeffs */
+    const double *rho_old_old_dev;                 /* given exactly when terms->rho_dev is */
+    const double *const *psi_old_old_dev;          /* n_rhs old-old fields */
+} mi_ddt_backward;
+int mi_ddt_backward_coeffs(double delta_t, double delta_t0, int32_t n_old_times, double coeffs_out[3]);
+int mi_fvm_ddt_backward(mi_ctx_t ctx, int64_t n, double r_delta_t, const double coeffs[3], double rho_value, const double *rho_dev,
+                        const double *rho_old_dev, const double *rho_old_old_dev, const double *vol_dev, const double *psi_old_dev,
+                        const double *psi_old_old_dev, double *diag_out_dev, double *source_out_dev);
+int mi_fvc_ddt_backward(mi_ctx_t ctx, int64_t n, double r_delta_t, const double coeffs[3], double rho_value, const double *rho_dev,
+                        const double *rho_old_dev, const double *rho_old_old_dev, const double *vf_dev, const double *vf_old_dev,
+                        const double *vf_old_old_dev, double *out_dev);
+int mi_ddt_phi_corr_backward(mi_addr_t addr, double r_delta_t, const double coeffs[3], const double *lambda_dev, const double *sfx_dev,
+                             const double *sfy_dev, const double *sfz_dev, const double *ux_old_dev, const double *uy_old_dev,
+                             const double *uz_old_dev, const double *ux_old_old_dev, const double *uy_old_old_dev,
+                             const double *uz_old_old_dev, const double *rho_old_dev_or_null, const double *rho_old_old_dev_or_null,
+                             const double *phi_old_dev, const double *phi_old_old_dev, double *out_dev);
+int mi_fvm_assemble_backward(mi_addr_t addr, const mi_fvm_terms *terms, const mi_ddt_backward *bw, const mi_div_correction *corr_or_null,
+                             double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev, double *const *source_out_dev,
+                             double *sum_mag_off_diag_out_dev_or_null);
 /* fvMatrix::setReference (src/finiteVolume/fvMatrices/fvMatrix/fvMatrix.C:964-981; icoFoam.C:89, simpleFoam/pEqn.H:21: the pressure level of a
  * closed domain): source[celli] += diag[celli]*value; diag[celli] += diag[celli].  celli < 0 (the rank does not hold the cell): no-op. */
 int mi_fvm_set_reference(mi_addr_t addr, int32_t celli, double value, double *diag_dev, double *source_dev);

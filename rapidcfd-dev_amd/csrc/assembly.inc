@@ -194,11 +194,30 @@ struct AsmArgs {
     double *diagOut, *sumMagOut;
 };
 struct AsmCorrArgs : AsmArgs { const int32_t *lo, *up; CorrIn corr; };   // CORR: caller-order face addressing and the correction's inputs
+// BACK: the backward time derivative in place of Euler's (backwardDdtScheme.C:456-607, static mesh): cA = coefft*rDeltaT (a host product,
+// as the reference forms it), the old-old fields; rdt / rhoValue / rho / rhoOld / psiOld of AsmArgs keep their meaning
+struct BackIn { double cA, c0, c00; const double* rhoOldOld; const double* psiOldOld[4]; };
+struct AsmBackArgs : AsmArgs { BackIn bw; };
+struct AsmCorrBackArgs : AsmCorrArgs { BackIn bw; };
+template <bool CORR, bool BACK> struct AsmSel { typedef typename std::conditional<CORR, AsmCorrArgs, AsmArgs>::type type; };
+template <> struct AsmSel<false, true> { typedef AsmBackArgs type; };
+template <> struct AsmSel<true, true> { typedef AsmCorrBackArgs type; };
+// fvm::ddt, backward: every product and difference rounded on its own (the reference's field operators; DESIGN 3.5d).  Constant density:
+// rho_value joins the (rDeltaT*V) factor; a density field: rho0 / rho00 join the coefficients inside the bracket.
+__device__ __forceinline__ double back_diag(double cA, double rho, double V) { return (cA * rho) * V; }
+__device__ __forceinline__ double back_source(double rdt, double rhoValue, double c0, double c00, double V, double p0, double p00)
+{
+    return ((rdt * V) * rhoValue) * ((c0 * p0) - (c00 * p00));
+}
+__device__ __forceinline__ double back_source_rho(double rdt, double c0, double c00, double V, double r0, double p0, double r00, double p00)
+{
+    return (rdt * V) * (((c0 * r0) * p0) - ((c00 * r00) * p00));
+}
 // CORR: each own face's t_r = faceFlux*(scale*corr_r) is formed once in the face pass and staged in LDS after lB / uB / uL; every cell
 // forms its n_rhs surfaceIntegrate row sums in mi_surface_integrate's order, ivf = sum/V, and subtracts the rounded V*ivf from the source
 // right after the ddt part (the div matrix's own source, fvMatrix.C:1819-1826), before the explicit terms
-template <bool DIV, bool LAP, int BS, bool R16, bool CORR = false>
-__global__ __launch_bounds__(BS) void k_row_assemble(const typename std::conditional<CORR, AsmCorrArgs, AsmArgs>::type a)
+template <bool DIV, bool LAP, int BS, bool R16, bool CORR = false, bool BACK = false>
+__global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR, BACK>::type a)
 {
     extern __shared__ __attribute__((aligned(16))) double rp_smem[];
     const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
@@ -292,14 +311,19 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const typename std::conditi
     for (int j = nb + 3; j < ne; ++j) nei_term(nei_get(nei_face(j)));
     const double V = a.vol ? a.vol[c] : 0.0;
     double d = 0.0;
-    if (a.ddt) { const double dA = (a.rdt * (a.rho ? a.rho[c] : a.rhoValue)) * V; d = DIV ? dA + sumB : dA; }
+    if constexpr (BACK) { const double dA = back_diag(a.bw.cA, a.rho ? a.rho[c] : a.rhoValue, V); d = DIV ? dA + sumB : dA; }
+    else if (a.ddt) { const double dA = (a.rdt * (a.rho ? a.rho[c] : a.rhoValue)) * V; d = DIV ? dA + sumB : dA; }
     else if (DIV) d = sumB;
-    if (LAP) d = (a.ddt || DIV) ? d - sumL : -sumL;
+    if (LAP) d = (BACK || a.ddt || DIV) ? d - sumL : -sumL;
     if (a.sp) { const double t = V * a.sp[c]; d = a.spMinus ? d - t : d + t; }
     a.diagOut[c] = d;
     if (mag) a.sumMagOut[c] = sumM;
     auto source = [&](int r, double vIvf) {
-        double s = a.ddt ? ((a.rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue)) * a.psiOld[r][c]) * V : 0.0;
+        double s;
+        if constexpr (BACK)
+            s = a.rhoOld ? back_source_rho(a.rdt, a.bw.c0, a.bw.c00, V, a.rhoOld[c], a.psiOld[r][c], a.bw.rhoOldOld[c], a.bw.psiOldOld[r][c])
+                         : back_source(a.rdt, a.rhoValue, a.bw.c0, a.bw.c00, V, a.psiOld[r][c], a.bw.psiOldOld[r][c]);
+        else s = a.ddt ? ((a.rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue)) * a.psiOld[r][c]) * V : 0.0;
         if (CORR) s = s - vIvf;
         for (int k = 0; k < a.nSu; ++k) { const double t = V * a.su[k * a.nRhs + r][c]; s = a.suMinus[k] ? s + t : s - t; }
         a.sourceOut[r][c] = s;
@@ -477,6 +501,94 @@ __global__ void k_ddt_phi_corr(const RowPassArgs a, double rDeltaT, const double
         const double q = fabs(phiCorr) / (fabs(p0) + 1e-15);
         const double coeff = 1.0 - (q < 1.0 ? q : 1.0);
         out[f] = (coeff * rDeltaT) * phiCorr;
+    }
+}
+// fvm::ddt, backward (backwardDdtScheme.C:456-607, static mesh): the constant-density form (rho_value 1: fvm::ddt(vf)) and the density-field
+// form; the roundings are back_diag / back_source[_rho]'s
+template <bool RHO>
+__global__ __launch_bounds__(RB) void k_fvm_ddt_backward(double rdt, double cA, double c0, double c00, double rhoValue, const double* __restrict__ rho,
+                                                         const double* __restrict__ rho0, const double* __restrict__ rho00, const double* __restrict__ vol,
+                                                         const double* __restrict__ psi0, const double* __restrict__ psi00, double* __restrict__ diag,
+                                                         double* __restrict__ source, int64_t n)
+{
+    chunk_loop2(n, [&](int64_t i) {
+            const double2 v = ld2(vol, i), p0 = ld2(psi0, i), p00 = ld2(psi00, i);
+            if (RHO) {
+                const double2 q = ld2(rho, i), q0 = ld2(rho0, i), q00 = ld2(rho00, i);
+                st2(diag, i, make_double2(back_diag(cA, q.x, v.x), back_diag(cA, q.y, v.y)));
+                st2(source, i, make_double2(back_source_rho(rdt, c0, c00, v.x, q0.x, p0.x, q00.x, p00.x), back_source_rho(rdt, c0, c00, v.y, q0.y, p0.y, q00.y, p00.y)));
+            } else {
+                st2(diag, i, make_double2(back_diag(cA, rhoValue, v.x), back_diag(cA, rhoValue, v.y)));
+                st2(source, i, make_double2(back_source(rdt, rhoValue, c0, c00, v.x, p0.x, p00.x), back_source(rdt, rhoValue, c0, c00, v.y, p0.y, p00.y)));
+            }
+        },
+        [&](int64_t i) {
+            if (RHO) { diag[i] = back_diag(cA, rho[i], vol[i]); source[i] = back_source_rho(rdt, c0, c00, vol[i], rho0[i], psi0[i], rho00[i], psi00[i]); }
+            else { diag[i] = back_diag(cA, rhoValue, vol[i]); source[i] = back_source(rdt, rhoValue, c0, c00, vol[i], psi0[i], psi00[i]); }
+        });
+}
+// fvc::ddt, backward (backwardDdtScheme.C:196-207, :268-280, :343-355): rr = rDeltaT*rho_value (a host product) without a density field
+__device__ __forceinline__ double back_fvc(double rr, double c, double c0, double c00, double f, double f0, double f00)
+{
+    return rr * (((c * f) - (c0 * f0)) + (c00 * f00));
+}
+__device__ __forceinline__ double back_fvc_rho(double rdt, double c, double c0, double c00, double r, double f, double r0, double f0, double r00, double f00)
+{
+    return rdt * ((((c * r) * f) - ((c0 * r0) * f0)) + ((c00 * r00) * f00));
+}
+template <bool RHO>
+__global__ __launch_bounds__(RB) void k_fvc_ddt_backward(double rr, double c, double c0, double c00, const double* __restrict__ rho,
+                                                         const double* __restrict__ rho0, const double* __restrict__ rho00, const double* __restrict__ vf,
+                                                         const double* __restrict__ vf0, const double* __restrict__ vf00, double* __restrict__ out, int64_t n)
+{
+    chunk_loop2(n, [&](int64_t i) {
+            const double2 f = ld2(vf, i), f0 = ld2(vf0, i), f00 = ld2(vf00, i);
+            if (RHO) {
+                const double2 q = ld2(rho, i), q0 = ld2(rho0, i), q00 = ld2(rho00, i);
+                st2(out, i, make_double2(back_fvc_rho(rr, c, c0, c00, q.x, f.x, q0.x, f0.x, q00.x, f00.x), back_fvc_rho(rr, c, c0, c00, q.y, f.y, q0.y, f0.y, q00.y, f00.y)));
+            } else st2(out, i, make_double2(back_fvc(rr, c, c0, c00, f.x, f0.x, f00.x), back_fvc(rr, c, c0, c00, f.y, f0.y, f00.y)));
+        },
+        [&](int64_t i) {
+            out[i] = RHO ? back_fvc_rho(rr, c, c0, c00, rho[i], vf[i], rho0[i], vf0[i], rho00[i], vf00[i]) : back_fvc(rr, c, c0, c00, vf[i], vf0[i], vf00[i]);
+        });
+}
+// fvc::ddtCorr, backward, internal faces (backwardDdtScheme.C:724-765, :868-950 first branch; fvcDdtPhiCoeff: ddtScheme.C:139-174) in ONE face
+// pass: a face gathers U0, U00 [rho0, rho00] of its two cells once and forms both fluxes from them -- flux(U0) for the coefficient (the OLD
+// fields only) and flux(W), W = coefft0*U0 - coefft00*U00 rounded per cell and component as the cell field it is in the reference; each flux
+// is flux_face's, operation for operation.  XCD-aware chunks as the gathering face passes (k_limited_weights, k_linear_upwind_corr).
+struct DdtCorrBackArgs {
+    const int32_t *lo, *up;
+    const double *lam, *s[3], *u0[3], *u00[3], *rho0, *rho00, *phi0, *phi00;
+    double* out;
+    double rdt, c0, c00;
+    int nf, xcd;
+};
+__global__ void k_ddt_phi_corr_backward(const DdtCorrBackArgs a)
+{
+    int f0, f1; block_chunk(a.nf, a.xcd, f0, f1);
+    for (int f = f0 + threadIdx.x; f < f1; f += blockDim.x) {
+        const int P = a.lo[f], N = a.up[f];
+        const double l = a.lam[f];
+        double p[3], n[3], pp[3], nn[3], wP[3], wN[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { p[d] = a.u0[d][P]; n[d] = a.u0[d][N]; pp[d] = a.u00[d][P]; nn[d] = a.u00[d][N]; }
+        if (a.rho0) {
+            const double rP = a.rho0[P], rN = a.rho0[N], rrP = a.rho00[P], rrN = a.rho00[N];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { p[d] = rP * p[d]; n[d] = rN * n[d]; pp[d] = rrP * pp[d]; nn[d] = rrN * nn[d]; }
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { wP[d] = (a.c0 * p[d]) - (a.c00 * pp[d]); wN[d] = (a.c0 * n[d]) - (a.c00 * nn[d]); }
+        const double sx = a.s[0][f], sy = a.s[1][f], sz = a.s[2][f];
+        auto flux = [&](const double* o, const double* q) {
+            const double ix = fma(l, o[0] - q[0], q[0]), iy = fma(l, o[1] - q[1], q[1]), iz = fma(l, o[2] - q[2], q[2]);
+            return fma(iz, sz, fma(ix, sx, iy * sy));
+        };
+        const double fU = flux(p, n), fW = flux(wP, wN);
+        const double p0 = a.phi0[f];
+        const double q = fabs(p0 - fU) / (fabs(p0) + 1e-15);
+        const double coeff = 1.0 - (q < 1.0 ? q : 1.0);
+        a.out[f] = (coeff * a.rdt) * (((a.c0 * p0) - (a.c00 * a.phi00[f])) - fW);
     }
 }
 __global__ __launch_bounds__(RB) void k_upwind_weights(const double* __restrict__ flux, double* __restrict__ w, int64_t n)
@@ -1110,9 +1222,29 @@ extern "C" int mi_fvm_assemble(mi_addr_t a, const mi_fvm_terms* t, double* lower
 {
     return mi_fvm_assemble_corrected(a, t, nullptr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
 }
+namespace {
+int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
+                  double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev);
+}
 // ... with the explicit correction of linearUpwind / LUST in the div term (CORR)
 extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
                                          double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
+{
+    return assemble_impl(a, t, nullptr, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+}
+// ... with the backward time derivative in place of Euler's (BACK), with or without the correction
+extern "C" int mi_fvm_assemble_backward(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev,
+                                        double* upper_out_dev, double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
+{
+    if (!a || !t || !bw) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: bad argument");
+    if (!t->ddt) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: terms->ddt is 0 (no time derivative: mi_fvm_assemble)");
+    if ((bw->rho_old_old_dev != nullptr) != (t->rho_dev != nullptr)) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: rho, rho_old and rho_old_old go together");
+    if (t->n_rhs > 0 && !bw->psi_old_old_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: old-old fields missing");
+    return assemble_impl(a, t, bw, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+}
+namespace {
+int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
+                  double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
 {
     if (!a || !t || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: bad argument");
     const bool DIV = t->div_flux_dev != nullptr, LAP = t->lap_delta_coeffs_dev != nullptr;
@@ -1142,7 +1274,7 @@ extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, con
     }
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    AsmCorrArgs ra{};
+    AsmCorrBackArgs ra{};
     if (CORR) {
         const double* outs[8] = {lower_out_dev, upper_out_dev, diag_out_dev, sum_mag_off_diag_out_dev};
         for (int r = 0; r < t->n_rhs; ++r) outs[4 + r] = source_out_dev[r];
@@ -1159,6 +1291,14 @@ extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, con
         ra.psiOld[r] = t->ddt ? t->psi_old_dev[r] : nullptr; ra.sourceOut[r] = source_out_dev[r];
         if (!ra.sourceOut[r] || (t->ddt && !ra.psiOld[r])) return fail(MI_ERR_ARG, "mi_fvm_assemble: null right-hand side array");
     }
+    const bool BACK = bw != nullptr;
+    if (BACK) {
+        ra.bw.cA = bw->coefft * t->r_delta_t; ra.bw.c0 = bw->coefft0; ra.bw.c00 = bw->coefft00; ra.bw.rhoOldOld = bw->rho_old_old_dev;
+        for (int r = 0; r < t->n_rhs; ++r) {
+            ra.bw.psiOldOld[r] = bw->psi_old_old_dev[r];
+            if (!ra.bw.psiOldOld[r]) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: null old-old field");
+        }
+    }
     for (int k = 0; k < t->n_su; ++k) {
         ra.suMinus[k] = t->su_sign[k] < 0 ? 1 : 0;
         for (int r = 0; r < t->n_rhs; ++r) { ra.su[k * t->n_rhs + r] = t->su_dev[k * t->n_rhs + r]; if (!ra.su[k * t->n_rhs + r]) return fail(MI_ERR_ARG, "mi_fvm_assemble: null explicit term"); }
@@ -1171,23 +1311,33 @@ extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, con
     ra.n = a->L.nCells; ra.cap = row_cap(rp, arrays); ra.xcd = a->ctx->xcdRows;
     const size_t lds = (size_t)arrays * ra.cap * sizeof(double);
     const bool r16 = a->row16.n > 0;
-    const AsmArgs& rb = ra;                        // the uncorrected kernels take the base arguments only
-#define MI_ASM_LAUNCH(D, L, K, ARGS)                                                                                             \
+    const AsmCorrArgs& rc = ra;                    // every kernel takes the arguments of its own variant only
+    const AsmArgs& rb = ra;
+    AsmBackArgs rk{}; static_cast<AsmArgs&>(rk) = rb; rk.bw = ra.bw;
+#define MI_ASM_LAUNCH(D, L, K, B, ARGS)                                                                                          \
     do {                                                                                                                           \
-        if (r16) { if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, true, K>, ARGS, lds);                     \
-                   if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, true, K>, ARGS, lds);                     \
-                   return row_launch(a, rp, k_row_assemble<D, L, 1024, true, K>, ARGS, lds); }                                    \
-        if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, false, K>, ARGS, lds);                               \
-        if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, false, K>, ARGS, lds);                               \
-        return row_launch(a, rp, k_row_assemble<D, L, 1024, false, K>, ARGS, lds);                                                \
+        if (r16) { if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, true, K, B>, ARGS, lds);                  \
+                   if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, true, K, B>, ARGS, lds);                  \
+                   return row_launch(a, rp, k_row_assemble<D, L, 1024, true, K, B>, ARGS, lds); }                                 \
+        if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, false, K, B>, ARGS, lds);                            \
+        if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, false, K, B>, ARGS, lds);                            \
+        return row_launch(a, rp, k_row_assemble<D, L, 1024, false, K, B>, ARGS, lds);                                             \
     } while (0)
-    if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, ra);
-    if (CORR) MI_ASM_LAUNCH(true, false, true, ra);
-    if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, rb);
-    if (DIV) MI_ASM_LAUNCH(true, false, false, rb);
-    MI_ASM_LAUNCH(false, true, false, rb);
+    if (BACK) {
+        if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, true, ra);
+        if (CORR) MI_ASM_LAUNCH(true, false, true, true, ra);
+        if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, true, rk);
+        if (DIV) MI_ASM_LAUNCH(true, false, false, true, rk);
+        MI_ASM_LAUNCH(false, true, false, true, rk);
+    }
+    if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, false, rc);
+    if (CORR) MI_ASM_LAUNCH(true, false, true, false, rc);
+    if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, false, rb);
+    if (DIV) MI_ASM_LAUNCH(true, false, false, false, rb);
+    MI_ASM_LAUNCH(false, true, false, false, rb);
 #undef MI_ASM_LAUNCH
 }
+} // namespace
 
 extern "C" int mi_surface_integrate(mi_addr_t a, const double* ssf_dev, const double* vol_dev_or_null, double* ivf_dev)
 {
@@ -1506,6 +1656,97 @@ extern "C" int mi_ddt_phi_corr(mi_addr_t a, double r_delta_t, const double* lamb
     ra.sc = rho_old_dev_or_null;
     if (a->L.nFaces == 0) return MI_OK;
     k_ddt_phi_corr<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, r_delta_t, phi_old_dev, out_dev, a->L.nFaces);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+// ---- the backward time scheme (backwardDdtScheme.C, static mesh; DESIGN 3.5d) ------------------------------------------------------
+extern "C" int mi_ddt_backward_coeffs(double delta_t, double delta_t0, int32_t n_old_times, double coeffs_out[3])
+{
+    if (!coeffs_out || !(delta_t > 0)) return fail(MI_ERR_ARG, "mi_ddt_backward_coeffs: deltaT must be positive");
+    if (n_old_times >= 2 && !(delta_t0 > 0)) return fail(MI_ERR_ARG, "mi_ddt_backward_coeffs: deltaT0 must be positive");
+    const double deltaT0 = n_old_times < 2 ? 1e15 : delta_t0;   // GREAT: fewer than two old times (backwardDdtScheme.C:57-69)
+    const double coefft = 1 + delta_t / (delta_t + deltaT0);
+    const double coefft00 = delta_t * delta_t / (deltaT0 * (delta_t + deltaT0));
+    coeffs_out[0] = coefft; coeffs_out[1] = coefft + coefft00; coeffs_out[2] = coefft00;
+    return MI_OK;
+}
+namespace {
+// the arrays of a streaming call: all present and 16-byte aligned, no output among the inputs or twice
+int stream_arrays(const char* who, const double* const* in, int nIn, double* const* out, int nOut)
+{
+    for (int i = 0; i < nIn; ++i) if (!in[i]) return fail(MI_ERR_ARG, std::string(who) + ": input arrays missing");
+    for (int o = 0; o < nOut; ++o) {
+        if (!out[o]) return fail(MI_ERR_ARG, std::string(who) + ": output arrays missing");
+        if (!al16(out[o])) return fail(MI_ERR_ARG, std::string(who) + ": arrays must be 16-byte aligned");
+        for (int i = 0; i < nIn; ++i) if (out[o] == in[i]) return fail(MI_ERR_ARG, std::string(who) + ": an output must not alias an input");
+        for (int q = 0; q < o; ++q) if (out[o] == out[q]) return fail(MI_ERR_ARG, std::string(who) + ": the outputs must differ");
+    }
+    for (int i = 0; i < nIn; ++i) if (!al16(in[i])) return fail(MI_ERR_ARG, std::string(who) + ": arrays must be 16-byte aligned");
+    return MI_OK;
+}
+} // namespace
+extern "C" int mi_fvm_ddt_backward(mi_ctx_t c, int64_t n, double r_delta_t, const double coeffs[3], double rho_value, const double* rho_dev,
+                                   const double* rho_old_dev, const double* rho_old_old_dev, const double* vol_dev, const double* psi_old_dev,
+                                   const double* psi_old_old_dev, double* diag_out_dev, double* source_out_dev)
+{
+    const char* who = "mi_fvm_ddt_backward";
+    if (!c || n < 0 || !coeffs) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    const bool RHO = rho_dev || rho_old_dev || rho_old_old_dev;
+    if (RHO && !(rho_dev && rho_old_dev && rho_old_old_dev)) return fail(MI_ERR_ARG, std::string(who) + ": rho, rho_old and rho_old_old go together");
+    const double* in[6] = {vol_dev, psi_old_dev, psi_old_old_dev, rho_dev, rho_old_dev, rho_old_old_dev};
+    double* out[2] = {diag_out_dev, source_out_dev};
+    MICHK(stream_arrays(who, in, RHO ? 6 : 3, out, 2));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const double cA = coeffs[0] * r_delta_t;
+    if (RHO) k_fvm_ddt_backward<true><<<RG, RB, 0, c->stream>>>(r_delta_t, cA, coeffs[1], coeffs[2], rho_value, rho_dev, rho_old_dev, rho_old_old_dev, vol_dev,
+                                                                 psi_old_dev, psi_old_old_dev, diag_out_dev, source_out_dev, n);
+    else k_fvm_ddt_backward<false><<<RG, RB, 0, c->stream>>>(r_delta_t, cA, coeffs[1], coeffs[2], rho_value, nullptr, nullptr, nullptr, vol_dev, psi_old_dev,
+                                                             psi_old_old_dev, diag_out_dev, source_out_dev, n);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+extern "C" int mi_fvc_ddt_backward(mi_ctx_t c, int64_t n, double r_delta_t, const double coeffs[3], double rho_value, const double* rho_dev,
+                                   const double* rho_old_dev, const double* rho_old_old_dev, const double* vf_dev, const double* vf_old_dev,
+                                   const double* vf_old_old_dev, double* out_dev)
+{
+    const char* who = "mi_fvc_ddt_backward";
+    if (!c || n < 0 || !coeffs) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    const bool RHO = rho_dev || rho_old_dev || rho_old_old_dev;
+    if (RHO && !(rho_dev && rho_old_dev && rho_old_old_dev)) return fail(MI_ERR_ARG, std::string(who) + ": rho, rho_old and rho_old_old go together");
+    const double* in[6] = {vf_dev, vf_old_dev, vf_old_old_dev, rho_dev, rho_old_dev, rho_old_old_dev};
+    double* out[1] = {out_dev};
+    MICHK(stream_arrays(who, in, RHO ? 6 : 3, out, 1));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (RHO) k_fvc_ddt_backward<true><<<RG, RB, 0, c->stream>>>(r_delta_t, coeffs[0], coeffs[1], coeffs[2], rho_dev, rho_old_dev, rho_old_old_dev, vf_dev,
+                                                                 vf_old_dev, vf_old_old_dev, out_dev, n);
+    else k_fvc_ddt_backward<false><<<RG, RB, 0, c->stream>>>(r_delta_t * rho_value, coeffs[0], coeffs[1], coeffs[2], nullptr, nullptr, nullptr, vf_dev, vf_old_dev,
+                                                             vf_old_old_dev, out_dev, n);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+extern "C" int mi_ddt_phi_corr_backward(mi_addr_t a, double r_delta_t, const double coeffs[3], const double* lambda_dev, const double* sfx_dev,
+                                        const double* sfy_dev, const double* sfz_dev, const double* ux_old_dev, const double* uy_old_dev,
+                                        const double* uz_old_dev, const double* ux_old_old_dev, const double* uy_old_old_dev, const double* uz_old_old_dev,
+                                        const double* rho_old_dev_or_null, const double* rho_old_old_dev_or_null, const double* phi_old_dev,
+                                        const double* phi_old_old_dev, double* out_dev)
+{
+    const char* who = "mi_ddt_phi_corr_backward";
+    RowPassArgs ra{};
+    MICHK(flux_args(a, who, lambda_dev, sfx_dev, sfy_dev, sfz_dev, ux_old_dev, uy_old_dev, uz_old_dev, ra));
+    if (!coeffs || !ux_old_old_dev || !uy_old_old_dev || !uz_old_old_dev || !phi_old_dev || !phi_old_old_dev || !out_dev)
+        return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if ((rho_old_dev_or_null != nullptr) != (rho_old_old_dev_or_null != nullptr)) return fail(MI_ERR_ARG, std::string(who) + ": rho_old and rho_old_old go together");
+    for (const double* q : {lambda_dev, sfx_dev, sfy_dev, sfz_dev, phi_old_dev, phi_old_old_dev})
+        if (q == out_dev) return fail(MI_ERR_ARG, std::string(who) + ": the output must not alias a face input");
+    if (a->L.nFaces == 0) return MI_OK;
+    DdtCorrBackArgs k{};
+    k.lo = ra.lo; k.up = ra.up; k.lam = lambda_dev; k.s[0] = sfx_dev; k.s[1] = sfy_dev; k.s[2] = sfz_dev;
+    k.u0[0] = ux_old_dev; k.u0[1] = uy_old_dev; k.u0[2] = uz_old_dev; k.u00[0] = ux_old_old_dev; k.u00[1] = uy_old_old_dev; k.u00[2] = uz_old_old_dev;
+    k.rho0 = rho_old_dev_or_null; k.rho00 = rho_old_old_dev_or_null; k.phi0 = phi_old_dev; k.phi00 = phi_old_old_dev; k.out = out_dev;
+    k.rdt = r_delta_t; k.c0 = coeffs[1]; k.c00 = coeffs[2]; k.nf = a->L.nFaces; k.xcd = a->ctx->xcdRows;
+    k_ddt_phi_corr_backward<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(k);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }

@@ -72,6 +72,7 @@ SYMBOLS = [
     "mi_linear_upwind_correction", "mi_patch_linear_upwind_correction", "mi_lust_weights", "mi_fvm_assemble_corrected",
     "mi_limiter_parse", "mi_limited_weights", "mi_patch_limited_weights",
     "mi_grad_limiter_parse", "mi_grad_boundary_create", "mi_grad_boundary_destroy", "mi_limited_grad",
+    "mi_ddt_backward_coeffs", "mi_fvm_ddt_backward", "mi_fvc_ddt_backward", "mi_ddt_phi_corr_backward", "mi_fvm_assemble_backward",
 ]
 
 
@@ -937,6 +938,20 @@ class FvmTerms(C.Structure):
                 ("psi_old_dev", C.POINTER(C.c_void_p)), ("n_su", C.c_int32), ("su_dev", C.POINTER(C.c_void_p)), ("su_sign", C.POINTER(C.c_double))]
 
 
+class DdtBackward(C.Structure):
+    """mi_ddt_backward (include/mi_ldu.h)"""
+    _fields_ = [("coefft", C.c_double), ("coefft0", C.c_double), ("coefft00", C.c_double), ("rho_old_old_dev", C.c_void_p),
+                ("psi_old_old_dev", C.POINTER(C.c_void_p))]
+
+
+def ddt_backward_coeffs(delta_t, delta_t0=None):
+    """(coefft, coefft0, coefft00) of the backward scheme (mi_ddt_backward_coeffs; host only, no GPU); delta_t0 None: the first step (the
+    field has no old-old time yet, deltaT0 = GREAT)"""
+    out = (C.c_double * 3)()
+    _chk(lib().mi_ddt_backward_coeffs(C.c_double(delta_t), C.c_double(0.0 if delta_t0 is None else delta_t0), C.c_int32(1 if delta_t0 is None else 2), out))
+    return (out[0], out[1], out[2])
+
+
 class DivCorrection(C.Structure):
     """mi_div_correction (include/mi_ldu.h)"""
     _fields_ = [("scale", C.c_double), ("cf_dev", C.c_void_p * 3), ("c_dev", C.c_void_p * 3), ("grad_dev", C.c_void_p * 12)]
@@ -1065,6 +1080,23 @@ class Assembly:
         _chk(lib().mi_ddt_phi_corr(self.addr.h, C.c_double(r_delta_t), _ptr(lam), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(u_old[0]), _ptr(u_old[1]),
                                    _ptr(u_old[2]), _ptr(rho_old), _ptr(phi_old), _ptr(out)))
 
+    def fvm_ddt_backward(self, r_delta_t, coeffs, vol, psi_old, psi_old_old, diag_out, source_out, rho_value=1.0, rho=None, rho_old=None, rho_old_old=None):
+        """fvm::ddt([rho,] vf), backward (backwardDdtScheme.C:456-607): coeffs from ddt_backward_coeffs; rho / rho_old / rho_old_old: a density
+        field (all three) or none (the constant rho_value)"""
+        _chk(lib().mi_fvm_ddt_backward(self.addr.ctx.h, C.c_int64(vol.numel()), C.c_double(r_delta_t), (C.c_double * 3)(*coeffs), C.c_double(rho_value),
+                                       _ptr(rho), _ptr(rho_old), _ptr(rho_old_old), _ptr(vol), _ptr(psi_old), _ptr(psi_old_old), _ptr(diag_out), _ptr(source_out)))
+
+    def fvc_ddt_backward(self, r_delta_t, coeffs, vf, vf_old, vf_old_old, out, rho_value=1.0, rho=None, rho_old=None, rho_old_old=None):
+        """fvc::ddt([rho,] vf), backward (backwardDdtScheme.C:196-207, 268-280, 343-355)"""
+        _chk(lib().mi_fvc_ddt_backward(self.addr.ctx.h, C.c_int64(vf.numel()), C.c_double(r_delta_t), (C.c_double * 3)(*coeffs), C.c_double(rho_value),
+                                       _ptr(rho), _ptr(rho_old), _ptr(rho_old_old), _ptr(vf), _ptr(vf_old), _ptr(vf_old_old), _ptr(out)))
+
+    def ddt_phi_corr_backward(self, r_delta_t, coeffs, lam, sf, u_old, u_old_old, rho_old, rho_old_old, phi_old, phi_old_old, out):
+        """fvc::ddtCorr([rho,] U, phi), backward, on the internal faces (backwardDdtScheme.C:724-765, 868-950; rho_old / rho_old_old both None or both given)"""
+        _chk(lib().mi_ddt_phi_corr_backward(self.addr.h, C.c_double(r_delta_t), (C.c_double * 3)(*coeffs), _ptr(lam), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]),
+                                            _ptr(u_old[0]), _ptr(u_old[1]), _ptr(u_old[2]), _ptr(u_old_old[0]), _ptr(u_old_old[1]), _ptr(u_old_old[2]),
+                                            _ptr(rho_old), _ptr(rho_old_old), _ptr(phi_old), _ptr(phi_old_old), _ptr(out)))
+
     def upwind_weights(self, face_flux, w_out):
         _chk(lib().mi_upwind_weights(self.addr.ctx.h, C.c_int64(face_flux.numel()), _ptr(face_flux), _ptr(w_out)))
 
@@ -1123,7 +1155,9 @@ class Assembly:
         laplacian = dict(delta_coeffs=, gamma_magsf=); sp = (field, sign); su = [(sign, [field per rhs]), ...]; vol is taken from ddt or the `vol` key of sp / su
         through ddt["vol"] (pass ddt=dict(vol=...) with r_delta_t omitted for no time derivative).
         div["correction"] = dict(scale=1.0 | 0.25, cf=[x, y, z], c=[x, y, z], grad=[[gx, gy, gz] per rhs]): the explicit correction of linearUpwind / LUST
-        in the same pass (mi_fvm_assemble_corrected)."""
+        in the same pass (mi_fvm_assemble_corrected).
+        ddt["backward"] = dict(coeffs=ddt_backward_coeffs(...), psi_old_old=[...], rho_old_old=None | tensor): the backward time derivative in place of
+        Euler's (mi_fvm_assemble_backward), with or without the correction."""
         t = FvmTerms()
         n_rhs = len(sources_out)
         keep = []
@@ -1147,7 +1181,17 @@ class Assembly:
             t.su_dev = C.cast(sd, C.POINTER(C.c_void_p)); t.su_sign = C.cast(sg, C.POINTER(C.c_double))
         so = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in sources_out])
         corr = (div or {}).get("correction")
-        if corr is None:
+        back = (ddt or {}).get("backward")
+        if back is not None:
+            b = DdtBackward()
+            b.coefft, b.coefft0, b.coefft00 = [float(x) for x in back["coeffs"]]
+            b.rho_old_old_dev = _ptr(back.get("rho_old_old")).value
+            poo = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in back["psi_old_old"]]); keep.append(poo)
+            b.psi_old_old_dev = C.cast(poo, C.POINTER(C.c_void_p))
+            k = None if corr is None else div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))
+            _chk(lib().mi_fvm_assemble_backward(self.addr.h, C.byref(t), C.byref(b), None if k is None else C.byref(k), _ptr(lower_out), _ptr(upper_out),
+                                                _ptr(diag_out), so, _ptr(sum_mag_out)))
+        elif corr is None:
             _chk(lib().mi_fvm_assemble(self.addr.h, C.byref(t), _ptr(lower_out), _ptr(upper_out), _ptr(diag_out), so, _ptr(sum_mag_out)))
         else:
             k = div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))

@@ -798,6 +798,58 @@ void fvm::assemble(fvVectorMatrix& M, scalar rDeltaT, scalar rho, const scalargp
     const mi_div_correction k = divCorrection(corr, 3);
     miCheck(mi_fvm_assemble_corrected(M.lduAddr().handle(), &t, &k, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble (corrected convection)");
 }
+// ---- the backward time scheme ----
+backwardDdtCoeffs::backwardDdtCoeffs(scalar deltaT, scalar deltaT0, int nOldTimes) : rDeltaT(1.0 / deltaT)
+{
+    double c[3];
+    miCheck(mi_ddt_backward_coeffs(deltaT, deltaT0, nOldTimes, c), "backwardDdtScheme");
+    coefft = c[0]; coefft0 = c[1]; coefft00 = c[2];
+}
+backwardDdtCoeffs::backwardDdtCoeffs(scalar deltaT, scalar deltaT0) : backwardDdtCoeffs(deltaT, deltaT0, 2) {}
+backwardDdtCoeffs backwardDdtCoeffs::firstStep(scalar deltaT) { return backwardDdtCoeffs(deltaT, 0.0, 1); }
+// the terms of the Euler overloads plus the backward part (the overloads of fvm::assemble that take backwardDdtCoeffs are inline over this)
+void fvm::assembleBackward(lduMatrix& M, scalargpuField* const* sources, const backwardDdtCoeffs& bd, scalar rho, const scalargpuField& V,
+                      const scalargpuField* const* psiOld, const scalargpuField* const* psiOldOld, int nRhs, const scalargpuField* faceFlux,
+                      const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const linearUpwindCorrection* corr,
+                      const scalargpuField* su)
+{
+    mi_fvm_terms t{};
+    t.ddt = 1; t.r_delta_t = bd.rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
+    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
+    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
+    const double *po[3], *poo[3]; double* so[3];
+    for (int r = 0; r < nRhs; ++r) { po[r] = psiOld[r]->data(); poo[r] = psiOldOld[r]->data(); so[r] = sources[r]->data(); }
+    t.n_rhs = nRhs; t.psi_old_dev = po;
+    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
+    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
+    mi_ddt_backward b{};
+    b.coefft = bd.coefft; b.coefft0 = bd.coefft0; b.coefft00 = bd.coefft00; b.psi_old_old_dev = poo;
+    mi_div_correction k{};
+    if (corr) k = divCorrection(*corr, (std::size_t)nRhs);
+    miCheck(mi_fvm_assemble_backward(M.lduAddr().handle(), &t, &b, corr ? &k : nullptr, faceFlux ? M.lower().data() : nullptr, M.upper().data(), M.diag().data(),
+                                     so, nullptr), "fvm::assemble (backward)");
+}
+void fvm::ddt(fvScalarMatrix& M, const backwardDdtCoeffs& bd, scalar rho, const scalargpuField& V, const scalargpuField& psiOld, const scalargpuField& psiOldOld)
+{
+    const double c[3] = {bd.coefft, bd.coefft0, bd.coefft00};
+    miCheck(mi_fvm_ddt_backward(miEngine::New().ctx, V.size(), bd.rDeltaT, c, rho, nullptr, nullptr, nullptr, V.data(), psiOld.data(), psiOldOld.data(),
+                                M.diag().data(), M.source().data()), "fvm::ddt (backward)");
+}
+void fvc::ddtCorr(scalargpuField& out, const lduAddressing& a, const backwardDdtCoeffs& bd, const scalargpuField& weights, const vectorgpuField& Sf,
+                  const vectorgpuField& Uold, const vectorgpuField& UoldOld, const scalargpuField& phiOld, const scalargpuField& phiOldOld)
+{
+    const double c[3] = {bd.coefft, bd.coefft0, bd.coefft00};
+    miCheck(mi_ddt_phi_corr_backward(a.handle(), bd.rDeltaT, c, weights.data(), Sf.component(0).data(), Sf.component(1).data(), Sf.component(2).data(),
+                                     Uold.component(0).data(), Uold.component(1).data(), Uold.component(2).data(), UoldOld.component(0).data(),
+                                     UoldOld.component(1).data(), UoldOld.component(2).data(), nullptr, nullptr, phiOld.data(), phiOldOld.data(), out.data()),
+            "fvc::ddtCorr (backward)");
+}
+void fvc::ddt(scalargpuField& out, const backwardDdtCoeffs& bd, const scalargpuField& vf, const scalargpuField& vfOld, const scalargpuField& vfOldOld)
+{
+    const double c[3] = {bd.coefft, bd.coefft0, bd.coefft00};
+    miCheck(mi_fvc_ddt_backward(miEngine::New().ctx, vf.size(), bd.rDeltaT, c, 1.0, nullptr, nullptr, nullptr, vf.data(), vfOld.data(), vfOldOld.data(), out.data()),
+            "fvc::ddt (backward)");
+}
 void fvc::linearUpwindCorrectionFlux(scalargpuField& out, const lduAddressing& a, const scalargpuField& faceFlux, const linearUpwindCorrection& corr)
 {
     const mi_div_correction k = divCorrection(corr, 1);

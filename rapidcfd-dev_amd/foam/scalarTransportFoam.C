@@ -4,7 +4,7 @@
 //         solve(fvm::ddt(T) + fvm::div(phi, T) - fvm::laplacian(DT, T) == fvOptions(T));        // (no fvOptions here)
 //
 // in a given velocity field, on a case directory: constant/polyMesh, constant/transportProperties (DT), system/controlDict (deltaT, endTime,
-// writeFormat, writePrecision), system/fvSchemes (div(phi,T): Gauss linear | upwind | limitedLinear k; laplacian: Gauss linear corrected |
+// writeFormat, writePrecision), system/fvSchemes (ddt(T): Euler | backward; div(phi,T): Gauss linear | upwind | limitedLinear k; laplacian: Gauss linear corrected |
 // uncorrected | orthogonal), system/fvSolution (solvers.T, SIMPLE.nNonOrthogonalCorrectors), 0/T and 0/U with fixedValue (inflow) and
 // zeroGradient (outflow, walls) patches [U: also noSlip].  The whole equation is ONE assembly pass (fvm::assemble -> mi_fvm_assemble); the patch
 // coefficients are the reference's: gaussConvectionScheme.C:96-110 (internalCoeffs = phi_b valueInternalCoeffs, boundaryCoeffs = -phi_b
@@ -51,7 +51,9 @@ int main(int argc, char** argv)
         const solution fvSolution(caseDir);
         const fvSchemes schemes(caseDir);
         const label nNonOrthCorr = fvSolution.solutionDict().found("SIMPLE") ? fvSolution.dict("SIMPLE").lookupOrDefault<label>("nNonOrthogonalCorrectors", 0) : 0;
-        if (schemes.ddtScheme("ddt(T)") != wordList{"Euler"}) FatalErrorIn("scalarTransportFoam", "ddtSchemes: only Euler");
+        const wordList ddtT = schemes.ddtScheme("ddt(T)");
+        if (ddtT != wordList{"Euler"} && ddtT != wordList{"backward"}) FatalErrorIn("scalarTransportFoam", "ddtSchemes: Euler | backward");
+        const bool backward = ddtT == wordList{"backward"};
         const wordList divT = schemes.divScheme("div(phi,T)");
         if (divT.size() < 2 || divT[0] != "Gauss" || (divT[1] != "linear" && divT[1] != "upwind" && !(divT[1] == "limitedLinear" && divT.size() == 3)))
             FatalErrorIn("scalarTransportFoam", "div(phi,T): Gauss linear | Gauss upwind | Gauss limitedLinear k");
@@ -144,16 +146,22 @@ int main(int argc, char** argv)
         scalargpuField w(nI);
         if (upwind) upwindWeights(w, phi);                      // (phi does not change: the upwind weights are formed once)
 
+        scalargpuField ToldOld(backward ? n : 0);
+
         Info << std::endl << "Calculating scalar transport" << std::endl << std::endl;
         for (label step = 1; step <= nSteps; ++step) {
             Info << "Time = " << step * deltaT << std::endl << std::endl;
             const scalargpuField Told(T);
+            // backward: T.oldTime().oldTime() -- a copy of the old field on the first step, where deltaT0 = GREAT (backwardDdtScheme.C:57-69)
+            const backwardDdtCoeffs bd = step == 1 ? backwardDdtCoeffs::firstStep(deltaT) : backwardDdtCoeffs(deltaT, deltaT);
+            if (backward && step == 1) ToldOld = Told;
             for (label nonOrth = 0; nonOrth <= nNonOrthCorr; ++nonOrth) {
                 vectorgpuField gT(n);
                 if (limited || corrected) gaussGrad(gT, T);
                 if (limited) limitedLinearWeights(w, addr, limiterK, weights, phi, T, gT, Cc);
                 fvScalarMatrix TEqn("T", addr, patchCells, notCoupled);
-                fvm::assemble(TEqn, rDeltaT, 1.0, V, Told, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
+                if (backward) fvm::assemble(TEqn, bd, 1.0, V, Told, ToldOld, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
+                else fvm::assemble(TEqn, rDeltaT, 1.0, V, Told, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
                 for (label q = 0; q < nP; ++q) { TEqn.internalCoeffs()[q] = icDev[q]; TEqn.boundaryCoeffs()[q] = bcDev[q]; }
                 if (corrected) {                                // - fvm::laplacian(DT, T), corrected: source += V*div(DT |Sf| correction(T))
                     scalargpuField cf(nI), d(n);
@@ -163,6 +171,7 @@ int main(int argc, char** argv)
                 }
                 TEqn.solve(T, TControls);
             }
+            if (backward) ToldOld = Told;
             Info << std::endl;
         }
         std::ostringstream tn; tn << std::setprecision(10) << nSteps * deltaT;
