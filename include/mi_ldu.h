@@ -749,6 +749,41 @@ int mi_patch_sngrad_correction_flux(mi_patch_t patch, const double *corr_vec_x_d
                                     const double *patch_weights_dev, const double *grad_x_dev, const double *grad_y_dev, const double *grad_z_dev,
                                     const double *nbr_grad_x_dev, const double *nbr_grad_y_dev, const double *nbr_grad_z_dev,
                                     const double *gamma_magsf_dev_or_null, double *flux_out_dev);
+/* ---- the `limited` snGrad scheme (finiteVolume/snGradSchemes/limitedSnGrad/limitedSnGrad.{H,C}): `laplacianSchemes { default Gauss linear
+ * limited 0.5; }`, `snGradSchemes { default limited corrected 0.33; }`.  correction(vf) = limiter * corr, with corr the `corrected` scheme's
+ * correction per component (the value mi_sngrad_correction_flux forms with gamma_magsf NULL) and ONE limiter per face,
+ *     limiter = min( k*mag(snGrad(vf)) / ((1 - k)*mag(corr) + SMALL), 1 )              (limitedSnGrad.C:58-84; SMALL = 1e-15),
+ * snGrad = nonOrthDeltaCoeffs*(vf[N] - vf[P]) (snGradScheme.C:103-108), mag = fabs for a scalar, sqrt(magSqr) of the three components
+ * for a vector.  k = 1 is `corrected` wherever |snGrad| >= SMALL, k = 0 `uncorrected`; neither is special-cased.
+ * mi_sngrad_parse: host only, no GPU.  Accepts `uncorrected`, `orthogonal`, `corrected`, `limited <k>` (a number directly after the
+ *   name: limitedSnGrad.H:86-97) and `limited corrected <k>`.  Refused (MI_ERR_ARG, the message names the token): k outside [0, 1], a
+ *   missing or extra token, `limited uncorrected|orthogonal <k>` (their correction() is not implemented in the reference), `limited
+ *   limited ...`, faceCorrected, linearFit, quadraticFit and unknown words.  limit_coeff is 1 for the kinds that do not read it.
+ * mi_sngrad_limited_correction_flux: one face pass over the internal faces for n_comp = 1 (scalar) or 3 (vector) components:
+ *   flux_out[j][f] = [gamma_magsf[f] *] (limiter[f] * corr_j[f]), every operation rounded where the reference's temporaries round it
+ *   (DESIGN 3.5e); limiter_out (or NULL) receives the limiter.  vf_dev[n_comp], grad_dev[3*n_comp] (grad_dev[3*j + d] = d(vf_j)/dx_d, the
+ *   full gradient as mi_gauss_grad + patches + /V leave it) and flux_out_dev[n_comp] are HOST arrays of device pointers.
+ * mi_patch_sngrad_limited_correction_flux: the same on one COUPLED patch; corr as mi_patch_sngrad_correction_flux forms it, snGrad =
+ *   patch_delta_coeffs*(nbr_vf - vf[faceCells]) (snGradScheme.C:165-169); nbr_vf / nbr_grad are the patchNeighbourFields
+ *   (mi_matrix_patch_neighbour_field, transformed where the patch transforms).  Non-coupled patches carry zero correction vectors: no call.
+ * Refused (MI_ERR_ARG, nothing launched): a missing array or one not aligned for a double, n_comp other than 1 or 3, limit_coeff
+ *   outside [0, 1], an output that aliases an input or another output. */
+enum { MI_SNGRAD_UNCORRECTED, MI_SNGRAD_ORTHOGONAL, MI_SNGRAD_CORRECTED, MI_SNGRAD_LIMITED };
+typedef struct mi_sngrad_scheme {
+    int32_t kind;          /* MI_SNGRAD_* */
+    double limit_coeff;    /* k of the limited kind */
+} mi_sngrad_scheme;
+int mi_sngrad_parse(const char *text, mi_sngrad_scheme *out);
+int mi_sngrad_limited_correction_flux(mi_addr_t addr, int32_t n_comp, double limit_coeff, const double *corr_vec_x_dev,
+                                      const double *corr_vec_y_dev, const double *corr_vec_z_dev, const double *weights_dev,
+                                      const double *delta_coeffs_dev, const double *const *vf_dev, const double *const *grad_dev,
+                                      const double *gamma_magsf_dev_or_null, double *const *flux_out_dev, double *limiter_out_dev_or_null);
+int mi_patch_sngrad_limited_correction_flux(mi_patch_t patch, int32_t n_comp, double limit_coeff, const double *corr_vec_x_dev,
+                                            const double *corr_vec_y_dev, const double *corr_vec_z_dev, const double *patch_weights_dev,
+                                            const double *patch_delta_coeffs_dev, const double *const *vf_dev,
+                                            const double *const *nbr_vf_dev, const double *const *grad_dev,
+                                            const double *const *nbr_grad_dev, const double *gamma_magsf_dev_or_null,
+                                            double *const *flux_out_dev, double *limiter_out_dev_or_null);
 /* fvPatchField::patchInternalField: out[i] = psi[faceCells[i]] (zeroGradient boundary values for the Gauss gradient, fvMatrix::flux ...) */
 int mi_patch_internal_field(mi_patch_t patch, const double *psi_dev, double *out_dev);
 /* inout -= x*y, the product rounded before the subtraction (a temporary field, then operator-=) */

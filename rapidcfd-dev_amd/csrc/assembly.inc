@@ -364,22 +364,36 @@ __global__ void k_face_conv_flux(const int32_t* __restrict__ lo, const int32_t* 
 // The reference builds three fields one after the other (interpolated gradient, dot product, product with gammaMagSf); the
 // values are rounded where its temporaries are, so one pass gives the same bits: interpolation lambda*(g[P]-g[N]) + g[N] as
 // one fma per component (surfaceInterpolationScheme.C:275-280), a & b = ax*bx + ay*by + az*bz contracted left to right.
+// (the two interpolate-and-dot forms are device functions: the limited passes below form exactly the same value)
+__device__ __forceinline__ double sngrad_face_corr(int P, int N, double l, double cx, double cy, double cz, const double* __restrict__ gx,
+                                                   const double* __restrict__ gy, const double* __restrict__ gz)
+{
+    const double nx = gx[N], ny = gy[N], nz = gz[N];
+    const double fx = fma(l, gx[P] - nx, nx), fy = fma(l, gy[P] - ny, ny), fz = fma(l, gz[P] - nz, nz);
+    return fma(cz, fz, fma(cx, fx, cy * fy));
+}
 __global__ void k_sngrad_corr_flux(const int32_t* __restrict__ lo, const int32_t* __restrict__ up, const double* __restrict__ cvx,
                                    const double* __restrict__ cvy, const double* __restrict__ cvz, const double* __restrict__ lambda,
                                    const double* __restrict__ gx, const double* __restrict__ gy, const double* __restrict__ gz,
                                    const double* __restrict__ gammaMagSf, double* __restrict__ flux, int nf)
 {
     for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += gridDim.x * blockDim.x) {
-        const int P = lo[f], N = up[f];
-        const double l = lambda[f];
-        const double nx = gx[N], ny = gy[N], nz = gz[N];
-        const double fx = fma(l, gx[P] - nx, nx), fy = fma(l, gy[P] - ny, ny), fz = fma(l, gz[P] - nz, nz);
-        const double corr = fma(cvz[f], fz, fma(cvx[f], fx, cvy[f] * fy));
+        const double corr = sngrad_face_corr(lo[f], up[f], lambda[f], cvx[f], cvy[f], cvz[f], gx, gy, gz);
         flux[f] = gammaMagSf ? gammaMagSf[f] * corr : corr;
     }
 }
 // the same on a COUPLED patch (processor / cyclic): the interpolate is pLambda*patchInternalField + (1 - pLambda)*patchNeighbourField,
 // written as separate field operations in the reference (surfaceInterpolationScheme.C:360-365), hence no contraction here
+__device__ __forceinline__ double sngrad_patch_corr(int c, int i, double l, double cx, double cy, double cz, const double* __restrict__ gx,
+                                                    const double* __restrict__ gy, const double* __restrict__ gz, const double* __restrict__ nx,
+                                                    const double* __restrict__ ny, const double* __restrict__ nz)
+{
+    const double m = 1.0 - l;
+    const double ax = l * gx[c], ay = l * gy[c], az = l * gz[c];
+    const double bx = m * nx[i], by = m * ny[i], bz = m * nz[i];
+    const double fx = ax + bx, fy = ay + by, fz = az + bz;
+    return fma(cz, fz, fma(cx, fx, cy * fy));
+}
 __global__ void k_patch_sngrad_corr_flux(const int32_t* __restrict__ faceCells, const double* __restrict__ cvx, const double* __restrict__ cvy,
                                          const double* __restrict__ cvz, const double* __restrict__ w, const double* __restrict__ gx,
                                          const double* __restrict__ gy, const double* __restrict__ gz, const double* __restrict__ nx,
@@ -388,13 +402,89 @@ __global__ void k_patch_sngrad_corr_flux(const int32_t* __restrict__ faceCells, 
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int c = faceCells[i];
-    const double l = w[i], m = 1.0 - l;
-    const double ax = l * gx[c], ay = l * gy[c], az = l * gz[c];
-    const double bx = m * nx[i], by = m * ny[i], bz = m * nz[i];
-    const double fx = ax + bx, fy = ay + by, fz = az + bz;
-    const double corr = fma(cvz[i], fz, fma(cvx[i], fx, cvy[i] * fy));
+    const double corr = sngrad_patch_corr(faceCells[i], i, w[i], cvx[i], cvy[i], cvz[i], gx, gy, gz, nx, ny, nz);
     flux[i] = gammaMagSf ? gammaMagSf[i] * corr : corr;
+}
+
+// ---- the `limited` snGrad scheme (snGradSchemes/limitedSnGrad/limitedSnGrad.C:58-84): correction(vf) = limiter*corr with
+//   corr    = correctedSnGrad::correction(vf)                       (per component, the value of the passes above)
+//   limiter = min( k*mag(snGrad(vf)) / ((1 - k)*mag(corr) + SMALL), 1 )
+// The reference runs about ten field passes with temporaries; here one face pass.  Every temporary is rounded where the reference
+// rounds it: snGrad = nonOrthDeltaCoeffs*(vf[N] - vf[P]) (snGradScheme.C:103-108), mag = fabs (scalar) | sqrt(magSqr) with magSqr the
+// engine's dot rule fma(z, z, fma(x, x, y*y)) (vector: ONE limiter from the magnitudes of the vector snGrad and the vector correction),
+// the products, the sum with SMALL, the quotient and limiter*corr one operation each, then gammaMagSf*(limiter*corr)
+// (gaussLaplacianSchemes.C:64-90).  min(q, 1) = (q < 1) ? q : 1 as Foam::min: a NaN quotient gives 1.  k = 0 and k = 1 take the same path.
+template <int NCOMP>
+struct SnGradLimArgs {
+    const double *cvx, *cvy, *cvz, *lambda, *deltaCoeffs, *gammaMagSf;   // gammaMagSf may be null
+    const double* vf[NCOMP];
+    const double* g[3 * NCOMP];                                          // g[3*j + d] = d(vf_j)/dx_d
+    double* flux[NCOMP];
+    double* limiter;                                                     // may be null
+    double k, oneMinusK;
+    int n;
+};
+template <int NCOMP>
+__device__ __forceinline__ double sngrad_limiter(double k, double oneMinusK, const double (&sn)[NCOMP], const double (&corr)[NCOMP])
+{
+    double magSn, magCorr;
+    if constexpr (NCOMP == 1) { magSn = fabs(sn[0]); magCorr = fabs(corr[0]); }
+    else {
+        magSn = sqrt(fma(sn[2], sn[2], fma(sn[0], sn[0], sn[1] * sn[1])));
+        magCorr = sqrt(fma(corr[2], corr[2], fma(corr[0], corr[0], corr[1] * corr[1])));
+    }
+    const double num = k * magSn;
+    const double den = (oneMinusK * magCorr) + 1e-15;                    // + SMALL
+    const double q = num / den;
+    return (q < 1.0) ? q : 1.0;
+}
+template <int NCOMP>
+__device__ __forceinline__ void sngrad_limited_store(const SnGradLimArgs<NCOMP>& a, int f, double lim, const double (&corr)[NCOMP])
+{
+    const bool scaled = a.gammaMagSf != nullptr;
+    const double gm = scaled ? a.gammaMagSf[f] : 0.0;
+#pragma unroll
+    for (int j = 0; j < NCOMP; ++j) {
+        const double lc = lim * corr[j];
+        a.flux[j][f] = scaled ? gm * lc : lc;
+    }
+    if (a.limiter) a.limiter[f] = lim;
+}
+template <int NCOMP>
+__global__ void k_sngrad_limited_flux(const int32_t* __restrict__ lo, const int32_t* __restrict__ up, const SnGradLimArgs<NCOMP> a)
+{
+    for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < a.n; f += gridDim.x * blockDim.x) {
+        const int P = lo[f], N = up[f];
+        const double l = a.lambda[f], cx = a.cvx[f], cy = a.cvy[f], cz = a.cvz[f], dc = a.deltaCoeffs[f];
+        double corr[NCOMP], sn[NCOMP];
+#pragma unroll
+        for (int j = 0; j < NCOMP; ++j) {
+            corr[j] = sngrad_face_corr(P, N, l, cx, cy, cz, a.g[3 * j], a.g[3 * j + 1], a.g[3 * j + 2]);
+            const double d = a.vf[j][N] - a.vf[j][P];
+            sn[j] = dc * d;
+        }
+        sngrad_limited_store<NCOMP>(a, f, sngrad_limiter<NCOMP>(a.k, a.oneMinusK, sn, corr), corr);
+    }
+}
+// COUPLED patch: corr as k_patch_sngrad_corr_flux forms it, snGrad = deltaCoeffs*(patchNeighbourField - patchInternalField)
+// (snGradScheme.C:165-169, coupledFvPatchField::snGrad); g holds the cell gradients, nbrVf / nbrG the patchNeighbourFields
+template <int NCOMP>
+struct SnGradNbrArgs { const double* vf[NCOMP]; const double* g[3 * NCOMP]; };
+template <int NCOMP>
+__global__ void k_patch_sngrad_limited_flux(const int32_t* __restrict__ faceCells, const SnGradLimArgs<NCOMP> a, const SnGradNbrArgs<NCOMP> nbr)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int c = faceCells[i];
+    const double l = a.lambda[i], cx = a.cvx[i], cy = a.cvy[i], cz = a.cvz[i], dc = a.deltaCoeffs[i];
+    double corr[NCOMP], sn[NCOMP];
+#pragma unroll
+    for (int j = 0; j < NCOMP; ++j) {
+        corr[j] = sngrad_patch_corr(c, i, l, cx, cy, cz, a.g[3 * j], a.g[3 * j + 1], a.g[3 * j + 2], nbr.g[3 * j], nbr.g[3 * j + 1], nbr.g[3 * j + 2]);
+        const double d = nbr.vf[j][i] - a.vf[j][c];
+        sn[j] = dc * d;
+    }
+    sngrad_limited_store<NCOMP>(a, i, sngrad_limiter<NCOMP>(a.k, a.oneMinusK, sn, corr), corr);
 }
 // fvPatchField::patchInternalField: out[i] = psi[faceCells[i]]
 __global__ void k_patch_internal_field(const int32_t* __restrict__ faceCells, const double* __restrict__ psi, double* __restrict__ out, int n)
@@ -1402,6 +1492,144 @@ extern "C" int mi_patch_sngrad_correction_flux(mi_patch_t p, const double* cvx_d
                                                                                  nbr_gx_dev, nbr_gy_dev, nbr_gz_dev, gamma_magsf_dev_or_null, flux_out_dev, p->nFaces);
     HIPCHK(hipGetLastError());
     return MI_OK;
+}
+// ---- the `limited` snGrad scheme: parser (host only) and the two face passes --------------------------------------------------
+extern "C" int mi_sngrad_parse(const char* text, mi_sngrad_scheme* out)
+{
+    const std::string who = "mi_sngrad_parse";
+    if (!text || !out) return fail(MI_ERR_ARG, who + ": bad argument");
+    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
+    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
+    for (const char* c = text; *c;) {
+        while (*c && sp(*c)) ++c;
+        const char* b = c;
+        while (*c && !sp(*c)) ++c;
+        if (c > b) tok.emplace_back(b, c);
+    }
+    if (tok.empty()) return fail(MI_ERR_ARG, who + ": empty scheme");
+    const char* const plain[] = {"uncorrected", "orthogonal", "corrected"};     // MI_SNGRAD_UNCORRECTED, _ORTHOGONAL, _CORRECTED
+    auto plain_kind = [&](const std::string& s) { for (int k = 0; k < 3; ++k) if (s == plain[k]) return k; return -1; };
+    mi_sngrad_scheme s{};
+    s.limit_coeff = 1.0;                                         // limitedSnGrad.H:122-127; read by the limited kind only
+    if (plain_kind(tok[0]) >= 0) {
+        if (tok.size() > 1) return fail(MI_ERR_ARG, who + ": extra '" + tok[1] + "' after '" + tok[0] + "'");
+        s.kind = plain_kind(tok[0]);
+        *out = s;
+        return MI_OK;
+    }
+    if (tok[0] != "limited") return fail(MI_ERR_ARG, who + ": snGrad scheme '" + tok[0] + "' is not supported (uncorrected | orthogonal | corrected | limited [corrected] <k>)");
+    if (tok.size() < 2) return fail(MI_ERR_ARG, who + ": 'limited' needs a coefficient ('limited <k>' | 'limited corrected <k>')");
+    // limitedSnGrad.H:86-110: a number directly after `limited` is the coefficient over `corrected`; otherwise a scheme, then the coefficient
+    auto number = [](const std::string& t, double* v) { char* end = nullptr; *v = std::strtod(t.c_str(), &end); return end != t.c_str() && *end == '\0'; };
+    std::size_t at = 1;
+    double k = 0;
+    if (!number(tok[1], &k)) {
+        if (tok[1] == "limited") return fail(MI_ERR_ARG, who + ": a limited scheme over a limited scheme ('limited limited') is not supported");
+        if (tok[1] == "uncorrected" || tok[1] == "orthogonal")
+            return fail(MI_ERR_ARG, who + ": 'limited " + tok[1] + "' is not supported: the correction() of '" + tok[1] + "' is not implemented in the reference");
+        if (tok[1] != "corrected") return fail(MI_ERR_ARG, who + ": corrected scheme '" + tok[1] + "' under 'limited' is not supported (only corrected)");
+        if (tok.size() < 3) return fail(MI_ERR_ARG, who + ": 'limited corrected' needs the coefficient k");
+        if (!number(tok[2], &k)) return fail(MI_ERR_ARG, who + ": '" + tok[2] + "' is not a number");
+        at = 2;
+    }
+    if (tok.size() > at + 1) return fail(MI_ERR_ARG, who + ": extra '" + tok[at + 1] + "'");
+    if (!(k >= 0 && k <= 1)) return fail(MI_ERR_ARG, who + ": limitCoeff is specified as " + tok[at] + " but should be >= 0 && <= 1");
+    s.kind = MI_SNGRAD_LIMITED; s.limit_coeff = k;
+    *out = s;
+    return MI_OK;
+}
+namespace {
+bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+// the checks both limited passes share; fills the argument block.  in[]: every input array, for the aliasing test
+template <int NCOMP>
+int sngrad_limited_args(const std::string& who, double k, const double* cvx, const double* cvy, const double* cvz, const double* w, const double* dc,
+                        const double* const* vf, const double* const* g, const double* const* nbrVf, const double* const* nbrG, const double* gamma,
+                        double* const* flux, double* limiter, int n, SnGradLimArgs<NCOMP>& a, SnGradNbrArgs<NCOMP>& nb)
+{
+    const double* in[6 + 8 * NCOMP];
+    int m = 0;
+    for (const double* q : {cvx, cvy, cvz, w, dc}) { if (!q) return fail(MI_ERR_ARG, who + ": a face array is missing"); in[m++] = q; }
+    for (int j = 0; j < NCOMP; ++j) in[m++] = vf[j];
+    for (int i = 0; i < 3 * NCOMP; ++i) in[m++] = g[i];
+    if (nbrVf) { for (int j = 0; j < NCOMP; ++j) in[m++] = nbrVf[j]; for (int i = 0; i < 3 * NCOMP; ++i) in[m++] = nbrG[i]; }
+    for (int i = 0; i < m; ++i) if (!in[i]) return fail(MI_ERR_ARG, who + ": an input array is missing");
+    if (gamma) in[m++] = gamma;
+    for (int i = 0; i < m; ++i) if (!al8(in[i])) return fail(MI_ERR_ARG, who + ": arrays must be aligned to 8 bytes");
+    double* outs[NCOMP + 1];
+    int no = 0;
+    for (int j = 0; j < NCOMP; ++j) outs[no++] = flux[j];
+    if (limiter) outs[no++] = limiter;
+    for (int i = 0; i < no; ++i) {
+        if (!outs[i]) return fail(MI_ERR_ARG, who + ": an output array is missing");
+        if (!al8(outs[i])) return fail(MI_ERR_ARG, who + ": arrays must be aligned to 8 bytes");
+        for (int q = 0; q < m; ++q) if (outs[i] == in[q]) return fail(MI_ERR_ARG, who + ": an output must not alias an input");
+        for (int q = 0; q < i; ++q) if (outs[i] == outs[q]) return fail(MI_ERR_ARG, who + ": the outputs must differ");
+    }
+    a.cvx = cvx; a.cvy = cvy; a.cvz = cvz; a.lambda = w; a.deltaCoeffs = dc; a.gammaMagSf = gamma; a.limiter = limiter;
+    a.k = k; a.oneMinusK = 1 - k; a.n = n;
+    for (int j = 0; j < NCOMP; ++j) { a.vf[j] = vf[j]; a.flux[j] = flux[j]; if (nbrVf) nb.vf[j] = nbrVf[j]; }
+    for (int i = 0; i < 3 * NCOMP; ++i) { a.g[i] = g[i]; if (nbrVf) nb.g[i] = nbrG[i]; }
+    return MI_OK;
+}
+template <int NCOMP>
+int sngrad_limited_internal(const std::string& who, mi_addr_s* a, double k, const double* cvx, const double* cvy, const double* cvz, const double* w,
+                            const double* dc, const double* const* vf, const double* const* g, const double* gamma, double* const* flux, double* limiter)
+{
+    SnGradLimArgs<NCOMP> q{}; SnGradNbrArgs<NCOMP> none{};
+    MICHK(sngrad_limited_args<NCOMP>(who, k, cvx, cvy, cvz, w, dc, vf, g, nullptr, nullptr, gamma, flux, limiter, a->L.nFaces, q, none));
+    HIPCHK(hipSetDevice(a->ctx->device));
+    MICHK(ensure_caller_tables(a));
+    if (a->L.nFaces == 0) return MI_OK;
+    k_sngrad_limited_flux<NCOMP><<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, q);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+template <int NCOMP>
+int sngrad_limited_patch(const std::string& who, mi_patch_s* p, double k, const double* cvx, const double* cvy, const double* cvz, const double* w,
+                         const double* dc, const double* const* vf, const double* const* nbrVf, const double* const* g, const double* const* nbrG,
+                         const double* gamma, double* const* flux, double* limiter)
+{
+    SnGradLimArgs<NCOMP> q{}; SnGradNbrArgs<NCOMP> nb{};
+    MICHK(sngrad_limited_args<NCOMP>(who, k, cvx, cvy, cvz, w, dc, vf, g, nbrVf, nbrG, gamma, flux, limiter, p->nFaces, q, nb));
+    HIPCHK(hipSetDevice(p->ctx->device));
+    k_patch_sngrad_limited_flux<NCOMP><<<(p->nFaces + 255) / 256, 256, 0, p->ctx->stream>>>(p->faceCells.p, q, nb);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+int sngrad_limited_common(const std::string& who, bool handle, int32_t n_comp, double k, bool tables)
+{
+    if (!handle) return fail(MI_ERR_ARG, who + ": bad argument");
+    if (n_comp != 1 && n_comp != 3) return fail(MI_ERR_ARG, who + ": n_comp must be 1 or 3");
+    if (!(k >= 0 && k <= 1)) return fail(MI_ERR_ARG, who + ": limit_coeff should be >= 0 && <= 1");
+    if (!tables) return fail(MI_ERR_ARG, who + ": a pointer table is missing");
+    return MI_OK;
+}
+} // namespace
+extern "C" int mi_sngrad_limited_correction_flux(mi_addr_t a, int32_t n_comp, double limit_coeff, const double* cvx_dev, const double* cvy_dev,
+                                                 const double* cvz_dev, const double* weights_dev, const double* delta_coeffs_dev,
+                                                 const double* const* vf_dev, const double* const* grad_dev, const double* gamma_magsf_dev_or_null,
+                                                 double* const* flux_out_dev, double* limiter_out_dev_or_null)
+{
+    const std::string who = "mi_sngrad_limited_correction_flux";
+    MICHK(sngrad_limited_common(who, a != nullptr, n_comp, limit_coeff, vf_dev && grad_dev && flux_out_dev));
+    if (n_comp == 1) return sngrad_limited_internal<1>(who, a, limit_coeff, cvx_dev, cvy_dev, cvz_dev, weights_dev, delta_coeffs_dev, vf_dev, grad_dev,
+                                                      gamma_magsf_dev_or_null, flux_out_dev, limiter_out_dev_or_null);
+    return sngrad_limited_internal<3>(who, a, limit_coeff, cvx_dev, cvy_dev, cvz_dev, weights_dev, delta_coeffs_dev, vf_dev, grad_dev,
+                                      gamma_magsf_dev_or_null, flux_out_dev, limiter_out_dev_or_null);
+}
+extern "C" int mi_patch_sngrad_limited_correction_flux(mi_patch_t p, int32_t n_comp, double limit_coeff, const double* cvx_dev, const double* cvy_dev,
+                                                       const double* cvz_dev, const double* weights_dev, const double* delta_coeffs_dev,
+                                                       const double* const* vf_dev, const double* const* nbr_vf_dev, const double* const* grad_dev,
+                                                       const double* const* nbr_grad_dev, const double* gamma_magsf_dev_or_null,
+                                                       double* const* flux_out_dev, double* limiter_out_dev_or_null)
+{
+    const std::string who = "mi_patch_sngrad_limited_correction_flux";
+    MICHK(sngrad_limited_common(who, p != nullptr, n_comp, limit_coeff, vf_dev && nbr_vf_dev && grad_dev && nbr_grad_dev && flux_out_dev));
+    if (p->nFaces == 0) return MI_OK;
+    if (n_comp == 1) return sngrad_limited_patch<1>(who, p, limit_coeff, cvx_dev, cvy_dev, cvz_dev, weights_dev, delta_coeffs_dev, vf_dev, nbr_vf_dev, grad_dev,
+                                                   nbr_grad_dev, gamma_magsf_dev_or_null, flux_out_dev, limiter_out_dev_or_null);
+    return sngrad_limited_patch<3>(who, p, limit_coeff, cvx_dev, cvy_dev, cvz_dev, weights_dev, delta_coeffs_dev, vf_dev, nbr_vf_dev, grad_dev,
+                                   nbr_grad_dev, gamma_magsf_dev_or_null, flux_out_dev, limiter_out_dev_or_null);
 }
 extern "C" int mi_patch_internal_field(mi_patch_t p, const double* psi_dev, double* out_dev)
 {

@@ -73,6 +73,7 @@ SYMBOLS = [
     "mi_limiter_parse", "mi_limited_weights", "mi_patch_limited_weights",
     "mi_grad_limiter_parse", "mi_grad_boundary_create", "mi_grad_boundary_destroy", "mi_limited_grad",
     "mi_ddt_backward_coeffs", "mi_fvm_ddt_backward", "mi_fvc_ddt_backward", "mi_ddt_phi_corr_backward", "mi_fvm_assemble_backward",
+    "mi_sngrad_parse", "mi_sngrad_limited_correction_flux", "mi_patch_sngrad_limited_correction_flux",
 ]
 
 
@@ -924,6 +925,14 @@ class Patch:
                                                    _ptr(grad[1]), _ptr(grad[2]), _ptr(nbr_grad[0]), _ptr(nbr_grad[1]), _ptr(nbr_grad[2]),
                                                    _ptr(gamma_magsf), _ptr(out)))
 
+    def sngrad_limited_correction_flux(self, limit_coeff, corr_vecs, weights, delta_coeffs, vf, nbr_vf, grad, nbr_grad, gamma_magsf, out, limiter_out=None):
+        """the `limited` snGrad scheme's correction flux on a COUPLED patch (limitedSnGrad.C:58-84): vf / nbr_vf 1 or 3 arrays (cell field, its
+        patchNeighbourField), grad / nbr_grad 3 or 9 (grad[3*j + d] = d(vf_j)/dx_d), out one patch array per component"""
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_patch_sngrad_limited_correction_flux(self.h, C.c_int32(len(vf)), C.c_double(limit_coeff), _ptr(corr_vecs[0]), _ptr(corr_vecs[1]),
+                                                           _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), pv(vf), pv(nbr_vf), pv(grad), pv(nbr_grad),
+                                                           _ptr(gamma_magsf), pv(out), _ptr(limiter_out)))
+
     def close(self):
         if self.h:
             lib().mi_patch_destroy(self.h)
@@ -1000,6 +1009,21 @@ def grad_limiter(scheme: str) -> GradLimiter:
     """mi_grad_limiter_parse: "cellLimited Gauss linear 1", "faceMDLimited Gauss linear 0.5" ... (host only, no GPU)"""
     out = GradLimiter()
     _chk(lib().mi_grad_limiter_parse(scheme.encode(), C.byref(out)))
+    return out
+
+
+class SnGradScheme(C.Structure):
+    """mi_sngrad_scheme (include/mi_ldu.h)"""
+    _fields_ = [("kind", C.c_int32), ("limit_coeff", C.c_double)]
+
+
+SNGRAD_KINDS = ("uncorrected", "orthogonal", "corrected", "limited")
+
+
+def sngrad_parse(text: str) -> SnGradScheme:
+    """mi_sngrad_parse: "uncorrected", "orthogonal", "corrected", "limited 0.5", "limited corrected 0.33" (host only, no GPU)"""
+    out = SnGradScheme()
+    _chk(lib().mi_sngrad_parse(text.encode(), C.byref(out)))
     return out
 
 
@@ -1112,6 +1136,14 @@ class Assembly:
         """gammaMagSf * (nonOrthCorrectionVectors & interpolate(grad)) on the internal faces (gaussLaplacianSchemes.C:64-90)"""
         _chk(lib().mi_sngrad_correction_flux(self.addr.h, _ptr(corr_vecs[0]), _ptr(corr_vecs[1]), _ptr(corr_vecs[2]), _ptr(weights), _ptr(grad[0]),
                                              _ptr(grad[1]), _ptr(grad[2]), _ptr(gamma_magsf), _ptr(out)))
+
+    def sngrad_limited_correction_flux(self, limit_coeff, corr_vecs, weights, delta_coeffs, vf, grad, gamma_magsf, out, limiter_out=None):
+        """[gammaMagSf *] limiter*correction of the `limited` snGrad scheme on the internal faces in one face pass (limitedSnGrad.C:58-84): vf 1 or
+        3 cell arrays, grad 3 or 9 (grad[3*j + d] = d(vf_j)/dx_d), out one face array per component, limiter_out one face array or None"""
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_sngrad_limited_correction_flux(self.addr.h, C.c_int32(len(vf)), C.c_double(limit_coeff), _ptr(corr_vecs[0]), _ptr(corr_vecs[1]),
+                                                     _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), pv(vf), pv(grad), _ptr(gamma_magsf), pv(out),
+                                                     _ptr(limiter_out)))
 
     def linear_upwind_correction(self, face_flux, cf, c, grad, out, scale=1.0):
         """faceFlux*correction(vf) of linearUpwind (scale 1) / LUST (scale 0.25) on the internal faces, one face pass for len(out) <= 4 components

@@ -9,7 +9,8 @@
 //
 // on a real case directory: constant/polyMesh, constant/transportProperties (nu), system/controlDict (deltaT, endTime, writeFormat,
 // writePrecision), system/fvSchemes (div(phi,U): Gauss linear | Gauss upwind | Gauss limitedLinear k; laplacian: Gauss linear corrected |
-// uncorrected -- the corrected form with its explicit non-orthogonal flux in UEqn's and pEqn's sources and in pEqn.flux()), system/fvSolution (solvers U, p [pFinal]; PISO: nCorrectors,
+// uncorrected | limited [corrected] k -- the corrected and limited forms with their explicit non-orthogonal flux in UEqn's and pEqn's sources and in
+// pEqn.flux(); limited: the U correction is ONE vector face pass, one limiter for the three components), system/fvSolution (solvers U, p [pFinal]; PISO: nCorrectors,
 // pRefCell, pRefValue), 0/U (fixedValue / noSlip patches), 0/p (zeroGradient patches: a closed domain, hence the reference level).
 // UEqn is the mirror's fvVectorMatrix: one set of coefficients and three sources out of ONE assembly pass (mi_fvm_assemble), the three
 // components solved as one batched PBiCG (fvMatrix<vector>::solveSegregated on the engine), A() and H() as fvMatrix.C:1374-1506; every
@@ -62,13 +63,11 @@ int main(int argc, char** argv)
         const wordList divU = schemes.divScheme("div(phi,U)");
         if (divU.size() < 2 || divU[0] != "Gauss" || (divU[1] != "linear" && divU[1] != "upwind" && !(divU[1] == "limitedLinear" && divU.size() == 3)))
             FatalErrorIn("icoFoam", "div(phi,U): Gauss linear | Gauss upwind | Gauss limitedLinear k");
-        bool corrected = false;
-        for (const char* term : {"laplacian(nu,U)", "laplacian((1|A(U)),p)"}) {
-            const wordList l = schemes.laplacianScheme(term);
-            if (l.size() != 3 || l[0] != "Gauss" || l[1] != "linear" || (l[2] != "orthogonal" && l[2] != "uncorrected" && l[2] != "corrected"))
-                FatalErrorIn("icoFoam", std::string("laplacianSchemes ") + term + ": Gauss linear corrected | uncorrected | orthogonal");
-            corrected = corrected || l[2] == "corrected";
-        }
+        const fv::snGradScheme snGradU = fv::snGradScheme::laplacian("icoFoam", "laplacian(nu,U)", schemes.laplacianScheme("laplacian(nu,U)"), [&] { return schemes.snGradScheme("snGrad(U)"); });
+        const fv::snGradScheme snGradP = fv::snGradScheme::laplacian("icoFoam", "laplacian((1|A(U)),p)", schemes.laplacianScheme("laplacian((1|A(U)),p)"), [&] { return schemes.snGradScheme("snGrad(p)"); });
+        // uncorrected | orthogonal | corrected as before: one `corrected` entry corrects both Laplacians; a `limited` entry limits its own
+        const bool corrected = snGradU.data().kind == MI_SNGRAD_CORRECTED || snGradP.data().kind == MI_SNGRAD_CORRECTED;
+        const bool correctedP = corrected || snGradP.limited();
         const bool upwind = divU[1] == "upwind", limited = divU[1] == "limitedLinear";
         const scalar limiterK = limited ? std::strtod(divU[2].c_str(), nullptr) : 0.0;
         Info << "Create mesh: nCells " << n << " nInternalFaces " << nI << " patches " << nP << "; nu " << nu << " deltaT " << deltaT << " steps " << nSteps
@@ -157,8 +156,9 @@ int main(int argc, char** argv)
         scalargpuField negNuMagSf(nI); fieldAxpby(negNuMagSf, -1.0, nuMagSf, 0.0, nuMagSf);
         // source -= V * fvc::div(gammaMagSf * correction(vf)): the explicit part of a `corrected` fvm::laplacian(gamma, vf) (gaussLaplacianSchemes.C:64-90);
         // returns the correction flux (pEqn keeps it: fvMatrix::flux() adds faceFluxCorrectionPtr, fvMatrix.C:1655-1658)
-        auto correctLaplacian = [&](fvScalarMatrix& M, const vectorgpuField& gradVf, const scalargpuField& gMagSf, scalargpuField& corrFlux) {
-            fvc::snGradCorrectionFlux(corrFlux, addr, corrVecs, weights, gradVf, gMagSf);
+        auto correctLaplacian = [&](fvScalarMatrix& M, const scalargpuField& vf, const vectorgpuField& gradVf, const scalargpuField& gMagSf, scalargpuField& corrFlux) {
+            if (snGradP.limited()) fvc::snGradLimitedCorrectionFlux(corrFlux, addr, snGradP, corrVecs, weights, deltaCoeffs, vf, gradVf, gMagSf);
+            else fvc::snGradCorrectionFlux(corrFlux, addr, corrVecs, weights, gradVf, gMagSf);
             scalargpuField d(n);
             fvc::surfaceIntegrate(d, addr, corrFlux, &V);
             fieldSubMul(M.source(), V, d);
@@ -206,7 +206,21 @@ int main(int argc, char** argv)
                     fieldSubMul(bc, phiB[q], UbDev[q].component(d));
                     UEqn.boundaryCoeffs()[q].component(d) = bc;
                 }
-            if (corrected)   // - fvm::laplacian(nu, U), corrected: its explicit part enters with the opposite sign -- gamma = -nu
+            if (snGradU.limited()) {   // limitedSnGrad<vector>: ONE limiter from the vector snGrad and the vector correction -- one face pass for U
+                vectorgpuField gUx(n), gUy(n), gUz(n), cf(nI);
+                vectorgpuField* const gU[3] = {&gUx, &gUy, &gUz};
+                for (direction d = 0; d < 3; ++d) {
+                    std::vector<const scalargpuField*> fixedValues;
+                    for (label q = 0; q < nP; ++q) fixedValues.push_back(&UbDev[q].component(d));
+                    gaussGrad(*gU[d], Uold.component(d), fixedValues);
+                }
+                fvc::snGradLimitedCorrectionFlux(cf, addr, snGradU, corrVecs, weights, deltaCoeffs, Uold, gU, negNuMagSf);
+                for (direction d = 0; d < 3; ++d) {
+                    scalargpuField dv(n);
+                    fvc::surfaceIntegrate(dv, addr, cf.component(d), &V);
+                    fieldSubMul(UEqn.source().component(d), V, dv);
+                }
+            } else if (corrected)   // - fvm::laplacian(nu, U), corrected: its explicit part enters with the opposite sign -- gamma = -nu
                 for (direction d = 0; d < 3; ++d) {
                     std::vector<const scalargpuField*> fixedValues;
                     for (label q = 0; q < nP; ++q) fixedValues.push_back(&UbDev[q].component(d));
@@ -245,13 +259,13 @@ int main(int argc, char** argv)
                     fvm::laplacian(pEqn, deltaCoeffs, gammaMagSf);                   // fvm::laplacian(rAU, p) == fvc::div(phiHbyA)
                     pEqn.source() = divPhi;
                     scalargpuField pCorrFlux(nI);
-                    if (corrected) { gradOfP(); correctLaplacian(pEqn, gradP, gammaMagSf, pCorrFlux); }
+                    if (correctedP) { gradOfP(); correctLaplacian(pEqn, p, gradP, gammaMagSf, pCorrFlux); }
                     pEqn.setReference(pRefCell, pRefValue);
                     pEqn.solve(p, (corr == nCorr - 1 && nonOrth == nNonOrthCorr) ? pFinalControls : pControls);
                     if (nonOrth == nNonOrthCorr) {                                   // phi = phiHbyA - pEqn.flux();
                         FieldFieldScalar bflux;
                         pEqn.flux(pflux, bflux, p);
-                        if (corrected) fieldAxpby(pflux, 1.0, pflux, 1.0, pCorrFlux);   // + faceFluxCorrection (formed from p before this solve)
+                        if (correctedP) fieldAxpby(pflux, 1.0, pflux, 1.0, pCorrFlux);   // + faceFluxCorrection (formed from p before this solve)
                         fieldAxpby(phi, 1.0, phiHbyA, -1.0, pflux);
                     }
                 }

@@ -698,18 +698,15 @@ void fvScalarMatrix::flux(scalargpuField& internalFlux, FieldFieldScalar& bounda
                               psi.data(), nbr ? nbr->data() : nullptr, boundaryFlux[p].data()), "fvMatrix::flux");
     }
 }
-void fvScalarMatrix::nonOrthCorrection(const scalargpuField& vf, const std::vector<const scalargpuField*>& patchValues, const vectorgpuField& Sf,
-                                       const std::vector<const vectorgpuField*>& patchSf, const scalargpuField& weights, const vectorgpuField& corrVecs,
-                                       const scalargpuField& gammaMagSf, const scalargpuField& V)
+void fvScalarMatrix::gaussGradOf(vectorgpuField& g, const scalargpuField& vf, const std::vector<const scalargpuField*>& patchValues, const vectorgpuField& Sf,
+                                 const std::vector<const vectorgpuField*>& patchSf, const scalargpuField& weights, const scalargpuField& V)
 {
     const lduAddressing& a = lduAddr();
     const label n = a.size(), nI = weights.size();
-    mi_ctx_t ctx = miEngine::New().ctx;
     scalargpuField ssf(nI);
     miCheck(mi_face_interpolate(a.handle(), weights.data(), vf.data(), ssf.data()), "linear::interpolate");
-    vectorgpuField g(n);                                                          // gaussGrad::gradf: internal faces, then every patch
     miCheck(mi_gauss_grad(a.handle(), Sf.component(0).data(), Sf.component(1).data(), Sf.component(2).data(), ssf.data(), nullptr,
-                          g.component(0).data(), g.component(1).data(), g.component(2).data()), "gaussGrad::gradf");
+                          g.component(0).data(), g.component(1).data(), g.component(2).data()), "gaussGrad::gradf");   // internal faces, then every patch
     for (std::size_t p = 0; p < patchFaceCells_.size(); ++p) {
         const label np = (label)patchFaceCells_[p].size();
         if (np == 0) continue;
@@ -720,13 +717,40 @@ void fvScalarMatrix::nonOrthCorrection(const scalargpuField& vf, const std::vect
         for (direction d = 0; d < 3; ++d)
             miCheck(mi_patch_add_product(P, patchSf[p]->component(d).data(), pv->data(), g.component(d).data(), 0), "gaussGrad::gradf (patch)");
     }
-    for (direction d = 0; d < 3; ++d) miCheck(mi_vec_div(ctx, n, g.component(d).data(), V.data(), g.component(d).data()), "gaussGrad /= V");
-    scalargpuField flux(nI), div(n);
+    for (direction d = 0; d < 3; ++d) miCheck(mi_vec_div(miEngine::New().ctx, n, g.component(d).data(), V.data(), g.component(d).data()), "gaussGrad /= V");
+}
+void fvScalarMatrix::subtractFluxDivergence(const scalargpuField& flux, const scalargpuField& V)
+{
+    const lduAddressing& a = lduAddr();
+    scalargpuField div(a.size());
+    miCheck(mi_surface_integrate(a.handle(), flux.data(), V.data(), div.data()), "fvc::div");
+    miCheck(mi_vec_submul(miEngine::New().ctx, a.size(), V.data(), div.data(), source_.data()), "fvm::laplacian: source -= V*div(correction)");
+}
+void fvScalarMatrix::nonOrthCorrection(const scalargpuField& vf, const std::vector<const scalargpuField*>& patchValues, const vectorgpuField& Sf,
+                                       const std::vector<const vectorgpuField*>& patchSf, const scalargpuField& weights, const vectorgpuField& corrVecs,
+                                       const scalargpuField& gammaMagSf, const scalargpuField& V)
+{
+    const lduAddressing& a = lduAddr();
+    vectorgpuField g(a.size());
+    gaussGradOf(g, vf, patchValues, Sf, patchSf, weights, V);
+    scalargpuField flux(weights.size());
     miCheck(mi_sngrad_correction_flux(a.handle(), corrVecs.component(0).data(), corrVecs.component(1).data(), corrVecs.component(2).data(), weights.data(),
                                       g.component(0).data(), g.component(1).data(), g.component(2).data(), gammaMagSf.data(), flux.data()),
             "correctedSnGrad::correction");
-    miCheck(mi_surface_integrate(a.handle(), flux.data(), V.data(), div.data()), "fvc::div");
-    miCheck(mi_vec_submul(ctx, n, V.data(), div.data(), source_.data()), "fvm::laplacian: source -= V*div(correction)");
+    subtractFluxDivergence(flux, V);
+}
+void fvScalarMatrix::nonOrthCorrection(const fv::snGradScheme& scheme, const scalargpuField& vf, const std::vector<const scalargpuField*>& patchValues,
+                                       const vectorgpuField& Sf, const std::vector<const vectorgpuField*>& patchSf, const scalargpuField& weights,
+                                       const scalargpuField& deltaCoeffs, const vectorgpuField& corrVecs, const scalargpuField& gammaMagSf,
+                                       const scalargpuField& V)
+{
+    if (!scheme.corrected()) return;
+    if (!scheme.limited()) { nonOrthCorrection(vf, patchValues, Sf, patchSf, weights, corrVecs, gammaMagSf, V); return; }
+    vectorgpuField g(lduAddr().size());
+    gaussGradOf(g, vf, patchValues, Sf, patchSf, weights, V);
+    scalargpuField flux(weights.size());
+    fvc::snGradLimitedCorrectionFlux(flux, lduAddr(), scheme, corrVecs, weights, deltaCoeffs, vf, g, gammaMagSf);
+    subtractFluxDivergence(flux, V);
 }
 fvScalarMatrix& fvScalarMatrix::operator+=(const fvScalarMatrix& B) { axpyFrom(B, 1.0); return *this; }
 fvScalarMatrix& fvScalarMatrix::operator-=(const fvScalarMatrix& B) { axpyFrom(B, -1.0); return *this; }
@@ -1077,6 +1101,59 @@ fv::limitedGradScheme fv::limitedGradScheme::New(const std::string& scheme)
     mi_grad_limiter l{};
     miCheck(mi_grad_limiter_parse(scheme.c_str(), &l), "gradScheme::New");
     return limitedGradScheme(l);
+}
+// ---- the snGrad schemes ---------------------------------------------------------------------------------------------------------------
+fv::snGradScheme fv::snGradScheme::New(const std::string& scheme)
+{
+    mi_sngrad_scheme s{};
+    miCheck(mi_sngrad_parse(scheme.c_str(), &s), "snGradScheme::New");
+    return snGradScheme(s);
+}
+fv::snGradScheme fv::snGradScheme::laplacian(const std::string& where, const std::string& term, const std::vector<std::string>& scheme,
+                                             const std::function<std::vector<std::string>()>& snGradEntry)
+{
+    const std::string forms = "laplacianSchemes " + term + ": Gauss linear corrected | uncorrected | orthogonal | limited [corrected] <k>";
+    if (scheme.size() < 3 || scheme[0] != "Gauss" || scheme[1] != "linear") FatalErrorIn(where, forms);
+    std::string tail;
+    for (std::size_t i = 2; i < scheme.size(); ++i) tail += (i > 2 ? " " : "") + scheme[i];
+    mi_sngrad_scheme s{};
+    if (mi_sngrad_parse(tail.c_str(), &s) != 0) FatalErrorIn(where, forms + " (" + mi_last_error() + ")");
+    if (s.kind == MI_SNGRAD_LIMITED) {
+        const std::vector<std::string> words = snGradEntry();
+        std::string entry;
+        for (std::size_t i = 0; i < words.size(); ++i) entry += (i ? " " : "") + words[i];
+        mi_sngrad_scheme e{};
+        if (mi_sngrad_parse(entry.c_str(), &e) != 0 || e.kind != s.kind || e.limit_coeff != s.limit_coeff)
+            FatalErrorIn(where, forms + " ('" + tail + "' needs the same snGradSchemes entry; that one says '" + entry + "')");
+    }
+    return snGradScheme(s);
+}
+void fvc::snGradLimitedCorrectionFlux(scalargpuField& flux, const lduAddressing& a, const fv::snGradScheme& s, const vectorgpuField& corrVecs,
+                                      const scalargpuField& weights, const scalargpuField& deltaCoeffs, const scalargpuField& vf, const vectorgpuField& gradVf,
+                                      const scalargpuField& gammaMagSf, scalargpuField* limiter)
+{
+    if (!s.limited()) FatalErrorIn("fvc::snGradLimitedCorrectionFlux", "the scheme is not `limited`");
+    const double* v[1] = {vf.data()};
+    const double* g[3] = {gradVf.component(0).data(), gradVf.component(1).data(), gradVf.component(2).data()};
+    double* out[1] = {flux.data()};
+    miCheck(mi_sngrad_limited_correction_flux(a.handle(), 1, s.limitCoeff(), corrVecs.component(0).data(), corrVecs.component(1).data(),
+                                              corrVecs.component(2).data(), weights.data(), deltaCoeffs.data(), v, g, gammaMagSf.data(), out,
+                                              limiter ? limiter->data() : nullptr), "limitedSnGrad::correction");
+}
+void fvc::snGradLimitedCorrectionFlux(vectorgpuField& flux, const lduAddressing& a, const fv::snGradScheme& s, const vectorgpuField& corrVecs,
+                                      const scalargpuField& weights, const scalargpuField& deltaCoeffs, const vectorgpuField& vf,
+                                      const vectorgpuField* const gradVf[3], const scalargpuField& gammaMagSf, scalargpuField* limiter)
+{
+    if (!s.limited()) FatalErrorIn("fvc::snGradLimitedCorrectionFlux", "the scheme is not `limited`");
+    const double *v[3], *g[9];
+    double* out[3];
+    for (int j = 0; j < 3; ++j) {
+        v[j] = vf.component(j).data(); out[j] = flux.component(j).data();
+        for (int d = 0; d < 3; ++d) g[3 * j + d] = gradVf[j]->component(d).data();
+    }
+    miCheck(mi_sngrad_limited_correction_flux(a.handle(), 3, s.limitCoeff(), corrVecs.component(0).data(), corrVecs.component(1).data(),
+                                              corrVecs.component(2).data(), weights.data(), deltaCoeffs.data(), v, g, gammaMagSf.data(), out,
+                                              limiter ? limiter->data() : nullptr), "limitedSnGrad::correction");
 }
 gradBoundary::gradBoundary(const lduAddressing& a, const std::vector<labelList>& faceCells, const std::vector<patchKind>& kinds) : h_(nullptr)
 {

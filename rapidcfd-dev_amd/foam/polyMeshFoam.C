@@ -15,6 +15,8 @@
 //        (host only: <caseDir>/0/<object> is read, written as <caseDir>/<timeName>/<object>, read again and compared)
 // -nonOrthCorrectors N: afterwards, laplacianFoam's non-orthogonal corrector loop (laplacianFoam.C:60-70) with the `corrected`
 // snGrad scheme: N times { assemble fvm::laplacian incl. the explicit correction from the current p; solve with PCG + DIC }.
+// With a <caseDir>/system/fvSchemes the scheme is its laplacianSchemes entry for laplacian(p): Gauss linear corrected | uncorrected |
+// orthogonal | limited [corrected] k (a limited one beside the same snGradSchemes entry).
 #include "polyMesh.H"
 #include "solution.H"
 
@@ -175,11 +177,15 @@ int main(int argc, char** argv)
             for (const polyPatch& P : mesh.boundary) zeros.emplace_back(P.nFaces);
             std::vector<const scalargpuField*> pv;                        // fixedValue 0 on `patch`, zeroGradient (patchInternalField) on `wall`
             for (std::size_t p = 0; p < patches.size(); ++p) pv.push_back(mesh.boundary[p].type == "patch" ? &zeros[p] : nullptr);
-            const scalargpuField weights(mesh.weights), gammaMagSf(magSfI), V(mesh.V);
+            const scalargpuField weights(mesh.weights), gammaMagSf(magSfI), V(mesh.V), deltaCoeffs(mesh.nonOrthDeltaCoeffs);
+            fv::snGradScheme snGrad = fv::snGradScheme::New("corrected");
+            if (std::ifstream(caseDir + "/system/fvSchemes").good())
+                snGrad = fv::snGradScheme::laplacian("polyMeshFoam", "laplacian(p)", fvSchemes(caseDir).laplacianScheme("laplacian(p)"),
+                                                     [&] { return fvSchemes(caseDir).snGradScheme("snGrad(p)"); });
             scalargpuField p(n);
             for (label corr = 0; corr < nCorr; ++corr) {
                 pEqn.source() = S;
-                pEqn.nonOrthCorrection(p, pv, SfI, pSf, weights, corrVecs, gammaMagSf, V);
+                pEqn.nonOrthCorrection(snGrad, p, pv, SfI, pSf, weights, deltaCoeffs, corrVecs, gammaMagSf, V);
                 pEqn.solve(p, dictionary{{"solver", "PCG"}, {"preconditioner", "DIC"}, {"tolerance", "1e-10"}, {"relTol", "0"}});
             }
             std::vector<scalar> h = p.asHost();

@@ -5,7 +5,7 @@
 //
 // in a given velocity field, on a case directory: constant/polyMesh, constant/transportProperties (DT), system/controlDict (deltaT, endTime,
 // writeFormat, writePrecision), system/fvSchemes (ddt(T): Euler | backward; div(phi,T): Gauss linear | upwind | limitedLinear k; laplacian: Gauss linear corrected |
-// uncorrected | orthogonal), system/fvSolution (solvers.T, SIMPLE.nNonOrthogonalCorrectors), 0/T and 0/U with fixedValue (inflow) and
+// uncorrected | orthogonal | limited [corrected] k), system/fvSolution (solvers.T, SIMPLE.nNonOrthogonalCorrectors), 0/T and 0/U with fixedValue (inflow) and
 // zeroGradient (outflow, walls) patches [U: also noSlip].  The whole equation is ONE assembly pass (fvm::assemble -> mi_fvm_assemble); the patch
 // coefficients are the reference's: gaussConvectionScheme.C:96-110 (internalCoeffs = phi_b valueInternalCoeffs, boundaryCoeffs = -phi_b
 // valueBoundaryCoeffs: fixedValue 0 / T_b, zeroGradient 1 / 0) and gaussLaplacianScheme.C:60-88 (fixedValue: DT |Sf| deltaCoeffs on both, with the
@@ -60,9 +60,8 @@ int main(int argc, char** argv)
         const bool upwind = divT[1] == "upwind", limited = divT[1] == "limitedLinear";
         const scalar limiterK = limited ? std::strtod(divT[2].c_str(), nullptr) : 0.0;
         const wordList lap = schemes.laplacianScheme("laplacian(DT,T)");
-        if (lap.size() != 3 || lap[0] != "Gauss" || lap[1] != "linear" || (lap[2] != "orthogonal" && lap[2] != "uncorrected" && lap[2] != "corrected"))
-            FatalErrorIn("scalarTransportFoam", "laplacianSchemes laplacian(DT,T): Gauss linear corrected | uncorrected | orthogonal");
-        const bool corrected = lap[2] == "corrected";
+        const fv::snGradScheme lapSnGrad = fv::snGradScheme::laplacian("scalarTransportFoam", "laplacian(DT,T)", lap, [&] { return schemes.snGradScheme("snGrad(T)"); });   // refuses anything else
+        const bool corrected = lapSnGrad.corrected();          // `corrected` and `limited [corrected] k`: an explicit non-orthogonal part
         Info << "Create mesh: nCells " << n << " nInternalFaces " << nI << " patches " << nP << "; DT " << DT << " deltaT " << deltaT << " steps " << nSteps
              << " div(phi,T) " << divT[1] << " laplacian " << lap[2] << " nNonOrthogonalCorrectors " << nNonOrthCorr << std::endl;
 
@@ -165,7 +164,8 @@ int main(int argc, char** argv)
                 for (label q = 0; q < nP; ++q) { TEqn.internalCoeffs()[q] = icDev[q]; TEqn.boundaryCoeffs()[q] = bcDev[q]; }
                 if (corrected) {                                // - fvm::laplacian(DT, T), corrected: source += V*div(DT |Sf| correction(T))
                     scalargpuField cf(nI), d(n);
-                    fvc::snGradCorrectionFlux(cf, addr, corrVecs, weights, gT, negDtMagSf);
+                    if (lapSnGrad.limited()) fvc::snGradLimitedCorrectionFlux(cf, addr, lapSnGrad, corrVecs, weights, deltaCoeffs, T, gT, negDtMagSf);
+                    else fvc::snGradCorrectionFlux(cf, addr, corrVecs, weights, gT, negDtMagSf);
                     fvc::surfaceIntegrate(d, addr, cf, &V);
                     fieldSubMul(TEqn.source(), V, d);
                 }
