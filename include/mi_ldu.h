@@ -784,6 +784,41 @@ int mi_patch_sngrad_limited_correction_flux(mi_patch_t patch, int32_t n_comp, do
                                             const double *const *nbr_vf_dev, const double *const *grad_dev,
                                             const double *const *nbr_grad_dev, const double *gamma_magsf_dev_or_null,
                                             double *const *flux_out_dev, double *limiter_out_dev_or_null);
+/* ---- fvc::div(nuEff*dev(T(fvc::grad(U)))) and fvc::div(muEff*dev2(T(fvc::grad(U)))): the explicit term of divDevReff / divDevRhoReff
+ * (incompressible laminar.C:202-225, compressible laminar.C:197, eddyViscosity.C:132).  grad[3*j + k] = d(U_j)/dx_k, nine
+ * cell arrays (component j's mi_gauss_grad + patches + /V); kind MI_DEV (dev, coefficient 1.0/3.0) or MI_DEV2 (dev2, 2.0/3.0:
+ * TensorI.H:534-546).  Per cell, every operation rounded as the reference's cell fields round it:
+ *     tr = (grad[0] + grad[4]) + grad[8];  ii = coeff*tr;  X_kj = grad[3*k + j] - (k == j ? ii : 0);  Y_kj = visc*X_kj.
+ * grad_dev, face_out_dev, div_out_dev and the other `const double *const *` arguments are HOST arrays of device pointers.
+ * mi_fvc_div_dev_tgrad: the internal faces, one face pass (a face gathers the ten cell values of its two cells once) and one row pass
+ *   for the three components:  I_kj = fma(lambda, Y_kj[P] - Y_kj[N], Y_kj[N]),  face_out[j] = fma(I_zj, Sf_z, fma(I_xj, Sf_x, I_yj*Sf_y)),
+ *   div_out[j] = surfaceIntegrate(face_out[j]) [/ vol] in mi_surface_integrate's order -- bit for bit mi_flux_div(v = column j of X,
+ *   cell_scale = visc).  `Vector & Tensor` is contracted per column as `Vector & Vector` is (an assumption: DESIGN 3.5a).  face_out is
+ *   kept for the caller.  A case with patches passes vol NULL, adds the patch fluxes below with mi_patch_add in patch order, then mi_vec_div.
+ *   Zero cells: MI_OK, nothing written.  Zero faces: MI_OK, div_out zeroed, the face arrays may be NULL.
+ * mi_patch_gauss_grad_correct: the boundary values of a Gauss gradient on a patch that is NOT coupled (gaussGrad.C:277-303) for n_comp 1
+ *   or 3:  n_k = Sf_k/magSf,  out[3*j + k] = g_k + n_k*(sngrad[j] - fma(n_z, g_z, fma(n_x, g_x, n_y*g_y))),  g = grad[3*j + .] at the
+ *   face's cell (the zeroGradient value).  patch_sngrad[j]: the field's snGrad on the patch, deltaCoeffs*(U_b - U_internal) for a
+ *   fixedValue patch, zeros for zeroGradient.  Outputs: 3*n_comp patch arrays.
+ * mi_patch_dev_tgrad_flux: the three flux components on one patch's faces, flux[j] = Sf_b & column j of (visc*dev[2](T(G))).
+ *   patch_weights NULL -- any patch that is not coupled: visc_dev and grad_dev[9] are the patch's own BOUNDARY values (patch arrays, e.g.
+ *   from mi_patch_gauss_grad_correct); nbr_* are not read.  patch_weights given -- a coupled patch (processor; cyclic WITHOUT rotation):
+ *   visc_dev and grad_dev[9] are the CELL arrays (read through faceCells), nbr_visc_dev / nbr_grad_dev[9] the patchNeighbourFields per
+ *   patch face; Y is formed on each side and I = (w*Y_P) + ((1 - w)*Y_N), uncontracted.  A transforming (rotational) coupled patch is
+ *   out of scope: the call does not transform the neighbour side.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): a kind other than the two, n_comp other than 1 or 3, a missing array or one
+ *   not aligned for a double, an output that aliases an input or another output. */
+enum { MI_DEV, MI_DEV2 };
+int mi_fvc_div_dev_tgrad(mi_addr_t addr, int32_t kind, const double *lambda_dev, const double *sfx_dev, const double *sfy_dev,
+                         const double *sfz_dev, const double *visc_dev, const double *const *grad_dev, const double *vol_dev_or_null,
+                         double *const *face_out_dev, double *const *div_out_dev);
+int mi_patch_gauss_grad_correct(mi_patch_t patch, int32_t n_comp, const double *patch_sfx_dev, const double *patch_sfy_dev,
+                                const double *patch_sfz_dev, const double *patch_magsf_dev, const double *const *patch_sngrad_dev,
+                                const double *const *grad_dev, double *const *patch_grad_out_dev);
+int mi_patch_dev_tgrad_flux(mi_patch_t patch, int32_t kind, const double *patch_sfx_dev, const double *patch_sfy_dev,
+                            const double *patch_sfz_dev, const double *patch_weights_dev_or_null, const double *visc_dev,
+                            const double *const *grad_dev, const double *nbr_visc_dev, const double *const *nbr_grad_dev,
+                            double *const *flux_out_dev);
 /* fvPatchField::patchInternalField: out[i] = psi[faceCells[i]] (zeroGradient boundary values for the Gauss gradient, fvMatrix::flux ...) */
 int mi_patch_internal_field(mi_patch_t patch, const double *psi_dev, double *out_dev);
 /* inout -= x*y, the product rounded before the subtraction (a temporary field, then operator-=) */

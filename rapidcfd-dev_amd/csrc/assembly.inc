@@ -486,6 +486,122 @@ __global__ void k_patch_sngrad_limited_flux(const int32_t* __restrict__ faceCell
     }
     sngrad_limited_store<NCOMP>(a, i, sngrad_limiter<NCOMP>(a.k, a.oneMinusK, sn, corr), corr);
 }
+
+// ---- fvc::div(nuEff*dev(T(fvc::grad(U)))) / fvc::div(muEff*dev2(T(fvc::grad(U)))): the explicit term of divDevReff / divDevRhoReff --
+// (incompressible laminar.C:202-225, compressible laminar.C:197, eddyViscosity.C:132).  The reference forms four cell tensor fields
+// (grad, T, dev, the product), interpolates nine components and contracts with Sf; here a face gathers the ten cell values (viscosity,
+// g[3*j + k] = d(U_j)/dx_k) of each of its two cells ONCE, forms Y in registers and writes the three flux components.  Per cell, each
+// operation rounded as the reference's cell fields round it:
+//   tr = (g[0] + g[4]) + g[8]                    TensorI.H:465-468 (the transposition keeps the diagonal)
+//   ii = coeff*tr                                SphericalTensor(coeff)*tr, coeff 1.0/3.0 (dev) | 2.0/3.0 (dev2): TensorI.H:534-546
+//   X_kj = g[3*k + j] - (k == j ? ii : 0)        T(...), TensorI.H:699-707; off-diagonals untouched
+//   Y_kj = visc*X_kj
+// y[3*k + j] = Y_kj: the storage of g, because T(gradU)_kj = gradU_jk = d(U_k)/dx_j = g[3*k + j].
+// Per face and component j: I_kj = fma(lambda, Y_kj[P] - Y_kj[N], Y_kj[N]) and flux_j = fma(I_zj, Sf_z, fma(I_xj, Sf_x, I_yj*Sf_y)) --
+// flux_face with v = column j of X and the viscosity as its cell scale, operation for operation (`Vector & Tensor` contracted per
+// column as `Vector & Vector` is: the standing assumption of DESIGN 3.5a, restated in 3.5f).
+template <int KIND>
+__device__ __forceinline__ void dev_tgrad_cell(double visc, const double (&g)[9], double (&y)[9])
+{
+    constexpr double coeff = KIND == MI_DEV ? 1.0 / 3.0 : 2.0 / 3.0;
+    const double tr = (g[0] + g[4]) + g[8];
+    const double ii = coeff * tr;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const double x = (i % 4 == 0) ? g[i] - ii : g[i];
+        y[i] = visc * x;
+    }
+}
+// flux_j = Sf & column j of the face tensor t (t[3*k + j])
+__device__ __forceinline__ double dev_tgrad_dot(const double (&t)[9], int j, double sx, double sy, double sz)
+{
+    return fma(t[6 + j], sz, fma(t[j], sx, t[3 + j] * sy));
+}
+struct DevTGradArgs {
+    const int32_t *lo, *up;
+    const double *lam, *s[3], *visc, *g[9];
+    double* out[3];
+    int nf, xcd;
+};
+// XCD-aware chunks as the other gathering face passes (k_limited_weights, k_ddt_phi_corr_backward)
+template <int KIND>
+__global__ void k_face_dev_tgrad_flux(const DevTGradArgs a)
+{
+    int f0, f1; block_chunk(a.nf, a.xcd, f0, f1);
+    for (int f = f0 + threadIdx.x; f < f1; f += blockDim.x) {
+        const int P = a.lo[f], N = a.up[f];
+        const double l = a.lam[f], sx = a.s[0][f], sy = a.s[1][f], sz = a.s[2][f];
+        double gP[9], gN[9], yP[9], yN[9], t[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { gP[i] = a.g[i][P]; gN[i] = a.g[i][N]; }
+        dev_tgrad_cell<KIND>(a.visc[P], gP, yP);
+        dev_tgrad_cell<KIND>(a.visc[N], gN, yN);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) t[i] = fma(l, yP[i] - yN[i], yN[i]);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a.out[j][f] = dev_tgrad_dot(t, j, sx, sy, sz);
+    }
+}
+// the same on one patch.  COUPLED (processor; cyclic without rotation): the cell side through faceCells from the cell arrays, the
+// other side the caller's patchNeighbourFields (nine gradient arrays and the viscosity per patch face), Y formed on each side,
+// I = (w*Y_P) + ((1 - w)*Y_N) uncontracted (separate field operations in the reference: sngrad_patch_corr's rule).  Not COUPLED: the
+// patch's own boundary values visc_b and G_b (mi_patch_gauss_grad_correct), no interpolation.
+struct PatchDevTGradArgs {
+    const int32_t* fc;
+    const double *w, *s[3], *visc, *g[9], *nvisc, *ng[9];
+    double* out[3];
+    int n;
+};
+template <int KIND, bool COUPLED>
+__global__ void k_patch_dev_tgrad_flux(const PatchDevTGradArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int c = COUPLED ? a.fc[i] : i;
+    double g[9], t[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) g[q] = a.g[q][c];
+    dev_tgrad_cell<KIND>(a.visc[c], g, t);
+    if (COUPLED) {
+        double yN[9];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) g[q] = a.ng[q][i];
+        dev_tgrad_cell<KIND>(a.nvisc[i], g, yN);
+        const double l = a.w[i], m = 1.0 - l;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) { const double p = l * t[q], n = m * yN[q]; t[q] = p + n; }
+    }
+    const double sx = a.s[0][i], sy = a.s[1][i], sz = a.s[2][i];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a.out[j][i] = dev_tgrad_dot(t, j, sx, sy, sz);
+}
+// gaussGrad::correctBoundaryConditions on a patch that is not coupled (gaussGrad.C:277-303):
+//   gGradbf += n*(vsf.boundaryField().snGrad() - (n & gGradbf)),   n = Sf/magSf (each component rounded),
+// gGradbf the zeroGradient value gGrad.correctBoundaryConditions() leaves = the cell gradient through faceCells.  Per component j
+//   gb_k = g_k + n_k*(sn_j - fma(n_z, g_z, fma(n_x, g_x, n_y*g_y))):  product, difference and sum each rounded.
+template <int NCOMP>
+struct PatchGradCorrArgs {
+    const int32_t* fc;
+    const double *s[3], *magSf, *sn[NCOMP], *g[3 * NCOMP];
+    double* out[3 * NCOMP];
+    int n;
+};
+template <int NCOMP>
+__global__ void k_patch_gauss_grad_correct(const PatchGradCorrArgs<NCOMP> a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int c = a.fc[i];
+    const double m = a.magSf[i];
+    const double nx = a.s[0][i] / m, ny = a.s[1][i] / m, nz = a.s[2][i] / m;
+#pragma unroll
+    for (int j = 0; j < NCOMP; ++j) {
+        const double gx = a.g[3 * j][c], gy = a.g[3 * j + 1][c], gz = a.g[3 * j + 2][c];
+        const double d = a.sn[j][i] - fma(nz, gz, fma(nx, gx, ny * gy));
+        const double cx = nx * d, cy = ny * d, cz = nz * d;
+        a.out[3 * j][i] = gx + cx; a.out[3 * j + 1][i] = gy + cy; a.out[3 * j + 2][i] = gz + cz;
+    }
+}
 // fvPatchField::patchInternalField: out[i] = psi[faceCells[i]]
 __global__ void k_patch_internal_field(const int32_t* __restrict__ faceCells, const double* __restrict__ psi, double* __restrict__ out, int n)
 {
@@ -942,6 +1058,58 @@ __global__ __launch_bounds__(BS) void k_gauss_grad(const GradArgs a)
     }
     if (a.vol) { const double v = a.vol[c]; ox /= v; oy /= v; oz /= v; }
     a.gx[c] = ox; a.gy[c] = oy; a.gz[c] = oz;
+}
+// fvc::surfaceIntegrate of three face fields at once (the flux components of k_face_dev_tgrad_flux): k_gauss_grad's skeleton with
+// three staged face arrays and plain sums -- own faces ascending +, then the losort faces -, then the optional /V, the order of
+// mi_surface_integrate (lduAddressingFunctors.H:10-64) -- so the row tables are read once for the three components
+struct RowSum3Args {
+    const int32_t *os, *ls, *losort, *blockStart;
+    const double *f[3], *vol;
+    double* out[3];
+    int n, cap, xcd;
+};
+template <int BS>
+__global__ __launch_bounds__(BS) void k_row_sum3(const RowSum3Args a)
+{
+    extern __shared__ __attribute__((aligned(16))) double rp_smem[];
+    double *s0 = rp_smem, *s1 = s0 + a.cap, *s2 = s1 + a.cap;
+    const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
+    int c0, cEnd;
+    if (a.blockStart) { c0 = a.blockStart[lb]; cEnd = a.blockStart[lb + 1]; }
+    else { c0 = lb * BS; cEnd = min(c0 + BS, a.n); }
+    const int tid = threadIdx.x, c = c0 + tid;
+    const bool live = c < cEnd;
+    const int f0 = a.os[c0], nf = a.os[cEnd] - f0;
+    const bool staged = nf <= a.cap;
+    if (staged) { stage_dma8<BS>(a.f[0] + f0, s0, nf, tid); stage_dma8<BS>(a.f[1] + f0, s1, nf, tid); stage_dma8<BS>(a.f[2] + f0, s2, nf, tid); }
+    int nb = 0, ne = 0;
+    if (live) { nb = a.ls[c]; ne = a.ls[c + 1]; }
+    const int cnt = ne - nb;
+    int nfk[4]; double n0[4], n1[4], n2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        nfk[k] = (k < cnt) ? a.losort[nb + k] : 0;
+        if (k < cnt && (!staged || nfk[k] < f0)) { const int f = nfk[k]; n0[k] = a.f[0][f]; n1[k] = a.f[1][f]; n2[k] = a.f[2][f]; }
+        else { n0[k] = n1[k] = n2[k] = 0.0; }
+    }
+    __syncthreads();
+    if (!live) return;
+    double o0 = 0, o1 = 0, o2 = 0;
+    const int ob = a.os[c], oe = a.os[c + 1];
+    if (staged) for (int j = ob - f0; j < oe - f0; ++j) { o0 += s0[j]; o1 += s1[j]; o2 += s2[j]; }
+    else for (int j = ob; j < oe; ++j) { o0 += a.f[0][j]; o1 += a.f[1][j]; o2 += a.f[2][j]; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) if (k < cnt) {
+        if (staged && nfk[k] >= f0) { const int j = nfk[k] - f0; n0[k] = s0[j]; n1[k] = s1[j]; n2[k] = s2[j]; }
+        o0 -= n0[k]; o1 -= n1[k]; o2 -= n2[k];
+    }
+    for (int j = nb + 4; j < ne; ++j) {
+        const int f = a.losort[j];
+        if (staged && f >= f0) { o0 -= s0[f - f0]; o1 -= s1[f - f0]; o2 -= s2[f - f0]; }
+        else { o0 -= a.f[0][f]; o1 -= a.f[1][f]; o2 -= a.f[2][f]; }
+    }
+    if (a.vol) { const double v = a.vol[c]; o0 /= v; o1 /= v; o2 /= v; }
+    a.out[0][c] = o0; a.out[1][c] = o1; a.out[2][c] = o2;
 }
 __global__ __launch_bounds__(RB) void k_vdiv(const double* x, const double* y, double* out, int64_t n) // out may alias x
 {
@@ -2177,6 +2345,132 @@ extern "C" int mi_gauss_grad(mi_addr_t a, const double* sfx_dev, const double* s
     if (rp.bs == 256) return row_launch(a, rp, k_gauss_grad<256>, ga, lds);
     if (rp.bs == 512) return row_launch(a, rp, k_gauss_grad<512>, ga, lds);
     return row_launch(a, rp, k_gauss_grad<1024>, ga, lds);
+}
+// ---- fvc::div(visc*dev[2](T(grad(U)))): internal faces, the boundary gradient, the patch flux (DESIGN 3.5f) ---------------------------
+namespace {
+// the arrays of one of the three entries: every one present and aligned for a double, no output among the inputs or twice
+int dev_tgrad_arrays(const std::string& who, const double* const* in, int nIn, double* const* out, int nOut)
+{
+    for (int i = 0; i < nIn; ++i) {
+        if (!in[i]) return fail(MI_ERR_ARG, who + ": an input array is missing");
+        if (!al8(in[i])) return fail(MI_ERR_ARG, who + ": arrays must be aligned to 8 bytes");
+    }
+    for (int o = 0; o < nOut; ++o) {
+        if (!out[o]) return fail(MI_ERR_ARG, who + ": an output array is missing");
+        if (!al8(out[o])) return fail(MI_ERR_ARG, who + ": arrays must be aligned to 8 bytes");
+        for (int i = 0; i < nIn; ++i) if (out[o] == in[i]) return fail(MI_ERR_ARG, who + ": an output must not alias an input");
+        for (int q = 0; q < o; ++q) if (out[o] == out[q]) return fail(MI_ERR_ARG, who + ": the outputs must differ");
+    }
+    return MI_OK;
+}
+int dev_kind(const std::string& who, int32_t kind)
+{
+    if (kind != MI_DEV && kind != MI_DEV2) return fail(MI_ERR_ARG, who + ": kind must be MI_DEV or MI_DEV2");
+    return MI_OK;
+}
+} // namespace
+extern "C" int mi_fvc_div_dev_tgrad(mi_addr_t a, int32_t kind, const double* lambda_dev, const double* sfx_dev, const double* sfy_dev,
+                                    const double* sfz_dev, const double* visc_dev, const double* const* grad_dev, const double* vol_dev_or_null,
+                                    double* const* face_out_dev, double* const* div_out_dev)
+{
+    const std::string who = "mi_fvc_div_dev_tgrad";
+    MICHK(dev_kind(who, kind));
+    if (!a) return fail(MI_ERR_ARG, who + ": bad argument");
+    if (!grad_dev || !face_out_dev || !div_out_dev) return fail(MI_ERR_ARG, who + ": a pointer table is missing");
+    if (a->L.nCells == 0) return MI_OK;
+    const double* in[16] = {visc_dev};
+    int nIn = 1;
+    for (int i = 0; i < 9; ++i) in[nIn++] = grad_dev[i];
+    if (vol_dev_or_null) in[nIn++] = vol_dev_or_null;
+    if (a->L.nFaces == 0) {                                      // no face (their arrays are empty), no launch: the sums are empty
+        MICHK(dev_tgrad_arrays(who, in, nIn, div_out_dev, 3));
+        HIPCHK(hipSetDevice(a->ctx->device));
+        for (int j = 0; j < 3; ++j) HIPCHK(hipMemsetAsync(div_out_dev[j], 0, (size_t)a->L.nCells * sizeof(double), a->ctx->stream));
+        return MI_OK;
+    }
+    for (const double* q : {lambda_dev, sfx_dev, sfy_dev, sfz_dev}) in[nIn++] = q;
+    double* out[6];
+    for (int j = 0; j < 3; ++j) { out[j] = face_out_dev[j]; out[3 + j] = div_out_dev[j]; }
+    MICHK(dev_tgrad_arrays(who, in, nIn, out, 6));
+    HIPCHK(hipSetDevice(a->ctx->device));
+    MICHK(ensure_caller_tables(a));
+    DevTGradArgs fa{};
+    fa.lo = a->lowerAddr.p; fa.up = a->upperAddr.p; fa.lam = lambda_dev; fa.s[0] = sfx_dev; fa.s[1] = sfy_dev; fa.s[2] = sfz_dev; fa.visc = visc_dev;
+    for (int i = 0; i < 9; ++i) fa.g[i] = grad_dev[i];
+    for (int j = 0; j < 3; ++j) fa.out[j] = face_out_dev[j];
+    fa.nf = a->L.nFaces; fa.xcd = a->ctx->xcdRows;
+    if (kind == MI_DEV) k_face_dev_tgrad_flux<MI_DEV><<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(fa);
+    else k_face_dev_tgrad_flux<MI_DEV2><<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(fa);
+    HIPCHK(hipGetLastError());
+    RowSum3Args ra{};
+    const mi_addr_s::RowPlan& rp = a->rowPlan[1];                // the gradient's plan: three staged arrays against its four
+    ra.os = a->ownerStartC.p; ra.ls = a->losortStartC.p; ra.losort = a->losortC.p; ra.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
+    for (int j = 0; j < 3; ++j) { ra.f[j] = face_out_dev[j]; ra.out[j] = div_out_dev[j]; }
+    ra.vol = vol_dev_or_null;
+    ra.n = a->L.nCells; ra.cap = row_cap(rp, 3); ra.xcd = a->ctx->xcdRows;
+    const size_t lds = (size_t)3 * ra.cap * sizeof(double);
+    if (rp.bs == 256) return row_launch(a, rp, k_row_sum3<256>, ra, lds);
+    if (rp.bs == 512) return row_launch(a, rp, k_row_sum3<512>, ra, lds);
+    return row_launch(a, rp, k_row_sum3<1024>, ra, lds);
+}
+namespace {
+template <int NCOMP>
+int patch_gauss_grad_correct(const std::string& who, mi_patch_s* p, const double* sfx, const double* sfy, const double* sfz, const double* magSf,
+                             const double* const* sn, const double* const* g, double* const* out)
+{
+    PatchGradCorrArgs<NCOMP> q{};
+    const double* in[4 + 4 * NCOMP] = {sfx, sfy, sfz, magSf};
+    int nIn = 4;
+    for (int j = 0; j < NCOMP; ++j) in[nIn++] = q.sn[j] = sn[j];
+    for (int i = 0; i < 3 * NCOMP; ++i) { in[nIn++] = q.g[i] = g[i]; q.out[i] = out[i]; }
+    MICHK(dev_tgrad_arrays(who, in, nIn, out, 3 * NCOMP));
+    q.fc = p->faceCells.p; q.s[0] = sfx; q.s[1] = sfy; q.s[2] = sfz; q.magSf = magSf; q.n = p->nFaces;
+    HIPCHK(hipSetDevice(p->ctx->device));
+    k_patch_gauss_grad_correct<NCOMP><<<(p->nFaces + 255) / 256, 256, 0, p->ctx->stream>>>(q);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+} // namespace
+extern "C" int mi_patch_gauss_grad_correct(mi_patch_t p, int32_t n_comp, const double* patch_sfx_dev, const double* patch_sfy_dev,
+                                           const double* patch_sfz_dev, const double* patch_magsf_dev, const double* const* patch_sngrad_dev,
+                                           const double* const* grad_dev, double* const* patch_grad_out_dev)
+{
+    const std::string who = "mi_patch_gauss_grad_correct";
+    if (n_comp != 1 && n_comp != 3) return fail(MI_ERR_ARG, who + ": n_comp must be 1 or 3");
+    if (!p) return fail(MI_ERR_ARG, who + ": bad argument");
+    if (!patch_sngrad_dev || !grad_dev || !patch_grad_out_dev) return fail(MI_ERR_ARG, who + ": a pointer table is missing");
+    if (p->nFaces == 0) return MI_OK;
+    if (n_comp == 1) return patch_gauss_grad_correct<1>(who, p, patch_sfx_dev, patch_sfy_dev, patch_sfz_dev, patch_magsf_dev, patch_sngrad_dev, grad_dev, patch_grad_out_dev);
+    return patch_gauss_grad_correct<3>(who, p, patch_sfx_dev, patch_sfy_dev, patch_sfz_dev, patch_magsf_dev, patch_sngrad_dev, grad_dev, patch_grad_out_dev);
+}
+extern "C" int mi_patch_dev_tgrad_flux(mi_patch_t p, int32_t kind, const double* patch_sfx_dev, const double* patch_sfy_dev, const double* patch_sfz_dev,
+                                       const double* patch_weights_dev_or_null, const double* visc_dev, const double* const* grad_dev,
+                                       const double* nbr_visc_dev, const double* const* nbr_grad_dev, double* const* flux_out_dev)
+{
+    const std::string who = "mi_patch_dev_tgrad_flux";
+    MICHK(dev_kind(who, kind));
+    if (!p) return fail(MI_ERR_ARG, who + ": bad argument");
+    const bool coupled = patch_weights_dev_or_null != nullptr;
+    if (!grad_dev || !flux_out_dev || (coupled && !nbr_grad_dev)) return fail(MI_ERR_ARG, who + ": a pointer table is missing");
+    if (p->nFaces == 0) return MI_OK;
+    PatchDevTGradArgs q{};
+    const double* in[24] = {patch_sfx_dev, patch_sfy_dev, patch_sfz_dev, visc_dev};
+    int nIn = 4;
+    for (int i = 0; i < 9; ++i) in[nIn++] = q.g[i] = grad_dev[i];
+    if (coupled) {
+        in[nIn++] = q.w = patch_weights_dev_or_null; in[nIn++] = q.nvisc = nbr_visc_dev;
+        for (int i = 0; i < 9; ++i) in[nIn++] = q.ng[i] = nbr_grad_dev[i];
+    }
+    MICHK(dev_tgrad_arrays(who, in, nIn, flux_out_dev, 3));
+    q.fc = p->faceCells.p; q.s[0] = patch_sfx_dev; q.s[1] = patch_sfy_dev; q.s[2] = patch_sfz_dev; q.visc = visc_dev; q.n = p->nFaces;
+    for (int j = 0; j < 3; ++j) q.out[j] = flux_out_dev[j];
+    HIPCHK(hipSetDevice(p->ctx->device));
+    const dim3 grid((p->nFaces + 255) / 256), block(256);
+    hipStream_t s = p->ctx->stream;
+    if (kind == MI_DEV) { if (coupled) k_patch_dev_tgrad_flux<MI_DEV, true><<<grid, block, 0, s>>>(q); else k_patch_dev_tgrad_flux<MI_DEV, false><<<grid, block, 0, s>>>(q); }
+    else { if (coupled) k_patch_dev_tgrad_flux<MI_DEV2, true><<<grid, block, 0, s>>>(q); else k_patch_dev_tgrad_flux<MI_DEV2, false><<<grid, block, 0, s>>>(q); }
+    HIPCHK(hipGetLastError());
+    return MI_OK;
 }
 extern "C" int mi_vec_axpby(mi_ctx_t c, int64_t n, double a, const double* x_dev, double b, const double* y_dev, double* out_dev)
 {

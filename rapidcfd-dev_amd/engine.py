@@ -74,6 +74,7 @@ SYMBOLS = [
     "mi_grad_limiter_parse", "mi_grad_boundary_create", "mi_grad_boundary_destroy", "mi_limited_grad",
     "mi_ddt_backward_coeffs", "mi_fvm_ddt_backward", "mi_fvc_ddt_backward", "mi_ddt_phi_corr_backward", "mi_fvm_assemble_backward",
     "mi_sngrad_parse", "mi_sngrad_limited_correction_flux", "mi_patch_sngrad_limited_correction_flux",
+    "mi_fvc_div_dev_tgrad", "mi_patch_gauss_grad_correct", "mi_patch_dev_tgrad_flux",
 ]
 
 
@@ -933,6 +934,21 @@ class Patch:
                                                            _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), pv(vf), pv(nbr_vf), pv(grad), pv(nbr_grad),
                                                            _ptr(gamma_magsf), pv(out), _ptr(limiter_out)))
 
+    def gauss_grad_correct(self, sf, magsf, sngrad, grad, out):
+        """the boundary values of a Gauss gradient on a patch that is NOT coupled (gaussGrad.C:277-303; mi_patch_gauss_grad_correct): sf [x, y, z]
+        and magsf patch arrays, sngrad 1 or 3 patch arrays (the field's snGrad on the patch: zeros for zeroGradient), grad 3 or 9 CELL arrays
+        (grad[3*j + k] = d(vf_j)/dx_k), out 3 or 9 patch arrays"""
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_patch_gauss_grad_correct(self.h, C.c_int32(len(sngrad)), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(magsf), pv(sngrad), pv(grad), pv(out)))
+
+    def dev_tgrad_flux(self, kind, sf, visc, grad, out, weights=None, nbr_visc=None, nbr_grad=None):
+        """Sf_b & (visc*dev[2](T(grad))) on the patch's faces, three components (mi_patch_dev_tgrad_flux); kind "dev" | "dev2".  weights None -- a patch
+        that is not coupled: visc and grad[9] are the patch's own boundary values (patch arrays).  weights given -- a coupled patch without
+        rotation: visc and grad[9] are the CELL arrays, nbr_visc / nbr_grad[9] their patchNeighbourFields"""
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs]) if xs is not None else None
+        _chk(lib().mi_patch_dev_tgrad_flux(self.h, C.c_int32(_dev_kind(kind)), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(weights), _ptr(visc), pv(grad),
+                                           _ptr(nbr_visc), pv(nbr_grad), pv(out)))
+
     def close(self):
         if self.h:
             lib().mi_patch_destroy(self.h)
@@ -1025,6 +1041,14 @@ def sngrad_parse(text: str) -> SnGradScheme:
     out = SnGradScheme()
     _chk(lib().mi_sngrad_parse(text.encode(), C.byref(out)))
     return out
+
+
+DEV_KINDS = ("dev", "dev2")        # MI_DEV, MI_DEV2: dev(T(grad(U))) of divDevReff, dev2(T(grad(U))) of divDevRhoReff
+
+
+def _dev_kind(kind) -> int:
+    """"dev" | "dev2" (or the number itself: the library refuses what it does not know)"""
+    return DEV_KINDS.index(kind) if kind in DEV_KINDS else int(kind)
 
 
 class GradBoundary:
@@ -1144,6 +1168,14 @@ class Assembly:
         _chk(lib().mi_sngrad_limited_correction_flux(self.addr.h, C.c_int32(len(vf)), C.c_double(limit_coeff), _ptr(corr_vecs[0]), _ptr(corr_vecs[1]),
                                                      _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), pv(vf), pv(grad), _ptr(gamma_magsf), pv(out),
                                                      _ptr(limiter_out)))
+
+    def div_dev_tgrad(self, kind, lam, sf, visc, grad, face_out, div_out, vol=None):
+        """fvc::div(visc*dev(T(grad))) ("dev": divDevReff) | fvc::div(visc*dev2(T(grad))) ("dev2": divDevRhoReff) on the internal faces in one face
+        pass and one row pass (mi_fvc_div_dev_tgrad): grad 9 cell arrays (grad[3*j + k] = d(U_j)/dx_k), face_out 3 face arrays (kept for the
+        patch sums and flux()), div_out 3 cell arrays [/ vol]"""
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_fvc_div_dev_tgrad(self.addr.h, C.c_int32(_dev_kind(kind)), _ptr(lam), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(visc), pv(grad),
+                                        _ptr(vol), pv(face_out), pv(div_out)))
 
     def linear_upwind_correction(self, face_flux, cf, c, grad, out, scale=1.0):
         """faceFlux*correction(vf) of linearUpwind (scale 1) / LUST (scale 0.25) on the internal faces, one face pass for len(out) <= 4 components

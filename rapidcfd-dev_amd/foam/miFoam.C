@@ -1155,6 +1155,67 @@ void fvc::snGradLimitedCorrectionFlux(vectorgpuField& flux, const lduAddressing&
                                               corrVecs.component(2).data(), weights.data(), deltaCoeffs.data(), v, g, gammaMagSf.data(), out,
                                               limiter ? limiter->data() : nullptr), "limitedSnGrad::correction");
 }
+// ---- divDevReff's explicit term -------------------------------------------------------------------------------------------------------
+void fvc::gaussGradBoundary(vectorgpuField& gb, const fvPatchCells& p, const vectorgpuField& pSf, const scalargpuField& pMagSf, const scalargpuField& pSnGrad,
+                            const vectorgpuField& gradVf)
+{
+    const double* sn[1] = {pSnGrad.data()};
+    const double* g[3] = {gradVf.component(0).data(), gradVf.component(1).data(), gradVf.component(2).data()};
+    double* out[3] = {gb.component(0).data(), gb.component(1).data(), gb.component(2).data()};
+    miCheck(mi_patch_gauss_grad_correct(p.handle(), 1, pSf.component(0).data(), pSf.component(1).data(), pSf.component(2).data(), pMagSf.data(), sn, g, out),
+            "gaussGrad::correctBoundaryConditions");
+}
+void fvc::gaussGradBoundary(vectorgpuField* const gb[3], const fvPatchCells& p, const vectorgpuField& pSf, const scalargpuField& pMagSf,
+                            const vectorgpuField& pSnGrad, const vectorgpuField* const gradVf[3])
+{
+    const double *sn[3], *g[9];
+    double* out[9];
+    for (int j = 0; j < 3; ++j) {
+        sn[j] = pSnGrad.component(j).data();
+        for (int k = 0; k < 3; ++k) { g[3 * j + k] = gradVf[j]->component(k).data(); out[3 * j + k] = gb[j]->component(k).data(); }
+    }
+    miCheck(mi_patch_gauss_grad_correct(p.handle(), 3, pSf.component(0).data(), pSf.component(1).data(), pSf.component(2).data(), pMagSf.data(), sn, g, out),
+            "gaussGrad::correctBoundaryConditions");
+}
+void fvc::divDevTGrad(vectorgpuField& div, const lduAddressing& a, devKind kind, const scalargpuField& weights, const vectorgpuField& Sf,
+                      const scalargpuField& visc, const vectorgpuField* const gradU[3], const std::vector<devTGradPatch>& patches, const scalargpuField& V,
+                      vectorgpuField* faceFlux)
+{
+    auto nine = [](const vectorgpuField* const g[3], const double* out[9]) {
+        for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) out[3 * j + k] = g[j]->component(k).data();
+    };
+    const double* g[9];
+    nine(gradU, g);
+    vectorgpuField own(faceFlux ? 0 : weights.size());
+    vectorgpuField& ff = faceFlux ? *faceFlux : own;
+    double* face[3] = {ff.component(0).data(), ff.component(1).data(), ff.component(2).data()};
+    double* sum[3] = {div.component(0).data(), div.component(1).data(), div.component(2).data()};
+    miCheck(mi_fvc_div_dev_tgrad(a.handle(), kind, weights.data(), Sf.component(0).data(), Sf.component(1).data(), Sf.component(2).data(), visc.data(), g,
+                                 nullptr, face, sum), "fvc::div(visc*dev(T(grad(U))))");
+    for (const devTGradPatch& p : patches) {                    // the boundary faces, in patch order (fvcSurfaceIntegrate.C:58-72)
+        const label np = p.cells->size();
+        if (np == 0) continue;
+        vectorgpuField pf(np);
+        double* out[3] = {pf.component(0).data(), pf.component(1).data(), pf.component(2).data()};
+        const double *pg[9], *ng[9];
+        if (p.weights) { nine(p.nbrGrad, ng); for (int i = 0; i < 9; ++i) pg[i] = g[i]; }
+        else nine(p.grad, pg);
+        miCheck(mi_patch_dev_tgrad_flux(p.cells->handle(), kind, p.Sf->component(0).data(), p.Sf->component(1).data(), p.Sf->component(2).data(),
+                                        p.weights ? p.weights->data() : nullptr, p.weights ? visc.data() : p.visc->data(), pg,
+                                        p.weights ? p.nbrVisc->data() : nullptr, p.weights ? ng : nullptr, out), "fvc::div(visc*dev(T(grad(U)))) (patch)");
+        for (direction d = 0; d < 3; ++d) p.cells->add(pf.component(d), div.component(d));
+    }
+    for (direction d = 0; d < 3; ++d) fieldDivide(div.component(d), div.component(d), V);
+}
+void fvVectorMatrix::subtractField(const vectorgpuField& vf, const scalargpuField& V)
+{
+    mi_ctx_t ctx = miEngine::New().ctx;
+    scalargpuField neg(V.size());
+    for (direction d = 0; d < 3; ++d) {
+        miCheck(mi_vec_axpby(ctx, V.size(), -1.0, vf.component(d).data(), 0.0, vf.component(d).data(), neg.data()), "fvMatrix - field: -field");
+        miCheck(mi_fvm_su(ctx, V.size(), V.data(), neg.data(), source_.component(d).data()), "fvMatrix - field: source += V*field");
+    }
+}
 gradBoundary::gradBoundary(const lduAddressing& a, const std::vector<labelList>& faceCells, const std::vector<patchKind>& kinds) : h_(nullptr)
 {
     if (faceCells.size() != kinds.size()) FatalErrorIn("gradBoundary", "one kind per patch");
