@@ -709,6 +709,72 @@ int mi_ddt_phi_corr_backward(mi_addr_t addr, double r_delta_t, const double coef
 int mi_fvm_assemble_backward(mi_addr_t addr, const mi_fvm_terms *terms, const mi_ddt_backward *bw, const mi_div_correction *corr_or_null,
                              double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev, double *const *source_out_dev,
                              double *sum_mag_off_diag_out_dev_or_null);
+/* ---- the CrankNicolson time scheme: the ddt0 state, fvm::ddt, fvc::ddt and the fused assembly ----
+ * CrankNicolsonDdtScheme<Type> (src/finiteVolume/finiteVolume/ddtSchemes/CrankNicolsonDdtScheme/CrankNicolsonDdtScheme.{H,C}), the
+ * !mesh().moving() branches.  The scheme carries STATE between time steps: ddt0(<name>), the previous step's time derivative, updated exactly
+ * once per time step on first use, multiplied by the off-centring coefficient oc; the step on which it is first used is Euler's.  Every
+ * expression below is evaluated by the reference as field operators, one pass and one rounding each; the engine rounds exactly as
+ * parenthesised here (no contraction).  off(x) = (oc < 1) ? oc*x : x (offCentre_, .C:250-267).
+ * NOT covered: the moving-mesh branches, the alpha*rho overloads, fvcDdtUfCorr, meshPhi; fvcDdt(dimensioned<Type>) (zero on a static mesh);
+ *   reading or writing a ddt0(...) file for restarts (that needs ddt0's boundary field, which no engine operator forms: the state lives in
+ *   memory for the run); icoFoam, which stays Euler-only.
+ * mi_ddt_cn_parse (host only): exactly `CrankNicolson <oc>` with 0 <= oc <= 1 (the constructor's check, .H:165-180), any whitespace between
+ *   and around.  MI_ERR_ARG with a message naming the token: a missing coefficient, an extra token, a non-number, NaN, oc outside [0, 1]
+ *   ("should be >= 0 and <= 1"), any other scheme name, the empty string.
+ * mi_ddt_cn_begin / mi_ddt_cn_step (host only): the DDt0Field's two time indices and the scalars of .C:186-247.
+ *   begin(oc, time_index): the ddt0 field is created (zero -- the CALLER zeroes its arrays) at this time index: start_time_index =
+ *   ddt0_time_index = time_index (ddt0_, .C:109-181).
+ *   step(state, time_index, deltaT, deltaT0): evaluate = (ddt0_time_index != time_index);
+ *       coef  = (time_index - start_time_index > 0) ? 1 + oc : 1;      r_dt_coef  = coef/deltaT     (one division)
+ *       coef0 = (time_index - start_time_index > 1) ? 1 + oc : 1;      r_dt_coef0 = coef0/deltaT0   (0 for deltaT0 <= 0 without evaluate)
+ *   and, when evaluate, ddt0_time_index = time_index -- the caller then runs mi_ddt_cn_update ONCE; a second step() in the same time step
+ *   (non-orthogonal correctors) returns the same r_dt_coef with evaluate 0.  So: the first step is pure Euler with ddt0 untouched, the second
+ *   has coef = 1 + oc, coef0 = 1, from the third on both are 1 + oc.  MI_ERR_ARG: deltaT <= 0; deltaT0 <= 0 when evaluate (read only then).
+ * mi_ddt_cn_update: the ddt0 update (.C:417-418, :507-508, :603-607; the same statements in fvmDdt :818-822, :900-904, :987-994) of n_fields
+ *   (1..4: the components of a vector) fields IN PLACE, one launch; element i of ddt0_inout_dev[k] is read and written by the same thread only
+ *     rho_old_dev NULL:  ddt0 = ((rDtCoef0*rho_value)*(psi0 - psi00)) - off(ddt0)             (rho_value 1: the plain form)
+ *     rho_old_dev given: ddt0 = (rDtCoef0*((rho0*psi0) - (rho00*psi00))) - off(ddt0)          (rho_old and rho_old_old together)
+ * mi_fvm_ddt_cn: fvmDdt(vf) .C:755-832, fvmDdt(dimensionedScalar rho, vf) :837-913, fvmDdt(volScalarField rho, vf) :919-1003; ddt0_dev
+ *   already updated for this time step
+ *     rho_dev NULL:  diag = (rDtCoef*rho_value)*V;  source = (((rDtCoef*rho_value)*psi0) + off(ddt0))*V
+ *     rho_dev given: diag = (rDtCoef*rho)*V;        source = (((rDtCoef*rho0)*psi0) + off(ddt0))*V       (rho and rho_old together)
+ * mi_fvc_ddt_cn: fvcDdt(vf) .C:426, fvcDdt(dimensionedScalar rho, vf) :516, fvcDdt(volScalarField rho, vf) :615-616
+ *     rho_dev NULL:  out = ((rDtCoef*rho_value)*(vf - vf0)) - off(ddt0)
+ *     rho_dev given: out = (rDtCoef*((rho*vf) - (rho0*vf0))) - off(ddt0)
+ *   The three device calls refuse (MI_ERR_ARG) a missing array, an unaligned array, an output that is also an input or another output, density
+ *   arrays given partly, and oc outside [0, 1].
+ * fvcDdtPhiCorr(U, phi) (.C:1164-1202) is Euler's expression with rDeltaT := rDtCoef: call mi_ddt_phi_corr with r_dt_coef.
+ * mi_fvm_assemble_cn: mi_fvm_assemble / mi_fvm_assemble_corrected (corr_or_null) with the CrankNicolson time derivative in the same row pass:
+ *   terms->ddt != 0 and terms->r_delta_t carries rDtCoef; cn = {oc, ddt0_dev[n_rhs]}.  diag's time part and the start of every source are
+ *   mi_fvm_ddt_cn's expressions -- off(ddt0) is added BEFORE the multiplication by V, which no su term of mi_fvm_assemble can express --
+ *   everything else is mi_fvm_assemble's, so the outputs equal mi_fvm_ddt_cn + mi_fvm_div + mi_fvm_laplacian + the mi_vec_axpby combinations
+ *   bit for bit.  MI_ERR_ARG: cn NULL, terms->ddt == 0, a missing ddt0 array, a ddt0 array among the outputs, oc outside [0, 1]; and every
+ *   refusal of mi_fvm_assemble[_corrected].                                                                                              */
+typedef struct mi_ddt_cn_state {
+    double oc;                                     /* the off-centring coefficient, 0 <= oc <= 1 */
+    int32_t start_time_index, ddt0_time_index;     /* DDt0Field::startTimeIndex() and the ddt0 field's own timeIndex() */
+} mi_ddt_cn_state;
+typedef struct mi_ddt_cn_scalars {
+    double r_dt_coef, r_dt_coef0;
+    int32_t evaluate;                              /* 1: run mi_ddt_cn_update with r_dt_coef0 before any other use of ddt0 in this time step */
+} mi_ddt_cn_scalars;
+typedef struct mi_ddt_cn_terms {
+    double oc;
+    const double *const *ddt0_dev;                 /* n_rhs ddt0 fields, already updated for this time step */
+} mi_ddt_cn_terms;
+int mi_ddt_cn_parse(const char *scheme, double *oc_out);
+int mi_ddt_cn_begin(double oc, int32_t time_index, mi_ddt_cn_state *state_out);
+int mi_ddt_cn_step(mi_ddt_cn_state *state, int32_t time_index, double delta_t, double delta_t0, mi_ddt_cn_scalars *out);
+int mi_ddt_cn_update(mi_ctx_t ctx, int64_t n, int32_t n_fields, double r_dt_coef0, double oc, double rho_value, const double *rho_old_dev,
+                     const double *rho_old_old_dev, const double *const *psi_old_dev, const double *const *psi_old_old_dev,
+                     double *const *ddt0_inout_dev);
+int mi_fvm_ddt_cn(mi_ctx_t ctx, int64_t n, double r_dt_coef, double oc, double rho_value, const double *rho_dev, const double *rho_old_dev,
+                  const double *vol_dev, const double *psi_old_dev, const double *ddt0_dev, double *diag_out_dev, double *source_out_dev);
+int mi_fvc_ddt_cn(mi_ctx_t ctx, int64_t n, double r_dt_coef, double oc, double rho_value, const double *rho_dev, const double *rho_old_dev,
+                  const double *vf_dev, const double *vf_old_dev, const double *ddt0_dev, double *out_dev);
+int mi_fvm_assemble_cn(mi_addr_t addr, const mi_fvm_terms *terms, const mi_ddt_cn_terms *cn, const mi_div_correction *corr_or_null,
+                       double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev, double *const *source_out_dev,
+                       double *sum_mag_off_diag_out_dev_or_null);
 /* fvMatrix::setReference (src/finiteVolume/fvMatrices/fvMatrix/fvMatrix.C:964-981; icoFoam.C:89, simpleFoam/pEqn.H:21: the pressure level of a
  * closed domain): source[celli] += diag[celli]*value; diag[celli] += diag[celli].  celli < 0 (the rank does not hold the cell): no-op. */
 int mi_fvm_set_reference(mi_addr_t addr, int32_t celli, double value, double *diag_dev, double *source_dev);

@@ -199,9 +199,19 @@ struct AsmCorrArgs : AsmArgs { const int32_t *lo, *up; CorrIn corr; };   // CORR
 struct BackIn { double cA, c0, c00; const double* rhoOldOld; const double* psiOldOld[4]; };
 struct AsmBackArgs : AsmArgs { BackIn bw; };
 struct AsmCorrBackArgs : AsmCorrArgs { BackIn bw; };
-template <bool CORR, bool BACK> struct AsmSel { typedef typename std::conditional<CORR, AsmCorrArgs, AsmArgs>::type type; };
-template <> struct AsmSel<false, true> { typedef AsmBackArgs type; };
-template <> struct AsmSel<true, true> { typedef AsmCorrBackArgs type; };
+// CN: the CrankNicolson time derivative (CrankNicolsonDdtScheme.C:755-1003, static mesh): rdt carries rDtCoef, the diagonal is Euler's with it,
+// and every source starts ((rdt*rho0)*psi0 + off(ddt0))*V -- ONE more cell array per right-hand side (ddt0, already updated for this time
+// step by mi_ddt_cn_update); off(x) = oc*x when offc (oc < 1, decided on the host: wave-uniform), else x (offCentre_, :250-267)
+struct CnIn { double oc; int offc; const double* ddt0[4]; };
+struct AsmCnArgs : AsmArgs { CnIn cn; };
+struct AsmCorrCnArgs : AsmCorrArgs { CnIn cn; };
+// the time form of a row pass: TF_EULER (or no time derivative: a.ddt), TF_BACK, TF_CN; each form's kernels take the arguments of that form only
+enum { TF_EULER = 0, TF_BACK = 1, TF_CN = 2 };
+template <bool CORR, int TF> struct AsmSel { typedef typename std::conditional<CORR, AsmCorrArgs, AsmArgs>::type type; };
+template <> struct AsmSel<false, TF_BACK> { typedef AsmBackArgs type; };
+template <> struct AsmSel<true, TF_BACK> { typedef AsmCorrBackArgs type; };
+template <> struct AsmSel<false, TF_CN> { typedef AsmCnArgs type; };
+template <> struct AsmSel<true, TF_CN> { typedef AsmCorrCnArgs type; };
 // fvm::ddt, backward: every product and difference rounded on its own (the reference's field operators; DESIGN 3.5d).  Constant density:
 // rho_value joins the (rDeltaT*V) factor; a density field: rho0 / rho00 join the coefficients inside the bracket.
 __device__ __forceinline__ double back_diag(double cA, double rho, double V) { return (cA * rho) * V; }
@@ -213,12 +223,17 @@ __device__ __forceinline__ double back_source_rho(double rdt, double c0, double 
 {
     return (rdt * V) * (((c0 * r0) * p0) - ((c00 * r00) * p00));
 }
+// fvm::ddt / fvc::ddt / the ddt0 update, CrankNicolson: every operator rounded on its own (DESIGN 3.5g).  cr = rDtCoef*rho_value (a host
+// product) or rDtCoef*rho0 of the cell; offd = cn_off(ddt0)
+__device__ __forceinline__ double cn_off(int offc, double oc, double x) { return offc ? oc * x : x; }
+__device__ __forceinline__ double cn_source(double cr, double p0, double offd, double V) { return ((cr * p0) + offd) * V; }
 // CORR: each own face's t_r = faceFlux*(scale*corr_r) is formed once in the face pass and staged in LDS after lB / uB / uL; every cell
 // forms its n_rhs surfaceIntegrate row sums in mi_surface_integrate's order, ivf = sum/V, and subtracts the rounded V*ivf from the source
 // right after the ddt part (the div matrix's own source, fvMatrix.C:1819-1826), before the explicit terms
-template <bool DIV, bool LAP, int BS, bool R16, bool CORR = false, bool BACK = false>
-__global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR, BACK>::type a)
+template <bool DIV, bool LAP, int BS, bool R16, bool CORR = false, int TF = TF_EULER>
+__global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR, TF>::type a)
 {
+    constexpr bool BACK = TF == TF_BACK, CN = TF == TF_CN;
     extern __shared__ __attribute__((aligned(16))) double rp_smem[];
     const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
     int c0, cEnd;
@@ -312,9 +327,9 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR,
     const double V = a.vol ? a.vol[c] : 0.0;
     double d = 0.0;
     if constexpr (BACK) { const double dA = back_diag(a.bw.cA, a.rho ? a.rho[c] : a.rhoValue, V); d = DIV ? dA + sumB : dA; }
-    else if (a.ddt) { const double dA = (a.rdt * (a.rho ? a.rho[c] : a.rhoValue)) * V; d = DIV ? dA + sumB : dA; }
+    else if (CN || a.ddt) { const double dA = (a.rdt * (a.rho ? a.rho[c] : a.rhoValue)) * V; d = DIV ? dA + sumB : dA; }
     else if (DIV) d = sumB;
-    if (LAP) d = (BACK || a.ddt || DIV) ? d - sumL : -sumL;
+    if (LAP) d = (BACK || CN || a.ddt || DIV) ? d - sumL : -sumL;
     if (a.sp) { const double t = V * a.sp[c]; d = a.spMinus ? d - t : d + t; }
     a.diagOut[c] = d;
     if (mag) a.sumMagOut[c] = sumM;
@@ -323,6 +338,7 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR,
         if constexpr (BACK)
             s = a.rhoOld ? back_source_rho(a.rdt, a.bw.c0, a.bw.c00, V, a.rhoOld[c], a.psiOld[r][c], a.bw.rhoOldOld[c], a.bw.psiOldOld[r][c])
                          : back_source(a.rdt, a.rhoValue, a.bw.c0, a.bw.c00, V, a.psiOld[r][c], a.bw.psiOldOld[r][c]);
+        else if constexpr (CN) s = cn_source(a.rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue), a.psiOld[r][c], cn_off(a.cn.offc, a.cn.oc, a.cn.ddt0[r][c]), V);
         else s = a.ddt ? ((a.rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue)) * a.psiOld[r][c]) * V : 0.0;
         if (CORR) s = s - vIvf;
         for (int k = 0; k < a.nSu; ++k) { const double t = V * a.su[k * a.nRhs + r][c]; s = a.suMinus[k] ? s + t : s - t; }
@@ -756,6 +772,89 @@ __global__ __launch_bounds__(RB) void k_fvc_ddt_backward(double rr, double c, do
         },
         [&](int64_t i) {
             out[i] = RHO ? back_fvc_rho(rr, c, c0, c00, rho[i], vf[i], rho0[i], vf0[i], rho00[i], vf00[i]) : back_fvc(rr, c, c0, c00, vf[i], vf0[i], vf00[i]);
+        });
+}
+// ---- CrankNicolson (CrankNicolsonDdtScheme.C, static mesh; DESIGN 3.5g) ----
+// the ddt0 update (:417-418, :507-508, :603-607; the same statements in fvmDdt :818-822, :900-904, :987-994): c0 = rDtCoef0*rho_value (a host
+// product) without a density field
+__device__ __forceinline__ double cn_ddt0(double c0, double p0, double p00, double offd) { return (c0 * (p0 - p00)) - offd; }
+__device__ __forceinline__ double cn_ddt0_rho(double rdt0, double r0, double p0, double r00, double p00, double offd)
+{
+    return (rdt0 * ((r0 * p0) - (r00 * p00))) - offd;
+}
+// up to four fields (the components of a vector) in ONE launch, in place: element i of ddt0[k] is read and written by the same thread only.
+// The field pointers travel in one by-value block and are indexed by compile-time constants (the unrolled k), so they stay in SGPRs.
+struct CnUpdateArgs {
+    double* ddt0[4]; const double *psi0[4], *psi00[4];
+    const double *rho0, *rho00;
+    double c0, oc; int offc, nFields; int64_t n;
+};
+template <bool RHO>
+__global__ __launch_bounds__(RB) void k_ddt_cn_update(const CnUpdateArgs a)
+{
+    auto one = [&](double r0, double p0, double r00, double p00, double d) {
+        const double offd = cn_off(a.offc, a.oc, d);
+        return RHO ? cn_ddt0_rho(a.c0, r0, p0, r00, p00, offd) : cn_ddt0(a.c0, p0, p00, offd);
+    };
+    chunk_loop2(a.n, [&](int64_t i) {
+            double2 q0 = make_double2(0.0, 0.0), q00 = q0;
+            if (RHO) { q0 = ld2(a.rho0, i); q00 = ld2(a.rho00, i); }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (k < a.nFields) {
+                const double2 p0 = ld2(a.psi0[k], i), p00 = ld2(a.psi00[k], i), d = ld2(a.ddt0[k], i);
+                st2(a.ddt0[k], i, make_double2(one(q0.x, p0.x, q00.x, p00.x, d.x), one(q0.y, p0.y, q00.y, p00.y, d.y)));
+            }
+        },
+        [&](int64_t i) {
+            const double r0 = RHO ? a.rho0[i] : 0.0, r00 = RHO ? a.rho00[i] : 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (k < a.nFields) a.ddt0[k][i] = one(r0, a.psi0[k][i], r00, a.psi00[k][i], a.ddt0[k][i]);
+        });
+}
+// fvm::ddt (:755-832, :837-913, :919-1003): diag = (rDtCoef*rho)*V (Euler's with rDtCoef); source = cn_source.  cr = rDtCoef*rho_value
+// (a host product) without a density field, else rdt = rDtCoef
+template <bool RHO>
+__global__ __launch_bounds__(RB) void k_fvm_ddt_cn(double rdt, double cr, double oc, int offc, const double* __restrict__ rho, const double* __restrict__ rho0,
+                                                   const double* __restrict__ vol, const double* __restrict__ psi0, const double* __restrict__ ddt0,
+                                                   double* __restrict__ diag, double* __restrict__ source, int64_t n)
+{
+    chunk_loop2(n, [&](int64_t i) {
+            const double2 v = ld2(vol, i), p0 = ld2(psi0, i), d = ld2(ddt0, i);
+            const double ox = cn_off(offc, oc, d.x), oy = cn_off(offc, oc, d.y);
+            if (RHO) {
+                const double2 q = ld2(rho, i), q0 = ld2(rho0, i);
+                st2(diag, i, make_double2((rdt * q.x) * v.x, (rdt * q.y) * v.y));
+                st2(source, i, make_double2(cn_source(rdt * q0.x, p0.x, ox, v.x), cn_source(rdt * q0.y, p0.y, oy, v.y)));
+            } else {
+                st2(diag, i, make_double2(cr * v.x, cr * v.y));
+                st2(source, i, make_double2(cn_source(cr, p0.x, ox, v.x), cn_source(cr, p0.y, oy, v.y)));
+            }
+        },
+        [&](int64_t i) {
+            const double o = cn_off(offc, oc, ddt0[i]);
+            if (RHO) { diag[i] = (rdt * rho[i]) * vol[i]; source[i] = cn_source(rdt * rho0[i], psi0[i], o, vol[i]); }
+            else { diag[i] = cr * vol[i]; source[i] = cn_source(cr, psi0[i], o, vol[i]); }
+        });
+}
+// fvc::ddt (:426, :516, :615-616)
+__device__ __forceinline__ double cn_fvc(double cr, double f, double f0, double offd) { return (cr * (f - f0)) - offd; }
+__device__ __forceinline__ double cn_fvc_rho(double rdt, double r, double f, double r0, double f0, double offd) { return (rdt * ((r * f) - (r0 * f0))) - offd; }
+template <bool RHO>
+__global__ __launch_bounds__(RB) void k_fvc_ddt_cn(double cr, double oc, int offc, const double* __restrict__ rho, const double* __restrict__ rho0,
+                                                   const double* __restrict__ vf, const double* __restrict__ vf0, const double* __restrict__ ddt0,
+                                                   double* __restrict__ out, int64_t n)
+{
+    chunk_loop2(n, [&](int64_t i) {
+            const double2 f = ld2(vf, i), f0 = ld2(vf0, i), d = ld2(ddt0, i);
+            const double ox = cn_off(offc, oc, d.x), oy = cn_off(offc, oc, d.y);
+            if (RHO) {
+                const double2 q = ld2(rho, i), q0 = ld2(rho0, i);
+                st2(out, i, make_double2(cn_fvc_rho(cr, q.x, f.x, q0.x, f0.x, ox), cn_fvc_rho(cr, q.y, f.y, q0.y, f0.y, oy)));
+            } else st2(out, i, make_double2(cn_fvc(cr, f.x, f0.x, ox), cn_fvc(cr, f.y, f0.y, oy)));
+        },
+        [&](int64_t i) {
+            const double o = cn_off(offc, oc, ddt0[i]);
+            out[i] = RHO ? cn_fvc_rho(cr, rho[i], vf[i], rho0[i], vf0[i], o) : cn_fvc(cr, vf[i], vf0[i], o);
         });
 }
 // fvc::ddtCorr, backward, internal faces (backwardDdtScheme.C:724-765, :868-950 first branch; fvcDdtPhiCoeff: ddtScheme.C:139-174) in ONE face
@@ -1481,14 +1580,14 @@ extern "C" int mi_fvm_assemble(mi_addr_t a, const mi_fvm_terms* t, double* lower
     return mi_fvm_assemble_corrected(a, t, nullptr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
 }
 namespace {
-int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
+int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_ddt_cn_terms* cn, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
                   double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev);
 }
 // ... with the explicit correction of linearUpwind / LUST in the div term (CORR)
 extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
                                          double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
 {
-    return assemble_impl(a, t, nullptr, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+    return assemble_impl(a, t, nullptr, nullptr, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
 }
 // ... with the backward time derivative in place of Euler's (BACK), with or without the correction
 extern "C" int mi_fvm_assemble_backward(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev,
@@ -1498,10 +1597,20 @@ extern "C" int mi_fvm_assemble_backward(mi_addr_t a, const mi_fvm_terms* t, cons
     if (!t->ddt) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: terms->ddt is 0 (no time derivative: mi_fvm_assemble)");
     if ((bw->rho_old_old_dev != nullptr) != (t->rho_dev != nullptr)) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: rho, rho_old and rho_old_old go together");
     if (t->n_rhs > 0 && !bw->psi_old_old_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: old-old fields missing");
-    return assemble_impl(a, t, bw, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+    return assemble_impl(a, t, bw, nullptr, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+}
+// ... with the CrankNicolson time derivative (CN), with or without the correction: terms->r_delta_t carries rDtCoef
+extern "C" int mi_fvm_assemble_cn(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_cn_terms* cn, const mi_div_correction* corr, double* lower_out_dev,
+                                  double* upper_out_dev, double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
+{
+    if (!a || !t || !cn) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: bad argument");
+    if (!t->ddt) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: terms->ddt is 0 (no time derivative: mi_fvm_assemble)");
+    if (!(cn->oc >= 0.0 && cn->oc <= 1.0)) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: the off-centring coefficient should be >= 0 and <= 1");
+    if (t->n_rhs > 0 && !cn->ddt0_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: ddt0 fields missing");
+    return assemble_impl(a, t, nullptr, cn, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
 }
 namespace {
-int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
+int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_ddt_cn_terms* cn, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
                   double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
 {
     if (!a || !t || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: bad argument");
@@ -1533,6 +1642,7 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw,
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     AsmCorrBackArgs ra{};
+    CnIn ci{};
     if (CORR) {
         const double* outs[8] = {lower_out_dev, upper_out_dev, diag_out_dev, sum_mag_off_diag_out_dev};
         for (int r = 0; r < t->n_rhs; ++r) outs[4 + r] = source_out_dev[r];
@@ -1557,6 +1667,16 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw,
             if (!ra.bw.psiOldOld[r]) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: null old-old field");
         }
     }
+    const bool CN = cn != nullptr;
+    if (CN) {
+        ci.oc = cn->oc; ci.offc = cn->oc < 1.0 ? 1 : 0;
+        for (int r = 0; r < t->n_rhs; ++r) {
+            const double* d = ci.ddt0[r] = cn->ddt0_dev[r];
+            if (!d) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: null ddt0 field");
+            if (d == lower_out_dev || d == upper_out_dev || d == diag_out_dev || d == sum_mag_off_diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: a ddt0 field must not be an output");
+            for (int q = 0; q < t->n_rhs; ++q) if (d == source_out_dev[q]) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: a ddt0 field must not be an output");
+        }
+    }
     for (int k = 0; k < t->n_su; ++k) {
         ra.suMinus[k] = t->su_sign[k] < 0 ? 1 : 0;
         for (int r = 0; r < t->n_rhs; ++r) { ra.su[k * t->n_rhs + r] = t->su_dev[k * t->n_rhs + r]; if (!ra.su[k * t->n_rhs + r]) return fail(MI_ERR_ARG, "mi_fvm_assemble: null explicit term"); }
@@ -1572,6 +1692,8 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw,
     const AsmCorrArgs& rc = ra;                    // every kernel takes the arguments of its own variant only
     const AsmArgs& rb = ra;
     AsmBackArgs rk{}; static_cast<AsmArgs&>(rk) = rb; rk.bw = ra.bw;
+    AsmCnArgs rn{}; static_cast<AsmArgs&>(rn) = rb; rn.cn = ci;
+    AsmCorrCnArgs rcn{}; static_cast<AsmCorrArgs&>(rcn) = rc; rcn.cn = ci;
 #define MI_ASM_LAUNCH(D, L, K, B, ARGS)                                                                                          \
     do {                                                                                                                           \
         if (r16) { if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, true, K, B>, ARGS, lds);                  \
@@ -1582,17 +1704,24 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw,
         return row_launch(a, rp, k_row_assemble<D, L, 1024, false, K, B>, ARGS, lds);                                             \
     } while (0)
     if (BACK) {
-        if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, true, ra);
-        if (CORR) MI_ASM_LAUNCH(true, false, true, true, ra);
-        if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, true, rk);
-        if (DIV) MI_ASM_LAUNCH(true, false, false, true, rk);
-        MI_ASM_LAUNCH(false, true, false, true, rk);
+        if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, TF_BACK, ra);
+        if (CORR) MI_ASM_LAUNCH(true, false, true, TF_BACK, ra);
+        if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, TF_BACK, rk);
+        if (DIV) MI_ASM_LAUNCH(true, false, false, TF_BACK, rk);
+        MI_ASM_LAUNCH(false, true, false, TF_BACK, rk);
     }
-    if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, false, rc);
-    if (CORR) MI_ASM_LAUNCH(true, false, true, false, rc);
-    if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, false, rb);
-    if (DIV) MI_ASM_LAUNCH(true, false, false, false, rb);
-    MI_ASM_LAUNCH(false, true, false, false, rb);
+    if (CN) {
+        if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, TF_CN, rcn);
+        if (CORR) MI_ASM_LAUNCH(true, false, true, TF_CN, rcn);
+        if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, TF_CN, rn);
+        if (DIV) MI_ASM_LAUNCH(true, false, false, TF_CN, rn);
+        MI_ASM_LAUNCH(false, true, false, TF_CN, rn);
+    }
+    if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, TF_EULER, rc);
+    if (CORR) MI_ASM_LAUNCH(true, false, true, TF_EULER, rc);
+    if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, TF_EULER, rb);
+    if (DIV) MI_ASM_LAUNCH(true, false, false, TF_EULER, rb);
+    MI_ASM_LAUNCH(false, true, false, TF_EULER, rb);
 #undef MI_ASM_LAUNCH
 }
 } // namespace
@@ -2143,6 +2272,115 @@ extern "C" int mi_ddt_phi_corr_backward(mi_addr_t a, double r_delta_t, const dou
     k.rho0 = rho_old_dev_or_null; k.rho00 = rho_old_old_dev_or_null; k.phi0 = phi_old_dev; k.phi00 = phi_old_old_dev; k.out = out_dev;
     k.rdt = r_delta_t; k.c0 = coeffs[1]; k.c00 = coeffs[2]; k.nf = a->L.nFaces; k.xcd = a->ctx->xcdRows;
     k_ddt_phi_corr_backward<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(k);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+// ---- the CrankNicolson time scheme (CrankNicolsonDdtScheme.C, static mesh; DESIGN 3.5g) ----------------------------------------------
+extern "C" int mi_ddt_cn_parse(const char* scheme, double* oc_out)
+{
+    const char* who = "mi_ddt_cn_parse";
+    if (!scheme || !oc_out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
+    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
+    for (const char* c = scheme; *c;) {
+        while (*c && sp(*c)) ++c;
+        const char* b = c;
+        while (*c && !sp(*c)) ++c;
+        if (c > b) tok.emplace_back(b, c);
+    }
+    if (tok.empty()) return fail(MI_ERR_ARG, std::string(who) + ": empty scheme");
+    if (tok[0] != "CrankNicolson") return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[0] + "' is not CrankNicolson");
+    if (tok.size() < 2) return fail(MI_ERR_ARG, std::string(who) + ": 'CrankNicolson' takes the off-centring coefficient, none given");
+    if (tok.size() > 2) return fail(MI_ERR_ARG, std::string(who) + ": 'CrankNicolson' takes one coefficient: extra '" + tok[2] + "'");
+    char* end = nullptr;
+    const double oc = std::strtod(tok[1].c_str(), &end);
+    if (end == tok[1].c_str() || *end != '\0' || oc != oc) return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[1] + "' is not a number");
+    if (!(oc >= 0.0 && oc <= 1.0))                                // CrankNicolsonDdtScheme.H:165-180
+        return fail(MI_ERR_ARG, std::string(who) + ": coefficient = " + tok[1] + " should be >= 0 and <= 1");
+    *oc_out = oc;
+    return MI_OK;
+}
+extern "C" int mi_ddt_cn_begin(double oc, int32_t time_index, mi_ddt_cn_state* state_out)
+{
+    if (!state_out) return fail(MI_ERR_ARG, "mi_ddt_cn_begin: bad argument");
+    if (!(oc >= 0.0 && oc <= 1.0)) return fail(MI_ERR_ARG, "mi_ddt_cn_begin: the off-centring coefficient should be >= 0 and <= 1");
+    state_out->oc = oc; state_out->start_time_index = time_index; state_out->ddt0_time_index = time_index;   // DDt0Field's constructor: both the current index
+    return MI_OK;
+}
+extern "C" int mi_ddt_cn_step(mi_ddt_cn_state* state, int32_t time_index, double delta_t, double delta_t0, mi_ddt_cn_scalars* out)
+{
+    if (!state || !out) return fail(MI_ERR_ARG, "mi_ddt_cn_step: bad argument");
+    if (!(delta_t > 0)) return fail(MI_ERR_ARG, "mi_ddt_cn_step: deltaT must be positive");
+    const int evaluate = state->ddt0_time_index != time_index;                         // :186-194
+    if (evaluate && !(delta_t0 > 0)) return fail(MI_ERR_ARG, "mi_ddt_cn_step: deltaT0 must be positive");
+    const double coef = time_index - state->start_time_index > 0 ? 1.0 + state->oc : 1.0;    // coef_ :196-211
+    const double coef0 = time_index - state->start_time_index > 1 ? 1.0 + state->oc : 1.0;   // coef0_ :214-229
+    out->r_dt_coef = coef / delta_t;                                                   // rDtCoef_ :232-238: one division
+    out->r_dt_coef0 = delta_t0 > 0 ? coef0 / delta_t0 : 0.0;                           // rDtCoef0_ :241-247 (the reference reads it only when evaluate)
+    out->evaluate = evaluate;
+    if (evaluate) state->ddt0_time_index = time_index;
+    return MI_OK;
+}
+extern "C" int mi_ddt_cn_update(mi_ctx_t c, int64_t n, int32_t n_fields, double r_dt_coef0, double oc, double rho_value, const double* rho_old_dev,
+                                const double* rho_old_old_dev, const double* const* psi_old_dev, const double* const* psi_old_old_dev,
+                                double* const* ddt0_inout_dev)
+{
+    const char* who = "mi_ddt_cn_update";
+    if (!c || n < 0 || n_fields < 1 || n_fields > 4 || !psi_old_dev || !psi_old_old_dev || !ddt0_inout_dev)
+        return fail(MI_ERR_ARG, std::string(who) + ": bad argument (1 to 4 fields)");
+    if (!(oc >= 0.0 && oc <= 1.0)) return fail(MI_ERR_ARG, std::string(who) + ": the off-centring coefficient should be >= 0 and <= 1");
+    const bool RHO = rho_old_dev || rho_old_old_dev;
+    if (RHO && !(rho_old_dev && rho_old_old_dev)) return fail(MI_ERR_ARG, std::string(who) + ": rho_old and rho_old_old go together");
+    const double* in[10]; double* out[4]; int nIn = 0;
+    for (int k = 0; k < n_fields; ++k) { in[nIn++] = psi_old_dev[k]; in[nIn++] = psi_old_old_dev[k]; out[k] = ddt0_inout_dev[k]; }
+    if (RHO) { in[nIn++] = rho_old_dev; in[nIn++] = rho_old_old_dev; }
+    MICHK(stream_arrays(who, in, nIn, out, n_fields));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    CnUpdateArgs a{};
+    for (int k = 0; k < n_fields; ++k) { a.ddt0[k] = ddt0_inout_dev[k]; a.psi0[k] = psi_old_dev[k]; a.psi00[k] = psi_old_old_dev[k]; }
+    a.rho0 = rho_old_dev; a.rho00 = rho_old_old_dev;
+    a.c0 = RHO ? r_dt_coef0 : r_dt_coef0 * rho_value; a.oc = oc; a.offc = oc < 1.0 ? 1 : 0; a.nFields = n_fields; a.n = n;
+    if (RHO) k_ddt_cn_update<true><<<RG, RB, 0, c->stream>>>(a);
+    else k_ddt_cn_update<false><<<RG, RB, 0, c->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+extern "C" int mi_fvm_ddt_cn(mi_ctx_t c, int64_t n, double r_dt_coef, double oc, double rho_value, const double* rho_dev, const double* rho_old_dev,
+                             const double* vol_dev, const double* psi_old_dev, const double* ddt0_dev, double* diag_out_dev, double* source_out_dev)
+{
+    const char* who = "mi_fvm_ddt_cn";
+    if (!c || n < 0) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!(oc >= 0.0 && oc <= 1.0)) return fail(MI_ERR_ARG, std::string(who) + ": the off-centring coefficient should be >= 0 and <= 1");
+    const bool RHO = rho_dev || rho_old_dev;
+    if (RHO && !(rho_dev && rho_old_dev)) return fail(MI_ERR_ARG, std::string(who) + ": rho and rho_old go together");
+    const double* in[5] = {vol_dev, psi_old_dev, ddt0_dev, rho_dev, rho_old_dev};
+    double* out[2] = {diag_out_dev, source_out_dev};
+    MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 2));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const int offc = oc < 1.0 ? 1 : 0;
+    if (RHO) k_fvm_ddt_cn<true><<<RG, RB, 0, c->stream>>>(r_dt_coef, 0.0, oc, offc, rho_dev, rho_old_dev, vol_dev, psi_old_dev, ddt0_dev, diag_out_dev, source_out_dev, n);
+    else k_fvm_ddt_cn<false><<<RG, RB, 0, c->stream>>>(r_dt_coef, r_dt_coef * rho_value, oc, offc, nullptr, nullptr, vol_dev, psi_old_dev, ddt0_dev, diag_out_dev, source_out_dev, n);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+extern "C" int mi_fvc_ddt_cn(mi_ctx_t c, int64_t n, double r_dt_coef, double oc, double rho_value, const double* rho_dev, const double* rho_old_dev,
+                             const double* vf_dev, const double* vf_old_dev, const double* ddt0_dev, double* out_dev)
+{
+    const char* who = "mi_fvc_ddt_cn";
+    if (!c || n < 0) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!(oc >= 0.0 && oc <= 1.0)) return fail(MI_ERR_ARG, std::string(who) + ": the off-centring coefficient should be >= 0 and <= 1");
+    const bool RHO = rho_dev || rho_old_dev;
+    if (RHO && !(rho_dev && rho_old_dev)) return fail(MI_ERR_ARG, std::string(who) + ": rho and rho_old go together");
+    const double* in[5] = {vf_dev, vf_old_dev, ddt0_dev, rho_dev, rho_old_dev};
+    double* out[1] = {out_dev};
+    MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 1));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const int offc = oc < 1.0 ? 1 : 0;
+    if (RHO) k_fvc_ddt_cn<true><<<RG, RB, 0, c->stream>>>(r_dt_coef, oc, offc, rho_dev, rho_old_dev, vf_dev, vf_old_dev, ddt0_dev, out_dev, n);
+    else k_fvc_ddt_cn<false><<<RG, RB, 0, c->stream>>>(r_dt_coef * rho_value, oc, offc, nullptr, nullptr, vf_dev, vf_old_dev, ddt0_dev, out_dev, n);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }

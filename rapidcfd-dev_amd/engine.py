@@ -73,6 +73,7 @@ SYMBOLS = [
     "mi_limiter_parse", "mi_limited_weights", "mi_patch_limited_weights",
     "mi_grad_limiter_parse", "mi_grad_boundary_create", "mi_grad_boundary_destroy", "mi_limited_grad",
     "mi_ddt_backward_coeffs", "mi_fvm_ddt_backward", "mi_fvc_ddt_backward", "mi_ddt_phi_corr_backward", "mi_fvm_assemble_backward",
+    "mi_ddt_cn_parse", "mi_ddt_cn_begin", "mi_ddt_cn_step", "mi_ddt_cn_update", "mi_fvm_ddt_cn", "mi_fvc_ddt_cn", "mi_fvm_assemble_cn",
     "mi_sngrad_parse", "mi_sngrad_limited_correction_flux", "mi_patch_sngrad_limited_correction_flux",
     "mi_fvc_div_dev_tgrad", "mi_patch_gauss_grad_correct", "mi_patch_dev_tgrad_flux",
 ]
@@ -977,6 +978,47 @@ def ddt_backward_coeffs(delta_t, delta_t0=None):
     return (out[0], out[1], out[2])
 
 
+class DdtCnState(C.Structure):
+    """mi_ddt_cn_state (include/mi_ldu.h)"""
+    _fields_ = [("oc", C.c_double), ("start_time_index", C.c_int32), ("ddt0_time_index", C.c_int32)]
+
+
+class DdtCnScalars(C.Structure):
+    """mi_ddt_cn_scalars (include/mi_ldu.h)"""
+    _fields_ = [("r_dt_coef", C.c_double), ("r_dt_coef0", C.c_double), ("evaluate", C.c_int32)]
+
+
+class DdtCnTerms(C.Structure):
+    """mi_ddt_cn_terms (include/mi_ldu.h)"""
+    _fields_ = [("oc", C.c_double), ("ddt0_dev", C.POINTER(C.c_void_p))]
+
+
+def ddt_cn_parse(scheme):
+    """the off-centring coefficient of `CrankNicolson <oc>` (mi_ddt_cn_parse; host only, no GPU); anything else raises MiError"""
+    oc = C.c_double()
+    _chk(lib().mi_ddt_cn_parse(str(scheme).encode(), C.byref(oc)))
+    return oc.value
+
+
+class CrankNicolson:
+    """The state of one ddt0 field (mi_ddt_cn_state; host only, no GPU): created at `time_index` -- the caller zeroes the ddt0 arrays then.
+    step(time_index, delta_t, delta_t0) -> (r_dt_coef, r_dt_coef0, evaluate); evaluate True (once per time step): run Assembly.ddt_cn_update
+    with r_dt_coef0 before any other use of ddt0 in this step."""
+
+    def __init__(self, oc, time_index):
+        self.state = DdtCnState()
+        _chk(lib().mi_ddt_cn_begin(C.c_double(oc), C.c_int32(time_index), C.byref(self.state)))
+
+    @property
+    def oc(self):
+        return self.state.oc
+
+    def step(self, time_index, delta_t, delta_t0):
+        out = DdtCnScalars()
+        _chk(lib().mi_ddt_cn_step(C.byref(self.state), C.c_int32(time_index), C.c_double(delta_t), C.c_double(delta_t0), C.byref(out)))
+        return (out.r_dt_coef, out.r_dt_coef0, bool(out.evaluate))
+
+
 class DivCorrection(C.Structure):
     """mi_div_correction (include/mi_ldu.h)"""
     _fields_ = [("scale", C.c_double), ("cf_dev", C.c_void_p * 3), ("c_dev", C.c_void_p * 3), ("grad_dev", C.c_void_p * 12)]
@@ -1145,6 +1187,26 @@ class Assembly:
                                             _ptr(u_old[0]), _ptr(u_old[1]), _ptr(u_old[2]), _ptr(u_old_old[0]), _ptr(u_old_old[1]), _ptr(u_old_old[2]),
                                             _ptr(rho_old), _ptr(rho_old_old), _ptr(phi_old), _ptr(phi_old_old), _ptr(out)))
 
+    def ddt_cn_update(self, r_dt_coef0, oc, psi_old, psi_old_old, ddt0_inout, rho_value=1.0, rho_old=None, rho_old_old=None):
+        """the ddt0 update of CrankNicolson (CrankNicolsonDdtScheme.C:417-418, 507-508, 603-607), IN PLACE, of 1..4 fields (lists of tensors) in one
+        launch; rho_old / rho_old_old: a density field (both) or none (the constant rho_value)"""
+        k = len(ddt0_inout)
+        assert len(psi_old) == k and len(psi_old_old) == k, "one old and one old-old field per ddt0 field"
+        arr = lambda xs: (C.c_void_p * max(k, 1))(*[_ptr(x) for x in xs])
+        n = next((x.numel() for x in (*ddt0_inout, *psi_old, *psi_old_old) if x is not None), 0)
+        _chk(lib().mi_ddt_cn_update(self.addr.ctx.h, C.c_int64(n), C.c_int32(k), C.c_double(r_dt_coef0), C.c_double(oc),
+                                    C.c_double(rho_value), _ptr(rho_old), _ptr(rho_old_old), arr(psi_old), arr(psi_old_old), arr(ddt0_inout)))
+
+    def fvm_ddt_cn(self, r_dt_coef, oc, vol, psi_old, ddt0, diag_out, source_out, rho_value=1.0, rho=None, rho_old=None):
+        """fvm::ddt([rho,] vf), CrankNicolson (CrankNicolsonDdtScheme.C:755-1003): ddt0 already updated for this time step"""
+        _chk(lib().mi_fvm_ddt_cn(self.addr.ctx.h, C.c_int64(vol.numel()), C.c_double(r_dt_coef), C.c_double(oc), C.c_double(rho_value), _ptr(rho), _ptr(rho_old),
+                                 _ptr(vol), _ptr(psi_old), _ptr(ddt0), _ptr(diag_out), _ptr(source_out)))
+
+    def fvc_ddt_cn(self, r_dt_coef, oc, vf, vf_old, ddt0, out, rho_value=1.0, rho=None, rho_old=None):
+        """fvc::ddt([rho,] vf), CrankNicolson (CrankNicolsonDdtScheme.C:426, 516, 615-616)"""
+        _chk(lib().mi_fvc_ddt_cn(self.addr.ctx.h, C.c_int64(vf.numel()), C.c_double(r_dt_coef), C.c_double(oc), C.c_double(rho_value), _ptr(rho), _ptr(rho_old),
+                                 _ptr(vf), _ptr(vf_old), _ptr(ddt0), _ptr(out)))
+
     def upwind_weights(self, face_flux, w_out):
         _chk(lib().mi_upwind_weights(self.addr.ctx.h, C.c_int64(face_flux.numel()), _ptr(face_flux), _ptr(w_out)))
 
@@ -1221,7 +1283,9 @@ class Assembly:
         div["correction"] = dict(scale=1.0 | 0.25, cf=[x, y, z], c=[x, y, z], grad=[[gx, gy, gz] per rhs]): the explicit correction of linearUpwind / LUST
         in the same pass (mi_fvm_assemble_corrected).
         ddt["backward"] = dict(coeffs=ddt_backward_coeffs(...), psi_old_old=[...], rho_old_old=None | tensor): the backward time derivative in place of
-        Euler's (mi_fvm_assemble_backward), with or without the correction."""
+        Euler's (mi_fvm_assemble_backward), with or without the correction.
+        ddt["crank_nicolson"] = dict(oc=, ddt0=[...]): the CrankNicolson time derivative (mi_fvm_assemble_cn); r_delta_t carries rDtCoef and the ddt0
+        fields are already updated for this time step.  Not together with "backward"."""
         t = FvmTerms()
         n_rhs = len(sources_out)
         keep = []
@@ -1246,7 +1310,18 @@ class Assembly:
         so = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in sources_out])
         corr = (div or {}).get("correction")
         back = (ddt or {}).get("backward")
-        if back is not None:
+        cn = (ddt or {}).get("crank_nicolson")
+        if back is not None and cn is not None:
+            raise MiError("Assembly.assemble: ddt takes 'backward' or 'crank_nicolson', not both")
+        if cn is not None:
+            b = DdtCnTerms()
+            b.oc = float(cn["oc"])
+            d0 = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in cn["ddt0"]]); keep.append(d0)
+            b.ddt0_dev = C.cast(d0, C.POINTER(C.c_void_p))
+            k = None if corr is None else div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))
+            _chk(lib().mi_fvm_assemble_cn(self.addr.h, C.byref(t), C.byref(b), None if k is None else C.byref(k), _ptr(lower_out), _ptr(upper_out),
+                                          _ptr(diag_out), so, _ptr(sum_mag_out)))
+        elif back is not None:
             b = DdtBackward()
             b.coefft, b.coefft0, b.coefft00 = [float(x) for x in back["coeffs"]]
             b.rho_old_old_dev = _ptr(back.get("rho_old_old")).value

@@ -874,6 +874,102 @@ void fvc::ddt(scalargpuField& out, const backwardDdtCoeffs& bd, const scalargpuF
     miCheck(mi_fvc_ddt_backward(miEngine::New().ctx, vf.size(), bd.rDeltaT, c, 1.0, nullptr, nullptr, nullptr, vf.data(), vfOld.data(), vfOldOld.data(), out.data()),
             "fvc::ddt (backward)");
 }
+// ---- the CrankNicolson time scheme ----
+fv::CrankNicolsonDdtScheme::CrankNicolsonDdtScheme(scalar ocCoeff) : ocCoeff_(ocCoeff), timeIndex_(0), deltaT_(0), deltaT0_(0)
+{
+    if (!(ocCoeff_ >= 0 && ocCoeff_ <= 1)) FatalErrorIn("CrankNicolsonDdtScheme", "coefficient = " + std::to_string(ocCoeff_) + " should be >= 0 and <= 1");
+}
+fv::CrankNicolsonDdtScheme fv::CrankNicolsonDdtScheme::New(const std::string& scheme)
+{
+    double oc = 0;
+    miCheck(mi_ddt_cn_parse(scheme.c_str(), &oc), "ddtSchemes");
+    return CrankNicolsonDdtScheme(oc);
+}
+fv::CrankNicolsonDdtScheme::DDt0Field& fv::CrankNicolsonDdtScheme::lookup(const word& name, label nCells, int nCmpt)
+{
+    if (nCmpt < 1 || nCmpt > 4) FatalErrorIn("CrankNicolsonDdtScheme", name + ": 1 to 4 components, " + std::to_string(nCmpt) + " given");
+    auto it = ddt0_.find(name);
+    if (it == ddt0_.end()) {                          // created zero, with the current time index as its own and as its start
+        DDt0Field f;
+        miCheck(mi_ddt_cn_begin(ocCoeff_, timeIndex_, &f.state), "CrankNicolsonDdtScheme");
+        for (int k = 0; k < nCmpt; ++k) f.cmpt.emplace_back(nCells);
+        it = ddt0_.emplace(name, std::move(f)).first;
+    }
+    if ((int)it->second.cmpt.size() != nCmpt || it->second.cmpt[0].size() != nCells)
+        FatalErrorIn("CrankNicolsonDdtScheme", name + ": used with another size or number of components than it was created with");
+    return it->second;
+}
+const scalargpuField& fv::CrankNicolsonDdtScheme::ddt0(const word& name, direction cmpt) const
+{
+    auto it = ddt0_.find(name);
+    if (it == ddt0_.end() || cmpt >= it->second.cmpt.size()) FatalErrorIn("CrankNicolsonDdtScheme", "no field " + name);
+    return it->second.cmpt[cmpt];
+}
+scalar fv::CrankNicolsonDdtScheme::evaluate(const word& name, scalar rho, const scalargpuField* const* psiOld, const scalargpuField* const* psiOldOld, int nCmpt)
+{
+    if (nCmpt < 1 || nCmpt > 4 || !psiOld || !psiOldOld) FatalErrorIn("CrankNicolsonDdtScheme", name + ": 1 to 4 components with their old and old-old fields");
+    for (int k = 0; k < nCmpt; ++k) if (!psiOld[k] || !psiOldOld[k]) FatalErrorIn("CrankNicolsonDdtScheme", name + ": a missing old or old-old field");
+    DDt0Field& f = lookup(name, psiOld[0]->size(), nCmpt);
+    mi_ddt_cn_scalars sc{};
+    miCheck(mi_ddt_cn_step(&f.state, timeIndex_, deltaT_, deltaT0_, &sc), "CrankNicolsonDdtScheme");
+    if (sc.evaluate) {
+        const double *po[4], *poo[4]; double* d[4];
+        for (int k = 0; k < nCmpt; ++k) { po[k] = psiOld[k]->data(); poo[k] = psiOldOld[k]->data(); d[k] = f.cmpt[k].data(); }
+        miCheck(mi_ddt_cn_update(miEngine::New().ctx, psiOld[0]->size(), nCmpt, sc.r_dt_coef0, ocCoeff_, rho, nullptr, nullptr, po, poo, d), name.c_str());
+    }
+    return sc.r_dt_coef;
+}
+scalar fv::CrankNicolsonDdtScheme::rDtCoef(const word& name, label nCells, int nCmpt)
+{
+    mi_ddt_cn_state probe = lookup(name, nCells, nCmpt).state;   // stepped on a COPY: the field's own time index stays, ddt0 is not due an update
+    mi_ddt_cn_scalars sc{};
+    miCheck(mi_ddt_cn_step(&probe, timeIndex_, deltaT_, deltaT0_ > 0 ? deltaT0_ : deltaT_, &sc), "CrankNicolsonDdtScheme");   // only r_dt_coef is used
+    return sc.r_dt_coef;
+}
+void fv::CrankNicolsonDdtScheme::assemble(lduMatrix& M, scalargpuField* const* sources, const word& name, scalar rho, const scalargpuField& V,
+                                          const scalargpuField* const* psiOld, const scalargpuField* const* psiOldOld, int nRhs, const scalargpuField* faceFlux,
+                                          const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf,
+                                          const linearUpwindCorrection* corr, const scalargpuField* su)
+{
+    if (nRhs < 1 || nRhs > 3 || !sources) FatalErrorIn("fvm::assemble (CrankNicolson)", name + ": 1 to 3 right-hand sides, " + std::to_string(nRhs) + " given");
+    for (int r = 0; r < nRhs; ++r) if (!sources[r]) FatalErrorIn("fvm::assemble (CrankNicolson)", name + ": a missing source field");
+    mi_fvm_terms t{};
+    t.ddt = 1; t.r_delta_t = evaluate(name, rho, psiOld, psiOldOld, nRhs); t.rho_value = rho; t.vol_dev = V.data();
+    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
+    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
+    const double *po[3], *d0[3]; double* so[3];
+    for (int r = 0; r < nRhs; ++r) { po[r] = psiOld[r]->data(); d0[r] = ddt0(name, r).data(); so[r] = sources[r]->data(); }
+    t.n_rhs = nRhs; t.psi_old_dev = po;
+    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
+    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
+    mi_ddt_cn_terms c{};
+    c.oc = ocCoeff_; c.ddt0_dev = d0;
+    mi_div_correction k{};
+    if (corr) k = divCorrection(*corr, (std::size_t)nRhs);
+    miCheck(mi_fvm_assemble_cn(M.lduAddr().handle(), &t, &c, corr ? &k : nullptr, faceFlux ? M.lower().data() : nullptr, M.upper().data(), M.diag().data(), so,
+                               nullptr), "fvm::assemble (CrankNicolson)");
+}
+void fvm::ddt(fvScalarMatrix& M, fv::CrankNicolsonDdtScheme& cn, const word& name, scalar rho, const scalargpuField& V, const scalargpuField& psiOld,
+              const scalargpuField& psiOldOld)
+{
+    const scalargpuField *po[1] = {&psiOld}, *poo[1] = {&psiOldOld};
+    const scalar rDtCoef = cn.evaluate(name, rho, po, poo, 1);
+    miCheck(mi_fvm_ddt_cn(miEngine::New().ctx, V.size(), rDtCoef, cn.ocCoeff(), rho, nullptr, nullptr, V.data(), psiOld.data(), cn.ddt0(name).data(),
+                          M.diag().data(), M.source().data()), "fvm::ddt (CrankNicolson)");
+}
+void fvc::ddtCorr(scalargpuField& out, const lduAddressing& a, fv::CrankNicolsonDdtScheme& cn, const word& name, const scalargpuField& weights,
+                  const vectorgpuField& Sf, const vectorgpuField& Uold, const scalargpuField& phiOld)
+{
+    fvc::ddtCorr(out, a, cn.rDtCoef(name, Uold.component(0).size(), 3), weights, Sf, Uold, phiOld);
+}
+void fvc::ddt(scalargpuField& out, fv::CrankNicolsonDdtScheme& cn, const word& name, const scalargpuField& vf, const scalargpuField& vfOld,
+              const scalargpuField& vfOldOld)
+{
+    const scalargpuField *po[1] = {&vfOld}, *poo[1] = {&vfOldOld};
+    const scalar rDtCoef = cn.evaluate(name, 1.0, po, poo, 1);
+    miCheck(mi_fvc_ddt_cn(miEngine::New().ctx, vf.size(), rDtCoef, cn.ocCoeff(), 1.0, nullptr, nullptr, vf.data(), vfOld.data(), cn.ddt0(name).data(), out.data()),
+            "fvc::ddt (CrankNicolson)");
+}
 void fvc::linearUpwindCorrectionFlux(scalargpuField& out, const lduAddressing& a, const scalargpuField& faceFlux, const linearUpwindCorrection& corr)
 {
     const mi_div_correction k = divCorrection(corr, 1);

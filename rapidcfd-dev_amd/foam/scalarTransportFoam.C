@@ -4,7 +4,7 @@
 //         solve(fvm::ddt(T) + fvm::div(phi, T) - fvm::laplacian(DT, T) == fvOptions(T));        // (no fvOptions here)
 //
 // in a given velocity field, on a case directory: constant/polyMesh, constant/transportProperties (DT), system/controlDict (deltaT, endTime,
-// writeFormat, writePrecision), system/fvSchemes (ddt(T): Euler | backward; div(phi,T): Gauss linear | upwind | limitedLinear k; laplacian: Gauss linear corrected |
+// writeFormat, writePrecision), system/fvSchemes (ddt(T): Euler | backward | CrankNicolson <oc>; div(phi,T): Gauss linear | upwind | limitedLinear k; laplacian: Gauss linear corrected |
 // uncorrected | orthogonal | limited [corrected] k), system/fvSolution (solvers.T, SIMPLE.nNonOrthogonalCorrectors), 0/T and 0/U with fixedValue (inflow) and
 // zeroGradient (outflow, walls) patches [U: also noSlip].  The whole equation is ONE assembly pass (fvm::assemble -> mi_fvm_assemble); the patch
 // coefficients are the reference's: gaussConvectionScheme.C:96-110 (internalCoeffs = phi_b valueInternalCoeffs, boundaryCoeffs = -phi_b
@@ -17,6 +17,7 @@
 #include <cmath>
 #include <iomanip>
 #include <memory>
+#include <optional>
 
 using namespace Foam;
 
@@ -52,8 +53,15 @@ int main(int argc, char** argv)
         const fvSchemes schemes(caseDir);
         const label nNonOrthCorr = fvSolution.solutionDict().found("SIMPLE") ? fvSolution.dict("SIMPLE").lookupOrDefault<label>("nNonOrthogonalCorrectors", 0) : 0;
         const wordList ddtT = schemes.ddtScheme("ddt(T)");
-        if (ddtT != wordList{"Euler"} && ddtT != wordList{"backward"}) FatalErrorIn("scalarTransportFoam", "ddtSchemes: Euler | backward");
+        const bool crankNicolson = !ddtT.empty() && ddtT[0] == "CrankNicolson";
+        if (ddtT != wordList{"Euler"} && ddtT != wordList{"backward"} && !crankNicolson)
+            FatalErrorIn("scalarTransportFoam", "ddtSchemes: Euler | backward | CrankNicolson <oc>");
         const bool backward = ddtT == wordList{"backward"};
+        std::string ddtEntry;
+        for (const word& wd : ddtT) ddtEntry += (ddtEntry.empty() ? "" : " ") + wd;
+        // CrankNicolson: the scheme object owns ddt0(T) for the run (fv::CrankNicolsonDdtScheme); a missing or bad coefficient is refused here
+        std::optional<fv::CrankNicolsonDdtScheme> cnScheme;
+        if (crankNicolson) cnScheme.emplace(fv::CrankNicolsonDdtScheme::New(ddtEntry));
         const wordList divT = schemes.divScheme("div(phi,T)");
         if (divT.size() < 2 || divT[0] != "Gauss" || (divT[1] != "linear" && divT[1] != "upwind" && !(divT[1] == "limitedLinear" && divT.size() == 3)))
             FatalErrorIn("scalarTransportFoam", "div(phi,T): Gauss linear | Gauss upwind | Gauss limitedLinear k");
@@ -145,7 +153,7 @@ int main(int argc, char** argv)
         scalargpuField w(nI);
         if (upwind) upwindWeights(w, phi);                      // (phi does not change: the upwind weights are formed once)
 
-        scalargpuField ToldOld(backward ? n : 0);
+        scalargpuField ToldOld((backward || crankNicolson) ? n : 0);
 
         Info << std::endl << "Calculating scalar transport" << std::endl << std::endl;
         for (label step = 1; step <= nSteps; ++step) {
@@ -153,13 +161,17 @@ int main(int argc, char** argv)
             const scalargpuField Told(T);
             // backward: T.oldTime().oldTime() -- a copy of the old field on the first step, where deltaT0 = GREAT (backwardDdtScheme.C:57-69)
             const backwardDdtCoeffs bd = step == 1 ? backwardDdtCoeffs::firstStep(deltaT) : backwardDdtCoeffs(deltaT, deltaT);
-            if (backward && step == 1) ToldOld = Told;
+            if ((backward || crankNicolson) && step == 1) ToldOld = Told;
+            // CrankNicolson: the time index is the step; deltaT0 is the previous step's size (the fixed deltaT, Time::deltaT0's start value too)
+            if (crankNicolson) cnScheme->setTime(step, deltaT, deltaT);
             for (label nonOrth = 0; nonOrth <= nNonOrthCorr; ++nonOrth) {
                 vectorgpuField gT(n);
                 if (limited || corrected) gaussGrad(gT, T);
                 if (limited) limitedLinearWeights(w, addr, limiterK, weights, phi, T, gT, Cc);
                 fvScalarMatrix TEqn("T", addr, patchCells, notCoupled);
-                if (backward) fvm::assemble(TEqn, bd, 1.0, V, Told, ToldOld, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
+                if (crankNicolson)                              // ddt0(T) is updated by the first corrector's assembly only (evaluate)
+                    fvm::assemble(TEqn, *cnScheme, fv::CrankNicolsonDdtScheme::ddt0Name("T"), 1.0, V, Told, ToldOld, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
+                else if (backward) fvm::assemble(TEqn, bd, 1.0, V, Told, ToldOld, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
                 else fvm::assemble(TEqn, rDeltaT, 1.0, V, Told, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
                 for (label q = 0; q < nP; ++q) { TEqn.internalCoeffs()[q] = icDev[q]; TEqn.boundaryCoeffs()[q] = bcDev[q]; }
                 if (corrected) {                                // - fvm::laplacian(DT, T), corrected: source += V*div(DT |Sf| correction(T))
@@ -171,7 +183,7 @@ int main(int argc, char** argv)
                 }
                 TEqn.solve(T, TControls);
             }
-            if (backward) ToldOld = Told;
+            if (backward || crankNicolson) ToldOld = Told;
             Info << std::endl;
         }
         std::ostringstream tn; tn << std::setprecision(10) << nSteps * deltaT;

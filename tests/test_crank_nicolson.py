@@ -1,0 +1,650 @@
+"""`ddtSchemes { default CrankNicolson <oc>; }`: the ddt0 state, fvm::ddt, fvc::ddt and the fused assembly with the CrankNicolson time
+derivative (CrankNicolsonDdtScheme.H:165-180, CrankNicolsonDdtScheme.C:186-267, 417-426, 507-516, 603-616, 755-1003; static mesh).
+
+The expected values are a numpy restatement of the reference's field expressions written here: numpy evaluates one operator per pass and
+rounds each (tests/test_backward_ddt.py explains why that is the reference's rounding), so every comparison with the engine is bit for bit.
+CPU: the parser, the state sequence through the C ABI, the order of accuracy and the Euler limit of the restatement, the exports.  GPU: the
+three streaming kernels, mi_fvm_assemble_cn against the engine's own unfused sequence and against the restatement in every block shape of
+the row pass (with the Euler and backward calls on the same inputs), a six-step time loop with changing step sizes and a repeated assembly,
+scalarTransportFoam with `default CrankNicolson 0.9`, and the mirror's fvc::ddt / fvc::ddtCorr from a small program of their own."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_backward_ddt as bw
+from test_backward_ddt import SHAPES, VARIANTS, _close, _env, _fused_inputs
+
+
+# ---- the restatement -----------------------------------------------------------------------------------------------------------
+def off(oc, x):
+    """offCentre_ (.C:250-267)"""
+    return oc * x if oc < 1.0 else x
+
+
+class State:
+    """the DDt0Field's two time indices and the host scalars (.C:109-181, 186-247)"""
+
+    def __init__(self, oc, time_index):
+        self.oc, self.start, self.index = oc, time_index, time_index
+
+    def scalars(self, time_index):
+        coef = 1.0 + self.oc if time_index - self.start > 0 else 1.0
+        coef0 = 1.0 + self.oc if time_index - self.start > 1 else 1.0
+        return coef, coef0
+
+    def step(self, time_index, dt, dt0):
+        coef, coef0 = self.scalars(time_index)
+        evaluate = self.index != time_index
+        if evaluate:
+            self.index = time_index
+        return coef / dt, coef0 / dt0, evaluate
+
+
+def ddt0_update(rdt0, oc, p0, p00, d, rho_value=None, rho0=None, rho00=None):
+    """the ddt0 assignment of fvcDdt / fvmDdt (:417-418 no density, :507-508 constant, :603-607 field)"""
+    if rho0 is not None:
+        return (rdt0 * ((rho0 * p0) - (rho00 * p00))) - off(oc, d)
+    c = rdt0 if rho_value is None else rdt0 * rho_value
+    return (c * (p0 - p00)) - off(oc, d)
+
+
+def fvm_ddt(rdt, oc, V, p0, d, rho_value=None, rho=None, rho0=None):
+    """-> (diag, source) of fvmDdt (:755-832 no density, :837-913 constant, :919-1003 field); d: ddt0, already updated"""
+    if rho is not None:
+        return (rdt * rho) * V, (((rdt * rho0) * p0) + off(oc, d)) * V
+    c = rdt if rho_value is None else rdt * rho_value
+    return c * V, ((c * p0) + off(oc, d)) * V
+
+
+def fvc_ddt(rdt, oc, f, f0, d, rho_value=None, rho=None, rho0=None):
+    """fvcDdt (:426 no density, :516 constant, :615-616 field)"""
+    if rho is not None:
+        return (rdt * ((rho * f) - (rho0 * f0))) - off(oc, d)
+    c = rdt if rho_value is None else rdt * rho_value
+    return (c * (f - f0)) - off(oc, d)
+
+
+# ---- CPU -----------------------------------------------------------------------------------------------------------------------
+def test_parser(pkg):
+    eng = pkg.engine
+    for text, oc in (("CrankNicolson 0.9", 0.9), ("CrankNicolson 1", 1.0), ("CrankNicolson 0", 0.0), ("  CrankNicolson\t0.5 ", 0.5)):
+        assert eng.ddt_cn_parse(text) == oc, text
+    for text, token in (("CrankNicolson", "CrankNicolson"), ("CrankNicolson 1.5", "1.5"), ("CrankNicolson -0.1", "-0.1"), ("CrankNicolson nan", "nan"),
+                        ("CrankNicolson one", "one"), ("CrankNicolson 0.9 1", "'1'"), ("Euler", "Euler"), ("backward", "backward"), ("", "empty")):
+        with pytest.raises(eng.MiError) as e:
+            eng.ddt_cn_parse(text)
+        assert token in str(e.value), (text, str(e.value))
+    for text in ("CrankNicolson 1.5", "CrankNicolson -0.1"):
+        with pytest.raises(eng.MiError, match="should be >= 0 and <= 1"):
+            eng.ddt_cn_parse(text)
+    oc = C.c_double()
+    assert eng.lib().mi_ddt_cn_parse(None, C.byref(oc)) != 0 and eng.lib().mi_ddt_cn_parse(b"CrankNicolson 1", None) != 0
+
+
+def test_state_sequence_through_the_c_abi(pkg):
+    """mi_ddt_cn_begin / mi_ddt_cn_step: Euler on the step of first use, coef0 one step behind coef, evaluate once per time index"""
+    eng = pkg.engine
+    oc, dts = 0.9, [0.01, 0.01, 0.004, 0.008]
+    want = [(1.0, 1.0, False), (1.9, 1.0, True), (1.9, 1.9, True), (1.9, 1.9, True)]
+    for first in (1, 5):
+        cn, ref = eng.CrankNicolson(oc, first), State(oc, first)
+        assert cn.oc == oc and cn.state.start_time_index == first and cn.state.ddt0_time_index == first
+        for k, dt in enumerate(dts):
+            dt0 = dts[k - 1] if k else dts[0]
+            assert (*ref.scalars(first + k), want[k][2]) == want[k]
+            got = cn.step(first + k, dt, dt0)
+            assert got == (want[k][0] / dt, want[k][1] / dt0, want[k][2]), (first, k, got)
+            assert got == ref.step(first + k, dt, dt0)
+            assert cn.state.ddt0_time_index == first + k and cn.state.start_time_index == first
+            again = cn.step(first + k, dt, dt0)                       # non-orthogonal correctors: the same scalars, no second update
+            assert again == (got[0], got[1], False), (first, k, again)
+    cn = eng.CrankNicolson(oc, 1)
+    for bad in (lambda: cn.step(1, 0.0, 0.01), lambda: cn.step(1, -0.01, 0.01), lambda: cn.step(2, 0.01, 0.0), lambda: cn.step(2, 0.01, -1.0),
+                lambda: eng.CrankNicolson(1.5, 1), lambda: eng.CrankNicolson(-0.1, 1), lambda: eng.CrankNicolson(float("nan"), 1)):
+        with pytest.raises(eng.MiError):
+            bad()
+    assert cn.state.ddt0_time_index == 1                              # a refused step leaves the state alone
+    assert cn.step(1, 0.01, 0.0) == (100.0, 0.0, False)               # delta_t0 is read only when evaluate is set
+    assert cn.step(1, 0.01, -1.0)[2] is False
+    assert cn.step(2, 0.01, 0.01) == (1.9 / 0.01, 1.0 / 0.01, True)
+
+
+def _decay_error(steps, oc):
+    """dT/dt = -2 T, T(0) = 1, one cell of volume 0.37, Sp as V*k on the diagonal, to t = 1: the set-up of
+    tests/test_backward_ddt.py::test_restated_fvm_ddt_is_second_order_and_euler_first, with the ddt0 state carried along"""
+    V, k = np.array([0.37]), 2.0
+    dt = 1.0 / steps
+    T0 = T00 = np.array([1.0])
+    st, d0 = State(oc, 1), np.zeros(1)
+    pairs = []
+    for s in range(1, steps + 1):
+        rdt, rdt0, evaluate = st.step(s, dt, dt)
+        if evaluate:
+            d0 = ddt0_update(rdt0, oc, T0, T00, d0)
+        d, src = fvm_ddt(rdt, oc, V, T0, d0)
+        pairs.append((d, src, (1.0 / dt) * V, ((1.0 / dt) * T0) * V))
+        T = src / (d + V * k)
+        T00, T0 = T0, T
+    return abs(T0[0] - np.exp(-2.0)), pairs
+
+
+def test_restatement_is_second_order_at_oc_1_and_euler_at_oc_0():
+    e = [_decay_error(s, 1.0)[0] for s in (20, 40, 80, 160)]
+    for a, b in zip(e, e[1:]):
+        assert 3.8 <= a / b <= 4.1, e
+    for d, src, de, se in _decay_error(40, 0.0)[1]:
+        assert np.array_equal(d, de) and np.array_equal(src, se)
+
+
+def test_exports(pkg):
+    from test_polymesh import PKG
+    eng = pkg.engine
+    names = ["mi_ddt_cn_parse", "mi_ddt_cn_begin", "mi_ddt_cn_step", "mi_ddt_cn_update", "mi_fvm_ddt_cn", "mi_fvc_ddt_cn", "mi_fvm_assemble_cn"]
+    for name in names:
+        assert name in eng.SYMBOLS and hasattr(eng.lib(), name), name
+    out = subprocess.run(["nm", "-D", "-C", os.path.join(PKG, "libmiFoam.so")], capture_output=True, text=True, check=True).stdout
+    assert "Foam::fv::CrankNicolsonDdtScheme::New(" in out and "Foam::fv::CrankNicolsonDdtScheme::assemble(" in out
+    assert "Foam::fvm::ddt(Foam::fvScalarMatrix&, Foam::fv::CrankNicolsonDdtScheme&" in out
+    assert "Foam::fvc::ddt(Foam::gpuList<double>&, Foam::fv::CrankNicolsonDdtScheme&" in out
+    assert "Foam::fvc::ddtCorr(Foam::gpuList<double>&, Foam::lduAddressing const&, Foam::fv::CrankNicolsonDdtScheme&" in out
+    assert "Foam::fv::CrankNicolsonDdtScheme::evaluate(" in out and "Foam::fv::CrankNicolsonDdtScheme::rDtCoef(" in out
+
+
+# ---- GPU -----------------------------------------------------------------------------------------------------------------------
+OCS = [1.0, 0.9, 0.0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3, 1027, 31 * 23 * 19])
+def test_streaming_kernels_against_the_restatement(pkg, n):
+    """mi_ddt_cn_update (one and three fields, in place) / mi_fvm_ddt_cn / mi_fvc_ddt_cn: the three density forms x three off-centring
+    coefficients; sizes with an odd tail and an unpaired element of the double2 loop"""
+    import torch
+    eng, ctx, dev, host, E = _env(pkg)
+    u = pkg.synthetic.splitmix_uniform
+    case = pkg.synthetic.box_case(2, 2, 2)
+    asm = eng.Assembly(eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr))
+    V, p = 0.5 + u(1, n), u(2, n) - 0.5
+    p0, p00, d0 = [u(3 + k, n) - 0.5 for k in range(3)], [u(6 + k, n) - 0.5 for k in range(3)], [40.0 * (u(9 + k, n) - 0.5) for k in range(3)]
+    rho, rho0, rho00 = 0.9 + u(15, n), 0.8 + u(16, n), 0.7 + u(17, n)
+    d, s, o = E(n), E(n), E(n)
+    rdt, rdt0 = 1.9 / 0.004, 1.9 / 0.01
+    for oc in OCS:
+        for form in ("none", "constant", "field"):
+            kw = dict(constant=dict(rho_value=1.3), field=dict(rho=rho, rho0=rho0)).get(form, {})
+            ukw = dict(constant=dict(rho_value=1.3), field=dict(rho0=rho0, rho00=rho00)).get(form, {})
+            ekw = dict(constant=dict(rho_value=1.3), field=dict(rho=dev(rho), rho_old=dev(rho0))).get(form, {})
+            eukw = dict(constant=dict(rho_value=1.3), field=dict(rho_old=dev(rho0), rho_old_old=dev(rho00))).get(form, {})
+            for k in (1, 3):
+                io = [dev(x) for x in d0[:k]]
+                asm.ddt_cn_update(rdt0, oc, [dev(x) for x in p0[:k]], [dev(x) for x in p00[:k]], io, **eukw)
+                for j in range(k):
+                    assert np.array_equal(host(io[j]), ddt0_update(rdt0, oc, p0[j], p00[j], d0[j], **ukw)), (form, oc, k, j)
+            asm.fvm_ddt_cn(rdt, oc, dev(V), dev(p0[0]), dev(d0[0]), d, s, **ekw)
+            rd, rs = fvm_ddt(rdt, oc, V, p0[0], d0[0], **kw)
+            assert np.array_equal(host(d), rd) and np.array_equal(host(s), rs), (form, oc)
+            asm.fvc_ddt_cn(rdt, oc, dev(p), dev(p0[0]), dev(d0[0]), o, **ekw)
+            assert np.array_equal(host(o), fvc_ddt(rdt, oc, p, p0[0], d0[0], **kw)), (form, oc)
+    if n != 1027:
+        return
+    # refusals: a missing array, an unaligned array, an output among the inputs or twice, one density array of two, oc outside [0, 1]
+    Vd, pd, p0d, p00d, dd, rd_ = dev(V), dev(p), dev(p0[0]), dev(p00[0]), dev(d0[0]), dev(rho)
+    odd = torch.empty(n + 1, dtype=torch.float64, device="cuda:0")[1:]
+    assert odd.data_ptr() % 16 == 8 and odd.is_contiguous()
+    for bad in (lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, None, d, s), lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, dd, None, s),
+                lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, dd, odd, s), lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, odd, dd, d, s),
+                lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, dd, p0d, s), lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, dd, d, dd),
+                lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, dd, d, d), lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, dd, d, s, rho=rd_),
+                lambda: asm.fvm_ddt_cn(rdt, 0.9, Vd, p0d, dd, d, s, rho_old=rd_), lambda: asm.fvm_ddt_cn(rdt, 1.5, Vd, p0d, dd, d, s),
+                lambda: asm.fvc_ddt_cn(rdt, 0.9, pd, p0d, dd, dd), lambda: asm.fvc_ddt_cn(rdt, 0.9, pd, p0d, dd, pd),
+                lambda: asm.fvc_ddt_cn(rdt, 0.9, pd, p0d, None, o), lambda: asm.fvc_ddt_cn(rdt, 0.9, pd, None, dd, o),
+                lambda: asm.fvc_ddt_cn(rdt, 0.9, pd, p0d, dd, odd), lambda: asm.fvc_ddt_cn(rdt, 0.9, pd, p0d, dd, o, rho_old=rd_),
+                lambda: asm.fvc_ddt_cn(rdt, -0.1, pd, p0d, dd, o),
+                lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d], [p00d], [p0d]), lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d], [p00d], [None]),
+                lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d], [None], [dd]), lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d], [p00d], [odd]),
+                lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d, p0d], [p00d, p00d], [dd, dd]), lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d], [p00d], [dd], rho_old=rd_),
+                lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d], [p00d], [dd], rho_old_old=rd_), lambda: asm.ddt_cn_update(rdt0, 2.0, [p0d], [p00d], [dd]),
+                lambda: asm.ddt_cn_update(rdt0, 0.9, [p0d] * 5, [p00d] * 5, [E(n) for _ in range(5)]), lambda: asm.ddt_cn_update(rdt0, 0.9, [], [], [])):
+        with pytest.raises(eng.MiError):
+            bad()
+    assert np.array_equal(host(dd), d0[0])                            # no refused call wrote
+
+
+# ---- the fused assembly ----------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,mode,tables", SHAPES)
+def test_fused_cn_assembly_bit_for_bit(pkg, orc, monkeypatch, name, mode, tables):
+    """mi_fvm_assemble_cn against (a) the engine's own unfused sequence -- mi_fvm_ddt_cn, mi_fvm_div, mi_fvm_laplacian, mi_fvm_su / Sp, the
+    mi_vec_axpby combinations, in the order tests/test_assembly.py uses -- and (b) the restatement; and on the same inputs the Euler call (no
+    `crank_nicolson` key) and the backward call against their own unfused sequences."""
+    from conftest import random_graph_case
+    monkeypatch.delenv("MI_ROW16", raising=False); monkeypatch.delenv("MI_XCD_ROWS", raising=False)
+    if tables == "row32":
+        monkeypatch.setenv("MI_ROW16", "0")
+    elif tables == "noxcd":
+        monkeypatch.setenv("MI_XCD_ROWS", "0")
+    monkeypatch.setenv("MI_ROW_BS", "1024" if mode == "fixed1024" else "256")
+    if mode.endswith("unstaged"):
+        monkeypatch.setenv("MI_ROW_CAP", "64")
+    eng, ctx, dev, host, E = _env(pkg)
+    syn = pkg.synthetic
+    case = syn.box_case(31, 23, 19, symmetric=False) if name == "box" else random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=False)
+    if mode.startswith("tiles"):
+        a0 = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
+        case = syn.renumber(case, a0.cell_perm())
+        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr, ordered=True, tile_cell_start=a0.tile_starts())
+        assert addr.is_ordered
+    else:
+        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
+    n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
+    q = _fused_inputs(pkg, n, nf)
+    u = syn.splitmix_uniform
+    ddt0 = [40.0 * (u(181 + k, n) - 0.5) for k in range(3)]
+    A = eng.Assembly(addr)
+    rdt, rdt_e = 1.9 / 0.004, 1.0 / 0.004                                  # rDtCoef of the CN call; Euler's and backward's rDeltaT
+    cb = bw.coeffs(0.004, 0.01)
+    vol, flux = dev(q["vol"]), dev(q["flux"])
+    uL, dL = orc.fvm_laplacian(n, lo, up, q["delta"], q["gamma"])
+    for vi, v in enumerate(VARIANTS):
+        if v["corr"] and name != "box":
+            continue
+        oc = OCS[vi % 3]                                                    # 1.0, 0.9, 0.0, 1.0, 0.9 over the five variants
+        R = v["n_rhs"]
+        DIV = v["div"] is not False
+        wh = None if not DIV else (orc.upwind_weights(q["flux"]) if v["div"] is None else q["w"])
+        wd = dev(q["w"]) if v["div"] == "w" else None
+        ddt = dict(vol=vol, psi_old=[dev(x) for x in q["psi0"][:R]])
+        cn = dict(oc=oc, ddt0=[dev(x) for x in ddt0[:R]])
+        back = dict(coeffs=cb, psi_old_old=[dev(x) for x in q["psi00"][:R]])
+        if v["field"]:
+            ddt.update(rho=dev(q["rho"]), rho_old=dev(q["rho0"])); back["rho_old_old"] = dev(q["rho00"])
+            rkw = dict(rho=q["rho"], rho0=q["rho0"])
+            ekw = dict(rho=ddt["rho"], rho_old=ddt["rho_old"])
+        else:
+            ddt["rho_value"] = 1.2
+            rkw, ekw = dict(rho_value=1.2), dict(rho_value=1.2)
+        div = None
+        if DIV:
+            div = dict(flux=flux, weights=wd)
+            if v["corr"]:
+                grads = [[dev(x) for x in g] for g in q["grad"][:R]]
+                div["correction"] = dict(scale=1.0, cf=[dev(x) for x in q["cf"]], c=[dev(x) for x in q["C"]], grad=grads)
+        lap = dict(delta_coeffs=dev(q["delta"]), gamma_magsf=dev(q["gamma"]))
+        sp = (dev(q["sp"]), -1.0) if v["extras"] else None
+        su = [(1.0, [dev(x) for x in q["su"][:R]]), (-1.0, [dev(x) for x in q["su2"][:R]])] if v["extras"] else []
+
+        def fused(ddt_arg):
+            o = dict(lower=E(nf) if DIV else None, upper=E(nf), diag=E(n), mag=E(n), src=[E(n) for _ in range(R)])
+            A.assemble(o["upper"], o["diag"], lower_out=o["lower"], sources_out=o["src"], ddt=ddt_arg, div=div, laplacian=lap, sp=sp, su=su, sum_mag_out=o["mag"])
+            return o
+
+        def unfused(time):
+            """the scheme-by-scheme calls and their combination, the order of tests/test_assembly.py::_fused_assembly_bit_exact"""
+            cl, cu, cd, lu, ld, dd, ds = E(nf), E(nf), E(n), E(nf), E(n), E(n), [E(n) for _ in range(R)]
+            t = [E(nf) for _ in range(R)]
+            if DIV:
+                wts = wd
+                if wts is None:
+                    wts = E(nf); A.upwind_weights(flux, wts)
+                A.fvm_div(wts, flux, cl, cu, cd)
+                if v["corr"]:
+                    A.linear_upwind_correction(flux, div["correction"]["cf"], div["correction"]["c"], div["correction"]["grad"], t)
+            A.fvm_laplacian(lap["delta_coeffs"], lap["gamma_magsf"], lu, ld)
+            for r in range(R):
+                if time == "cn":
+                    A.fvm_ddt_cn(rdt, oc, vol, ddt["psi_old"][r], cn["ddt0"][r], dd, ds[r], **ekw)
+                elif time == "backward":
+                    A.fvm_ddt_backward(rdt_e, cb, vol, ddt["psi_old"][r], back["psi_old_old"][r], dd, ds[r], rho_old_old=back.get("rho_old_old"), **ekw)
+                elif v["field"]:
+                    A.fvm_ddt_euler_rho(rdt_e, ddt["rho"], ddt["rho_old"], vol, ddt["psi_old"][r], dd, ds[r])
+                else:
+                    A.fvm_ddt_euler(rdt_e, 1.2, vol, ddt["psi_old"][r], dd, ds[r])
+                if v["corr"]:
+                    ivf = E(n); A.surface_integrate(t[r], vol, ivf); A.submul(vol, ivf, ds[r])
+                if v["extras"]:
+                    A.fvm_su(vol, su[0][1][r], ds[r])                           # + su: source -= V*su
+                    p = vol * su[1][1][r]; ds[r].add_(p)                        # == su2: source += V*su2
+            if DIV:
+                A.axpby(1.0, cl, -1.0, lu, cl); A.axpby(1.0, cu, -1.0, lu, cu)
+                A.axpby(1.0, dd, 1.0, cd, dd)
+            else:
+                A.axpby(-1.0, lu, 0.0, lu, cu)
+            A.axpby(1.0, dd, -1.0, ld, dd)
+            if v["extras"]:
+                p = vol * sp[0]; dd.sub_(p)
+            return dict(lower=cl if DIV else None, upper=cu, diag=dd, src=ds, t=t)
+
+        def same(got, seq, what):
+            for key in ("lower", "upper", "diag"):
+                if got[key] is not None:
+                    assert np.array_equal(host(got[key]), host(seq[key])), (v["tag"], what, key)
+            for r in range(R):
+                assert np.array_equal(host(got["src"][r]), host(seq["src"][r])), (v["tag"], what, r)
+
+        got = fused(dict(ddt, r_delta_t=rdt, crank_nicolson=cn))
+        seq = unfused("cn")
+        same(got, seq, "cn")
+        for r in range(R):
+            assert np.array_equal(host(cn["ddt0"][r]), ddt0[r])                 # an input only
+        # (b) the restatement
+        if DIV:
+            lB, uB, dB = orc.fvm_div(n, lo, up, wh, q["flux"])
+            lower, upper = lB - uL, uB - uL
+        else:
+            lower, upper = None, -uL
+        for r in range(R):
+            dD, s = fvm_ddt(rdt, oc, q["vol"], q["psi0"][r], ddt0[r], **rkw)
+            if v["corr"]:
+                ivf = orc.surface_integrate(n, lo, up, host(seq["t"][r]), q["vol"])
+                s = s - q["vol"] * ivf
+            if v["extras"]:
+                s = s - q["vol"] * q["su"][r]
+                s = s + q["vol"] * q["su2"][r]
+            assert np.array_equal(host(got["src"][r]), s), (v["tag"], r)
+        diag = ((dD + dB) - dL) if DIV else (dD - dL)
+        if v["extras"]:
+            diag = diag - q["vol"] * q["sp"]
+        assert np.array_equal(host(got["diag"]), diag) and np.array_equal(host(got["upper"]), upper), v["tag"]
+        if DIV:
+            assert np.array_equal(host(got["lower"]), lower), v["tag"]
+        assert np.array_equal(host(got["mag"]), orc.row_face_op(2, n, lo, up, lower, upper, np.zeros(n))), v["tag"]
+        # Euler and backward untouched: the same call without the `crank_nicolson` key, and with the `backward` key
+        eul = fused(dict(ddt, r_delta_t=rdt_e))
+        same(eul, unfused("euler"), "euler")
+        bwd = fused(dict(ddt, r_delta_t=rdt_e, backward=back))
+        same(bwd, unfused("backward"), "backward")
+        for r in range(R):
+            assert not np.array_equal(host(eul["src"][r]), host(got["src"][r])) and not np.array_equal(host(bwd["src"][r]), host(got["src"][r]))
+    # refusals of the CrankNicolson entry point
+    ddt = dict(r_delta_t=rdt, vol=vol, psi_old=[dev(q["psi0"][0])])
+    d0, p00 = dev(ddt0[0]), dev(q["psi00"][0])
+    o = dict(lower=E(nf), upper=E(nf), diag=E(n), src=[E(n)])
+    call = lambda d: A.assemble(o["upper"], o["diag"], lower_out=o["lower"], sources_out=o["src"], ddt=d, div=dict(flux=flux), laplacian=lap)
+    call(dict(ddt, crank_nicolson=dict(oc=0.9, ddt0=[d0])))
+    for bad in (dict(vol=vol, crank_nicolson=dict(oc=0.9, ddt0=[d0])),                                       # terms->ddt == 0
+                dict(ddt, crank_nicolson=dict(oc=0.9, ddt0=[None])),                                         # a missing ddt0 array
+                dict(ddt, crank_nicolson=dict(oc=0.9, ddt0=[o["src"][0]])),                                  # a ddt0 array among the outputs
+                dict(ddt, crank_nicolson=dict(oc=0.9, ddt0=[o["diag"]])),
+                dict(ddt, crank_nicolson=dict(oc=1.5, ddt0=[d0])),                                           # oc outside [0, 1]
+                dict(ddt, rho=dev(q["rho"]), crank_nicolson=dict(oc=0.9, ddt0=[d0])),                        # rho without rho_old (mi_fvm_assemble's)
+                dict(ddt, crank_nicolson=dict(oc=0.9, ddt0=[d0]), backward=dict(coeffs=cb, psi_old_old=[p00]))):   # both schemes
+        with pytest.raises(eng.MiError):
+            call(bad)
+    with pytest.raises(eng.MiError):                                                                         # a coefficient output aliasing an input
+        A.assemble(flux, o["diag"], lower_out=o["lower"], sources_out=o["src"], ddt=dict(ddt, crank_nicolson=dict(oc=0.9, ddt0=[d0])), div=dict(flux=flux))
+    with pytest.raises(eng.MiError):                                                                         # no face term at all
+        A.assemble(o["upper"], o["diag"], sources_out=o["src"], ddt=dict(ddt, crank_nicolson=dict(oc=0.9, ddt0=[d0])))
+    t = eng.FvmTerms()
+    assert eng.lib().mi_fvm_assemble_cn(addr.h, C.byref(t), None, None, None, None, None, None, None) != 0   # cn NULL
+
+
+# ---- the statements of scalarTransportFoam walked with the restatement ----------------------------------------------------------------
+def walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, dts, scheme, corrected, n_non_orth, oc=None, repeat_at=()):
+    """tests/test_scalartransportfoam.py::oracle_scalar_transport with the ddt line replaced by the restatement and its state (the ddt0 field
+    created at the first step's time index, updated once per step), one step size per step.  oc None: Euler.  repeat_at: steps whose first
+    assembly is formed twice (the second must see the same ddt0).  -> solver lines, T, mesh data, per step the assembled system and ddt0"""
+    from test_polymesh import geometry
+    syn = pkg.synthetic
+    G = geometry(pts, faces, owner, neighbour)
+    n, nI = int(owner.max()) + 1, len(neighbour)
+    lo, up = owner[:nI].astype(np.int32), neighbour.astype(np.int32)
+    V, lam, delta, magSf = G["V"], G["weights"], G["delta"], G["magSf"][:nI]
+    Sf = [np.ascontiguousarray(G["Sf"][:nI, k]) for k in range(3)]
+    nhat = G["Sf"][:nI] / magSf[:, None]
+    cv = nhat - (G["C"][up] - G["C"][lo]) * delta[:, None]
+    cv = [np.ascontiguousarray(cv[:, k]) for k in range(3)]
+    u0 = np.array([1.0, 0.2, 0.0])
+    U = [np.full(n, u0[k]) for k in range(3)]
+    phi = orc.flux_div(n, lo, up, lam, Sf, U, want_div=False)
+    P = []
+    for name, ptype, cnt, start in patches:
+        fc = owner[start:start + cnt].astype(np.int32)
+        sfb = G["Sf"][start:start + cnt]
+        ub = np.tile(u0, (cnt, 1)) if name in ("inlet", "outlet") else np.zeros((cnt, 3))
+        phib = ub[:, 0] * sfb[:, 0] + ub[:, 1] * sfb[:, 1] + ub[:, 2] * sfb[:, 2]
+        diff = DT * G["magSf"][start:start + cnt] * G["delta_b"][start - nI:start - nI + cnt]
+        fixed = name == "inlet"
+        tb = tin if fixed else None
+        P.append(dict(fc=fc, sf=[np.ascontiguousarray(sfb[:, k]) for k in range(3)], tb=tb,
+                      ic=diff if fixed else phib, bc=(diff * tb - phib * tb) if fixed else np.zeros(cnt)))
+
+    def grad(T):
+        g = orc.gauss_grad(n, lo, up, Sf, orc.face_interpolate(lo, up, lam, T), None)
+        for q in P:
+            for k in range(3):
+                g[k] = orc.patch_add_product(q["fc"], q["sf"][k], T[q["fc"]] if q["tb"] is None else q["tb"], g[k], 0)
+        return [x / V for x in g]
+
+    T = T0.copy()
+    Too = None
+    uL, dL = orc.fvm_laplacian(n, lo, up, delta, DT * magSf)
+    st, d0 = (None if oc is None else State(oc, 1)), np.zeros(n)
+    lines, systems = [], []
+    for step, dt in enumerate(dts):
+        Told = T.copy()
+        if step == 0:
+            Too = Told.copy()
+        for non_orth in range(n_non_orth + 1):
+            gT = grad(T) if corrected else None
+            w = orc.upwind_weights(phi) if scheme == "upwind" else lam
+            lB, uB, dB = orc.fvm_div(n, lo, up, w, phi)
+            for _ in range(2 if (step in repeat_at and non_orth == 0) else 1):
+                if st is None:
+                    dD, sD = orc.fvm_ddt_euler(1.0 / dt, 1.0, V, Told)
+                else:
+                    rdt, rdt0, evaluate = st.step(step + 1, dt, dts[step - 1] if step else dt)
+                    assert evaluate == (step > 0 and non_orth == 0 and _ == 0)
+                    if evaluate:
+                        d0 = ddt0_update(rdt0, oc, Told, Too, d0)
+                    dD, sD = fvm_ddt(rdt, oc, V, Told, d0)
+            lower, upper, diag, source = lB - uL, uB - uL, (dD + dB) - dL, sD
+            if non_orth == 0:
+                systems.append(dict(lower=lower, upper=upper, diag=diag, source=source, ddt0=d0.copy()))
+            if corrected:
+                cf = orc.sngrad_correction_flux(lo, up, cv, lam, gT, -(DT * magSf))
+                source = orc.submul(V, orc.surface_integrate(n, lo, up, cf, V), source)
+            for q in P:
+                diag = orc.patch_add(q["fc"], q["ic"], diag, 0); source = orc.patch_add(q["fc"], q["bc"], source, 0)
+            T, perf = orc.System([syn.LduCase(n, lo, up, diag, upper, lower, source)]).pbicg(T, source, "AINV", tolerance=1e-10, relTol=0.0)
+            lines.append(("AINVPBiCG", "T", perf["initialResidual"], perf["finalResidual"], perf["nIterations"]))
+        Too = Told
+    return lines, T, dict(G=G, n=n, nI=nI, lo=lo, up=up, phi=phi, P=P), systems
+
+
+@pytest.fixture(scope="module")
+def loop_case(pkg, orc):
+    """the 12 x 8 x 6 box of the time loop and its Euler walk, computed once"""
+    from test_polymesh import make_box_mesh
+    mesh = make_box_mesh((12, 8, 6), seed=None)
+    cnt_in = [pt[2] for pt in mesh[4] if pt[0] == "inlet"][0]
+    tin = 1.0 + 0.5 * np.sin(np.arange(cnt_in))
+    n = int(mesh[2].max()) + 1
+    dts = [0.01, 0.01, 0.004, 0.008, 0.008, 0.01]
+    euler = walk(pkg, orc, *mesh, tin, np.zeros(n), 0.01, dts, "linear", False, 0)
+    return dict(mesh=mesh, tin=tin, n=n, dts=dts, DT=0.01, euler=euler)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("oc", [0.9, 1.0, 0.0])
+def test_time_loop_with_changing_step_sizes(pkg, orc, loop_case, oc):
+    """six steps of ddt(T) + div(phi,T) - laplacian(DT,T) through Python: the state object, the evaluate-once update, the fused assembly,
+    PBiCG + DILU, against the same statements walked with the restatement and the oracle's PBiCG; steps 2 and 4 assemble twice.  oc 0: the
+    assembled arrays are the Euler assembly's."""
+    import torch
+    eng, ctx, dev, host, E = _env(pkg)
+    L = loop_case
+    DT, dts, n = L["DT"], L["dts"], L["n"]
+    repeat_at = (2, 4)
+    ref_lines, Tref, M, systems = walk(pkg, orc, *L["mesh"], L["tin"], np.zeros(n), DT, dts, "linear", False, 0, oc=oc, repeat_at=repeat_at)
+    elines, Teuler, _, esystems = L["euler"]
+    G, nI, lo, up = M["G"], M["nI"], M["lo"], M["up"]
+    addr = eng.Addressing(ctx, n, lo, up)
+    A, mat = eng.Assembly(addr), eng.Matrix(addr)
+    V, lam, phi = dev(G["V"]), dev(G["weights"]), dev(M["phi"])
+    lap = dict(delta_coeffs=dev(G["delta"]), gamma_magsf=dev(DT * G["magSf"][:nI]))
+    uL, dL = orc.fvm_laplacian(n, lo, up, G["delta"], DT * G["magSf"][:nI])
+    lB, uB, dB = orc.fvm_div(n, lo, up, G["weights"], M["phi"])
+    patch = [(eng.Patch(ctx, n, q["fc"]), dev(q["ic"]), dev(q["bc"])) for q in M["P"]]
+    T = torch.zeros(n, dtype=torch.float64, device="cuda:0")
+    lower, upper, diag, src = E(nI), E(nI), E(n), E(n)
+    ref, d0 = State(oc, 1), np.zeros(n)                                    # the restated state, on the fields each step starts from
+    el, eu, ed, es = E(nI), E(nI), E(n), E(n)
+    cn, ddt0 = eng.CrankNicolson(oc, 1), torch.zeros(n, dtype=torch.float64, device="cuda:0")      # created zero at the first step's time index
+    Too = None
+    for step, dt in enumerate(dts):
+        Told = T.clone()
+        if step == 0:
+            Too = Told.clone()
+        for rep in range(2 if step in repeat_at else 1):
+            rdt, rdt0, evaluate = cn.step(step + 1, dt, dts[step - 1] if step else dt)
+            assert evaluate == (step > 0 and rep == 0), (step, rep)
+            assert (rdt, rdt0, evaluate) == ref.step(step + 1, dt, dts[step - 1] if step else dt)
+            if evaluate:
+                A.ddt_cn_update(rdt0, oc, [Told], [Too], [ddt0])
+                d0 = ddt0_update(rdt0, oc, host(Told), host(Too), d0)
+            A.assemble(upper, diag, lower_out=lower, sources_out=[src], ddt=dict(r_delta_t=rdt, vol=V, psi_old=[Told], crank_nicolson=dict(oc=oc, ddt0=[ddt0])),
+                       div=dict(flux=phi, weights=lam), laplacian=lap)
+            dD, sD = fvm_ddt(rdt, oc, G["V"], host(Told), d0)
+            assert np.array_equal(host(ddt0), d0), (step, rep)                  # the second assembly of a step sees an unchanged ddt0
+            assert np.array_equal(host(lower), lB - uL) and np.array_equal(host(upper), uB - uL), (step, rep)
+            assert np.array_equal(host(diag), (dD + dB) - dL) and np.array_equal(host(src), sD), (step, rep)
+        if oc == 0.0:
+            A.assemble(eu, ed, lower_out=el, sources_out=[es], ddt=dict(r_delta_t=1.0 / dt, vol=V, psi_old=[Told]), div=dict(flux=phi, weights=lam), laplacian=lap)
+            for got, e in ((lower, el), (upper, eu), (diag, ed), (src, es)):
+                assert np.array_equal(host(got), host(e)), step
+        for p, ic, bc in patch:
+            p.add(ic, diag, 0); p.add(bc, src, 0)
+        mat.set_coeffs(diag, upper, lower)
+        perf = mat.pbicg(T, src, "DILU", tolerance=1e-10, relTol=0.0)
+        r = ref_lines[step]
+        assert _close((perf["initialResidual"], perf["finalResidual"], perf["nIterations"]), r[2:]), (step, perf, r)
+        Too = Told
+    Tg = host(T)
+    assert np.max(np.abs(Tg - Tref)) <= 1e-8 * np.max(np.abs(Tref))
+    assert 0.05 < np.max(Tref) < 2.0
+    if oc == 0.0:
+        assert np.max(np.abs(Tref - Teuler)) <= 1e-8 * np.max(np.abs(Tref))      # the Euler walk: the same arrays every step
+    else:
+        assert np.max(np.abs(Tref - Teuler)) > 1e-5 * np.max(np.abs(Tref))       # the scheme is not a no-op
+        assert np.any(systems[2]["ddt0"] != 0.0) and not np.any(systems[0]["ddt0"] != 0.0)
+
+
+def _channel(tmp_path, dims, n_steps, scheme, corrected, n_non_orth, ddt_entry):
+    from test_scalartransportfoam import write_channel
+    case_dir = str(tmp_path / "channel")
+    made = write_channel(case_dir, dims, 0.01, 0.01, n_steps, scheme, corrected, n_non_orth)
+    fs = os.path.join(case_dir, "system", "fvSchemes")
+    txt = open(fs).read()
+    assert "ddtSchemes { default Euler; }" in txt
+    open(fs, "w").write(txt.replace("ddtSchemes { default Euler; }", "ddtSchemes { default %s; }" % ddt_entry))
+    return case_dir, made
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims, n_steps, scheme, corrected, n_non_orth", [((12, 8, 6), 4, "upwind", False, 0), ((12, 9, 7), 3, "linear", True, 2)])
+def test_scalarTransportFoam_with_the_crank_nicolson_scheme(pkg, orc, tmp_path, dims, n_steps, scheme, corrected, n_non_orth):
+    """the application with `ddtSchemes { default CrankNicolson 0.9; }`: T.oldTime().oldTime() kept, ddt0(T) owned by the scheme object and
+    updated by the first corrector's assembly only; every solver line and the written T against the walk, with the comparisons of
+    tests/test_backward_ddt.py::test_scalarTransportFoam_with_the_backward_scheme"""
+    from test_polymesh import PKG, LINE, read_vol_field
+    DT, delta_t = 0.01, 0.01
+    case_dir, (pts, faces, owner, neighbour, patches, tin, T0) = _channel(tmp_path, dims, n_steps, scheme, corrected, n_non_orth, "CrankNicolson 0.9")
+    ref, Tref, _, _ = walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, [delta_t] * n_steps, scheme, corrected, n_non_orth, oc=0.9)
+    _, Teuler, _, _ = walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, [delta_t] * n_steps, scheme, corrected, n_non_orth)
+    out = subprocess.run([os.path.join(PKG, "scalarTransportFoam"), case_dir], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr + out.stdout[-1500:]
+    got = [(m.group(1), m.group(2), float(m.group(3)), float(m.group(4)), int(m.group(5))) for m in map(LINE.match, out.stdout.splitlines()) if m]
+    assert len(got) == len(ref) == n_steps * (n_non_orth + 1)
+    for g, r in zip(got, ref):
+        assert g[:2] == r[:2] and g[4] == r[4], (g, r)
+        assert abs(g[2] - r[2]) <= 1e-7 * max(r[2], 1e-12) + 1e-14 and abs(g[3] - r[3]) <= 1e-6 * max(r[2], 1e-12) + 1e-14, (g, r)
+    f = read_vol_field(os.path.join(case_dir, f"{n_steps * delta_t:.10g}", "T"))
+    assert f["header"]["class"] == "volScalarField" and np.max(np.abs(f["internalField"] - Tref)) <= 1e-8 * np.max(np.abs(Tref))
+    assert 0.05 < np.max(Tref) < 2.0 and np.min(Tref) > -0.2
+    bf = dict(f["boundaryField"])
+    assert bf["inlet"]["type"] == "fixedValue" and np.array_equal(bf["inlet"]["value"], tin) and bf["outlet"] == {"type": "zeroGradient"}
+    assert np.max(np.abs(Teuler - Tref)) > 1e-5 * np.max(np.abs(Tref))          # not the Euler result
+
+
+@pytest.mark.gpu
+def test_scalarTransportFoam_refuses_crank_nicolson_without_a_coefficient(pkg, tmp_path):
+    from test_polymesh import PKG
+    case_dir, _ = _channel(tmp_path, (12, 8, 6), 1, "upwind", False, 0, "CrankNicolson")
+    out = subprocess.run([os.path.join(PKG, "scalarTransportFoam"), case_dir], capture_output=True, text=True, timeout=600)
+    assert out.returncode != 0 and "CrankNicolson" in out.stderr + out.stdout and "coefficient" in out.stderr + out.stdout, out.stderr + out.stdout[-800:]
+
+
+MIRROR_PROGRAM = r'''
+#include "miFoam.H"
+#include <cstdio>
+using namespace Foam;
+// three time steps of fvc::ddt(T) (twice per step) and fvc::ddtCorr(U, phi) through fv::CrankNicolsonDdtScheme; every double printed as %a
+static std::vector<double> field(int s, int n, int salt) { std::vector<double> v(n); for (int i = 0; i < n; ++i) v[i] = ((i * 7 + s * 13 + salt) % 11) / 8.0 - 0.5 + s * 0.125; return v; }
+static void print(const char* tag, int s, const scalargpuField& f) { std::printf("%s %d", tag, s); for (double x : f.asHost()) std::printf(" %a", x); std::printf("\n"); }
+int main()
+{
+    try {
+        const int n = 7; const double oc = 0.9, dts[3] = {0.01, 0.004, 0.008};
+        fv::CrankNicolsonDdtScheme cn = fv::CrankNicolsonDdtScheme::New("CrankNicolson 0.9");
+        labelList lo(n - 1), up(n - 1); for (int i = 0; i < n - 1; ++i) { lo[i] = i; up[i] = i + 1; }
+        lduAddressing addr(n, lo, up);
+        scalargpuField w(field(0, n - 1, 3)), phiOld(field(1, n - 1, 5)), out(n), again(n), corr(n - 1), corrE(n - 1);
+        vectorgpuField Sf(n - 1), Uold(n);
+        for (int d = 0; d < 3; ++d) { Sf.component(d) = field(2, n - 1, d); Uold.component(d) = field(3, n, d); }
+        const word name = fv::CrankNicolsonDdtScheme::ddt0Name("T");
+        for (int s = 1; s <= 3; ++s) {
+            cn.setTime(s, dts[s - 1], s > 1 ? dts[s - 2] : dts[0]);
+            const scalargpuField vf(field(s, n, 0)), vf0(field(s - 1, n, 0)), vf00(field(s > 1 ? s - 2 : 0, n, 0));
+            fvc::ddt(out, cn, name, vf, vf0, vf00);
+            print("ddt", s, out); print("ddt0", s, cn.ddt0(name));
+            fvc::ddt(again, cn, name, vf, vf0, vf00);                       // the same time step: ddt0 is not updated again
+            print("again", s, again); print("ddt0again", s, cn.ddt0(name));
+            const word nameU = fv::CrankNicolsonDdtScheme::ddt0Name("U");
+            std::printf("rDtCoef %d %a\n", s, cn.rDtCoef(nameU, n, 3));
+            fvc::ddtCorr(corr, addr, cn, nameU, w, Sf, Uold, phiOld);
+            fvc::ddtCorr(corrE, addr, (s > 1 ? 1.0 + oc : 1.0) / dts[s - 1], w, Sf, Uold, phiOld);   // Euler's call with rDtCoef
+            std::printf("ddtCorr %d %d\n", s, (int)(corr.asHost() == corrE.asHost()));
+            for (direction d = 0; d < 3; ++d) for (double x : cn.ddt0(nameU, d).asHost()) if (x != 0.0) std::printf("ddt0(U) touched\n");
+        }
+        const scalargpuField a(field(1, n, 0)); const scalargpuField* p[1] = {&a};
+        for (int bad : {0, 5}) { try { cn.evaluate("ddt0(X)", 1.0, p, p, bad); std::printf("accepted %d\n", bad); } catch (const error&) { std::printf("refused %d\n", bad); } }
+    } catch (const std::exception& e) { std::printf("FAILED %s\n", e.what()); return 1; }
+    return 0;
+}
+'''
+
+
+@pytest.mark.gpu
+def test_mirror_fvc_ddt_and_ddt_corr_through_the_scheme_object(pkg, tmp_path):
+    """the mirror's fv::CrankNicolsonDdtScheme from a small program of its own: fvc::ddt over three steps with changing step sizes against
+    the restatement bit for bit, twice per step (one update per step); fvc::ddtCorr is Euler's call with rDtCoef of ddt0(U), which it neither
+    reads nor updates; a component count outside 1..4 is refused"""
+    from test_polymesh import PKG
+    src, exe = tmp_path / "cn.C", tmp_path / "cn"
+    src.write_text(MIRROR_PROGRAM)
+    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(PKG, "foam"), "-I", os.path.join(os.path.dirname(PKG), "include"), str(src), "-o", str(exe),
+                    "-L" + PKG, "-lmiFoam", "-lrapidcfd_amd", "-Wl,-rpath," + PKG], check=True, capture_output=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "FAILED" not in out.stdout, out.stdout + out.stderr
+    got = {}
+    for line in out.stdout.splitlines():
+        w = line.split()
+        if w[0] in ("ddt", "ddt0", "again", "ddt0again", "rDtCoef"):
+            got[(w[0], int(w[1]))] = np.array([float.fromhex(x) for x in w[2:]])
+    n, oc, dts = 7, 0.9, [0.01, 0.004, 0.008]
+    field = lambda s: np.array([((i * 7 + s * 13) % 11) / 8.0 - 0.5 + s * 0.125 for i in range(n)])
+    st, d0 = State(oc, 1), np.zeros(n)
+    for s in (1, 2, 3):
+        rdt, rdt0, evaluate = st.step(s, dts[s - 1], dts[s - 2] if s > 1 else dts[0])
+        if evaluate:
+            d0 = ddt0_update(rdt0, oc, field(s - 1), field(s - 2 if s > 1 else 0), d0)
+        want = fvc_ddt(rdt, oc, field(s), field(s - 1), d0)
+        for a, b in (("ddt", "ddt0"), ("again", "ddt0again")):
+            assert np.array_equal(got[(a, s)], want) and np.array_equal(got[(b, s)], d0), (a, s)
+        assert got[("rDtCoef", s)][0] == rdt, s
+        assert f"ddtCorr {s} 1" in out.stdout, out.stdout
+    assert np.any(d0 != 0.0) and "touched" not in out.stdout
+    assert "refused 0" in out.stdout and "refused 5" in out.stdout and "accepted" not in out.stdout
