@@ -1415,6 +1415,15 @@ int row_launch(mi_addr_s* a, const mi_addr_s::RowPlan& rp, K kernel, const A& ar
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
+// the block size of the row plan and the form of the row tables (16-bit row16 / losort16 or the 32-bit ones) pick a kernel instantiation:
+// f(RowShape<BS, R16>{}) launches it
+template <int BS, bool R16> struct RowShape { static constexpr int bs = BS; static constexpr bool r16 = R16; };
+template <class F>
+int for_row_shape(const mi_addr_s* a, const mi_addr_s::RowPlan& rp, F f)
+{
+    if (a->row16.n > 0) return rp.bs == 256 ? f(RowShape<256, true>{}) : rp.bs == 512 ? f(RowShape<512, true>{}) : f(RowShape<1024, true>{});
+    return rp.bs == 256 ? f(RowShape<256, false>{}) : rp.bs == 512 ? f(RowShape<512, false>{}) : f(RowShape<1024, false>{});
+}
 template <int KIND, int OM, int NM>
 int row_pass(mi_addr_s* a, RowPassArgs ra)
 {
@@ -1426,14 +1435,7 @@ int row_pass(mi_addr_s* a, RowPassArgs ra)
     ra.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
     ra.n = a->L.nCells; ra.cap = row_cap(rp, arrays); ra.xcd = a->ctx->xcdRows;
     const size_t lds = (size_t)arrays * ra.cap * sizeof(double);
-    if (a->row16.n > 0) {
-        if (rp.bs == 256) return row_launch(a, rp, k_row_pass<KIND, OM, NM, 256, true>, ra, lds);
-        if (rp.bs == 512) return row_launch(a, rp, k_row_pass<KIND, OM, NM, 512, true>, ra, lds);
-        return row_launch(a, rp, k_row_pass<KIND, OM, NM, 1024, true>, ra, lds);
-    }
-    if (rp.bs == 256) return row_launch(a, rp, k_row_pass<KIND, OM, NM, 256, false>, ra, lds);
-    if (rp.bs == 512) return row_launch(a, rp, k_row_pass<KIND, OM, NM, 512, false>, ra, lds);
-    return row_launch(a, rp, k_row_pass<KIND, OM, NM, 1024, false>, ra, lds);
+    return for_row_shape(a, rp, [&](auto s) { return row_launch(a, rp, k_row_pass<KIND, OM, NM, decltype(s)::bs, decltype(s)::r16>, ra, lds); });
 }
 template <int OM, int NM>
 int row_sum(mi_addr_s* a, const double* ownArr, const double* neiArr, const double* init, const double* vol, double* out)
@@ -1574,20 +1576,23 @@ extern "C" int mi_lust_weights(mi_ctx_t c, int64_t n_faces, const double* cd_wei
 }
 
 // [fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- explicit terms] in one row pass (k_row_assemble)
+namespace {
+// the time form of one assembly: Euler (or no time derivative), or the inputs of backward / CrankNicolson as their entry read them
+struct TimeForm { int form; BackIn bw; CnIn cn; };
+struct AsmOut { double *lower, *upper, *diag; double* const* source; double* sumMag; };
+int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const TimeForm& tf, const mi_div_correction* corr, const AsmOut& o);
+int n_rhs_held(const mi_fvm_terms* t) { return std::min(std::max(t->n_rhs, 0), 4); } // assemble_impl refuses a count outside 0..4
+}
 extern "C" int mi_fvm_assemble(mi_addr_t a, const mi_fvm_terms* t, double* lower_out_dev, double* upper_out_dev, double* diag_out_dev,
                                double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
 {
     return mi_fvm_assemble_corrected(a, t, nullptr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
 }
-namespace {
-int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_ddt_cn_terms* cn, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
-                  double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev);
-}
 // ... with the explicit correction of linearUpwind / LUST in the div term (CORR)
 extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
                                          double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
 {
-    return assemble_impl(a, t, nullptr, nullptr, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+    return assemble_impl(a, t, TimeForm{TF_EULER, {}, {}}, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
 }
 // ... with the backward time derivative in place of Euler's (BACK), with or without the correction
 extern "C" int mi_fvm_assemble_backward(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev,
@@ -1597,7 +1602,9 @@ extern "C" int mi_fvm_assemble_backward(mi_addr_t a, const mi_fvm_terms* t, cons
     if (!t->ddt) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: terms->ddt is 0 (no time derivative: mi_fvm_assemble)");
     if ((bw->rho_old_old_dev != nullptr) != (t->rho_dev != nullptr)) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: rho, rho_old and rho_old_old go together");
     if (t->n_rhs > 0 && !bw->psi_old_old_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: old-old fields missing");
-    return assemble_impl(a, t, bw, nullptr, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+    TimeForm tf{TF_BACK, {bw->coefft * t->r_delta_t, bw->coefft0, bw->coefft00, bw->rho_old_old_dev, {}}, {}};
+    for (int r = 0; r < n_rhs_held(t); ++r) tf.bw.psiOldOld[r] = bw->psi_old_old_dev[r];
+    return assemble_impl(a, t, tf, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
 }
 // ... with the CrankNicolson time derivative (CN), with or without the correction: terms->r_delta_t carries rDtCoef
 extern "C" int mi_fvm_assemble_cn(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_cn_terms* cn, const mi_div_correction* corr, double* lower_out_dev,
@@ -1607,28 +1614,64 @@ extern "C" int mi_fvm_assemble_cn(mi_addr_t a, const mi_fvm_terms* t, const mi_d
     if (!t->ddt) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: terms->ddt is 0 (no time derivative: mi_fvm_assemble)");
     if (!(cn->oc >= 0.0 && cn->oc <= 1.0)) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: the off-centring coefficient should be >= 0 and <= 1");
     if (t->n_rhs > 0 && !cn->ddt0_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: ddt0 fields missing");
-    return assemble_impl(a, t, nullptr, cn, corr, lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev);
+    TimeForm tf{TF_CN, {}, {cn->oc, cn->oc < 1.0 ? 1 : 0, {}}};
+    for (int r = 0; r < n_rhs_held(t); ++r) tf.cn.ddt0[r] = cn->ddt0_dev[r];
+    return assemble_impl(a, t, tf, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
 }
 namespace {
-int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_ddt_cn_terms* cn, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
-                  double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
+// the argument block of one kernel variant, built once as that variant's own type, and its launch; everything was checked by assemble_impl
+template <bool DIV, bool LAP, bool CORR, int TF>
+int asm_launch(mi_addr_s* a, const mi_fvm_terms* t, const TimeForm& tf, const CorrIn& corr, const AsmOut& o)
 {
-    if (!a || !t || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: bad argument");
+    typename AsmSel<CORR, TF>::type ra{};
+    ra.flux = t->div_flux_dev; ra.w = t->div_weights_dev; ra.delta = t->lap_delta_coeffs_dev; ra.gam = t->lap_gamma_magsf_dev;
+    ra.lowerOut = o.lower; ra.upperOut = o.upper; ra.diagOut = o.diag; ra.sumMagOut = o.sumMag;
+    ra.ddt = t->ddt ? 1 : 0; ra.rdt = t->r_delta_t; ra.rhoValue = t->rho_value; ra.rho = t->rho_dev; ra.rhoOld = t->rho_old_dev; ra.vol = t->vol_dev;
+    ra.sp = t->sp_dev; ra.spMinus = t->sp_sign < 0 ? 1 : 0;
+    ra.nRhs = t->n_rhs; ra.nSu = t->n_su;
+    for (int r = 0; r < t->n_rhs; ++r) { ra.psiOld[r] = t->ddt ? t->psi_old_dev[r] : nullptr; ra.sourceOut[r] = o.source[r]; }
+    for (int k = 0; k < t->n_su; ++k) ra.suMinus[k] = t->su_sign[k] < 0 ? 1 : 0;
+    for (int j = 0; j < t->n_su * t->n_rhs; ++j) ra.su[j] = t->su_dev[j];
+    if constexpr (CORR) { ra.lo = a->lowerAddr.p; ra.up = a->upperAddr.p; ra.corr = corr; }
+    if constexpr (TF == TF_BACK) ra.bw = tf.bw;
+    if constexpr (TF == TF_CN) ra.cn = tf.cn;
+    ra.os = a->ownerStartC.p; ra.ls = a->losortStartC.p; ra.losort = a->losortC.p;
+    ra.row16 = a->row16.p; ra.losort16 = a->losort16.p; ra.esc = a->rowEsc.p; ra.escStart = a->rowEscStart.p;
+    const mi_addr_s::RowPlan& rp = a->rowPlan[0];
+    ra.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
+    const int arrays = (DIV ? 2 : 0) + (LAP ? 1 : 0) + (CORR ? t->n_rhs : 0);
+    ra.n = a->L.nCells; ra.cap = row_cap(rp, arrays); ra.xcd = a->ctx->xcdRows;
+    const size_t lds = (size_t)arrays * ra.cap * sizeof(double);
+    return for_row_shape(a, rp, [&](auto s) { return row_launch(a, rp, k_row_assemble<DIV, LAP, decltype(s)::bs, decltype(s)::r16, CORR, TF>, ra, lds); });
+}
+// the five (DIV, LAP, CORR) cases of one time form
+template <int TF>
+int asm_launch_tf(bool DIV, bool LAP, bool CORR, mi_addr_s* a, const mi_fvm_terms* t, const TimeForm& tf, const CorrIn& corr, const AsmOut& o)
+{
+    if (CORR && LAP) return asm_launch<true, true, true, TF>(a, t, tf, corr, o);
+    if (CORR) return asm_launch<true, false, true, TF>(a, t, tf, corr, o);
+    if (DIV && LAP) return asm_launch<true, true, false, TF>(a, t, tf, corr, o);
+    if (DIV) return asm_launch<true, false, false, TF>(a, t, tf, corr, o);
+    return asm_launch<false, true, false, TF>(a, t, tf, corr, o);
+}
+int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const TimeForm& tf, const mi_div_correction* corr, const AsmOut& o)
+{
+    if (!a || !t || !o.diag) return fail(MI_ERR_ARG, "mi_fvm_assemble: bad argument");
     const bool DIV = t->div_flux_dev != nullptr, LAP = t->lap_delta_coeffs_dev != nullptr;
     if (LAP && !t->lap_gamma_magsf_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: laplacian needs deltaCoeffs and gammaMagSf");
     if (!DIV && !LAP) return fail(MI_ERR_ARG, "mi_fvm_assemble: no face term (use mi_fvm_ddt_euler* for a diagonal matrix)");
-    if (!upper_out_dev || (DIV && !lower_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_assemble: coefficient outputs missing (a convection term makes the matrix asymmetric)");
+    if (!o.upper || (DIV && !o.lower)) return fail(MI_ERR_ARG, "mi_fvm_assemble: coefficient outputs missing (a convection term makes the matrix asymmetric)");
     if (t->n_rhs < 0 || t->n_rhs > 4 || t->n_su < 0 || t->n_su > 4) return fail(MI_ERR_ARG, "mi_fvm_assemble: at most 4 right-hand sides and 4 explicit terms");
     if ((t->ddt || t->sp_dev || t->n_su > 0) && !t->vol_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: cell volumes needed");
     if (t->ddt && ((t->rho_dev != nullptr) != (t->rho_old_dev != nullptr))) return fail(MI_ERR_ARG, "mi_fvm_assemble: rho and rho_old go together");
-    if (t->n_rhs > 0 && (!source_out_dev || (t->ddt && !t->psi_old_dev))) return fail(MI_ERR_ARG, "mi_fvm_assemble: source outputs / old fields missing");
+    if (t->n_rhs > 0 && (!o.source || (t->ddt && !t->psi_old_dev))) return fail(MI_ERR_ARG, "mi_fvm_assemble: source outputs / old fields missing");
     if (t->n_su > 0 && (!t->su_dev || !t->su_sign || t->n_rhs == 0)) return fail(MI_ERR_ARG, "mi_fvm_assemble: explicit terms need su_dev, su_sign and a right-hand side");
     const double* faceIn[4] = {t->div_flux_dev, t->div_weights_dev, t->lap_delta_coeffs_dev, t->lap_gamma_magsf_dev};
     for (const double* q : faceIn) {
         if (q && !al16(q)) return fail(MI_ERR_ARG, "mi_fvm_assemble: face fields must be 16-byte aligned");
-        if (q && (q == upper_out_dev || q == lower_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_assemble: a coefficient output must not alias an input (cut faces are recomputed from the inputs)");
+        if (q && (q == o.upper || q == o.lower)) return fail(MI_ERR_ARG, "mi_fvm_assemble: a coefficient output must not alias an input (cut faces are recomputed from the inputs)");
     }
-    if (lower_out_dev && lower_out_dev == upper_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: lower_out and upper_out must differ");
+    if (o.lower && o.lower == o.upper) return fail(MI_ERR_ARG, "mi_fvm_assemble: lower_out and upper_out must differ");
     const bool CORR = corr != nullptr;
     if (CORR) {
         const char* who = "mi_fvm_assemble_corrected";
@@ -1641,88 +1684,30 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw,
     }
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    AsmCorrBackArgs ra{};
-    CnIn ci{};
+    CorrIn ci{};
     if (CORR) {
-        const double* outs[8] = {lower_out_dev, upper_out_dev, diag_out_dev, sum_mag_off_diag_out_dev};
-        for (int r = 0; r < t->n_rhs; ++r) outs[4 + r] = source_out_dev[r];
-        MICHK(corr_in("mi_fvm_assemble_corrected", corr, t->n_rhs, ra.corr, outs, 4 + t->n_rhs));
-        ra.lo = a->lowerAddr.p; ra.up = a->upperAddr.p;
+        const double* outs[8] = {o.lower, o.upper, o.diag, o.sumMag};
+        for (int r = 0; r < t->n_rhs; ++r) outs[4 + r] = o.source[r];
+        MICHK(corr_in("mi_fvm_assemble_corrected", corr, t->n_rhs, ci, outs, 4 + t->n_rhs));
     }
     if (a->L.nCells == 0) return MI_OK;
-    ra.flux = t->div_flux_dev; ra.w = t->div_weights_dev; ra.delta = t->lap_delta_coeffs_dev; ra.gam = t->lap_gamma_magsf_dev;
-    ra.lowerOut = lower_out_dev; ra.upperOut = upper_out_dev; ra.diagOut = diag_out_dev; ra.sumMagOut = sum_mag_off_diag_out_dev;
-    ra.ddt = t->ddt ? 1 : 0; ra.rdt = t->r_delta_t; ra.rhoValue = t->rho_value; ra.rho = t->rho_dev; ra.rhoOld = t->rho_old_dev; ra.vol = t->vol_dev;
-    ra.sp = t->sp_dev; ra.spMinus = t->sp_sign < 0 ? 1 : 0;
-    ra.nRhs = t->n_rhs; ra.nSu = t->n_su;
-    for (int r = 0; r < t->n_rhs; ++r) {
-        ra.psiOld[r] = t->ddt ? t->psi_old_dev[r] : nullptr; ra.sourceOut[r] = source_out_dev[r];
-        if (!ra.sourceOut[r] || (t->ddt && !ra.psiOld[r])) return fail(MI_ERR_ARG, "mi_fvm_assemble: null right-hand side array");
-    }
-    const bool BACK = bw != nullptr;
-    if (BACK) {
-        ra.bw.cA = bw->coefft * t->r_delta_t; ra.bw.c0 = bw->coefft0; ra.bw.c00 = bw->coefft00; ra.bw.rhoOldOld = bw->rho_old_old_dev;
+    for (int r = 0; r < t->n_rhs; ++r)
+        if (!o.source[r] || (t->ddt && !t->psi_old_dev[r])) return fail(MI_ERR_ARG, "mi_fvm_assemble: null right-hand side array");
+    if (tf.form == TF_BACK)
+        for (int r = 0; r < t->n_rhs; ++r)
+            if (!tf.bw.psiOldOld[r]) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: null old-old field");
+    if (tf.form == TF_CN)
         for (int r = 0; r < t->n_rhs; ++r) {
-            ra.bw.psiOldOld[r] = bw->psi_old_old_dev[r];
-            if (!ra.bw.psiOldOld[r]) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: null old-old field");
-        }
-    }
-    const bool CN = cn != nullptr;
-    if (CN) {
-        ci.oc = cn->oc; ci.offc = cn->oc < 1.0 ? 1 : 0;
-        for (int r = 0; r < t->n_rhs; ++r) {
-            const double* d = ci.ddt0[r] = cn->ddt0_dev[r];
+            const double* d = tf.cn.ddt0[r];
             if (!d) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: null ddt0 field");
-            if (d == lower_out_dev || d == upper_out_dev || d == diag_out_dev || d == sum_mag_off_diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: a ddt0 field must not be an output");
-            for (int q = 0; q < t->n_rhs; ++q) if (d == source_out_dev[q]) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: a ddt0 field must not be an output");
+            if (d == o.lower || d == o.upper || d == o.diag || d == o.sumMag) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: a ddt0 field must not be an output");
+            for (int q = 0; q < t->n_rhs; ++q) if (d == o.source[q]) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: a ddt0 field must not be an output");
         }
-    }
-    for (int k = 0; k < t->n_su; ++k) {
-        ra.suMinus[k] = t->su_sign[k] < 0 ? 1 : 0;
-        for (int r = 0; r < t->n_rhs; ++r) { ra.su[k * t->n_rhs + r] = t->su_dev[k * t->n_rhs + r]; if (!ra.su[k * t->n_rhs + r]) return fail(MI_ERR_ARG, "mi_fvm_assemble: null explicit term"); }
-    }
-    ra.os = a->ownerStartC.p; ra.ls = a->losortStartC.p; ra.losort = a->losortC.p;
-    ra.row16 = a->row16.p; ra.losort16 = a->losort16.p; ra.esc = a->rowEsc.p; ra.escStart = a->rowEscStart.p;
-    const mi_addr_s::RowPlan& rp = a->rowPlan[0];
-    ra.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
-    const int arrays = (DIV ? 2 : 0) + (LAP ? 1 : 0) + (CORR ? t->n_rhs : 0);
-    ra.n = a->L.nCells; ra.cap = row_cap(rp, arrays); ra.xcd = a->ctx->xcdRows;
-    const size_t lds = (size_t)arrays * ra.cap * sizeof(double);
-    const bool r16 = a->row16.n > 0;
-    const AsmCorrArgs& rc = ra;                    // every kernel takes the arguments of its own variant only
-    const AsmArgs& rb = ra;
-    AsmBackArgs rk{}; static_cast<AsmArgs&>(rk) = rb; rk.bw = ra.bw;
-    AsmCnArgs rn{}; static_cast<AsmArgs&>(rn) = rb; rn.cn = ci;
-    AsmCorrCnArgs rcn{}; static_cast<AsmCorrArgs&>(rcn) = rc; rcn.cn = ci;
-#define MI_ASM_LAUNCH(D, L, K, B, ARGS)                                                                                          \
-    do {                                                                                                                           \
-        if (r16) { if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, true, K, B>, ARGS, lds);                  \
-                   if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, true, K, B>, ARGS, lds);                  \
-                   return row_launch(a, rp, k_row_assemble<D, L, 1024, true, K, B>, ARGS, lds); }                                 \
-        if (rp.bs == 256) return row_launch(a, rp, k_row_assemble<D, L, 256, false, K, B>, ARGS, lds);                            \
-        if (rp.bs == 512) return row_launch(a, rp, k_row_assemble<D, L, 512, false, K, B>, ARGS, lds);                            \
-        return row_launch(a, rp, k_row_assemble<D, L, 1024, false, K, B>, ARGS, lds);                                             \
-    } while (0)
-    if (BACK) {
-        if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, TF_BACK, ra);
-        if (CORR) MI_ASM_LAUNCH(true, false, true, TF_BACK, ra);
-        if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, TF_BACK, rk);
-        if (DIV) MI_ASM_LAUNCH(true, false, false, TF_BACK, rk);
-        MI_ASM_LAUNCH(false, true, false, TF_BACK, rk);
-    }
-    if (CN) {
-        if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, TF_CN, rcn);
-        if (CORR) MI_ASM_LAUNCH(true, false, true, TF_CN, rcn);
-        if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, TF_CN, rn);
-        if (DIV) MI_ASM_LAUNCH(true, false, false, TF_CN, rn);
-        MI_ASM_LAUNCH(false, true, false, TF_CN, rn);
-    }
-    if (CORR && LAP) MI_ASM_LAUNCH(true, true, true, TF_EULER, rc);
-    if (CORR) MI_ASM_LAUNCH(true, false, true, TF_EULER, rc);
-    if (DIV && LAP) MI_ASM_LAUNCH(true, true, false, TF_EULER, rb);
-    if (DIV) MI_ASM_LAUNCH(true, false, false, TF_EULER, rb);
-    MI_ASM_LAUNCH(false, true, false, TF_EULER, rb);
-#undef MI_ASM_LAUNCH
+    for (int j = 0; j < t->n_su * t->n_rhs; ++j)
+        if (!t->su_dev[j]) return fail(MI_ERR_ARG, "mi_fvm_assemble: null explicit term");
+    if (tf.form == TF_BACK) return asm_launch_tf<TF_BACK>(DIV, LAP, CORR, a, t, tf, ci, o);
+    if (tf.form == TF_CN) return asm_launch_tf<TF_CN>(DIV, LAP, CORR, a, t, tf, ci, o);
+    return asm_launch_tf<TF_EULER>(DIV, LAP, CORR, a, t, tf, ci, o);
 }
 } // namespace
 

@@ -1318,23 +1318,18 @@ class Assembly:
             b.oc = float(cn["oc"])
             d0 = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in cn["ddt0"]]); keep.append(d0)
             b.ddt0_dev = C.cast(d0, C.POINTER(C.c_void_p))
-            k = None if corr is None else div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))
-            _chk(lib().mi_fvm_assemble_cn(self.addr.h, C.byref(t), C.byref(b), None if k is None else C.byref(k), _ptr(lower_out), _ptr(upper_out),
-                                          _ptr(diag_out), so, _ptr(sum_mag_out)))
+            entry, form = lib().mi_fvm_assemble_cn, (C.byref(b),)
         elif back is not None:
             b = DdtBackward()
             b.coefft, b.coefft0, b.coefft00 = [float(x) for x in back["coeffs"]]
             b.rho_old_old_dev = _ptr(back.get("rho_old_old")).value
             poo = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in back["psi_old_old"]]); keep.append(poo)
             b.psi_old_old_dev = C.cast(poo, C.POINTER(C.c_void_p))
-            k = None if corr is None else div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))
-            _chk(lib().mi_fvm_assemble_backward(self.addr.h, C.byref(t), C.byref(b), None if k is None else C.byref(k), _ptr(lower_out), _ptr(upper_out),
-                                                _ptr(diag_out), so, _ptr(sum_mag_out)))
-        elif corr is None:
-            _chk(lib().mi_fvm_assemble(self.addr.h, C.byref(t), _ptr(lower_out), _ptr(upper_out), _ptr(diag_out), so, _ptr(sum_mag_out)))
+            entry, form = lib().mi_fvm_assemble_backward, (C.byref(b),)
         else:
-            k = div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))
-            _chk(lib().mi_fvm_assemble_corrected(self.addr.h, C.byref(t), C.byref(k), _ptr(lower_out), _ptr(upper_out), _ptr(diag_out), so, _ptr(sum_mag_out)))
+            entry, form = lib().mi_fvm_assemble_corrected, ()      # without a correction: mi_fvm_assemble
+        k = None if corr is None else div_correction(corr["cf"], corr["c"], corr["grad"], corr.get("scale", 1.0))
+        _chk(entry(self.addr.h, C.byref(t), *form, None if k is None else C.byref(k), _ptr(lower_out), _ptr(upper_out), _ptr(diag_out), so, _ptr(sum_mag_out)))
 
     def fvc_div(self, face_flux, weights, vf, vol, face_out, div_out):
         """fvc::div(faceFlux, vf) (gaussConvectionScheme.C:117-140); weights None: upwind"""

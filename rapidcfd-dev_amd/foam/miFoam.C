@@ -632,17 +632,67 @@ void fvVectorMatrix::H(vectorgpuField& Hphi, const vectorgpuField& psi, const sc
     addBoundarySource(Hphi);
     for (direction d = 0; d < 3; ++d) miCheck(mi_vec_div(ctx, Hphi.size(), Hphi.component(d).data(), V.data(), Hphi.component(d).data()), "fvMatrix::H");
 }
+namespace {
+mi_div_correction divCorrection(const linearUpwindCorrection& corr, std::size_t nRhs)
+{
+    if (!corr.Cf || !corr.C || corr.grad.size() != nRhs) FatalErrorIn("linearUpwind::correction", "one gradient per component of the field is needed");
+    mi_div_correction k{};
+    k.scale = corr.scale;
+    for (int d = 0; d < 3; ++d) { k.cf_dev[d] = corr.Cf->component(d).data(); k.c_dev[d] = corr.C->component(d).data(); }
+    for (std::size_t r = 0; r < nRhs; ++r) {
+        if (!corr.grad[r]) FatalErrorIn("linearUpwind::correction", "null gradient");
+        for (int d = 0; d < 3; ++d) k.grad_dev[3 * r + d] = corr.grad[r]->component(d).data();
+    }
+    return k;
+}
+// the time form of one fvm::assemble: rDeltaT is Euler's and backward's 1/deltaT or CrankNicolson's rDtCoef; fields: backward's old-old fields /
+// CrankNicolson's ddt0 fields, one per right-hand side
+struct ddtForm
+{
+    enum { Euler, backward, CrankNicolson } kind;
+    scalar rDeltaT;
+    const backwardDdtCoeffs* bd;
+    scalar ocCoeff;
+    const scalargpuField* const* fields;
+};
+// the worker of every fvm::assemble: the terms, the time form's part and the optional correction, then the one matching C entry (corr / su nullptr: none)
+void assembleTerms(const char* where, lduMatrix& M, scalargpuField* const* sources, const ddtForm& f, scalar rho, const scalargpuField& V,
+                   const scalargpuField* const* psiOld, int nRhs, const scalargpuField* faceFlux, const scalargpuField* weights, const scalargpuField* deltaCoeffs,
+                   const scalargpuField* gammaMagSf, const linearUpwindCorrection* corr, const scalargpuField* su)
+{
+    mi_fvm_terms t{};
+    t.ddt = 1; t.r_delta_t = f.rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
+    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
+    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
+    const double *po[3], *tf[3]; double* so[3];
+    for (int r = 0; r < nRhs; ++r) { po[r] = psiOld[r]->data(); so[r] = sources[r]->data(); if (f.kind != ddtForm::Euler) tf[r] = f.fields[r]->data(); }
+    t.n_rhs = nRhs; t.psi_old_dev = po;
+    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
+    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
+    mi_div_correction k{};
+    if (corr) k = divCorrection(*corr, (std::size_t)nRhs);
+    const mi_div_correction* kp = corr ? &k : nullptr;
+    const mi_addr_t a = M.lduAddr().handle();
+    double *lower = faceFlux ? M.lower().data() : nullptr, *upper = M.upper().data(), *diag = M.diag().data();
+    if (f.kind == ddtForm::backward) {
+        mi_ddt_backward b{};
+        b.coefft = f.bd->coefft; b.coefft0 = f.bd->coefft0; b.coefft00 = f.bd->coefft00; b.psi_old_old_dev = tf;
+        miCheck(mi_fvm_assemble_backward(a, &t, &b, kp, lower, upper, diag, so, nullptr), where);
+    } else if (f.kind == ddtForm::CrankNicolson) {
+        mi_ddt_cn_terms c{};
+        c.oc = f.ocCoeff; c.ddt0_dev = tf;
+        miCheck(mi_fvm_assemble_cn(a, &t, &c, kp, lower, upper, diag, so, nullptr), where);
+    } else if (corr)
+        miCheck(mi_fvm_assemble_corrected(a, &t, kp, lower, upper, diag, so, nullptr), where);
+    else
+        miCheck(mi_fvm_assemble(a, &t, lower, upper, diag, so, nullptr), where);
+}
+ddtForm EulerForm(scalar rDeltaT) { return {ddtForm::Euler, rDeltaT, nullptr, 0, nullptr}; }
+}
 void fvm::assemble(fvVectorMatrix& M, scalar rDeltaT, scalar rho, const scalargpuField& V, const vectorgpuField& psiOld, const scalargpuField* faceFlux,
                    const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf)
 {
-    mi_fvm_terms t{};
-    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
-    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
-    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
-    const double* po[3] = {psiOld.component(0).data(), psiOld.component(1).data(), psiOld.component(2).data()};
-    t.n_rhs = 3; t.psi_old_dev = po;
-    double* so[3] = {M.source().component(0).data(), M.source().component(1).data(), M.source().component(2).data()};
-    miCheck(mi_fvm_assemble(M.lduAddr().handle(), &t, faceFlux ? M.lower().data() : nullptr, M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble");
+    assembleTerms("fvm::assemble", M, cmpts(M.source()), EulerForm(rDeltaT), rho, V, cmpts(psiOld), 3, faceFlux, weights, deltaCoeffs, gammaMagSf, nullptr, nullptr);
 }
 void fvm::laplacian(fvScalarMatrix& M, const scalargpuField& deltaCoeffs, const scalargpuField& gammaMagSf)
 {
@@ -770,57 +820,21 @@ void fvm::ddt(fvScalarMatrix& M, scalar rDeltaT, scalar rho, const scalargpuFiel
 void fvm::assemble(fvScalarMatrix& M, scalar rDeltaT, scalar rho, const scalargpuField& V, const scalargpuField& psiOld, const scalargpuField* faceFlux,
                    const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const scalargpuField* su)
 {
-    mi_fvm_terms t{};
-    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
-    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
-    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
-    const double* po[1] = {psiOld.data()}; t.n_rhs = 1; t.psi_old_dev = po;
-    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
-    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
-    double* so[1] = {M.source().data()};
-    miCheck(mi_fvm_assemble(M.lduAddr().handle(), &t, faceFlux ? M.lower().data() : nullptr, M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble");
-}
-namespace {
-mi_div_correction divCorrection(const linearUpwindCorrection& corr, std::size_t nRhs)
-{
-    if (!corr.Cf || !corr.C || corr.grad.size() != nRhs) FatalErrorIn("linearUpwind::correction", "one gradient per component of the field is needed");
-    mi_div_correction k{};
-    k.scale = corr.scale;
-    for (int d = 0; d < 3; ++d) { k.cf_dev[d] = corr.Cf->component(d).data(); k.c_dev[d] = corr.C->component(d).data(); }
-    for (std::size_t r = 0; r < nRhs; ++r) {
-        if (!corr.grad[r]) FatalErrorIn("linearUpwind::correction", "null gradient");
-        for (int d = 0; d < 3; ++d) k.grad_dev[3 * r + d] = corr.grad[r]->component(d).data();
-    }
-    return k;
-}
+    scalargpuField* so = &M.source(); const scalargpuField* po = &psiOld;
+    assembleTerms("fvm::assemble", M, &so, EulerForm(rDeltaT), rho, V, &po, 1, faceFlux, weights, deltaCoeffs, gammaMagSf, nullptr, su);
 }
 void fvm::assemble(fvScalarMatrix& M, scalar rDeltaT, scalar rho, const scalargpuField& V, const scalargpuField& psiOld, const scalargpuField& faceFlux,
                    const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const linearUpwindCorrection& corr,
                    const scalargpuField* su)
 {
-    mi_fvm_terms t{};
-    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
-    t.div_flux_dev = faceFlux.data(); t.div_weights_dev = weights ? weights->data() : nullptr;
-    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
-    const double* po[1] = {psiOld.data()}; t.n_rhs = 1; t.psi_old_dev = po;
-    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
-    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
-    double* so[1] = {M.source().data()};
-    const mi_div_correction k = divCorrection(corr, 1);
-    miCheck(mi_fvm_assemble_corrected(M.lduAddr().handle(), &t, &k, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble (corrected convection)");
+    scalargpuField* so = &M.source(); const scalargpuField* po = &psiOld;
+    assembleTerms("fvm::assemble (corrected convection)", M, &so, EulerForm(rDeltaT), rho, V, &po, 1, &faceFlux, weights, deltaCoeffs, gammaMagSf, &corr, su);
 }
 void fvm::assemble(fvVectorMatrix& M, scalar rDeltaT, scalar rho, const scalargpuField& V, const vectorgpuField& psiOld, const scalargpuField& faceFlux,
                    const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const linearUpwindCorrection& corr)
 {
-    mi_fvm_terms t{};
-    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
-    t.div_flux_dev = faceFlux.data(); t.div_weights_dev = weights ? weights->data() : nullptr;
-    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
-    const double* po[3] = {psiOld.component(0).data(), psiOld.component(1).data(), psiOld.component(2).data()};
-    t.n_rhs = 3; t.psi_old_dev = po;
-    double* so[3] = {M.source().component(0).data(), M.source().component(1).data(), M.source().component(2).data()};
-    const mi_div_correction k = divCorrection(corr, 3);
-    miCheck(mi_fvm_assemble_corrected(M.lduAddr().handle(), &t, &k, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "fvm::assemble (corrected convection)");
+    assembleTerms("fvm::assemble (corrected convection)", M, cmpts(M.source()), EulerForm(rDeltaT), rho, V, cmpts(psiOld), 3, &faceFlux, weights, deltaCoeffs,
+                  gammaMagSf, &corr, nullptr);
 }
 // ---- the backward time scheme ----
 backwardDdtCoeffs::backwardDdtCoeffs(scalar deltaT, scalar deltaT0, int nOldTimes) : rDeltaT(1.0 / deltaT)
@@ -837,21 +851,8 @@ void fvm::assembleBackward(lduMatrix& M, scalargpuField* const* sources, const b
                       const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const linearUpwindCorrection* corr,
                       const scalargpuField* su)
 {
-    mi_fvm_terms t{};
-    t.ddt = 1; t.r_delta_t = bd.rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
-    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
-    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
-    const double *po[3], *poo[3]; double* so[3];
-    for (int r = 0; r < nRhs; ++r) { po[r] = psiOld[r]->data(); poo[r] = psiOldOld[r]->data(); so[r] = sources[r]->data(); }
-    t.n_rhs = nRhs; t.psi_old_dev = po;
-    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
-    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
-    mi_ddt_backward b{};
-    b.coefft = bd.coefft; b.coefft0 = bd.coefft0; b.coefft00 = bd.coefft00; b.psi_old_old_dev = poo;
-    mi_div_correction k{};
-    if (corr) k = divCorrection(*corr, (std::size_t)nRhs);
-    miCheck(mi_fvm_assemble_backward(M.lduAddr().handle(), &t, &b, corr ? &k : nullptr, faceFlux ? M.lower().data() : nullptr, M.upper().data(), M.diag().data(),
-                                     so, nullptr), "fvm::assemble (backward)");
+    assembleTerms("fvm::assemble (backward)", M, sources, {ddtForm::backward, bd.rDeltaT, &bd, 0, psiOldOld}, rho, V, psiOld, nRhs, faceFlux, weights, deltaCoeffs,
+                  gammaMagSf, corr, su);
 }
 void fvm::ddt(fvScalarMatrix& M, const backwardDdtCoeffs& bd, scalar rho, const scalargpuField& V, const scalargpuField& psiOld, const scalargpuField& psiOldOld)
 {
@@ -933,21 +934,11 @@ void fv::CrankNicolsonDdtScheme::assemble(lduMatrix& M, scalargpuField* const* s
 {
     if (nRhs < 1 || nRhs > 3 || !sources) FatalErrorIn("fvm::assemble (CrankNicolson)", name + ": 1 to 3 right-hand sides, " + std::to_string(nRhs) + " given");
     for (int r = 0; r < nRhs; ++r) if (!sources[r]) FatalErrorIn("fvm::assemble (CrankNicolson)", name + ": a missing source field");
-    mi_fvm_terms t{};
-    t.ddt = 1; t.r_delta_t = evaluate(name, rho, psiOld, psiOldOld, nRhs); t.rho_value = rho; t.vol_dev = V.data();
-    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
-    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
-    const double *po[3], *d0[3]; double* so[3];
-    for (int r = 0; r < nRhs; ++r) { po[r] = psiOld[r]->data(); d0[r] = ddt0(name, r).data(); so[r] = sources[r]->data(); }
-    t.n_rhs = nRhs; t.psi_old_dev = po;
-    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
-    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
-    mi_ddt_cn_terms c{};
-    c.oc = ocCoeff_; c.ddt0_dev = d0;
-    mi_div_correction k{};
-    if (corr) k = divCorrection(*corr, (std::size_t)nRhs);
-    miCheck(mi_fvm_assemble_cn(M.lduAddr().handle(), &t, &c, corr ? &k : nullptr, faceFlux ? M.lower().data() : nullptr, M.upper().data(), M.diag().data(), so,
-                               nullptr), "fvm::assemble (CrankNicolson)");
+    const scalar rDtCoef = evaluate(name, rho, psiOld, psiOldOld, nRhs);
+    const scalargpuField* d0[3];
+    for (int r = 0; r < nRhs; ++r) d0[r] = &ddt0(name, r);
+    assembleTerms("fvm::assemble (CrankNicolson)", M, sources, {ddtForm::CrankNicolson, rDtCoef, nullptr, ocCoeff_, d0}, rho, V, psiOld, nRhs, faceFlux, weights,
+                  deltaCoeffs, gammaMagSf, corr, su);
 }
 void fvm::ddt(fvScalarMatrix& M, fv::CrankNicolsonDdtScheme& cn, const word& name, scalar rho, const scalargpuField& V, const scalargpuField& psiOld,
               const scalargpuField& psiOldOld)
@@ -979,7 +970,7 @@ void fvc::linearUpwindCorrectionFlux(scalargpuField& out, const lduAddressing& a
 void fvc::linearUpwindCorrectionFlux(vectorgpuField& out, const lduAddressing& a, const scalargpuField& faceFlux, const linearUpwindCorrection& corr)
 {
     const mi_div_correction k = divCorrection(corr, 3);
-    double* o[3] = {out.component(0).data(), out.component(1).data(), out.component(2).data()};
+    const auto o = cmptData(out);
     miCheck(mi_linear_upwind_correction(a.handle(), &k, 3, faceFlux.data(), o), "linearUpwind::correction");
 }
 void fvc::grad(vectorgpuField& g, const lduAddressing& a, const vectorgpuField& Sf, const scalargpuField& ssf, const scalargpuField& V)
@@ -1230,7 +1221,7 @@ void fvc::snGradLimitedCorrectionFlux(scalargpuField& flux, const lduAddressing&
 {
     if (!s.limited()) FatalErrorIn("fvc::snGradLimitedCorrectionFlux", "the scheme is not `limited`");
     const double* v[1] = {vf.data()};
-    const double* g[3] = {gradVf.component(0).data(), gradVf.component(1).data(), gradVf.component(2).data()};
+    const auto g = cmptData(gradVf);
     double* out[1] = {flux.data()};
     miCheck(mi_sngrad_limited_correction_flux(a.handle(), 1, s.limitCoeff(), corrVecs.component(0).data(), corrVecs.component(1).data(),
                                               corrVecs.component(2).data(), weights.data(), deltaCoeffs.data(), v, g, gammaMagSf.data(), out,
@@ -1256,8 +1247,8 @@ void fvc::gaussGradBoundary(vectorgpuField& gb, const fvPatchCells& p, const vec
                             const vectorgpuField& gradVf)
 {
     const double* sn[1] = {pSnGrad.data()};
-    const double* g[3] = {gradVf.component(0).data(), gradVf.component(1).data(), gradVf.component(2).data()};
-    double* out[3] = {gb.component(0).data(), gb.component(1).data(), gb.component(2).data()};
+    const auto g = cmptData(gradVf);
+    const auto out = cmptData(gb);
     miCheck(mi_patch_gauss_grad_correct(p.handle(), 1, pSf.component(0).data(), pSf.component(1).data(), pSf.component(2).data(), pMagSf.data(), sn, g, out),
             "gaussGrad::correctBoundaryConditions");
 }
@@ -1284,15 +1275,15 @@ void fvc::divDevTGrad(vectorgpuField& div, const lduAddressing& a, devKind kind,
     nine(gradU, g);
     vectorgpuField own(faceFlux ? 0 : weights.size());
     vectorgpuField& ff = faceFlux ? *faceFlux : own;
-    double* face[3] = {ff.component(0).data(), ff.component(1).data(), ff.component(2).data()};
-    double* sum[3] = {div.component(0).data(), div.component(1).data(), div.component(2).data()};
+    const auto face = cmptData(ff);
+    const auto sum = cmptData(div);
     miCheck(mi_fvc_div_dev_tgrad(a.handle(), kind, weights.data(), Sf.component(0).data(), Sf.component(1).data(), Sf.component(2).data(), visc.data(), g,
                                  nullptr, face, sum), "fvc::div(visc*dev(T(grad(U))))");
     for (const devTGradPatch& p : patches) {                    // the boundary faces, in patch order (fvcSurfaceIntegrate.C:58-72)
         const label np = p.cells->size();
         if (np == 0) continue;
         vectorgpuField pf(np);
-        double* out[3] = {pf.component(0).data(), pf.component(1).data(), pf.component(2).data()};
+        const auto out = cmptData(pf);
         const double *pg[9], *ng[9];
         if (p.weights) { nine(p.nbrGrad, ng); for (int i = 0; i < 9; ++i) pg[i] = g[i]; }
         else nine(p.grad, pg);
@@ -1327,12 +1318,12 @@ void fvc::limitedGrad(vectorgpuField& g, const lduAddressing& a, const fv::limit
                       const vectorgpuField& C, const vectorgpuField& Cf, const scalargpuField* bValue, const vectorgpuField* bCf, scalargpuField* limiter)
 {
     const double* v[1] = {vf.data()};
-    const double* c[3] = {C.component(0).data(), C.component(1).data(), C.component(2).data()};
-    const double* cf[3] = {Cf.component(0).data(), Cf.component(1).data(), Cf.component(2).data()};
+    const auto c = cmptData(C);
+    const auto cf = cmptData(Cf);
     const double* bv[1] = {bValue ? bValue->data() : nullptr};
     const double* bcf[3] = {nullptr, nullptr, nullptr};
     if (bCf) for (int d = 0; d < 3; ++d) bcf[d] = bCf->component(d).data();
-    double* gr[3] = {g.component(0).data(), g.component(1).data(), g.component(2).data()};
+    const auto gr = cmptData(g);
     double* lim[1] = {limiter ? limiter->data() : nullptr};
     miCheck(mi_limited_grad(a.handle(), &s.data(), b ? b->handle() : nullptr, 1, v, c, cf, bValue ? bv : nullptr, bCf ? bcf : nullptr, gr,
                             limiter ? lim : nullptr), "fvc::grad (limited)");

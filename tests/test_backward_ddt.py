@@ -379,65 +379,28 @@ def test_fused_backward_assembly_bit_for_bit(pkg, orc, monkeypatch, name, mode, 
 
 
 # ---- the statements of scalarTransportFoam walked with the restatement ----------------------------------------------------------------
+class BackwardDdt:
+    """the time scheme object of tests/transport_walk.py::walk: fvm::ddt(T) by the restatement; the old-old field is kept from step to step
+    (the first step: the old field, with GREAT as the previous step size)"""
+
+    def start_step(self, step, dts, Told):
+        self.Too = Told.copy() if step == 0 else self.Told
+        self.Told, self.rdt = Told, 1.0 / dts[step]
+        self.c = coeffs(dts[step], None if step == 0 else dts[step - 1])
+
+    def assemble(self, V, non_orth, rep):
+        return fvm_ddt(self.rdt, self.c, V, self.Told, self.Too)
+
+    def state(self):
+        return {}
+
+
 def walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, dts, scheme, corrected, n_non_orth, backward=True):
-    """tests/test_scalartransportfoam.py::oracle_scalar_transport with the ddt line replaced by the restatement (GREAT on the first step,
-    the previous step size afterwards) and one step size per step"""
-    from test_polymesh import geometry
-    syn = pkg.synthetic
-    G = geometry(pts, faces, owner, neighbour)
-    n, nI = int(owner.max()) + 1, len(neighbour)
-    lo, up = owner[:nI].astype(np.int32), neighbour.astype(np.int32)
-    V, lam, delta, magSf = G["V"], G["weights"], G["delta"], G["magSf"][:nI]
-    Sf = [np.ascontiguousarray(G["Sf"][:nI, k]) for k in range(3)]
-    nhat = G["Sf"][:nI] / magSf[:, None]
-    cv = nhat - (G["C"][up] - G["C"][lo]) * delta[:, None]
-    cv = [np.ascontiguousarray(cv[:, k]) for k in range(3)]
-    u0 = np.array([1.0, 0.2, 0.0])
-    U = [np.full(n, u0[k]) for k in range(3)]
-    phi = orc.flux_div(n, lo, up, lam, Sf, U, want_div=False)
-    P = []
-    for name, ptype, cnt, start in patches:
-        fc = owner[start:start + cnt].astype(np.int32)
-        sfb = G["Sf"][start:start + cnt]
-        ub = np.tile(u0, (cnt, 1)) if name in ("inlet", "outlet") else np.zeros((cnt, 3))
-        phib = ub[:, 0] * sfb[:, 0] + ub[:, 1] * sfb[:, 1] + ub[:, 2] * sfb[:, 2]
-        diff = DT * G["magSf"][start:start + cnt] * G["delta_b"][start - nI:start - nI + cnt]
-        fixed = name == "inlet"
-        tb = tin if fixed else None
-        P.append(dict(fc=fc, sf=[np.ascontiguousarray(sfb[:, k]) for k in range(3)], tb=tb,
-                      ic=diff if fixed else phib, bc=(diff * tb - phib * tb) if fixed else np.zeros(cnt)))
-
-    def grad(T):
-        g = orc.gauss_grad(n, lo, up, Sf, orc.face_interpolate(lo, up, lam, T), None)
-        for q in P:
-            for k in range(3):
-                g[k] = orc.patch_add_product(q["fc"], q["sf"][k], T[q["fc"]] if q["tb"] is None else q["tb"], g[k], 0)
-        return [x / V for x in g]
-
-    T = T0.copy()
-    Too = None
-    uL, dL = orc.fvm_laplacian(n, lo, up, delta, DT * magSf)
-    lines = []
-    for step, dt in enumerate(dts):
-        Told = T.copy()
-        if step == 0:
-            Too = Told.copy()
-        c = coeffs(dt, None if step == 0 else dts[step - 1])
-        for non_orth in range(n_non_orth + 1):
-            gT = grad(T) if corrected else None
-            w = orc.upwind_weights(phi) if scheme == "upwind" else lam
-            lB, uB, dB = orc.fvm_div(n, lo, up, w, phi)
-            dD, sD = fvm_ddt(1.0 / dt, c, V, Told, Too) if backward else orc.fvm_ddt_euler(1.0 / dt, 1.0, V, Told)
-            lower, upper, diag, source = lB - uL, uB - uL, (dD + dB) - dL, sD
-            if corrected:
-                cf = orc.sngrad_correction_flux(lo, up, cv, lam, gT, -(DT * magSf))
-                source = orc.submul(V, orc.surface_integrate(n, lo, up, cf, V), source)
-            for q in P:
-                diag = orc.patch_add(q["fc"], q["ic"], diag, 0); source = orc.patch_add(q["fc"], q["bc"], source, 0)
-            T, perf = orc.System([syn.LduCase(n, lo, up, diag, upper, lower, source)]).pbicg(T, source, "AINV", tolerance=1e-10, relTol=0.0)
-            lines.append(("AINVPBiCG", "T", perf["initialResidual"], perf["finalResidual"], perf["nIterations"]))
-        Too = Told
-    return lines, T, dict(G=G, n=n, nI=nI, lo=lo, up=up, phi=phi, P=P)
+    """tests/transport_walk.py::walk with the ddt line by the restatement (backward False: Euler) and one step size per step"""
+    import transport_walk
+    w = transport_walk.walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, dts, scheme, "corrected" if corrected else None, n_non_orth,
+                            ddt=BackwardDdt() if backward else None)
+    return w.lines, w.T, w.mesh
 
 
 def _close(g, r):
@@ -499,24 +462,20 @@ def test_time_loop_with_changing_step_sizes(pkg, orc):
 def test_scalarTransportFoam_with_the_backward_scheme(pkg, orc, tmp_path, dims, n_steps, scheme, corrected, n_non_orth):
     """the application with `ddtSchemes { default backward; }`: T.oldTime().oldTime() kept, GREAT on the first step, deltaT0 = deltaT
     afterwards; every solver line and the written T against the walk, with the comparisons of tests/test_scalartransportfoam.py"""
-    from test_polymesh import PKG, LINE, read_vol_field
+    from test_polymesh import PKG, read_vol_field
+    from transport_walk import assert_solver_lines, rewrite_schemes, solver_lines
     from test_scalartransportfoam import write_channel
     DT, delta_t = 0.01, 0.01
     case_dir = str(tmp_path / "channel")
     pts, faces, owner, neighbour, patches, tin, T0 = write_channel(case_dir, dims, DT, delta_t, n_steps, scheme, corrected, n_non_orth)
-    fs = os.path.join(case_dir, "system", "fvSchemes")
-    txt = open(fs).read()
-    assert "ddtSchemes { default Euler; }" in txt
-    open(fs, "w").write(txt.replace("ddtSchemes { default Euler; }", "ddtSchemes { default backward; }"))
+    rewrite_schemes(case_dir, ("ddtSchemes { default Euler; }", "ddtSchemes { default backward; }"))
     ref, Tref, _ = walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, [delta_t] * n_steps, scheme, corrected, n_non_orth)
     _, Teuler, _ = walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, [delta_t] * n_steps, scheme, corrected, n_non_orth, backward=False)
     out = subprocess.run([os.path.join(PKG, "scalarTransportFoam"), case_dir], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr + out.stdout[-1500:]
-    got = [(m.group(1), m.group(2), float(m.group(3)), float(m.group(4)), int(m.group(5))) for m in map(LINE.match, out.stdout.splitlines()) if m]
+    got = solver_lines(out.stdout)
     assert len(got) == len(ref) == n_steps * (n_non_orth + 1)
-    for g, r in zip(got, ref):
-        assert g[:2] == r[:2] and g[4] == r[4], (g, r)
-        assert abs(g[2] - r[2]) <= 1e-7 * max(r[2], 1e-12) + 1e-14 and abs(g[3] - r[3]) <= 1e-6 * max(r[2], 1e-12) + 1e-14, (g, r)
+    assert_solver_lines(got, ref)
     f = read_vol_field(os.path.join(case_dir, f"{n_steps * delta_t:.10g}", "T"))
     assert f["header"]["class"] == "volScalarField" and np.max(np.abs(f["internalField"] - Tref)) <= 1e-8 * np.max(np.abs(Tref))
     assert 0.05 < np.max(Tref) < 2.0 and np.min(Tref) > -0.2

@@ -13,7 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_polymesh import PKG, HEADER, make_box_mesh, geometry, write_case, LINE, read_vol_field
+from test_polymesh import PKG, HEADER, make_box_mesh, geometry, write_case, read_vol_field
+from transport_walk import assert_solver_lines, solver_lines
 
 pytestmark = pytest.mark.gpu
 
@@ -209,14 +210,11 @@ def test_icoFoam_cavity_matches_the_oracle_statement_for_statement(pkg, orc, tmp
     pts, faces, owner, neighbour, patches = write_cavity(case_dir, dims, nu, delta_t, n_steps, div_scheme, write_format, corrected)
     out = subprocess.run([os.path.join(PKG, "icoFoam"), case_dir], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr + out.stdout[-2000:]
-    got = [(m.group(1), m.group(2), float(m.group(3)), float(m.group(4)), int(m.group(5))) for m in map(LINE.match, out.stdout.splitlines()) if m]
+    got = solver_lines(out.stdout)
     cont = [tuple(map(float, m.groups())) for m in map(CONT.match, out.stdout.splitlines()) if m]
     ref_lines, ref_cont, refU, refp = oracle_icofoam(pkg, orc, pts, faces, owner, neighbour, patches, nu, delta_t, n_steps, div_scheme, corrected)
     assert len(got) == len(ref_lines) == n_steps * (7 if corrected else 5) and len(cont) == len(ref_cont) == n_steps * 2
-    for g, r in zip(got, ref_lines):
-        assert g[0] == r[0] and g[1] == r[1], (g, r)
-        assert g[4] == r[4], (g, r)                                                   # the same iteration counts
-        assert abs(g[2] - r[2]) <= 1e-7 * max(r[2], 1e-12) + 1e-14 and abs(g[3] - r[3]) <= 1e-6 * max(r[2], 1e-12) + 1e-14, (g, r)
+    assert_solver_lines(got, ref_lines)                                               # the same names and iteration counts, the residuals to the bars
     for g, r in zip(cont, ref_cont):
         assert abs(g[0] - r[0]) <= 1e-6 * r[0] + 1e-16 and abs(g[1] - r[1]) < 1e-15 and abs(g[2] - r[2]) < 1e-15, (g, r)
     assert all(c[0] < 1e-6 for c in cont[1::2])                                       # the final corrector closes continuity to the solver's tolerance

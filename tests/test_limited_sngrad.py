@@ -431,58 +431,12 @@ def test_engine_limited_laplacian_three_nonorth_correctors(pkg, orc):
 
 # ---- the applications ------------------------------------------------------------------------------------------------------------
 def walk_scalar_transport(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, delta_t, n_steps, k, n_non_orth):
-    """the walk of tests/test_scalartransportfoam.py (div Gauss linear), the correction flux of the Laplacian swapped for the restatement;
-    k None: `corrected`.  -> solver lines, T, share of faces with limiter < 1 over the run"""
-    from test_polymesh import geometry
-    syn = pkg.synthetic
-    G = geometry(pts, faces, owner, neighbour)
-    n, nI = int(owner.max()) + 1, len(neighbour)
-    lo, up = owner[:nI].astype(np.int32), neighbour.astype(np.int32)
-    V, lam, delta, magSf = G["V"], G["weights"], G["delta"], G["magSf"][:nI]
-    Sf = [np.ascontiguousarray(G["Sf"][:nI, d]) for d in range(3)]
-    cv = G["Sf"][:nI] / magSf[:, None] - (G["C"][up] - G["C"][lo]) * delta[:, None]
-    cv = [np.ascontiguousarray(cv[:, d]) for d in range(3)]
-    u0 = np.array([1.0, 0.2, 0.0])
-    phi = orc.flux_div(n, lo, up, lam, Sf, [np.full(n, u0[d]) for d in range(3)], want_div=False)
-    P = []
-    for name, ptype, cnt, start in patches:
-        fc = owner[start:start + cnt].astype(np.int32)
-        sfb = G["Sf"][start:start + cnt]
-        ub = np.tile(u0, (cnt, 1)) if name in ("inlet", "outlet") else np.zeros((cnt, 3))
-        phib = ub[:, 0] * sfb[:, 0] + ub[:, 1] * sfb[:, 1] + ub[:, 2] * sfb[:, 2]
-        diff = DT * G["magSf"][start:start + cnt] * G["delta_b"][start - nI:start - nI + cnt]
-        fixed = name == "inlet"
-        tb = tin if fixed else None
-        P.append(dict(fc=fc, sf=[np.ascontiguousarray(sfb[:, d]) for d in range(3)], tb=tb, ic=diff if fixed else phib, bc=(diff * tb - phib * tb) if fixed else np.zeros(cnt)))
-
-    def grad(T):
-        g = orc.gauss_grad(n, lo, up, Sf, orc.face_interpolate(lo, up, lam, T), None)
-        for q in P:
-            for d in range(3):
-                g[d] = orc.patch_add_product(q["fc"], q["sf"][d], T[q["fc"]] if q["tb"] is None else q["tb"], g[d], 0)
-        return [x / V for x in g]
-
-    T = T0.copy()
-    uL, dL = orc.fvm_laplacian(n, lo, up, delta, DT * magSf)
-    lines, limited, total = [], 0, 0
-    for step in range(n_steps):
-        Told = T.copy()
-        for non_orth in range(n_non_orth + 1):
-            gT = grad(T)
-            lB, uB, dB = orc.fvm_div(n, lo, up, lam, phi)
-            dD, sD = orc.fvm_ddt_euler(1.0 / delta_t, 1.0, V, Told)
-            lower, upper, diag, source = lB - uL, uB - uL, (dD + dB) - dL, sD
-            if k is None:
-                cf = orc.sngrad_correction_flux(lo, up, cv, lam, gT, -(DT * magSf))
-            else:
-                (cf,), lim = limited_flux(orc, lo, up, k, cv, lam, delta, [T], gT, -(DT * magSf))
-                limited += int(np.sum(lim < 1.0)); total += nI
-            source = orc.submul(V, orc.surface_integrate(n, lo, up, cf, V), source)
-            for q in P:
-                diag = orc.patch_add(q["fc"], q["ic"], diag, 0); source = orc.patch_add(q["fc"], q["bc"], source, 0)
-            T, perf = orc.System([syn.LduCase(n, lo, up, diag, upper, lower, source)]).pbicg(T, source, "AINV", tolerance=1e-10, relTol=0.0)
-            lines.append(("AINVPBiCG", "T", perf["initialResidual"], perf["finalResidual"], perf["nIterations"]))
-    return lines, T, limited / max(total, 1)
+    """tests/transport_walk.py::walk (div Gauss linear) with the correction flux of the Laplacian by the restatement; k None: `corrected`.
+    -> solver lines, T, share of faces with limiter < 1 over the run"""
+    import transport_walk
+    w = transport_walk.walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, [delta_t] * n_steps, "linear", "corrected" if k is None else ("limited", k),
+                            n_non_orth)
+    return w.lines, w.T, w.limited_share
 
 
 def walk_icofoam(pkg, orc, pts, faces, owner, neighbour, patches, nu, delta_t, n_steps, k):
@@ -587,10 +541,8 @@ def walk_icofoam(pkg, orc, pts, faces, owner, neighbour, patches, nu, delta_t, n
 
 
 def set_laplacian_scheme(case_dir, scheme):
-    sch = os.path.join(case_dir, "system", "fvSchemes")
-    text = open(sch).read()
-    assert "Gauss linear corrected" in text and "default corrected" in text
-    open(sch, "w").write(text.replace("Gauss linear corrected", "Gauss linear " + scheme).replace("default corrected", "default " + scheme))
+    from transport_walk import rewrite_schemes
+    rewrite_schemes(case_dir, ("Gauss linear corrected", "Gauss linear " + scheme), ("default corrected", "default " + scheme))
 
 
 def test_the_walks_reproduce_the_existing_corrected_walks(pkg, orc, tmp_path):
@@ -613,7 +565,8 @@ def test_the_walks_reproduce_the_existing_corrected_walks(pkg, orc, tmp_path):
 def test_scalarTransportFoam_limited_laplacian_matches_the_walk(pkg, orc, tmp_path):
     """the distorted (12, 9, 7) channel, `Gauss linear limited 0.5`, 2 non-orthogonal correctors, 3 steps: every solver line and the written T to
     the bars of test_scalartransportfoam.py.  k = 0.5: 32.3 % of the faces take limiter < 1 over the run on this mesh (the walk reports the share)."""
-    from test_polymesh import PKG, LINE, read_vol_field
+    from test_polymesh import PKG, read_vol_field
+    from transport_walk import assert_solver_lines, solver_lines
     from test_scalartransportfoam import write_channel
     DT, delta_t, n_steps, n_non_orth, k = 0.01, 0.01, 3, 2, 0.5
     case_dir = str(tmp_path / "channel")
@@ -621,14 +574,12 @@ def test_scalarTransportFoam_limited_laplacian_matches_the_walk(pkg, orc, tmp_pa
     set_laplacian_scheme(case_dir, "limited 0.5")
     out = subprocess.run([os.path.join(PKG, "scalarTransportFoam"), case_dir], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr + out.stdout[-1500:]
-    got = [(m.group(1), m.group(2), float(m.group(3)), float(m.group(4)), int(m.group(5))) for m in map(LINE.match, out.stdout.splitlines()) if m]
+    got = solver_lines(out.stdout)
     ref, Tref, share = walk_scalar_transport(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, delta_t, n_steps, k, n_non_orth)
     print(f"scalarTransportFoam limited {k}: share of faces with limiter < 1 over the run = {share:.4f}")
     assert share > 0
     assert len(got) == len(ref) == n_steps * (n_non_orth + 1)
-    for g, r in zip(got, ref):
-        assert g[:2] == r[:2] and g[4] == r[4], (g, r)
-        assert abs(g[2] - r[2]) <= 1e-7 * max(r[2], 1e-12) + 1e-14 and abs(g[3] - r[3]) <= 1e-6 * max(r[2], 1e-12) + 1e-14, (g, r)
+    assert_solver_lines(got, ref)
     f = read_vol_field(os.path.join(case_dir, f"{n_steps * delta_t:.10g}", "T"))
     assert f["header"]["class"] == "volScalarField" and np.max(np.abs(f["internalField"] - Tref)) <= 1e-8 * np.max(np.abs(Tref))
     # ... and the limiter limits: not the `corrected` result
@@ -641,7 +592,8 @@ def test_icoFoam_limited_laplacians_match_the_walk(pkg, orc, tmp_path):
     """the distorted (12, 9, 7) cavity, `Gauss linear limited corrected 0.33`, 3 steps: every solver line, the continuity errors and the written
     U and p to the bars of test_icofoam.py.  k = 0.33: 52.1 % of the faces take limiter < 1 in the U correction and 34.6 % in the p
     correction over the run on this mesh (the walk reports the shares)."""
-    from test_polymesh import PKG, LINE, read_vol_field
+    from test_polymesh import PKG, read_vol_field
+    from transport_walk import assert_solver_lines, solver_lines
     from test_icofoam import CONT, write_cavity
     nu, delta_t, n_steps, k = 0.01, 0.005, 3, 0.33
     case_dir = str(tmp_path / "cavity")
@@ -649,15 +601,13 @@ def test_icoFoam_limited_laplacians_match_the_walk(pkg, orc, tmp_path):
     set_laplacian_scheme(case_dir, "limited corrected 0.33")
     out = subprocess.run([os.path.join(PKG, "icoFoam"), case_dir], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr + out.stdout[-2000:]
-    got = [(m.group(1), m.group(2), float(m.group(3)), float(m.group(4)), int(m.group(5))) for m in map(LINE.match, out.stdout.splitlines()) if m]
+    got = solver_lines(out.stdout)
     cont = [tuple(map(float, m.groups())) for m in map(CONT.match, out.stdout.splitlines()) if m]
     ref_lines, ref_cont, refU, refp, share = walk_icofoam(pkg, orc, pts, faces, owner, neighbour, patches, nu, delta_t, n_steps, k)
     print(f"icoFoam limited corrected {k}: share of faces with limiter < 1 over the run: U {share['U']:.4f}, p {share['p']:.4f}")
     assert share["U"] > 0 and share["p"] > 0
     assert len(got) == len(ref_lines) == n_steps * 7 and len(cont) == len(ref_cont) == n_steps * 2
-    for g, r in zip(got, ref_lines):
-        assert g[0] == r[0] and g[1] == r[1] and g[4] == r[4], (g, r)
-        assert abs(g[2] - r[2]) <= 1e-7 * max(r[2], 1e-12) + 1e-14 and abs(g[3] - r[3]) <= 1e-6 * max(r[2], 1e-12) + 1e-14, (g, r)
+    assert_solver_lines(got, ref_lines)
     for g, r in zip(cont, ref_cont):
         assert abs(g[0] - r[0]) <= 1e-6 * r[0] + 1e-16 and abs(g[1] - r[1]) < 1e-15 and abs(g[2] - r[2]) < 1e-15, (g, r)
     tn = f"{n_steps * delta_t:.10g}"

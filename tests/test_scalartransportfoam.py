@@ -11,7 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_polymesh import PKG, HEADER, make_box_mesh, geometry, write_case, LINE, read_vol_field
+from test_polymesh import PKG, HEADER, make_box_mesh, geometry, write_case, read_vol_field
+from transport_walk import assert_solver_lines, solver_lines, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -55,62 +56,8 @@ snGradSchemes {{ default {'corrected' if corrected else 'uncorrected'}; }}
 
 
 def oracle_scalar_transport(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, delta_t, n_steps, scheme, corrected, n_non_orth):
-    syn = pkg.synthetic
-    G = geometry(pts, faces, owner, neighbour)
-    n, nI = int(owner.max()) + 1, len(neighbour)
-    lo, up = owner[:nI].astype(np.int32), neighbour.astype(np.int32)
-    V, lam, delta, magSf = G["V"], G["weights"], G["delta"], G["magSf"][:nI]
-    Sf = [np.ascontiguousarray(G["Sf"][:nI, k]) for k in range(3)]
-    centres = [np.ascontiguousarray(G["C"][:, k]) for k in range(3)]
-    nhat = G["Sf"][:nI] / magSf[:, None]
-    cv = nhat - (G["C"][up] - G["C"][lo]) * delta[:, None]
-    cv = [np.ascontiguousarray(cv[:, k]) for k in range(3)]
-    u0 = np.array([1.0, 0.2, 0.0])
-    U = [np.full(n, u0[k]) for k in range(3)]
-    phi = orc.flux_div(n, lo, up, lam, Sf, U, want_div=False)
-    P = []
-    for name, ptype, cnt, start in patches:
-        fc = owner[start:start + cnt].astype(np.int32)
-        sfb = G["Sf"][start:start + cnt]
-        ub = np.tile(u0, (cnt, 1)) if name in ("inlet", "outlet") else np.zeros((cnt, 3))
-        phib = ub[:, 0] * sfb[:, 0] + ub[:, 1] * sfb[:, 1] + ub[:, 2] * sfb[:, 2]
-        diff = DT * G["magSf"][start:start + cnt] * G["delta_b"][start - nI:start - nI + cnt]
-        fixed = name == "inlet"
-        tb = tin if fixed else None
-        P.append(dict(fc=fc, sf=[np.ascontiguousarray(sfb[:, k]) for k in range(3)], tb=tb,
-                      ic=diff if fixed else phib, bc=(diff * tb - phib * tb) if fixed else np.zeros(cnt)))
-
-    def grad(T):
-        g = orc.gauss_grad(n, lo, up, Sf, orc.face_interpolate(lo, up, lam, T), None)
-        for q in P:
-            for k in range(3):
-                g[k] = orc.patch_add_product(q["fc"], q["sf"][k], T[q["fc"]] if q["tb"] is None else q["tb"], g[k], 0)
-        return [x / V for x in g]
-
-    T = T0.copy()
-    uL, dL = orc.fvm_laplacian(n, lo, up, delta, DT * magSf)
-    lines = []
-    for step in range(n_steps):
-        Told = T.copy()
-        for non_orth in range(n_non_orth + 1):
-            gT = grad(T) if (corrected or scheme.startswith("limitedLinear")) else None
-            if scheme == "upwind":
-                w = orc.upwind_weights(phi)
-            elif scheme.startswith("limitedLinear"):
-                w, _ = orc.limited_linear_weights(lo, up, float(scheme.split()[1]), lam, phi, T, gT, centres)
-            else:
-                w = lam
-            lB, uB, dB = orc.fvm_div(n, lo, up, w, phi)
-            dD, sD = orc.fvm_ddt_euler(1.0 / delta_t, 1.0, V, Told)
-            lower, upper, diag, source = lB - uL, uB - uL, (dD + dB) - dL, sD
-            if corrected:
-                cf = orc.sngrad_correction_flux(lo, up, cv, lam, gT, -(DT * magSf))
-                source = orc.submul(V, orc.surface_integrate(n, lo, up, cf, V), source)
-            for q in P:
-                diag = orc.patch_add(q["fc"], q["ic"], diag, 0); source = orc.patch_add(q["fc"], q["bc"], source, 0)
-            T, perf = orc.System([syn.LduCase(n, lo, up, diag, upper, lower, source)]).pbicg(T, source, "AINV", tolerance=1e-10, relTol=0.0)
-            lines.append(("AINVPBiCG", "T", perf["initialResidual"], perf["finalResidual"], perf["nIterations"]))
-    return lines, T
+    w = walk(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, [delta_t] * n_steps, scheme, "corrected" if corrected else None, n_non_orth)
+    return w.lines, w.T
 
 
 @pytest.mark.parametrize("dims, n_steps, scheme, corrected, n_non_orth", [((12, 8, 6), 4, "upwind", False, 0), ((12, 8, 6), 4, "linear", False, 0),
@@ -121,12 +68,10 @@ def test_scalarTransportFoam_matches_the_oracle_statement_for_statement(pkg, orc
     pts, faces, owner, neighbour, patches, tin, T0 = write_channel(case_dir, dims, DT, delta_t, n_steps, scheme, corrected, n_non_orth, smooth_start=scheme.startswith("limitedLinear"))
     out = subprocess.run([os.path.join(PKG, "scalarTransportFoam"), case_dir], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr + out.stdout[-1500:]
-    got = [(m.group(1), m.group(2), float(m.group(3)), float(m.group(4)), int(m.group(5))) for m in map(LINE.match, out.stdout.splitlines()) if m]
+    got = solver_lines(out.stdout)
     ref, Tref = oracle_scalar_transport(pkg, orc, pts, faces, owner, neighbour, patches, tin, T0, DT, delta_t, n_steps, scheme, corrected, n_non_orth)
     assert len(got) == len(ref) == n_steps * (n_non_orth + 1)
-    for g, r in zip(got, ref):
-        assert g[:2] == r[:2] and g[4] == r[4], (g, r)
-        assert abs(g[2] - r[2]) <= 1e-7 * max(r[2], 1e-12) + 1e-14 and abs(g[3] - r[3]) <= 1e-6 * max(r[2], 1e-12) + 1e-14, (g, r)
+    assert_solver_lines(got, ref)
     f = read_vol_field(os.path.join(case_dir, f"{n_steps * delta_t:.10g}", "T"))
     assert f["header"]["class"] == "volScalarField" and np.max(np.abs(f["internalField"] - Tref)) <= 1e-8 * np.max(np.abs(Tref))
     assert 0.05 < np.max(Tref) < 2.0 and np.min(Tref) > -0.2                          # the inflow profile has entered the channel

@@ -4,7 +4,7 @@ turn in each round (all in one process):
         with the CrankNicolson time derivative (mi_fvm_assemble_cn) beside Euler's (mi_fvm_assemble) and backward's
         (mi_fvm_assemble_backward), in the caller's numbering (fixed blocks) and under ordered addressing (blocks = the layout's tiles);
   (ii)  the evaluate-once ddt0 update of the three components in one launch (mi_ddt_cn_update, density field);
-  (iii) with --parent-lib PATH: the Euler and backward assemblies of another build of the library (the parent commit's, built to a side
+  (iii) with --parent-lib PATH: the Euler, backward and CrankNicolson assemblies of another build of the library (the parent commit's, built to a side
         directory), its own context and addressing, in the same rounds.
 The Euler assembly is timed TWICE per round (A, B): the spread between two alternated runs of identical code is the margin the comparisons
 are judged within.
@@ -31,7 +31,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--dims", type=int, nargs=3, default=[216, 216, 216])
 ap.add_argument("--reps", type=int, default=9, help="rounds; each round times every variant once, in turn")
 ap.add_argument("--iters", type=int, default=20, help="calls per timed window")
-ap.add_argument("--parent-lib", default=None, help="another build of librapidcfd_amd.so whose Euler and backward assemblies are timed in the same rounds")
+ap.add_argument("--parent-lib", default=None, help="another build of librapidcfd_amd.so whose Euler, backward and CrankNicolson assemblies are timed in the same rounds")
+ap.add_argument("--reverse", action="store_true", help="time the variants of a round in the reverse order")
 ap.add_argument("--out", default=None, help="also write the result as JSON to this file")
 args = ap.parse_args()
 
@@ -103,6 +104,9 @@ if args.parent_lib:
     for tag, pa in (("caller numbering", pa0), ("ordered addressing", pa1)):
         variants[f"assemble Euler, parent library [{tag}]"] = (assemble(eng.Assembly(pa), EULER), B_E, parent)
         variants[f"assemble backward, parent library [{tag}]"] = (assemble(eng.Assembly(pa), BACK), B_B, parent)
+        variants[f"assemble CrankNicolson, parent library [{tag}]"] = (assemble(eng.Assembly(pa), CN), B_C, parent)
+if args.reverse:
+    variants = dict(reversed(list(variants.items())))
 
 times = {k: [] for k in variants}
 for fn, _, lib in variants.values():
@@ -140,8 +144,9 @@ for tag in ("caller numbering", "ordered addressing"):
     if args.parent_lib:
         cmp[f"Euler A / parent library [{tag}]"] = ratio(f"assemble Euler A [{tag}]", f"assemble Euler, parent library [{tag}]")
         cmp[f"backward / parent library [{tag}]"] = ratio(f"assemble backward [{tag}]", f"assemble backward, parent library [{tag}]")
+        cmp[f"CrankNicolson / parent library [{tag}]"] = ratio(f"assemble CrankNicolson [{tag}]", f"assemble CrankNicolson, parent library [{tag}]")
 line = json.dumps(dict(tool="bench_crank_nicolson", dims=args.dims, cells=N, faces=F, reps=args.reps, iters=args.iters,
-                       parent_library=bool(args.parent_lib), variants=res, comparisons=cmp))
+                       parent_library=bool(args.parent_lib), reverse=args.reverse, variants=res, comparisons=cmp))
 print(line)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
