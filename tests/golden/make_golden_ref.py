@@ -4,7 +4,7 @@ coarse-cell maps are frozen in tests/golden/golden_ref_pair.npz; its PCG::solve 
 PBiCG.C, PBiCGStab.C, smoothSolver.C + the functor headers, oracle/_ref/libref_solvers.so) run on the oracle's primitives and their psi and
 solverPerformance are frozen in tests/golden/golden_ref_solvers.npz; its GAMGSolver::solve / Vcycle / initVcycle /
 solveCoarsestLevel (GAMGSolverSolve.C, oracle/_ref/libref_gamg.so) run on the oracle's hierarchy and primitives ->
-tests/golden/golden_ref_gamg.npz; its fvMatrix-assembly functors (oracle/_ref/libref_fvm.so) -> tests/golden/golden_ref_fvm.npz.  Needs the reference tree:
+tests/golden/golden_ref_gamg.npz and, at every control edge of the V-cycle, tests/golden/golden_ref_gamg_controls.npz; its fvMatrix-assembly functors (oracle/_ref/libref_fvm.so) -> tests/golden/golden_ref_fvm.npz.  Needs the reference tree:
     python tests/golden/make_golden_ref.py
 """
 import os
@@ -123,6 +123,97 @@ def build_gamg(pkg, orc):
     out = {}
     for key, S, H, src, kw in gamg_runs(pkg, orc):
         x, p = orc.ref_gamg_solve(H, np.zeros(S.n), src, **kw)
+        out[key + "/psi"] = x
+        out[key + "/perf"] = np.array([p["initialResidual"], p["finalResidual"], p["nIterations"], p["converged"], p["singular"]], dtype=np.float64)
+    return out
+
+
+# ---- the V-cycle at every control edge (tests/test_gamg_controls.py) ----------------------------------------------------------
+GAMG_BASE = dict(tolerance=1e-9, maxIter=100)
+# id -> controls on top of GAMG_BASE; what each row reaches is derived and asserted in test_gamg_controls.py
+GAMG_CONTROL_ROWS = {
+    "S1": dict(nPreSweeps=2, preSweepsLevelMultiplier=2, maxPreSweeps=5),
+    "S2": dict(nPreSweeps=1, preSweepsLevelMultiplier=0),
+    "S3": dict(nPreSweeps=1, maxPreSweeps=0),
+    "S4": dict(nPostSweeps=0),
+    "S5": dict(nPostSweeps=0, postSweepsLevelMultiplier=0),
+    "S6": dict(maxPostSweeps=1),
+    "S7": dict(maxPostSweeps=0),
+    "S8": dict(nPostSweeps=1, postSweepsLevelMultiplier=2, maxPostSweeps=3, nFinestSweeps=1),
+    "S9": dict(nFinestSweeps=0, maxIter=6),
+    "S10": dict(nFinestSweeps=0, nPostSweeps=0, postSweepsLevelMultiplier=0, maxIter=6),
+    "S11": dict(omega=1.0, maxIter=8),
+    "S12": dict(omega=0.6),
+    "X1": dict(scaleCorrection=1),
+    "X2": dict(scaleCorrection=0),
+    "C1": dict(relTol=0.1),
+    "C2": dict(relTol=0.1, tolerance=0.0),
+    "C3": dict(maxIter=0),
+    "C4": dict(maxIter=1),
+    "C5": dict(tolerance=1e30),
+    "C6": dict(tolerance=1e30, minIter=3),
+    "C7": dict(minIter=3, maxIter=2, tolerance=0.0),
+    "C8": dict(minIter=6, maxIter=2, tolerance=0.0),
+}
+GAMG_FORCED_CONTROLS = [dict(), dict(minIter=1), dict(tolerance=0.0, maxIter=3), dict(minIter=2, nPreSweeps=1)]   # exact and all-zero systems
+GAMG_SHALLOW_DIMS = [(4, 3, 2), (4, 4, 3), (6, 4, 4)]            # 1, 2 and 3 levels with nCellsInCoarsestLevel 12
+GAMG_SHALLOW_CONTROLS = [dict(), dict(nPreSweeps=1), dict(scaleCorrection=1), dict(scaleCorrection=0), dict(nPostSweeps=0, nFinestSweeps=1)]
+GAMG_COUPLED_ROWS = ("S1", "S4", "C1", "S9")
+
+
+def gamg_args(kw):
+    args = dict(GAMG_BASE); args.update(kw)
+    return args
+
+
+def gamg_case_F(pkg, sym):
+    return pkg.synthetic.box_case(12, 10, 8, symmetric=sym)
+
+
+def gamg_case_coupled(pkg, sym):
+    syn = pkg.synthetic
+    return syn.add_cyclic_y(syn.box_case(12, 12, 10, symmetric=sym), asym_shift=0.0 if sym else 0.2)
+
+
+def gamg_exact_system(pkg, orc, case):
+    """(start, source) of a system whose start is its solution up to the rounding of one Amul"""
+    x = pkg.synthetic.splitmix_uniform(7, case.n_cells) - 0.5
+    return x, orc.System([case]).amul(x)
+
+
+def gamg_control_runs(pkg, orc):
+    """(key, System, GamgSysHierarchy, start, source, controls) of every run frozen in golden_ref_gamg_controls.npz"""
+    for sym in (True, False):
+        tag = "sym" if sym else "asym"
+        case = gamg_case_F(pkg, sym)
+        S = orc.System([case])
+        H = orc.GamgSysHierarchy(S, [orc.box_face_weights(case)], 10)
+        zero = np.zeros(case.n_cells)
+        for rid, kw in GAMG_CONTROL_ROWS.items():
+            yield f"F/{tag}/{rid}", S, H, zero, case.source, gamg_args(kw)
+        x, b = gamg_exact_system(pkg, orc, case)
+        for k, kw in enumerate(GAMG_FORCED_CONTROLS):
+            yield f"exact/{tag}/{k}", S, H, x, b, gamg_args(kw)
+            yield f"zero/{tag}/{k}", S, H, zero, zero, gamg_args(kw)
+        for dims in GAMG_SHALLOW_DIMS:
+            sc = pkg.synthetic.box_case(*dims, symmetric=sym)
+            Ss = orc.System([sc])
+            Hs = orc.GamgSysHierarchy(Ss, [orc.box_face_weights(sc)], 12)
+            for k, kw in enumerate(GAMG_SHALLOW_CONTROLS):
+                yield f"shallow_{dims[0]}x{dims[1]}x{dims[2]}/{tag}/{k}", Ss, Hs, np.zeros(sc.n_cells), sc.source, gamg_args(kw)
+        cc = gamg_case_coupled(pkg, sym)
+        Sc = orc.System([cc])
+        Hc = orc.GamgSysHierarchy(Sc, [orc.box_face_weights(cc)], 10)
+        for rid in GAMG_COUPLED_ROWS:
+            yield f"coupled/{tag}/{rid}", Sc, Hc, np.zeros(cc.n_cells), cc.source, gamg_args(GAMG_CONTROL_ROWS[rid])
+
+
+def build_gamg_controls(pkg, orc):
+    """psi and solverPerformance of the REFERENCE's GAMGSolver::solve (GAMGSolverSolve.C compiled from the reference tree,
+    oracle/_ref/libref_gamg.so) for every run of gamg_control_runs"""
+    out = {}
+    for key, S, H, start, src, kw in gamg_control_runs(pkg, orc):
+        x, p = orc.ref_gamg_solve(H, start, src, **kw)
         out[key + "/psi"] = x
         out[key + "/perf"] = np.array([p["initialResidual"], p["finalResidual"], p["nIterations"], p["converged"], p["singular"]], dtype=np.float64)
     return out
@@ -334,6 +425,7 @@ if __name__ == "__main__":
     np.savez_compressed(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden_ref_functors.npz"), **build_functors(pkg, orc))
     assert orc.ref_gamg_available(), "oracle/_ref/libref_gamg.so missing"
     np.savez_compressed(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden_ref_gamg.npz"), **build_gamg(pkg, orc))
+    np.savez_compressed(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden_ref_gamg_controls.npz"), **build_gamg_controls(pkg, orc))
     assert orc.ref_gamg_functors_available(), "oracle/_ref/libref_gamg_functors.so missing"
     np.savez_compressed(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden_ref_gamg_functors.npz"), **build_gamg_functors(pkg, orc))
     assert orc.ref_gamg_scale_available(), "oracle/_ref/libref_gamg_scale.so missing"
