@@ -2,6 +2,9 @@
 import numpy as np
 import pytest
 
+from assembly_support import (OTHER_TABLES, ROW_MODES, box_centres, dot_contracted, euler_ddt_call, fma, gpu_env, set_row_blocks, set_row_tables, shape_case,
+                              shaped_addressing, unfused_sequence)
+
 
 def box_patches(dims):
     """faceCells of the six boundary patches of a lexicographic box (x-min, x-max, y-min, ...)."""
@@ -132,26 +135,10 @@ def test_engine_assembly_bit_exact(pkg, orc, dims):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["fixed256", "fixed1024", "tiles", "tiles_unstaged", "fixed_unstaged"])
+@pytest.mark.parametrize("mode", ROW_MODES)
 @pytest.mark.parametrize("name", ["box", "graph"])
 def test_row_passes_bit_exact_for_every_block_shape(pkg, orc, monkeypatch, name, mode):
     _row_passes_bit_exact(pkg, orc, monkeypatch, name, mode, "default")
-
-
-# the forms of the row tables and of the block mapping that the defaults never take: (tables, mode)
-OTHER_TABLES = ([("row32", m) for m in ("fixed256", "fixed1024", "tiles", "tiles_unstaged", "fixed_unstaged")]
-                + [("noxcd", m) for m in ("fixed256", "tiles")])
-
-
-def _set_tables(monkeypatch, tables):
-    """before the context (MI_XCD_ROWS is read by mi_ctx_create) and before the first row pass (MI_ROW16: ensure_caller_tables)"""
-    monkeypatch.delenv("MI_ROW16", raising=False); monkeypatch.delenv("MI_XCD_ROWS", raising=False)
-    if tables == "row32":       # the 32-bit row tables: also what a block that does not fit 16 bits falls back to
-        monkeypatch.setenv("MI_ROW16", "0")
-    elif tables == "noxcd":     # blockIdx.x as it comes, in every row pass, face pass and gradient pass
-        monkeypatch.setenv("MI_XCD_ROWS", "0")
-    else:
-        assert tables == "default"
 
 
 @pytest.mark.gpu
@@ -168,29 +155,17 @@ def _row_passes_bit_exact(pkg, orc, monkeypatch, name, mode, tables):
     fixed ranges of 256 / 1024 cells in the caller's numbering, the layout's tiles under ordered addressing; neighbour-side
     faces inside the block come from LDS, cut faces are gathered / recomputed.  Same bits as the oracle in every shape,
     and on the unstaged path a block takes when its faces do not fit the LDS arrays."""
-    import torch
-    from conftest import random_graph_case
-    eng, syn = pkg.engine, pkg.synthetic
-    _set_tables(monkeypatch, tables)
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    case = syn.box_case(31, 23, 19, symmetric=False) if name == "box" else random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=False)
+    set_row_tables(monkeypatch, tables)
+    set_row_blocks(monkeypatch, mode, grad=True)
+    eng, ctx, dev, host, E = gpu_env(pkg)
+    syn = pkg.synthetic
+    case, addr = shaped_addressing(eng, ctx, syn, shape_case(pkg, name), mode)
     if mode.startswith("tiles"):
-        a0 = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-        case = syn.renumber(case, a0.cell_perm())
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr, ordered=True, tile_cell_start=a0.tile_starts())
         assert addr.is_ordered and addr.n_tiles > 4
     else:
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
         assert not addr.is_ordered
-    for var in ("MI_ROW_BS", "MI_GRAD_BS"):
-        monkeypatch.setenv(var, "1024" if mode == "fixed1024" else "256")
-    if mode.endswith("unstaged"):
-        monkeypatch.setenv("MI_ROW_CAP", "64")
     n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
     asm = eng.Assembly(addr)
-    E = lambda m: torch.empty(m, dtype=torch.float64, device="cuda:0")
     for kind in (0, 1, 2):
         start = syn.splitmix_uniform(kind, n)
         io = dev(start)
@@ -243,10 +218,6 @@ def test_compressible_operators_oracle_against_plain_numpy(pkg, orc):
     (EulerDdtScheme.C:403-440, 663-720; fvmSup.C:34-214; ddtScheme.C:139-174; pEqn.H:49-71): the C restatements against the
     formulas written out with numpy field operations -- one rounding per operation, so bit for bit (the fused multiply-adds of
     the interpolate / dot product are evaluated in exact rational arithmetic and rounded once)"""
-    from fractions import Fraction
-
-    def fma(a, b, c):       # one rounding: exact rational arithmetic, then float() rounds to nearest even
-        return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
     syn = pkg.synthetic
     case = syn.box_case(7, 6, 5)
     n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
@@ -272,7 +243,7 @@ def test_compressible_operators_oracle_against_plain_numpy(pkg, orc):
         for f in range(nf):
             P, N = lo[f], up[f]
             i = [fma(lam[f], V[k][P] - V[k][N], V[k][N]) for k in range(3)]
-            out[f] = fma(i[2], Sf[2][f], fma(i[0], Sf[0][f], i[1] * Sf[1][f]))   # Vector operator& as the compiled reference rounds it
+            out[f] = dot_contracted(*i, Sf[0][f], Sf[1][f], Sf[2][f])            # Vector operator& as the compiled reference rounds it
         return out
     phi, div = orc.flux_div(n, lo, up, lam, Sf, U, scale=rho0, add_a=aA, add_b=aB, vol=vol)
     ref = flux(rho0) + aA * aB
@@ -391,11 +362,7 @@ def test_assemble_then_solve_matches_oracle_end_to_end(pkg, orc):
 # ---- scheme front-end: ddt, upwind / limitedLinear weights, Gauss gradient ---------------------------------------
 def box_geometry(dims):
     """cell centres, internal-face area vectors Sf and linear weights of the uniform lexicographic box"""
-    nx, ny, nz = dims
-    h = 1.0 / nx
-    c = np.arange(nx * ny * nz)
-    C = [(c % nx + 0.5) * h, ((c // nx) % ny + 0.5) * h, (c // (nx * ny) + 0.5) * h]
-    return h, C
+    return 1.0 / dims[0], box_centres(dims)
 
 
 def face_dirs(case, dims):
@@ -493,7 +460,7 @@ def test_engine_scheme_front_end_bit_exact(pkg, orc, dims):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["fixed256", "fixed1024", "tiles", "tiles_unstaged"])
+@pytest.mark.parametrize("mode", ROW_MODES[:4])
 @pytest.mark.parametrize("name", ["box", "graph"])
 def test_fused_assembly_equals_the_unfused_sequence_bit_for_bit(pkg, orc, monkeypatch, name, mode):
     _fused_assembly_bit_exact(pkg, orc, monkeypatch, name, mode, "default")
@@ -509,30 +476,17 @@ def test_fused_assembly_bit_exact_with_the_other_row_tables(pkg, orc, monkeypatc
 
 def _fused_assembly_bit_exact(pkg, orc, monkeypatch, name, mode, tables):
     """mi_fvm_assemble -- [fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- explicit terms] in ONE row pass -- against (a) the
-    oracle's unfused sequence (tests/assembly_full_size.py: oracle_assemble) and (b) the engine's own scheme-by-scheme calls combined
+    oracle's unfused sequence (tests/assembly_full_size.py: oracle_assemble) and (b) the engine's own scheme-by-scheme calls (tests/assembly_support.py: unfused_sequence) combined
     with mi_vec_axpby the way fvMatrix::operator+ / - combine them (fvMatrix.C:1693-2030), for three systems (momentum-like with three
     right-hand sides, upwind convection, Sp and two explicit terms; pressure-like symmetric; convection with given weights), in every
     block shape of the row passes; plus fvMatrix<vector>::relax fed with the pass's sumMagOffDiag, setValues (reference and upstream
     semantics) and setReference."""
     import torch
     import assembly_full_size as afs
-    from conftest import random_graph_case
-    eng, syn = pkg.engine, pkg.synthetic
-    _set_tables(monkeypatch, tables)
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    case = syn.box_case(31, 23, 19, symmetric=False) if name == "box" else random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=False)
-    if mode.startswith("tiles"):
-        a0 = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-        case = syn.renumber(case, a0.cell_perm())
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr, ordered=True, tile_cell_start=a0.tile_starts())
-        assert addr.is_ordered
-    else:
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-    monkeypatch.setenv("MI_ROW_BS", "1024" if mode == "fixed1024" else "256")
-    if mode.endswith("unstaged"):
-        monkeypatch.setenv("MI_ROW_CAP", "64")
+    set_row_tables(monkeypatch, tables)
+    set_row_blocks(monkeypatch, mode)            # MI_GRAD_BS stays: engine_run's Gauss gradient runs on the default gradient plan
+    eng, ctx, dev, host, E = gpu_env(pkg)
+    case, addr = shaped_addressing(eng, ctx, pkg.synthetic, shape_case(pkg, name), mode)
     M = dict(n=case.n_cells, nf=case.n_faces, lo=case.lower_addr, up=case.upper_addr, dims=(1, 1, 1))
     q = afs.inputs(pkg, M)
     got = afs.engine_run(pkg, ctx, addr, M, q)
@@ -543,18 +497,12 @@ def _fused_assembly_bit_exact(pkg, orc, monkeypatch, name, mode, tables):
     # (b) the engine's own unfused sequence for the momentum-like system
     n, nf = M["n"], M["nf"]
     asm = eng.Assembly(addr)
-    E = lambda m: torch.empty(m, dtype=torch.float64, device="cuda:0")
-    wts, cl, cu, cd, lu, ld, dd, ds = E(nf), E(nf), E(nf), E(n), E(nf), E(n), E(n), [E(n) for _ in range(3)]
     flux, vol = dev(q["flux"]), dev(q["vol"])
-    asm.upwind_weights(flux, wts); asm.fvm_div(wts, flux, cl, cu, cd); asm.fvm_laplacian(dev(q["delta"]), dev(q["gamma"]), lu, ld)
-    for r in range(3):
-        asm.fvm_ddt_euler_rho(q["rdt"], dev(q["rho"]), dev(q["rho0"]), vol, dev(q["V"][r]), dd, ds[r])
-        asm.fvm_su(vol, dev(q["su"][r]), ds[r])                                   # + su: source -= V*su
-        t = vol * dev(q["g"][r]); ds[r].add_(t)                                   # == g: source += V*g
-    asm.axpby(1.0, cl, -1.0, lu, cl); asm.axpby(1.0, cu, -1.0, lu, cu)
-    asm.axpby(1.0, dd, 1.0, cd, dd); asm.axpby(1.0, dd, -1.0, ld, dd)
-    t = vol * dev(q["sp"]); dd.sub_(t)
-    for key, t in (("lower", cl), ("upper", cu), ("diag", dd), ("source0", ds[0]), ("source1", ds[1]), ("source2", ds[2])):
+    seq = unfused_sequence(asm, E, vol, euler_ddt_call(asm, q["rdt"], vol, [dev(x) for x in q["V"]], rho=dev(q["rho"]), rho_old=dev(q["rho0"])), 3,
+                           dict(delta_coeffs=dev(q["delta"]), gamma_magsf=dev(q["gamma"])), div=dict(flux=flux, weights=None), sp=(dev(q["sp"]), -1.0),
+                           su=[(1.0, [dev(x) for x in q["su"]]), (-1.0, [dev(x) for x in q["g"]])])
+    cl, dd = seq["lower"], seq["diag"]
+    for key, t in (("lower", cl), ("upper", seq["upper"]), ("diag", dd), ("source0", seq["src"][0]), ("source1", seq["src"][1]), ("source2", seq["src"][2])):
         assert np.array_equal(host(t), got["assemble_momentum/" + key]), key
     # fvc::div(faceFlux, vf) (gaussConvectionScheme::fvcDiv): upwind and given weights, against the oracle's interpolate -> product -> surfaceIntegrate
     Kf, dv = E(nf), E(n)

@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from assembly_support import SHAPES, VARIANTS, FusedCase, gpu_env
+
 GREAT = 1e15
 
 
@@ -109,22 +111,12 @@ def test_restated_fvm_ddt_is_second_order_and_euler_first():
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def _env(pkg):
-    import torch
-    eng = pkg.engine
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    E = lambda m: torch.empty(m, dtype=torch.float64, device="cuda:0")
-    return eng, ctx, dev, host, E
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 2, 3, 1027, 31 * 23 * 19])
 def test_streaming_kernels_against_the_restatement(pkg, n):
     """mi_fvm_ddt_backward / mi_fvc_ddt_backward: the three density forms x the three coefficient sets; sizes with an odd tail and an unpaired
     element of the double2 loop"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     u = pkg.synthetic.splitmix_uniform
     syn = pkg.synthetic
     case = syn.box_case(2, 2, 2)
@@ -162,7 +154,7 @@ def test_ddt_corr_against_the_restatement(pkg, orc, name):
     """mi_ddt_phi_corr_backward with and without density; faces with phi0 == 0.0 (coefficient 0) and faces whose phi0 equals flux(U0) bit for
     bit (coefficient 1)"""
     from conftest import random_graph_case
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     syn = pkg.synthetic
     u = syn.splitmix_uniform
     case = syn.box_case(13, 11, 9) if name == "box" else random_graph_case(pkg, 9000, extra=3.0, seed=5)
@@ -198,165 +190,45 @@ def test_ddt_corr_against_the_restatement(pkg, orc, name):
 
 
 # ---- the fused assembly ----------------------------------------------------------------------------------------------------------
-def _fused_inputs(pkg, n, nf):
-    u = pkg.synthetic.splitmix_uniform
-    flux = u(110, nf) - 0.45
-    flux[::7] = 0.0
-    return dict(flux=flux, w=0.3 + 0.4 * u(140, nf), vol=0.5 + u(111, n), delta=1.0 + u(107, nf), gamma=0.5 + u(108, nf),
-                rho=0.8 + u(135, n), rho0=0.7 + u(136, n), rho00=0.6 + u(137, n), sp=u(153, n),
-                psi0=[u(131 + k, n) - 0.5 for k in range(3)], psi00=[u(171 + k, n) - 0.5 for k in range(3)],
-                su=[u(154 + k, n) - 0.5 for k in range(3)], su2=[u(158 + k, n) - 0.5 for k in range(3)],
-                C=[u(144 + k, n) for k in range(3)], cf=[u(147 + k, nf) for k in range(3)],
-                grad=[[4.0 * (u(200 + 3 * r + k, n) - 0.5) for k in range(3)] for r in range(3)])
+def backward_ddt_call(V, rdt, c):
+    """the ddt_call of assembly_support.unfused_sequence for the backward scheme on the fields of the variant V"""
+    return lambda r, dd, ds: V.case.A.fvm_ddt_backward(rdt, c, V.case.vol, V.psi_old[r], V.psi_old_old[r], dd, ds, rho_old_old=V.rho_old_old, **V.rho)
 
 
-# n_rhs, density, convection weights (None: upwind; "w": given; False: no convection), Sp and the two explicit terms, the correction
-VARIANTS = [
-    dict(tag="momentum", n_rhs=3, field=True, div=None, extras=True, corr=False),
-    dict(tag="scalar", n_rhs=1, field=False, div="w", extras=False, corr=False),
-    dict(tag="symmetric", n_rhs=1, field=False, div=False, extras=True, corr=False),
-    dict(tag="corrected", n_rhs=3, field=True, div=None, extras=True, corr=True),
-    dict(tag="corrected_scalar", n_rhs=1, field=False, div=None, extras=False, corr=True),
-]
-SHAPES = ([(name, mode, "default") for name in ("box", "graph") for mode in ("fixed256", "fixed1024", "tiles", "tiles_unstaged")]
-          + [("box", "fixed256", "row32"), ("graph", "tiles", "noxcd")])
+def backward_arg(V, c):
+    """the `backward` key of Assembly.assemble's ddt argument on the fields of the variant V"""
+    back = dict(coeffs=c, psi_old_old=V.psi_old_old)
+    if V.rho_old_old is not None:
+        back["rho_old_old"] = V.rho_old_old
+    return back
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,mode,tables", SHAPES)
 def test_fused_backward_assembly_bit_for_bit(pkg, orc, monkeypatch, name, mode, tables):
     """mi_fvm_assemble_backward against (a) the engine's own unfused sequence -- mi_fvm_ddt_backward, mi_fvm_div, mi_fvm_laplacian, mi_fvm_su /
-    Sp, the mi_vec_axpby combinations, in the order tests/test_assembly.py uses -- and (b) the restatement (the corrected variants take the
-    correction's face field from the engine's own face pass, which tests/test_linear_upwind.py pins); and on the same inputs the Euler call,
-    which takes no `backward` key, against its unfused sequence."""
-    import torch
-    from conftest import random_graph_case
-    monkeypatch.delenv("MI_ROW16", raising=False); monkeypatch.delenv("MI_XCD_ROWS", raising=False)
-    if tables == "row32":
-        monkeypatch.setenv("MI_ROW16", "0")
-    elif tables == "noxcd":
-        monkeypatch.setenv("MI_XCD_ROWS", "0")
-    monkeypatch.setenv("MI_ROW_BS", "1024" if mode == "fixed1024" else "256")
-    if mode.endswith("unstaged"):
-        monkeypatch.setenv("MI_ROW_CAP", "64")
-    eng, ctx, dev, host, E = _env(pkg)
-    syn = pkg.synthetic
-    case = syn.box_case(31, 23, 19, symmetric=False) if name == "box" else random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=False)
-    if mode.startswith("tiles"):
-        a0 = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-        case = syn.renumber(case, a0.cell_perm())
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr, ordered=True, tile_cell_start=a0.tile_starts())
-        assert addr.is_ordered
-    else:
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-    n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
-    q = _fused_inputs(pkg, n, nf)
-    A = eng.Assembly(addr)
+    Sp, the mi_vec_axpby combinations, in the order of tests/assembly_support.py::unfused_sequence -- and (b) the restatement (the corrected
+    variants take the correction's face field from the engine's own face pass, which tests/test_linear_upwind.py pins); and on the same
+    inputs the Euler call, which takes no `backward` key, against its unfused sequence."""
+    F = FusedCase(pkg, orc, monkeypatch, name, mode, tables)
+    eng, dev, host, E, A, addr, q = F.eng, F.dev, F.host, F.E, F.A, F.addr, F.q
+    n, nf, vol, flux, lap = F.n, F.nf, F.vol, F.flux, F.lap
     dt, dt0 = 0.004, 0.01
     c, rdt = coeffs(dt, dt0), 1.0 / dt
-    vol, flux = dev(q["vol"]), dev(q["flux"])
-    uL, dL = orc.fvm_laplacian(n, lo, up, q["delta"], q["gamma"])
     for v in VARIANTS:
         if v["corr"] and name != "box":
             continue
-        R = v["n_rhs"]
-        DIV = v["div"] is not False
-        wh = None if not DIV else (orc.upwind_weights(q["flux"]) if v["div"] is None else q["w"])
-        wd = dev(q["w"]) if v["div"] == "w" else None
-        ddt = dict(r_delta_t=rdt, vol=vol, psi_old=[dev(x) for x in q["psi0"][:R]])
-        back = dict(coeffs=c, psi_old_old=[dev(x) for x in q["psi00"][:R]])
-        if v["field"]:
-            ddt.update(rho=dev(q["rho"]), rho_old=dev(q["rho0"])); back["rho_old_old"] = dev(q["rho00"])
-            rkw = dict(rho=q["rho"], rho0=q["rho0"], rho00=q["rho00"])
-            ekw = dict(rho=ddt["rho"], rho_old=ddt["rho_old"], rho_old_old=back["rho_old_old"])
-        else:
-            ddt["rho_value"] = 1.2
-            rkw, ekw = dict(rho_value=1.2), dict(rho_value=1.2)
-        div = None
-        if DIV:
-            div = dict(flux=flux, weights=wd)
-            if v["corr"]:
-                grads = [[dev(x) for x in g] for g in q["grad"][:R]]
-                div["correction"] = dict(scale=1.0, cf=[dev(x) for x in q["cf"]], c=[dev(x) for x in q["C"]], grad=grads)
-        lap = dict(delta_coeffs=dev(q["delta"]), gamma_magsf=dev(q["gamma"]))
-        sp = (dev(q["sp"]), -1.0) if v["extras"] else None
-        su = [(1.0, [dev(x) for x in q["su"][:R]]), (-1.0, [dev(x) for x in q["su2"][:R]])] if v["extras"] else []
-
-        def fused(ddt_arg):
-            o = dict(lower=E(nf) if DIV else None, upper=E(nf), diag=E(n), mag=E(n), src=[E(n) for _ in range(R)])
-            A.assemble(o["upper"], o["diag"], lower_out=o["lower"], sources_out=o["src"], ddt=ddt_arg, div=div, laplacian=lap, sp=sp, su=su, sum_mag_out=o["mag"])
-            return o
-
-        def unfused(backward):
-            """the scheme-by-scheme calls and their combination, the order of tests/test_assembly.py::_fused_assembly_bit_exact"""
-            cl, cu, cd, lu, ld, dd, ds = E(nf), E(nf), E(n), E(nf), E(n), E(n), [E(n) for _ in range(R)]
-            t = [E(nf) for _ in range(R)]
-            if DIV:
-                wts = wd
-                if wts is None:
-                    wts = E(nf); A.upwind_weights(flux, wts)
-                A.fvm_div(wts, flux, cl, cu, cd)
-                if v["corr"]:
-                    A.linear_upwind_correction(flux, div["correction"]["cf"], div["correction"]["c"], div["correction"]["grad"], t)
-            A.fvm_laplacian(lap["delta_coeffs"], lap["gamma_magsf"], lu, ld)
-            for r in range(R):
-                if backward:
-                    A.fvm_ddt_backward(rdt, c, vol, ddt["psi_old"][r], back["psi_old_old"][r], dd, ds[r], **ekw)
-                elif v["field"]:
-                    A.fvm_ddt_euler_rho(rdt, ddt["rho"], ddt["rho_old"], vol, ddt["psi_old"][r], dd, ds[r])
-                else:
-                    A.fvm_ddt_euler(rdt, 1.2, vol, ddt["psi_old"][r], dd, ds[r])
-                if v["corr"]:
-                    ivf = E(n); A.surface_integrate(t[r], vol, ivf); A.submul(vol, ivf, ds[r])
-                if v["extras"]:
-                    A.fvm_su(vol, su[0][1][r], ds[r])                           # + su: source -= V*su
-                    p = vol * su[1][1][r]; ds[r].add_(p)                        # == su2: source += V*su2
-            if DIV:
-                A.axpby(1.0, cl, -1.0, lu, cl); A.axpby(1.0, cu, -1.0, lu, cu)
-                A.axpby(1.0, dd, 1.0, cd, dd)
-            else:
-                A.axpby(-1.0, lu, 0.0, lu, cu)
-            A.axpby(1.0, dd, -1.0, ld, dd)
-            if v["extras"]:
-                p = vol * sp[0]; dd.sub_(p)
-            return dict(lower=cl if DIV else None, upper=cu, diag=dd, src=ds, t=t)
-
-        got = fused(dict(ddt, backward=back))
-        seq = unfused(True)
-        for key in ("lower", "upper", "diag"):
-            if got[key] is not None:
-                assert np.array_equal(host(got[key]), host(seq[key])), (v["tag"], key)
-        for r in range(R):
-            assert np.array_equal(host(got["src"][r]), host(seq["src"][r])), (v["tag"], r)
-        # (b) the restatement
-        if DIV:
-            lB, uB, dB = orc.fvm_div(n, lo, up, wh, q["flux"])
-            lower, upper = lB - uL, uB - uL
-        else:
-            lower, upper = None, -uL
-        for r in range(R):
-            dD, s = fvm_ddt(rdt, c, q["vol"], q["psi0"][r], q["psi00"][r], **rkw)
-            if v["corr"]:
-                ivf = orc.surface_integrate(n, lo, up, host(seq["t"][r]), q["vol"])
-                s = s - q["vol"] * ivf
-            if v["extras"]:
-                s = s - q["vol"] * q["su"][r]
-                s = s + q["vol"] * q["su2"][r]
-            assert np.array_equal(host(got["src"][r]), s), (v["tag"], r)
-        diag = ((dD + dB) - dL) if DIV else (dD - dL)
-        if v["extras"]:
-            diag = diag - q["vol"] * q["sp"]
-        assert np.array_equal(host(got["diag"]), diag) and np.array_equal(host(got["upper"]), upper), v["tag"]
-        if DIV:
-            assert np.array_equal(host(got["lower"]), lower), v["tag"]
-        assert np.array_equal(host(got["mag"]), orc.row_face_op(2, n, lo, up, lower, upper, np.zeros(n))), v["tag"]
+        V = F.variant(v)
+        rkw = dict(rho=q["rho"], rho0=q["rho0"], rho00=q["rho00"]) if v["field"] else dict(rho_value=1.2)
+        ddt = dict(V.ddt, r_delta_t=rdt)
+        got = V.fused(dict(ddt, backward=backward_arg(V, c)))
+        seq = V.unfused(backward_ddt_call(V, rdt, c))
+        V.assert_same(got, seq, "backward")
+        V.assert_restated(got, seq, lambda r: fvm_ddt(rdt, c, q["vol"], q["psi0"][r], q["psi00"][r], **rkw))
         # Euler untouched: the same call without the `backward` key
-        eul, seq_e = fused(ddt), unfused(False)
-        for key in ("lower", "upper", "diag"):
-            if eul[key] is not None:
-                assert np.array_equal(host(eul[key]), host(seq_e[key])), (v["tag"], key)
-        for r in range(R):
-            assert np.array_equal(host(eul["src"][r]), host(seq_e["src"][r])), (v["tag"], r)
+        eul = V.fused(ddt)
+        V.assert_same(eul, V.unfused(V.euler(rdt)), "euler")
+        for r in range(V.R):
             assert not np.array_equal(host(eul["src"][r]), host(got["src"][r]))
     # refusals of the backward entry point
     R = 1
@@ -414,7 +286,7 @@ def test_time_loop_with_changing_step_sizes(pkg, orc):
     with the restatement and the oracle's PBiCG"""
     import torch
     from test_polymesh import make_box_mesh
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     DT, dts = 0.01, [0.01, 0.01, 0.004, 0.008, 0.008, 0.01]
     pts, faces, owner, neighbour, patches = make_box_mesh((12, 8, 6), seed=None)
     cnt_in = [pt[2] for pt in patches if pt[0] == "inlet"][0]

@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 
 import test_backward_ddt as bw
-from test_backward_ddt import SHAPES, VARIANTS, _close, _env, _fused_inputs
+from assembly_support import SHAPES, VARIANTS, FusedCase, gpu_env
+from test_backward_ddt import _close
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
@@ -163,7 +164,7 @@ def test_streaming_kernels_against_the_restatement(pkg, n):
     """mi_ddt_cn_update (one and three fields, in place) / mi_fvm_ddt_cn / mi_fvc_ddt_cn: the three density forms x three off-centring
     coefficients; sizes with an odd tail and an unpaired element of the double2 loop"""
     import torch
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     u = pkg.synthetic.splitmix_uniform
     case = pkg.synthetic.box_case(2, 2, 2)
     asm = eng.Assembly(eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr))
@@ -218,145 +219,34 @@ def test_streaming_kernels_against_the_restatement(pkg, n):
 @pytest.mark.parametrize("name,mode,tables", SHAPES)
 def test_fused_cn_assembly_bit_for_bit(pkg, orc, monkeypatch, name, mode, tables):
     """mi_fvm_assemble_cn against (a) the engine's own unfused sequence -- mi_fvm_ddt_cn, mi_fvm_div, mi_fvm_laplacian, mi_fvm_su / Sp, the
-    mi_vec_axpby combinations, in the order tests/test_assembly.py uses -- and (b) the restatement; and on the same inputs the Euler call (no
-    `crank_nicolson` key) and the backward call against their own unfused sequences."""
-    from conftest import random_graph_case
-    monkeypatch.delenv("MI_ROW16", raising=False); monkeypatch.delenv("MI_XCD_ROWS", raising=False)
-    if tables == "row32":
-        monkeypatch.setenv("MI_ROW16", "0")
-    elif tables == "noxcd":
-        monkeypatch.setenv("MI_XCD_ROWS", "0")
-    monkeypatch.setenv("MI_ROW_BS", "1024" if mode == "fixed1024" else "256")
-    if mode.endswith("unstaged"):
-        monkeypatch.setenv("MI_ROW_CAP", "64")
-    eng, ctx, dev, host, E = _env(pkg)
-    syn = pkg.synthetic
-    case = syn.box_case(31, 23, 19, symmetric=False) if name == "box" else random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=False)
-    if mode.startswith("tiles"):
-        a0 = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-        case = syn.renumber(case, a0.cell_perm())
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr, ordered=True, tile_cell_start=a0.tile_starts())
-        assert addr.is_ordered
-    else:
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-    n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
-    q = _fused_inputs(pkg, n, nf)
-    u = syn.splitmix_uniform
+    mi_vec_axpby combinations, in the order of tests/assembly_support.py::unfused_sequence -- and (b) the restatement; and on the same inputs
+    the Euler call (no `crank_nicolson` key) and the backward call against their own unfused sequences."""
+    F = FusedCase(pkg, orc, monkeypatch, name, mode, tables)
+    eng, dev, host, E, A, addr, q = F.eng, F.dev, F.host, F.E, F.A, F.addr, F.q
+    n, nf, vol, flux, lap = F.n, F.nf, F.vol, F.flux, F.lap
+    u = pkg.synthetic.splitmix_uniform
     ddt0 = [40.0 * (u(181 + k, n) - 0.5) for k in range(3)]
-    A = eng.Assembly(addr)
     rdt, rdt_e = 1.9 / 0.004, 1.0 / 0.004                                  # rDtCoef of the CN call; Euler's and backward's rDeltaT
     cb = bw.coeffs(0.004, 0.01)
-    vol, flux = dev(q["vol"]), dev(q["flux"])
-    uL, dL = orc.fvm_laplacian(n, lo, up, q["delta"], q["gamma"])
     for vi, v in enumerate(VARIANTS):
         if v["corr"] and name != "box":
             continue
         oc = OCS[vi % 3]                                                    # 1.0, 0.9, 0.0, 1.0, 0.9 over the five variants
-        R = v["n_rhs"]
-        DIV = v["div"] is not False
-        wh = None if not DIV else (orc.upwind_weights(q["flux"]) if v["div"] is None else q["w"])
-        wd = dev(q["w"]) if v["div"] == "w" else None
-        ddt = dict(vol=vol, psi_old=[dev(x) for x in q["psi0"][:R]])
-        cn = dict(oc=oc, ddt0=[dev(x) for x in ddt0[:R]])
-        back = dict(coeffs=cb, psi_old_old=[dev(x) for x in q["psi00"][:R]])
-        if v["field"]:
-            ddt.update(rho=dev(q["rho"]), rho_old=dev(q["rho0"])); back["rho_old_old"] = dev(q["rho00"])
-            rkw = dict(rho=q["rho"], rho0=q["rho0"])
-            ekw = dict(rho=ddt["rho"], rho_old=ddt["rho_old"])
-        else:
-            ddt["rho_value"] = 1.2
-            rkw, ekw = dict(rho_value=1.2), dict(rho_value=1.2)
-        div = None
-        if DIV:
-            div = dict(flux=flux, weights=wd)
-            if v["corr"]:
-                grads = [[dev(x) for x in g] for g in q["grad"][:R]]
-                div["correction"] = dict(scale=1.0, cf=[dev(x) for x in q["cf"]], c=[dev(x) for x in q["C"]], grad=grads)
-        lap = dict(delta_coeffs=dev(q["delta"]), gamma_magsf=dev(q["gamma"]))
-        sp = (dev(q["sp"]), -1.0) if v["extras"] else None
-        su = [(1.0, [dev(x) for x in q["su"][:R]]), (-1.0, [dev(x) for x in q["su2"][:R]])] if v["extras"] else []
-
-        def fused(ddt_arg):
-            o = dict(lower=E(nf) if DIV else None, upper=E(nf), diag=E(n), mag=E(n), src=[E(n) for _ in range(R)])
-            A.assemble(o["upper"], o["diag"], lower_out=o["lower"], sources_out=o["src"], ddt=ddt_arg, div=div, laplacian=lap, sp=sp, su=su, sum_mag_out=o["mag"])
-            return o
-
-        def unfused(time):
-            """the scheme-by-scheme calls and their combination, the order of tests/test_assembly.py::_fused_assembly_bit_exact"""
-            cl, cu, cd, lu, ld, dd, ds = E(nf), E(nf), E(n), E(nf), E(n), E(n), [E(n) for _ in range(R)]
-            t = [E(nf) for _ in range(R)]
-            if DIV:
-                wts = wd
-                if wts is None:
-                    wts = E(nf); A.upwind_weights(flux, wts)
-                A.fvm_div(wts, flux, cl, cu, cd)
-                if v["corr"]:
-                    A.linear_upwind_correction(flux, div["correction"]["cf"], div["correction"]["c"], div["correction"]["grad"], t)
-            A.fvm_laplacian(lap["delta_coeffs"], lap["gamma_magsf"], lu, ld)
-            for r in range(R):
-                if time == "cn":
-                    A.fvm_ddt_cn(rdt, oc, vol, ddt["psi_old"][r], cn["ddt0"][r], dd, ds[r], **ekw)
-                elif time == "backward":
-                    A.fvm_ddt_backward(rdt_e, cb, vol, ddt["psi_old"][r], back["psi_old_old"][r], dd, ds[r], rho_old_old=back.get("rho_old_old"), **ekw)
-                elif v["field"]:
-                    A.fvm_ddt_euler_rho(rdt_e, ddt["rho"], ddt["rho_old"], vol, ddt["psi_old"][r], dd, ds[r])
-                else:
-                    A.fvm_ddt_euler(rdt_e, 1.2, vol, ddt["psi_old"][r], dd, ds[r])
-                if v["corr"]:
-                    ivf = E(n); A.surface_integrate(t[r], vol, ivf); A.submul(vol, ivf, ds[r])
-                if v["extras"]:
-                    A.fvm_su(vol, su[0][1][r], ds[r])                           # + su: source -= V*su
-                    p = vol * su[1][1][r]; ds[r].add_(p)                        # == su2: source += V*su2
-            if DIV:
-                A.axpby(1.0, cl, -1.0, lu, cl); A.axpby(1.0, cu, -1.0, lu, cu)
-                A.axpby(1.0, dd, 1.0, cd, dd)
-            else:
-                A.axpby(-1.0, lu, 0.0, lu, cu)
-            A.axpby(1.0, dd, -1.0, ld, dd)
-            if v["extras"]:
-                p = vol * sp[0]; dd.sub_(p)
-            return dict(lower=cl if DIV else None, upper=cu, diag=dd, src=ds, t=t)
-
-        def same(got, seq, what):
-            for key in ("lower", "upper", "diag"):
-                if got[key] is not None:
-                    assert np.array_equal(host(got[key]), host(seq[key])), (v["tag"], what, key)
-            for r in range(R):
-                assert np.array_equal(host(got["src"][r]), host(seq["src"][r])), (v["tag"], what, r)
-
-        got = fused(dict(ddt, r_delta_t=rdt, crank_nicolson=cn))
-        seq = unfused("cn")
-        same(got, seq, "cn")
-        for r in range(R):
+        V = F.variant(v)
+        cn = dict(oc=oc, ddt0=[dev(x) for x in ddt0[:V.R]])
+        rkw = dict(rho=q["rho"], rho0=q["rho0"]) if v["field"] else dict(rho_value=1.2)
+        got = V.fused(dict(V.ddt, r_delta_t=rdt, crank_nicolson=cn))
+        seq = V.unfused(lambda r, dd, ds: A.fvm_ddt_cn(rdt, oc, vol, V.psi_old[r], cn["ddt0"][r], dd, ds, **V.rho))
+        V.assert_same(got, seq, "cn")
+        for r in range(V.R):
             assert np.array_equal(host(cn["ddt0"][r]), ddt0[r])                 # an input only
-        # (b) the restatement
-        if DIV:
-            lB, uB, dB = orc.fvm_div(n, lo, up, wh, q["flux"])
-            lower, upper = lB - uL, uB - uL
-        else:
-            lower, upper = None, -uL
-        for r in range(R):
-            dD, s = fvm_ddt(rdt, oc, q["vol"], q["psi0"][r], ddt0[r], **rkw)
-            if v["corr"]:
-                ivf = orc.surface_integrate(n, lo, up, host(seq["t"][r]), q["vol"])
-                s = s - q["vol"] * ivf
-            if v["extras"]:
-                s = s - q["vol"] * q["su"][r]
-                s = s + q["vol"] * q["su2"][r]
-            assert np.array_equal(host(got["src"][r]), s), (v["tag"], r)
-        diag = ((dD + dB) - dL) if DIV else (dD - dL)
-        if v["extras"]:
-            diag = diag - q["vol"] * q["sp"]
-        assert np.array_equal(host(got["diag"]), diag) and np.array_equal(host(got["upper"]), upper), v["tag"]
-        if DIV:
-            assert np.array_equal(host(got["lower"]), lower), v["tag"]
-        assert np.array_equal(host(got["mag"]), orc.row_face_op(2, n, lo, up, lower, upper, np.zeros(n))), v["tag"]
+        V.assert_restated(got, seq, lambda r: fvm_ddt(rdt, oc, q["vol"], q["psi0"][r], ddt0[r], **rkw))
         # Euler and backward untouched: the same call without the `crank_nicolson` key, and with the `backward` key
-        eul = fused(dict(ddt, r_delta_t=rdt_e))
-        same(eul, unfused("euler"), "euler")
-        bwd = fused(dict(ddt, r_delta_t=rdt_e, backward=back))
-        same(bwd, unfused("backward"), "backward")
-        for r in range(R):
+        eul = V.fused(dict(V.ddt, r_delta_t=rdt_e))
+        V.assert_same(eul, V.unfused(V.euler(rdt_e)), "euler")
+        bwd = V.fused(dict(V.ddt, r_delta_t=rdt_e, backward=bw.backward_arg(V, cb)))
+        V.assert_same(bwd, V.unfused(bw.backward_ddt_call(V, rdt_e, cb)), "backward")
+        for r in range(V.R):
             assert not np.array_equal(host(eul["src"][r]), host(got["src"][r])) and not np.array_equal(host(bwd["src"][r]), host(got["src"][r]))
     # refusals of the CrankNicolson entry point
     ddt = dict(r_delta_t=rdt, vol=vol, psi_old=[dev(q["psi0"][0])])
@@ -436,7 +326,7 @@ def test_time_loop_with_changing_step_sizes(pkg, orc, loop_case, oc):
     PBiCG + DILU, against the same statements walked with the restatement and the oracle's PBiCG; steps 2 and 4 assemble twice.  oc 0: the
     assembled arrays are the Euler assembly's."""
     import torch
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     L = loop_case
     DT, dts, n = L["DT"], L["dts"], L["n"]
     repeat_at = (2, 4)

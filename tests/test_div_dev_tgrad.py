@@ -13,10 +13,11 @@ orc_surface_integrate.  The patch forms are written out with the exact-rational 
 (fma(I_zj, Sf_z, fma(I_xj, Sf_x, I_yj*Sf_y)), the engine's dot rule: DESIGN 3.5a)."""
 import ctypes as C
 import functools
-from fractions import Fraction
 
 import numpy as np
 import pytest
+
+from assembly_support import ROW_MODES, fma_each, gpu_env, set_row_blocks
 
 EPS = np.finfo(np.float64).eps
 COEFF = {"dev": 1.0 / 3.0, "dev2": 2.0 / 3.0}
@@ -24,14 +25,6 @@ MESHES = [(3, 2, 2), (9, 8, 7), (13, 11, 9)]
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
-def fma(a, b, c):
-    """element-wise fma with ONE rounding: exact rational arithmetic, then float() rounds to nearest even"""
-    out = np.empty(a.shape[0])
-    for i, (x, y, z) in enumerate(zip(a.tolist(), b.tolist(), c.tolist())):
-        out[i] = float(Fraction(x) * Fraction(y) + Fraction(z)) if np.isfinite(x) and np.isfinite(y) and np.isfinite(z) else x * y + z
-    return out
-
-
 def x_of(kind, g):
     """dev[2](T(grad)) of nine arrays -> (x[3*k + j] = X_kj, ii)"""
     tr = (g[0] + g[4]) + g[8]
@@ -45,7 +38,7 @@ def y_of(kind, visc, g):
 
 def dot_col(t, j, s):
     """Sf & column j of the tensor t (t[3*k + j]): fma(t_zj, Sf_z, fma(t_xj, Sf_x, t_yj*Sf_y))"""
-    return fma(t[6 + j], s[2], fma(t[j], s[0], t[3 + j] * s[1]))
+    return fma_each(t[6 + j], s[2], fma_each(t[j], s[0], t[3 + j] * s[1]))
 
 
 def internal(orc, M, kind, visc, g, vol):
@@ -77,7 +70,7 @@ def gauss_grad_correct(fc, s, mag, sn, g):
     out = []
     for j in range(len(sn)):
         gc = [g[3 * j + k][fc] for k in range(3)]
-        d = sn[j] - fma(nh[2], gc[2], fma(nh[0], gc[0], nh[1] * gc[1]))
+        d = sn[j] - fma_each(nh[2], gc[2], fma_each(nh[0], gc[0], nh[1] * gc[1]))
         out += [gc[k] + (nh[k] * d) for k in range(3)]
     return out
 
@@ -212,16 +205,6 @@ def test_restatement_solenoidal_field_gives_both_kinds_the_same_bits(pkg, orc):
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def _env(pkg):
-    import torch
-    eng = pkg.engine
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    E = lambda m: torch.full((m,), -77.0, dtype=torch.float64, device="cuda:0")
-    return eng, ctx, dev, host, E
-
-
 def _inputs(M, dims, dev):
     G, nI = M["G"], M["nI"]
     g, visc = fields(dims)
@@ -243,7 +226,7 @@ def test_engine_internal_faces_bit_exact(pkg, orc, dims, kind):
     """(3, 2, 2): one partial block; (9, 8, 7): 504 cells, two 256-cell blocks of the gradient plan; (13, 11, 9): 1 287 cells.  face_out and
     div_out with and without vol against the restatement, and against three mi_flux_div calls on the engine"""
     import torch
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     M = mesh(dims)
     n, nI, lo, up = M["n"], M["nI"], M["lo"], M["up"]
     assert n == {(3, 2, 2): 12, (9, 8, 7): 504, (13, 11, 9): 1287}[dims]
@@ -269,20 +252,16 @@ def test_engine_internal_faces_bit_exact(pkg, orc, dims, kind):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dims", [(9, 8, 7), (13, 11, 9)])
-@pytest.mark.parametrize("mode", ["fixed256", "fixed1024", "tiles", "tiles_unstaged", "fixed_unstaged"])
+@pytest.mark.parametrize("mode", ROW_MODES)
 def test_engine_every_row_plan_gives_the_bits_of_the_default(pkg, monkeypatch, dims, mode):
     """gradient-plan blocks of 256 / 1024 cells, the layout's tiles under ordered addressing, and the unstaged fall-back (MI_ROW_CAP=64): the
     bits of the default plan, which are the restatement's"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     M = mesh(dims)
     n, lo, up = M["n"], M["lo"], M["up"]
     lam, sf, visc, g, V = _inputs(M, dims, dev)
     default = {(k, v): _run(eng, eng.Addressing(ctx, n, lo, up), k, lam, sf, visc, g, V if v else None, E, host) for k in ("dev", "dev2") for v in (True, False)}
-    bs = "1024" if mode == "fixed1024" else "256"
-    monkeypatch.setenv("MI_ROW_BS", bs)                                       # read at the first caller-order operator of an addressing
-    monkeypatch.setenv("MI_GRAD_BS", bs)
-    if mode.endswith("unstaged"):
-        monkeypatch.setenv("MI_ROW_CAP", "64")
+    set_row_blocks(monkeypatch, mode, grad=True)                              # after the default plan's runs above
     if mode.startswith("fixed"):                                              # the 504 cells of (9, 8, 7) are ONE default tile, a numbering that is tile-contiguous
         monkeypatch.setenv("MI_TILE_CELLS", "256")                            # as it stands; tiles of 256 cells permute it, so the fixed blocks are taken
     addr = eng.Addressing(ctx, n, lo, up, ordered=mode.startswith("tiles"))
@@ -299,7 +278,7 @@ def test_engine_every_row_plan_gives_the_bits_of_the_default(pkg, monkeypatch, d
 @pytest.mark.parametrize("n_comp", [1, 3])
 def test_engine_patch_gauss_grad_correct_bit_exact(pkg, n_comp):
     """the box's wall patch (and its inlet): a fixedValue snGrad, deltaCoeffs*(U_b - U_internal), and the zero one of zeroGradient"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     dims = (9, 8, 7)
     M = mesh(dims)
     n = M["n"]
@@ -330,7 +309,7 @@ def test_engine_patch_gauss_grad_correct_bit_exact(pkg, n_comp):
 def test_engine_patch_flux_wall_and_coupled_bit_exact(pkg, kind):
     """NULL weights: the wall patch from its own boundary values (the corrected boundary gradient, a boundary viscosity).  Weights given: the
     first min(64, nI) internal faces posed as a patch whose neighbour values are the upper cells' (weights off 0.5)"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     for dims in ((3, 2, 2), (9, 8, 7)):
         M = mesh(dims)
         n, nI, lo, up, G = M["n"], M["nI"], M["lo"], M["up"], M["G"]
@@ -374,7 +353,7 @@ def test_engine_patch_flux_wall_and_coupled_bit_exact(pkg, kind):
 def test_engine_whole_term_into_the_source(pkg, orc, kind):
     """(9, 8, 7): the internal sums, the patch fluxes added in patch order (corner cells carry two and three boundary faces, from two
     patches and twice from one), /V, then source += V*div (negated with mi_vec_axpby, mi_fvm_su) -- against the same walk in numpy"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     dims = (9, 8, 7)
     M = mesh(dims)
     n, nI, lo, up, G = M["n"], M["nI"], M["lo"], M["up"], M["G"]
@@ -418,7 +397,7 @@ def test_engine_whole_term_into_the_source(pkg, orc, kind):
 
 @pytest.mark.gpu
 def test_engine_refusals_launch_nothing_and_zero_faces_are_ok(pkg):
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     dims = (3, 2, 2)
     M = mesh(dims)
     n, nI, lo, up, G = M["n"], M["nI"], M["lo"], M["up"], M["G"]

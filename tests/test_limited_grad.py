@@ -11,18 +11,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from assembly_support import ROW_MODES, bits, gpu_env, rmax, rmin, same, set_row_blocks, set_row_tables, shape_case, shaped_addressing, signed_flux
+
 SMALL, VSMALL = 1e-15, 1e-300                                   # doubleScalar.H:57-58
 KINDS = ("cellLimited", "cellMDLimited", "faceLimited", "faceMDLimited")
 OTHER, COUPLED, FIXES = 0, 1, 2                                  # MI_GRAD_PATCH_*
-
-
-def rmax(a, b):
-    """Foam::max: (s1 > s2) ? s1 : s2"""
-    return a if a > b else b
-
-
-def rmin(a, b):
-    return a if a < b else b
 
 
 def vmax(a, b):
@@ -33,7 +26,7 @@ def vmin(a, b):
     return np.where(a < b, a, b)
 
 
-def dot(a, b):
+def dot_uncontracted(a, b):
     """Vector & Vector uncontracted: (ax*bx + ay*by) + az*bz"""
     return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
 
@@ -51,14 +44,14 @@ def literal(kind, k, lo, up, C, Cf, vf, grad, patches):
 
     def md(c, j, maxD, minD, dcf):                              # cellMDLimitedGrad<scalar>::limitFace on component j's gradient
         gi = gj(c, j)
-        e = dot(dcf, gi)
+        e = dot_uncontracted(dcf, gi)
         if e > maxD:
             t = maxD - e
         elif e < minD:
             t = minD - e
         else:
             return
-        m = dot(dcf, dcf)
+        m = dot_uncontracted(dcf, dcf)
         g[c][3 * j:3 * j + 3] = [gi[i] + dcf[i] * t / m for i in range(3)]
 
     def lf(lim, maxD, minD, e):                                  # cellLimitedGrad<scalar>::limitFace
@@ -97,7 +90,7 @@ def literal(kind, k, lo, up, C, Cf, vf, grad, patches):
             for c, cf in order:
                 d = sub(cf, C[c])
                 for j in range(nc):
-                    lim[c][j] = lf(lim[c][j], mx[c][j], mn[c][j], dot(d, gj(c, j)))
+                    lim[c][j] = lf(lim[c][j], mx[c][j], mn[c][j], dot_uncontracted(d, gj(c, j)))
             for c in range(n):
                 g[c] = [g[c][3 * j + i] * lim[c][j] for j in range(nc) for i in range(3)]
             return g, lim
@@ -112,15 +105,15 @@ def literal(kind, k, lo, up, C, Cf, vf, grad, patches):
     for f in range(len(lo)):
         o, nb = lo[f], up[f]
         if kind == "faceLimited" and nc == 3:
-            gradf = [dot(sub(Cf[f], C[o]), gj(o, j)) for j in range(3)]
-            sO, sN = dot(gradf, vf[o]), dot(gradf, vf[nb])
+            gradf = [dot_uncontracted(sub(Cf[f], C[o]), gj(o, j)) for j in range(3)]
+            sO, sN = dot_uncontracted(gradf, vf[o]), dot_uncontracted(gradf, vf[nb])
             mxF, mnF = rmax(sO, sN), rmin(sO, sN)
             t = rk * (mxF - mnF); mxF = mxF + t; mnF = mnF - t
-            lim[o] = lf(lim[o], mxF - sO, mnF - sO, dot(gradf, gradf))
-            gradf = [dot(sub(Cf[f], C[nb]), gj(nb, j)) for j in range(3)]
-            sO, sN = dot(gradf, vf[o]), dot(gradf, vf[nb])
+            lim[o] = lf(lim[o], mxF - sO, mnF - sO, dot_uncontracted(gradf, gradf))
+            gradf = [dot_uncontracted(sub(Cf[f], C[nb]), gj(nb, j)) for j in range(3)]
+            sO, sN = dot_uncontracted(gradf, vf[o]), dot_uncontracted(gradf, vf[nb])
             mxF, mnF = rmax(sO, sN), rmin(sO, sN)                     # faceLimitedGrads.C:241-254: not expanded
-            lim[nb] = lf(lim[nb], mxF - sN, mnF - sN, dot(gradf, gradf))
+            lim[nb] = lf(lim[nb], mxF - sN, mnF - sN, dot_uncontracted(gradf, gradf))
             continue
         for j in range(nc):
             vO, vN = vf[o][j], vf[nb][j]
@@ -128,8 +121,8 @@ def literal(kind, k, lo, up, C, Cf, vf, grad, patches):
             if kind == "faceLimited" or expand_md:
                 t = rk * (mxF - mnF); mxF = mxF + t; mnF = mnF - t
             if kind == "faceLimited":
-                lim[o] = lf(lim[o], mxF - vO, mnF - vO, dot(sub(Cf[f], C[o]), gj(o, j)))
-                lim[nb] = lf(lim[nb], mxF - vN, mnF - vN, dot(sub(Cf[f], C[nb]), gj(nb, j)))
+                lim[o] = lf(lim[o], mxF - vO, mnF - vO, dot_uncontracted(sub(Cf[f], C[o]), gj(o, j)))
+                lim[nb] = lf(lim[nb], mxF - vN, mnF - vN, dot_uncontracted(sub(Cf[f], C[nb]), gj(nb, j)))
             else:
                 md(o, j, mxF - vO, mnF - vO, sub(Cf[f], C[o]))
                 md(nb, j, mxF - vN, mnF - vN, sub(Cf[f], C[nb]))
@@ -139,11 +132,11 @@ def literal(kind, k, lo, up, C, Cf, vf, grad, patches):
         for i, o in enumerate(fc):
             d = sub(pcf[i], C[o])
             if kind == "faceLimited" and nc == 3:
-                gradf = [dot(d, gj(o, j)) for j in range(3)]
-                sO, sN = dot(gradf, vf[o]), dot(gradf, val[i])
+                gradf = [dot_uncontracted(d, gj(o, j)) for j in range(3)]
+                sO, sN = dot_uncontracted(gradf, vf[o]), dot_uncontracted(gradf, val[i])
                 mxF, mnF = rmax(sO, sN), rmin(sO, sN)
                 t = rk * (mxF - mnF); mxF = mxF + t; mnF = mnF - t
-                lim[o] = lf(lim[o], mxF - sO, mnF - sO, dot(gradf, gradf))
+                lim[o] = lf(lim[o], mxF - sO, mnF - sO, dot_uncontracted(gradf, gradf))
                 continue
             for j in range(nc):
                 vO, vN = vf[o][j], val[i][j]
@@ -151,7 +144,7 @@ def literal(kind, k, lo, up, C, Cf, vf, grad, patches):
                 if kind == "faceLimited" or expand_md:
                     t = rk * (mxF - mnF); mxF = mxF + t; mnF = mnF - t
                 if kind == "faceLimited":
-                    lim[o] = lf(lim[o], mxF - vO, mnF - vO, dot(d, gj(o, j)))
+                    lim[o] = lf(lim[o], mxF - vO, mnF - vO, dot_uncontracted(d, gj(o, j)))
                 else:
                     md(o, j, mxF - vO, mnF - vO, d)
     if kind == "faceLimited":
@@ -212,11 +205,11 @@ def _lf(lim, m, maxD, minD, e):
 
 def _md(gi, m, maxD, minD, d):
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        e = dot(d, gi)
+        e = dot_uncontracted(d, gi)
         c1 = m & (e > maxD)
         c2 = m & ~c1 & (e < minD)
         t = np.where(c1, maxD - e, minD - e)
-        msq = dot(d, d)
+        msq = dot_uncontracted(d, d)
         u = c1 | c2
         return [np.where(u, gi[i] + d[i] * t / msq, gi[i]) for i in range(3)]
 
@@ -252,7 +245,7 @@ def restate(kind, k, n, lo, up, C, Cf, vf, grad, bcell=None, bkind=None, bv=None
             for j in range(nc):
                 gi = [g[3 * j + i][c] for i in range(3)]
                 if kind == "cellLimited":
-                    lim[j][c] = _lf(lim[j][c], m, mx[j][c], mn[j][c], dot(d, gi))
+                    lim[j][c] = _lf(lim[j][c], m, mx[j][c], mn[j][c], dot_uncontracted(d, gi))
                 else:
                     gi = _md(gi, m, mx[j][c], mn[j][c], d)
                     for i in range(3):
@@ -266,13 +259,13 @@ def restate(kind, k, n, lo, up, C, Cf, vf, grad, bcell=None, bkind=None, bv=None
         d, w, own = _face_data(sl, c, e, lo, up, C, Cf, bcf, v, bv)
         m = np.ones(c.shape[0], bool)
         if kind == "faceLimited" and nc == 3:
-            gf = [dot(d, [g[3 * j + i][c] for i in range(3)]) for j in range(3)]
-            sc, so = dot(gf, [x[c] for x in v]), dot(gf, w)
+            gf = [dot_uncontracted(d, [g[3 * j + i][c] for i in range(3)]) for j in range(3)]
+            sc, so = dot_uncontracted(gf, [x[c] for x in v]), dot_uncontracted(gf, w)
             sO, sN = np.where(own, sc, so), np.where(own, so, sc)
             mxF, mnF = vmax(sO, sN), vmin(sO, sN)
             t = rk * (mxF - mnF)
             mxF, mnF = np.where(own, mxF + t, mxF), np.where(own, mnF - t, mnF)
-            lim[c] = _lf(lim[c], m, mxF - sc, mnF - sc, dot(gf, gf))
+            lim[c] = _lf(lim[c], m, mxF - sc, mnF - sc, dot_uncontracted(gf, gf))
             continue
         for j in range(nc):
             vc = v[j][c]
@@ -282,7 +275,7 @@ def restate(kind, k, n, lo, up, C, Cf, vf, grad, bcell=None, bkind=None, bv=None
                 t = rk * (mxF - mnF); mxF = mxF + t; mnF = mnF - t
             gi = [g[3 * j + i][c] for i in range(3)]
             if kind == "faceLimited":
-                lim[c] = _lf(lim[c], m, mxF - vc, mnF - vc, dot(d, gi))
+                lim[c] = _lf(lim[c], m, mxF - vc, mnF - vc, dot_uncontracted(d, gi))
             else:
                 gi = _md(gi, m, mxF - vc, mnF - vc, d)
                 for i in range(3):
@@ -290,15 +283,6 @@ def restate(kind, k, n, lo, up, C, Cf, vf, grad, bcell=None, bkind=None, bv=None
     if kind == "faceMDLimited":
         return g, None
     return [x * lim for x in g], [lim]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    """bit for bit, signed zeros included"""
-    return np.array_equal(bits(a), bits(b))
 
 
 # ---- meshes: geometry, boundary patches, fields -----------------------------------------------------------------------------------------
@@ -457,9 +441,9 @@ def test_restatement_leaves_the_gradient_of_a_linear_field(pkg, kind, nc):
     and dyadic coefficients: every centre, value and extrapolate is exact, so no face overshoots its bound by a rounding)"""
     M = box_mesh(pkg.synthetic, (8, 6, 5))
     a = [np.array([0.5, -0.25, 0.75]), np.array([-1.0, 0.5, 0.25]), np.array([0.125, 1.0, -0.5])][:nc]
-    vf = [dot(M["C"], x) for x in a]
+    vf = [dot_uncontracted(M["C"], x) for x in a]
     bcf = boundary_flat(M)[2]
-    bv = [dot(bcf, x) for x in a]
+    bv = [dot_uncontracted(bcf, x) for x in a]
     grad = [np.full(M["n"], x[i]) for x in a for i in range(3)]
     for k in (1.0, 0.5):
         g, lim = run_restate(kind, k, M, vf, grad, bv)
@@ -515,15 +499,6 @@ def test_face_limited_vector_keeps_the_neighbour_side_bounds_unexpanded():
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------------------
-def _env(pkg):
-    import torch
-    eng = pkg.engine
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    return eng, ctx, dev, host
-
-
 def _engine_run(eng, A, B, kind, k, M, vf, grad, bv, dev, host, with_limiter=True):
     """mi_limited_grad on device copies -> (grad, limiter or None) on the host"""
     import torch
@@ -553,9 +528,9 @@ def _check(eng, A, B, kind, k, M, vf, grad, bv, dev, host, tag=""):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["box", "skewed", "graph", "skewed_noxcd"])
 def test_every_kind_against_the_restatement(pkg, monkeypatch, name):
-    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of the three-array gradient pass (MI_XCD_ROWS is read by mi_ctx_create)
-        monkeypatch.setenv("MI_XCD_ROWS", "0"); name = name[:-len("_noxcd")]
-    eng, ctx, dev, host = _env(pkg)
+    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of the three-array gradient pass
+        set_row_tables(monkeypatch, "noxcd"); name = name[:-len("_noxcd")]
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
     M = box_mesh(syn, (13, 11, 9)) if name == "box" else skewed((9, 8, 7)) if name == "skewed" else graph_mesh(pkg)
     addr = eng.Addressing(ctx, M["n"], M["lo"], M["up"])
@@ -573,7 +548,7 @@ def test_every_kind_against_the_restatement(pkg, monkeypatch, name):
 @pytest.mark.gpu
 def test_identity_writes_nothing(pkg):
     import torch
-    eng, ctx, dev, host = _env(pkg)
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
     M = box_mesh(syn, (6, 5, 4))
     addr = eng.Addressing(ctx, M["n"], M["lo"], M["up"])
@@ -597,7 +572,7 @@ def test_cyclic_patch_takes_the_patch_neighbour_field(pkg):
     """the box made periodic in x: the two cyclic patches are coupled, their values mi_matrix_patch_neighbour_field; the other four
     walls fixesValue"""
     import torch
-    eng, ctx, dev, host = _env(pkg)
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
     dims = (12, 7, 6)
     M0 = box_mesh(syn, dims)
@@ -634,31 +609,16 @@ def test_cyclic_patch_takes_the_patch_neighbour_field(pkg):
     B.close()
 
 
-def _shape_addr(eng, ctx, syn, case, mode):
-    if mode.startswith("tiles"):
-        a0 = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-        case = syn.renumber(case, a0.cell_perm())
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr, ordered=True, tile_cell_start=a0.tile_starts())
-        assert addr.is_ordered
-        return case, addr
-    return case, eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["fixed256", "fixed1024", "tiles", "tiles_unstaged", "fixed_unstaged"])
+@pytest.mark.parametrize("mode", ROW_MODES)
 def test_every_row_pass_shape(pkg, monkeypatch, mode):
     """gradient plan blocks of 256 / 1024 cells, the layout's tiles under ordered addressing, and the unstaged fall-back (MI_ROW_CAP=64):
     every kind identical to the restatement"""
-    from conftest import random_graph_case
-    eng, ctx, dev, host = _env(pkg)
+    set_row_blocks(monkeypatch, mode, grad=True)
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
-    bs = "1024" if mode == "fixed1024" else "256"
-    monkeypatch.setenv("MI_ROW_BS", bs)
-    monkeypatch.setenv("MI_GRAD_BS", bs)
-    if mode.endswith("unstaged"):
-        monkeypatch.setenv("MI_ROW_CAP", "64")
-    for case in (syn.box_case(31, 23, 19), random_graph_case(pkg, 9000, extra=3.0, seed=5)):
-        case, addr = _shape_addr(eng, ctx, syn, case, mode)
+    for name in ("box", "graph"):
+        case, addr = shaped_addressing(eng, ctx, syn, shape_case(pkg, name, symmetric=True), mode)
         M = random_geometry(syn, case.n_cells, case.lower_addr, case.upper_addr, 70)
         A = eng.Assembly(addr)
         B = eng.GradBoundary(addr, M["fcs"], M["kinds"])
@@ -673,7 +633,7 @@ def test_every_row_pass_shape(pkg, monkeypatch, mode):
 def test_in_place_equals_out_of_place(pkg):
     """the gradient limited where it lies equals a copy limited from the same inputs; the inputs stay as they were"""
     import torch
-    eng, ctx, dev, host = _env(pkg)
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
     M = skewed((8, 7, 6))
     addr = eng.Addressing(ctx, M["n"], M["lo"], M["up"])
@@ -696,7 +656,7 @@ def test_in_place_equals_out_of_place(pkg):
 @pytest.mark.gpu
 def test_argument_errors(pkg):
     import torch
-    eng, ctx, dev, host = _env(pkg)
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
     M = box_mesh(syn, (6, 5, 4))
     addr = eng.Addressing(ctx, M["n"], M["lo"], M["up"])
@@ -747,7 +707,7 @@ def test_argument_errors(pkg):
     B.close(); Bo.close()
 
 
-def fma(a, b, c):
+def fma_signed_zero(a, b, c):
     """one rounding (exact rational arithmetic), with IEEE's sign of a zero result: (+-0) + (+-0) keeps a common sign, any other
     exact zero is +0 -- a limited gradient has exact zeros of both signs (limiter 0)"""
     from fractions import Fraction
@@ -769,7 +729,7 @@ def correction_flux(lo, up, flux, cf, C, grad):
         dx, dy, dz = cf[0][f] - C[0][c], cf[1][f] - C[1][c], cf[2][f] - C[2][c]
         for j in range(3):
             gx, gy, gz = grad[3 * j][c], grad[3 * j + 1][c], grad[3 * j + 2][c]
-            out[j][f] = fl * (1.0 * fma(dz, gz, fma(dx, gx, dy * gy)))
+            out[j][f] = fl * (1.0 * fma_signed_zero(dz, gz, fma_signed_zero(dx, gx, dy * gy)))
     return out
 
 
@@ -778,8 +738,7 @@ def test_cell_limited_feeds_the_linear_upwind_correction(pkg):
     """`grad(U) cellLimited Gauss linear 1` -> `Gauss linearUpwind grad(U)`: mi_gauss_grad + the wall faces + /V, the limiter, then
     mi_linear_upwind_correction, against the restatement chain (the Gauss gradient is the engine's: it has its own tests)"""
     import torch
-    from test_linear_upwind import signed_flux
-    eng, ctx, dev, host = _env(pkg)
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
     M = box_mesh(syn, (11, 9, 7))
     n, lo, up = M["n"], M["lo"], M["up"]
@@ -817,7 +776,7 @@ def test_cell_limited_feeds_the_linear_upwind_correction(pkg):
     rg, _ = run_restate("cellLimited", 1.0, M, U, g0, bv)
     assert all(same(host(x), y) for x, y in zip(grads, rg))
     assert not all(same(x, y) for x, y in zip(rg, g0))
-    flux = signed_flux(u(7, nf), nf)
+    flux = signed_flux(u(7, nf))
     out = [torch.empty(nf, dtype=torch.float64, device="cuda:0") for _ in range(3)]
     A.linear_upwind_correction(dev(flux), Cfd, Cd, [grads[3 * j:3 * j + 3] for j in range(3)], out)
     ref = correction_flux(lo, up, flux, M["Cf"], M["C"], rg)
@@ -828,7 +787,7 @@ def test_cell_limited_feeds_the_linear_upwind_correction(pkg):
 @pytest.mark.gpu
 def test_at_the_bench_size(pkg):
     """216^3 with the six walls: scalar cellLimited and vector cellMDLimited against the vectorised restatement"""
-    eng, ctx, dev, host = _env(pkg)
+    eng, ctx, dev, host, _ = gpu_env(pkg)
     syn = pkg.synthetic
     M = box_mesh(syn, (216, 216, 216))
     addr = eng.Addressing(ctx, M["n"], M["lo"], M["up"])

@@ -3,10 +3,10 @@ and their V (NVDVTVDV.H) and bounded (Limited.H, Limited01.H) forms.  An indepen
 headers, with fma written out exactly (Fraction) where the compiled reference contracts; then mi_limiter_parse on the
 host and the engine's face pass and coupled-patch pass against the restatement, bit for bit (gpu)."""
 import os
-from fractions import Fraction
-
 import numpy as np
 import pytest
+
+from assembly_support import bits, dot_contracted, fma, gpu_env, rmax, rmin, same, set_row_tables, signed_flux
 
 SMALL = 1e-15                                                   # doubleScalar.H: SMALL = 1.0e-15
 KINDS = ["limitedLinear", "vanLeer", "MUSCL", "Minmod", "SuperBee", "UMIST", "vanAlbada", "OSPRE", "QUICK", "limitedCubic", "Gamma", "SFCD"]
@@ -16,14 +16,9 @@ BOUNDED = {"limitedLinear": ("limitedLimitedLinear", "limitedLinear01"), "vanLee
            "Gamma": ("limitedGamma", "Gamma01")}               # makeLLimitedSurfaceInterpolationTypeScheme in vanLeer.C, MUSCL.C, ...
 
 
-def fma(a, b, c):
-    """one rounding: exact rational arithmetic, then float() rounds to nearest even"""
-    return float(Fraction(a) * Fraction(b) + Fraction(c))
-
-
 def dot(a, b):
-    """Vector & Vector as the compiled reference contracts it (and every face pass of the engine): fma(az, bz, fma(ax, bx, ay*by))"""
-    return fma(a[2], b[2], fma(a[0], b[0], a[1] * b[1]))
+    """Vector & Vector of two triples, as the compiled reference contracts it"""
+    return dot_contracted(a[0], a[1], a[2], b[0], b[1], b[2])
 
 
 def sign(s):
@@ -34,16 +29,6 @@ def sign(s):
 def stabilise(s, small):
     """Scalar.H stabilise(): s >= 0 ? s + small : s - small"""
     return s + small if s >= 0 else s - small
-
-
-def rmax(a, b):
-    """doubleScalar max (label.H:285-298 MAXMIN): (s1 > s2) ? s1 : s2 -- max(-0.0, 0.0) is +0.0"""
-    return a if a > b else b
-
-
-def rmin(a, b):
-    """(s1 < s2) ? s1 : s2"""
-    return a if a < b else b
 
 
 def d_and_grad(d, g):
@@ -212,15 +197,6 @@ def restate_patch(kind, vec, bounds, k, fc, pcdw, pflux, phi, nbr_phi, grad, nbr
     return np.array(w), np.array(lim)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    """bit for bit, signed zeros included"""
-    return np.array_equal(bits(a), bits(b))
-
-
 # ---- CPU -----------------------------------------------------------------------------------------------------------------------
 def _names():
     """every registered name with valid coefficients -> (kind, vector_form, bounded, k, lower, upper)"""
@@ -333,16 +309,6 @@ def test_mirror_exposes_the_limited_schemes(pkg, tmp_path):
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def _env(pkg):
-    import torch
-    eng = pkg.engine
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    E = lambda m: torch.empty(m, dtype=torch.float64, device="cuda:0")
-    return eng, ctx, dev, host, E
-
-
 def _schemes():
     """(scheme string, kind name, vec, bounds, k) over every kind x {scalar, V} x {unbounded, the registered bounded forms} x k in {1, 0.33, 0}"""
     out = []
@@ -361,9 +327,7 @@ def _fields(pkg, n, nf, seed):
     """inputs that reach every branch: zero fluxes of both signs, equal and nearly equal neighbour values (gradf == 0, the r guard),
     zero gradients (the phict guard), values either side of the bounds"""
     u = pkg.synthetic.splitmix_uniform
-    flux = u(seed, nf) - 0.45
-    flux[::7] = 0.0
-    flux[3::11] = -0.0
+    flux = signed_flux(u(seed, nf))
     cdw = 0.3 + 0.4 * u(seed + 1, nf)
     phi = []
     for j in range(3):
@@ -395,9 +359,9 @@ def _graded_box(pkg, dims):
 @pytest.mark.parametrize("name", ["box", "graph", "box_noxcd"])
 def test_every_scheme_against_the_restatement(pkg, monkeypatch, name):
     from conftest import random_graph_case
-    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of k_limited_weights (MI_XCD_ROWS is read by mi_ctx_create)
-        monkeypatch.setenv("MI_XCD_ROWS", "0"); name = name[:-len("_noxcd")]
-    eng, ctx, dev, host, E = _env(pkg)
+    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of k_limited_weights
+        set_row_tables(monkeypatch, "noxcd"); name = name[:-len("_noxcd")]
+    eng, ctx, dev, host, E = gpu_env(pkg)
     if name == "box":
         case, Cc = _graded_box(pkg, (9, 8, 7))
     else:
@@ -427,7 +391,7 @@ def test_limited_linear_equals_the_existing_kernel_and_the_reference(pkg):
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import make_golden_ref as mg
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_ref_fvm.npz"))
     cols = lambda a: [dev(np.ascontiguousarray(a[:, k])) for k in range(3)]
     for name, case in mg.fvm_cases(pkg).items():
@@ -446,7 +410,7 @@ def test_limited_linear_equals_the_existing_kernel_and_the_reference(pkg):
 @pytest.mark.gpu
 def test_cyclic_patch_against_the_restatement(pkg):
     """LimitedScheme.C:145-195 on a cyclic channel (x-min <-> x-max): phiN and gradcN from mi_matrix_patch_neighbour_field"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     syn = pkg.synthetic
     u = syn.splitmix_uniform
     dims = (12, 7, 6)
@@ -498,7 +462,7 @@ def test_limited_weights_feed_the_assembly(pkg, orc, scheme):
     """ddt + div - laplacian with the limited weights through mi_fvm_assemble against the oracle's unfused assembly of the same terms
     with the restated weights"""
     from assembly_full_size import oracle_assemble
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     case, Cc = _graded_box(pkg, (10, 9, 8))
     n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
     u = pkg.synthetic.splitmix_uniform
@@ -530,7 +494,7 @@ def test_every_kind_at_the_bench_size(pkg):
     """216^3: every kind, scalar and V, runs over the 30 M faces; 4096 seeded faces per kind against the restatement; limitedLinear
     equals mi_limited_linear_weights over the whole array"""
     import torch
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     case = pkg.synthetic.box_case(216, 216, 216)
     n, nf = case.n_cells, case.n_faces
     A = eng.Assembly(eng.Addressing(ctx, n, case.lower_addr, case.upper_addr))
@@ -569,7 +533,7 @@ def test_every_kind_at_the_bench_size(pkg):
 @pytest.mark.gpu
 def test_argument_errors(pkg):
     import torch
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     case = pkg.synthetic.box_case(6, 5, 4)
     n, nf = case.n_cells, case.n_faces
     flux, cdw, phi, grad = _fields(pkg, n, nf, 800)

@@ -9,33 +9,26 @@ reference and each rounded, so every comparison with the engine is bit for bit:
     limiter = min(k*mag(sn)/((1 - k)*mag(corr) + SMALL), 1)
     result  = limiter*corr                                  then gammaMagSf*result (gaussLaplacianSchemes.C:64-90)
 mag of a vector is sqrt(magSqr) with magSqr contracted as every dot product of the engine's face passes is:
-fma(z, z, fma(x, x, y*y)), written out exactly here with Fraction."""
+fma(z, z, fma(x, x, y*y)), written out exactly with Fraction (assembly_support.fma_each)."""
 import ctypes as C
 import functools
 import os
 import subprocess
-from fractions import Fraction
 
 import numpy as np
 import pytest
+
+from assembly_support import fma_each, gpu_env
 
 SMALL = 1e-15
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
-def fma(a, b, c):
-    """element-wise fma with ONE rounding: exact rational arithmetic, then float() rounds to nearest even (non-finite operands: a*b + c)"""
-    out = np.empty(a.shape[0])
-    for i, (x, y, z) in enumerate(zip(a.tolist(), b.tolist(), c.tolist())):
-        out[i] = float(Fraction(x) * Fraction(y) + Fraction(z)) if np.isfinite(x) and np.isfinite(y) and np.isfinite(z) else x * y + z
-    return out
-
-
 def mag(v):
     """mag(scalar) = fabs; mag(Vector) = sqrt(magSqr), magSqr = fma(z, z, fma(x, x, y*y))"""
     if len(v) == 1:
         return np.abs(v[0])
-    return np.sqrt(fma(v[2], v[2], fma(v[0], v[0], v[1] * v[1])))
+    return np.sqrt(fma_each(v[2], v[2], fma_each(v[0], v[0], v[1] * v[1])))
 
 
 def limit(k, sn, corr, gamma_magsf=None):
@@ -189,23 +182,13 @@ def test_restatement_nan_quotient_gives_limiter_one():
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def _env(pkg):
-    import torch
-    eng = pkg.engine
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    E = lambda m: torch.full((m,), -77.0, dtype=torch.float64, device="cuda:0")
-    return eng, ctx, dev, host, E
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("dims", MESHES)
 @pytest.mark.parametrize("n_comp", [1, 3])
 def test_engine_limited_flux_internal_faces_bit_exact(pkg, orc, dims, n_comp):
     """(3, 2, 2): 20 faces, one partial block; (9, 8, 7): 1 321 faces, several blocks and a tail.  Every k, with and without gammaMagSf,
     with and without the limiter output: flux of every component and the limiter bit for bit"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     M = mesh(dims)
     G, n, nI, lo, up = M["G"], M["n"], M["nI"], M["lo"], M["up"]
     assert nI == {(3, 2, 2): 20, (9, 8, 7): 1321}[dims]
@@ -238,7 +221,7 @@ def test_engine_limited_flux_nan_in_one_cell(pkg, orc, n_comp):
     """a NaN in vf at one cell: the quotient of that cell's faces is NaN, Foam::min gives limiter 1, the flux there is the full correction
     (finite: the gradient arrays are separate inputs here); a NaN in one gradient array at another cell: limiter 1 and a NaN flux in that
     component.  Every other face keeps its bits."""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     dims, k = (9, 8, 7), 0.5
     M = mesh(dims)
     G, n, nI, lo, up = M["G"], M["n"], M["nI"], M["lo"], M["up"]
@@ -268,7 +251,7 @@ def test_engine_limited_flux_nan_in_one_cell(pkg, orc, n_comp):
 @pytest.mark.parametrize("n_comp", [1, 3])
 def test_engine_limited_flux_coupled_patch_bit_exact(pkg, orc, n_comp):
     """the first min(64, nI) internal faces posed as a patch whose neighbour values are the upper cells'"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     for dims in MESHES:
         M = mesh(dims)
         G, n, nI, lo, up = M["G"], M["n"], M["nI"], M["lo"], M["up"]
@@ -299,7 +282,7 @@ def test_engine_limited_flux_coupled_patch_bit_exact(pkg, orc, n_comp):
 
 @pytest.mark.gpu
 def test_engine_limited_flux_refusals_launch_nothing(pkg):
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     dims = (3, 2, 2)
     M = mesh(dims)
     G, n, nI, lo, up = M["G"], M["n"], M["nI"], M["lo"], M["up"]
@@ -356,7 +339,7 @@ def test_engine_limited_laplacian_three_nonorth_correctors(pkg, orc):
     test_engine_nonorth_correction_bit_exact_and_corrected_solve"""
     import torch
     from test_assembly import nonorth_source_correction
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg, fill=-77.0)
     syn = pkg.synthetic
     k = 0.5
     M = mesh((9, 8, 7))

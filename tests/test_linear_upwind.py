@@ -2,20 +2,11 @@
 matrix (gaussConvectionScheme.C:109-112; linearUpwind.C:33-62; LUST.H:104-126).  An independent restatement of the reference's
 functors (CPU), then the engine's face pass, patch pass, LUST weights and the fused assembly against it and against the engine's own
 unfused sequence, bit for bit (gpu)."""
-from fractions import Fraction
-
 import numpy as np
 import pytest
 
-
-def fma(a, b, c):
-    """one rounding: exact rational arithmetic, then float() rounds to nearest even"""
-    return float(Fraction(a) * Fraction(b) + Fraction(c))
-
-
-def dot(dx, dy, dz, gx, gy, gz):
-    """Vector & Vector as every face pass of the engine contracts it: fma(dz, gz, fma(dx, gx, dy*gy))"""
-    return fma(dz, gz, fma(dx, gx, dy * gy))
+from assembly_support import (ROW_MODES, bits, box_centres, dot_contracted, gpu_env, same, set_row_blocks, set_row_tables, shape_case, shaped_addressing,
+                              signed_flux)
 
 
 def restate_internal(lo, up, flux, cf, C, grads, scale):
@@ -28,7 +19,7 @@ def restate_internal(lo, up, flux, cf, C, grads, scale):
         c = lo[f] if fl > 0 else up[f]
         dx, dy, dz = cf[0][f] - C[0][c], cf[1][f] - C[1][c], cf[2][f] - C[2][c]
         for r, g in enumerate(grads):
-            out[r][f] = fl * (scale * dot(dx, dy, dz, g[0][c], g[1][c], g[2][c]))
+            out[r][f] = fl * (scale * dot_contracted(dx, dy, dz, g[0][c], g[1][c], g[2][c]))
     return out
 
 
@@ -44,39 +35,13 @@ def restate_patch(fc, pflux, pcf, C, pd, grads, nbr, scale):
             else:
                 g = [nbr[r][k][i] for k in range(3)]
             e = (dx, dy, dz) if fl > 0 else (dx - pd[0][i], dy - pd[1][i], dz - pd[2][i])
-            out[r][i] = fl * (scale * dot(*e, *g))
+            out[r][i] = fl * (scale * dot_contracted(*e, *g))
     return out
 
 
 def lust_weights(cdw, flux):
     """0.75*w_linear + 0.25*pos(faceFlux): three field operations (numpy evaluates them one by one, no contraction)"""
     return 0.75 * cdw + 0.25 * (flux >= 0).astype(np.float64)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return a.view(np.uint64)
-
-
-def same(a, b):
-    """bit for bit, signed zeros included"""
-    return np.array_equal(bits(a), bits(b))
-
-
-def box_centres(dims):
-    """cell centres of the uniform lexicographic box"""
-    nx, ny, nz = dims
-    h = 1.0 / nx
-    c = np.arange(nx * ny * nz)
-    return [(c % nx + 0.5) * h, ((c // nx) % ny + 0.5) * h, (c // (nx * ny) + 0.5) * h]
-
-
-def signed_flux(u, nf):
-    """both signs, exact zeros of both signs"""
-    f = u - 0.45
-    f[::7] = 0.0
-    f[3::11] = -0.0
-    return f
 
 
 # ---- CPU -----------------------------------------------------------------------------------------------------------------------
@@ -92,7 +57,7 @@ def test_restatement_reconstructs_the_face_value_of_a_linear_field(pkg):
     a, b = np.array([0.75, -1.25, 0.5]), 0.3
     phi = lambda X: a[0] * X[0] + a[1] * X[1] + a[2] * X[2] + b
     grad = [np.full(case.n_cells, a[k]) for k in range(3)]
-    flux = signed_flux(syn.splitmix_uniform(3, case.n_faces), case.n_faces)
+    flux = signed_flux(syn.splitmix_uniform(3, case.n_faces))
     assert np.any(flux > 0) and np.any(flux < 0) and np.any(flux == 0)
     unit = np.where(flux > 0, 1.0, -1.0)                   # the same upwind side as flux, |flux| = 1: t = +-corr exactly
     corr = restate_internal(lo, up, unit, cf, C, [grad], 1.0)[0] * unit
@@ -130,16 +95,6 @@ def test_mirror_exports_the_corrected_convection(pkg):
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def _env(pkg):
-    import torch
-    eng = pkg.engine
-    ctx = eng.Context(0, torch.cuda.current_stream().cuda_stream)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:0")
-    host = lambda t: (torch.cuda.synchronize(), t.cpu().numpy())[1]
-    E = lambda m: torch.empty(m, dtype=torch.float64, device="cuda:0")
-    return eng, ctx, dev, host, E
-
-
 def _mesh(pkg, name):
     """-> (n, lo, up, C, Cf): the box, the skewed mesh, the random graph (seeded centres)"""
     syn = pkg.synthetic
@@ -167,15 +122,15 @@ def _grads(pkg, n, n_rhs, seed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["box", "skewed", "graph", "skewed_noxcd"])
 def test_face_pass_and_lust_weights_against_the_restatement(pkg, monkeypatch, name):
-    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of the face pass (MI_XCD_ROWS is read by mi_ctx_create)
-        monkeypatch.setenv("MI_XCD_ROWS", "0"); name = name[:-len("_noxcd")]
-    eng, ctx, dev, host, E = _env(pkg)
+    if name.endswith("_noxcd"):   # the plain blockIdx.x mapping of the face pass
+        set_row_tables(monkeypatch, "noxcd"); name = name[:-len("_noxcd")]
+    eng, ctx, dev, host, E = gpu_env(pkg)
     syn = pkg.synthetic
     n, lo, up, C, cf = _mesh(pkg, name)
     nf = lo.shape[0]
     addr = eng.Addressing(ctx, n, lo, up)
     A = eng.Assembly(addr)
-    flux = signed_flux(syn.splitmix_uniform(7, nf), nf)
+    flux = signed_flux(syn.splitmix_uniform(7, nf))
     fd, Cd, cfd = dev(flux), [dev(x) for x in C], [dev(x) for x in cf]
     for n_rhs, scale in ((1, 1.0), (3, 1.0), (4, 0.25), (3, 0.25)):
         g = _grads(pkg, n, n_rhs, 60 + n_rhs)
@@ -196,7 +151,7 @@ def test_unfused_sequence_and_the_cyclic_patch(pkg, orc):
     """face pass -> mi_surface_integrate(t, V) -> source -= V*ivf against the oracle's surfaceIntegrate and the rounded product; then a
     cyclic channel: the patch pass with patchNeighbourField gradients, the patch faces added before the division by V -- and the fused
     call refusing that addressing"""
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     syn = pkg.synthetic
     u = syn.splitmix_uniform
     dims = (12, 7, 6)
@@ -204,7 +159,7 @@ def test_unfused_sequence_and_the_cyclic_patch(pkg, orc):
     n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
     C = box_centres(dims); cf = [0.5 * (x[lo] + x[up]) for x in C]
     V = 0.5 + u(1, n); src = u(2, n) - 0.5
-    flux = signed_flux(u(3, nf), nf)
+    flux = signed_flux(u(3, nf))
     g = _grads(pkg, n, 3, 70)
     Cd, cfd, gd, Vd = [dev(x) for x in C], [dev(x) for x in cf], [[dev(x) for x in gr] for gr in g], dev(V)
     addr = eng.Addressing(ctx, n, lo, up)
@@ -229,7 +184,7 @@ def test_unfused_sequence_and_the_cyclic_patch(pkg, orc):
     CA = eng.Assembly(caddr)
     h = 1.0 / dims[0]
     npf = [len(f) for f in fcs]
-    pflux = [signed_flux(u(80 + p, m), m) for p, m in enumerate(npf)]
+    pflux = [signed_flux(u(80 + p, m)) for p, m in enumerate(npf)]
     pcf = [[np.full(npf[p], 0.0 if p == 0 else 1.0), C[1][fcs[p]], C[2][fcs[p]]] for p in range(2)]   # the x = 0 / x = 1 planes
     pd = [[np.full(npf[p], (-h if p == 0 else h) if k == 0 else 0.0) for k in range(3)] for p in range(2)]
     # patchNeighbourField of every gradient component through the engine (the partner patch's cells), concatenated by patch
@@ -314,7 +269,7 @@ def _fused_vs_unfused(pkg, eng, ctx, addr, n, nf, q, cfg, dev, host, E):
 
 def _fused_inputs(pkg, n, nf):
     u = pkg.synthetic.splitmix_uniform
-    q = dict(flux=signed_flux(u(110, nf), nf), vol=0.5 + u(111, n), cdw=0.3 + 0.4 * u(140, nf), delta=1.0 + u(107, nf), gamma=0.5 + u(108, nf),
+    q = dict(flux=signed_flux(u(110, nf)), vol=0.5 + u(111, n), cdw=0.3 + 0.4 * u(140, nf), delta=1.0 + u(107, nf), gamma=0.5 + u(108, nf),
              rho=0.8 + u(135, n), rho0=0.7 + u(136, n), rdt=1.0 / 3e-4, sp=u(153, n),
              psi0=[u(131 + k, n) - 0.5 for k in range(4)], su=[u(154 + k, n) - 0.5 for k in range(4)], su2=[u(158 + k, n) - 0.5 for k in range(4)],
              C=[u(144 + k, n) for k in range(3)], cf=[u(147 + k, nf) for k in range(3)])
@@ -332,23 +287,12 @@ CONFIGS = [
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["fixed256", "fixed1024", "tiles", "tiles_unstaged", "fixed_unstaged"])
+@pytest.mark.parametrize("mode", ROW_MODES)
 @pytest.mark.parametrize("name", ["box", "graph"])
 def test_fused_correction_equals_the_unfused_sequence_bit_for_bit(pkg, monkeypatch, name, mode):
-    from conftest import random_graph_case
-    eng, ctx, dev, host, E = _env(pkg)
-    syn = pkg.synthetic
-    case = syn.box_case(31, 23, 19, symmetric=False) if name == "box" else random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=False)
-    monkeypatch.setenv("MI_ROW_BS", "1024" if mode == "fixed1024" else "256")
-    if mode.endswith("unstaged"):
-        monkeypatch.setenv("MI_ROW_CAP", "64")
-    if mode.startswith("tiles"):
-        a0 = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
-        case = syn.renumber(case, a0.cell_perm())
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr, ordered=True, tile_cell_start=a0.tile_starts())
-        assert addr.is_ordered
-    else:
-        addr = eng.Addressing(ctx, case.n_cells, case.lower_addr, case.upper_addr)
+    set_row_blocks(monkeypatch, mode)
+    eng, ctx, dev, host, E = gpu_env(pkg)
+    case, addr = shaped_addressing(eng, ctx, pkg.synthetic, shape_case(pkg, name), mode)
     n, nf = case.n_cells, case.n_faces
     q = _fused_inputs(pkg, n, nf)
     for cfg in CONFIGS:
@@ -361,7 +305,7 @@ def test_fused_correction_equals_the_unfused_sequence_bit_for_bit(pkg, monkeypat
 @pytest.mark.gpu
 def test_fused_correction_argument_errors(pkg):
     import torch
-    eng, ctx, dev, host, E = _env(pkg)
+    eng, ctx, dev, host, E = gpu_env(pkg)
     syn = pkg.synthetic
     case = syn.box_case(9, 8, 7, symmetric=False)
     n, nf = case.n_cells, case.n_faces
