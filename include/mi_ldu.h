@@ -775,6 +775,75 @@ int mi_fvc_ddt_cn(mi_ctx_t ctx, int64_t n, double r_dt_coef, double oc, double r
 int mi_fvm_assemble_cn(mi_addr_t addr, const mi_fvm_terms *terms, const mi_ddt_cn_terms *cn, const mi_div_correction *corr_or_null,
                        double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev, double *const *source_out_dev,
                        double *sum_mag_off_diag_out_dev_or_null);
+/* ---- steadyState, the local-time-step schemes localEuler and CoEuler, and bounded Gauss convection ----
+ * src/finiteVolume/finiteVolume/ddtSchemes/{steadyStateDdtScheme,localEulerDdtScheme,CoEulerDdtScheme} and convectionSchemes/
+ * boundedConvectionScheme, the static-mesh branches.  Every expression is evaluated by the reference as field operators, one pass and one
+ * rounding each; the engine rounds exactly as parenthesised here (no contraction).  max(a, b) = (a > b) ? a : b.  r = the rDeltaT CELL field.
+ * NOT covered: SLTS, the `bounded` ddt scheme, the alpha*rho overloads, fvcDdtUfCorr, moving meshes, `bounded` together with the backward or
+ *   CrankNicolson assembly forms.
+ * steadyState: fvmDdt is an empty matrix, fvcDdt a zero field, fvcDdtPhiCorr a zero flux -- no call: leave the term out (terms->ddt == 0).
+ * mi_ddt_local_parse (host only): `steadyState` | `localEuler <rDeltaT>` | `CoEuler <phi> <rho> <maxCo>`, any whitespace between and around.
+ *   MI_ERR_ARG with a message naming the token: a missing or an extra word, a maxCo that is not a number, not finite or not > 0, `Euler` /
+ *   `backward` / `CrankNicolson ...` ("not a local scheme"), any other name, a name longer than 63 characters, the empty string, NULL.
+ * mi_fvm_ddt_local: fvmDdt of localEuler (localEulerDdtScheme.C:339-445) and of CoEuler with r = CorDeltaT() (CoEulerDdtScheme.C:459-606)
+ *     rho_dev NULL:  diag = (r*rho_value)*V;  source = ((r*rho_value)*psi0)*V      (rho_value 1: fvm::ddt(vf), r*V and (r*psi0)*V)
+ *     rho_dev given: diag = (r*rho)*V;        source = ((r*rho0)*psi0)*V           (rho and rho_old together)
+ * mi_fvc_ddt_local: fvcDdt (:149-157, :200-209, :255-264; CoEuler :232-452)
+ *     rho_dev NULL:  out = (r*rho_value)*(vf - vf0)
+ *     rho_dev given: out = r*((rho*vf) - (rho0*vf0))
+ *   Both refuse (MI_ERR_ARG) a missing or unaligned array, an output that is also an input or the other output, density arrays given partly.
+ * mi_ddt_phi_corr_local: fvcDdtPhiCorr(U, phi) (:531-560; CoEuler :651-680), internal faces, one face pass: mi_ddt_phi_corr without density and
+ *   with rDeltaT := fvc::interpolate(r) on the face, fma(lambda, r[P] - r[N], r[N]) (surfaceInterpolationScheme.C:275-280):
+ *     out = ((1 - min(|phiCorr|/(|phi0| + SMALL), 1))*rDeltaT_f)*phiCorr,  phiCorr = phi0 - (Sf & interpolate(U0))
+ *   The density forms fvcDdtPhiCorr(rho, U, phi) of both schemes (:653-726) use the GLOBAL 1/deltaT: that is mi_ddt_phi_corr.
+ * mi_co_face_r_delta_t: CoEulerDdtScheme::CofrDeltaT (CoEulerDdtScheme.C:125-167) as a streaming pass over n faces (a patch's: the caller passes
+ *   the patch's own deltaCoeffs, magSf, phi and -- mass flux -- the face density, the old density's boundary values)
+ *     Co = (deltaCoeffs*(|phi|/magSf))*deltaT     [rho_face given: |phi|/(rho_face*magSf)];     out = max(Co/maxCo, 1.0)/deltaT
+ * mi_co_r_delta_t: CoEulerDdtScheme::CorDeltaT (:61-94) on the internal faces in ONE row pass: out[c] = the maximum, from 0.0, of that face value
+ *   over the cell's own faces, then its neighbour-side faces.  No face array is written.  lambda / rho_old given (together): the mass-flux form,
+ *   rho_face = fvc::interpolate(rho.oldTime()) = fma(lambda, rho0[P] - rho0[N], rho0[N]) formed per face from the two cells.  A cell without
+ *   internal faces gets 0.0 -- the patches follow (mi_patch_max per patch, in patch order; all values are positive, so the order is free).
+ *   MI_ERR_ARG: deltaT or maxCo not positive and finite, lambda without rho_old or the reverse, the output among the inputs.
+ * mi_patch_max (declared with mi_patch_add): cell_inout[faceCells[i]] = max(cell_inout[faceCells[i]], pf[i]) (matrixPatchOperation, :99-114).
+ * mi_fvm_assemble_local: mi_fvm_assemble / mi_fvm_assemble_corrected (corr_or_null) with, in the same row pass,
+ *   r_delta_t_dev given: the localEuler / CoEuler time derivative -- mi_fvm_ddt_local's expressions in place of Euler's; terms->ddt != 0 and
+ *     terms->r_delta_t is ignored.  NULL: terms->ddt decides between Euler and no time derivative (steadyState), as in mi_fvm_assemble.
+ *   div_flux_dev given: bounded Gauss convection (boundedConvectionScheme.C:69-92), fvmDiv = scheme.fvmDiv(flux, vf) - fvm::Sp(divPhi, vf) with
+ *     divPhi = fvc::surfaceIntegrate(faceFlux) INCLUDING the boundary faces (mi_surface_integrate without volumes + mi_patch_add per patch +
+ *     mi_vec_div): sumB' = sumB - (V*divPhi) -- the product rounded first (fvmSup.C:118), subtracted from the negSumDiag result
+ *     (lduMatrixOperations.C:319-322) -- before sumB meets the time part.
+ *   The outputs equal mi_fvm_ddt_local (or mi_fvm_ddt_euler*, or nothing) + mi_fvm_div [+ diag_div -= V*divPhi] + mi_fvm_laplacian + the
+ *   mi_vec_axpby combinations bit for bit.  MI_ERR_ARG, nothing launched: loc NULL, both pointers NULL ("use mi_fvm_assemble"), r_delta_t_dev
+ *   with terms->ddt == 0, div_flux_dev without terms->div_flux_dev, either array among the outputs; and every refusal of mi_fvm_assemble[_corrected]. */
+#define MI_DDT_STEADY_STATE 0
+#define MI_DDT_LOCAL_EULER 1
+#define MI_DDT_CO_EULER 2
+typedef struct mi_ddt_local_scheme {
+    int32_t kind;                                  /* MI_DDT_STEADY_STATE | MI_DDT_LOCAL_EULER | MI_DDT_CO_EULER */
+    char name[64];                                 /* localEuler: the rDeltaT field's name; CoEuler: the flux's name */
+    char rho_name[64];                             /* CoEuler: the density's name (read for a mass flux) */
+    double max_co;                                 /* CoEuler */
+} mi_ddt_local_scheme;
+typedef struct mi_fvm_local_terms {
+    const double *r_delta_t_dev;                   /* n cells */
+    const double *div_flux_dev;                    /* n cells: fvc::surfaceIntegrate(faceFlux) */
+} mi_fvm_local_terms;
+int mi_ddt_local_parse(const char *scheme, mi_ddt_local_scheme *out);
+int mi_fvm_ddt_local(mi_ctx_t ctx, int64_t n, const double *r_delta_t_dev, double rho_value, const double *rho_dev, const double *rho_old_dev,
+                     const double *vol_dev, const double *psi_old_dev, double *diag_out_dev, double *source_out_dev);
+int mi_fvc_ddt_local(mi_ctx_t ctx, int64_t n, const double *r_delta_t_dev, double rho_value, const double *rho_dev, const double *rho_old_dev,
+                     const double *vf_dev, const double *vf_old_dev, double *out_dev);
+int mi_ddt_phi_corr_local(mi_addr_t addr, const double *r_delta_t_dev, const double *lambda_dev, const double *sfx_dev, const double *sfy_dev,
+                          const double *sfz_dev, const double *ux_old_dev, const double *uy_old_dev, const double *uz_old_dev,
+                          const double *phi_old_dev, double *out_dev);
+int mi_co_face_r_delta_t(mi_ctx_t ctx, int64_t n, const double *delta_coeffs_dev, const double *mag_sf_dev, const double *phi_dev,
+                         const double *rho_face_dev_or_null, double delta_t, double max_co, double *out_dev);
+int mi_co_r_delta_t(mi_addr_t addr, const double *delta_coeffs_dev, const double *mag_sf_dev, const double *phi_dev,
+                    const double *lambda_dev_or_null, const double *rho_old_dev_or_null, double delta_t, double max_co,
+                    double *r_delta_t_out_dev);
+int mi_fvm_assemble_local(mi_addr_t addr, const mi_fvm_terms *terms, const mi_fvm_local_terms *loc, const mi_div_correction *corr_or_null,
+                          double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev, double *const *source_out_dev,
+                          double *sum_mag_off_diag_out_dev_or_null);
 /* fvMatrix::setReference (src/finiteVolume/fvMatrices/fvMatrix/fvMatrix.C:964-981; icoFoam.C:89, simpleFoam/pEqn.H:21: the pressure level of a
  * closed domain): source[celli] += diag[celli]*value; diag[celli] += diag[celli].  celli < 0 (the rank does not hold the cell): no-op. */
 int mi_fvm_set_reference(mi_addr_t addr, int32_t celli, double value, double *diag_dev, double *source_dev);
@@ -892,6 +961,7 @@ int mi_vec_submul(mi_ctx_t ctx, int64_t n, const double *x_dev, const double *y_
 int mi_patch_create(mi_ctx_t ctx, int32_t n_cells, int32_t n_patch_faces, const int32_t *face_cells_host, mi_patch_t *out);
 int mi_patch_destroy(mi_patch_t patch);
 int mi_patch_add(mi_patch_t patch, const double *pf_dev, double *intf_dev, int fn);
+int mi_patch_max(mi_patch_t patch, const double *pf_dev, double *cell_inout_dev);   /* cell = max(cell, pf) per face cell (CoEuler, above) */
 /* coupled part of fvMatrix::addBoundarySource (fvMatrix.C:318-346; used by fvMatrix::H, :1458-1506):
  * intf[faceCells[i]] +=(fn 0) / -=(fn 1) pf[i]*q[i], e.g. boundaryCoeffs * patchNeighbourField.            */
 int mi_patch_add_product(mi_patch_t patch, const double *pf_dev, const double *q_dev, double *intf_dev, int fn);

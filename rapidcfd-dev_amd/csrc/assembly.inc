@@ -205,13 +205,22 @@ struct AsmCorrBackArgs : AsmCorrArgs { BackIn bw; };
 struct CnIn { double oc; int offc; const double* ddt0[4]; };
 struct AsmCnArgs : AsmArgs { CnIn cn; };
 struct AsmCorrCnArgs : AsmCorrArgs { CnIn cn; };
-// the time form of a row pass: TF_EULER (or no time derivative: a.ddt), TF_BACK, TF_CN; each form's kernels take the arguments of that form only
-enum { TF_EULER = 0, TF_BACK = 1, TF_CN = 2 };
+// LOCAL: the local-time-step derivative (localEulerDdtScheme.C:339-445, CoEulerDdtScheme.C:459-606, static mesh) and / or the bounded Gauss
+// convection (boundedConvectionScheme.C:69-92).  rdt given: Euler's expressions with rDeltaT read per cell, a.rdt ignored; rdt null: a.ddt
+// decides between Euler and no time derivative (steadyState), as in TF_EULER.  divPhi given: sumB - V*divPhi (fvm::Sp(divPhi, vf) subtracted
+// from the convection matrix, the product rounded first: fvmSup.C:118) before sumB meets the time part.  Both are wave-uniform tests.
+struct LocalIn { const double *rdt, *divPhi; };
+struct AsmLocalArgs : AsmArgs { LocalIn loc; };
+struct AsmCorrLocalArgs : AsmCorrArgs { LocalIn loc; };
+// the time form of a row pass: TF_EULER (or no time derivative: a.ddt), TF_BACK, TF_CN, TF_LOCAL; each form's kernels take the arguments of that form only
+enum { TF_EULER = 0, TF_BACK = 1, TF_CN = 2, TF_LOCAL = 3 };
 template <bool CORR, int TF> struct AsmSel { typedef typename std::conditional<CORR, AsmCorrArgs, AsmArgs>::type type; };
 template <> struct AsmSel<false, TF_BACK> { typedef AsmBackArgs type; };
 template <> struct AsmSel<true, TF_BACK> { typedef AsmCorrBackArgs type; };
 template <> struct AsmSel<false, TF_CN> { typedef AsmCnArgs type; };
 template <> struct AsmSel<true, TF_CN> { typedef AsmCorrCnArgs type; };
+template <> struct AsmSel<false, TF_LOCAL> { typedef AsmLocalArgs type; };
+template <> struct AsmSel<true, TF_LOCAL> { typedef AsmCorrLocalArgs type; };
 // fvm::ddt, backward: every product and difference rounded on its own (the reference's field operators; DESIGN 3.5d).  Constant density:
 // rho_value joins the (rDeltaT*V) factor; a density field: rho0 / rho00 join the coefficients inside the bracket.
 __device__ __forceinline__ double back_diag(double cA, double rho, double V) { return (cA * rho) * V; }
@@ -233,7 +242,7 @@ __device__ __forceinline__ double cn_source(double cr, double p0, double offd, d
 template <bool DIV, bool LAP, int BS, bool R16, bool CORR = false, int TF = TF_EULER>
 __global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR, TF>::type a)
 {
-    constexpr bool BACK = TF == TF_BACK, CN = TF == TF_CN;
+    constexpr bool BACK = TF == TF_BACK, CN = TF == TF_CN, LOCAL = TF == TF_LOCAL;
     extern __shared__ __attribute__((aligned(16))) double rp_smem[];
     const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
     int c0, cEnd;
@@ -325,9 +334,14 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR,
     for (int k = 0; k < 3; ++k) if (k < cnt) nei_term((staged && nfk[k] >= f0) ? nei_get(nfk[k]) : nv[k]);
     for (int j = nb + 3; j < ne; ++j) nei_term(nei_get(nei_face(j)));
     const double V = a.vol ? a.vol[c] : 0.0;
+    double rdt = a.rdt;
+    if constexpr (LOCAL) {
+        if (a.loc.rdt) rdt = a.loc.rdt[c];
+        if (DIV && a.loc.divPhi) { const double t = V * a.loc.divPhi[c]; sumB = sumB - t; }
+    }
     double d = 0.0;
     if constexpr (BACK) { const double dA = back_diag(a.bw.cA, a.rho ? a.rho[c] : a.rhoValue, V); d = DIV ? dA + sumB : dA; }
-    else if (CN || a.ddt) { const double dA = (a.rdt * (a.rho ? a.rho[c] : a.rhoValue)) * V; d = DIV ? dA + sumB : dA; }
+    else if (CN || a.ddt) { const double dA = (rdt * (a.rho ? a.rho[c] : a.rhoValue)) * V; d = DIV ? dA + sumB : dA; }
     else if (DIV) d = sumB;
     if (LAP) d = (BACK || CN || a.ddt || DIV) ? d - sumL : -sumL;
     if (a.sp) { const double t = V * a.sp[c]; d = a.spMinus ? d - t : d + t; }
@@ -338,8 +352,8 @@ __global__ __launch_bounds__(BS) void k_row_assemble(const typename AsmSel<CORR,
         if constexpr (BACK)
             s = a.rhoOld ? back_source_rho(a.rdt, a.bw.c0, a.bw.c00, V, a.rhoOld[c], a.psiOld[r][c], a.bw.rhoOldOld[c], a.bw.psiOldOld[r][c])
                          : back_source(a.rdt, a.rhoValue, a.bw.c0, a.bw.c00, V, a.psiOld[r][c], a.bw.psiOldOld[r][c]);
-        else if constexpr (CN) s = cn_source(a.rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue), a.psiOld[r][c], cn_off(a.cn.offc, a.cn.oc, a.cn.ddt0[r][c]), V);
-        else s = a.ddt ? ((a.rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue)) * a.psiOld[r][c]) * V : 0.0;
+        else if constexpr (CN) s = cn_source(rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue), a.psiOld[r][c], cn_off(a.cn.offc, a.cn.oc, a.cn.ddt0[r][c]), V);
+        else s = a.ddt ? ((rdt * (a.rhoOld ? a.rhoOld[c] : a.rhoValue)) * a.psiOld[r][c]) * V : 0.0;
         if (CORR) s = s - vIvf;
         for (int k = 0; k < a.nSu; ++k) { const double t = V * a.su[k * a.nRhs + r][c]; s = a.suMinus[k] ? s + t : s - t; }
         a.sourceOut[r][c] = s;
@@ -649,6 +663,18 @@ __global__ void k_patch_add(const int32_t* __restrict__ cells, const int32_t* __
     }
 }
 
+// cell = max(cell, patch face values) per unique patch cell (matrixPatchOperation with maxOp: CoEulerDdtScheme.C:99-114); (a > b) ? a : b
+__global__ void k_patch_max(const int32_t* __restrict__ cells, const int32_t* __restrict__ start, const int32_t* __restrict__ sort,
+                            const double* __restrict__ pf, double* __restrict__ intf, int nU)
+{
+    for (int u = blockIdx.x * blockDim.x + threadIdx.x; u < nU; u += gridDim.x * blockDim.x) {
+        const int c = cells[u];
+        double out = intf[c];
+        for (int k = start[u]; k < start[u + 1]; ++k) { const double v = pf[sort[k]]; out = v > out ? v : out; }
+        intf[c] = out;
+    }
+}
+
 __global__ __launch_bounds__(RB) void k_relax_dominance(double* __restrict__ D, const double* __restrict__ sumOff, double alpha, int64_t n)
 {
     chunk_loop(n, [&](int64_t i) {
@@ -895,6 +921,140 @@ __global__ void k_ddt_phi_corr_backward(const DdtCorrBackArgs a)
         const double coeff = 1.0 - (q < 1.0 ? q : 1.0);
         a.out[f] = (coeff * a.rdt) * (((a.c0 * p0) - (a.c00 * a.phi00[f])) - fW);
     }
+}
+// ---- the local-time-step schemes localEuler and CoEuler (localEulerDdtScheme.C, CoEulerDdtScheme.C, static mesh; DESIGN 3.5h) ----
+// fvm::ddt (localEulerDdtScheme.C:339-445): Euler's expressions with rDeltaT a cell field -- diag = (r*rho)*V, source = ((r*rho0)*psi0)*V;
+// without a density field rho = rho0 = rhoValue (1: the plain form, r*1 is exact)
+template <bool RHO>
+__global__ __launch_bounds__(RB) void k_fvm_ddt_local(const double* __restrict__ rD, double rhoValue, const double* __restrict__ rho, const double* __restrict__ rho0,
+                                                      const double* __restrict__ vol, const double* __restrict__ psi0, double* __restrict__ diag,
+                                                      double* __restrict__ source, int64_t n)
+{
+    chunk_loop2(n, [&](int64_t i) {
+            const double2 r = ld2(rD, i), v = ld2(vol, i), p0 = ld2(psi0, i);
+            double2 q = make_double2(rhoValue, rhoValue), q0 = q;
+            if (RHO) { q = ld2(rho, i); q0 = ld2(rho0, i); }
+            st2(diag, i, make_double2((r.x * q.x) * v.x, (r.y * q.y) * v.y));
+            st2(source, i, make_double2(((r.x * q0.x) * p0.x) * v.x, ((r.y * q0.y) * p0.y) * v.y));
+        },
+        [&](int64_t i) {
+            const double q = RHO ? rho[i] : rhoValue, q0 = RHO ? rho0[i] : rhoValue;
+            diag[i] = (rD[i] * q) * vol[i]; source[i] = ((rD[i] * q0) * psi0[i]) * vol[i];
+        });
+}
+// fvc::ddt (:149-157, :200-209, :255-264): (r*rhoValue)*(vf - vf0), or r*((rho*vf) - (rho0*vf0)) with a density field
+template <bool RHO>
+__global__ __launch_bounds__(RB) void k_fvc_ddt_local(const double* __restrict__ rD, double rhoValue, const double* __restrict__ rho, const double* __restrict__ rho0,
+                                                      const double* __restrict__ vf, const double* __restrict__ vf0, double* __restrict__ out, int64_t n)
+{
+    auto one = [&](double r, double q, double f, double q0, double f0) { return RHO ? r * ((q * f) - (q0 * f0)) : (r * rhoValue) * (f - f0); };
+    chunk_loop2(n, [&](int64_t i) {
+            const double2 r = ld2(rD, i), f = ld2(vf, i), f0 = ld2(vf0, i);
+            double2 q = make_double2(0.0, 0.0), q0 = q;
+            if (RHO) { q = ld2(rho, i); q0 = ld2(rho0, i); }
+            st2(out, i, make_double2(one(r.x, q.x, f.x, q0.x, f0.x), one(r.y, q.y, f.y, q0.y, f0.y)));
+        },
+        [&](int64_t i) { out[i] = one(rD[i], RHO ? rho[i] : 0.0, vf[i], RHO ? rho0[i] : 0.0, vf0[i]); });
+}
+// fvc::ddtCorr(U, phi) (:531-560): k_ddt_phi_corr with rDeltaT := fvc::interpolate(rDeltaT) on the face, one fma (surfaceInterpolationScheme.C:275-280)
+__global__ void k_ddt_phi_corr_local(const RowPassArgs a, const double* __restrict__ rD, const double* __restrict__ phi0, double* __restrict__ out, int nf)
+{
+    for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += gridDim.x * blockDim.x) {
+        const double p0 = phi0[f];
+        const double phiCorr = p0 - flux_face(a, f);
+        const double q = fabs(phiCorr) / (fabs(p0) + 1e-15);
+        const double coeff = 1.0 - (q < 1.0 ? q : 1.0);
+        const double rn = rD[a.up[f]];
+        const double rf = fma(a.a0[f], rD[a.lo[f]] - rn, rn);
+        out[f] = (coeff * rf) * phiCorr;
+    }
+}
+// CoEulerDdtScheme::CofrDeltaT on one face (CoEulerDdtScheme.C:125-167), every field operator rounded on its own:
+//   Co = (deltaCoeffs*(|phi|/magSf))*deltaT  [mass flux: |phi|/(rho_f*magSf)];  x = max(Co/maxCo, 1)/deltaT,  max(a, b) = (a > b) ? a : b
+__device__ __forceinline__ double co_face_x(double dc, double phi, double magSf, bool mass, double rhoF, double deltaT, double maxCo)
+{
+    const double den = mass ? rhoF * magSf : magSf;
+    const double co = (dc * (fabs(phi) / den)) * deltaT;
+    const double q = co / maxCo;
+    return (q > 1.0 ? q : 1.0) / deltaT;
+}
+// ... as a streaming pass over n faces (a patch's): rhoF null: volumetric flux
+__global__ __launch_bounds__(RB) void k_co_face_r_delta_t(const double* __restrict__ dc, const double* __restrict__ magSf, const double* __restrict__ phi,
+                                                          const double* __restrict__ rhoF, double deltaT, double maxCo, double* __restrict__ out, int64_t n)
+{
+    const bool mass = rhoF != nullptr;
+    chunk_loop2(n, [&](int64_t i) {
+            const double2 d = ld2(dc, i), m = ld2(magSf, i), p = ld2(phi, i);
+            const double2 r = mass ? ld2(rhoF, i) : make_double2(0.0, 0.0);
+            st2(out, i, make_double2(co_face_x(d.x, p.x, m.x, mass, r.x, deltaT, maxCo), co_face_x(d.y, p.y, m.y, mass, r.y, deltaT, maxCo)));
+        },
+        [&](int64_t i) { out[i] = co_face_x(dc[i], phi[i], magSf[i], mass, mass ? rhoF[i] : 0.0, deltaT, maxCo); });
+}
+// CoEulerDdtScheme::CorDeltaT on the internal faces (:61-94: matrixOperation with maxOp from 0.0, own faces then neighbour-side faces) in ONE
+// row pass on k_row_pass's skeleton: a block forms x_f of its own faces once and stages them in LDS, cut neighbour-side faces are recomputed
+// from the inputs before the barrier, every cell takes its max; no face array is written (the reference: about six face passes, the
+// temporaries and the row gather).  Mass flux (rho given): rho_f = fvc::interpolate(rho.oldTime()) gathered at the face's two cells.
+struct CoArgs {
+    const uint32_t* row16; const uint16_t* losort16; const int32_t *esc, *escStart;
+    const int32_t *os, *ls, *losort, *blockStart;
+    int n, cap, xcd;
+    const double *delta, *magSf, *phi, *lam, *rho;   // lam, rho null: volumetric flux
+    const int32_t *lo, *up;                           // caller-order face addressing (read with rho)
+    double deltaT, maxCo;
+    double* out;
+};
+template <int BS, bool R16>
+__global__ __launch_bounds__(BS) void k_co_r_delta_t(const CoArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double rp_smem[];
+    const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
+    int c0, cEnd;
+    if (a.blockStart) { c0 = a.blockStart[lb]; cEnd = a.blockStart[lb + 1]; }
+    else { c0 = lb * BS; cEnd = min(c0 + BS, a.n); }
+    const int tid = threadIdx.x, c = c0 + tid;
+    const bool live = c < cEnd;
+    const int f0 = a.os[c0], nf = a.os[cEnd] - f0;
+    const bool staged = nf <= a.cap;
+    const bool mass = a.rho != nullptr;
+    double* sX = rp_smem;
+    auto face = [&](int f) -> double {
+        double rhoF = 0.0;
+        if (mass) { const double rn = a.rho[a.up[f]]; rhoF = fma(a.lam[f], a.rho[a.lo[f]] - rn, rn); }
+        return co_face_x(a.delta[f], a.phi[f], a.magSf[f], mass, rhoF, a.deltaT, a.maxCo);
+    };
+    if (staged)
+        for (int j = tid; j < nf; j += BS) sX[j] = face(f0 + j);
+    int nb = 0, ne = 0, ob = 0, oe = 0;
+    const int escBase = R16 ? a.escStart[lb] : 0;
+    if (live) {
+        if (R16) {
+            const uint32_t w1 = a.row16[c], w0 = tid ? a.row16[c - 1] : 0u;
+            const int lsBase = a.ls[c0];
+            ob = f0 + (int)(w0 & 0xFFFFu); oe = f0 + (int)(w1 & 0xFFFFu); nb = lsBase + (int)(w0 >> 16); ne = lsBase + (int)(w1 >> 16);
+        } else { nb = a.ls[c]; ne = a.ls[c + 1]; ob = a.os[c]; oe = a.os[c + 1]; }
+    }
+    auto nei_face = [&](int j) -> int {
+        if (!R16) return a.losort[j];
+        const unsigned e = a.losort16[j];
+        return (e & 0x8000u) ? a.esc[escBase + (int)(e & 0x7FFFu)] : f0 + (int)e;
+    };
+    // cut neighbour-side faces are recomputed from the inputs (same roundings) before the barrier
+    const int cnt = ne - nb;
+    int nfk[3]; double nv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        nfk[k] = (k < cnt) ? nei_face(nb + k) : 0;
+        nv[k] = (k < cnt && (!staged || nfk[k] < f0)) ? face(nfk[k]) : 0.0;
+    }
+    __syncthreads();
+    if (!live) return;
+    double acc = 0.0;
+    auto take = [&](double x) { acc = x > acc ? x : acc; };
+    for (int j = ob; j < oe; ++j) take(staged ? sX[j - f0] : face(j));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) if (k < cnt) take((staged && nfk[k] >= f0) ? sX[nfk[k] - f0] : nv[k]);
+    for (int j = nb + 3; j < ne; ++j) { const int f = nei_face(j); take((staged && f >= f0) ? sX[f - f0] : face(f)); }
+    a.out[c] = acc;
 }
 __global__ __launch_bounds__(RB) void k_upwind_weights(const double* __restrict__ flux, double* __restrict__ w, int64_t n)
 {
@@ -1356,6 +1516,18 @@ extern "C" int mi_patch_add(mi_patch_t p, const double* pf_dev, double* intf_dev
     return MI_OK;
 }
 
+// cell_inout[faceCells] = max(cell_inout[faceCells], pf): the patch part of CoEulerDdtScheme::CorDeltaT
+extern "C" int mi_patch_max(mi_patch_t p, const double* pf_dev, double* cell_inout_dev)
+{
+    if (!p || !cell_inout_dev || (p->nFaces > 0 && !pf_dev)) return fail(MI_ERR_ARG, "mi_patch_max: bad argument");
+    if (pf_dev == cell_inout_dev) return fail(MI_ERR_ARG, "mi_patch_max: the patch field must not be the cell field");
+    if (p->nUnique == 0) return MI_OK;
+    HIPCHK(hipSetDevice(p->ctx->device));
+    k_patch_max<<<grid_for(p->nUnique), 256, 0, p->ctx->stream>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, cell_inout_dev, p->nUnique);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+
 // coupled part of fvMatrix::addBoundarySource (fvMatrix.C:318-346): source[faceCells] += boundaryCoeffs * patchNeighbourField
 extern "C" int mi_patch_add_product(mi_patch_t p, const double* pf_dev, const double* q_dev, double* intf_dev, int fn)
 {
@@ -1577,8 +1749,8 @@ extern "C" int mi_lust_weights(mi_ctx_t c, int64_t n_faces, const double* cd_wei
 
 // [fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- explicit terms] in one row pass (k_row_assemble)
 namespace {
-// the time form of one assembly: Euler (or no time derivative), or the inputs of backward / CrankNicolson as their entry read them
-struct TimeForm { int form; BackIn bw; CnIn cn; };
+// the time form of one assembly: Euler (or no time derivative), or the inputs of backward / CrankNicolson / the local forms as their entry read them
+struct TimeForm { int form; BackIn bw; CnIn cn; LocalIn loc; };
 struct AsmOut { double *lower, *upper, *diag; double* const* source; double* sumMag; };
 int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const TimeForm& tf, const mi_div_correction* corr, const AsmOut& o);
 int n_rhs_held(const mi_fvm_terms* t) { return std::min(std::max(t->n_rhs, 0), 4); } // assemble_impl refuses a count outside 0..4
@@ -1592,7 +1764,7 @@ extern "C" int mi_fvm_assemble(mi_addr_t a, const mi_fvm_terms* t, double* lower
 extern "C" int mi_fvm_assemble_corrected(mi_addr_t a, const mi_fvm_terms* t, const mi_div_correction* corr, double* lower_out_dev, double* upper_out_dev,
                                          double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
 {
-    return assemble_impl(a, t, TimeForm{TF_EULER, {}, {}}, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
+    return assemble_impl(a, t, TimeForm{TF_EULER, {}, {}, {}}, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
 }
 // ... with the backward time derivative in place of Euler's (BACK), with or without the correction
 extern "C" int mi_fvm_assemble_backward(mi_addr_t a, const mi_fvm_terms* t, const mi_ddt_backward* bw, const mi_div_correction* corr, double* lower_out_dev,
@@ -1602,7 +1774,7 @@ extern "C" int mi_fvm_assemble_backward(mi_addr_t a, const mi_fvm_terms* t, cons
     if (!t->ddt) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: terms->ddt is 0 (no time derivative: mi_fvm_assemble)");
     if ((bw->rho_old_old_dev != nullptr) != (t->rho_dev != nullptr)) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: rho, rho_old and rho_old_old go together");
     if (t->n_rhs > 0 && !bw->psi_old_old_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_backward: old-old fields missing");
-    TimeForm tf{TF_BACK, {bw->coefft * t->r_delta_t, bw->coefft0, bw->coefft00, bw->rho_old_old_dev, {}}, {}};
+    TimeForm tf{TF_BACK, {bw->coefft * t->r_delta_t, bw->coefft0, bw->coefft00, bw->rho_old_old_dev, {}}, {}, {}};
     for (int r = 0; r < n_rhs_held(t); ++r) tf.bw.psiOldOld[r] = bw->psi_old_old_dev[r];
     return assemble_impl(a, t, tf, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
 }
@@ -1614,8 +1786,28 @@ extern "C" int mi_fvm_assemble_cn(mi_addr_t a, const mi_fvm_terms* t, const mi_d
     if (!t->ddt) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: terms->ddt is 0 (no time derivative: mi_fvm_assemble)");
     if (!(cn->oc >= 0.0 && cn->oc <= 1.0)) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: the off-centring coefficient should be >= 0 and <= 1");
     if (t->n_rhs > 0 && !cn->ddt0_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble_cn: ddt0 fields missing");
-    TimeForm tf{TF_CN, {}, {cn->oc, cn->oc < 1.0 ? 1 : 0, {}}};
+    TimeForm tf{TF_CN, {}, {cn->oc, cn->oc < 1.0 ? 1 : 0, {}}, {}};
     for (int r = 0; r < n_rhs_held(t); ++r) tf.cn.ddt0[r] = cn->ddt0_dev[r];
+    return assemble_impl(a, t, tf, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
+}
+// ... with the local-time-step derivative (localEuler / CoEuler: rDeltaT a cell field) and / or the bounded Gauss convection (LOCAL), with or
+// without the correction
+extern "C" int mi_fvm_assemble_local(mi_addr_t a, const mi_fvm_terms* t, const mi_fvm_local_terms* loc, const mi_div_correction* corr, double* lower_out_dev,
+                                     double* upper_out_dev, double* diag_out_dev, double* const* source_out_dev, double* sum_mag_off_diag_out_dev)
+{
+    const char* who = "mi_fvm_assemble_local";
+    if (!a || !t || !loc) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!loc->r_delta_t_dev && !loc->div_flux_dev) return fail(MI_ERR_ARG, std::string(who) + ": neither r_delta_t_dev nor div_flux_dev (use mi_fvm_assemble)");
+    if (loc->r_delta_t_dev && !t->ddt) return fail(MI_ERR_ARG, std::string(who) + ": r_delta_t_dev with terms->ddt == 0 (steadyState takes no rDeltaT field)");
+    if (loc->div_flux_dev && !t->div_flux_dev) return fail(MI_ERR_ARG, std::string(who) + ": bounded (div_flux_dev) without a convection term (terms->div_flux_dev is NULL)");
+    if (loc->div_flux_dev && !t->vol_dev) return fail(MI_ERR_ARG, std::string(who) + ": cell volumes needed");
+    for (const double* q : {loc->r_delta_t_dev, loc->div_flux_dev}) {
+        if (!q) continue;
+        bool hit = q == lower_out_dev || q == upper_out_dev || q == diag_out_dev || q == sum_mag_off_diag_out_dev;
+        for (int r = 0; source_out_dev && r < n_rhs_held(t); ++r) hit = hit || q == source_out_dev[r];
+        if (hit) return fail(MI_ERR_ARG, std::string(who) + ": r_delta_t_dev / div_flux_dev must not be an output");
+    }
+    TimeForm tf{TF_LOCAL, {}, {}, {loc->r_delta_t_dev, loc->div_flux_dev}};
     return assemble_impl(a, t, tf, corr, {lower_out_dev, upper_out_dev, diag_out_dev, source_out_dev, sum_mag_off_diag_out_dev});
 }
 namespace {
@@ -1635,6 +1827,7 @@ int asm_launch(mi_addr_s* a, const mi_fvm_terms* t, const TimeForm& tf, const Co
     if constexpr (CORR) { ra.lo = a->lowerAddr.p; ra.up = a->upperAddr.p; ra.corr = corr; }
     if constexpr (TF == TF_BACK) ra.bw = tf.bw;
     if constexpr (TF == TF_CN) ra.cn = tf.cn;
+    if constexpr (TF == TF_LOCAL) ra.loc = tf.loc;
     ra.os = a->ownerStartC.p; ra.ls = a->losortStartC.p; ra.losort = a->losortC.p;
     ra.row16 = a->row16.p; ra.losort16 = a->losort16.p; ra.esc = a->rowEsc.p; ra.escStart = a->rowEscStart.p;
     const mi_addr_s::RowPlan& rp = a->rowPlan[0];
@@ -1707,6 +1900,7 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const TimeForm& tf, const 
         if (!t->su_dev[j]) return fail(MI_ERR_ARG, "mi_fvm_assemble: null explicit term");
     if (tf.form == TF_BACK) return asm_launch_tf<TF_BACK>(DIV, LAP, CORR, a, t, tf, ci, o);
     if (tf.form == TF_CN) return asm_launch_tf<TF_CN>(DIV, LAP, CORR, a, t, tf, ci, o);
+    if (tf.form == TF_LOCAL) return asm_launch_tf<TF_LOCAL>(DIV, LAP, CORR, a, t, tf, ci, o);
     return asm_launch_tf<TF_EULER>(DIV, LAP, CORR, a, t, tf, ci, o);
 }
 } // namespace
@@ -2368,6 +2562,143 @@ extern "C" int mi_fvc_ddt_cn(mi_ctx_t c, int64_t n, double r_dt_coef, double oc,
     else k_fvc_ddt_cn<false><<<RG, RB, 0, c->stream>>>(r_dt_coef * rho_value, oc, offc, nullptr, nullptr, vf_dev, vf_old_dev, ddt0_dev, out_dev, n);
     HIPCHK(hipGetLastError());
     return MI_OK;
+}
+// ---- steadyState, localEuler and CoEuler (steadyStateDdtScheme.C, localEulerDdtScheme.C, CoEulerDdtScheme.C, static mesh; DESIGN 3.5h) ----
+extern "C" int mi_ddt_local_parse(const char* scheme, mi_ddt_local_scheme* out)
+{
+    const char* who = "mi_ddt_local_parse";
+    if (!scheme || !out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument (NULL)");
+    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
+    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
+    for (const char* c = scheme; *c;) {
+        while (*c && sp(*c)) ++c;
+        const char* b = c;
+        while (*c && !sp(*c)) ++c;
+        if (c > b) tok.emplace_back(b, c);
+    }
+    if (tok.empty()) return fail(MI_ERR_ARG, std::string(who) + ": empty scheme");
+    const std::string& name = tok[0];
+    if (name == "Euler" || name == "backward" || name == "CrankNicolson") return fail(MI_ERR_ARG, std::string(who) + ": '" + name + "' is not a local scheme");
+    size_t words = 0;                                            // what follows the scheme's name
+    const char* takes = "";
+    if (name == "steadyState") { words = 0; takes = "no argument"; }
+    else if (name == "localEuler") { words = 1; takes = "the name of the rDeltaT field"; }
+    else if (name == "CoEuler") { words = 3; takes = "the flux's name, the density's name and maxCo"; }
+    else return fail(MI_ERR_ARG, std::string(who) + ": '" + name + "' is not steadyState, localEuler or CoEuler");
+    if (tok.size() - 1 < words) return fail(MI_ERR_ARG, std::string(who) + ": '" + name + "' takes " + takes + ": " + std::to_string(tok.size() - 1) + " of " + std::to_string(words) + " given after '" + tok.back() + "'");
+    if (tok.size() - 1 > words) return fail(MI_ERR_ARG, std::string(who) + ": '" + name + "' takes " + takes + ": extra '" + tok[words + 1] + "'");
+    mi_ddt_local_scheme s{};
+    for (size_t k = 1; k < tok.size() && k <= 2; ++k)
+        if (tok[k].size() >= sizeof(s.name)) return fail(MI_ERR_ARG, std::string(who) + ": the name '" + tok[k] + "' is longer than " + std::to_string(sizeof(s.name) - 1) + " characters");
+    if (name == "steadyState") s.kind = MI_DDT_STEADY_STATE;
+    else if (name == "localEuler") { s.kind = MI_DDT_LOCAL_EULER; std::memcpy(s.name, tok[1].c_str(), tok[1].size()); }
+    else {
+        s.kind = MI_DDT_CO_EULER;
+        std::memcpy(s.name, tok[1].c_str(), tok[1].size()); std::memcpy(s.rho_name, tok[2].c_str(), tok[2].size());
+        char* end = nullptr;
+        const double m = std::strtod(tok[3].c_str(), &end);
+        if (end == tok[3].c_str() || *end != '\0' || m != m) return fail(MI_ERR_ARG, std::string(who) + ": maxCo '" + tok[3] + "' is not a number");
+        if (!(m > 0.0) || m - m != 0.0) return fail(MI_ERR_ARG, std::string(who) + ": maxCo = " + tok[3] + " should be finite and > 0");
+        s.max_co = m;
+    }
+    *out = s;
+    return MI_OK;
+}
+extern "C" int mi_fvm_ddt_local(mi_ctx_t c, int64_t n, const double* r_delta_t_dev, double rho_value, const double* rho_dev, const double* rho_old_dev,
+                                const double* vol_dev, const double* psi_old_dev, double* diag_out_dev, double* source_out_dev)
+{
+    const char* who = "mi_fvm_ddt_local";
+    if (!c || n < 0) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    const bool RHO = rho_dev || rho_old_dev;
+    if (RHO && !(rho_dev && rho_old_dev)) return fail(MI_ERR_ARG, std::string(who) + ": rho and rho_old go together");
+    const double* in[5] = {r_delta_t_dev, vol_dev, psi_old_dev, rho_dev, rho_old_dev};
+    double* out[2] = {diag_out_dev, source_out_dev};
+    MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 2));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (RHO) k_fvm_ddt_local<true><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, rho_dev, rho_old_dev, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
+    else k_fvm_ddt_local<false><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, nullptr, nullptr, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+extern "C" int mi_fvc_ddt_local(mi_ctx_t c, int64_t n, const double* r_delta_t_dev, double rho_value, const double* rho_dev, const double* rho_old_dev,
+                                const double* vf_dev, const double* vf_old_dev, double* out_dev)
+{
+    const char* who = "mi_fvc_ddt_local";
+    if (!c || n < 0) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    const bool RHO = rho_dev || rho_old_dev;
+    if (RHO && !(rho_dev && rho_old_dev)) return fail(MI_ERR_ARG, std::string(who) + ": rho and rho_old go together");
+    const double* in[5] = {r_delta_t_dev, vf_dev, vf_old_dev, rho_dev, rho_old_dev};
+    double* out[1] = {out_dev};
+    MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 1));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (RHO) k_fvc_ddt_local<true><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, rho_dev, rho_old_dev, vf_dev, vf_old_dev, out_dev, n);
+    else k_fvc_ddt_local<false><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, nullptr, nullptr, vf_dev, vf_old_dev, out_dev, n);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+extern "C" int mi_ddt_phi_corr_local(mi_addr_t a, const double* r_delta_t_dev, const double* lambda_dev, const double* sfx_dev, const double* sfy_dev,
+                                     const double* sfz_dev, const double* ux_old_dev, const double* uy_old_dev, const double* uz_old_dev,
+                                     const double* phi_old_dev, double* out_dev)
+{
+    const char* who = "mi_ddt_phi_corr_local";
+    RowPassArgs ra{};
+    MICHK(flux_args(a, who, lambda_dev, sfx_dev, sfy_dev, sfz_dev, ux_old_dev, uy_old_dev, uz_old_dev, ra));
+    if (!r_delta_t_dev || !phi_old_dev || !out_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    for (const double* q : {r_delta_t_dev, lambda_dev, sfx_dev, sfy_dev, sfz_dev, ux_old_dev, uy_old_dev, uz_old_dev})
+        if (q == out_dev) return fail(MI_ERR_ARG, std::string(who) + ": the output must not alias an input that other faces read");
+    if (a->L.nFaces == 0) return MI_OK;
+    k_ddt_phi_corr_local<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, r_delta_t_dev, phi_old_dev, out_dev, a->L.nFaces);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+namespace {
+int co_scalars(const char* who, double delta_t, double max_co)
+{
+    if (!(delta_t > 0.0) || delta_t - delta_t != 0.0) return fail(MI_ERR_ARG, std::string(who) + ": deltaT must be positive and finite");
+    if (!(max_co > 0.0) || max_co - max_co != 0.0) return fail(MI_ERR_ARG, std::string(who) + ": maxCo must be positive and finite");
+    return MI_OK;
+}
+} // namespace
+extern "C" int mi_co_face_r_delta_t(mi_ctx_t c, int64_t n, const double* delta_coeffs_dev, const double* mag_sf_dev, const double* phi_dev,
+                                    const double* rho_face_dev_or_null, double delta_t, double max_co, double* out_dev)
+{
+    const char* who = "mi_co_face_r_delta_t";
+    if (!c || n < 0) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    MICHK(co_scalars(who, delta_t, max_co));
+    const double* in[4] = {delta_coeffs_dev, mag_sf_dev, phi_dev, rho_face_dev_or_null};
+    double* out[1] = {out_dev};
+    MICHK(stream_arrays(who, in, rho_face_dev_or_null ? 4 : 3, out, 1));
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    k_co_face_r_delta_t<<<RG, RB, 0, c->stream>>>(delta_coeffs_dev, mag_sf_dev, phi_dev, rho_face_dev_or_null, delta_t, max_co, out_dev, n);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+extern "C" int mi_co_r_delta_t(mi_addr_t a, const double* delta_coeffs_dev, const double* mag_sf_dev, const double* phi_dev, const double* lambda_dev_or_null,
+                               const double* rho_old_dev_or_null, double delta_t, double max_co, double* r_delta_t_out_dev)
+{
+    const char* who = "mi_co_r_delta_t";
+    if (!a || !delta_coeffs_dev || !mag_sf_dev || !phi_dev || !r_delta_t_out_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if ((lambda_dev_or_null != nullptr) != (rho_old_dev_or_null != nullptr))
+        return fail(MI_ERR_ARG, std::string(who) + ": the mass-flux form takes lambda and rho_old together");
+    MICHK(co_scalars(who, delta_t, max_co));
+    for (const double* q : {delta_coeffs_dev, mag_sf_dev, phi_dev, lambda_dev_or_null, rho_old_dev_or_null})
+        if (q == r_delta_t_out_dev) return fail(MI_ERR_ARG, std::string(who) + ": the output must not alias an input (cut faces are recomputed from the inputs)");
+    HIPCHK(hipSetDevice(a->ctx->device));
+    MICHK(ensure_caller_tables(a));
+    if (a->L.nCells == 0) return MI_OK;
+    CoArgs ra{};
+    ra.delta = delta_coeffs_dev; ra.magSf = mag_sf_dev; ra.phi = phi_dev; ra.lam = lambda_dev_or_null; ra.rho = rho_old_dev_or_null;
+    ra.lo = a->lowerAddr.p; ra.up = a->upperAddr.p; ra.deltaT = delta_t; ra.maxCo = max_co; ra.out = r_delta_t_out_dev;
+    ra.os = a->ownerStartC.p; ra.ls = a->losortStartC.p; ra.losort = a->losortC.p;
+    ra.row16 = a->row16.p; ra.losort16 = a->losort16.p; ra.esc = a->rowEsc.p; ra.escStart = a->rowEscStart.p;
+    const mi_addr_s::RowPlan& rp = a->rowPlan[0];
+    ra.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
+    ra.n = a->L.nCells; ra.cap = row_cap(rp, 1); ra.xcd = a->ctx->xcdRows;
+    const size_t lds = (size_t)ra.cap * sizeof(double);
+    return for_row_shape(a, rp, [&](auto s) { return row_launch(a, rp, k_co_r_delta_t<decltype(s)::bs, decltype(s)::r16>, ra, lds); });
 }
 extern "C" int mi_upwind_weights(mi_ctx_t c, int64_t n_faces, const double* face_flux_dev, double* weights_out_dev)
 {

@@ -74,6 +74,8 @@ SYMBOLS = [
     "mi_grad_limiter_parse", "mi_grad_boundary_create", "mi_grad_boundary_destroy", "mi_limited_grad",
     "mi_ddt_backward_coeffs", "mi_fvm_ddt_backward", "mi_fvc_ddt_backward", "mi_ddt_phi_corr_backward", "mi_fvm_assemble_backward",
     "mi_ddt_cn_parse", "mi_ddt_cn_begin", "mi_ddt_cn_step", "mi_ddt_cn_update", "mi_fvm_ddt_cn", "mi_fvc_ddt_cn", "mi_fvm_assemble_cn",
+    "mi_ddt_local_parse", "mi_fvm_ddt_local", "mi_fvc_ddt_local", "mi_ddt_phi_corr_local", "mi_co_face_r_delta_t", "mi_co_r_delta_t", "mi_patch_max",
+    "mi_fvm_assemble_local",
     "mi_sngrad_parse", "mi_sngrad_limited_correction_flux", "mi_patch_sngrad_limited_correction_flux",
     "mi_fvc_div_dev_tgrad", "mi_patch_gauss_grad_correct", "mi_patch_dev_tgrad_flux",
 ]
@@ -893,6 +895,10 @@ class Patch:
     def add(self, pf, intf, fn: int = 0):
         _chk(lib().mi_patch_add(self.h, _ptr(pf), _ptr(intf), int(fn)))
 
+    def max(self, pf, cell_inout):
+        """cell_inout[faceCells] = max(cell_inout[faceCells], pf): the patch part of CoEuler's CorDeltaT (mi_patch_max)"""
+        _chk(lib().mi_patch_max(self.h, _ptr(pf), _ptr(cell_inout)))
+
     def add_product(self, pf, q, intf, fn: int = 0):
         """intf[faceCells] += pf*q (coupled part of addBoundarySource)"""
         _chk(lib().mi_patch_add_product(self.h, _ptr(pf), _ptr(q), _ptr(intf), int(fn)))
@@ -1017,6 +1023,28 @@ class CrankNicolson:
         out = DdtCnScalars()
         _chk(lib().mi_ddt_cn_step(C.byref(self.state), C.c_int32(time_index), C.c_double(delta_t), C.c_double(delta_t0), C.byref(out)))
         return (out.r_dt_coef, out.r_dt_coef0, bool(out.evaluate))
+
+
+class DdtLocalScheme(C.Structure):
+    """mi_ddt_local_scheme (include/mi_ldu.h)"""
+    _fields_ = [("kind", C.c_int32), ("name", C.c_char * 64), ("rho_name", C.c_char * 64), ("max_co", C.c_double)]
+
+
+class FvmLocalTerms(C.Structure):
+    """mi_fvm_local_terms (include/mi_ldu.h)"""
+    _fields_ = [("r_delta_t_dev", C.c_void_p), ("div_flux_dev", C.c_void_p)]
+
+
+def ddt_local_parse(scheme):
+    """`steadyState` -> dict(kind="steadyState"); `localEuler <rDeltaT>` -> dict(kind="localEuler", r_delta_t=name); `CoEuler <phi> <rho> <maxCo>`
+    -> dict(kind="CoEuler", phi=, rho=, max_co=) (mi_ddt_local_parse; host only, no GPU); anything else raises MiError"""
+    s = DdtLocalScheme()
+    _chk(lib().mi_ddt_local_parse(None if scheme is None else str(scheme).encode(), C.byref(s)))
+    if s.kind == 0:
+        return dict(kind="steadyState")
+    if s.kind == 1:
+        return dict(kind="localEuler", r_delta_t=s.name.decode())
+    return dict(kind="CoEuler", phi=s.name.decode(), rho=s.rho_name.decode(), max_co=s.max_co)
 
 
 class DivCorrection(C.Structure):
@@ -1207,6 +1235,32 @@ class Assembly:
         _chk(lib().mi_fvc_ddt_cn(self.addr.ctx.h, C.c_int64(vf.numel()), C.c_double(r_dt_coef), C.c_double(oc), C.c_double(rho_value), _ptr(rho), _ptr(rho_old),
                                  _ptr(vf), _ptr(vf_old), _ptr(ddt0), _ptr(out)))
 
+    def fvm_ddt_local(self, r_delta_t, vol, psi_old, diag_out, source_out, rho_value=1.0, rho=None, rho_old=None):
+        """fvm::ddt([rho,] vf), localEuler / CoEuler (localEulerDdtScheme.C:339-445): r_delta_t the rDeltaT CELL field"""
+        _chk(lib().mi_fvm_ddt_local(self.addr.ctx.h, C.c_int64(vol.numel()), _ptr(r_delta_t), C.c_double(rho_value), _ptr(rho), _ptr(rho_old), _ptr(vol),
+                                    _ptr(psi_old), _ptr(diag_out), _ptr(source_out)))
+
+    def fvc_ddt_local(self, r_delta_t, vf, vf_old, out, rho_value=1.0, rho=None, rho_old=None):
+        """fvc::ddt([rho,] vf), localEuler / CoEuler (localEulerDdtScheme.C:149-157, 200-209, 255-264)"""
+        _chk(lib().mi_fvc_ddt_local(self.addr.ctx.h, C.c_int64(vf.numel()), _ptr(r_delta_t), C.c_double(rho_value), _ptr(rho), _ptr(rho_old), _ptr(vf),
+                                    _ptr(vf_old), _ptr(out)))
+
+    def ddt_phi_corr_local(self, r_delta_t, lam, sf, u_old, phi_old, out):
+        """fvc::ddtCorr(U, phi), localEuler / CoEuler, on the internal faces (localEulerDdtScheme.C:531-560): rDeltaT interpolated per face"""
+        _chk(lib().mi_ddt_phi_corr_local(self.addr.h, _ptr(r_delta_t), _ptr(lam), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(u_old[0]), _ptr(u_old[1]),
+                                         _ptr(u_old[2]), _ptr(phi_old), _ptr(out)))
+
+    def co_face_r_delta_t(self, delta_coeffs, mag_sf, phi, delta_t, max_co, out, rho_face=None):
+        """CoEuler's face rDeltaT max(Co/maxCo, 1)/deltaT as a streaming pass (a patch's faces; CoEulerDdtScheme.C:125-167); rho_face: mass flux"""
+        _chk(lib().mi_co_face_r_delta_t(self.addr.ctx.h, C.c_int64(out.numel()), _ptr(delta_coeffs), _ptr(mag_sf), _ptr(phi), _ptr(rho_face),
+                                        C.c_double(delta_t), C.c_double(max_co), _ptr(out)))
+
+    def co_r_delta_t(self, delta_coeffs, mag_sf, phi, delta_t, max_co, out, lam=None, rho_old=None):
+        """CoEuler's cell rDeltaT over the internal faces in one row pass (CoEulerDdtScheme.C:61-94); lam and rho_old together: mass flux.  The
+        patches follow with Patch.max"""
+        _chk(lib().mi_co_r_delta_t(self.addr.h, _ptr(delta_coeffs), _ptr(mag_sf), _ptr(phi), _ptr(lam), _ptr(rho_old), C.c_double(delta_t),
+                                   C.c_double(max_co), _ptr(out)))
+
     def upwind_weights(self, face_flux, w_out):
         _chk(lib().mi_upwind_weights(self.addr.ctx.h, C.c_int64(face_flux.numel()), _ptr(face_flux), _ptr(w_out)))
 
@@ -1285,12 +1339,16 @@ class Assembly:
         ddt["backward"] = dict(coeffs=ddt_backward_coeffs(...), psi_old_old=[...], rho_old_old=None | tensor): the backward time derivative in place of
         Euler's (mi_fvm_assemble_backward), with or without the correction.
         ddt["crank_nicolson"] = dict(oc=, ddt0=[...]): the CrankNicolson time derivative (mi_fvm_assemble_cn); r_delta_t carries rDtCoef and the ddt0
-        fields are already updated for this time step.  Not together with "backward"."""
+        fields are already updated for this time step.  Not together with "backward".
+        ddt["local"] = dict(r_delta_t=tensor): the localEuler / CoEuler time derivative, rDeltaT a cell field (mi_fvm_assemble_local; the scalar r_delta_t is
+        ignored).  Not together with "backward" or "crank_nicolson".
+        div["bounded"] = tensor: bounded Gauss convection, the tensor fvc::surfaceIntegrate(faceFlux) with the boundary faces (mi_fvm_assemble_local); with
+        ddt["local"], with Euler, or with no time derivative (steadyState)."""
         t = FvmTerms()
         n_rhs = len(sources_out)
         keep = []
-        if ddt is not None and "r_delta_t" in ddt:
-            t.ddt = 1; t.r_delta_t = float(ddt["r_delta_t"]); t.rho_value = float(ddt.get("rho_value", 1.0))
+        if ddt is not None and ("r_delta_t" in ddt or "local" in ddt):
+            t.ddt = 1; t.r_delta_t = float(ddt.get("r_delta_t", 0.0)); t.rho_value = float(ddt.get("rho_value", 1.0))
             t.rho_dev = _ptr(ddt.get("rho")).value; t.rho_old_dev = _ptr(ddt.get("rho_old")).value
             po = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in ddt["psi_old"]]); keep.append(po)
             t.psi_old_dev = C.cast(po, C.POINTER(C.c_void_p))
@@ -1311,9 +1369,18 @@ class Assembly:
         corr = (div or {}).get("correction")
         back = (ddt or {}).get("backward")
         cn = (ddt or {}).get("crank_nicolson")
+        local = (ddt or {}).get("local")
+        bounded = (div or {}).get("bounded")
         if back is not None and cn is not None:
             raise MiError("Assembly.assemble: ddt takes 'backward' or 'crank_nicolson', not both")
-        if cn is not None:
+        if (local is not None or bounded is not None) and (back is not None or cn is not None):
+            raise MiError("Assembly.assemble: ddt['local'] and div['bounded'] do not combine with 'backward' or 'crank_nicolson'")
+        if local is not None or bounded is not None:
+            b = FvmLocalTerms()
+            b.r_delta_t_dev = _ptr(None if local is None else local["r_delta_t"]).value
+            b.div_flux_dev = _ptr(bounded).value
+            entry, form = lib().mi_fvm_assemble_local, (C.byref(b),)
+        elif cn is not None:
             b = DdtCnTerms()
             b.oc = float(cn["oc"])
             d0 = (C.c_void_p * max(n_rhs, 1))(*[_ptr(x) for x in cn["ddt0"]]); keep.append(d0)

@@ -1344,4 +1344,188 @@ void fvc::limitedGrad(vectorgpuField* const g[3], const lduAddressing& a, const 
                             limiter ? lim : nullptr), "fvc::grad (limited)");
 }
 
+// ---- steadyState, localEuler, CoEuler and the bounded convection scheme ----
+namespace {
+mi_ddt_local_scheme parseLocal(const std::string& scheme, int kind, const char* name)
+{
+    mi_ddt_local_scheme s{};
+    miCheck(mi_ddt_local_parse(scheme.c_str(), &s), "ddtSchemes");
+    if (s.kind != kind) FatalErrorIn("ddtSchemes", "'" + scheme + "' is not " + name);
+    return s;
+}
+}
+fv::steadyStateDdtScheme fv::steadyStateDdtScheme::New(const std::string& scheme)
+{
+    parseLocal(scheme, MI_DDT_STEADY_STATE, "steadyState");
+    return steadyStateDdtScheme();
+}
+fv::localEulerDdtScheme fv::localEulerDdtScheme::New(const std::string& scheme)
+{
+    return localEulerDdtScheme(parseLocal(scheme, MI_DDT_LOCAL_EULER, "localEuler").name);
+}
+void fv::localEulerDdtScheme::bind(const word& name, const scalargpuField& rDeltaT)
+{
+    if (name != rDeltaTName_) FatalErrorIn("localEulerDdtScheme", "the scheme reads the field '" + rDeltaTName_ + "', not '" + name + "'");
+    field_ = &rDeltaT;
+}
+const scalargpuField& fv::localEulerDdtScheme::localRDeltaT() const
+{
+    if (!field_) FatalErrorIn("localEulerDdtScheme", "no field '" + rDeltaTName_ + "' (bind it first)");
+    return *field_;
+}
+const scalargpuField* fv::localEulerDdtScheme::rDeltaT(label nCells)
+{
+    if (localRDeltaT().size() != nCells) FatalErrorIn("localEulerDdtScheme", "the field '" + rDeltaTName_ + "' has another size than the mesh");
+    return field_;
+}
+fv::CoEulerDdtScheme::CoEulerDdtScheme(const word& phiName, const word& rhoName, scalar maxCo)
+    : phiName_(phiName), rhoName_(rhoName), maxCo_(maxCo), deltaT_(0), addr_(nullptr), deltaCoeffs_(nullptr), magSf_(nullptr), weights_(nullptr), phi_(nullptr),
+      rhoOld_(nullptr)
+{
+    if (!(maxCo_ > 0)) FatalErrorIn("CoEulerDdtScheme", "maxCo = " + std::to_string(maxCo_) + " should be > 0");
+}
+fv::CoEulerDdtScheme fv::CoEulerDdtScheme::New(const std::string& scheme)
+{
+    const mi_ddt_local_scheme s = parseLocal(scheme, MI_DDT_CO_EULER, "CoEuler");
+    return CoEulerDdtScheme(s.name, s.rho_name, s.max_co);
+}
+void fv::CoEulerDdtScheme::setMesh(const lduAddressing& a, const scalargpuField& deltaCoeffs, const scalargpuField& magSf, const scalargpuField& weights)
+{
+    addr_ = &a; deltaCoeffs_ = &deltaCoeffs; magSf_ = &magSf; weights_ = &weights;
+}
+void fv::CoEulerDdtScheme::bind(const word& phiName, const scalargpuField& phi, const word& rhoName, const scalargpuField* rhoOld)
+{
+    if (phiName != phiName_) FatalErrorIn("CoEulerDdtScheme", "the scheme reads the flux '" + phiName_ + "', not '" + phiName + "'");
+    if (rhoOld && rhoName != rhoName_) FatalErrorIn("CoEulerDdtScheme", "the scheme reads the density '" + rhoName_ + "', not '" + rhoName + "'");
+    phi_ = &phi; rhoOld_ = rhoOld;
+}
+void fv::CoEulerDdtScheme::addPatch(const fvPatchCells& cells, const scalargpuField& pDeltaCoeffs, const scalargpuField& pMagSf, const scalargpuField& pPhi,
+                                    const scalargpuField* pRhoOld)
+{
+    patches_.push_back({&cells, &pDeltaCoeffs, &pMagSf, &pPhi, pRhoOld});
+}
+void fv::CoEulerDdtScheme::CorDeltaT(scalargpuField& rDeltaT) const
+{
+    if (!addr_ || !phi_) FatalErrorIn("CoEulerDdtScheme", "setMesh and bind('" + phiName_ + "', ...) come first");
+    miCheck(mi_co_r_delta_t(addr_->handle(), deltaCoeffs_->data(), magSf_->data(), phi_->data(), rhoOld_ ? weights_->data() : nullptr,
+                            rhoOld_ ? rhoOld_->data() : nullptr, deltaT_, maxCo_, rDeltaT.data()), "CoEulerDdtScheme::CorDeltaT");
+    for (const patchIn& p : patches_) {
+        if (p.cells->size() == 0) continue;
+        if (rhoOld_ && !p.rhoOld) FatalErrorIn("CoEulerDdtScheme", "a mass flux needs the old density '" + rhoName_ + "' on every patch");
+        scalargpuField x(p.cells->size());
+        miCheck(mi_co_face_r_delta_t(miEngine::New().ctx, x.size(), p.deltaCoeffs->data(), p.magSf->data(), p.phi->data(), rhoOld_ ? p.rhoOld->data() : nullptr,
+                                     deltaT_, maxCo_, x.data()), "CoEulerDdtScheme::CofrDeltaT");
+        miCheck(mi_patch_max(p.cells->handle(), x.data(), rDeltaT.data()), "CoEulerDdtScheme::CorDeltaT");
+    }
+}
+const scalargpuField* fv::CoEulerDdtScheme::rDeltaT(label nCells)
+{
+    if (!rDeltaT_ || rDeltaT_->size() != nCells) rDeltaT_.reset(new scalargpuField(nCells));
+    CorDeltaT(*rDeltaT_);
+    return rDeltaT_.get();
+}
+bool fv::boundedConvection(std::vector<std::string>& entry)
+{
+    if (entry.empty() || entry[0] != "bounded") return false;
+    entry.erase(entry.begin());
+    return true;
+}
+void fvm::assembleLocal(lduMatrix& M, scalargpuField* const* sources, const scalargpuField* rDeltaT, scalar rho, const scalargpuField& V,
+                        const scalargpuField* const* psiOld, int nRhs, const scalargpuField* faceFlux, const scalargpuField* weights, const scalargpuField* deltaCoeffs,
+                        const scalargpuField* gammaMagSf, const scalargpuField* divPhi, const linearUpwindCorrection* corr, const scalargpuField* su)
+{
+    const char* where = "fvm::assemble (steadyState | localEuler | CoEuler, bounded)";
+    if (nRhs < 1 || nRhs > 3 || !sources || !psiOld) FatalErrorIn(where, "1 to 3 right-hand sides, " + std::to_string(nRhs) + " given");
+    mi_fvm_terms t{};
+    t.ddt = rDeltaT ? 1 : 0; t.rho_value = rho; t.vol_dev = V.data();
+    t.div_flux_dev = faceFlux ? faceFlux->data() : nullptr; t.div_weights_dev = weights ? weights->data() : nullptr;
+    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
+    const double* po[3]; double* so[3];
+    for (int r = 0; r < nRhs; ++r) { po[r] = psiOld[r]->data(); so[r] = sources[r]->data(); }
+    t.n_rhs = nRhs; t.psi_old_dev = po;
+    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
+    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
+    mi_div_correction k{};
+    if (corr) k = divCorrection(*corr, (std::size_t)nRhs);
+    const mi_addr_t a = M.lduAddr().handle();
+    double *lower = faceFlux ? M.lower().data() : nullptr, *upper = M.upper().data(), *diag = M.diag().data();
+    if (!rDeltaT && !divPhi) {                        // steadyState with a plain convection scheme: the assembly without a time derivative
+        miCheck(mi_fvm_assemble_corrected(a, &t, corr ? &k : nullptr, lower, upper, diag, so, nullptr), where);
+        return;
+    }
+    const mi_fvm_local_terms loc{rDeltaT ? rDeltaT->data() : nullptr, divPhi ? divPhi->data() : nullptr};
+    miCheck(mi_fvm_assemble_local(a, &t, &loc, corr ? &k : nullptr, lower, upper, diag, so, nullptr), where);
+}
+void fvm::assembleBounded(fvScalarMatrix& M, scalar rDeltaT, scalar rho, const scalargpuField& V, const scalargpuField& psiOld, const scalargpuField& faceFlux,
+                          const scalargpuField* weights, const scalargpuField* deltaCoeffs, const scalargpuField* gammaMagSf, const scalargpuField& divPhi,
+                          const linearUpwindCorrection* corr, const scalargpuField* su)
+{
+    mi_fvm_terms t{};
+    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = rho; t.vol_dev = V.data();
+    t.div_flux_dev = faceFlux.data(); t.div_weights_dev = weights ? weights->data() : nullptr;
+    t.lap_delta_coeffs_dev = deltaCoeffs ? deltaCoeffs->data() : nullptr; t.lap_gamma_magsf_dev = gammaMagSf ? gammaMagSf->data() : nullptr;
+    const double* po[1] = {psiOld.data()}; double* so[1] = {M.source().data()};
+    t.n_rhs = 1; t.psi_old_dev = po;
+    const double* sd[1] = {su ? su->data() : nullptr}; const double sg[1] = {1.0};
+    if (su) { t.n_su = 1; t.su_dev = sd; t.su_sign = sg; }
+    mi_div_correction k{};
+    if (corr) k = divCorrection(*corr, 1);
+    const mi_fvm_local_terms loc{nullptr, divPhi.data()};
+    miCheck(mi_fvm_assemble_local(M.lduAddr().handle(), &t, &loc, corr ? &k : nullptr, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr),
+            "fvm::assemble (bounded)");
+}
+namespace {
+void ddtLocal(fvScalarMatrix& M, const scalargpuField* r, scalar rho, const scalargpuField& V, const scalargpuField& psiOld)
+{
+    if (!r) {                                         // steadyState: the empty matrix
+        miDeviceZero(M.diag().data(), sizeof(scalar) * (std::size_t)M.diag().size());
+        miDeviceZero(M.source().data(), sizeof(scalar) * (std::size_t)M.source().size());
+        return;
+    }
+    miCheck(mi_fvm_ddt_local(miEngine::New().ctx, V.size(), r->data(), rho, nullptr, nullptr, V.data(), psiOld.data(), M.diag().data(), M.source().data()),
+            "fvm::ddt (localEuler | CoEuler)");
+}
+void fvcDdtLocal(scalargpuField& out, const scalargpuField* r, const scalargpuField& vf, const scalargpuField& vfOld)
+{
+    if (!r) { miDeviceZero(out.data(), sizeof(scalar) * (std::size_t)out.size()); return; }
+    miCheck(mi_fvc_ddt_local(miEngine::New().ctx, vf.size(), r->data(), 1.0, nullptr, nullptr, vf.data(), vfOld.data(), out.data()), "fvc::ddt (localEuler | CoEuler)");
+}
+void ddtCorrLocal(scalargpuField& out, const lduAddressing& a, const scalargpuField* r, const scalargpuField& weights, const vectorgpuField& Sf,
+                  const vectorgpuField& Uold, const scalargpuField& phiOld)
+{
+    if (!r) { miDeviceZero(out.data(), sizeof(scalar) * (std::size_t)out.size()); return; }
+    miCheck(mi_ddt_phi_corr_local(a.handle(), r->data(), weights.data(), Sf.component(0).data(), Sf.component(1).data(), Sf.component(2).data(),
+                                  Uold.component(0).data(), Uold.component(1).data(), Uold.component(2).data(), phiOld.data(), out.data()),
+            "fvc::ddtCorr (localEuler | CoEuler)");
+}
+}
+void fvm::ddt(fvScalarMatrix& M, fv::steadyStateDdtScheme& s, scalar rho, const scalargpuField& V, const scalargpuField& psiOld) { ddtLocal(M, s.rDeltaT(V.size()), rho, V, psiOld); }
+void fvm::ddt(fvScalarMatrix& M, fv::localEulerDdtScheme& s, scalar rho, const scalargpuField& V, const scalargpuField& psiOld) { ddtLocal(M, s.rDeltaT(V.size()), rho, V, psiOld); }
+void fvm::ddt(fvScalarMatrix& M, fv::CoEulerDdtScheme& s, scalar rho, const scalargpuField& V, const scalargpuField& psiOld) { ddtLocal(M, s.rDeltaT(V.size()), rho, V, psiOld); }
+void fvc::ddt(scalargpuField& out, fv::steadyStateDdtScheme& s, const scalargpuField& vf, const scalargpuField& vfOld) { fvcDdtLocal(out, s.rDeltaT(vf.size()), vf, vfOld); }
+void fvc::ddt(scalargpuField& out, fv::localEulerDdtScheme& s, const scalargpuField& vf, const scalargpuField& vfOld) { fvcDdtLocal(out, s.rDeltaT(vf.size()), vf, vfOld); }
+void fvc::ddt(scalargpuField& out, fv::CoEulerDdtScheme& s, const scalargpuField& vf, const scalargpuField& vfOld) { fvcDdtLocal(out, s.rDeltaT(vf.size()), vf, vfOld); }
+void fvc::ddtCorr(scalargpuField& out, const lduAddressing& a, fv::steadyStateDdtScheme& s, const scalargpuField& weights, const vectorgpuField& Sf,
+                  const vectorgpuField& Uold, const scalargpuField& phiOld)
+{
+    ddtCorrLocal(out, a, s.rDeltaT(Uold.size()), weights, Sf, Uold, phiOld);
+}
+void fvc::ddtCorr(scalargpuField& out, const lduAddressing& a, fv::localEulerDdtScheme& s, const scalargpuField& weights, const vectorgpuField& Sf,
+                  const vectorgpuField& Uold, const scalargpuField& phiOld)
+{
+    ddtCorrLocal(out, a, s.rDeltaT(Uold.size()), weights, Sf, Uold, phiOld);
+}
+void fvc::ddtCorr(scalargpuField& out, const lduAddressing& a, fv::CoEulerDdtScheme& s, const scalargpuField& weights, const vectorgpuField& Sf,
+                  const vectorgpuField& Uold, const scalargpuField& phiOld)
+{
+    ddtCorrLocal(out, a, s.rDeltaT(Uold.size()), weights, Sf, Uold, phiOld);
+}
+void fvc::divBounded(scalargpuField& out, const lduAddressing& a, const scalargpuField& faceFlux, const scalargpuField* weights, const scalargpuField& vf,
+                     const scalargpuField& V, const scalargpuField& divPhi)
+{
+    scalargpuField face(faceFlux.size());
+    miCheck(mi_fvc_div(a.handle(), faceFlux.data(), weights ? weights->data() : nullptr, vf.data(), V.data(), face.data(), out.data()), "fvc::div (bounded)");
+    fieldSubMul(out, divPhi, vf);                     // - (divPhi*vf): the product rounded first
+}
+
 } // namespace Foam

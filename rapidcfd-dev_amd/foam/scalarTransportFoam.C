@@ -4,7 +4,7 @@
 //         solve(fvm::ddt(T) + fvm::div(phi, T) - fvm::laplacian(DT, T) == fvOptions(T));        // (no fvOptions here)
 //
 // in a given velocity field, on a case directory: constant/polyMesh, constant/transportProperties (DT), system/controlDict (deltaT, endTime,
-// writeFormat, writePrecision), system/fvSchemes (ddt(T): Euler | backward | CrankNicolson <oc>; div(phi,T): Gauss linear | upwind | limitedLinear k; laplacian: Gauss linear corrected |
+// writeFormat, writePrecision), system/fvSchemes (ddt(T): Euler | backward | CrankNicolson <oc> | steadyState | CoEuler phi rho <maxCo>; div(phi,T): [bounded] Gauss linear | upwind | limitedLinear k; laplacian: Gauss linear corrected |
 // uncorrected | orthogonal | limited [corrected] k), system/fvSolution (solvers.T, SIMPLE.nNonOrthogonalCorrectors), 0/T and 0/U with fixedValue (inflow) and
 // zeroGradient (outflow, walls) patches [U: also noSlip].  The whole equation is ONE assembly pass (fvm::assemble -> mi_fvm_assemble); the patch
 // coefficients are the reference's: gaussConvectionScheme.C:96-110 (internalCoeffs = phi_b valueInternalCoeffs, boundaryCoeffs = -phi_b
@@ -54,17 +54,29 @@ int main(int argc, char** argv)
         const label nNonOrthCorr = fvSolution.solutionDict().found("SIMPLE") ? fvSolution.dict("SIMPLE").lookupOrDefault<label>("nNonOrthogonalCorrectors", 0) : 0;
         const wordList ddtT = schemes.ddtScheme("ddt(T)");
         const bool crankNicolson = !ddtT.empty() && ddtT[0] == "CrankNicolson";
-        if (ddtT != wordList{"Euler"} && ddtT != wordList{"backward"} && !crankNicolson)
-            FatalErrorIn("scalarTransportFoam", "ddtSchemes: Euler | backward | CrankNicolson <oc>");
+        const bool steady = !ddtT.empty() && ddtT[0] == "steadyState", coEuler = !ddtT.empty() && ddtT[0] == "CoEuler";
+        if (ddtT != wordList{"Euler"} && ddtT != wordList{"backward"} && !crankNicolson && !steady && !coEuler)
+            FatalErrorIn("scalarTransportFoam", "ddtSchemes: Euler | backward | CrankNicolson <oc> | steadyState | CoEuler phi rho <maxCo>");
         const bool backward = ddtT == wordList{"backward"};
         std::string ddtEntry;
         for (const word& wd : ddtT) ddtEntry += (ddtEntry.empty() ? "" : " ") + wd;
         // CrankNicolson: the scheme object owns ddt0(T) for the run (fv::CrankNicolsonDdtScheme); a missing or bad coefficient is refused here
         std::optional<fv::CrankNicolsonDdtScheme> cnScheme;
         if (crankNicolson) cnScheme.emplace(fv::CrankNicolsonDdtScheme::New(ddtEntry));
-        const wordList divT = schemes.divScheme("div(phi,T)");
+        // steadyState / CoEuler: the entry is parsed by the scheme's New (a missing maxCo, an extra word ... are refused there); phi is a volumetric
+        // flux here, so CoEuler never reads the density its entry names
+        std::optional<fv::steadyStateDdtScheme> steadyScheme;
+        std::optional<fv::CoEulerDdtScheme> coScheme;
+        if (steady) steadyScheme.emplace(fv::steadyStateDdtScheme::New(ddtEntry));
+        if (coEuler) {
+            coScheme.emplace(fv::CoEulerDdtScheme::New(ddtEntry));
+            if (coScheme->phiName() != "phi") FatalErrorIn("scalarTransportFoam", "ddtSchemes: CoEuler reads the flux '" + coScheme->phiName() + "'; the flux here is phi");
+        }
+        wordList divT = schemes.divScheme("div(phi,T)");
+        const bool bounded = fv::boundedConvection(divT);       // `bounded Gauss ...`: - fvm::Sp(fvc::surfaceIntegrate(phi), T) in the convection matrix
         if (divT.size() < 2 || divT[0] != "Gauss" || (divT[1] != "linear" && divT[1] != "upwind" && !(divT[1] == "limitedLinear" && divT.size() == 3)))
-            FatalErrorIn("scalarTransportFoam", "div(phi,T): Gauss linear | Gauss upwind | Gauss limitedLinear k");
+            FatalErrorIn("scalarTransportFoam", "div(phi,T): [bounded] Gauss linear | Gauss upwind | Gauss limitedLinear k");
+        if (bounded && (backward || crankNicolson)) FatalErrorIn("scalarTransportFoam", "div(phi,T): bounded goes with Euler, steadyState or CoEuler");
         const bool upwind = divT[1] == "upwind", limited = divT[1] == "limitedLinear";
         const scalar limiterK = limited ? std::strtod(divT[2].c_str(), nullptr) : 0.0;
         const wordList lap = schemes.laplacianScheme("laplacian(DT,T)");
@@ -133,6 +145,42 @@ int main(int argc, char** argv)
                 bcDev.emplace_back(scalarField((std::size_t)np, 0.0));
             }
         }
+        // bounded: divPhi = fvc::surfaceIntegrate(phi), boundary faces included, formed once (phi does not change)
+        scalargpuField divPhi(bounded ? n : 0);
+        if (bounded) {
+            fvc::surfaceIntegrate(divPhi, addr, phi);
+            for (label q = 0; q < nP; ++q) patch[q]->add(phiB[q], divPhi);
+            fieldDivide(divPhi, divPhi, V);
+        }
+        // CoEuler: mesh.deltaCoeffs() = 1/|delta| (internal faces: C_N - C_P; patches: the patch-normal delta nHat (nHat & (Cf - Cn)), fvPatch.C:147-191)
+        // and magSf, per patch too; rDeltaT itself is formed by every assembly (CorDeltaT)
+        scalargpuField coDelta(coEuler ? nI : 0), magSfI(coEuler ? nI : 0);
+        std::vector<scalargpuField> coDeltaB, magSfB;
+        if (coEuler) {
+            scalarField dh((std::size_t)nI), mh((std::size_t)nI);
+            for (label f = 0; f < nI; ++f) {
+                const vector &cn = mesh.C[(std::size_t)mesh.neighbour[f]], &co = mesh.C[(std::size_t)mesh.owner[f]];
+                const scalar dx = cn[0] - co[0], dy = cn[1] - co[1], dz = cn[2] - co[2];
+                dh[f] = 1.0 / std::sqrt(dx * dx + dy * dy + dz * dz); mh[f] = mesh.magSf[f];
+            }
+            coDelta = dh; magSfI = mh;
+            for (label p = 0; p < nP; ++p) {
+                const label np = mesh.boundary[p].nFaces, f0 = mesh.boundary[p].startFace;
+                scalarField db((std::size_t)np);
+                for (label i = 0; i < np; ++i) {
+                    const vector &cf = mesh.Cf[f0 + i], &co = mesh.C[(std::size_t)patchCells[p][i]], &sf = mesh.Sf[f0 + i];
+                    const scalar m = mesh.magSf[f0 + i], nx = sf[0] / m, ny = sf[1] / m, nz = sf[2] / m;
+                    const scalar nd = nx * (cf[0] - co[0]) + ny * (cf[1] - co[1]) + nz * (cf[2] - co[2]);
+                    const scalar vx = nx * nd, vy = ny * nd, vz = nz * nd;
+                    db[i] = 1.0 / std::sqrt(vx * vx + vy * vy + vz * vz);
+                }
+                coDeltaB.emplace_back(db); magSfB.emplace_back(mesh.patchMagSf[p]);
+            }
+            coScheme->setMesh(addr, coDelta, magSfI, weights);
+            coScheme->bind("phi", phi);
+            for (label p = 0; p < nP; ++p) coScheme->addPatch(*patch[p], coDeltaB[p], magSfB[p], phiB[p]);
+            coScheme->setTime(deltaT);
+        }
         scalargpuField T(readVolScalarInternalField(caseDir + "/0/T", n));
         auto gaussGrad = [&](vectorgpuField& g, const scalargpuField& vf) {       // fvc::grad(T), Gauss linear, with T_b on fixedValue patches / patchInternalField
             scalargpuField ff(nI);
@@ -172,6 +220,9 @@ int main(int argc, char** argv)
                 if (crankNicolson)                              // ddt0(T) is updated by the first corrector's assembly only (evaluate)
                     fvm::assemble(TEqn, *cnScheme, fv::CrankNicolsonDdtScheme::ddt0Name("T"), 1.0, V, Told, ToldOld, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
                 else if (backward) fvm::assemble(TEqn, bd, 1.0, V, Told, ToldOld, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
+                else if (steady) fvm::assemble(TEqn, *steadyScheme, 1.0, V, Told, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf, bounded ? &divPhi : nullptr);
+                else if (coEuler) fvm::assemble(TEqn, *coScheme, 1.0, V, Told, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf, bounded ? &divPhi : nullptr);
+                else if (bounded) fvm::assembleBounded(TEqn, rDeltaT, 1.0, V, Told, phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf, divPhi);
                 else fvm::assemble(TEqn, rDeltaT, 1.0, V, Told, &phi, (upwind || limited) ? &w : &weights, &deltaCoeffs, &dtMagSf);
                 for (label q = 0; q < nP; ++q) { TEqn.internalCoeffs()[q] = icDev[q]; TEqn.boundaryCoeffs()[q] = bcDev[q]; }
                 if (corrected) {                                // - fvm::laplacian(DT, T), corrected: source += V*div(DT |Sf| correction(T))
