@@ -452,6 +452,9 @@ int mi_gamg_level_coeffs(mi_gamg_t g, mi_matrix_t m, int32_t level, double *diag
  * Every scheme is one streaming face pass + one row pass whose own-face reads are staged through LDS
  * (the reference: 3-6 Thrust passes + temporaries).  They need the caller's faces owner-sorted
  * (OpenFOAM's upper-triangular order); face fields 16-byte aligned.
+ * A mesh without internal faces (one cell; cells joined by patches only) is legal: every face array is
+ * empty, its pointer may be NULL and is never read, every row sum is +0.0; mi_fvm_assemble* then takes
+ * each face term as present and empty.
  * mi_row_face_op kind: 0 sumDiag, 1 negSumDiag, 2 sumMagOffDiag; lower_dev NULL => symmetric.
  * mi_patch_*: a boundary patch = its faceCells; mi_patch_add applies pf per unique cell in ascending
  * patch-face order (addToInternalField, K26): fn 0 add, 1 subtract, 2 add magnitudes.          */

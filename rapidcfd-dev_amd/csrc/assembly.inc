@@ -1470,6 +1470,10 @@ int ensure_caller_tables(mi_addr_s* a)
     return MI_OK;
 }
 int grid_for(int n) { int b = (n + 255) / 256; return b < 1 ? 1 : (b > 8192 ? 8192 : b); }
+// a mesh without internal faces is legal lduAddressing (one cell; cells joined by patches only): its face arrays are empty, an empty
+// array's pointer may be NULL and is never read -- the entries ask for a face array only of a mesh that has faces (shown by the
+// meshes one_cell and no_faces of tests/test_degenerate_meshes.py)
+bool faceless(const mi_addr_s* a) { return a->L.nFaces == 0; }
 } // namespace
 
 extern "C" int mi_patch_create(mi_ctx_t ctx, int32_t n_cells, int32_t n_patch_faces, const int32_t* face_cells_host, mi_patch_t* out)
@@ -1620,7 +1624,7 @@ int row_sum(mi_addr_s* a, const double* ownArr, const double* neiArr, const doub
 
 extern "C" int mi_row_face_op(mi_addr_t a, int kind, const double* lower_dev, const double* upper_dev, double* inout_dev)
 {
-    if (!a || !upper_dev || !inout_dev || kind < 0 || kind > 2) return fail(MI_ERR_ARG, "mi_row_face_op: bad argument");
+    if (!a || (!upper_dev && !faceless(a)) || !inout_dev || kind < 0 || kind > 2) return fail(MI_ERR_ARG, "mi_row_face_op: bad argument");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     const double* lo = lower_dev ? lower_dev : upper_dev; // symmetric: lower aliases upper (lduMatrix.C:328-345)
@@ -1631,11 +1635,12 @@ extern "C" int mi_row_face_op(mi_addr_t a, int kind, const double* lower_dev, co
 
 extern "C" int mi_fvm_laplacian(mi_addr_t a, const double* delta_coeffs_dev, const double* gamma_magsf_dev, double* upper_out_dev, double* diag_out_dev)
 {
-    if (!a || !delta_coeffs_dev || !gamma_magsf_dev || !upper_out_dev || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_laplacian: bad argument");
+    if (!a || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_laplacian: bad argument");
+    if (!faceless(a) && (!delta_coeffs_dev || !gamma_magsf_dev || !upper_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_laplacian: bad argument");
     if (!al16(delta_coeffs_dev) || !al16(gamma_magsf_dev) || !al16(upper_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_laplacian: face fields must be 16-byte aligned");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    if (upper_out_dev == delta_coeffs_dev || upper_out_dev == gamma_magsf_dev) return fail(MI_ERR_ARG, "mi_fvm_laplacian: upper_out must not alias an input");
+    if (!faceless(a) && (upper_out_dev == delta_coeffs_dev || upper_out_dev == gamma_magsf_dev)) return fail(MI_ERR_ARG, "mi_fvm_laplacian: upper_out must not alias an input");
     // one pass (the reference: 3 + temporaries): each block forms the coefficients of its own faces, keeps them in LDS for
     // the row sums of its cells and recomputes only the faces cut by its boundary (with the same single rounding)
     RowPassArgs ra{};
@@ -1645,12 +1650,13 @@ extern "C" int mi_fvm_laplacian(mi_addr_t a, const double* delta_coeffs_dev, con
 
 extern "C" int mi_fvm_div(mi_addr_t a, const double* weights_dev, const double* face_flux_dev, double* lower_out_dev, double* upper_out_dev, double* diag_out_dev)
 {
-    if (!a || !weights_dev || !face_flux_dev || !lower_out_dev || !upper_out_dev || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_div: bad argument");
+    if (!a || !diag_out_dev) return fail(MI_ERR_ARG, "mi_fvm_div: bad argument");
+    if (!faceless(a) && (!weights_dev || !face_flux_dev || !lower_out_dev || !upper_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_div: bad argument");
     if (!al16(weights_dev) || !al16(face_flux_dev) || !al16(lower_out_dev) || !al16(upper_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_div: face fields must be 16-byte aligned");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    if (lower_out_dev == weights_dev || lower_out_dev == face_flux_dev || upper_out_dev == weights_dev || upper_out_dev == face_flux_dev ||
-        lower_out_dev == upper_out_dev)
+    if (!faceless(a) && (lower_out_dev == weights_dev || lower_out_dev == face_flux_dev || upper_out_dev == weights_dev || upper_out_dev == face_flux_dev ||
+                         lower_out_dev == upper_out_dev))
         return fail(MI_ERR_ARG, "mi_fvm_div: the coefficient outputs must not alias an input or each other");
     RowPassArgs ra{};
     ra.a0 = weights_dev; ra.a1 = face_flux_dev; ra.f0out = lower_out_dev; ra.f1out = upper_out_dev; ra.out = diag_out_dev;
@@ -1685,6 +1691,7 @@ extern "C" int mi_linear_upwind_correction(mi_addr_t a, const mi_div_correction*
 {
     const char* who = "mi_linear_upwind_correction";
     if (!a) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (faceless(a)) return MI_OK;                        // no face to correct: the outputs are empty
     if (!face_flux_dev) return fail(MI_ERR_ARG, std::string(who) + ": the correction of a convection scheme needs its faceFlux");
     if (!al16(face_flux_dev)) return fail(MI_ERR_ARG, std::string(who) + ": face fields must be 16-byte aligned");
     if (!out_dev || n_rhs < 1 || n_rhs > 4) return fail(MI_ERR_ARG, std::string(who) + ": 1 to 4 outputs needed");
@@ -1799,7 +1806,7 @@ extern "C" int mi_fvm_assemble_local(mi_addr_t a, const mi_fvm_terms* t, const m
     if (!a || !t || !loc) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
     if (!loc->r_delta_t_dev && !loc->div_flux_dev) return fail(MI_ERR_ARG, std::string(who) + ": neither r_delta_t_dev nor div_flux_dev (use mi_fvm_assemble)");
     if (loc->r_delta_t_dev && !t->ddt) return fail(MI_ERR_ARG, std::string(who) + ": r_delta_t_dev with terms->ddt == 0 (steadyState takes no rDeltaT field)");
-    if (loc->div_flux_dev && !t->div_flux_dev) return fail(MI_ERR_ARG, std::string(who) + ": bounded (div_flux_dev) without a convection term (terms->div_flux_dev is NULL)");
+    if (loc->div_flux_dev && !t->div_flux_dev && !faceless(a)) return fail(MI_ERR_ARG, std::string(who) + ": bounded (div_flux_dev) without a convection term (terms->div_flux_dev is NULL)");
     if (loc->div_flux_dev && !t->vol_dev) return fail(MI_ERR_ARG, std::string(who) + ": cell volumes needed");
     for (const double* q : {loc->r_delta_t_dev, loc->div_flux_dev}) {
         if (!q) continue;
@@ -1850,10 +1857,14 @@ int asm_launch_tf(bool DIV, bool LAP, bool CORR, mi_addr_s* a, const mi_fvm_term
 int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const TimeForm& tf, const mi_div_correction* corr, const AsmOut& o)
 {
     if (!a || !t || !o.diag) return fail(MI_ERR_ARG, "mi_fvm_assemble: bad argument");
-    const bool DIV = t->div_flux_dev != nullptr, LAP = t->lap_delta_coeffs_dev != nullptr;
-    if (LAP && !t->lap_gamma_magsf_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: laplacian needs deltaCoeffs and gammaMagSf");
+    // a face term is present when its array is given.  A mesh without faces (one_cell, no_faces: tests/test_degenerate_meshes.py) gives every
+    // face array empty and maybe NULL: its face terms are all taken as present and empty -- no face is read or written, every row sum is
+    // +0.0 as in the unfused sequence -- and the checks of the face arrays do not apply
+    const bool noFaces = faceless(a);
+    const bool DIV = t->div_flux_dev != nullptr || noFaces, LAP = t->lap_delta_coeffs_dev != nullptr || noFaces;
+    if (LAP && !t->lap_gamma_magsf_dev && !noFaces) return fail(MI_ERR_ARG, "mi_fvm_assemble: laplacian needs deltaCoeffs and gammaMagSf");
     if (!DIV && !LAP) return fail(MI_ERR_ARG, "mi_fvm_assemble: no face term (use mi_fvm_ddt_euler* for a diagonal matrix)");
-    if (!o.upper || (DIV && !o.lower)) return fail(MI_ERR_ARG, "mi_fvm_assemble: coefficient outputs missing (a convection term makes the matrix asymmetric)");
+    if (!noFaces && (!o.upper || (DIV && !o.lower))) return fail(MI_ERR_ARG, "mi_fvm_assemble: coefficient outputs missing (a convection term makes the matrix asymmetric)");
     if (t->n_rhs < 0 || t->n_rhs > 4 || t->n_su < 0 || t->n_su > 4) return fail(MI_ERR_ARG, "mi_fvm_assemble: at most 4 right-hand sides and 4 explicit terms");
     if ((t->ddt || t->sp_dev || t->n_su > 0) && !t->vol_dev) return fail(MI_ERR_ARG, "mi_fvm_assemble: cell volumes needed");
     if (t->ddt && ((t->rho_dev != nullptr) != (t->rho_old_dev != nullptr))) return fail(MI_ERR_ARG, "mi_fvm_assemble: rho and rho_old go together");
@@ -1862,10 +1873,10 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const TimeForm& tf, const 
     const double* faceIn[4] = {t->div_flux_dev, t->div_weights_dev, t->lap_delta_coeffs_dev, t->lap_gamma_magsf_dev};
     for (const double* q : faceIn) {
         if (q && !al16(q)) return fail(MI_ERR_ARG, "mi_fvm_assemble: face fields must be 16-byte aligned");
-        if (q && (q == o.upper || q == o.lower)) return fail(MI_ERR_ARG, "mi_fvm_assemble: a coefficient output must not alias an input (cut faces are recomputed from the inputs)");
+        if (q && !noFaces && (q == o.upper || q == o.lower)) return fail(MI_ERR_ARG, "mi_fvm_assemble: a coefficient output must not alias an input (cut faces are recomputed from the inputs)");
     }
     if (o.lower && o.lower == o.upper) return fail(MI_ERR_ARG, "mi_fvm_assemble: lower_out and upper_out must differ");
-    const bool CORR = corr != nullptr;
+    const bool CORR = corr != nullptr && !noFaces;        // no face: nothing to correct, the correction's face arrays are empty
     if (CORR) {
         const char* who = "mi_fvm_assemble_corrected";
         if (!DIV) return fail(MI_ERR_ARG, std::string(who) + ": a convection correction without a convection term (div_flux_dev is NULL)");
@@ -1907,7 +1918,7 @@ int assemble_impl(mi_addr_t a, const mi_fvm_terms* t, const TimeForm& tf, const 
 
 extern "C" int mi_surface_integrate(mi_addr_t a, const double* ssf_dev, const double* vol_dev_or_null, double* ivf_dev)
 {
-    if (!a || !ssf_dev || !ivf_dev) return fail(MI_ERR_ARG, "mi_surface_integrate: bad argument");
+    if (!a || (!ssf_dev && !faceless(a)) || !ivf_dev) return fail(MI_ERR_ARG, "mi_surface_integrate: bad argument");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     return row_sum<M_PLUS, M_MINUS>(a, ssf_dev, ssf_dev, nullptr, vol_dev_or_null, ivf_dev);
@@ -1915,7 +1926,7 @@ extern "C" int mi_surface_integrate(mi_addr_t a, const double* ssf_dev, const do
 
 extern "C" int mi_face_interpolate(mi_addr_t a, const double* lambda_dev, const double* phi_dev, double* sf_dev)
 {
-    if (!a || !lambda_dev || !phi_dev || !sf_dev) return fail(MI_ERR_ARG, "mi_face_interpolate: bad argument");
+    if (!a || !phi_dev || (!faceless(a) && (!lambda_dev || !sf_dev))) return fail(MI_ERR_ARG, "mi_face_interpolate: bad argument");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces == 0) return MI_OK;
@@ -1929,8 +1940,8 @@ extern "C" int mi_face_interpolate(mi_addr_t a, const double* lambda_dev, const 
 extern "C" int mi_fvc_div(mi_addr_t a, const double* face_flux_dev, const double* weights_dev_or_null, const double* vf_dev, const double* vol_dev_or_null,
                           double* face_out_dev, double* div_out_dev)
 {
-    if (!a || !face_flux_dev || !vf_dev || !face_out_dev || !div_out_dev) return fail(MI_ERR_ARG, "mi_fvc_div: bad argument");
-    if (face_out_dev == face_flux_dev || face_out_dev == weights_dev_or_null) return fail(MI_ERR_ARG, "mi_fvc_div: face_out must not alias a face input");
+    if (!a || !vf_dev || !div_out_dev || (!faceless(a) && (!face_flux_dev || !face_out_dev))) return fail(MI_ERR_ARG, "mi_fvc_div: bad argument");
+    if (!faceless(a) && (face_out_dev == face_flux_dev || face_out_dev == weights_dev_or_null)) return fail(MI_ERR_ARG, "mi_fvc_div: face_out must not alias a face input");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces > 0) {
@@ -2323,7 +2334,8 @@ namespace {
 int flux_args(mi_addr_t a, const char* who, const double* lambda_dev, const double* sfx_dev, const double* sfy_dev, const double* sfz_dev, const double* vx_dev,
               const double* vy_dev, const double* vz_dev, RowPassArgs& ra)
 {
-    if (!a || !lambda_dev || !sfx_dev || !sfy_dev || !sfz_dev || !vx_dev || !vy_dev || !vz_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!a || !vx_dev || !vy_dev || !vz_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!faceless(a) && (!lambda_dev || !sfx_dev || !sfy_dev || !sfz_dev)) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     ra.a0 = lambda_dev; ra.a1 = lambda_dev; ra.sx = sfx_dev; ra.sy = sfy_dev; ra.sz = sfz_dev; ra.vx = vx_dev; ra.vy = vy_dev; ra.vz = vz_dev;
@@ -2337,7 +2349,8 @@ extern "C" int mi_flux_div(mi_addr_t a, const double* lambda_dev, const double* 
 {
     RowPassArgs ra{};
     MICHK(flux_args(a, "mi_flux_div", lambda_dev, sfx_dev, sfy_dev, sfz_dev, vx_dev, vy_dev, vz_dev, ra));
-    if (!phi_out_dev || !div_out_dev || (add_b_dev_or_null && !add_a_dev_or_null)) return fail(MI_ERR_ARG, "mi_flux_div: bad argument");
+    if ((!phi_out_dev && !faceless(a)) || !div_out_dev || (add_b_dev_or_null && !add_a_dev_or_null)) return fail(MI_ERR_ARG, "mi_flux_div: bad argument");
+    if (faceless(a)) return row_sum<M_PLUS, M_MINUS>(a, phi_out_dev, phi_out_dev, nullptr, vol_dev_or_null, div_out_dev);   // every row sum is empty
     if (phi_out_dev == lambda_dev || phi_out_dev == sfx_dev || phi_out_dev == sfy_dev || phi_out_dev == sfz_dev || phi_out_dev == add_a_dev_or_null || phi_out_dev == add_b_dev_or_null)
         return fail(MI_ERR_ARG, "mi_flux_div: phi_out must not alias a face input (faces cut by a block boundary are recomputed from the inputs)");
     ra.sc = cell_scale_dev_or_null; ra.addA = add_a_dev_or_null; ra.addB = add_b_dev_or_null;
@@ -2356,9 +2369,9 @@ extern "C" int mi_ddt_phi_corr(mi_addr_t a, double r_delta_t, const double* lamb
 {
     RowPassArgs ra{};
     MICHK(flux_args(a, "mi_ddt_phi_corr", lambda_dev, sfx_dev, sfy_dev, sfz_dev, ux_old_dev, uy_old_dev, uz_old_dev, ra));
+    if (a->L.nFaces == 0) return MI_OK;
     if (!phi_old_dev || !out_dev) return fail(MI_ERR_ARG, "mi_ddt_phi_corr: bad argument");
     ra.sc = rho_old_dev_or_null;
-    if (a->L.nFaces == 0) return MI_OK;
     k_ddt_phi_corr<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, r_delta_t, phi_old_dev, out_dev, a->L.nFaces);
     HIPCHK(hipGetLastError());
     return MI_OK;
@@ -2680,12 +2693,13 @@ extern "C" int mi_co_r_delta_t(mi_addr_t a, const double* delta_coeffs_dev, cons
                                const double* rho_old_dev_or_null, double delta_t, double max_co, double* r_delta_t_out_dev)
 {
     const char* who = "mi_co_r_delta_t";
-    if (!a || !delta_coeffs_dev || !mag_sf_dev || !phi_dev || !r_delta_t_out_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
-    if ((lambda_dev_or_null != nullptr) != (rho_old_dev_or_null != nullptr))
+    if (!a || !r_delta_t_out_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!faceless(a) && (!delta_coeffs_dev || !mag_sf_dev || !phi_dev)) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!faceless(a) && (lambda_dev_or_null != nullptr) != (rho_old_dev_or_null != nullptr))
         return fail(MI_ERR_ARG, std::string(who) + ": the mass-flux form takes lambda and rho_old together");
     MICHK(co_scalars(who, delta_t, max_co));
     for (const double* q : {delta_coeffs_dev, mag_sf_dev, phi_dev, lambda_dev_or_null, rho_old_dev_or_null})
-        if (q == r_delta_t_out_dev) return fail(MI_ERR_ARG, std::string(who) + ": the output must not alias an input (cut faces are recomputed from the inputs)");
+        if (q && q == r_delta_t_out_dev) return fail(MI_ERR_ARG, std::string(who) + ": the output must not alias an input (cut faces are recomputed from the inputs)");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nCells == 0) return MI_OK;
@@ -2702,8 +2716,9 @@ extern "C" int mi_co_r_delta_t(mi_addr_t a, const double* delta_coeffs_dev, cons
 }
 extern "C" int mi_upwind_weights(mi_ctx_t c, int64_t n_faces, const double* face_flux_dev, double* weights_out_dev)
 {
-    if (!c || n_faces < 0 || !face_flux_dev || !weights_out_dev) return fail(MI_ERR_ARG, "mi_upwind_weights: bad argument");
+    if (!c || n_faces < 0 || (n_faces > 0 && (!face_flux_dev || !weights_out_dev))) return fail(MI_ERR_ARG, "mi_upwind_weights: bad argument");
     if (!al16(face_flux_dev) || !al16(weights_out_dev)) return fail(MI_ERR_ARG, "mi_upwind_weights: arrays must be 16-byte aligned");
+    if (n_faces == 0) return MI_OK;
     HIPCHK(hipSetDevice(c->device));
     k_upwind_weights<<<RG, RB, 0, c->stream>>>(face_flux_dev, weights_out_dev, n_faces);
     HIPCHK(hipGetLastError());
@@ -2885,7 +2900,8 @@ extern "C" int mi_patch_limited_weights(mi_patch_t p, const mi_limiter* lim, con
 extern "C" int mi_gauss_grad(mi_addr_t a, const double* sfx_dev, const double* sfy_dev, const double* sfz_dev, const double* ssf_dev,
                              const double* vol_dev_or_null, double* gx_dev, double* gy_dev, double* gz_dev)
 {
-    if (!a || !sfx_dev || !sfy_dev || !sfz_dev || !ssf_dev || !gx_dev || !gy_dev || !gz_dev) return fail(MI_ERR_ARG, "mi_gauss_grad: bad argument");
+    if (!a || !gx_dev || !gy_dev || !gz_dev) return fail(MI_ERR_ARG, "mi_gauss_grad: bad argument");
+    if (!faceless(a) && (!sfx_dev || !sfy_dev || !sfz_dev || !ssf_dev)) return fail(MI_ERR_ARG, "mi_gauss_grad: bad argument");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nCells == 0) return MI_OK;
@@ -3028,8 +3044,9 @@ extern "C" int mi_patch_dev_tgrad_flux(mi_patch_t p, int32_t kind, const double*
 }
 extern "C" int mi_vec_axpby(mi_ctx_t c, int64_t n, double a, const double* x_dev, double b, const double* y_dev, double* out_dev)
 {
-    if (!c || n < 0 || !x_dev || !y_dev || !out_dev) return fail(MI_ERR_ARG, "mi_vec_axpby: bad argument");
+    if (!c || n < 0 || (n > 0 && (!x_dev || !y_dev || !out_dev))) return fail(MI_ERR_ARG, "mi_vec_axpby: bad argument");
     if (!al16(x_dev) || !al16(y_dev) || !al16(out_dev)) return fail(MI_ERR_ARG, "mi_vec_axpby: arrays must be 16-byte aligned");
+    if (n == 0) return MI_OK;
     HIPCHK(hipSetDevice(c->device));
     k_axpby<<<RG, RB, 0, c->stream>>>(a, x_dev, b, y_dev, out_dev, n);
     HIPCHK(hipGetLastError());

@@ -310,7 +310,7 @@ extern "C" int mi_limited_grad(mi_addr_t a, const mi_grad_limiter* lim, mi_grad_
     const double* in[14];
     int m = 0;
     for (int j = 0; j < n_comp; ++j) in[m++] = vf_dev[j];
-    for (int d = 0; d < 3; ++d) { in[m++] = c_dev[d]; in[m++] = cf_dev[d]; }
+    for (int d = 0; d < 3; ++d) { in[m++] = c_dev[d]; if (a->L.nFaces > 0) in[m++] = cf_dev[d]; }   // no faces: the face centres are empty arrays (one_cell, tests/test_degenerate_meshes.py)
     if (hasB) { for (int j = 0; j < n_comp; ++j) in[m++] = bvalue_dev[j]; for (int d = 0; d < 3; ++d) in[m++] = bcf_dev[d]; }
     double* outs[12];
     int no = 0;

@@ -70,11 +70,214 @@ def shaped_addressing(eng, ctx, syn, case, mode):
 
 
 def shape_case(pkg, name, symmetric=False):
-    """the two meshes of the shape tests, the smallest with several tiles and several 1024-cell blocks with cut faces on both sides"""
+    """"box" / "graph": the two meshes of the shape tests, the smallest with several tiles and several 1024-cell blocks with cut faces on
+    both sides; every other name: a mesh of DEGENERATE_MESHES"""
     from conftest import random_graph_case
     if name == "box":
         return pkg.synthetic.box_case(31, 23, 19, symmetric=symmetric)
-    return random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=symmetric)
+    if name == "graph":
+        return random_graph_case(pkg, 9000, extra=3.0, seed=5, symmetric=symmetric)
+    return degenerate_case(pkg, name, symmetric=symmetric)
+
+
+# ---- the degenerate meshes (tests/test_degenerate_meshes.py) ---------------------------------------------------------------------------
+# legal lduAddressing a polyhedral or agglomerated mesh brings and a box never does: cells without faces, a block of cells without faces,
+# rows of thousands of faces, cell counts around a block boundary, blocks at and past the limits of the 16-bit row tables
+EDGE_SIZES = (255, 256, 257, 1023, 1024, 1025)
+DEGENERATE_MESHES = (("one_cell", "no_faces", "isolated", "hub_first", "hub_last") + tuple(f"edge_{n}" for n in EDGE_SIZES)
+                     + ("dense_fits", "dense_fallback", "own_32767", "own_32768"))
+ROW16_LIMITS = (32768, 32768, 65536)        # own faces, cut faces, neighbour-list entries of one block (ensure_caller_tables)
+HUB_SPOKES = 3000                           # the tiling takes at most 4 094 faces on one cell
+ISOLATED_N, ISOLATED_EMPTY = 1500, (512, 768)
+
+
+def case_from_pairs(pkg, n, lo, up, seed, symmetric=False):
+    """an LduCase on the faces (lo[i], up[i]), lo < up, already sorted by (lo, up) without duplicates; coefficients as
+    conftest.random_graph_case forms them: upper = -(0.2 + u), an independent lower, a dominant diag (0.05 + u on a cell without faces)"""
+    syn = pkg.synthetic
+    lo, up = np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(up, dtype=np.int32)
+    nf = lo.shape[0]
+    assert up.shape[0] == nf and (nf == 0 or (lo.min() >= 0 and up.max() < n and np.all(lo < up)))
+    key = lo.astype(np.int64) * n + up
+    assert np.all(key[1:] > key[:-1]), "faces sorted by (lower, upper), no duplicate pair"
+    c = syn.splitmix_uniform(seed + 1, 2 * nf)
+    upper = -(0.2 + c[:nf])
+    lower = None if symmetric else -(0.2 + c[nf:])
+    diag = np.zeros(n)
+    np.subtract.at(diag, lo, upper if symmetric else lower)
+    np.subtract.at(diag, up, upper)
+    diag += 0.05 + syn.splitmix_uniform(seed + 2, n)
+    return syn.LduCase(n, lo, up, diag, upper, lower, syn.splitmix_uniform(seed + 3, n) - 0.5)
+
+
+def isolated_labels(pkg):
+    """the kept labels of "isolated", sorted: all of 0..1499 but the block 512..767 and 37 single cells -- the first and the last cell, the
+    cells on both sides of the 256- and 1024-cell block boundaries, and 31 seeded ones"""
+    a, b = ISOLATED_EMPTY
+    drop = {0, 255, 256, 1023, 1024, ISOLATED_N - 1}
+    for x in (pkg.synthetic.splitmix_uniform(91, 400) * ISOLATED_N).astype(np.int64).tolist():
+        if len(drop) < 37 and not a <= x < b:
+            drop.add(x)
+    assert len(drop) == 37
+    keep = np.ones(ISOLATED_N, bool)
+    keep[a:b] = False
+    keep[sorted(drop)] = False
+    return np.nonzero(keep)[0]
+
+
+def hub_pairs(first):
+    """hub_first: cell 0 joins every cell 1..3000, plus the chain i-(i+1) for i >= 1; hub_last: every cell 0..2999 joins cell 3000, plus
+    the chain -- 5 999 faces each"""
+    m = HUB_SPOKES
+    if first:
+        lo = np.concatenate([np.zeros(m, np.int64), np.arange(1, m)])
+        up = np.concatenate([np.arange(1, m + 1), np.arange(2, m + 1)])
+    else:
+        lo = np.concatenate([np.arange(m), np.arange(m - 1)])
+        up = np.concatenate([np.full(m, m), np.arange(1, m)])
+    order = np.lexsort((up, lo))
+    return m + 1, lo[order], up[order]
+
+
+def own_pairs(drop_last):
+    """cells 0..1023 own 32 faces each into the cells 1024..3071, cell i joining 1024 + (32 i + j) mod 2048 for j < 32: 32 768 own faces in
+    the first 1024-cell block, exactly the limit of the 16-bit tables; drop_last: one fewer"""
+    i, j = np.repeat(np.arange(1024), 32), np.tile(np.arange(32), 1024)
+    lo, up = i, 1024 + (32 * i + j) % 2048
+    if drop_last:
+        lo, up = lo[:-1], up[:-1]
+    return 3072, lo, up
+
+
+def degenerate_case(pkg, name, symmetric=False):
+    from conftest import random_graph_case
+    none = np.zeros(0, np.int32)
+    if name == "one_cell":
+        return case_from_pairs(pkg, 1, none, none, 21, symmetric)
+    if name == "no_faces":
+        return case_from_pairs(pkg, 300, none, none, 23, symmetric)
+    if name == "isolated":
+        g = random_graph_case(pkg, ISOLATED_N - 37 - (ISOLATED_EMPTY[1] - ISOLATED_EMPTY[0]), extra=2.5, seed=25)
+        labels = isolated_labels(pkg)                        # sorted: the map is monotone, so the faces stay in upper-triangular order
+        return case_from_pairs(pkg, ISOLATED_N, labels[g.lower_addr], labels[g.upper_addr], 27, symmetric)
+    if name in ("hub_first", "hub_last"):
+        return case_from_pairs(pkg, *hub_pairs(name == "hub_first"), 29, symmetric)
+    if name.startswith("edge_"):
+        return random_graph_case(pkg, int(name[5:]), extra=2.5, symmetric=symmetric)
+    if name == "dense_fits":
+        return random_graph_case(pkg, 2048, extra=12, symmetric=symmetric)
+    if name == "dense_fallback":
+        return random_graph_case(pkg, 2048, extra=40, symmetric=symmetric)
+    if name in ("own_32767", "own_32768"):
+        return case_from_pairs(pkg, *own_pairs(name == "own_32767"), 31, symmetric)
+    raise KeyError(name)
+
+
+def block_counts(case, bs):
+    """host only -> (own faces, cut faces, neighbour-list entries) per block of consecutive cells, the three counts ensure_caller_tables
+    holds against ROW16_LIMITS; a cut face: a neighbour-side face owned by a cell of an earlier block.  bs: cells per block (256, 1024), or
+    the blocks' first cells followed by n_cells (the layout's tiles)"""
+    n = case.n_cells
+    starts = np.append(np.arange(0, n, bs), n) if np.isscalar(bs) else np.asarray(bs, dtype=np.int64)
+    nb = len(starts) - 1
+    bo = np.searchsorted(starts, case.lower_addr, side="right") - 1
+    bn = np.searchsorted(starts, case.upper_addr, side="right") - 1
+    return np.bincount(bo, minlength=nb), np.bincount(bn[bo != bn], minlength=nb), np.bincount(bn, minlength=nb)
+
+
+def fits_row16(case, bs):
+    """every block below the three limits: the addressing keeps the 16-bit row tables"""
+    return all(int(c.max()) < lim for c, lim in zip(block_counts(case, bs), ROW16_LIMITS))
+
+
+def row_blocks(addr, case, bs):
+    """the cell ranges the row passes of this addressing own (ensure_caller_tables): the layout's tiles where the numbering is
+    tile-contiguous and no tile has more than 1024 cells, fixed ranges of bs cells otherwise -> the blocks' first cells followed by n_cells"""
+    if addr.is_ordered:
+        ts = np.asarray(addr.tile_starts(), dtype=np.int64)
+        if int(np.diff(ts).max()) <= 1024:
+            return ts
+    return np.append(np.arange(0, case.n_cells, bs), case.n_cells)
+
+
+def row_passes_bit_exact(eng, orc, syn, case, addr, dev, host, E):
+    """The row passes (row face ops, fvm::laplacian, fvm::div, surfaceIntegrate, Gauss grad, the interpolated flux with its surfaceIntegrate,
+    fvc::div) on one mesh under one addressing against the oracle, bit for bit, and face_interpolate; where the mesh has faces, the
+    refusals of an output aliasing an input.  -> the engine's results by name, for a caller that compares two runs array by array"""
+    import pytest
+    n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
+    asm = eng.Assembly(addr)
+    got = {}
+    lower = case.upper if case.lower is None else case.lower
+    for kind in (0, 1, 2):
+        start = syn.splitmix_uniform(kind, n)
+        io = dev(start)
+        asm.row_face_op(kind, dev(lower), dev(case.upper), io)
+        got[f"row_face_op{kind}/asymmetric"] = host(io)
+        assert np.array_equal(host(io), orc.row_face_op(kind, n, lo, up, lower, case.upper, start)), kind
+        io = dev(start)
+        asm.row_face_op(kind, None, dev(case.upper), io)
+        got[f"row_face_op{kind}/symmetric"] = host(io)
+        assert np.array_equal(host(io), orc.row_face_op(kind, n, lo, up, None, case.upper, start)), kind
+    delta, gam = 1.0 + syn.splitmix_uniform(7, nf), 0.5 + syn.splitmix_uniform(8, nf)
+    uo, do = E(nf), E(n)
+    asm.fvm_laplacian(dev(delta), dev(gam), uo, do)
+    ru, rd = orc.fvm_laplacian(n, lo, up, delta, gam)
+    got["laplacian/upper"], got["laplacian/diag"] = host(uo), host(do)
+    assert np.array_equal(host(uo), ru) and np.array_equal(host(do), rd)
+    w, phi = syn.splitmix_uniform(9, nf), syn.splitmix_uniform(10, nf) - 0.5
+    lo_o, uo, do = E(nf), E(nf), E(n)
+    asm.fvm_div(dev(w), dev(phi), lo_o, uo, do)
+    rl, ru, rd = orc.fvm_div(n, lo, up, w, phi)
+    got["div/lower"], got["div/upper"], got["div/diag"] = host(lo_o), host(uo), host(do)
+    assert np.array_equal(host(lo_o), rl) and np.array_equal(host(uo), ru) and np.array_equal(host(do), rd)
+    vol = 0.5 + syn.splitmix_uniform(11, n)
+    out = E(n)
+    asm.surface_integrate(dev(phi), None, out); assert np.array_equal(host(out), orc.surface_integrate(n, lo, up, phi))
+    got["surface_integrate"] = host(out)
+    asm.surface_integrate(dev(phi), dev(vol), out); assert np.array_equal(host(out), orc.surface_integrate(n, lo, up, phi, vol))
+    got["surface_integrate/vol"] = host(out)
+    Sf = [syn.splitmix_uniform(20 + k, nf) - 0.5 for k in range(3)]
+    g = [E(n) for _ in range(3)]
+    asm.gauss_grad([dev(x) for x in Sf], dev(phi), dev(vol), g)
+    for k, (a, b) in enumerate(zip(g, orc.gauss_grad(n, lo, up, Sf, phi, vol))):
+        got[f"gauss_grad/{k}"] = host(a)
+        assert np.array_equal(host(a), b)
+    # round 5: the flux of an interpolated (scaled) cell vector and its surfaceIntegrate in one row pass (pEqn.H:49-71)
+    lam = syn.splitmix_uniform(30, nf)
+    V = [syn.splitmix_uniform(31 + k, n) - 0.5 for k in range(3)]
+    rho, aA, aB = 0.8 + syn.splitmix_uniform(35, n), syn.splitmix_uniform(36, nf) - 0.5, syn.splitmix_uniform(37, nf)
+    po, dv = E(nf), E(n)
+    for kw in (dict(), dict(scale=rho), dict(scale=rho, add_a=aA, add_b=aB, vol=vol), dict(add_a=aA)):
+        asm.flux_div(dev(lam), [dev(x) for x in Sf], [dev(x) for x in V], po, dv, cell_scale=dev(kw["scale"]) if "scale" in kw else None,
+                     add_a=dev(kw["add_a"]) if "add_a" in kw else None, add_b=dev(kw["add_b"]) if "add_b" in kw else None,
+                     vol=dev(kw["vol"]) if "vol" in kw else None)
+        rp, rd = orc.flux_div(n, lo, up, lam, Sf, V, **kw)
+        got["flux_div/" + "+".join(sorted(kw)) + "/phi"], got["flux_div/" + "+".join(sorted(kw)) + "/div"] = host(po), host(dv)
+        assert np.array_equal(host(po), rp) and np.array_equal(host(dv), rd), sorted(kw)
+    # fvc::interpolate and fvc::div(faceFlux, vf) (gaussConvectionScheme::fvcDiv): upwind and given weights
+    cellf = syn.splitmix_uniform(12, n)
+    sf = E(nf)
+    asm.face_interpolate(dev(w), dev(cellf), sf)
+    got["face_interpolate"] = host(sf)
+    assert np.array_equal(host(sf), orc.face_interpolate(lo, up, w, cellf))
+    Kf, dv = E(nf), E(n)
+    for wts in (None, w):
+        asm.fvc_div(dev(phi), None if wts is None else dev(wts), dev(cellf), dev(vol), Kf, dv)
+        ref_f = phi * orc.face_interpolate(lo, up, orc.upwind_weights(phi) if wts is None else wts, cellf)
+        tag = "fvc_div/" + ("upwind" if wts is None else "weights")
+        got[tag + "/face"], got[tag + "/div"] = host(Kf), host(dv)
+        assert np.array_equal(host(Kf), ref_f) and np.array_equal(host(dv), orc.surface_integrate(n, lo, up, ref_f, vol)), tag
+    if nf == 0:
+        return got
+    # the fused passes recompute cut faces from their inputs: an output aliasing an input is refused
+    d = dev(delta)
+    with pytest.raises(eng.MiError):
+        asm.fvm_laplacian(d, dev(gam), d, do)
+    l = dev(lam)
+    with pytest.raises(eng.MiError):
+        asm.flux_div(l, [dev(x) for x in Sf], [dev(x) for x in V], l, dv)
+    return got
 
 
 # ---- exact arithmetic --------------------------------------------------------------------------------------------------------------

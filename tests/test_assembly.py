@@ -2,8 +2,8 @@
 import numpy as np
 import pytest
 
-from assembly_support import (OTHER_TABLES, ROW_MODES, box_centres, dot_contracted, euler_ddt_call, fma, gpu_env, set_row_blocks, set_row_tables, shape_case,
-                              shaped_addressing, unfused_sequence)
+from assembly_support import (OTHER_TABLES, ROW_MODES, box_centres, dot_contracted, euler_ddt_call, fma, gpu_env, row_passes_bit_exact, set_row_blocks, set_row_tables,
+                              shape_case, shaped_addressing, unfused_sequence)
 
 
 def box_patches(dims):
@@ -164,53 +164,7 @@ def _row_passes_bit_exact(pkg, orc, monkeypatch, name, mode, tables):
         assert addr.is_ordered and addr.n_tiles > 4
     else:
         assert not addr.is_ordered
-    n, nf, lo, up = case.n_cells, case.n_faces, case.lower_addr, case.upper_addr
-    asm = eng.Assembly(addr)
-    for kind in (0, 1, 2):
-        start = syn.splitmix_uniform(kind, n)
-        io = dev(start)
-        asm.row_face_op(kind, dev(case.lower), dev(case.upper), io)
-        assert np.array_equal(host(io), orc.row_face_op(kind, n, lo, up, case.lower, case.upper, start)), kind
-        io = dev(start)
-        asm.row_face_op(kind, None, dev(case.upper), io)
-        assert np.array_equal(host(io), orc.row_face_op(kind, n, lo, up, None, case.upper, start)), kind
-    delta, gam = 1.0 + syn.splitmix_uniform(7, nf), 0.5 + syn.splitmix_uniform(8, nf)
-    uo, do = E(nf), E(n)
-    asm.fvm_laplacian(dev(delta), dev(gam), uo, do)
-    ru, rd = orc.fvm_laplacian(n, lo, up, delta, gam)
-    assert np.array_equal(host(uo), ru) and np.array_equal(host(do), rd)
-    w, phi = syn.splitmix_uniform(9, nf), syn.splitmix_uniform(10, nf) - 0.5
-    lo_o, uo, do = E(nf), E(nf), E(n)
-    asm.fvm_div(dev(w), dev(phi), lo_o, uo, do)
-    rl, ru, rd = orc.fvm_div(n, lo, up, w, phi)
-    assert np.array_equal(host(lo_o), rl) and np.array_equal(host(uo), ru) and np.array_equal(host(do), rd)
-    vol = 0.5 + syn.splitmix_uniform(11, n)
-    out = E(n)
-    asm.surface_integrate(dev(phi), None, out); assert np.array_equal(host(out), orc.surface_integrate(n, lo, up, phi))
-    asm.surface_integrate(dev(phi), dev(vol), out); assert np.array_equal(host(out), orc.surface_integrate(n, lo, up, phi, vol))
-    Sf = [syn.splitmix_uniform(20 + k, nf) - 0.5 for k in range(3)]
-    g = [E(n) for _ in range(3)]
-    asm.gauss_grad([dev(x) for x in Sf], dev(phi), dev(vol), g)
-    for a, b in zip(g, orc.gauss_grad(n, lo, up, Sf, phi, vol)):
-        assert np.array_equal(host(a), b)
-    # round 5: the flux of an interpolated (scaled) cell vector and its surfaceIntegrate in one row pass (pEqn.H:49-71)
-    lam = syn.splitmix_uniform(30, nf)
-    V = [syn.splitmix_uniform(31 + k, n) - 0.5 for k in range(3)]
-    rho, aA, aB = 0.8 + syn.splitmix_uniform(35, n), syn.splitmix_uniform(36, nf) - 0.5, syn.splitmix_uniform(37, nf)
-    po, dv = E(nf), E(n)
-    for kw in (dict(), dict(scale=rho), dict(scale=rho, add_a=aA, add_b=aB, vol=vol), dict(add_a=aA)):
-        asm.flux_div(dev(lam), [dev(x) for x in Sf], [dev(x) for x in V], po, dv, cell_scale=dev(kw["scale"]) if "scale" in kw else None,
-                     add_a=dev(kw["add_a"]) if "add_a" in kw else None, add_b=dev(kw["add_b"]) if "add_b" in kw else None,
-                     vol=dev(kw["vol"]) if "vol" in kw else None)
-        rp, rd = orc.flux_div(n, lo, up, lam, Sf, V, **kw)
-        assert np.array_equal(host(po), rp) and np.array_equal(host(dv), rd), sorted(kw)
-    # the fused passes recompute cut faces from their inputs: an output aliasing an input is refused
-    d = dev(delta)
-    with pytest.raises(eng.MiError):
-        asm.fvm_laplacian(d, dev(gam), d, do)
-    l = dev(lam)
-    with pytest.raises(eng.MiError):
-        asm.flux_div(l, [dev(x) for x in Sf], [dev(x) for x in V], l, dv)
+    row_passes_bit_exact(eng, orc, syn, case, addr, dev, host, E)
 
 
 def test_compressible_operators_oracle_against_plain_numpy(pkg, orc):
