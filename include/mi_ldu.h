@@ -557,6 +557,56 @@ int mi_grad_boundary_destroy(mi_grad_boundary_t boundary);
 int mi_limited_grad(mi_addr_t addr, const mi_grad_limiter *lim, mi_grad_boundary_t boundary_or_null, int32_t n_comp,
                     const double *const *vf_dev, const double *const *c_dev, const double *const *cf_dev, const double *const *bvalue_dev,
                     const double *const *bcf_dev, double *const *grad_inout_dev, double *const *limiter_out_dev_or_null);
+/* ---- the leastSquares gradient scheme (finiteVolume/gradSchemes/leastSquaresGrad: leastSquaresVectors.C, leastSquaresGrad.C) ----
+ * The reference's device code for this scheme cannot be the definition (leastSquaresGrad.C:120-136 writes through a permutation iterator
+ * whose indices repeat and reads ownLs where the loop it replaces reads neiLs; leastSquaresVectors.C:85-98 does not compile; SURVEY
+ * Appendix B).  The definition is what the two files keep of the upstream algorithm; it is restated in tests/test_least_squares_grad.py,
+ * not pinned by a compiled reference.
+ * mi_grad_scheme_parse: host only, no GPU.  The gradSchemes entry: accepts exactly `Gauss linear`, `leastSquares` and
+ *   `cellLimited|cellMDLimited|faceLimited|faceMDLimited <Gauss linear|leastSquares> <k>` (gradScheme::New, gradScheme.C:34-77; the limited
+ *   constructors cellLimitedGrad.H:88-107 and siblings).  A limited entry fills `limiter` exactly as mi_grad_limiter_parse does (same k range,
+ *   identity, whitespace rules); an unlimited one leaves it zero.  Refused (MI_ERR_ARG): any other base (fourth, ...), another
+ *   interpolation, a limited scheme over a limited one, a trailing token after leastSquares, a missing or extra coefficient, an empty string.
+ *   mi_grad_limiter_parse keeps its narrower grammar.
+ * mi_ls_vectors_create: the least-squares vectors of one mesh, built once on the device (leastSquaresVectors.C:123-225, the host loops):
+ *   dd[c] summed per cell in the loops' order -- internal faces in face order (neighbour side w*wdd, owner side (1 - w)*wdd,
+ *   wdd = (magSf/magSqr(d))*sqr(d), d = C[nei] - C[own]), then the patches in patch order (coupled: ((1 - pw)*pMagSf/magSqr(d))*sqr(d),
+ *   the others (pMagSf/magSqr(d))*sqr(d), d = p.delta() as the caller supplies it) -- then inv(dd) in the host Field<symmTensor> form
+ *   (symmTensorField.C:50-105): CALLER CELL 0 ALONE decides removeCmpts (magSqr(dd[0].cc)/magSqr(dd[0]) < SMALL), a removed component gets
+ *   +1 before and -1 after the inversion in every cell (one 48-byte read-back; this is what makes a one-cell-thick mesh with empty patches
+ *   work), the inversion itself SymmTensorI.H:344-399; then pVectors = (1 - w)*magSfByMagSqrd*(invDd[own] & d), nVectors =
+ *   -w*magSfByMagSqrd*(invDd[nei] & d) and the boundary pVectors (:190-225).  Every expression is rounded operation by operation, left to
+ *   right as written.  c_dev: cell centres [x, y, z]; weights_dev / mag_sf_dev: internal faces; b_*: boundary face fields,
+ *   the patch-ordered concatenation of `boundary` (MI_GRAD_PATCH_COUPLED takes the coupled branch, FIXES_VALUE and OTHER the other one;
+ *   b_weights is read on coupled faces only and may be NULL without them).  boundary NULL: no boundary faces; otherwise it must outlive the
+ *   handle.  A mesh or a cell without faces is legal: such a cell's inverse is not finite and is read by nobody.
+ * mi_ls_vectors_fields: copies the vectors out (LeastSquaresP / LeastSquaresN and the boundary field of LeastSquaresP), three arrays each,
+ *   the caller's face order; bp_out may be NULL when the boundary has no faces.
+ * mi_ls_grad: the gradient's internal field in ONE row pass (grad_out_dev[3*j + k] = d(vf_j)/dx_k, n_comp = 1 or 3): the loop of
+ *   leastSquaresGrad.C:109-118 then the patches (:139-189) with the arithmetic of leastSquaresCalcGradFunctor (:39-53) contracted as every
+ *   device functor is (inferred, not pinned): delta rounded once, then grad[3*j + k] = fma(+-ls_k, delta_j, grad[3*j + k]).
+ *   Per cell: the neighbour-side faces ascending (nVectors, delta = vf[c] - vf[own(f)], fma(-ls_k, ...)), its own faces ascending
+ *   (pVectors, delta = vf[nei(f)] - vf[c]), its boundary faces by patch and face (fma(bLs_k, bvalue - vf[c], g_k)); no division by V; a
+ *   cell without faces gets +0.  bvalue_dev[j]: per boundary face the patchNeighbourField (coupled) or the boundary value (the others), as
+ *   for mi_limited_grad.  The gradient's boundary values stay the caller's (mi_patch_gauss_grad_correct, which leastSquaresGrad.C:193 calls too).
+ *   A limited leastSquares gradient is mi_ls_grad followed by mi_limited_grad (cellLimitedGrad::calcGrad takes any basicGradScheme_).
+ * Refused (MI_ERR_ARG, nothing launched): n_comp not 1 or 3, a missing array, a boundary built for another addressing, NULL boundary
+ *   arrays while the boundary has faces, an output that aliases an input or another output. */
+enum { MI_GRAD_BASE_GAUSS_LINEAR, MI_GRAD_BASE_LEAST_SQUARES };
+typedef struct mi_grad_scheme {
+    int32_t base;          /* MI_GRAD_BASE_* */
+    int32_t limited;       /* 1: `limiter` holds the limited scheme wrapped around the base */
+    mi_grad_limiter limiter;
+} mi_grad_scheme;
+typedef struct mi_ls_vectors_s *mi_ls_vectors_t;
+int mi_grad_scheme_parse(const char *scheme, mi_grad_scheme *out);
+int mi_ls_vectors_create(mi_addr_t addr, mi_grad_boundary_t boundary_or_null, const double *const *c_dev, const double *weights_dev,
+                         const double *mag_sf_dev, const double *b_weights_dev, const double *b_mag_sf_dev, const double *const *b_delta_dev,
+                         mi_ls_vectors_t *out);
+int mi_ls_vectors_destroy(mi_ls_vectors_t lsv);
+int mi_ls_vectors_fields(mi_ls_vectors_t lsv, double *const *p_out_dev, double *const *n_out_dev, double *const *bp_out_dev_or_null);
+int mi_ls_grad(mi_ls_vectors_t lsv, int32_t n_comp, const double *const *vf_dev, const double *const *bvalue_dev_or_null,
+               double *const *grad_out_dev);
 int mi_vec_axpby(mi_ctx_t ctx, int64_t n, double a, const double *x_dev, double b, const double *y_dev, double *out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),

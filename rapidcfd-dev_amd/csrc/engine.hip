@@ -2501,6 +2501,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "gamg_engine.inc"
 #include "assembly.inc"
 #include "limited_grad.inc"
+#include "least_squares.inc"
 
 mi_matrix_s::~mi_matrix_s()
 {

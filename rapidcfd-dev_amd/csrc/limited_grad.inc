@@ -183,6 +183,7 @@ struct mi_grad_boundary_s {
     mi_addr_s* addr = nullptr;
     int32_t nCells = 0, nFaces = 0, nLimited = 0;
     DevBuf<int32_t> allStart, all, limStart, lim;
+    std::vector<int32_t> patchSizes, patchKinds;      // the patches as given (least_squares.inc marks the coupled faces from them)
 };
 
 namespace {
@@ -207,13 +208,10 @@ int grad_lim_check(const char* who, const mi_grad_limiter* l)
     if (l->identity != (l->k < 1.0e-15 ? 1 : 0)) return fail(MI_ERR_ARG, std::string(who) + ": identity must be k < SMALL");
     return MI_OK;
 }
-} // namespace
-
-extern "C" int mi_grad_limiter_parse(const char* scheme, mi_grad_limiter* out)
+// whitespace-separated words, as the reference's Istream reads them
+std::vector<std::string> grad_tokens(const char* scheme)
 {
-    const char* who = "mi_grad_limiter_parse";
-    if (!scheme || !out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
-    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
+    std::vector<std::string> tok;
     auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
     for (const char* c = scheme; *c;) {
         while (*c && sp(*c)) ++c;
@@ -221,8 +219,30 @@ extern "C" int mi_grad_limiter_parse(const char* scheme, mi_grad_limiter* out)
         while (*c && !sp(*c)) ++c;
         if (c > b) tok.emplace_back(b, c);
     }
+    return tok;
+}
+int grad_lim_kind(const std::string& s) { for (int k = 0; k < 4; ++k) if (s == kGradLimNames[k]) return k; return -1; }
+// the coefficient token of a limited scheme (readScalar, then the constructors' range check)
+int grad_lim_fill(const char* who, int kind, const std::string& ktok, mi_grad_limiter* out)
+{
+    char* end = nullptr;
+    const double k = std::strtod(ktok.c_str(), &end);
+    if (end == ktok.c_str() || *end != '\0') return fail(MI_ERR_ARG, std::string(who) + ": '" + ktok + "' is not a number");
+    mi_grad_limiter l{};
+    l.kind = kind; l.k = k; l.identity = k < 1.0e-15 ? 1 : 0;
+    MICHK(grad_lim_check(who, &l));
+    *out = l;
+    return MI_OK;
+}
+} // namespace
+
+extern "C" int mi_grad_limiter_parse(const char* scheme, mi_grad_limiter* out)
+{
+    const char* who = "mi_grad_limiter_parse";
+    if (!scheme || !out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    const std::vector<std::string> tok = grad_tokens(scheme);
     if (tok.empty()) return fail(MI_ERR_ARG, std::string(who) + ": empty scheme");
-    auto kind_of = [](const std::string& s) { for (int k = 0; k < 4; ++k) if (s == kGradLimNames[k]) return k; return -1; };
+    auto kind_of = grad_lim_kind;
     const int kind = kind_of(tok[0]);
     if (kind < 0) return fail(MI_ERR_ARG, std::string(who) + ": unknown limited gradient scheme '" + tok[0] + "'");
     if (tok.size() < 2) return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[0] + "' needs a base gradient scheme and a coefficient");
@@ -232,14 +252,7 @@ extern "C" int mi_grad_limiter_parse(const char* scheme, mi_grad_limiter* out)
     if (tok[2] != "linear") return fail(MI_ERR_ARG, std::string(who) + ": interpolation scheme '" + tok[2] + "' is not supported (only linear)");
     if (tok.size() < 4) return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[0] + "' needs the coefficient k");
     if (tok.size() > 4) return fail(MI_ERR_ARG, std::string(who) + ": extra '" + tok[4] + "'");
-    char* end = nullptr;
-    const double k = std::strtod(tok[3].c_str(), &end);
-    if (end == tok[3].c_str() || *end != '\0') return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[3] + "' is not a number");
-    mi_grad_limiter l{};
-    l.kind = kind; l.k = k; l.identity = k < 1.0e-15 ? 1 : 0;
-    MICHK(grad_lim_check(who, &l));
-    *out = l;
-    return MI_OK;
+    return grad_lim_fill(who, kind, tok[3], out);
 }
 
 extern "C" int mi_grad_boundary_create(mi_addr_t a, int32_t n_patches, const int32_t* patch_sizes, const int32_t* const* face_cells_host,
@@ -281,6 +294,7 @@ extern "C" int mi_grad_boundary_create(mi_addr_t a, int32_t n_patches, const int
     HIPCHK(hipSetDevice(a->ctx->device));
     mi_grad_boundary_s* b = new mi_grad_boundary_s();
     b->ctx = a->ctx; b->addr = a; b->nCells = n; b->nFaces = (int32_t)total; b->nLimited = limStart[n];
+    if (n_patches > 0) { b->patchSizes.assign(patch_sizes, patch_sizes + n_patches); b->patchKinds.assign(patch_kinds, patch_kinds + n_patches); }
     hipStream_t s = a->ctx->stream;
     int r = MI_OK;
     if (b->nFaces > 0) { r = b->allStart.upload(allStart, s); if (r == MI_OK) r = b->all.upload(all, s); }

@@ -78,6 +78,7 @@ SYMBOLS = [
     "mi_fvm_assemble_local",
     "mi_sngrad_parse", "mi_sngrad_limited_correction_flux", "mi_patch_sngrad_limited_correction_flux",
     "mi_fvc_div_dev_tgrad", "mi_patch_gauss_grad_correct", "mi_patch_dev_tgrad_flux",
+    "mi_grad_scheme_parse", "mi_ls_vectors_create", "mi_ls_vectors_destroy", "mi_ls_vectors_fields", "mi_ls_grad",
 ]
 
 
@@ -1145,6 +1146,45 @@ class GradBoundary:
             self.h = C.c_void_p()
 
 
+class GradScheme(C.Structure):
+    """mi_grad_scheme (include/mi_ldu.h)"""
+    _fields_ = [("base", C.c_int32), ("limited", C.c_int32), ("limiter", GradLimiter)]
+
+
+GRAD_BASES = ("Gauss linear", "leastSquares")
+
+
+def grad_scheme(scheme: str) -> GradScheme:
+    """mi_grad_scheme_parse: a gradSchemes entry -- "Gauss linear", "leastSquares", "cellLimited leastSquares 1",
+    "faceMDLimited Gauss linear 0.5" ... (host only, no GPU)"""
+    out = GradScheme()
+    _chk(lib().mi_grad_scheme_parse(scheme.encode(), C.byref(out)))
+    return out
+
+
+class LsVectors:
+    """The least-squares vectors of a mesh, built once on the device (mi_ls_vectors_create): centres [x, y, z] cell arrays, weights / mag_sf
+    internal-face arrays, b_weights / b_mag_sf / b_delta ([x, y, z]) boundary-face arrays in the patch order of `boundary` (a GradBoundary or
+    None; b_weights is read on coupled patches only).  The boundary must stay open as long as the vectors are used."""
+
+    def __init__(self, addr: Addressing, boundary, centres, weights, mag_sf, b_weights=None, b_mag_sf=None, b_delta=None):
+        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        self.addr, self.boundary = addr, boundary
+        self.h = C.c_void_p()
+        _chk(lib().mi_ls_vectors_create(addr.h, boundary.h if boundary is not None else None, pv(centres), _ptr(weights), _ptr(mag_sf),
+                                        _ptr(b_weights), _ptr(b_mag_sf), pv(b_delta), C.byref(self.h)))
+
+    def fields(self, p_out, n_out, bp_out=None):
+        """copies pVectors, nVectors (internal faces) and the boundary pVectors into three arrays each (mi_ls_vectors_fields)"""
+        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_ls_vectors_fields(self.h, pv(p_out), pv(n_out), pv(bp_out)))
+
+    def close(self):
+        if self.h:
+            lib().mi_ls_vectors_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Assembly:
     """fvm::div / fvm::laplacian / negSumDiag / relax ... on caller-order arrays of an Addressing."""
 
@@ -1317,6 +1357,15 @@ class Assembly:
         pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
         _chk(lib().mi_limited_grad(self.addr.h, C.byref(lim), boundary.h if boundary is not None else None, C.c_int32(len(vf)), pv(vf),
                                    pv(centres), pv(cf), pv(bvalue), pv(bcf), pv(grad), pv(limiter_out)))
+
+    def ls_grad(self, lsv, vf, grad_out, bvalue=None):
+        """the leastSquares gradient's internal field in one row pass (mi_ls_grad): lsv an LsVectors of this addressing, vf 1 or 3 cell arrays,
+        grad_out 3 or 9 (grad_out[3*j + k] = d(vf_j)/dx_k), bvalue one boundary-face array per component (patchNeighbourField on coupled
+        patches, the boundary value elsewhere)"""
+        if lsv.addr is not self.addr:
+            raise MiError("ls_grad: the vectors were built for another addressing")
+        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_ls_grad(lsv.h, C.c_int32(len(vf)), pv(vf), pv(bvalue), pv(grad_out)))
 
     def lust_weights(self, cd_weights, face_flux, w_out):
         """LUST weights 0.75*cd_weights + 0.25*pos(faceFlux) (LUST.H:104-110)"""

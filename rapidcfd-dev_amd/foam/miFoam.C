@@ -1344,6 +1344,59 @@ void fvc::limitedGrad(vectorgpuField* const g[3], const lduAddressing& a, const 
                             limiter ? lim : nullptr), "fvc::grad (limited)");
 }
 
+// ---- the leastSquares gradient scheme ----------------------------------------------------------------------------------------------
+fv::gradScheme fv::gradScheme::New(const std::string& entry)
+{
+    mi_grad_scheme s{};
+    miCheck(mi_grad_scheme_parse(entry.c_str(), &s), "gradScheme::New");
+    return gradScheme(s);
+}
+fv::limitedGradScheme fv::gradScheme::limiter() const
+{
+    if (!s_.limited) FatalErrorIn("gradScheme::limiter", "the gradient scheme is not a limited one");
+    return limitedGradScheme(s_.limiter);
+}
+leastSquaresVectors::leastSquaresVectors(const lduAddressing& a, const gradBoundary* b, const vectorgpuField& C, const scalargpuField& weights,
+                                         const scalargpuField& magSf, const scalargpuField* bWeights, const scalargpuField* bMagSf,
+                                         const vectorgpuField* bDelta)
+    : h_(nullptr), nFaces_(weights.size()), nBFaces_(bMagSf ? bMagSf->size() : 0)
+{
+    const auto c = cmptData(C);
+    const double* bd[3] = {nullptr, nullptr, nullptr};
+    if (bDelta) for (int d = 0; d < 3; ++d) bd[d] = bDelta->component(d).data();
+    miCheck(mi_ls_vectors_create(a.handle(), b ? b->handle() : nullptr, c, weights.data(), magSf.data(), bWeights ? bWeights->data() : nullptr,
+                                 bMagSf ? bMagSf->data() : nullptr, bDelta ? bd : nullptr, &h_), "leastSquaresVectors::New");
+}
+leastSquaresVectors::~leastSquaresVectors() { if (h_) mi_ls_vectors_destroy(h_); }
+void leastSquaresVectors::fields(vectorgpuField& pVectors, vectorgpuField& nVectors, vectorgpuField* bPVectors) const
+{
+    if (pVectors.size() != nFaces_ || nVectors.size() != nFaces_ || (bPVectors && bPVectors->size() != nBFaces_))
+        FatalErrorIn("leastSquaresVectors::fields", "the fields have another size than the mesh's faces");
+    const auto p = cmptData(pVectors);
+    const auto n = cmptData(nVectors);
+    double* bp[3] = {nullptr, nullptr, nullptr};
+    if (bPVectors) for (int d = 0; d < 3; ++d) bp[d] = bPVectors->component(d).data();
+    miCheck(mi_ls_vectors_fields(h_, p, n, bPVectors ? bp : nullptr), "leastSquaresVectors::fields");
+}
+void fvc::leastSquaresGrad(vectorgpuField& g, const leastSquaresVectors& lsv, const scalargpuField& vf, const scalargpuField* bValue)
+{
+    const double* v[1] = {vf.data()};
+    const double* bv[1] = {bValue ? bValue->data() : nullptr};
+    const auto gr = cmptData(g);
+    miCheck(mi_ls_grad(lsv.handle(), 1, v, bValue ? bv : nullptr, gr), "fvc::grad (leastSquares)");
+}
+void fvc::leastSquaresGrad(vectorgpuField* const g[3], const leastSquaresVectors& lsv, const vectorgpuField& vf, const vectorgpuField* bValue)
+{
+    const double *v[3], *bv[3] = {nullptr, nullptr, nullptr};
+    double* gr[9];
+    for (int d = 0; d < 3; ++d) {
+        v[d] = vf.component(d).data();
+        if (bValue) bv[d] = bValue->component(d).data();
+        for (int k = 0; k < 3; ++k) gr[3 * d + k] = g[d]->component(k).data();
+    }
+    miCheck(mi_ls_grad(lsv.handle(), 3, v, bValue ? bv : nullptr, gr), "fvc::grad (leastSquares)");
+}
+
 // ---- steadyState, localEuler, CoEuler and the bounded convection scheme ----
 namespace {
 mi_ddt_local_scheme parseLocal(const std::string& scheme, int kind, const char* name)
