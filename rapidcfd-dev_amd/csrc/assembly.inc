@@ -1469,7 +1469,9 @@ int ensure_caller_tables(mi_addr_s* a)
     }
     return MI_OK;
 }
-int grid_for(int n) { int b = (n + 255) / 256; return b < 1 ? 1 : (b > 8192 ? 8192 : b); }
+// workgroups of a face pass or a unique-cell patch pass: one thread per item up to the context's cap (MI_FACE_GRID, 8192 unless a
+// test lowers it); past it the kernel's own loop -- grid-stride or block_chunk -- walks the rest, so EVERY kernel launched with it loops
+int grid_for(const mi_ctx_s* c, int n) { const int b = (n + 255) / 256, cap = c->faceGrid; return b < 1 ? 1 : (b > cap ? cap : b); }
 // a mesh without internal faces is legal lduAddressing (one cell; cells joined by patches only): its face arrays are empty, an empty
 // array's pointer may be NULL and is never read -- the entries ask for a face array only of a mesh that has faces (shown by the
 // meshes one_cell and no_faces of tests/test_degenerate_meshes.py)
@@ -1512,7 +1514,7 @@ extern "C" int mi_patch_add(mi_patch_t p, const double* pf_dev, double* intf_dev
     if (p->nUnique == 0) return MI_OK;
     HIPCHK(hipSetDevice(p->ctx->device));
     hipStream_t s = p->ctx->stream;
-    const int g = grid_for(p->nUnique);
+    const int g = grid_for(p->ctx, p->nUnique);
     if (fn == 0) k_patch_add<0><<<g, 256, 0, s>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, intf_dev, p->nUnique);
     else if (fn == 1) k_patch_add<1><<<g, 256, 0, s>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, intf_dev, p->nUnique);
     else k_patch_add<2><<<g, 256, 0, s>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, intf_dev, p->nUnique);
@@ -1527,7 +1529,7 @@ extern "C" int mi_patch_max(mi_patch_t p, const double* pf_dev, double* cell_ino
     if (pf_dev == cell_inout_dev) return fail(MI_ERR_ARG, "mi_patch_max: the patch field must not be the cell field");
     if (p->nUnique == 0) return MI_OK;
     HIPCHK(hipSetDevice(p->ctx->device));
-    k_patch_max<<<grid_for(p->nUnique), 256, 0, p->ctx->stream>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, cell_inout_dev, p->nUnique);
+    k_patch_max<<<grid_for(p->ctx, p->nUnique), 256, 0, p->ctx->stream>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, cell_inout_dev, p->nUnique);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -1539,7 +1541,7 @@ extern "C" int mi_patch_add_product(mi_patch_t p, const double* pf_dev, const do
     if (p->nUnique == 0) return MI_OK;
     HIPCHK(hipSetDevice(p->ctx->device));
     hipStream_t s = p->ctx->stream;
-    const int g = grid_for(p->nUnique);
+    const int g = grid_for(p->ctx, p->nUnique);
     if (fn == 0) k_patch_add<0, true><<<g, 256, 0, s>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, intf_dev, p->nUnique, q_dev);
     else k_patch_add<1, true><<<g, 256, 0, s>>>(p->cells.p, p->start.p, p->sort.p, pf_dev, intf_dev, p->nUnique, q_dev);
     HIPCHK(hipGetLastError());
@@ -1707,8 +1709,8 @@ extern "C" int mi_linear_upwind_correction(mi_addr_t a, const mi_div_correction*
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces == 0) return MI_OK;
-    k_linear_upwind_corr<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, face_flux_dev, q, o, n_rhs, a->L.nFaces,
-                                                                            a->ctx->xcdRows);
+    k_linear_upwind_corr<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, face_flux_dev, q, o, n_rhs, a->L.nFaces,
+                                                                                    a->ctx->xcdRows);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -1930,7 +1932,7 @@ extern "C" int mi_face_interpolate(mi_addr_t a, const double* lambda_dev, const 
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces == 0) return MI_OK;
-    k_face_interpolate<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, lambda_dev, phi_dev, sf_dev, a->L.nFaces);
+    k_face_interpolate<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, lambda_dev, phi_dev, sf_dev, a->L.nFaces);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -1945,7 +1947,7 @@ extern "C" int mi_fvc_div(mi_addr_t a, const double* face_flux_dev, const double
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces > 0) {
-        k_face_conv_flux<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, weights_dev_or_null, face_flux_dev, vf_dev, face_out_dev, a->L.nFaces);
+        k_face_conv_flux<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, weights_dev_or_null, face_flux_dev, vf_dev, face_out_dev, a->L.nFaces);
         HIPCHK(hipGetLastError());
     }
     return row_sum<M_PLUS, M_MINUS>(a, face_out_dev, face_out_dev, nullptr, vol_dev_or_null, div_out_dev);
@@ -1961,8 +1963,8 @@ extern "C" int mi_sngrad_correction_flux(mi_addr_t a, const double* cvx_dev, con
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces == 0) return MI_OK;
-    k_sngrad_corr_flux<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, cvx_dev, cvy_dev, cvz_dev, weights_dev, gx_dev, gy_dev,
-                                                                          gz_dev, gamma_magsf_dev_or_null, flux_out_dev, a->L.nFaces);
+    k_sngrad_corr_flux<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, cvx_dev, cvy_dev, cvz_dev, weights_dev, gx_dev, gy_dev,
+                                                                                  gz_dev, gamma_magsf_dev_or_null, flux_out_dev, a->L.nFaces);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -2067,7 +2069,7 @@ int sngrad_limited_internal(const std::string& who, mi_addr_s* a, double k, cons
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces == 0) return MI_OK;
-    k_sngrad_limited_flux<NCOMP><<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, q);
+    k_sngrad_limited_flux<NCOMP><<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, q);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -2209,11 +2211,11 @@ extern "C" int mi_fvm_set_reference(mi_addr_t a, int32_t celli, double value, do
 __global__ void k_set_values_cells(const int32_t* __restrict__ labels, const double* __restrict__ values, int nSet, double* __restrict__ psi,
                                    const double* __restrict__ diag, double* __restrict__ source, uint8_t* __restrict__ mask, double* __restrict__ val)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nSet) return;
-    const int c = labels[i];
-    const double v = values[i];
-    psi[c] = v; source[c] = v * diag[c]; mask[c] = 1; val[c] = v;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nSet; i += gridDim.x * blockDim.x) {
+        const int c = labels[i];
+        const double v = values[i];
+        psi[c] = v; source[c] = v * diag[c]; mask[c] = 1; val[c] = v;
+    }
 }
 template <bool UPSTREAM>
 __global__ void k_set_values_rows(const int32_t* __restrict__ os, const int32_t* __restrict__ ls, const int32_t* __restrict__ losort,
@@ -2261,14 +2263,14 @@ extern "C" int mi_fvm_set_values(mi_addr_t a, int32_t n_set, const int32_t* cell
     if (a->setMask.n != (size_t)n) { MICHK(a->setMask.alloc((size_t)n)); MICHK(a->setVal.alloc((size_t)n)); }
     HIPCHK(hipMemsetAsync(a->setMask.p, 0, (size_t)n, s));
     const double* L = lower_in_dev ? lower_in_dev : upper_in_dev;
-    if (n_set > 0) k_set_values_cells<<<grid_for(n_set), 256, 0, s>>>(cell_labels_dev, values_dev, n_set, psi_dev, diag_dev, source_dev, a->setMask.p, a->setVal.p);
+    if (n_set > 0) k_set_values_cells<<<grid_for(c, n_set), 256, 0, s>>>(cell_labels_dev, values_dev, n_set, psi_dev, diag_dev, source_dev, a->setMask.p, a->setVal.p);
     if (n > 0) {
         if (upstream_semantics) k_set_values_rows<true><<<(n + 255) / 256, 256, 0, s>>>(a->ownerStartC.p, a->losortStartC.p, a->losortC.p, a->lowerAddr.p, a->upperAddr.p, a->setMask.p, a->setVal.p, upper_in_dev, L, source_dev, n);
         else k_set_values_rows<false><<<(n + 255) / 256, 256, 0, s>>>(a->ownerStartC.p, a->losortStartC.p, a->losortC.p, a->lowerAddr.p, a->upperAddr.p, a->setMask.p, a->setVal.p, upper_in_dev, L, source_dev, n);
     }
     if (nf > 0) {
-        if (upstream_semantics) k_set_values_faces<true><<<grid_for(nf), 256, 0, s>>>(a->lowerAddr.p, a->upperAddr.p, a->setMask.p, upper_in_dev, L, upper_out_dev, lower_out_dev, nf);
-        else k_set_values_faces<false><<<grid_for(nf), 256, 0, s>>>(a->lowerAddr.p, a->upperAddr.p, a->setMask.p, upper_in_dev, L, upper_out_dev, lower_out_dev, nf);
+        if (upstream_semantics) k_set_values_faces<true><<<grid_for(c, nf), 256, 0, s>>>(a->lowerAddr.p, a->upperAddr.p, a->setMask.p, upper_in_dev, L, upper_out_dev, lower_out_dev, nf);
+        else k_set_values_faces<false><<<grid_for(c, nf), 256, 0, s>>>(a->lowerAddr.p, a->upperAddr.p, a->setMask.p, upper_in_dev, L, upper_out_dev, lower_out_dev, nf);
     }
     for (int32_t p = 0; p < n_patches; ++p) {
         if (!patches[p] || patches[p]->nFaces == 0) continue;
@@ -2358,7 +2360,7 @@ extern "C" int mi_flux_div(mi_addr_t a, const double* lambda_dev, const double* 
     //  in round 5, measured slower (832 against ~560 us at 216^3, 2.26 x the algorithmic traffic: profiles/r05_assembly_pmc.md) and removed
     //  in round 6; the face pass + row sum below is the only form)
     if (a->L.nFaces > 0) {
-        k_face_flux<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, phi_out_dev, a->L.nFaces);
+        k_face_flux<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, phi_out_dev, a->L.nFaces);
         HIPCHK(hipGetLastError());
     }
     return row_sum<M_PLUS, M_MINUS>(a, phi_out_dev, phi_out_dev, nullptr, vol_dev_or_null, div_out_dev);
@@ -2372,7 +2374,7 @@ extern "C" int mi_ddt_phi_corr(mi_addr_t a, double r_delta_t, const double* lamb
     if (a->L.nFaces == 0) return MI_OK;
     if (!phi_old_dev || !out_dev) return fail(MI_ERR_ARG, "mi_ddt_phi_corr: bad argument");
     ra.sc = rho_old_dev_or_null;
-    k_ddt_phi_corr<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, r_delta_t, phi_old_dev, out_dev, a->L.nFaces);
+    k_ddt_phi_corr<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, r_delta_t, phi_old_dev, out_dev, a->L.nFaces);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -2463,7 +2465,7 @@ extern "C" int mi_ddt_phi_corr_backward(mi_addr_t a, double r_delta_t, const dou
     k.u0[0] = ux_old_dev; k.u0[1] = uy_old_dev; k.u0[2] = uz_old_dev; k.u00[0] = ux_old_old_dev; k.u00[1] = uy_old_old_dev; k.u00[2] = uz_old_old_dev;
     k.rho0 = rho_old_dev_or_null; k.rho00 = rho_old_old_dev_or_null; k.phi0 = phi_old_dev; k.phi00 = phi_old_old_dev; k.out = out_dev;
     k.rdt = r_delta_t; k.c0 = coeffs[1]; k.c00 = coeffs[2]; k.nf = a->L.nFaces; k.xcd = a->ctx->xcdRows;
-    k_ddt_phi_corr_backward<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(k);
+    k_ddt_phi_corr_backward<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(k);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -2662,7 +2664,7 @@ extern "C" int mi_ddt_phi_corr_local(mi_addr_t a, const double* r_delta_t_dev, c
     for (const double* q : {r_delta_t_dev, lambda_dev, sfx_dev, sfy_dev, sfz_dev, ux_old_dev, uy_old_dev, uz_old_dev})
         if (q == out_dev) return fail(MI_ERR_ARG, std::string(who) + ": the output must not alias an input that other faces read");
     if (a->L.nFaces == 0) return MI_OK;
-    k_ddt_phi_corr_local<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, r_delta_t_dev, phi_old_dev, out_dev, a->L.nFaces);
+    k_ddt_phi_corr_local<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(ra, r_delta_t_dev, phi_old_dev, out_dev, a->L.nFaces);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -2735,7 +2737,7 @@ extern "C" int mi_limited_linear_weights(mi_addr_t a, double k, const double* cd
     MICHK(ensure_caller_tables(a));
     if (a->L.nFaces == 0) return MI_OK;
     const double twoByk = 2.0 / (k > 1e-15 ? k : 1e-15);
-    k_limited_linear_weights<<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, twoByk, cd_weights_dev, face_flux_dev,
+    k_limited_linear_weights<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(a->lowerAddr.p, a->upperAddr.p, twoByk, cd_weights_dev, face_flux_dev,
         phi_dev, gradx_dev, grady_dev, gradz_dev, cx_dev, cy_dev, cz_dev, weights_out_dev, limiter_out_dev_or_null, a->L.nFaces, a->ctx->xcdRows);
     HIPCHK(hipGetLastError());
     return MI_OK;
@@ -2867,7 +2869,7 @@ extern "C" int mi_limited_weights(mi_addr_t a, const mi_limiter* lim, const doub
     if (a->L.nFaces == 0) return MI_OK;
     q.lo = a->lowerAddr.p; q.up = a->upperAddr.p; q.w = weights_out_dev; q.limOut = limiter_out_dev_or_null;
     q.nf = a->L.nFaces; q.xcd = a->ctx->xcdRows;
-    dispatch_k_limited_weights(lim->kind, lim->vector_form != 0, dim3(grid_for(a->L.nFaces)), dim3(256), a->ctx->stream, q);
+    dispatch_k_limited_weights(lim->kind, lim->vector_form != 0, dim3(grid_for(a->ctx, a->L.nFaces)), dim3(256), a->ctx->stream, q);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -2969,8 +2971,8 @@ extern "C" int mi_fvc_div_dev_tgrad(mi_addr_t a, int32_t kind, const double* lam
     for (int i = 0; i < 9; ++i) fa.g[i] = grad_dev[i];
     for (int j = 0; j < 3; ++j) fa.out[j] = face_out_dev[j];
     fa.nf = a->L.nFaces; fa.xcd = a->ctx->xcdRows;
-    if (kind == MI_DEV) k_face_dev_tgrad_flux<MI_DEV><<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(fa);
-    else k_face_dev_tgrad_flux<MI_DEV2><<<grid_for(a->L.nFaces), 256, 0, a->ctx->stream>>>(fa);
+    if (kind == MI_DEV) k_face_dev_tgrad_flux<MI_DEV><<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(fa);
+    else k_face_dev_tgrad_flux<MI_DEV2><<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(fa);
     HIPCHK(hipGetLastError());
     RowSum3Args ra{};
     const mi_addr_s::RowPlan& rp = a->rowPlan[1];                // the gradient's plan: three staged arrays against its four

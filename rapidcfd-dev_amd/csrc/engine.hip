@@ -84,7 +84,7 @@ struct mi_ctx_s {
     // the switches of the context moment: mi_ctx_create fills every one from its row of switches.hpp (CTX_SWITCHES below), which says what it means
     int tileFlags = 0, attachEvents = 0, persist = 0, xcdRows = 0, deferPsi = 0, fusePerm = 0, pairAT = 0, fusePrologue = 0, multiPipe = 0, winDirect = 0, gamgGraphAttached = 0;
     int pcgPersist = 0, pcgFuseRP = 0, pcgFuseTest = 0, persistGrid = 0, persistShared = 0, fuseFinal = 0, amulBS = 0, pcgBatch = 0, pcgGraph = 0, pbicgHostStepped = 0;
-    int gamgDeviceInvert = 0, gamgAlwaysAgglomerate = 0, gamgGraph = 0, gamgFuse = 0;
+    int gamgDeviceInvert = 0, gamgAlwaysAgglomerate = 0, gamgGraph = 0, gamgFuse = 0, faceGrid = 0;
     int64_t stats[13] = {}; // mi_ctx_stat
     int persistCoop = -1; // cooperative launch of the persistent kernel possible on this device AND its barrier litmus clean (-1: not asked yet)
     uint64_t faultEpoch = 0; // faults of the persistent kernel reported on this context so far (fetch_state); a matrix re-zeroes its barrier words when it has missed one
@@ -103,7 +103,7 @@ static constexpr CtxSwitch CTX_SWITCHES[] = {
     {SW_PCG_FUSE_RP, &mi_ctx_s::pcgFuseRP}, {SW_PCG_FUSE_TEST, &mi_ctx_s::pcgFuseTest}, {SW_PERSIST_GRID, &mi_ctx_s::persistGrid}, {SW_PERSIST_SHARED, &mi_ctx_s::persistShared},
     {SW_PCG_FUSE_FINAL, &mi_ctx_s::fuseFinal}, {SW_AMUL_BS, &mi_ctx_s::amulBS}, {SW_PCG_BATCH, &mi_ctx_s::pcgBatch}, {SW_PCG_GRAPH, &mi_ctx_s::pcgGraph},
     {SW_PBICG_HOST_STEPPED, &mi_ctx_s::pbicgHostStepped}, {SW_GAMG_DEVICE_INVERT, &mi_ctx_s::gamgDeviceInvert}, {SW_GAMG_ALWAYS_AGGLOMERATE, &mi_ctx_s::gamgAlwaysAgglomerate},
-    {SW_GAMG_GRAPH, &mi_ctx_s::gamgGraph}, {SW_GAMG_FUSE, &mi_ctx_s::gamgFuse},
+    {SW_GAMG_GRAPH, &mi_ctx_s::gamgGraph}, {SW_GAMG_FUSE, &mi_ctx_s::gamgFuse}, {SW_FACE_GRID, &mi_ctx_s::faceGrid},
 };
 constexpr bool ctx_switches_match_table()   // every sw::CTX row exactly once, no other row at all
 {
@@ -300,6 +300,7 @@ extern "C" int mi_ctx_create(int device, void* hip_stream, mi_ctx_t* out)
     }
     { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess) c->nCU = pr.multiProcessorCount; }
     for (const CtxSwitch& s : CTX_SWITCHES) ctx_store(c, s, sw::get(s.id));
+    if (c->faceGrid < 1) c->faceGrid = 1;
     if (c->pcgBatch < 1) c->pcgBatch = 1;   // every batched loop advances by the batch length: 0 or less would never end
     if (c->amulBS != 256 && c->amulBS != 512 && c->amulBS != 1024) c->amulBS = 0;   // 0 = choose per launch from the LDS footprint
     *out = c;

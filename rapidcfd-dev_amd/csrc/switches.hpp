@@ -83,6 +83,7 @@ namespace mi {
     X(ROW_CAP,                 "MI_ROW_CAP",                 0,        ROWS,          DIAG,      nullptr,               "forced staging capacity of the assembly row passes: a small value sends blocks down the unstaged path") \
     X(ROW_BS,                  "MI_ROW_BS",                  1024,     ROWS,          DIAG,      nullptr,               "cells per block of the one- and two-array row passes when the numbering is not tile-contiguous: 256, 512 or 1024") \
     X(GRAD_BS,                 "MI_GRAD_BS",                 256,      ROWS,          DIAG,      nullptr,               "... of the four-array gradient pass") \
+    X(FACE_GRID,               "MI_FACE_GRID",               8192,     CTX,           DIAG,      nullptr,               "the most workgroups (of 256 threads) a face pass or a unique-cell patch pass of assembly.inc is launched with (grid_for); below 1 = 1; a small value makes every such kernel walk its loop on a small mesh (tests)") \
     X(GAMG_ALWAYS_AGGLOMERATE, "MI_GAMG_ALWAYS_AGGLOMERATE", 0,        CTX,           DIAG,      nullptr,               "1: the level matrices are agglomerated again at every solve, also for unchanged coefficients") \
     X(MATCH_PARALLEL,          "MI_MATCH_PARALLEL",          0,        ADDR | HIER,   DIAG,      nullptr,               "1: large levels of the tile clustering (tiling.cpp) and of the pair agglomeration (gamg.cpp) are matched by the host threads; measured slower (profiles/r04_p_*)") \
     X(MATCH_LATER_ONLY,        "MI_MATCH_LATER_ONLY",        1,        HIER,          DIAG,      nullptr,               "the pair agglomeration looks only at faces to later cells (forward sweep over owned faces); 0 = every face of a cell") \

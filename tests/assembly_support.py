@@ -57,6 +57,16 @@ def set_row_blocks(monkeypatch, mode, grad=False):
         monkeypatch.setenv("MI_ROW_CAP", "64")
 
 
+def set_face_grid(monkeypatch, blocks):
+    """the most workgroups a face pass or a unique-cell patch pass is launched with (MI_FACE_GRID; None: the default, 8192).  Call it
+    BEFORE gpu_env: the switch is read by mi_ctx_create.  A small value makes every such kernel walk its grid-stride or block_chunk loop
+    on a small mesh (tests/test_launch_grids.py)"""
+    if blocks is None:
+        monkeypatch.delenv("MI_FACE_GRID", raising=False)
+    else:
+        monkeypatch.setenv("MI_FACE_GRID", str(blocks))
+
+
 def shaped_addressing(eng, ctx, syn, case, mode):
     """-> (case, addr).  tiles*: the case renumbered into the tile order of a probe addressing, under ordered addressing on the probe's
     tile starts (the row passes own the layout's tiles); otherwise the case as it is (fixed ranges of cells)"""
