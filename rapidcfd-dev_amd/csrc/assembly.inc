@@ -14,6 +14,30 @@ enum { ROW_SUMDIAG = 0, ROW_NEGSUMDIAG = 1, ROW_SUMMAGOFFDIAG = 2 };
 enum { M_PLUS = 0, M_MINUS = 1, M_MAG = 2 };
 
 template <int MODE> __device__ __forceinline__ double face_term(double v) { return MODE == M_PLUS ? v : MODE == M_MINUS ? -v : fabs(v); }
+// A streaming pass states its formula ONCE: f(x, o) sees one element -- x[k] its value in input stream k, o[k] what goes to output stream k --
+// and runs for both lanes of a 16-byte pair and for the unpaired last element of an odd chunk.  Every load of an element precedes its
+// stores, so a stream updated in place stands in both lists.  UNROLL 4: chunk_loop, 2: chunk_loop2 (kernels.hip.hpp).
+template <int UNROLL, int NIN, int NOUT, class F>
+__device__ __forceinline__ void cell_map(int64_t n, const double* const (&in)[NIN], double* const (&out)[NOUT], F f)
+{
+    auto pair = [&](int64_t i) {
+        double x[NIN], y[NIN], ox[NOUT], oy[NOUT];
+#pragma unroll
+        for (int k = 0; k < NIN; ++k) { const double2 v = ld2(in[k], i); x[k] = v.x; y[k] = v.y; }
+        f(x, ox); f(y, oy);
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k) st2(out[k], i, make_double2(ox[k], oy[k]));
+    };
+    auto one = [&](int64_t i) {
+        double x[NIN], o[NOUT];
+#pragma unroll
+        for (int k = 0; k < NIN; ++k) x[k] = in[k][i];
+        f(x, o);
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k) out[k][i] = o[k];
+    };
+    if (UNROLL == 4) chunk_loop(n, pair, one); else chunk_loop2(n, pair, one);
+}
 
 // Row sum over faces: out[c] = (init ? init[c] : 0) + sum_{own faces} f(ownArr[j]) + sum_{neighbour faces} g(neiArr[losort])
 // [/ vol[c]].  A workgroup owns RS consecutive cells; their own faces are one contiguous range in the
@@ -641,9 +665,7 @@ __global__ void k_patch_internal_field(const int32_t* __restrict__ faceCells, co
 // inout -= x*y with the product rounded first (`source -= V*div(...)`: a temporary field, then operator-=)
 __global__ __launch_bounds__(RB) void k_submul(const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ io, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) { const double2 a = ld2(x, i), b = ld2(y, i); double2 c = ld2(io, i); const double t0 = a.x * b.x, t1 = a.y * b.y;
-                                   c.x -= t0; c.y -= t1; st2(io, i, c); },
-        [&](int64_t i) { const double t = x[i] * y[i]; io[i] -= t; });
+    cell_map<4>(n, {x, y, io}, {io}, [](const double (&v)[3], double (&o)[1]) { const double t = v[0] * v[1]; o[0] = v[2] - t; });
 }
 
 // patch contribution per unique patch cell, ascending patch-face order (fvMatrix.C:38-75,978-1085)
@@ -677,67 +699,65 @@ __global__ void k_patch_max(const int32_t* __restrict__ cells, const int32_t* __
 
 __global__ __launch_bounds__(RB) void k_relax_dominance(double* __restrict__ D, const double* __restrict__ sumOff, double alpha, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) {
-            const double2 d = ld2(D, i), s = ld2(sumOff, i);
-            st2(D, i, make_double2(fmax(fabs(d.x), s.x) / alpha, fmax(fabs(d.y), s.y) / alpha));
-        },
-        [&](int64_t i) { D[i] = fmax(fabs(D[i]), sumOff[i]) / alpha; });
+    cell_map<4>(n, {D, sumOff}, {D}, [&](const double (&v)[2], double (&o)[1]) { o[0] = fmax(fabs(v[0]), v[1]) / alpha; });
 }
 __global__ __launch_bounds__(RB) void k_relax_source(double* __restrict__ S, const double* __restrict__ D, const double* __restrict__ D0,
                                                      const double* __restrict__ psi, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) {
-            const double2 d = ld2(D, i), d0 = ld2(D0, i), p = ld2(psi, i), s = ld2(S, i);
-            st2(S, i, make_double2(s.x + (d.x - d0.x) * p.x, s.y + (d.y - d0.y) * p.y));   // S += (D - D0)*psi: three field operations (fvMatrix.C:1344), three roundings
-        },
-        [&](int64_t i) { S[i] = S[i] + (D[i] - D0[i]) * psi[i]; });
+    cell_map<4>(n, {D, D0, psi, S}, {S}, [](const double (&v)[4], double (&o)[1]) {
+        const auto& [d, d0, p, s] = v;
+        o[0] = s + (d - d0) * p;                             // S += (D - D0)*psi: three field operations (fvMatrix.C:1344), three roundings
+    });
 }
 
 // fvm::ddt, Euler (EulerDdtScheme.C fvmDdt): diag = rDeltaT*rho*V, source = rDeltaT*rho*psi0*V
 __global__ __launch_bounds__(RB) void k_ddt_euler(double rr, const double* __restrict__ vol, const double* __restrict__ psi0,
                                                   double* __restrict__ diag, double* __restrict__ source, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) { const double2 v = ld2(vol, i), p = ld2(psi0, i);
-          st2(diag, i, make_double2(rr * v.x, rr * v.y)); st2(source, i, make_double2((rr * p.x) * v.x, (rr * p.y) * v.y)); },
-        [&](int64_t i) { diag[i] = rr * vol[i]; source[i] = (rr * psi0[i]) * vol[i]; });
+    cell_map<4>(n, {vol, psi0}, {diag, source}, [&](const double (&x)[2], double (&o)[2]) {
+        const auto& [v, p] = x;
+        o[0] = rr * v; o[1] = (rr * p) * v;
+    });
 }
 // fvm::ddt(rho, vf) with a density FIELD (EulerDdtScheme.C:403-440): diag = rDeltaT*rho*V, source = rDeltaT*rho0*psi0*V
 __global__ __launch_bounds__(RB) void k_ddt_euler_rho(double r, const double* __restrict__ rho, const double* __restrict__ rho0, const double* __restrict__ vol,
                                                       const double* __restrict__ psi0, double* __restrict__ diag, double* __restrict__ source, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) { const double2 q = ld2(rho, i), q0 = ld2(rho0, i), v = ld2(vol, i), p = ld2(psi0, i);
-          st2(diag, i, make_double2((r * q.x) * v.x, (r * q.y) * v.y)); st2(source, i, make_double2(((r * q0.x) * p.x) * v.x, ((r * q0.y) * p.y) * v.y)); },
-        [&](int64_t i) { diag[i] = (r * rho[i]) * vol[i]; source[i] = ((r * rho0[i]) * psi0[i]) * vol[i]; });
+    cell_map<4>(n, {rho, rho0, vol, psi0}, {diag, source}, [&](const double (&x)[4], double (&o)[2]) {
+        const auto& [q, q0, v, p] = x;
+        o[0] = (r * q) * v; o[1] = ((r * q0) * p) * v;
+    });
 }
 // fvm::Su / fvm::Sp / fvm::SuSp (fvmSup.C:34-54, 100-170, 190-214); the product with V is rounded before it is added
 __global__ __launch_bounds__(RB) void k_fvm_su(const double* __restrict__ vol, const double* __restrict__ su, double* __restrict__ source, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) { const double2 v = ld2(vol, i), q = ld2(su, i), s = ld2(source, i); st2(source, i, make_double2(s.x - v.x * q.x, s.y - v.y * q.y)); },
-        [&](int64_t i) { source[i] = source[i] - vol[i] * su[i]; });
+    cell_map<4>(n, {vol, su, source}, {source}, [](const double (&x)[3], double (&o)[1]) { o[0] = x[2] - x[0] * x[1]; });
 }
 __global__ __launch_bounds__(RB) void k_fvm_sp(const double* __restrict__ vol, const double* __restrict__ sp, double spValue, double* __restrict__ diag, int64_t n)
 {
-    if (sp) chunk_loop(n, [&](int64_t i) { const double2 v = ld2(vol, i), q = ld2(sp, i), d = ld2(diag, i); st2(diag, i, make_double2(d.x + v.x * q.x, d.y + v.y * q.y)); },
-        [&](int64_t i) { diag[i] = diag[i] + vol[i] * sp[i]; });
-    else chunk_loop(n, [&](int64_t i) { const double2 v = ld2(vol, i), d = ld2(diag, i); st2(diag, i, make_double2(d.x + v.x * spValue, d.y + v.y * spValue)); },
-        [&](int64_t i) { diag[i] = diag[i] + vol[i] * spValue; });
+    if (sp) cell_map<4>(n, {vol, sp, diag}, {diag}, [](const double (&x)[3], double (&o)[1]) { o[0] = x[2] + x[0] * x[1]; });
+    else cell_map<4>(n, {vol, diag}, {diag}, [&](const double (&x)[2], double (&o)[1]) { o[0] = x[1] + x[0] * spValue; });
 }
 __global__ __launch_bounds__(RB) void k_fvm_susp(const double* __restrict__ vol, const double* __restrict__ susp, const double* __restrict__ vf,
                                                  double* __restrict__ diag, double* __restrict__ source, int64_t n)
 {
-    auto one = [](double v, double q, double f, double& d, double& s) {
+    cell_map<4>(n, {vol, susp, vf, diag, source}, {diag, source}, [](const double (&x)[5], double (&o)[2]) {
+        const auto& [v, q, f, d, s] = x;
         const double mx = q > 0 ? q : 0.0, mn = q < 0 ? q : 0.0;
-        d = d + v * mx; s = s - (v * mn) * f;
-    };
-    chunk_loop(n, [&](int64_t i) { const double2 v = ld2(vol, i), q = ld2(susp, i), f = ld2(vf, i); double2 d = ld2(diag, i), s = ld2(source, i);
-          one(v.x, q.x, f.x, d.x, s.x); one(v.y, q.y, f.y, d.y, s.y); st2(diag, i, d); st2(source, i, s); },
-        [&](int64_t i) { double d = diag[i], s = source[i]; one(vol[i], susp[i], vf[i], d, s); diag[i] = d; source[i] = s; });
+        o[0] = d + v * mx; o[1] = s - (v * mn) * f;
+    });
 }
 // phi = Sf & interpolate([sc *] V) [+ addA [* addB]] as a plain face pass (mi_flux_div's default form: this pass + the row sum of
 // fvc::surfaceIntegrate; measured faster than the one-row-pass form of round 5, whose cut faces each cost eight scattered gathers; that form was removed in round 6)
 __global__ void k_face_flux(const RowPassArgs a, double* __restrict__ out, int nf)
 {
     for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += gridDim.x * blockDim.x) out[f] = flux_face(a, f);
+}
+// fvcDdtPhiCoeff (ddtScheme.C:139-174): 1 - min(|phiCorr| / (|phi0| + SMALL), 1), min(q, 1) = (q < 1) ? q : 1
+__device__ __forceinline__ double ddt_phi_coeff(double phi0, double phiCorr)
+{
+    const double q = fabs(phiCorr) / (fabs(phi0) + 1e-15);
+    return 1.0 - (q < 1.0 ? q : 1.0);
 }
 // fvc::ddtCorr(rho, U, phi), Euler, internal faces (EulerDdtScheme.C:663-720 / :523-551; fvcDdtPhiCoeff: ddtScheme.C:139-174) in ONE
 // face pass (the reference: rhoU0, three interpolates, the dot product, phiCorr, the coefficient's five field operations, two products)
@@ -746,9 +766,7 @@ __global__ void k_ddt_phi_corr(const RowPassArgs a, double rDeltaT, const double
     for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += gridDim.x * blockDim.x) {
         const double p0 = phi0[f];
         const double phiCorr = p0 - flux_face(a, f);
-        const double q = fabs(phiCorr) / (fabs(p0) + 1e-15);
-        const double coeff = 1.0 - (q < 1.0 ? q : 1.0);
-        out[f] = (coeff * rDeltaT) * phiCorr;
+        out[f] = (ddt_phi_coeff(p0, phiCorr) * rDeltaT) * phiCorr;
     }
 }
 // fvm::ddt, backward (backwardDdtScheme.C:456-607, static mesh): the constant-density form (rho_value 1: fvm::ddt(vf)) and the density-field
@@ -759,21 +777,14 @@ __global__ __launch_bounds__(RB) void k_fvm_ddt_backward(double rdt, double cA, 
                                                          const double* __restrict__ psi0, const double* __restrict__ psi00, double* __restrict__ diag,
                                                          double* __restrict__ source, int64_t n)
 {
-    chunk_loop2(n, [&](int64_t i) {
-            const double2 v = ld2(vol, i), p0 = ld2(psi0, i), p00 = ld2(psi00, i);
-            if (RHO) {
-                const double2 q = ld2(rho, i), q0 = ld2(rho0, i), q00 = ld2(rho00, i);
-                st2(diag, i, make_double2(back_diag(cA, q.x, v.x), back_diag(cA, q.y, v.y)));
-                st2(source, i, make_double2(back_source_rho(rdt, c0, c00, v.x, q0.x, p0.x, q00.x, p00.x), back_source_rho(rdt, c0, c00, v.y, q0.y, p0.y, q00.y, p00.y)));
-            } else {
-                st2(diag, i, make_double2(back_diag(cA, rhoValue, v.x), back_diag(cA, rhoValue, v.y)));
-                st2(source, i, make_double2(back_source(rdt, rhoValue, c0, c00, v.x, p0.x, p00.x), back_source(rdt, rhoValue, c0, c00, v.y, p0.y, p00.y)));
-            }
-        },
-        [&](int64_t i) {
-            if (RHO) { diag[i] = back_diag(cA, rho[i], vol[i]); source[i] = back_source_rho(rdt, c0, c00, vol[i], rho0[i], psi0[i], rho00[i], psi00[i]); }
-            else { diag[i] = back_diag(cA, rhoValue, vol[i]); source[i] = back_source(rdt, rhoValue, c0, c00, vol[i], psi0[i], psi00[i]); }
-        });
+    if (RHO) cell_map<2>(n, {vol, psi0, psi00, rho, rho0, rho00}, {diag, source}, [&](const double (&x)[6], double (&o)[2]) {
+        const auto& [v, p0, p00, q, q0, q00] = x;
+        o[0] = back_diag(cA, q, v); o[1] = back_source_rho(rdt, c0, c00, v, q0, p0, q00, p00);
+    });
+    else cell_map<2>(n, {vol, psi0, psi00}, {diag, source}, [&](const double (&x)[3], double (&o)[2]) {
+        const auto& [v, p0, p00] = x;
+        o[0] = back_diag(cA, rhoValue, v); o[1] = back_source(rdt, rhoValue, c0, c00, v, p0, p00);
+    });
 }
 // fvc::ddt, backward (backwardDdtScheme.C:196-207, :268-280, :343-355): rr = rDeltaT*rho_value (a host product) without a density field
 __device__ __forceinline__ double back_fvc(double rr, double c, double c0, double c00, double f, double f0, double f00)
@@ -789,16 +800,11 @@ __global__ __launch_bounds__(RB) void k_fvc_ddt_backward(double rr, double c, do
                                                          const double* __restrict__ rho0, const double* __restrict__ rho00, const double* __restrict__ vf,
                                                          const double* __restrict__ vf0, const double* __restrict__ vf00, double* __restrict__ out, int64_t n)
 {
-    chunk_loop2(n, [&](int64_t i) {
-            const double2 f = ld2(vf, i), f0 = ld2(vf0, i), f00 = ld2(vf00, i);
-            if (RHO) {
-                const double2 q = ld2(rho, i), q0 = ld2(rho0, i), q00 = ld2(rho00, i);
-                st2(out, i, make_double2(back_fvc_rho(rr, c, c0, c00, q.x, f.x, q0.x, f0.x, q00.x, f00.x), back_fvc_rho(rr, c, c0, c00, q.y, f.y, q0.y, f0.y, q00.y, f00.y)));
-            } else st2(out, i, make_double2(back_fvc(rr, c, c0, c00, f.x, f0.x, f00.x), back_fvc(rr, c, c0, c00, f.y, f0.y, f00.y)));
-        },
-        [&](int64_t i) {
-            out[i] = RHO ? back_fvc_rho(rr, c, c0, c00, rho[i], vf[i], rho0[i], vf0[i], rho00[i], vf00[i]) : back_fvc(rr, c, c0, c00, vf[i], vf0[i], vf00[i]);
-        });
+    if (RHO) cell_map<2>(n, {vf, vf0, vf00, rho, rho0, rho00}, {out}, [&](const double (&x)[6], double (&o)[1]) {
+        const auto& [f, f0, f00, q, q0, q00] = x;
+        o[0] = back_fvc_rho(rr, c, c0, c00, q, f, q0, f0, q00, f00);
+    });
+    else cell_map<2>(n, {vf, vf0, vf00}, {out}, [&](const double (&x)[3], double (&o)[1]) { o[0] = back_fvc(rr, c, c0, c00, x[0], x[1], x[2]); });
 }
 // ---- CrankNicolson (CrankNicolsonDdtScheme.C, static mesh; DESIGN 3.5g) ----
 // the ddt0 update (:417-418, :507-508, :603-607; the same statements in fvmDdt :818-822, :900-904, :987-994): c0 = rDtCoef0*rho_value (a host
@@ -844,23 +850,14 @@ __global__ __launch_bounds__(RB) void k_fvm_ddt_cn(double rdt, double cr, double
                                                    const double* __restrict__ vol, const double* __restrict__ psi0, const double* __restrict__ ddt0,
                                                    double* __restrict__ diag, double* __restrict__ source, int64_t n)
 {
-    chunk_loop2(n, [&](int64_t i) {
-            const double2 v = ld2(vol, i), p0 = ld2(psi0, i), d = ld2(ddt0, i);
-            const double ox = cn_off(offc, oc, d.x), oy = cn_off(offc, oc, d.y);
-            if (RHO) {
-                const double2 q = ld2(rho, i), q0 = ld2(rho0, i);
-                st2(diag, i, make_double2((rdt * q.x) * v.x, (rdt * q.y) * v.y));
-                st2(source, i, make_double2(cn_source(rdt * q0.x, p0.x, ox, v.x), cn_source(rdt * q0.y, p0.y, oy, v.y)));
-            } else {
-                st2(diag, i, make_double2(cr * v.x, cr * v.y));
-                st2(source, i, make_double2(cn_source(cr, p0.x, ox, v.x), cn_source(cr, p0.y, oy, v.y)));
-            }
-        },
-        [&](int64_t i) {
-            const double o = cn_off(offc, oc, ddt0[i]);
-            if (RHO) { diag[i] = (rdt * rho[i]) * vol[i]; source[i] = cn_source(rdt * rho0[i], psi0[i], o, vol[i]); }
-            else { diag[i] = cr * vol[i]; source[i] = cn_source(cr, psi0[i], o, vol[i]); }
-        });
+    if (RHO) cell_map<2>(n, {vol, psi0, ddt0, rho, rho0}, {diag, source}, [&](const double (&x)[5], double (&o)[2]) {
+        const auto& [v, p0, d, q, q0] = x;
+        o[0] = (rdt * q) * v; o[1] = cn_source(rdt * q0, p0, cn_off(offc, oc, d), v);
+    });
+    else cell_map<2>(n, {vol, psi0, ddt0}, {diag, source}, [&](const double (&x)[3], double (&o)[2]) {
+        const auto& [v, p0, d] = x;
+        o[0] = cr * v; o[1] = cn_source(cr, p0, cn_off(offc, oc, d), v);
+    });
 }
 // fvc::ddt (:426, :516, :615-616)
 __device__ __forceinline__ double cn_fvc(double cr, double f, double f0, double offd) { return (cr * (f - f0)) - offd; }
@@ -870,18 +867,11 @@ __global__ __launch_bounds__(RB) void k_fvc_ddt_cn(double cr, double oc, int off
                                                    const double* __restrict__ vf, const double* __restrict__ vf0, const double* __restrict__ ddt0,
                                                    double* __restrict__ out, int64_t n)
 {
-    chunk_loop2(n, [&](int64_t i) {
-            const double2 f = ld2(vf, i), f0 = ld2(vf0, i), d = ld2(ddt0, i);
-            const double ox = cn_off(offc, oc, d.x), oy = cn_off(offc, oc, d.y);
-            if (RHO) {
-                const double2 q = ld2(rho, i), q0 = ld2(rho0, i);
-                st2(out, i, make_double2(cn_fvc_rho(cr, q.x, f.x, q0.x, f0.x, ox), cn_fvc_rho(cr, q.y, f.y, q0.y, f0.y, oy)));
-            } else st2(out, i, make_double2(cn_fvc(cr, f.x, f0.x, ox), cn_fvc(cr, f.y, f0.y, oy)));
-        },
-        [&](int64_t i) {
-            const double o = cn_off(offc, oc, ddt0[i]);
-            out[i] = RHO ? cn_fvc_rho(cr, rho[i], vf[i], rho0[i], vf0[i], o) : cn_fvc(cr, vf[i], vf0[i], o);
-        });
+    if (RHO) cell_map<2>(n, {vf, vf0, ddt0, rho, rho0}, {out}, [&](const double (&x)[5], double (&o)[1]) {
+        const auto& [f, f0, d, q, q0] = x;
+        o[0] = cn_fvc_rho(cr, q, f, q0, f0, cn_off(offc, oc, d));
+    });
+    else cell_map<2>(n, {vf, vf0, ddt0}, {out}, [&](const double (&x)[3], double (&o)[1]) { o[0] = cn_fvc(cr, x[0], x[1], cn_off(offc, oc, x[2])); });
 }
 // fvc::ddtCorr, backward, internal faces (backwardDdtScheme.C:724-765, :868-950 first branch; fvcDdtPhiCoeff: ddtScheme.C:139-174) in ONE face
 // pass: a face gathers U0, U00 [rho0, rho00] of its two cells once and forms both fluxes from them -- flux(U0) for the coefficient (the OLD
@@ -917,9 +907,7 @@ __global__ void k_ddt_phi_corr_backward(const DdtCorrBackArgs a)
         };
         const double fU = flux(p, n), fW = flux(wP, wN);
         const double p0 = a.phi0[f];
-        const double q = fabs(p0 - fU) / (fabs(p0) + 1e-15);
-        const double coeff = 1.0 - (q < 1.0 ? q : 1.0);
-        a.out[f] = (coeff * a.rdt) * (((a.c0 * p0) - (a.c00 * a.phi00[f])) - fW);
+        a.out[f] = (ddt_phi_coeff(p0, p0 - fU) * a.rdt) * (((a.c0 * p0) - (a.c00 * a.phi00[f])) - fW);
     }
 }
 // ---- the local-time-step schemes localEuler and CoEuler (localEulerDdtScheme.C, CoEulerDdtScheme.C, static mesh; DESIGN 3.5h) ----
@@ -930,31 +918,20 @@ __global__ __launch_bounds__(RB) void k_fvm_ddt_local(const double* __restrict__
                                                       const double* __restrict__ vol, const double* __restrict__ psi0, double* __restrict__ diag,
                                                       double* __restrict__ source, int64_t n)
 {
-    chunk_loop2(n, [&](int64_t i) {
-            const double2 r = ld2(rD, i), v = ld2(vol, i), p0 = ld2(psi0, i);
-            double2 q = make_double2(rhoValue, rhoValue), q0 = q;
-            if (RHO) { q = ld2(rho, i); q0 = ld2(rho0, i); }
-            st2(diag, i, make_double2((r.x * q.x) * v.x, (r.y * q.y) * v.y));
-            st2(source, i, make_double2(((r.x * q0.x) * p0.x) * v.x, ((r.y * q0.y) * p0.y) * v.y));
-        },
-        [&](int64_t i) {
-            const double q = RHO ? rho[i] : rhoValue, q0 = RHO ? rho0[i] : rhoValue;
-            diag[i] = (rD[i] * q) * vol[i]; source[i] = ((rD[i] * q0) * psi0[i]) * vol[i];
-        });
+    auto one = [](double r, double v, double p0, double q, double q0, double (&o)[2]) { o[0] = (r * q) * v; o[1] = ((r * q0) * p0) * v; };
+    if (RHO) cell_map<2>(n, {rD, vol, psi0, rho, rho0}, {diag, source}, [&](const double (&x)[5], double (&o)[2]) { one(x[0], x[1], x[2], x[3], x[4], o); });
+    else cell_map<2>(n, {rD, vol, psi0}, {diag, source}, [&](const double (&x)[3], double (&o)[2]) { one(x[0], x[1], x[2], rhoValue, rhoValue, o); });
 }
 // fvc::ddt (:149-157, :200-209, :255-264): (r*rhoValue)*(vf - vf0), or r*((rho*vf) - (rho0*vf0)) with a density field
 template <bool RHO>
 __global__ __launch_bounds__(RB) void k_fvc_ddt_local(const double* __restrict__ rD, double rhoValue, const double* __restrict__ rho, const double* __restrict__ rho0,
                                                       const double* __restrict__ vf, const double* __restrict__ vf0, double* __restrict__ out, int64_t n)
 {
-    auto one = [&](double r, double q, double f, double q0, double f0) { return RHO ? r * ((q * f) - (q0 * f0)) : (r * rhoValue) * (f - f0); };
-    chunk_loop2(n, [&](int64_t i) {
-            const double2 r = ld2(rD, i), f = ld2(vf, i), f0 = ld2(vf0, i);
-            double2 q = make_double2(0.0, 0.0), q0 = q;
-            if (RHO) { q = ld2(rho, i); q0 = ld2(rho0, i); }
-            st2(out, i, make_double2(one(r.x, q.x, f.x, q0.x, f0.x), one(r.y, q.y, f.y, q0.y, f0.y)));
-        },
-        [&](int64_t i) { out[i] = one(rD[i], RHO ? rho[i] : 0.0, vf[i], RHO ? rho0[i] : 0.0, vf0[i]); });
+    if (RHO) cell_map<2>(n, {rD, vf, vf0, rho, rho0}, {out}, [](const double (&x)[5], double (&o)[1]) {
+        const auto& [r, f, f0, q, q0] = x;
+        o[0] = r * ((q * f) - (q0 * f0));
+    });
+    else cell_map<2>(n, {rD, vf, vf0}, {out}, [&](const double (&x)[3], double (&o)[1]) { o[0] = (x[0] * rhoValue) * (x[1] - x[2]); });
 }
 // fvc::ddtCorr(U, phi) (:531-560): k_ddt_phi_corr with rDeltaT := fvc::interpolate(rDeltaT) on the face, one fma (surfaceInterpolationScheme.C:275-280)
 __global__ void k_ddt_phi_corr_local(const RowPassArgs a, const double* __restrict__ rD, const double* __restrict__ phi0, double* __restrict__ out, int nf)
@@ -962,11 +939,9 @@ __global__ void k_ddt_phi_corr_local(const RowPassArgs a, const double* __restri
     for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += gridDim.x * blockDim.x) {
         const double p0 = phi0[f];
         const double phiCorr = p0 - flux_face(a, f);
-        const double q = fabs(phiCorr) / (fabs(p0) + 1e-15);
-        const double coeff = 1.0 - (q < 1.0 ? q : 1.0);
         const double rn = rD[a.up[f]];
         const double rf = fma(a.a0[f], rD[a.lo[f]] - rn, rn);
-        out[f] = (coeff * rf) * phiCorr;
+        out[f] = (ddt_phi_coeff(p0, phiCorr) * rf) * phiCorr;
     }
 }
 // CoEulerDdtScheme::CofrDeltaT on one face (CoEulerDdtScheme.C:125-167), every field operator rounded on its own:
@@ -982,13 +957,8 @@ __device__ __forceinline__ double co_face_x(double dc, double phi, double magSf,
 __global__ __launch_bounds__(RB) void k_co_face_r_delta_t(const double* __restrict__ dc, const double* __restrict__ magSf, const double* __restrict__ phi,
                                                           const double* __restrict__ rhoF, double deltaT, double maxCo, double* __restrict__ out, int64_t n)
 {
-    const bool mass = rhoF != nullptr;
-    chunk_loop2(n, [&](int64_t i) {
-            const double2 d = ld2(dc, i), m = ld2(magSf, i), p = ld2(phi, i);
-            const double2 r = mass ? ld2(rhoF, i) : make_double2(0.0, 0.0);
-            st2(out, i, make_double2(co_face_x(d.x, p.x, m.x, mass, r.x, deltaT, maxCo), co_face_x(d.y, p.y, m.y, mass, r.y, deltaT, maxCo)));
-        },
-        [&](int64_t i) { out[i] = co_face_x(dc[i], phi[i], magSf[i], mass, mass ? rhoF[i] : 0.0, deltaT, maxCo); });
+    if (rhoF) cell_map<2>(n, {dc, magSf, phi, rhoF}, {out}, [&](const double (&x)[4], double (&o)[1]) { o[0] = co_face_x(x[0], x[2], x[1], true, x[3], deltaT, maxCo); });
+    else cell_map<2>(n, {dc, magSf, phi}, {out}, [&](const double (&x)[3], double (&o)[1]) { o[0] = co_face_x(x[0], x[2], x[1], false, 0.0, deltaT, maxCo); });
 }
 // CoEulerDdtScheme::CorDeltaT on the internal faces (:61-94: matrixOperation with maxOp from 0.0, own faces then neighbour-side faces) in ONE
 // row pass on k_row_pass's skeleton: a block forms x_f of its own faces once and stages them in LDS, cut neighbour-side faces are recomputed
@@ -1058,8 +1028,7 @@ __global__ __launch_bounds__(BS) void k_co_r_delta_t(const CoArgs a)
 }
 __global__ __launch_bounds__(RB) void k_upwind_weights(const double* __restrict__ flux, double* __restrict__ w, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) { const double2 f = ld2(flux, i); st2(w, i, make_double2(f.x >= 0 ? 1.0 : 0.0, f.y >= 0 ? 1.0 : 0.0)); },
-        [&](int64_t i) { w[i] = flux[i] >= 0 ? 1.0 : 0.0; });
+    cell_map<4>(n, {flux}, {w}, [](const double (&f)[1], double (&o)[1]) { o[0] = f[0] >= 0 ? 1.0 : 0.0; });
 }
 // limitedLinear(k): NVDTVD.H r(), limitedLinear.H:79-97, limitedSurfaceInterpolationScheme.C:177-187 in ONE face pass
 // (the reference: grad field, limiter transform with seven gathers, weights transform)
@@ -1128,9 +1097,7 @@ __global__ void k_patch_linear_upwind_corr(const int32_t* __restrict__ faceCells
 // LUST weights (LUST.H:104-110): 0.75*w_linear + 0.25*pos(faceFlux) -- three field operations, three roundings (no fma)
 __global__ __launch_bounds__(RB) void k_lust_weights(const double* __restrict__ cdw, const double* __restrict__ flux, double* __restrict__ w, int64_t n)
 {
-    chunk_loop(n, [&](int64_t i) { const double2 c = ld2(cdw, i), f = ld2(flux, i);
-                                   st2(w, i, make_double2(0.75 * c.x + 0.25 * (f.x >= 0 ? 1.0 : 0.0), 0.75 * c.y + 0.25 * (f.y >= 0 ? 1.0 : 0.0))); },
-        [&](int64_t i) { w[i] = 0.75 * cdw[i] + 0.25 * (flux[i] >= 0 ? 1.0 : 0.0); });
+    cell_map<4>(n, {cdw, flux}, {w}, [](const double (&x)[2], double (&o)[1]) { o[0] = 0.75 * x[0] + 0.25 * (x[1] >= 0 ? 1.0 : 0.0); });
 }
 // ---- the TVD/NVD limited schemes (limitedSchemes/*, DESIGN 3.5b) ------------------------------------------------------------------
 // LimitedSchemeCalcLimiterFunctor (LimitedScheme.C:41-55) for every limiter of the family over NVDTVD (a scalar) or NVDVTVDV (the "V"
@@ -1372,13 +1339,11 @@ __global__ __launch_bounds__(BS) void k_row_sum3(const RowSum3Args a)
 }
 __global__ __launch_bounds__(RB) void k_vdiv(const double* x, const double* y, double* out, int64_t n) // out may alias x
 {
-    chunk_loop(n, [&](int64_t i) { const double2 u = ld2(x, i), v = ld2(y, i); st2(out, i, make_double2(u.x / v.x, u.y / v.y)); },
-        [&](int64_t i) { out[i] = x[i] / y[i]; });
+    cell_map<4>(n, {x, y}, {out}, [](const double (&v)[2], double (&o)[1]) { o[0] = v[0] / v[1]; });
 }
 __global__ __launch_bounds__(RB) void k_axpby(double a, const double* x, double b, const double* y, double* out, int64_t n) // out may alias x or y
 {
-    chunk_loop(n, [&](int64_t i) { const double2 u = ld2(x, i), v = ld2(y, i); st2(out, i, make_double2(fma(a, u.x, b * v.x), fma(a, u.y, b * v.y))); },
-        [&](int64_t i) { out[i] = fma(a, x[i], b * y[i]); });
+    cell_map<4>(n, {x, y}, {out}, [&](const double (&v)[2], double (&o)[1]) { o[0] = fma(a, v[0], b * v[1]); });
 }
 
 } // namespace mi
@@ -1572,6 +1537,35 @@ extern "C" int mi_patch_flux(mi_patch_t p, const double* internal_coeffs_dev, co
 
 namespace {
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// a streaming pass on the fixed RG x RB grid, on the context's stream
+template <class K, class... A>
+int cell_launch(mi_ctx_s* c, K kernel, A... args)
+{
+    HIPCHK(hipSetDevice(c->device));
+    kernel<<<RG, RB, 0, c->stream>>>(args...);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+// the whitespace-separated words of a scheme string, as the reference's Istream reads them
+std::vector<std::string> scheme_words(const char* text)
+{
+    std::vector<std::string> tok;
+    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
+    for (const char* c = text; *c;) {
+        while (*c && sp(*c)) ++c;
+        const char* b = c;
+        while (*c && !sp(*c)) ++c;
+        if (c > b) tok.emplace_back(b, c);
+    }
+    return tok;
+}
+// is the whole word a number (strtod: "nan" and "inf" are numbers; who refuses them says so itself)
+bool scheme_number(const std::string& word, double& v)
+{
+    char* end = nullptr;
+    v = std::strtod(word.c_str(), &end);
+    return end != word.c_str() && *end == '\0';
+}
 // LDS per workgroup of a row pass: `arrays` staged face arrays of cap doubles.  Two workgroups per CU stay resident when the
 // largest block fits in 76 KiB; a block with more own faces than cap falls back to global reads inside the kernel.
 int row_cap(const mi_addr_s::RowPlan& rp, int arrays)
@@ -1750,10 +1744,7 @@ extern "C" int mi_lust_weights(mi_ctx_t c, int64_t n_faces, const double* cd_wei
     if (!c || n_faces < 0 || !cd_weights_dev || !face_flux_dev || !weights_out_dev) return fail(MI_ERR_ARG, "mi_lust_weights: bad argument");
     if (!al16(cd_weights_dev) || !al16(face_flux_dev) || !al16(weights_out_dev)) return fail(MI_ERR_ARG, "mi_lust_weights: arrays must be 16-byte aligned");
     if (n_faces == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    k_lust_weights<<<RG, RB, 0, c->stream>>>(cd_weights_dev, face_flux_dev, weights_out_dev, n_faces);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_lust_weights, cd_weights_dev, face_flux_dev, weights_out_dev, n_faces);
 }
 
 // [fvm::ddt] + [fvm::div] - [fvm::laplacian] [+- fvm::Sp] [+- explicit terms] in one row pass (k_row_assemble)
@@ -1987,14 +1978,7 @@ extern "C" int mi_sngrad_parse(const char* text, mi_sngrad_scheme* out)
 {
     const std::string who = "mi_sngrad_parse";
     if (!text || !out) return fail(MI_ERR_ARG, who + ": bad argument");
-    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
-    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
-    for (const char* c = text; *c;) {
-        while (*c && sp(*c)) ++c;
-        const char* b = c;
-        while (*c && !sp(*c)) ++c;
-        if (c > b) tok.emplace_back(b, c);
-    }
+    const std::vector<std::string> tok = scheme_words(text);
     if (tok.empty()) return fail(MI_ERR_ARG, who + ": empty scheme");
     const char* const plain[] = {"uncorrected", "orthogonal", "corrected"};     // MI_SNGRAD_UNCORRECTED, _ORTHOGONAL, _CORRECTED
     auto plain_kind = [&](const std::string& s) { for (int k = 0; k < 3; ++k) if (s == plain[k]) return k; return -1; };
@@ -2009,16 +1993,15 @@ extern "C" int mi_sngrad_parse(const char* text, mi_sngrad_scheme* out)
     if (tok[0] != "limited") return fail(MI_ERR_ARG, who + ": snGrad scheme '" + tok[0] + "' is not supported (uncorrected | orthogonal | corrected | limited [corrected] <k>)");
     if (tok.size() < 2) return fail(MI_ERR_ARG, who + ": 'limited' needs a coefficient ('limited <k>' | 'limited corrected <k>')");
     // limitedSnGrad.H:86-110: a number directly after `limited` is the coefficient over `corrected`; otherwise a scheme, then the coefficient
-    auto number = [](const std::string& t, double* v) { char* end = nullptr; *v = std::strtod(t.c_str(), &end); return end != t.c_str() && *end == '\0'; };
     std::size_t at = 1;
     double k = 0;
-    if (!number(tok[1], &k)) {
+    if (!scheme_number(tok[1], k)) {
         if (tok[1] == "limited") return fail(MI_ERR_ARG, who + ": a limited scheme over a limited scheme ('limited limited') is not supported");
         if (tok[1] == "uncorrected" || tok[1] == "orthogonal")
             return fail(MI_ERR_ARG, who + ": 'limited " + tok[1] + "' is not supported: the correction() of '" + tok[1] + "' is not implemented in the reference");
         if (tok[1] != "corrected") return fail(MI_ERR_ARG, who + ": corrected scheme '" + tok[1] + "' under 'limited' is not supported (only corrected)");
         if (tok.size() < 3) return fail(MI_ERR_ARG, who + ": 'limited corrected' needs the coefficient k");
-        if (!number(tok[2], &k)) return fail(MI_ERR_ARG, who + ": '" + tok[2] + "' is not a number");
+        if (!scheme_number(tok[2], k)) return fail(MI_ERR_ARG, who + ": '" + tok[2] + "' is not a number");
         at = 2;
     }
     if (tok.size() > at + 1) return fail(MI_ERR_ARG, who + ": extra '" + tok[at + 1] + "'");
@@ -2134,10 +2117,7 @@ extern "C" int mi_vec_submul(mi_ctx_t c, int64_t n, const double* x_dev, const d
     if (!c || n < 0 || (n > 0 && (!x_dev || !y_dev || !inout_dev))) return fail(MI_ERR_ARG, "mi_vec_submul: bad argument");
     if (!al16(x_dev) || !al16(y_dev) || !al16(inout_dev)) return fail(MI_ERR_ARG, "mi_vec_submul: arrays must be 16-byte aligned");
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    k_submul<<<RG, RB, 0, c->stream>>>(x_dev, y_dev, inout_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_submul, x_dev, y_dev, inout_dev, n);
 }
 
 // fvMatrix<Type>::relax(alpha) (fvMatrix.C:1087-1345): one diagonal, n_rhs sources / solution components (the vector equation's
@@ -2171,12 +2151,12 @@ extern "C" int mi_relax_multi(mi_addr_t a, double alpha, double* diag_dev, const
             MICHK(mi_patch_add(patches[p], boundary_coeffs_dev[p], sumOff, 2));
         } else MICHK(mi_patch_add(patches[p], internal_coeffs_dev[p], diag_dev, 2));
     }
-    k_relax_dominance<<<RG, RB, 0, s>>>(diag_dev, sumOff, alpha, n);
+    MICHK(cell_launch(c, k_relax_dominance, diag_dev, sumOff, alpha, n));
     for (int32_t p = 0; p < n_patches; ++p) {
         if (!patches[p] || patches[p]->nFaces == 0) continue;
         MICHK(mi_patch_add(patches[p], internal_coeffs_dev[p], diag_dev, 1));
     }
-    for (int32_t r = 0; r < n_rhs; ++r) k_relax_source<<<RG, RB, 0, s>>>(source_dev[r], diag_dev, a->relaxD0.p, psi_dev[r], n);
+    for (int32_t r = 0; r < n_rhs; ++r) MICHK(cell_launch(c, k_relax_source, source_dev[r], diag_dev, a->relaxD0.p, psi_dev[r], n));
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
@@ -2288,10 +2268,7 @@ extern "C" int mi_fvm_ddt_euler(mi_ctx_t c, int64_t n, double r_delta_t, double 
 {
     if (!c || n < 0 || !vol_dev || !psi_old_dev || !diag_out_dev || !source_out_dev) return fail(MI_ERR_ARG, "mi_fvm_ddt_euler: bad argument");
     if (!al16(vol_dev) || !al16(psi_old_dev) || !al16(diag_out_dev) || !al16(source_out_dev)) return fail(MI_ERR_ARG, "mi_fvm_ddt_euler: arrays must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    k_ddt_euler<<<RG, RB, 0, c->stream>>>(r_delta_t * rho, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_ddt_euler, r_delta_t * rho, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
 }
 extern "C" int mi_fvm_ddt_euler_rho(mi_ctx_t c, int64_t n, double r_delta_t, const double* rho_dev, const double* rho_old_dev, const double* vol_dev,
                                     const double* psi_old_dev, double* diag_out_dev, double* source_out_dev)
@@ -2299,38 +2276,26 @@ extern "C" int mi_fvm_ddt_euler_rho(mi_ctx_t c, int64_t n, double r_delta_t, con
     if (!c || n < 0 || !rho_dev || !rho_old_dev || !vol_dev || !psi_old_dev || !diag_out_dev || !source_out_dev) return fail(MI_ERR_ARG, "mi_fvm_ddt_euler_rho: bad argument");
     if (!al16(rho_dev) || !al16(rho_old_dev) || !al16(vol_dev) || !al16(psi_old_dev) || !al16(diag_out_dev) || !al16(source_out_dev))
         return fail(MI_ERR_ARG, "mi_fvm_ddt_euler_rho: arrays must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    k_ddt_euler_rho<<<RG, RB, 0, c->stream>>>(r_delta_t, rho_dev, rho_old_dev, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_ddt_euler_rho, r_delta_t, rho_dev, rho_old_dev, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
 }
 extern "C" int mi_fvm_su(mi_ctx_t c, int64_t n, const double* vol_dev, const double* su_dev, double* source_inout_dev)
 {
     if (!c || n < 0 || !vol_dev || !su_dev || !source_inout_dev) return fail(MI_ERR_ARG, "mi_fvm_su: bad argument");
     if (!al16(vol_dev) || !al16(su_dev) || !al16(source_inout_dev)) return fail(MI_ERR_ARG, "mi_fvm_su: arrays must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    k_fvm_su<<<RG, RB, 0, c->stream>>>(vol_dev, su_dev, source_inout_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_fvm_su, vol_dev, su_dev, source_inout_dev, n);
 }
 extern "C" int mi_fvm_sp(mi_ctx_t c, int64_t n, const double* vol_dev, const double* sp_dev_or_null, double sp_value, double* diag_inout_dev)
 {
     if (!c || n < 0 || !vol_dev || !diag_inout_dev) return fail(MI_ERR_ARG, "mi_fvm_sp: bad argument");
     if (!al16(vol_dev) || (sp_dev_or_null && !al16(sp_dev_or_null)) || !al16(diag_inout_dev)) return fail(MI_ERR_ARG, "mi_fvm_sp: arrays must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    k_fvm_sp<<<RG, RB, 0, c->stream>>>(vol_dev, sp_dev_or_null, sp_value, diag_inout_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_fvm_sp, vol_dev, sp_dev_or_null, sp_value, diag_inout_dev, n);
 }
 extern "C" int mi_fvm_susp(mi_ctx_t c, int64_t n, const double* vol_dev, const double* susp_dev, const double* vf_dev, double* diag_inout_dev,
                            double* source_inout_dev)
 {
     if (!c || n < 0 || !vol_dev || !susp_dev || !vf_dev || !diag_inout_dev || !source_inout_dev) return fail(MI_ERR_ARG, "mi_fvm_susp: bad argument");
     if (!al16(vol_dev) || !al16(susp_dev) || !al16(vf_dev) || !al16(diag_inout_dev) || !al16(source_inout_dev)) return fail(MI_ERR_ARG, "mi_fvm_susp: arrays must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    k_fvm_susp<<<RG, RB, 0, c->stream>>>(vol_dev, susp_dev, vf_dev, diag_inout_dev, source_inout_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_fvm_susp, vol_dev, susp_dev, vf_dev, diag_inout_dev, source_inout_dev, n);
 }
 namespace {
 int flux_args(mi_addr_t a, const char* who, const double* lambda_dev, const double* sfx_dev, const double* sfy_dev, const double* sfz_dev, const double* vx_dev,
@@ -2416,14 +2381,11 @@ extern "C" int mi_fvm_ddt_backward(mi_ctx_t c, int64_t n, double r_delta_t, cons
     double* out[2] = {diag_out_dev, source_out_dev};
     MICHK(stream_arrays(who, in, RHO ? 6 : 3, out, 2));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
     const double cA = coeffs[0] * r_delta_t;
-    if (RHO) k_fvm_ddt_backward<true><<<RG, RB, 0, c->stream>>>(r_delta_t, cA, coeffs[1], coeffs[2], rho_value, rho_dev, rho_old_dev, rho_old_old_dev, vol_dev,
+    if (RHO) return cell_launch(c, k_fvm_ddt_backward<true>, r_delta_t, cA, coeffs[1], coeffs[2], rho_value, rho_dev, rho_old_dev, rho_old_old_dev, vol_dev,
                                                                  psi_old_dev, psi_old_old_dev, diag_out_dev, source_out_dev, n);
-    else k_fvm_ddt_backward<false><<<RG, RB, 0, c->stream>>>(r_delta_t, cA, coeffs[1], coeffs[2], rho_value, nullptr, nullptr, nullptr, vol_dev, psi_old_dev,
+    return cell_launch(c, k_fvm_ddt_backward<false>, r_delta_t, cA, coeffs[1], coeffs[2], rho_value, nullptr, nullptr, nullptr, vol_dev, psi_old_dev,
                                                              psi_old_old_dev, diag_out_dev, source_out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
 }
 extern "C" int mi_fvc_ddt_backward(mi_ctx_t c, int64_t n, double r_delta_t, const double coeffs[3], double rho_value, const double* rho_dev,
                                    const double* rho_old_dev, const double* rho_old_old_dev, const double* vf_dev, const double* vf_old_dev,
@@ -2437,13 +2399,10 @@ extern "C" int mi_fvc_ddt_backward(mi_ctx_t c, int64_t n, double r_delta_t, cons
     double* out[1] = {out_dev};
     MICHK(stream_arrays(who, in, RHO ? 6 : 3, out, 1));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    if (RHO) k_fvc_ddt_backward<true><<<RG, RB, 0, c->stream>>>(r_delta_t, coeffs[0], coeffs[1], coeffs[2], rho_dev, rho_old_dev, rho_old_old_dev, vf_dev,
+    if (RHO) return cell_launch(c, k_fvc_ddt_backward<true>, r_delta_t, coeffs[0], coeffs[1], coeffs[2], rho_dev, rho_old_dev, rho_old_old_dev, vf_dev,
                                                                  vf_old_dev, vf_old_old_dev, out_dev, n);
-    else k_fvc_ddt_backward<false><<<RG, RB, 0, c->stream>>>(r_delta_t * rho_value, coeffs[0], coeffs[1], coeffs[2], nullptr, nullptr, nullptr, vf_dev, vf_old_dev,
+    return cell_launch(c, k_fvc_ddt_backward<false>, r_delta_t * rho_value, coeffs[0], coeffs[1], coeffs[2], nullptr, nullptr, nullptr, vf_dev, vf_old_dev,
                                                              vf_old_old_dev, out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
 }
 extern "C" int mi_ddt_phi_corr_backward(mi_addr_t a, double r_delta_t, const double coeffs[3], const double* lambda_dev, const double* sfx_dev,
                                         const double* sfy_dev, const double* sfz_dev, const double* ux_old_dev, const double* uy_old_dev,
@@ -2474,21 +2433,13 @@ extern "C" int mi_ddt_cn_parse(const char* scheme, double* oc_out)
 {
     const char* who = "mi_ddt_cn_parse";
     if (!scheme || !oc_out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
-    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
-    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
-    for (const char* c = scheme; *c;) {
-        while (*c && sp(*c)) ++c;
-        const char* b = c;
-        while (*c && !sp(*c)) ++c;
-        if (c > b) tok.emplace_back(b, c);
-    }
+    const std::vector<std::string> tok = scheme_words(scheme);
     if (tok.empty()) return fail(MI_ERR_ARG, std::string(who) + ": empty scheme");
     if (tok[0] != "CrankNicolson") return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[0] + "' is not CrankNicolson");
     if (tok.size() < 2) return fail(MI_ERR_ARG, std::string(who) + ": 'CrankNicolson' takes the off-centring coefficient, none given");
     if (tok.size() > 2) return fail(MI_ERR_ARG, std::string(who) + ": 'CrankNicolson' takes one coefficient: extra '" + tok[2] + "'");
-    char* end = nullptr;
-    const double oc = std::strtod(tok[1].c_str(), &end);
-    if (end == tok[1].c_str() || *end != '\0' || oc != oc) return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[1] + "' is not a number");
+    double oc = 0;
+    if (!scheme_number(tok[1], oc) || oc != oc) return fail(MI_ERR_ARG, std::string(who) + ": '" + tok[1] + "' is not a number");
     if (!(oc >= 0.0 && oc <= 1.0))                                // CrankNicolsonDdtScheme.H:165-180
         return fail(MI_ERR_ARG, std::string(who) + ": coefficient = " + tok[1] + " should be >= 0 and <= 1");
     *oc_out = oc;
@@ -2530,15 +2481,12 @@ extern "C" int mi_ddt_cn_update(mi_ctx_t c, int64_t n, int32_t n_fields, double 
     if (RHO) { in[nIn++] = rho_old_dev; in[nIn++] = rho_old_old_dev; }
     MICHK(stream_arrays(who, in, nIn, out, n_fields));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
     CnUpdateArgs a{};
     for (int k = 0; k < n_fields; ++k) { a.ddt0[k] = ddt0_inout_dev[k]; a.psi0[k] = psi_old_dev[k]; a.psi00[k] = psi_old_old_dev[k]; }
     a.rho0 = rho_old_dev; a.rho00 = rho_old_old_dev;
     a.c0 = RHO ? r_dt_coef0 : r_dt_coef0 * rho_value; a.oc = oc; a.offc = oc < 1.0 ? 1 : 0; a.nFields = n_fields; a.n = n;
-    if (RHO) k_ddt_cn_update<true><<<RG, RB, 0, c->stream>>>(a);
-    else k_ddt_cn_update<false><<<RG, RB, 0, c->stream>>>(a);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    if (RHO) return cell_launch(c, k_ddt_cn_update<true>, a);
+    return cell_launch(c, k_ddt_cn_update<false>, a);
 }
 extern "C" int mi_fvm_ddt_cn(mi_ctx_t c, int64_t n, double r_dt_coef, double oc, double rho_value, const double* rho_dev, const double* rho_old_dev,
                              const double* vol_dev, const double* psi_old_dev, const double* ddt0_dev, double* diag_out_dev, double* source_out_dev)
@@ -2552,12 +2500,9 @@ extern "C" int mi_fvm_ddt_cn(mi_ctx_t c, int64_t n, double r_dt_coef, double oc,
     double* out[2] = {diag_out_dev, source_out_dev};
     MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 2));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
     const int offc = oc < 1.0 ? 1 : 0;
-    if (RHO) k_fvm_ddt_cn<true><<<RG, RB, 0, c->stream>>>(r_dt_coef, 0.0, oc, offc, rho_dev, rho_old_dev, vol_dev, psi_old_dev, ddt0_dev, diag_out_dev, source_out_dev, n);
-    else k_fvm_ddt_cn<false><<<RG, RB, 0, c->stream>>>(r_dt_coef, r_dt_coef * rho_value, oc, offc, nullptr, nullptr, vol_dev, psi_old_dev, ddt0_dev, diag_out_dev, source_out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    if (RHO) return cell_launch(c, k_fvm_ddt_cn<true>, r_dt_coef, 0.0, oc, offc, rho_dev, rho_old_dev, vol_dev, psi_old_dev, ddt0_dev, diag_out_dev, source_out_dev, n);
+    return cell_launch(c, k_fvm_ddt_cn<false>, r_dt_coef, r_dt_coef * rho_value, oc, offc, nullptr, nullptr, vol_dev, psi_old_dev, ddt0_dev, diag_out_dev, source_out_dev, n);
 }
 extern "C" int mi_fvc_ddt_cn(mi_ctx_t c, int64_t n, double r_dt_coef, double oc, double rho_value, const double* rho_dev, const double* rho_old_dev,
                              const double* vf_dev, const double* vf_old_dev, const double* ddt0_dev, double* out_dev)
@@ -2571,26 +2516,16 @@ extern "C" int mi_fvc_ddt_cn(mi_ctx_t c, int64_t n, double r_dt_coef, double oc,
     double* out[1] = {out_dev};
     MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 1));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
     const int offc = oc < 1.0 ? 1 : 0;
-    if (RHO) k_fvc_ddt_cn<true><<<RG, RB, 0, c->stream>>>(r_dt_coef, oc, offc, rho_dev, rho_old_dev, vf_dev, vf_old_dev, ddt0_dev, out_dev, n);
-    else k_fvc_ddt_cn<false><<<RG, RB, 0, c->stream>>>(r_dt_coef * rho_value, oc, offc, nullptr, nullptr, vf_dev, vf_old_dev, ddt0_dev, out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    if (RHO) return cell_launch(c, k_fvc_ddt_cn<true>, r_dt_coef, oc, offc, rho_dev, rho_old_dev, vf_dev, vf_old_dev, ddt0_dev, out_dev, n);
+    return cell_launch(c, k_fvc_ddt_cn<false>, r_dt_coef * rho_value, oc, offc, nullptr, nullptr, vf_dev, vf_old_dev, ddt0_dev, out_dev, n);
 }
 // ---- steadyState, localEuler and CoEuler (steadyStateDdtScheme.C, localEulerDdtScheme.C, CoEulerDdtScheme.C, static mesh; DESIGN 3.5h) ----
 extern "C" int mi_ddt_local_parse(const char* scheme, mi_ddt_local_scheme* out)
 {
     const char* who = "mi_ddt_local_parse";
     if (!scheme || !out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument (NULL)");
-    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
-    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
-    for (const char* c = scheme; *c;) {
-        while (*c && sp(*c)) ++c;
-        const char* b = c;
-        while (*c && !sp(*c)) ++c;
-        if (c > b) tok.emplace_back(b, c);
-    }
+    const std::vector<std::string> tok = scheme_words(scheme);
     if (tok.empty()) return fail(MI_ERR_ARG, std::string(who) + ": empty scheme");
     const std::string& name = tok[0];
     if (name == "Euler" || name == "backward" || name == "CrankNicolson") return fail(MI_ERR_ARG, std::string(who) + ": '" + name + "' is not a local scheme");
@@ -2610,9 +2545,8 @@ extern "C" int mi_ddt_local_parse(const char* scheme, mi_ddt_local_scheme* out)
     else {
         s.kind = MI_DDT_CO_EULER;
         std::memcpy(s.name, tok[1].c_str(), tok[1].size()); std::memcpy(s.rho_name, tok[2].c_str(), tok[2].size());
-        char* end = nullptr;
-        const double m = std::strtod(tok[3].c_str(), &end);
-        if (end == tok[3].c_str() || *end != '\0' || m != m) return fail(MI_ERR_ARG, std::string(who) + ": maxCo '" + tok[3] + "' is not a number");
+        double m = 0;
+        if (!scheme_number(tok[3], m) || m != m) return fail(MI_ERR_ARG, std::string(who) + ": maxCo '" + tok[3] + "' is not a number");
         if (!(m > 0.0) || m - m != 0.0) return fail(MI_ERR_ARG, std::string(who) + ": maxCo = " + tok[3] + " should be finite and > 0");
         s.max_co = m;
     }
@@ -2630,11 +2564,8 @@ extern "C" int mi_fvm_ddt_local(mi_ctx_t c, int64_t n, const double* r_delta_t_d
     double* out[2] = {diag_out_dev, source_out_dev};
     MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 2));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    if (RHO) k_fvm_ddt_local<true><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, rho_dev, rho_old_dev, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
-    else k_fvm_ddt_local<false><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, nullptr, nullptr, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    if (RHO) return cell_launch(c, k_fvm_ddt_local<true>, r_delta_t_dev, rho_value, rho_dev, rho_old_dev, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
+    return cell_launch(c, k_fvm_ddt_local<false>, r_delta_t_dev, rho_value, nullptr, nullptr, vol_dev, psi_old_dev, diag_out_dev, source_out_dev, n);
 }
 extern "C" int mi_fvc_ddt_local(mi_ctx_t c, int64_t n, const double* r_delta_t_dev, double rho_value, const double* rho_dev, const double* rho_old_dev,
                                 const double* vf_dev, const double* vf_old_dev, double* out_dev)
@@ -2647,11 +2578,8 @@ extern "C" int mi_fvc_ddt_local(mi_ctx_t c, int64_t n, const double* r_delta_t_d
     double* out[1] = {out_dev};
     MICHK(stream_arrays(who, in, RHO ? 5 : 3, out, 1));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    if (RHO) k_fvc_ddt_local<true><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, rho_dev, rho_old_dev, vf_dev, vf_old_dev, out_dev, n);
-    else k_fvc_ddt_local<false><<<RG, RB, 0, c->stream>>>(r_delta_t_dev, rho_value, nullptr, nullptr, vf_dev, vf_old_dev, out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    if (RHO) return cell_launch(c, k_fvc_ddt_local<true>, r_delta_t_dev, rho_value, rho_dev, rho_old_dev, vf_dev, vf_old_dev, out_dev, n);
+    return cell_launch(c, k_fvc_ddt_local<false>, r_delta_t_dev, rho_value, nullptr, nullptr, vf_dev, vf_old_dev, out_dev, n);
 }
 extern "C" int mi_ddt_phi_corr_local(mi_addr_t a, const double* r_delta_t_dev, const double* lambda_dev, const double* sfx_dev, const double* sfy_dev,
                                      const double* sfz_dev, const double* ux_old_dev, const double* uy_old_dev, const double* uz_old_dev,
@@ -2686,10 +2614,7 @@ extern "C" int mi_co_face_r_delta_t(mi_ctx_t c, int64_t n, const double* delta_c
     double* out[1] = {out_dev};
     MICHK(stream_arrays(who, in, rho_face_dev_or_null ? 4 : 3, out, 1));
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    k_co_face_r_delta_t<<<RG, RB, 0, c->stream>>>(delta_coeffs_dev, mag_sf_dev, phi_dev, rho_face_dev_or_null, delta_t, max_co, out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_co_face_r_delta_t, delta_coeffs_dev, mag_sf_dev, phi_dev, rho_face_dev_or_null, delta_t, max_co, out_dev, n);
 }
 extern "C" int mi_co_r_delta_t(mi_addr_t a, const double* delta_coeffs_dev, const double* mag_sf_dev, const double* phi_dev, const double* lambda_dev_or_null,
                                const double* rho_old_dev_or_null, double delta_t, double max_co, double* r_delta_t_out_dev)
@@ -2721,10 +2646,7 @@ extern "C" int mi_upwind_weights(mi_ctx_t c, int64_t n_faces, const double* face
     if (!c || n_faces < 0 || (n_faces > 0 && (!face_flux_dev || !weights_out_dev))) return fail(MI_ERR_ARG, "mi_upwind_weights: bad argument");
     if (!al16(face_flux_dev) || !al16(weights_out_dev)) return fail(MI_ERR_ARG, "mi_upwind_weights: arrays must be 16-byte aligned");
     if (n_faces == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    k_upwind_weights<<<RG, RB, 0, c->stream>>>(face_flux_dev, weights_out_dev, n_faces);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_upwind_weights, face_flux_dev, weights_out_dev, n_faces);
 }
 extern "C" int mi_limited_linear_weights(mi_addr_t a, double k, const double* cd_weights_dev, const double* face_flux_dev,
                                          const double* phi_dev, const double* gradx_dev, const double* grady_dev, const double* gradz_dev,
@@ -2812,14 +2734,7 @@ int lim_outputs(const char* who, const double* const* in, int m, double* w, doub
 extern "C" int mi_limiter_parse(const char* scheme, mi_limiter* out)
 {
     if (!scheme || !out) return fail(MI_ERR_ARG, "mi_limiter_parse: bad argument");
-    std::vector<std::string> tok;                                // whitespace-separated words, as the reference's Istream reads them
-    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
-    for (const char* c = scheme; *c;) {
-        while (*c && sp(*c)) ++c;
-        const char* b = c;
-        while (*c && !sp(*c)) ++c;
-        if (c > b) tok.emplace_back(b, c);
-    }
+    const std::vector<std::string> tok = scheme_words(scheme);
     if (tok.empty()) return fail(MI_ERR_ARG, "mi_limiter_parse: empty scheme");
     const std::string& name = tok[0];
     const LimName* e = nullptr;
@@ -2829,11 +2744,8 @@ extern "C" int mi_limiter_parse(const char* scheme, mi_limiter* out)
     const int got = (int)tok.size() - 1;
     if (got > want) return fail(MI_ERR_ARG, "mi_limiter_parse: '" + name + "' takes " + std::to_string(want) + " coefficient(s): extra '" + tok[want + 1] + "'");
     double v[3] = {0, 0, 0};
-    for (int j = 0; j < got; ++j) {
-        char* end = nullptr;
-        v[j] = std::strtod(tok[j + 1].c_str(), &end);
-        if (end == tok[j + 1].c_str() || *end != '\0') return fail(MI_ERR_ARG, "mi_limiter_parse: '" + tok[j + 1] + "' is not a number");
-    }
+    for (int j = 0; j < got; ++j)
+        if (!scheme_number(tok[j + 1], v[j])) return fail(MI_ERR_ARG, "mi_limiter_parse: '" + tok[j + 1] + "' is not a number");
     if (got < want) return fail(MI_ERR_ARG, "mi_limiter_parse: '" + name + "' takes " + std::to_string(want) + " coefficient(s), " + std::to_string(got) + " given");
     mi_limiter l{};
     l.kind = e->kind; l.vector_form = e->vec; l.bounded = e->bounded ? 1 : 0;
@@ -3049,17 +2961,11 @@ extern "C" int mi_vec_axpby(mi_ctx_t c, int64_t n, double a, const double* x_dev
     if (!c || n < 0 || (n > 0 && (!x_dev || !y_dev || !out_dev))) return fail(MI_ERR_ARG, "mi_vec_axpby: bad argument");
     if (!al16(x_dev) || !al16(y_dev) || !al16(out_dev)) return fail(MI_ERR_ARG, "mi_vec_axpby: arrays must be 16-byte aligned");
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(c->device));
-    k_axpby<<<RG, RB, 0, c->stream>>>(a, x_dev, b, y_dev, out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_axpby, a, x_dev, b, y_dev, out_dev, n);
 }
 extern "C" int mi_vec_div(mi_ctx_t c, int64_t n, const double* x_dev, const double* y_dev, double* out_dev)
 {
     if (!c || n < 0 || !x_dev || !y_dev || !out_dev) return fail(MI_ERR_ARG, "mi_vec_div: bad argument");
     if (!al16(x_dev) || !al16(y_dev) || !al16(out_dev)) return fail(MI_ERR_ARG, "mi_vec_div: arrays must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    k_vdiv<<<RG, RB, 0, c->stream>>>(x_dev, y_dev, out_dev, n);
-    HIPCHK(hipGetLastError());
-    return MI_OK;
+    return cell_launch(c, k_vdiv, x_dev, y_dev, out_dev, n);
 }

@@ -240,7 +240,7 @@ extern "C" int mi_grad_scheme_parse(const char* scheme, mi_grad_scheme* out)
 {
     const char* who = "mi_grad_scheme_parse";
     if (!scheme || !out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
-    const std::vector<std::string> tok = grad_tokens(scheme);
+    const std::vector<std::string> tok = scheme_words(scheme);
     if (tok.empty()) return fail(MI_ERR_ARG, std::string(who) + ": empty scheme");
     mi_grad_scheme g{};
     const int kind = grad_lim_kind(tok[0]);

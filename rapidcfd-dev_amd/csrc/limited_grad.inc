@@ -208,26 +208,12 @@ int grad_lim_check(const char* who, const mi_grad_limiter* l)
     if (l->identity != (l->k < 1.0e-15 ? 1 : 0)) return fail(MI_ERR_ARG, std::string(who) + ": identity must be k < SMALL");
     return MI_OK;
 }
-// whitespace-separated words, as the reference's Istream reads them
-std::vector<std::string> grad_tokens(const char* scheme)
-{
-    std::vector<std::string> tok;
-    auto sp = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; };
-    for (const char* c = scheme; *c;) {
-        while (*c && sp(*c)) ++c;
-        const char* b = c;
-        while (*c && !sp(*c)) ++c;
-        if (c > b) tok.emplace_back(b, c);
-    }
-    return tok;
-}
 int grad_lim_kind(const std::string& s) { for (int k = 0; k < 4; ++k) if (s == kGradLimNames[k]) return k; return -1; }
 // the coefficient token of a limited scheme (readScalar, then the constructors' range check)
 int grad_lim_fill(const char* who, int kind, const std::string& ktok, mi_grad_limiter* out)
 {
-    char* end = nullptr;
-    const double k = std::strtod(ktok.c_str(), &end);
-    if (end == ktok.c_str() || *end != '\0') return fail(MI_ERR_ARG, std::string(who) + ": '" + ktok + "' is not a number");
+    double k = 0;
+    if (!scheme_number(ktok, k)) return fail(MI_ERR_ARG, std::string(who) + ": '" + ktok + "' is not a number");
     mi_grad_limiter l{};
     l.kind = kind; l.k = k; l.identity = k < 1.0e-15 ? 1 : 0;
     MICHK(grad_lim_check(who, &l));
@@ -240,7 +226,7 @@ extern "C" int mi_grad_limiter_parse(const char* scheme, mi_grad_limiter* out)
 {
     const char* who = "mi_grad_limiter_parse";
     if (!scheme || !out) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
-    const std::vector<std::string> tok = grad_tokens(scheme);
+    const std::vector<std::string> tok = scheme_words(scheme);
     if (tok.empty()) return fail(MI_ERR_ARG, std::string(who) + ": empty scheme");
     auto kind_of = grad_lim_kind;
     const int kind = kind_of(tok[0]);

@@ -346,6 +346,26 @@ def signed_flux(u, neg_zero=True):
     return f
 
 
+# ---- restatements shared by a scheme's own test and tests/test_streaming_passes.py -------------------------------------------------
+# the sizes of the streaming (double2) kernels: 1 and 3 an unpaired element, 1027 many one-pair blocks and a tail, 1 050 625 the first
+# size at which a thread walks more than one pair (chunk 1028 > 2*256) with an odd last chunk, 5 243 907 five to six pairs per thread
+# (the unroll-by-4 body and its remainder)
+STREAM_SIZES = (1, 2, 3, 1027, 1050625, 5243907)
+
+
+def lust_weights(cdw, flux):
+    """0.75*w_linear + 0.25*pos(faceFlux): three field operations (numpy evaluates them one by one, no contraction)"""
+    return 0.75 * cdw + 0.25 * (flux >= 0).astype(np.float64)
+
+
+def co_face(dc, phi, mag_sf, dt, max_co, rho_f=None):
+    """CofrDeltaT (CoEulerDdtScheme.C:125-167): max(a, b) = (a > b) ? a : b"""
+    den = mag_sf if rho_f is None else rho_f * mag_sf
+    co = (dc * (np.abs(phi) / den)) * dt
+    q = co / max_co
+    return np.where(q > 1.0, q, 1.0) / dt
+
+
 # ---- the fused-assembly check -------------------------------------------------------------------------------------------------------
 # n_rhs, density, convection weights (None: upwind; "w": given; False: no convection), Sp and the two explicit terms, the correction
 VARIANTS = [

@@ -112,7 +112,7 @@ def test_restated_fvm_ddt_is_second_order_and_euler_first():
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [1, 2, 3, 1027, 31 * 23 * 19])
+@pytest.mark.parametrize("n", [1, 2, 3, 1027, 31 * 23 * 19, 1050625, 5243907])
 def test_streaming_kernels_against_the_restatement(pkg, n):
     """mi_fvm_ddt_backward / mi_fvc_ddt_backward: the three density forms x the three coefficient sets; sizes with an odd tail and an unpaired
     element of the double2 loop"""

@@ -159,7 +159,7 @@ OCS = [1.0, 0.9, 0.0]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [1, 2, 3, 1027, 31 * 23 * 19])
+@pytest.mark.parametrize("n", [1, 2, 3, 1027, 31 * 23 * 19, 1050625, 5243907])
 def test_streaming_kernels_against_the_restatement(pkg, n):
     """mi_ddt_cn_update (one and three fields, in place) / mi_fvm_ddt_cn / mi_fvc_ddt_cn: the three density forms x three off-centring
     coefficients; sizes with an odd tail and an unpaired element of the double2 loop"""

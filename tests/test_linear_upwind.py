@@ -5,8 +5,8 @@ unfused sequence, bit for bit (gpu)."""
 import numpy as np
 import pytest
 
-from assembly_support import (ROW_MODES, bits, box_centres, dot_contracted, gpu_env, same, set_row_blocks, set_row_tables, shape_case, shaped_addressing,
-                              signed_flux)
+from assembly_support import (ROW_MODES, bits, box_centres, dot_contracted, gpu_env, lust_weights, same, set_row_blocks, set_row_tables, shape_case,
+                              shaped_addressing, signed_flux)
 
 
 def restate_internal(lo, up, flux, cf, C, grads, scale):
@@ -37,11 +37,6 @@ def restate_patch(fc, pflux, pcf, C, pd, grads, nbr, scale):
             e = (dx, dy, dz) if fl > 0 else (dx - pd[0][i], dy - pd[1][i], dz - pd[2][i])
             out[r][i] = fl * (scale * dot_contracted(*e, *g))
     return out
-
-
-def lust_weights(cdw, flux):
-    """0.75*w_linear + 0.25*pos(faceFlux): three field operations (numpy evaluates them one by one, no contraction)"""
-    return 0.75 * cdw + 0.25 * (flux >= 0).astype(np.float64)
 
 
 # ---- CPU -----------------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from assembly_support import (OTHER_TABLES, ROW_MODES, SHAPES, VARIANTS, FusedCase, gpu_env, set_row_blocks, set_row_tables, shape_case,
+from assembly_support import (OTHER_TABLES, ROW_MODES, SHAPES, VARIANTS, FusedCase, co_face, gpu_env, set_row_blocks, set_row_tables, shape_case,
                               shaped_addressing, signed_flux)
 
 NEW_ENTRIES = ("mi_ddt_local_parse", "mi_fvm_ddt_local", "mi_fvc_ddt_local", "mi_ddt_phi_corr_local", "mi_co_face_r_delta_t", "mi_co_r_delta_t",
@@ -47,14 +47,6 @@ def ddt_corr(orc, n, lo, up, r, lam, Sf, U0, phi0):
     k = 1 - np.minimum(np.abs(phi_corr) / (np.abs(phi0) + 1e-15), 1.0)
     rf = orc.face_interpolate(lo, up, lam, r)
     return (k * rf) * phi_corr, k
-
-
-def co_face(dc, phi, mag_sf, dt, max_co, rho_f=None):
-    """CofrDeltaT (CoEulerDdtScheme.C:125-167): max(a, b) = (a > b) ? a : b"""
-    den = mag_sf if rho_f is None else rho_f * mag_sf
-    co = (dc * (np.abs(phi) / den)) * dt
-    q = co / max_co
-    return np.where(q > 1.0, q, 1.0) / dt
 
 
 def co_cells(n, lo, up, x, patches=()):
