@@ -518,6 +518,44 @@ int mi_patch_limited_weights(mi_patch_t patch, const mi_limiter *lim, const doub
                              const double *const *phi_dev, const double *const *nbr_phi_dev, const double *const *grad_dev,
                              const double *const *nbr_grad_dev, const double *const *patch_delta_dev,
                              double *weights_out_dev, double *limiter_out_dev_or_null);
+/* ---- the filtered centred limiters of resolved (LES / DNS) runs: filteredLinear, filteredLinear2[V] k l, filteredLinear3[V] k ----
+ * LimitedScheme limiters that remove staggering from a centred scheme (limitedSchemes/filteredLinear/filteredLinear.H:69-94 and .C:33-37,
+ * filteredLinear2/filteredLinear2.H:80-141, filteredLinear2V.H:80-152 and filteredLinear2.C:34-44, filteredLinear3/filteredLinear3.H:72-107,
+ * filteredLinear3V.H:72-112 and filteredLinear3.C:34-44).  Every one reads the gradient at BOTH cells of a face and none reads the flux: only
+ * the weight blend does.  With d = C[N] - C[P] (the patch delta on a coupled patch), dc = d & gradc the dot product of every face pass here
+ * (fma(dz, gz, fma(dx, gx, dy*gy)); V forms: dfV = phiN - phiP, df = dfV & dfV and dc = dfV & (d & gradc), component j of the inner
+ * product d & grad(phi_j)), max / min the reference's ternaries ((a > b) ? a : b: max(-0.0, 0) = +0.0), SMALL = 1e-15, VSMALL = 1e-300,
+ * and 2*x, 0.5*x exact, the limiters are -- no product-plus-sum in them to contract, evaluated left to right as parenthesised:
+ *   filteredLinear        df = phiN - phiP:  max(min(2 - (0.5*min(|df - dcP|, |df - dcN|))/(max(|dcP|, |dcN|) + SMALL), 1), 0.8)
+ *   filteredLinear2[V]    tdc = 2*dc, l_ = l + 1.0 (the constructor):  m = df > 0 ? min(max(df - tdcP, 0), max(df - tdcN, 0))
+ *                         : min(max(tdcP - df, 0), max(tdcN - df, 0));  max(min(l_ - (k*m)/(max(|df|, max(|tdcP|, |tdcN|)) + SMALL), 1), 0)
+ *                         (filteredLinear2V adds VSMALL where the scalar form adds SMALL)
+ *   filteredLinear3[V]    dP = 2*dcP, dN = 2*dcN:  max(min(1 - ((k*(dN - df))*(dP - df))/max((dN + dP)*(dN + dP), SMALL), 1), 0)
+ *                         (filteredLinear3V uses SMALL too)
+ * then w = fma(lim, cdw, (1 - lim)*pos(faceFlux)) as mi_limited_weights.
+ * mi_filtered_parse: host only, no GPU.  Accepts exactly the five registered names with 0, 2, 2, 1, 1 coefficients; l is kept as written in
+ *   the case (the engine adds the constructor's 1.0).  Refused (MI_ERR_ARG, *out untouched): any other name (filteredLinearV, a name of
+ *   mi_limiter_parse, ...), a missing or extra coefficient, a coefficient that is not a number, k or l outside [0, 1] as the constructors do.
+ *   mi_limiter_parse keeps refusing these names: a filtered scheme is no mi_limiter.
+ * mi_filtered_weights / mi_patch_filtered_weights: the face pass and the coupled-patch pass of mi_limited_weights / mi_patch_limited_weights
+ *   (the same kernels, further kinds) with the same argument conventions -- scalar form 1 phi and 3 grad arrays, V form 3 and 9 with
+ *   grad[3*j + k] = d(phi_j)/dx_k; limiter_out may be NULL -- and the same refusals, nothing launched: an invalid struct (kind, vector_form
+ *   on filteredLinear, k or l out of range), missing arrays, unaligned face fields, an output that aliases an input.  Non-coupled patches
+ *   take limiter 1: no call is needed. */
+enum { MI_FLT_LINEAR, MI_FLT_LINEAR2, MI_FLT_LINEAR3 };
+typedef struct mi_filtered_limiter {
+    int32_t kind;          /* MI_FLT_* */
+    int32_t vector_form;   /* 1: filteredLinear2V / filteredLinear3V (3 phi, 9 grad arrays); filteredLinear has none */
+    double k, l;           /* l as written in the case; read by filteredLinear2[V] only, k by all but filteredLinear */
+} mi_filtered_limiter;
+int mi_filtered_parse(const char *scheme, mi_filtered_limiter *out);
+int mi_filtered_weights(mi_addr_t addr, const mi_filtered_limiter *lim, const double *cd_weights_dev, const double *face_flux_dev,
+                        const double *const *phi_dev, const double *const *grad_dev, const double *const *c_dev,
+                        double *weights_out_dev, double *limiter_out_dev_or_null);
+int mi_patch_filtered_weights(mi_patch_t patch, const mi_filtered_limiter *lim, const double *patch_cd_weights_dev, const double *patch_flux_dev,
+                              const double *const *phi_dev, const double *const *nbr_phi_dev, const double *const *grad_dev,
+                              const double *const *nbr_grad_dev, const double *const *patch_delta_dev,
+                              double *weights_out_dev, double *limiter_out_dev_or_null);
 int mi_gauss_grad(mi_addr_t addr, const double *sfx_dev, const double *sfy_dev, const double *sfz_dev,
                   const double *ssf_dev, const double *vol_dev_or_null, double *gx_dev, double *gy_dev, double *gz_dev);
 /* ---- the limited gradient schemes (finiteVolume/gradSchemes/limitedGradSchemes: cellLimitedGrad, cellMDLimitedGrad, faceLimitedGrad, faceMDLimitedGrad) ----
@@ -713,6 +751,43 @@ int mi_lust_weights(mi_ctx_t ctx, int64_t n_faces, const double *cd_weights_dev,
 int mi_fvm_assemble_corrected(mi_addr_t addr, const mi_fvm_terms *terms, const mi_div_correction *corr_or_null,
                               double *lower_out_dev_or_null, double *upper_out_dev, double *diag_out_dev,
                               double *const *source_out_dev, double *sum_mag_off_diag_out_dev_or_null);
+/* ---- explicit correction of the centred fourth-order scheme `Gauss cubic` ----
+ * cubic<Type> is linear<Type> with corrected() true (src/finiteVolume/interpolation/surfaceInterpolation/schemes/cubic/cubic.H:104-107): the
+ * weights are the linear ones (mesh.weights()), and gaussConvectionScheme::fvmDiv (gaussConvectionScheme.C:109-112) adds
+ * fvc::surfaceIntegrate(faceFlux*correction(vf)), i.e. source -= V*ivf, exactly as it does for linearUpwind above.  correction(vf)
+ * (cubic.H:111-184, the two-weight interpolate of surfaceInterpolationScheme.C:159-166,250-265), per face f from the one lambda = mesh.weights(),
+ * every field operator rounded on its own:
+ *     kSc   = lambda*(1 - lambda*(3 - 2*lambda))
+ *     kVecP = ((1 - lambda)*(1 - lambda))*lambda
+ *     kVecN = (lambda*lambda)*(lambda - 1)
+ * and per component r (gaussGrad of vf.component(r): grad_dev[3*r + k] = d(vf_r)/dx_k, the Gauss linear cell gradient, e.g. mi_gauss_grad):
+ *     c0   = fma(kSc, vf_r[P], (-kSc)*vf_r[N])                    (interpolate(vf, kSc, -kSc): the functor, first product fused)
+ *     gI_k = fma(kVecP, grad_r,k[P], kVecN*grad_r,k[N])            (interpolate(grad, kVecP, kVecN), k = 0..2)
+ *     corr = c0 + (((gI & Sf)/magSf)/deltaCoeffs)                 (gI & Sf = fma(gIz, Sfz, fma(gIx, Sfx, gIy*Sfy)))
+ *     out  = faceFlux*corr, or corr itself when face_flux is NULL (fvc::interpolate under cubic: linear interpolate + corr)
+ * mi_cubic_geometry: lambda = mesh.weights(), Sf (3 component arrays), magSf, surfaceInterpolation::deltaCoeffs() of the faces in question.
+ * mi_cubic_correction: the internal faces, n_rhs <= 4 components in ONE face pass (the reference: about twenty per vector).
+ * mi_patch_cubic_correction: one COUPLED patch (processor, or cyclic without rotation) with the patch's own lambda / Sf / magSf / deltaCoeffs:
+ *   vf / grad through the patch's faceCells, nbr_vf / nbr_grad the patchNeighbourField (mi_matrix_patch_neighbour_field per array).  The
+ *   reference evaluates a patch with field operators, so nothing but the dot product is contracted:
+ *   c0 = kSc*pif + (-kSc)*pnf and gI_k = kVecP*g_k[o] + kVecN*nbr_g_k[i] are two rounded products and a sum.  Non-coupled patches take zero
+ *   (cubic.H:175-181): no call is needed.
+ * Into the matrix by the unfused route of linearUpwind: mi_fvm_div with the linear weights; mi_surface_integrate(t, ...) plus the coupled
+ *   faces through mi_patch_add; mi_vec_submul(V, ivf, source).  mi_fvm_assemble_corrected and its time forms do NOT take cubic:
+ *   mi_div_correction carries linearUpwind's inputs and is unchanged.
+ * Both refuse (MI_ERR_ARG, nothing launched): n_rhs outside 1..4, a missing geometry / table / array, unaligned face fields (internal faces),
+ *   an output that aliases an input or another output.                                                                              */
+typedef struct mi_cubic_geometry {
+    const double *lambda_dev;                      /* mesh.weights() */
+    const double *sf_dev[3];                       /* Sf, component arrays */
+    const double *mag_sf_dev;                      /* magSf */
+    const double *delta_coeffs_dev;                /* surfaceInterpolation::deltaCoeffs() */
+} mi_cubic_geometry;
+int mi_cubic_correction(mi_addr_t addr, const mi_cubic_geometry *geo, int32_t n_rhs, const double *const *vf_dev,
+                        const double *const *grad_dev, const double *face_flux_dev_or_null, double *const *out_dev);
+int mi_patch_cubic_correction(mi_patch_t patch, const mi_cubic_geometry *patch_geo, int32_t n_rhs, const double *const *vf_dev,
+                              const double *const *nbr_vf_dev, const double *const *grad_dev, const double *const *nbr_grad_dev,
+                              const double *patch_flux_dev_or_null, double *const *out_dev);
 /* ---- the backward time scheme: fvm::ddt, fvc::ddt, fvc::ddtCorr and the fused assembly ----
  * backwardDdtScheme<Type> (src/finiteVolume/finiteVolume/ddtSchemes/backwardDdtScheme/backwardDdtScheme.C), the static-mesh branches.  The
  * reference evaluates every expression below as field operators, one pass and one rounding per operator; the engine rounds every product,

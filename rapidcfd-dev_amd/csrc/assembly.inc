@@ -1099,19 +1099,89 @@ __global__ __launch_bounds__(RB) void k_lust_weights(const double* __restrict__ 
 {
     cell_map<4>(n, {cdw, flux}, {w}, [](const double (&x)[2], double (&o)[1]) { o[0] = 0.75 * x[0] + 0.25 * (x[1] >= 0 ? 1.0 : 0.0); });
 }
+// ---- the explicit correction of `cubic` (schemes/cubic/cubic.H:111-184, DESIGN 3.5j) ---------------------------------------------------
+// [faceFlux *] correction(vf) for n_rhs <= 4 components in one face pass (the reference: three coefficient fields, then per component the
+// two-weight interpolate, the gradient's interpolate, the dot product, two divisions and the sum).  The coefficients come from the one
+// lambda stream, each field operator rounded on its own:  kSc = lambda*(1 - lambda*(3 - 2*lambda)),  kVecP = ((1 - lambda)*(1 - lambda))*lambda,
+// kVecN = (lambda*lambda)*(lambda - 1).  On the internal faces the interpolate functor (surfaceInterpolationScheme.C:159-166) contracts
+// its first product; on a coupled patch the reference evaluates field operators (.C:257-259): two rounded products and a sum.
+struct CubicGeo { const double *lam, *sf[3], *magSf, *dc; };
+__device__ __forceinline__ void cubic_coeffs(double lam, double& kSc, double& kP, double& kN)
+{
+    kSc = lam * (1 - lam * (3 - 2 * lam));
+    kP = ((1 - lam) * (1 - lam)) * lam;
+    kN = (lam * lam) * (lam - 1);
+}
+// corr = c0 + (((gI & Sf)/magSf)/deltaCoeffs), then the flux; gI the interpolated gradient
+__device__ __forceinline__ double cubic_close(const CubicGeo& g, int f, double c0, double gx, double gy, double gz, const double* flux)
+{
+    const double corr = c0 + ((lu_dot(gx, gy, gz, g.sf[0][f], g.sf[1][f], g.sf[2][f]) / g.magSf[f]) / g.dc[f]);
+    return flux ? flux[f] * corr : corr;
+}
+struct CubicArgs {
+    const int32_t *lo, *up;
+    CubicGeo g;
+    const double *flux, *vf[4], *grad[12];
+    double* out[4];
+    int nRhs, nf, xcd;
+};
+// the internal faces: XCD-aware chunks as k_linear_upwind_corr; seven face arrays streamed, vf and its gradient gathered at both cells
+__global__ void k_cubic_corr(const CubicArgs a)
+{
+    int f0, f1; block_chunk(a.nf, a.xcd, f0, f1);
+    for (int f = f0 + threadIdx.x; f < f1; f += blockDim.x) {
+        const int P = a.lo[f], N = a.up[f];
+        double kSc, kP, kN; cubic_coeffs(a.g.lam[f], kSc, kP, kN);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r < a.nRhs) {
+                const double c0 = fma(kSc, a.vf[r][P], (-kSc) * a.vf[r][N]);
+                double gI[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) gI[k] = fma(kP, a.grad[3 * r + k][P], kN * a.grad[3 * r + k][N]);
+                a.out[r][f] = cubic_close(a.g, f, c0, gI[0], gI[1], gI[2], a.flux);
+            }
+    }
+}
+struct PatchCubicArgs {
+    const int32_t* fc;
+    CubicGeo g;
+    const double *flux, *vf[4], *nvf[4], *grad[12], *ngrad[12];
+    double* out[4];
+    int nRhs, n;
+};
+// one COUPLED patch: vf / grad through faceCells, nvf / ngrad the caller's patchNeighbourField; nothing contracted but the dot product
+__global__ void k_patch_cubic_corr(const PatchCubicArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int o = a.fc[i];
+    double kSc, kP, kN; cubic_coeffs(a.g.lam[i], kSc, kP, kN);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (r < a.nRhs) {
+            const double c0 = kSc * a.vf[r][o] + (-kSc) * a.nvf[r][i];
+            double gI[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) gI[k] = kP * a.grad[3 * r + k][o] + kN * a.ngrad[3 * r + k][i];
+            a.out[r][i] = cubic_close(a.g, i, c0, gI[0], gI[1], gI[2], a.flux);
+        }
+}
 // ---- the TVD/NVD limited schemes (limitedSchemes/*, DESIGN 3.5b) ------------------------------------------------------------------
 // LimitedSchemeCalcLimiterFunctor (LimitedScheme.C:41-55) for every limiter of the family over NVDTVD (a scalar) or NVDVTVDV (the "V"
 // schemes: a vector, its gradient grad[3*j + k] = d(phi_j)/dx_k), with the LimitedLimiter bounds (Limited.H:93-133, scalar form only),
 // then the weights lim*cdw + (1 - lim)*pos(flux) (limitedSurfaceInterpolationScheme.C:155-161).  One contraction rule throughout: a dot
 // product is lu_dot, of two products in a sum the first is fused; max / min are the reference's (s1 > s2) ? s1 : s2 / (s1 < s2) ? s1 : s2.
-enum { LIM_LINEAR, LIM_VANLEER, LIM_MUSCL, LIM_MINMOD, LIM_SUPERBEE, LIM_UMIST, LIM_VANALBADA, LIM_OSPRE, LIM_QUICK, LIM_CUBIC, LIM_GAMMA, LIM_SFCD, LIM_N };
-struct LimCoef { double twoByk, gammaK, lower, upper; int bounded; };
+enum { LIM_LINEAR, LIM_VANLEER, LIM_MUSCL, LIM_MINMOD, LIM_SUPERBEE, LIM_UMIST, LIM_VANALBADA, LIM_OSPRE, LIM_QUICK, LIM_CUBIC, LIM_GAMMA, LIM_SFCD, LIM_N,
+       // the filtered centred limiters (mi_filtered_limiter, DESIGN 3.5j): kinds of the same face passes that no mi_limiter reaches
+       LIM_FLT_LINEAR = LIM_N, LIM_FLT_LINEAR2, LIM_FLT_LINEAR3, LIM_ALL };
+struct LimCoef { double twoByk, gammaK, lower, upper; int bounded; double fltK, fltL; };   // fltL: l_ = l + 1.0 (filteredLinear2.H:101)
 __device__ __forceinline__ double rmax(double a, double b) { return a > b ? a : b; }
 __device__ __forceinline__ double rmin(double a, double b) { return a < b ? a : b; }
 __device__ __forceinline__ double rsign(double s) { return s >= 0 ? 1.0 : -1.0; }
 __device__ __forceinline__ double rstab(double s) { return s >= 0 ? s + 1e-15 : s - 1e-15; }   // stabilise(s, SMALL)
 // phi(p, j): component j at the owner side (p) or the neighbour side; grad(p, c): gradient component c there.  Only what KIND reads
-// is loaded: the scalar form gathers the gradient at the upwind cell only, limitedCubic at both.
+// is loaded: the scalar form gathers the gradient at the upwind cell only, limitedCubic and the filtered kinds at both.
 template <int KIND, bool VEC, class PHI, class GRAD>
 __device__ __forceinline__ double lim_face(const LimCoef& L, double cdw, double fl, const PHI& phi, const GRAD& grad, double dx, double dy, double dz)
 {
@@ -1119,9 +1189,36 @@ __device__ __forceinline__ double lim_face(const LimCoef& L, double cdw, double 
     double pP[M], pN[M];
 #pragma unroll
     for (int j = 0; j < M; ++j) { pP[j] = phi(true, j); pN[j] = phi(false, j); }
+    auto dg = [&](bool p, int j) { return lu_dot(dx, dy, dz, grad(p, 3 * j), grad(p, 3 * j + 1), grad(p, 3 * j + 2)); };   // d & grad(phi_j)
+    if constexpr (KIND >= LIM_FLT_LINEAR) {                        // centred: both cells' gradients, never the flux; no product-plus-sum to contract
+        double df, cP, cN;                                        // the face difference and d & gradc at either cell (V: along dfV)
+        if (VEC) {                                                // filteredLinear2V.H:117-126, filteredLinear3V.H:97-106
+            double dfV[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dfV[j] = pN[j] - pP[j];
+            df = lu_dot(dfV[0], dfV[1], dfV[2], dfV[0], dfV[1], dfV[2]);
+            cP = lu_dot(dfV[0], dfV[1], dfV[2], dg(true, 0), dg(true, 1), dg(true, 2));
+            cN = lu_dot(dfV[0], dfV[1], dfV[2], dg(false, 0), dg(false, 1), dg(false, 2));
+        } else {
+            df = pN[0] - pP[0];
+            cP = dg(true, 0);
+            cN = dg(false, 0);
+        }
+        if constexpr (KIND == LIM_FLT_LINEAR) {                   // filteredLinear.H:81-92: between linear and 20 % upwind
+            const double lim = 2 - (0.5 * rmin(fabs(df - cP), fabs(df - cN))) / (rmax(fabs(cP), fabs(cN)) + 1e-15);
+            return rmax(rmin(lim, 1.0), 0.8);
+        }
+        const double tP = 2 * cP, tN = 2 * cN;                    // exact
+        if constexpr (KIND == LIM_FLT_LINEAR2) {                  // filteredLinear2.H:117-140; the V form adds VSMALL (filteredLinear2V.H:135,141)
+            const double m = df > 0 ? rmin(rmax(df - tP, 0.0), rmax(df - tN, 0.0)) : rmin(rmax(tP - df, 0.0), rmax(tN - df, 0.0));
+            const double lim = L.fltL - (L.fltK * m) / (rmax(fabs(df), rmax(fabs(tP), fabs(tN))) + (VEC ? 1e-300 : 1e-15));
+            return rmax(rmin(lim, 1.0), 0.0);
+        }
+        const double lim = 1 - ((L.fltK * (tN - df)) * (tP - df)) / rmax((tN + tP) * (tN + tP), 1e-15);   // filteredLinear3.H:104, filteredLinear3V.H:109
+        return rmax(rmin(lim, 1.0), 0.0);
+    }
     if (!VEC && L.bounded && ((fl > 0 && (pP[0] < L.lower || pN[0] > L.upper)) || (fl < 0 && (pN[0] < L.lower || pP[0] > L.upper)))) return 0.0;
     const bool up = fl > 0;                                       // strict (NVDTVD.H:110)
-    auto dg = [&](bool p, int j) { return lu_dot(dx, dy, dz, grad(p, 3 * j), grad(p, 3 * j + 1), grad(p, 3 * j + 2)); };   // d & grad(phi_j)
     double gfV[3] = {0.0, 0.0, 0.0}, gradf, gradcf;
     if (VEC) {
 #pragma unroll
@@ -2707,13 +2804,16 @@ int lim_check(const char* who, const mi_limiter* l, LimCoef& c)
     void dispatch_##KERNEL(int kind, bool vec, dim3 g, dim3 b, hipStream_t s, const ARGS& a)                                             \
     {                                                                                                                                    \
         typedef void (*F)(dim3, dim3, hipStream_t, const ARGS&);                                                                         \
-        static const F tab[2][LIM_N] = {                                                                                                 \
+        static const F tab[2][LIM_ALL] = {                                                                                               \
             {launch_##KERNEL<0, false>, launch_##KERNEL<1, false>, launch_##KERNEL<2, false>, launch_##KERNEL<3, false>,                 \
              launch_##KERNEL<4, false>, launch_##KERNEL<5, false>, launch_##KERNEL<6, false>, launch_##KERNEL<7, false>,                 \
-             launch_##KERNEL<8, false>, launch_##KERNEL<9, false>, launch_##KERNEL<10, false>, launch_##KERNEL<11, false>},              \
+             launch_##KERNEL<8, false>, launch_##KERNEL<9, false>, launch_##KERNEL<10, false>, launch_##KERNEL<11, false>,               \
+             launch_##KERNEL<LIM_FLT_LINEAR, false>, launch_##KERNEL<LIM_FLT_LINEAR2, false>, launch_##KERNEL<LIM_FLT_LINEAR3, false>},  \
             {launch_##KERNEL<0, true>, launch_##KERNEL<1, true>, launch_##KERNEL<2, true>, launch_##KERNEL<3, true>,                     \
              launch_##KERNEL<4, true>, launch_##KERNEL<5, true>, launch_##KERNEL<6, true>, launch_##KERNEL<7, true>,                     \
-             launch_##KERNEL<8, true>, launch_##KERNEL<9, true>, launch_##KERNEL<10, true>, launch_##KERNEL<11, true>}};                \
+             launch_##KERNEL<8, true>, launch_##KERNEL<9, true>, launch_##KERNEL<10, true>, launch_##KERNEL<11, true>,                   \
+             nullptr /* filteredLinear has no V form: flt_check refuses it */, launch_##KERNEL<LIM_FLT_LINEAR2, true>,                   \
+             launch_##KERNEL<LIM_FLT_LINEAR3, true>}};                                                                                   \
         tab[vec ? 1 : 0][kind](g, b, s, a);                                                                                              \
     }
 MI_LIM_CASES(k_limited_weights, LimArgs)
@@ -2758,15 +2858,15 @@ extern "C" int mi_limiter_parse(const char* scheme, mi_limiter* out)
     return MI_OK;
 }
 
-extern "C" int mi_limited_weights(mi_addr_t a, const mi_limiter* lim, const double* cd_weights_dev, const double* face_flux_dev,
-                                  const double* const* phi_dev, const double* const* grad_dev, const double* const* c_dev,
-                                  double* weights_out_dev, double* limiter_out_dev_or_null)
+namespace {
+// the internal-face pass of a checked limiter (coefficients k, kernel kind, V form): mi_limited_weights and mi_filtered_weights
+int lim_internal(const char* who, mi_addr_s* a, const LimCoef& k, int kind, bool vec, const double* cd_weights_dev, const double* face_flux_dev,
+                 const double* const* phi_dev, const double* const* grad_dev, const double* const* c_dev, double* weights_out_dev,
+                 double* limiter_out_dev_or_null)
 {
-    const char* who = "mi_limited_weights";
-    if (!a || !phi_dev || !grad_dev || !c_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
     LimArgs q{};
-    MICHK(lim_check(who, lim, q.k));
-    const int m = lim->vector_form ? 3 : 1;
+    q.k = k;
+    const int m = vec ? 3 : 1;
     const double* in[17];
     int n = 0;
     in[n++] = q.cdw = cd_weights_dev; in[n++] = q.flux = face_flux_dev;
@@ -2781,23 +2881,20 @@ extern "C" int mi_limited_weights(mi_addr_t a, const mi_limiter* lim, const doub
     if (a->L.nFaces == 0) return MI_OK;
     q.lo = a->lowerAddr.p; q.up = a->upperAddr.p; q.w = weights_out_dev; q.limOut = limiter_out_dev_or_null;
     q.nf = a->L.nFaces; q.xcd = a->ctx->xcdRows;
-    dispatch_k_limited_weights(lim->kind, lim->vector_form != 0, dim3(grid_for(a->ctx, a->L.nFaces)), dim3(256), a->ctx->stream, q);
+    dispatch_k_limited_weights(kind, vec, dim3(grid_for(a->ctx, a->L.nFaces)), dim3(256), a->ctx->stream, q);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
-
-extern "C" int mi_patch_limited_weights(mi_patch_t p, const mi_limiter* lim, const double* patch_cd_weights_dev, const double* patch_flux_dev,
-                                        const double* const* phi_dev, const double* const* nbr_phi_dev, const double* const* grad_dev,
-                                        const double* const* nbr_grad_dev, const double* const* patch_delta_dev,
-                                        double* weights_out_dev, double* limiter_out_dev_or_null)
+// the same on one coupled patch: mi_patch_limited_weights and mi_patch_filtered_weights
+int lim_patch(const char* who, mi_patch_s* p, const LimCoef& k, int kind, bool vec, const double* patch_cd_weights_dev, const double* patch_flux_dev,
+              const double* const* phi_dev, const double* const* nbr_phi_dev, const double* const* grad_dev, const double* const* nbr_grad_dev,
+              const double* const* patch_delta_dev, double* weights_out_dev, double* limiter_out_dev_or_null)
 {
-    const char* who = "mi_patch_limited_weights";
-    if (!p) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
-    PatchLimArgs q{};
-    MICHK(lim_check(who, lim, q.k));
     if (p->nFaces == 0) return MI_OK;
     if (!phi_dev || !nbr_phi_dev || !grad_dev || !nbr_grad_dev || !patch_delta_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
-    const int m = lim->vector_form ? 3 : 1;
+    PatchLimArgs q{};
+    q.k = k;
+    const int m = vec ? 3 : 1;
     const double* in[29];
     int n = 0;
     in[n++] = q.cdw = patch_cd_weights_dev; in[n++] = q.flux = patch_flux_dev;
@@ -2807,7 +2904,184 @@ extern "C" int mi_patch_limited_weights(mi_patch_t p, const mi_limiter* lim, con
     MICHK(lim_outputs(who, in, n, weights_out_dev, limiter_out_dev_or_null));
     HIPCHK(hipSetDevice(p->ctx->device));
     q.fc = p->faceCells.p; q.w = weights_out_dev; q.limOut = limiter_out_dev_or_null; q.n = p->nFaces;
-    dispatch_k_patch_limited_weights(lim->kind, lim->vector_form != 0, dim3((p->nFaces + 255) / 256), dim3(256), p->ctx->stream, q);
+    dispatch_k_patch_limited_weights(kind, vec, dim3((p->nFaces + 255) / 256), dim3(256), p->ctx->stream, q);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+} // namespace
+
+extern "C" int mi_limited_weights(mi_addr_t a, const mi_limiter* lim, const double* cd_weights_dev, const double* face_flux_dev,
+                                  const double* const* phi_dev, const double* const* grad_dev, const double* const* c_dev,
+                                  double* weights_out_dev, double* limiter_out_dev_or_null)
+{
+    const char* who = "mi_limited_weights";
+    if (!a || !phi_dev || !grad_dev || !c_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    LimCoef k;
+    MICHK(lim_check(who, lim, k));
+    return lim_internal(who, a, k, lim->kind, lim->vector_form != 0, cd_weights_dev, face_flux_dev, phi_dev, grad_dev, c_dev, weights_out_dev,
+                        limiter_out_dev_or_null);
+}
+
+extern "C" int mi_patch_limited_weights(mi_patch_t p, const mi_limiter* lim, const double* patch_cd_weights_dev, const double* patch_flux_dev,
+                                        const double* const* phi_dev, const double* const* nbr_phi_dev, const double* const* grad_dev,
+                                        const double* const* nbr_grad_dev, const double* const* patch_delta_dev,
+                                        double* weights_out_dev, double* limiter_out_dev_or_null)
+{
+    const char* who = "mi_patch_limited_weights";
+    if (!p) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    LimCoef k;
+    MICHK(lim_check(who, lim, k));
+    return lim_patch(who, p, k, lim->kind, lim->vector_form != 0, patch_cd_weights_dev, patch_flux_dev, phi_dev, nbr_phi_dev, grad_dev, nbr_grad_dev,
+                     patch_delta_dev, weights_out_dev, limiter_out_dev_or_null);
+}
+
+// ---- the filtered centred limiters: parse (host only) and the two face passes on the limited schemes' kernels (DESIGN 3.5j) -----------
+namespace {
+struct FltName { const char* name; int kind, vec, nCoef; };
+// the names the reference registers (limitedSchemes/filteredLinear/filteredLinear.C:33-37, filteredLinear2/filteredLinear2.C:34-44,
+// filteredLinear3/filteredLinear3.C:34-44)
+const FltName kFltNames[] = {
+    {"filteredLinear", MI_FLT_LINEAR, 0, 0}, {"filteredLinear2", MI_FLT_LINEAR2, 0, 2}, {"filteredLinear2V", MI_FLT_LINEAR2, 1, 2},
+    {"filteredLinear3", MI_FLT_LINEAR3, 0, 1}, {"filteredLinear3V", MI_FLT_LINEAR3, 1, 1},
+};
+// the constructors' checks (filteredLinear2.H:85-99, filteredLinear2V.H:85-99, filteredLinear3.H:75-81, filteredLinear3V.H:75-81) on a
+// caller-filled mi_filtered_limiter; a coefficient its kind does not read is not looked at
+int flt_check(const char* who, const mi_filtered_limiter* l, LimCoef& c)
+{
+    if (!l || l->kind < MI_FLT_LINEAR || l->kind > MI_FLT_LINEAR3 || (l->vector_form != 0 && l->vector_form != 1) ||
+        (l->kind == MI_FLT_LINEAR && l->vector_form))
+        return fail(MI_ERR_ARG, std::string(who) + ": invalid mi_filtered_limiter");
+    if (l->kind != MI_FLT_LINEAR && !(l->k >= 0 && l->k <= 1)) return fail(MI_ERR_ARG, std::string(who) + ": coefficient k should be >= 0 and <= 1");
+    if (l->kind == MI_FLT_LINEAR2 && !(l->l >= 0 && l->l <= 1)) return fail(MI_ERR_ARG, std::string(who) + ": coefficient l should be >= 0 and <= 1");
+    c = LimCoef{};
+    c.fltK = l->k;
+    c.fltL = l->l + 1.0;                                         // filteredLinear2.H:101: l_ += 1.0
+    return MI_OK;
+}
+} // namespace
+
+extern "C" int mi_filtered_parse(const char* scheme, mi_filtered_limiter* out)
+{
+    const std::string who = "mi_filtered_parse";
+    if (!scheme || !out) return fail(MI_ERR_ARG, who + ": bad argument");
+    const std::vector<std::string> tok = scheme_words(scheme);
+    if (tok.empty()) return fail(MI_ERR_ARG, who + ": empty scheme");
+    const std::string& name = tok[0];
+    const FltName* e = nullptr;
+    for (const FltName& x : kFltNames) if (name == x.name) e = &x;
+    if (!e) return fail(MI_ERR_ARG, who + ": unknown filtered scheme '" + name + "' (filteredLinear | filteredLinear2 k l | filteredLinear2V k l | "
+                                          "filteredLinear3 k | filteredLinear3V k)");
+    const int want = e->nCoef, got = (int)tok.size() - 1;
+    if (got > want) return fail(MI_ERR_ARG, who + ": '" + name + "' takes " + std::to_string(want) + " coefficient(s): extra '" + tok[want + 1] + "'");
+    double v[2] = {0, 0};
+    for (int j = 0; j < got; ++j)
+        if (!scheme_number(tok[j + 1], v[j])) return fail(MI_ERR_ARG, who + ": '" + tok[j + 1] + "' is not a number");
+    if (got < want) return fail(MI_ERR_ARG, who + ": '" + name + "' takes " + std::to_string(want) + " coefficient(s), " + std::to_string(got) + " given");
+    mi_filtered_limiter l{};
+    l.kind = e->kind; l.vector_form = e->vec; l.k = v[0]; l.l = v[1];
+    LimCoef c;
+    MICHK(flt_check(who.c_str(), &l, c));
+    *out = l;
+    return MI_OK;
+}
+
+extern "C" int mi_filtered_weights(mi_addr_t a, const mi_filtered_limiter* lim, const double* cd_weights_dev, const double* face_flux_dev,
+                                   const double* const* phi_dev, const double* const* grad_dev, const double* const* c_dev,
+                                   double* weights_out_dev, double* limiter_out_dev_or_null)
+{
+    const char* who = "mi_filtered_weights";
+    if (!a || !phi_dev || !grad_dev || !c_dev) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    LimCoef k;
+    MICHK(flt_check(who, lim, k));
+    return lim_internal(who, a, k, LIM_FLT_LINEAR + lim->kind, lim->vector_form != 0, cd_weights_dev, face_flux_dev, phi_dev, grad_dev, c_dev,
+                        weights_out_dev, limiter_out_dev_or_null);
+}
+
+extern "C" int mi_patch_filtered_weights(mi_patch_t p, const mi_filtered_limiter* lim, const double* patch_cd_weights_dev, const double* patch_flux_dev,
+                                         const double* const* phi_dev, const double* const* nbr_phi_dev, const double* const* grad_dev,
+                                         const double* const* nbr_grad_dev, const double* const* patch_delta_dev,
+                                         double* weights_out_dev, double* limiter_out_dev_or_null)
+{
+    const char* who = "mi_patch_filtered_weights";
+    if (!p) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    LimCoef k;
+    MICHK(flt_check(who, lim, k));
+    return lim_patch(who, p, k, LIM_FLT_LINEAR + lim->kind, lim->vector_form != 0, patch_cd_weights_dev, patch_flux_dev, phi_dev, nbr_phi_dev, grad_dev,
+                     nbr_grad_dev, patch_delta_dev, weights_out_dev, limiter_out_dev_or_null);
+}
+
+// ---- the cubic correction: the internal faces and one coupled patch (DESIGN 3.5j) ----------------------------------------------------
+namespace {
+// geometry, fields and outputs of either cubic pass: every array present, the streamed face fields aligned, no output among the inputs or twice
+int cubic_arrays(const std::string& who, const mi_cubic_geometry* geo, int nRhs, const double* flux, const double* const* const* cellIn, int nCellIn,
+                 double* const* out, bool aligned, CubicGeo& g)
+{
+    if (!geo) return fail(MI_ERR_ARG, who + ": the geometry is missing");
+    g.lam = geo->lambda_dev; g.magSf = geo->mag_sf_dev; g.dc = geo->delta_coeffs_dev;
+    for (int d = 0; d < 3; ++d) g.sf[d] = geo->sf_dev[d];
+    const double* in[7 + 32] = {g.lam, g.sf[0], g.sf[1], g.sf[2], g.magSf, g.dc};
+    int m = 6;
+    for (int j = 0; j < m; ++j) if (!in[j]) return fail(MI_ERR_ARG, who + ": geometry arrays missing (lambda, Sf x3, magSf, deltaCoeffs)");
+    if (aligned) for (int j = 0; j < m; ++j) if (!al16(in[j])) return fail(MI_ERR_ARG, who + ": face fields must be 16-byte aligned");
+    if (flux) { if (aligned && !al16(flux)) return fail(MI_ERR_ARG, who + ": face fields must be 16-byte aligned"); in[m++] = flux; }
+    for (int t = 0; t < nCellIn; ++t) {
+        const int cnt = (t % 2 == 0 ? 1 : 3) * nRhs;              // tables alternate: a field (n_rhs arrays), its gradient (3*n_rhs)
+        for (int j = 0; j < cnt; ++j) {
+            if (!cellIn[t][j]) return fail(MI_ERR_ARG, who + ": input arrays missing (one field and 3 gradient components per right-hand side)");
+            in[m++] = cellIn[t][j];
+        }
+    }
+    for (int r = 0; r < nRhs; ++r) {
+        if (!out[r]) return fail(MI_ERR_ARG, who + ": null output");
+        if (aligned && !al16(out[r])) return fail(MI_ERR_ARG, who + ": face fields must be 16-byte aligned");
+        for (int j = 0; j < m; ++j) if (out[r] == in[j]) return fail(MI_ERR_ARG, who + ": an output must not alias an input");
+        for (int s = 0; s < r; ++s) if (out[s] == out[r]) return fail(MI_ERR_ARG, who + ": the outputs must differ");
+    }
+    return MI_OK;
+}
+} // namespace
+
+extern "C" int mi_cubic_correction(mi_addr_t a, const mi_cubic_geometry* geo, int32_t n_rhs, const double* const* vf_dev, const double* const* grad_dev,
+                                   const double* face_flux_dev_or_null, double* const* out_dev)
+{
+    const std::string who = "mi_cubic_correction";
+    if (!a) return fail(MI_ERR_ARG, who + ": bad argument");
+    if (n_rhs < 1 || n_rhs > 4) return fail(MI_ERR_ARG, who + ": a correction needs 1 to 4 components");
+    if (faceless(a)) return MI_OK;                        // no face to correct: the outputs are empty
+    if (!vf_dev || !grad_dev || !out_dev) return fail(MI_ERR_ARG, who + ": a pointer table is missing");
+    CubicArgs q{};
+    const double* const* tables[2] = {vf_dev, grad_dev};
+    MICHK(cubic_arrays(who, geo, n_rhs, face_flux_dev_or_null, tables, 2, out_dev, true, q.g));
+    HIPCHK(hipSetDevice(a->ctx->device));
+    MICHK(ensure_caller_tables(a));
+    if (a->L.nFaces == 0) return MI_OK;
+    q.lo = a->lowerAddr.p; q.up = a->upperAddr.p; q.flux = face_flux_dev_or_null;
+    for (int r = 0; r < n_rhs; ++r) { q.vf[r] = vf_dev[r]; q.out[r] = out_dev[r]; }
+    for (int j = 0; j < 3 * n_rhs; ++j) q.grad[j] = grad_dev[j];
+    q.nRhs = n_rhs; q.nf = a->L.nFaces; q.xcd = a->ctx->xcdRows;
+    k_cubic_corr<<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(q);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+
+extern "C" int mi_patch_cubic_correction(mi_patch_t p, const mi_cubic_geometry* patch_geo, int32_t n_rhs, const double* const* vf_dev,
+                                         const double* const* nbr_vf_dev, const double* const* grad_dev, const double* const* nbr_grad_dev,
+                                         const double* patch_flux_dev_or_null, double* const* out_dev)
+{
+    const std::string who = "mi_patch_cubic_correction";
+    if (!p) return fail(MI_ERR_ARG, who + ": bad argument");
+    if (n_rhs < 1 || n_rhs > 4) return fail(MI_ERR_ARG, who + ": a correction needs 1 to 4 components");
+    if (p->nFaces == 0) return MI_OK;
+    if (!vf_dev || !nbr_vf_dev || !grad_dev || !nbr_grad_dev || !out_dev) return fail(MI_ERR_ARG, who + ": a pointer table is missing");
+    PatchCubicArgs q{};
+    const double* const* tables[4] = {vf_dev, grad_dev, nbr_vf_dev, nbr_grad_dev};
+    MICHK(cubic_arrays(who, patch_geo, n_rhs, patch_flux_dev_or_null, tables, 4, out_dev, false, q.g));
+    HIPCHK(hipSetDevice(p->ctx->device));
+    q.fc = p->faceCells.p; q.flux = patch_flux_dev_or_null;
+    for (int r = 0; r < n_rhs; ++r) { q.vf[r] = vf_dev[r]; q.nvf[r] = nbr_vf_dev[r]; q.out[r] = out_dev[r]; }
+    for (int j = 0; j < 3 * n_rhs; ++j) { q.grad[j] = grad_dev[j]; q.ngrad[j] = nbr_grad_dev[j]; }
+    q.nRhs = n_rhs; q.n = p->nFaces;
+    k_patch_cubic_corr<<<(p->nFaces + 255) / 256, 256, 0, p->ctx->stream>>>(q);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }

@@ -71,6 +71,7 @@ SYMBOLS = [
     "mi_comm_create_external", "mi_addr_create_ordered", "mi_addr_tile_starts", "mi_addr_is_ordered",
     "mi_linear_upwind_correction", "mi_patch_linear_upwind_correction", "mi_lust_weights", "mi_fvm_assemble_corrected",
     "mi_limiter_parse", "mi_limited_weights", "mi_patch_limited_weights",
+    "mi_filtered_parse", "mi_filtered_weights", "mi_patch_filtered_weights", "mi_cubic_correction", "mi_patch_cubic_correction",
     "mi_grad_limiter_parse", "mi_grad_boundary_create", "mi_grad_boundary_destroy", "mi_limited_grad",
     "mi_ddt_backward_coeffs", "mi_fvm_ddt_backward", "mi_fvc_ddt_backward", "mi_ddt_phi_corr_backward", "mi_fvm_assemble_backward",
     "mi_ddt_cn_parse", "mi_ddt_cn_begin", "mi_ddt_cn_step", "mi_ddt_cn_update", "mi_fvm_ddt_cn", "mi_fvc_ddt_cn", "mi_fvm_assemble_cn",
@@ -928,6 +929,22 @@ class Patch:
         _chk(lib().mi_patch_limited_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), pv(phi), pv(nbr_phi), pv(grad),
                                             pv(nbr_grad), pv(patch_delta), _ptr(w_out), _ptr(limiter_out)))
 
+    def filtered_weights(self, lim, patch_cd_weights, patch_flux, phi, nbr_phi, grad, nbr_grad, patch_delta, w_out, limiter_out=None):
+        """a filtered scheme's weights on a COUPLED patch (mi_patch_filtered_weights): the arguments of limited_weights; lim a FilteredLimiter
+        or a scheme name"""
+        lim = filtered(lim) if isinstance(lim, str) else lim
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_patch_filtered_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), pv(phi), pv(nbr_phi), pv(grad),
+                                             pv(nbr_grad), pv(patch_delta), _ptr(w_out), _ptr(limiter_out)))
+
+    def cubic_correction(self, geo, vf, nbr_vf, grad, nbr_grad, out, patch_flux=None):
+        """[patchFlux *] correction(vf) of cubic on a COUPLED patch (mi_patch_cubic_correction): geo a CubicGeometry of the patch's arrays, vf /
+        nbr_vf one array per component (cell field, its patchNeighbourField), grad / nbr_grad one [gx, gy, gz] per component, out one patch
+        array per component"""
+        pv = lambda xs: (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_patch_cubic_correction(self.h, C.byref(geo), C.c_int32(len(out)), pv(vf), pv(nbr_vf), pv([g for gr in grad for g in gr]),
+                                             pv([g for gr in nbr_grad for g in gr]), _ptr(patch_flux), pv(out)))
+
     def sngrad_correction_flux(self, corr_vecs, weights, grad, nbr_grad, gamma_magsf, out):
         """non-orthogonal correction flux on a COUPLED patch (gaussLaplacianSchemes.C:64-90 + surfaceInterpolationScheme.C:360-365)"""
         _chk(lib().mi_patch_sngrad_correction_flux(self.h, _ptr(corr_vecs[0]), _ptr(corr_vecs[1]), _ptr(corr_vecs[2]), _ptr(weights), _ptr(grad[0]),
@@ -1081,6 +1098,38 @@ def limiter(scheme: str) -> Limiter:
     out = Limiter()
     _chk(lib().mi_limiter_parse(scheme.encode(), C.byref(out)))
     return out
+
+
+class FilteredLimiter(C.Structure):
+    """mi_filtered_limiter (include/mi_ldu.h)"""
+    _fields_ = [("kind", C.c_int32), ("vector_form", C.c_int32), ("k", C.c_double), ("l", C.c_double)]
+
+
+FILTERED_KINDS = ("filteredLinear", "filteredLinear2", "filteredLinear3")
+
+
+def filtered(scheme: str) -> FilteredLimiter:
+    """mi_filtered_parse: "filteredLinear", "filteredLinear2 1 0", "filteredLinear2V 1 0", "filteredLinear3 0.5", "filteredLinear3V 0.5" (host only,
+    no GPU); l stays as written (the engine adds the constructor's 1.0)"""
+    out = FilteredLimiter()
+    _chk(lib().mi_filtered_parse(scheme.encode(), C.byref(out)))
+    return out
+
+
+class CubicGeometry(C.Structure):
+    """mi_cubic_geometry (include/mi_ldu.h)"""
+    _fields_ = [("lambda_dev", C.c_void_p), ("sf_dev", C.c_void_p * 3), ("mag_sf_dev", C.c_void_p), ("delta_coeffs_dev", C.c_void_p)]
+
+
+def cubic_geometry(lam, sf, mag_sf, delta_coeffs) -> CubicGeometry:
+    """the face geometry the cubic correction reads: mesh.weights(), Sf as [x, y, z], magSf, surfaceInterpolation::deltaCoeffs() (of the
+    internal faces, or of one coupled patch)"""
+    g = CubicGeometry()
+    g.lambda_dev = _ptr(lam).value; g.mag_sf_dev = _ptr(mag_sf).value; g.delta_coeffs_dev = _ptr(delta_coeffs).value
+    for d in range(3):
+        g.sf_dev[d] = _ptr(sf[d]).value
+    g.arrays = (lam, tuple(sf), mag_sf, delta_coeffs)   # the struct holds bare addresses: keep the tensors alive as long as it lives
+    return g
 
 
 class GradLimiter(C.Structure):
@@ -1347,6 +1396,22 @@ class Assembly:
         pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
         _chk(lib().mi_limited_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), pv(phi), pv(grad), pv(centres), _ptr(w_out),
                                       _ptr(limiter_out)))
+
+    def filtered_weights(self, lim, cd_weights, face_flux, phi, grad, centres, w_out, limiter_out=None):
+        """a filtered scheme's weights on the internal faces in one face pass (mi_filtered_weights): lim a FilteredLimiter or a scheme name
+        ("filteredLinear2V 1 0"), the other arguments as limited_weights"""
+        lim = filtered(lim) if isinstance(lim, str) else lim
+        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_filtered_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), pv(phi), pv(grad), pv(centres), _ptr(w_out),
+                                       _ptr(limiter_out)))
+
+    def cubic_correction(self, geo, vf, grad, out, face_flux=None):
+        """[faceFlux *] correction(vf) of cubic on the internal faces, one face pass for len(out) <= 4 components (mi_cubic_correction; cubic.H:111-184):
+        geo a CubicGeometry, vf one cell array per component, grad one [gx, gy, gz] (Gauss linear) per component; face_flux None: the bare
+        correction field of fvc::interpolate"""
+        pv = lambda xs: (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_cubic_correction(self.addr.h, C.byref(geo), C.c_int32(len(out)), pv(vf), pv([g for gr in grad for g in gr]), _ptr(face_flux),
+                                       pv(out)))
 
     def limited_grad(self, lim, vf, centres, cf, grad, boundary=None, bvalue=None, bcf=None, limiter_out=None):
         """limits a Gauss linear gradient in place (mi_limited_grad): lim a GradLimiter or a scheme ("cellLimited Gauss linear 1"), vf 1 or 3

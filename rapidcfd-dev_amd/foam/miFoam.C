@@ -973,6 +973,36 @@ void fvc::linearUpwindCorrectionFlux(vectorgpuField& out, const lduAddressing& a
     const auto o = cmptData(out);
     miCheck(mi_linear_upwind_correction(a.handle(), &k, 3, faceFlux.data(), o), "linearUpwind::correction");
 }
+namespace {
+mi_cubic_geometry cubicGeometry(const scalargpuField& lambda, const vectorgpuField& Sf, const scalargpuField& magSf, const scalargpuField& deltaCoeffs)
+{
+    mi_cubic_geometry g{};
+    g.lambda_dev = lambda.data(); g.mag_sf_dev = magSf.data(); g.delta_coeffs_dev = deltaCoeffs.data();
+    for (int d = 0; d < 3; ++d) g.sf_dev[d] = Sf.component(d).data();
+    return g;
+}
+}
+void fvc::cubicCorrectionFlux(scalargpuField& out, const lduAddressing& a, const scalargpuField* faceFlux, const scalargpuField& lambda, const vectorgpuField& Sf,
+                              const scalargpuField& magSf, const scalargpuField& deltaCoeffs, const scalargpuField& vf, const vectorgpuField& gradVf)
+{
+    const mi_cubic_geometry geo = cubicGeometry(lambda, Sf, magSf, deltaCoeffs);
+    const double* v[1] = {vf.data()};
+    const auto g = cmptData(gradVf);
+    double* o[1] = {out.data()};
+    miCheck(mi_cubic_correction(a.handle(), &geo, 1, v, g, faceFlux ? faceFlux->data() : nullptr, o), "cubic::correction");
+}
+void fvc::cubicCorrectionFlux(vectorgpuField& out, const lduAddressing& a, const scalargpuField* faceFlux, const scalargpuField& lambda, const vectorgpuField& Sf,
+                              const scalargpuField& magSf, const scalargpuField& deltaCoeffs, const vectorgpuField& vf, const vectorgpuField* const gradVf[3])
+{
+    const mi_cubic_geometry geo = cubicGeometry(lambda, Sf, magSf, deltaCoeffs);
+    const double *v[3], *g[9];
+    double* o[3];
+    for (int j = 0; j < 3; ++j) {
+        v[j] = vf.component(j).data(); o[j] = out.component(j).data();
+        for (int d = 0; d < 3; ++d) g[3 * j + d] = gradVf[j]->component(d).data();
+    }
+    miCheck(mi_cubic_correction(a.handle(), &geo, 3, v, g, faceFlux ? faceFlux->data() : nullptr, o), "cubic::correction");
+}
 void fvc::grad(vectorgpuField& g, const lduAddressing& a, const vectorgpuField& Sf, const scalargpuField& ssf, const scalargpuField& V)
 {
     miCheck(mi_gauss_grad(a.handle(), Sf.component(0).data(), Sf.component(1).data(), Sf.component(2).data(), ssf.data(), V.data(),
@@ -1116,6 +1146,51 @@ void patchLimitedWeights(scalargpuField& w, const fvPatchCells& p, const limited
                          const vectorgpuField* const nbrGradVf[3], const vectorgpuField& pDelta, scalargpuField* limiter)
 {
     patchLimitedCall(w, p, s, pCdWeights, pFaceFlux, limitedArrays(vf, gradVf), limitedArrays(nbrVf, nbrGradVf), pDelta, limiter);
+}
+
+filteredScheme filteredScheme::New(const std::string& scheme)
+{
+    mi_filtered_limiter l{};
+    miCheck(mi_filtered_parse(scheme.c_str(), &l), "limitedSurfaceInterpolationScheme::New");
+    return filteredScheme(l);
+}
+namespace {
+void filteredCall(scalargpuField& w, const lduAddressing& a, const filteredScheme& s, const scalargpuField& cdWeights, const scalargpuField& faceFlux,
+                  const limitedArrays& q, const vectorgpuField& C, scalargpuField* limiter)
+{
+    const double* c[3];
+    miCheck(mi_filtered_weights(a.handle(), &s.data(), cdWeights.data(), faceFlux.data(), q.phi, q.grad, comps(C, c), w.data(),
+                                limiter ? limiter->data() : nullptr), "LimitedScheme::weights (filtered)");
+}
+void patchFilteredCall(scalargpuField& w, const fvPatchCells& p, const filteredScheme& s, const scalargpuField& pCdWeights, const scalargpuField& pFaceFlux,
+                       const limitedArrays& own, const limitedArrays& nbr, const vectorgpuField& pDelta, scalargpuField* limiter)
+{
+    const double* d[3];
+    miCheck(mi_patch_filtered_weights(p.handle(), &s.data(), pCdWeights.data(), pFaceFlux.data(), own.phi, nbr.phi, own.grad, nbr.grad,
+                                      comps(pDelta, d), w.data(), limiter ? limiter->data() : nullptr), "LimitedScheme::weights (filtered, coupled patch)");
+}
+} // namespace
+void filteredWeights(scalargpuField& w, const lduAddressing& a, const filteredScheme& s, const scalargpuField& cdWeights, const scalargpuField& faceFlux,
+                     const scalargpuField& vf, const vectorgpuField& gradVf, const vectorgpuField& C, scalargpuField* limiter)
+{
+    filteredCall(w, a, s, cdWeights, faceFlux, limitedArrays(vf, gradVf), C, limiter);
+}
+void filteredWeights(scalargpuField& w, const lduAddressing& a, const filteredScheme& s, const scalargpuField& cdWeights, const scalargpuField& faceFlux,
+                     const vectorgpuField& vf, const vectorgpuField* const gradVf[3], const vectorgpuField& C, scalargpuField* limiter)
+{
+    filteredCall(w, a, s, cdWeights, faceFlux, limitedArrays(vf, gradVf), C, limiter);
+}
+void patchFilteredWeights(scalargpuField& w, const fvPatchCells& p, const filteredScheme& s, const scalargpuField& pCdWeights, const scalargpuField& pFaceFlux,
+                          const scalargpuField& vf, const scalargpuField& nbrVf, const vectorgpuField& gradVf, const vectorgpuField& nbrGradVf,
+                          const vectorgpuField& pDelta, scalargpuField* limiter)
+{
+    patchFilteredCall(w, p, s, pCdWeights, pFaceFlux, limitedArrays(vf, gradVf), limitedArrays(nbrVf, nbrGradVf), pDelta, limiter);
+}
+void patchFilteredWeights(scalargpuField& w, const fvPatchCells& p, const filteredScheme& s, const scalargpuField& pCdWeights, const scalargpuField& pFaceFlux,
+                          const vectorgpuField& vf, const vectorgpuField& nbrVf, const vectorgpuField* const gradVf[3],
+                          const vectorgpuField* const nbrGradVf[3], const vectorgpuField& pDelta, scalargpuField* limiter)
+{
+    patchFilteredCall(w, p, s, pCdWeights, pFaceFlux, limitedArrays(vf, gradVf), limitedArrays(nbrVf, nbrGradVf), pDelta, limiter);
 }
 
 // ---- Pstream: the parallel run as this path sees it -------------------------------------------------------------
