@@ -645,6 +645,53 @@ int mi_ls_vectors_destroy(mi_ls_vectors_t lsv);
 int mi_ls_vectors_fields(mi_ls_vectors_t lsv, double *const *p_out_dev, double *const *n_out_dev, double *const *bp_out_dev_or_null);
 int mi_ls_grad(mi_ls_vectors_t lsv, int32_t n_comp, const double *const *vf_dev, const double *const *bvalue_dev_or_null,
                double *const *grad_out_dev);
+/* ---- fvc::surfaceSum and fvc::reconstruct: a face flux back to a cell vector (finiteVolume/fvc/fvcReconstruct.C:45-84) ----
+ * The pEqn.H / UEqn.H line of the buoyant and multiphase solvers, U = HbyA + rAU*fvc::reconstruct((phig - p_rghEqn.flux())/rhorAUf).  The
+ * reference evaluates inv(surfaceSum(SfHat*mesh.Sf())) & surfaceSum(SfHat*ssf), SfHat = Sf/magSf, and re-forms and re-inverts the geometric
+ * tensor on every call; on a static mesh it is a constant, built here once per mesh.  Restated in tests/reconstruct_support.py, not pinned by
+ * a compiled reference.
+ * Order (fvcSurfaceIntegrate.C:262-360 with surfaceIntegrateFunctor<Type, false>, :40-132): a cell starts from +0.0 and meets its own faces
+ *   ascending, its neighbour-side faces in losort order, then its boundary faces by patch and by face within the patch
+ *   (surfaceIntegratePatchFunctor's running add).  Every term is ADDED on both sides, unlike surfaceIntegrate.  Coupled patches are added
+ *   like any other and no neighbour value is read: an attached (decomposed) matrix needs no communication.
+ * mi_surface_sum: out[c] = the sum of ssf[f] (MI_SURFACE_SUM) or of |ssf[f]| (MI_SURFACE_SUM_MAG: the fvc::surfaceSum(mag(phi)) of
+ *   CourantNo.H) over the internal faces of c in that order -- the row pass of mi_row_face_op kind 0 / kind 2 with lower NULL started from
+ *   +0.0 (no new kernel).  Boundary faces are then added per patch with mi_patch_add (fn 0 / fn 2), as for mi_gauss_grad.
+ * mi_reconstruct_create: SfHat_k = Sf_k/magSf (one division per component, internal and boundary faces alike), the geometric tensor
+ *   T_ab[c] = sum_f SfHat_a[f]*Sf_b[f] -- NINE components (T_xy and T_yx may differ in the last bit), each product rounded, then added in
+ *   the order above -- and its inverse in the device Field<tensor> form (tensorField.C:226-305): CALLER CELL 0 ALONE decides removeCmpts
+ *   (scale = magSqr(T[0]), the nine squares summed left to right xx xy xz yx yy yz zx zy zz; x is removed when T[0].xx/scale < SMALL = 1e-15,
+ *   likewise y and z; a cell 0 without faces gives 0/0, the comparison is false and nothing is removed; one 72-byte read-back); a removed
+ *   component adds the whole tensor (1,0,0, 0,0,0, 0,0,0) ... to every cell before the inversion and subtracts it after (the zeros are added
+ *   too: a -0.0 component becomes +0.0; this is what makes a one-cell-thick mesh with empty patches work); det as TensorI.H:552-560, left to
+ *   right, the inverse the nine cofactor expressions of :588-604, each divided by det.  Every operation is rounded on its own (DESIGN 3.5c /
+ *   3.5i); that the reference's device functor is not contracted is an ASSUMPTION.  sf_dev [x, y, z] / mag_sf_dev: internal
+ *   faces; b_*: boundary face fields, the patch-ordered concatenation of `boundary` (mi_grad_boundary_create; the patch kinds are not read).
+ *   boundary NULL: no boundary faces; otherwise it must outlive the handle.  The caller's geometry arrays are not kept.  The handle owns
+ *   SfHat (internal and boundary) and the nine inverse arrays: 24F + 72N + 24nb bytes, about 1.45 GB at 216^3.  After mesh motion: destroy
+ *   and create.  Works under the caller's numbering and under mi_addr_create_ordered, as mi_ls_grad does.
+ * mi_reconstruct_fields: copies the inverse out, nine cell arrays xx xy xz yx yy yz zx zy zz, and removeCmpts as three 0 / 1 host values
+ *   (removed_out_host may be NULL).
+ * mi_fvc_reconstruct: n_rhs = 1..4 fluxes in ONE row pass (out_dev[3*r + k] = component k of reconstruct(ssf_r)): s_k[c] = sum_f
+ *   SfHat_k[f]*ssf[f], the product rounded, then added, in the order above; out_a = row a of T^-1 dotted with s as the engine's dot product
+ *   (the same standing assumption): fma(R_az, s_z, fma(R_ax, s_x, R_ay*s_y)).  No division by V.  The pass reads 24 bytes
+ *   of geometry per face and performs no division.  b_ssf_dev[r]: the boundary fluxes, patch-ordered; may be NULL without boundary faces.
+ *   A cell without faces has T = 0 and det = 0: its inverse and output are not finite, which is legal.  The result's boundary values
+ *   (zeroGradient: mi_patch_internal_field; coupled patches through the neighbour-field entries) stay the caller's, as for every gradient.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): n_rhs outside 1..4, a mode other than the two, a missing array or one not
+ *   aligned for a double, a boundary built for another addressing, NULL boundary arrays while the boundary has faces, an output that aliases
+ *   an input or another output.  Zero cells: MI_OK, nothing written.  Zero internal faces is legal (the face arrays may be NULL).
+ * Out of scope: reconstruct of a surfaceVectorField (tensor result), fvc::reconstructMag, fvc::average, fvc::curl, a Courant-number entry
+ *   (it needs a max reduction), moving meshes. */
+typedef struct mi_reconstruct_s *mi_reconstruct_t;
+enum { MI_SURFACE_SUM, MI_SURFACE_SUM_MAG };
+int mi_surface_sum(mi_addr_t addr, int32_t mode, const double *ssf_dev, double *out_dev);
+int mi_reconstruct_create(mi_addr_t addr, mi_grad_boundary_t boundary_or_null, const double *const *sf_dev, const double *mag_sf_dev,
+                          const double *const *b_sf_dev, const double *b_mag_sf_dev, mi_reconstruct_t *out);
+int mi_reconstruct_destroy(mi_reconstruct_t rc);
+int mi_reconstruct_fields(mi_reconstruct_t rc, double *const *inv_out_dev, int32_t *removed_out_host);
+int mi_fvc_reconstruct(mi_reconstruct_t rc, int32_t n_rhs, const double *const *ssf_dev, const double *const *b_ssf_dev_or_null,
+                       double *const *out_dev);
 int mi_vec_axpby(mi_ctx_t ctx, int64_t n, double a, const double *x_dev, double b, const double *y_dev, double *out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),

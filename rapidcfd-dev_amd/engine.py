@@ -80,6 +80,7 @@ SYMBOLS = [
     "mi_sngrad_parse", "mi_sngrad_limited_correction_flux", "mi_patch_sngrad_limited_correction_flux",
     "mi_fvc_div_dev_tgrad", "mi_patch_gauss_grad_correct", "mi_patch_dev_tgrad_flux",
     "mi_grad_scheme_parse", "mi_ls_vectors_create", "mi_ls_vectors_destroy", "mi_ls_vectors_fields", "mi_ls_grad",
+    "mi_surface_sum", "mi_reconstruct_create", "mi_reconstruct_destroy", "mi_reconstruct_fields", "mi_fvc_reconstruct",
 ]
 
 
@@ -1234,6 +1235,46 @@ class LsVectors:
             self.h = C.c_void_p()
 
 
+SURFACE_SUM_MODES = ("sum", "mag")
+
+
+class Reconstruct:
+    """fvc::reconstruct's data of a mesh, built once on the device (mi_reconstruct_create): sf [x, y, z] / mag_sf internal-face arrays, b_sf /
+    b_mag_sf boundary-face arrays in the patch order of `boundary` (a GradBoundary or None: no boundary faces).  The handle keeps SfHat and
+    the inverse geometric tensor; the boundary must stay open as long as it is used.  After mesh motion: close and build again."""
+
+    def __init__(self, addr: Addressing, boundary, sf, mag_sf, b_sf=None, b_mag_sf=None):
+        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        self.addr, self.boundary = addr, boundary
+        self.h = C.c_void_p()
+        _chk(lib().mi_reconstruct_create(addr.h, boundary.h if boundary is not None else None, pv(sf), _ptr(mag_sf), pv(b_sf), _ptr(b_mag_sf),
+                                         C.byref(self.h)))
+
+    def fields(self, inv_out):
+        """copies the inverse tensor into nine cell arrays xx xy xz yx yy yz zx zy zz (mi_reconstruct_fields) -> removeCmpts as (x, y, z) of 0 / 1"""
+        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        removed = (C.c_int32 * 3)(0, 0, 0)
+        _chk(lib().mi_reconstruct_fields(self.h, pv(inv_out), removed))
+        return tuple(int(x) for x in removed)
+
+    def close(self):
+        if self.h:
+            lib().mi_reconstruct_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def reconstruct_create(addr: Addressing, boundary, sf, mag_sf, b_sf=None, b_mag_sf=None) -> Reconstruct:
+    return Reconstruct(addr, boundary, sf, mag_sf, b_sf, b_mag_sf)
+
+
+def reconstruct_fields(rc: Reconstruct, inv_out):
+    return rc.fields(inv_out)
+
+
+def reconstruct_destroy(rc: Reconstruct):
+    rc.close()
+
+
 class Assembly:
     """fvm::div / fvm::laplacian / negSumDiag / relax ... on caller-order arrays of an Addressing."""
 
@@ -1431,6 +1472,21 @@ class Assembly:
             raise MiError("ls_grad: the vectors were built for another addressing")
         pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
         _chk(lib().mi_ls_grad(lsv.h, C.c_int32(len(vf)), pv(vf), pv(bvalue), pv(grad_out)))
+
+    def surface_sum(self, ssf, out, mode="sum"):
+        """fvc::surfaceSum over the internal faces, every term added on both sides (mi_surface_sum): mode "sum" | "mag" (the sum of |ssf|, as
+        in CourantNo.H); the boundary faces follow per patch with Patch.add (fn 0 / fn 2)"""
+        m = SURFACE_SUM_MODES.index(mode) if mode in SURFACE_SUM_MODES else int(mode)
+        _chk(lib().mi_surface_sum(self.addr.h, C.c_int32(m), _ptr(ssf), _ptr(out)))
+
+    def reconstruct(self, rc, ssf, out, b_ssf=None):
+        """fvc::reconstruct of 1 to 4 face fluxes in one row pass (mi_fvc_reconstruct): rc a Reconstruct of this addressing, ssf one internal-
+        face array per flux, b_ssf one boundary-face array per flux (None without boundary faces), out three cell arrays per flux
+        (out[3*r + k] = component k of flux r's vector)"""
+        if rc.addr is not self.addr:
+            raise MiError("reconstruct: the handle was built for another addressing")
+        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
+        _chk(lib().mi_fvc_reconstruct(rc.h, C.c_int32(len(ssf)), pv(ssf), pv(b_ssf), pv(out)))
 
     def lust_weights(self, cd_weights, face_flux, w_out):
         """LUST weights 0.75*cd_weights + 0.25*pos(faceFlux) (LUST.H:104-110)"""

@@ -1472,6 +1472,57 @@ void fvc::leastSquaresGrad(vectorgpuField* const g[3], const leastSquaresVectors
     miCheck(mi_ls_grad(lsv.handle(), 3, v, bValue ? bv : nullptr, gr), "fvc::grad (leastSquares)");
 }
 
+// ---- fvc::surfaceSum and fvc::reconstruct ------------------------------------------------------------------------------------------------
+reconstructData::reconstructData(const lduAddressing& a, const gradBoundary* b, const vectorgpuField& Sf, const scalargpuField& magSf,
+                                 const vectorgpuField* bSf, const scalargpuField* bMagSf)
+    : h_(nullptr), nCells_(a.size())
+{
+    const auto s = cmptData(Sf);
+    const double* bs[3] = {nullptr, nullptr, nullptr};
+    if (bSf) for (int d = 0; d < 3; ++d) bs[d] = bSf->component(d).data();
+    miCheck(mi_reconstruct_create(a.handle(), b ? b->handle() : nullptr, s, magSf.data(), bSf ? bs : nullptr, bMagSf ? bMagSf->data() : nullptr, &h_),
+            "reconstructData::New");
+}
+reconstructData::~reconstructData() { if (h_) mi_reconstruct_destroy(h_); }
+void reconstructData::fields(scalargpuField* const inv[9], int removed[3]) const
+{
+    double* out[9];
+    for (int i = 0; i < 9; ++i) {
+        if (!inv[i] || inv[i]->size() != nCells_) FatalErrorIn("reconstructData::fields", "the fields have another size than the mesh's cells");
+        out[i] = inv[i]->data();
+    }
+    int32_t rm[3] = {0, 0, 0};
+    miCheck(mi_reconstruct_fields(h_, out, rm), "reconstructData::fields");
+    if (removed) for (int d = 0; d < 3; ++d) removed[d] = rm[d];
+}
+void fvc::surfaceSum(scalargpuField& out, const lduAddressing& a, const scalargpuField& ssf, bool mag)
+{
+    miCheck(mi_surface_sum(a.handle(), mag ? MI_SURFACE_SUM_MAG : MI_SURFACE_SUM, ssf.data(), out.data()), "fvc::surfaceSum");
+}
+void fvc::surfaceSumPatch(scalargpuField& out, const fvPatchCells& p, const scalargpuField& pssf, bool mag)
+{
+    if (p.size()) miCheck(mi_patch_add(p.handle(), pssf.data(), out.data(), mag ? 2 : 0), "fvc::surfaceSum (patch)");
+}
+void fvc::reconstruct(vectorgpuField& out, const reconstructData& rc, const scalargpuField& ssf, const scalargpuField* bssf)
+{
+    vectorgpuField* const o[1] = {&out};
+    const scalargpuField* const s[1] = {&ssf};
+    const scalargpuField* const b[1] = {bssf};
+    reconstruct(o, rc, 1, s, bssf ? b : nullptr);
+}
+void fvc::reconstruct(vectorgpuField* const out[], const reconstructData& rc, label n, const scalargpuField* const ssf[], const scalargpuField* const bssf[])
+{
+    if (n < 1 || n > 4) FatalErrorIn("fvc::reconstruct", "1 to 4 fluxes in one call");
+    const double *s[4], *b[4];
+    double* o[12];
+    for (label r = 0; r < n; ++r) {
+        s[r] = ssf[r]->data();
+        b[r] = bssf ? bssf[r]->data() : nullptr;
+        for (int k = 0; k < 3; ++k) o[3 * r + k] = out[r]->component(k).data();
+    }
+    miCheck(mi_fvc_reconstruct(rc.handle(), (int32_t)n, s, bssf ? b : nullptr, o), "fvc::reconstruct");
+}
+
 // ---- steadyState, localEuler, CoEuler and the bounded convection scheme ----
 namespace {
 mi_ddt_local_scheme parseLocal(const std::string& scheme, int kind, const char* name)
