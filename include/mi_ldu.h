@@ -693,6 +693,77 @@ int mi_reconstruct_fields(mi_reconstruct_t rc, double *const *inv_out_dev, int32
 int mi_fvc_reconstruct(mi_reconstruct_t rc, int32_t n_rhs, const double *const *ssf_dev, const double *const *b_ssf_dev_or_null,
                        double *const *out_dev);
 int mi_vec_axpby(mi_ctx_t ctx, int64_t n, double a, const double *x_dev, double b, const double *y_dev, double *out_dev);
+/* ---- explicit MULES: limiter, limit and explicitSolve (finiteVolume/fvMatrices/solvers/MULES/MULESTemplates.C:36-813, MULESFunctors.H;
+ *      DESIGN 3.5l) ----
+ * What every VOF solver of the reference (interFoam and its family) advances its phase fraction with.  The reference spends more than 60
+ * launches on one limit + explicitSolve; here it is one row pass to open, one row pass and one face pass per limiter iteration, one face
+ * pass to apply and one row pass to solve.  Restated in tests/mules_support.py, not pinned by a compiled reference.
+ * Order: a cell meets its own faces ascending, its neighbour-side faces in losort order, then its boundary faces by patch and by face, as
+ *   in mi_fvc_reconstruct.  Every operation is rounded on its own; max / min are (a > b) ? a : b and (a < b) ? a : b.
+ * mi_mules_create: the handle of one mesh.  boundary NULL: no boundary faces; otherwise it must outlive the handle.  Its
+ *   MI_GRAD_PATCH_COUPLED patches take the coupled rules (psiPf = patchNeighbourField; lambda from the face cell by the sign of phiCorr),
+ *   FIXES_VALUE and OTHER the rule of every other patch (limited only where phiBD + phiCorr > SMALL*SMALL).
+ *   patch_is_wedge_host_or_null[p] != 0 marks patch p a wedge patch (lambda = 0 after every iteration) whatever its kind.  The handle owns
+ *   six cell arrays -- the transformed bounds psiMaxn and psiMinn, sumPhip, mSumPhim, lambdap, lambdam -- and one byte and one label per
+ *   boundary face, so no call allocates.  mi_mules_work copies the six arrays out in that order.
+ * mi_mules_fields: r_delta_t, or r_delta_t_dev per cell (explicitLTSSolve) when not NULL; rho_dev and rho_old_dev, both or neither
+ *   (neither: geometricOneField); sp_dev / su_dev or NULL (zeroField); an absent term's operation is NOT performed (one*x = x,
+ *   x - zero = x, zero - x = -x), so a -0.0 survives where 0.0 - x would lose it.  vol_dev, psi_dev, psi_old_dev: cell arrays.
+ *   b_psi_dev: per boundary face the patchNeighbourField (coupled patches) or the patch value, patch-ordered as mi_limited_grad's bvalue.
+ * mi_mules_flux: the face arrays, each with its patch-ordered boundary twin b_*.  Which of them a call reads or writes is listed below;
+ *   the others are not looked at.
+ * mi_mules_begin: form MI_MULES_LIMITER takes phi_bd / phi_corr as given and leaves lambda as given (MULES::limiter's arguments);
+ *   MI_MULES_LIMIT reads phi and phi_psi and WRITES phi_bd = phi*(w*(psiP - psiN) + psiN) with w = pos(phi) (coupled patch faces:
+ *   phi*(w*psiInternal + (1 - w)*psiNeighbour); other patch faces: phi*psiPf), phi_corr = phi_psi - phi_bd and lambda = 1.  Either way it
+ *   then fills psiMaxn / psiMinn (from psi_min / psi_max over the NEIGHBOUR cells and the boundary psiPf -- the cell's own value is not
+ *   among them --, clamped by psi_max / psi_min, then the static-mesh expressions of :538-554), sumPhip and mSumPhim (from VSMALL;
+ *   `phiCorr > 0.0` picks the branch).
+ * mi_mules_iterate: n limiter iterations, lambda in place: sumlPhip / mSumlPhim over lambda*phi_corr, lambdam = max(min((sumlPhip +
+ *   psiMaxn)/(mSumPhim - SMALL), 1), 0), lambdap = max(min((mSumlPhim + psiMinn)/(sumPhip + SMALL), 1), 0), then per face min(lambda, ...)
+ *   by the sign of phi_corr.  The syncFaceList(minOp) that ends an iteration needs the other side of a coupled face and is the CALLER's:
+ *   on a boundary with coupled patches iterate one at a time and take the minimum of the two sides (mi_vec_min) after each.
+ * mi_mules_apply: out = phi_bd + lambda*phi_corr, or lambda*phi_corr with return_corr, the product rounded first.  out may be the array
+ *   that was phi_psi (the reference overwrites phiPsi).
+ * mi_mules_limiter = begin(MI_MULES_LIMITER) + iterate(n_limiter_iter); mi_mules_limit = begin(MI_MULES_LIMIT) + iterate + apply; 3 is
+ *   what MULES::explicitSolve passes.  mi_mules_explicit_solve: psi_out = (rho_old*psi_old*rDeltaT + Su - surfaceIntegrate(phi_psi))
+ *   /(rho*rDeltaT - Sp), surfaceIntegrate being own +, neighbour side -, boundary +, then /V.  It needs no begin and reads no psi_dev, which may be NULL or psi_out itself (the reference overwrites psi).
+ * mi_vec_min: out = (x < y) ? x : y element by element (out may alias x or y): minOp over the two patch slices of a one-rank cyclic pair.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): a handle or boundary of another addressing, missing arrays, NULL boundary
+ *   arrays while the boundary has faces, an array not aligned for a double, an output that aliases an input or another output, rho
+ *   without rho_old (or the reverse), n < 0, iterate or apply before begin, an unknown form, and -- on a boundary with coupled patches --
+ *   iterate with n > 1, mi_mules_limiter and mi_mules_limit.  Zero cells: MI_OK.  Zero internal faces is legal (the face arrays may be NULL).
+ * Out of scope: CMULES (correct, limiterCorr -- it can reuse the iteration's two kernels), IMULES, limitSum, moving meshes (Vsc0), the
+ *   minOp sync across ranks, interfaceCompression. */
+typedef struct mi_mules_s *mi_mules_t;
+enum { MI_MULES_LIMITER, MI_MULES_LIMIT };
+typedef struct mi_mules_fields {
+    double r_delta_t;
+    const double *r_delta_t_dev;              /* per cell, or NULL: r_delta_t */
+    const double *rho_dev, *rho_old_dev;      /* both or neither */
+    const double *sp_dev, *su_dev;            /* each or NULL */
+    const double *vol_dev, *psi_dev, *psi_old_dev;
+    const double *b_psi_dev;
+    double psi_max, psi_min;
+} mi_mules_fields;
+typedef struct mi_mules_flux {
+    const double *phi_dev, *b_phi_dev;          /* begin(MI_MULES_LIMIT): read */
+    const double *phi_psi_dev, *b_phi_psi_dev;  /* begin(MI_MULES_LIMIT): read */
+    double *phi_bd_dev, *b_phi_bd_dev;          /* begin(MI_MULES_LIMIT): written; otherwise read */
+    double *phi_corr_dev, *b_phi_corr_dev;      /* likewise */
+    double *lambda_dev, *b_lambda_dev;          /* begin(MI_MULES_LIMIT): written; iterate: read and written; otherwise read */
+    double *out_dev, *b_out_dev;                /* apply: written */
+} mi_mules_flux;
+int mi_mules_create(mi_addr_t addr, mi_grad_boundary_t boundary_or_null, const int32_t *patch_is_wedge_host_or_null, mi_mules_t *out);
+int mi_mules_destroy(mi_mules_t mules);
+int mi_mules_work(mi_mules_t mules, double *const *out_dev);
+int mi_mules_begin(mi_mules_t mules, int32_t form, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_iterate(mi_mules_t mules, int32_t n, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_apply(mi_mules_t mules, int32_t return_corr, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_limiter(mi_mules_t mules, int32_t n_limiter_iter, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_limit(mi_mules_t mules, int32_t n_limiter_iter, int32_t return_corr, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_explicit_solve(mi_mules_t mules, const mi_mules_fields *fields, const double *phi_psi_dev, const double *b_phi_psi_dev,
+                            double *psi_out_dev);
+int mi_vec_min(mi_ctx_t ctx, int64_t n, const double *x_dev, const double *y_dev, double *out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

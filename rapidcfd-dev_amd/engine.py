@@ -81,6 +81,8 @@ SYMBOLS = [
     "mi_fvc_div_dev_tgrad", "mi_patch_gauss_grad_correct", "mi_patch_dev_tgrad_flux",
     "mi_grad_scheme_parse", "mi_ls_vectors_create", "mi_ls_vectors_destroy", "mi_ls_vectors_fields", "mi_ls_grad",
     "mi_surface_sum", "mi_reconstruct_create", "mi_reconstruct_destroy", "mi_reconstruct_fields", "mi_fvc_reconstruct",
+    "mi_mules_create", "mi_mules_destroy", "mi_mules_work", "mi_mules_begin", "mi_mules_iterate", "mi_mules_apply", "mi_mules_limiter", "mi_mules_limit",
+    "mi_mules_explicit_solve", "mi_vec_min",
 ]
 
 
@@ -1275,6 +1277,91 @@ def reconstruct_destroy(rc: Reconstruct):
     rc.close()
 
 
+class MulesFields(C.Structure):
+    """mi_mules_fields (include/mi_ldu.h)"""
+    _fields_ = [("r_delta_t", C.c_double), ("r_delta_t_dev", C.c_void_p), ("rho_dev", C.c_void_p), ("rho_old_dev", C.c_void_p),
+                ("sp_dev", C.c_void_p), ("su_dev", C.c_void_p), ("vol_dev", C.c_void_p), ("psi_dev", C.c_void_p), ("psi_old_dev", C.c_void_p),
+                ("b_psi_dev", C.c_void_p), ("psi_max", C.c_double), ("psi_min", C.c_double)]
+
+
+class MulesFlux(C.Structure):
+    """mi_mules_flux (include/mi_ldu.h)"""
+    _fields_ = [(name, C.c_void_p) for name in ("phi_dev", "b_phi_dev", "phi_psi_dev", "b_phi_psi_dev", "phi_bd_dev", "b_phi_bd_dev", "phi_corr_dev",
+                                                "b_phi_corr_dev", "lambda_dev", "b_lambda_dev", "out_dev", "b_out_dev")]
+
+
+MULES_FORMS = ("limiter", "limit")      # MI_MULES_LIMITER, MI_MULES_LIMIT
+
+
+def mules_fields(vol, psi, psi_old, r_delta_t=1.0, b_psi=None, psi_max=1.0, psi_min=0.0, rho=None, rho_old=None, sp=None, su=None):
+    """mi_mules_fields: r_delta_t a number, or a cell tensor (explicitLTSSolve); rho and rho_old both or neither; sp / su or None; b_psi the
+    patch-ordered boundary values (patchNeighbourField on coupled patches).  Returns the structure; it keeps the tensors alive"""
+    lts = not isinstance(r_delta_t, (int, float))
+    f = MulesFields(0.0 if lts else float(r_delta_t), _ptr(r_delta_t) if lts else None, _ptr(rho), _ptr(rho_old), _ptr(sp), _ptr(su), _ptr(vol),
+                    _ptr(psi), _ptr(psi_old), _ptr(b_psi), float(psi_max), float(psi_min))
+    f._keep = (r_delta_t, rho, rho_old, sp, su, vol, psi, psi_old, b_psi)
+    return f
+
+
+def mules_flux(**arrays):
+    """mi_mules_flux from keywords: phi, phi_psi, phi_bd, phi_corr, lambda_, out and their boundary twins b_phi, ... (None: not given)"""
+    x = MulesFlux()
+    for key, t in arrays.items():
+        name = key.rstrip("_") + "_dev"
+        if not hasattr(x, name):
+            raise MiError("mules_flux: unknown array '%s'" % key)
+        setattr(x, name, _ptr(t))
+    x._keep = arrays
+    return x
+
+
+class Mules:
+    """Explicit MULES on one mesh (mi_mules_create): boundary a GradBoundary or None (no boundary faces), wedge one flag per patch or None.
+    The handle owns the six cell work arrays, so no call allocates; the boundary must stay open as long as it is used.  fields is a
+    mules_fields(...), flux a mules_flux(...)."""
+
+    def __init__(self, addr: Addressing, boundary=None, wedge=None):
+        self.addr, self.boundary = addr, boundary
+        self.h = C.c_void_p()
+        w = None if wedge is None else (C.c_int32 * max(len(wedge), 1))(*[int(bool(x)) for x in wedge])
+        _chk(lib().mi_mules_create(addr.h, boundary.h if boundary is not None else None, w, C.byref(self.h)))
+
+    def work(self, out):
+        """copies psiMaxn, psiMinn (transformed), sumPhip, mSumPhim, lambdap, lambdam into six cell arrays (mi_mules_work)"""
+        pv = None if out is None else (C.c_void_p * 6)(*[_ptr(x) for x in out])
+        _chk(lib().mi_mules_work(self.h, pv))
+
+    def begin(self, form, fields, flux):
+        f = MULES_FORMS.index(form) if form in MULES_FORMS else int(form)
+        _chk(lib().mi_mules_begin(self.h, C.c_int32(f), C.byref(fields) if fields is not None else None, C.byref(flux) if flux is not None else None))
+
+    def iterate(self, n, fields, flux):
+        _chk(lib().mi_mules_iterate(self.h, C.c_int32(n), C.byref(fields) if fields is not None else None, C.byref(flux) if flux is not None else None))
+
+    def apply(self, return_corr, fields, flux):
+        _chk(lib().mi_mules_apply(self.h, C.c_int32(int(bool(return_corr))), C.byref(fields) if fields is not None else None,
+                                  C.byref(flux) if flux is not None else None))
+
+    def limiter(self, fields, flux, n_limiter_iter=3):
+        """MULES::limiter: begin("limiter") + iterate(n_limiter_iter)"""
+        _chk(lib().mi_mules_limiter(self.h, C.c_int32(n_limiter_iter), C.byref(fields) if fields is not None else None,
+                                    C.byref(flux) if flux is not None else None))
+
+    def limit(self, fields, flux, n_limiter_iter=3, return_corr=False):
+        """MULES::limit: begin("limit") + iterate(n_limiter_iter) + apply(return_corr)"""
+        _chk(lib().mi_mules_limit(self.h, C.c_int32(n_limiter_iter), C.c_int32(int(bool(return_corr))), C.byref(fields) if fields is not None else None,
+                                  C.byref(flux) if flux is not None else None))
+
+    def explicit_solve(self, fields, phi_psi, psi_out, b_phi_psi=None):
+        """MULES::explicitSolve(rDeltaT, rho, psi, phiPsi, Sp, Su): the new psi into psi_out"""
+        _chk(lib().mi_mules_explicit_solve(self.h, C.byref(fields) if fields is not None else None, _ptr(phi_psi), _ptr(b_phi_psi), _ptr(psi_out)))
+
+    def close(self):
+        if self.h:
+            lib().mi_mules_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Assembly:
     """fvm::div / fvm::laplacian / negSumDiag / relax ... on caller-order arrays of an Addressing."""
 
@@ -1487,6 +1574,37 @@ class Assembly:
             raise MiError("reconstruct: the handle was built for another addressing")
         pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
         _chk(lib().mi_fvc_reconstruct(rc.h, C.c_int32(len(ssf)), pv(ssf), pv(b_ssf), pv(out)))
+
+    def _mules(self, mu):
+        if mu.addr is not self.addr:
+            raise MiError("mules: the handle was built for another addressing")
+        return mu
+
+    def mules_begin(self, mu, form, fields, flux):
+        """opens a MULES limiter on a Mules of this addressing (mi_mules_begin): form "limiter" (phi_bd, phi_corr and lambda as given) or
+        "limit" (phi and phi_psi given; phi_bd, phi_corr and lambda = 1 written)"""
+        self._mules(mu).begin(form, fields, flux)
+
+    def mules_iterate(self, mu, n, fields, flux):
+        """n limiter iterations, lambda in place (mi_mules_iterate); with coupled patches one at a time, vec_min on the two sides after each"""
+        self._mules(mu).iterate(n, fields, flux)
+
+    def mules_apply(self, mu, return_corr, fields, flux):
+        """out = phi_bd + lambda*phi_corr, or lambda*phi_corr with return_corr (mi_mules_apply)"""
+        self._mules(mu).apply(return_corr, fields, flux)
+
+    def mules_limiter(self, mu, fields, flux, n_limiter_iter=3):
+        self._mules(mu).limiter(fields, flux, n_limiter_iter)
+
+    def mules_limit(self, mu, fields, flux, n_limiter_iter=3, return_corr=False):
+        self._mules(mu).limit(fields, flux, n_limiter_iter, return_corr)
+
+    def mules_explicit_solve(self, mu, fields, phi_psi, psi_out, b_phi_psi=None):
+        self._mules(mu).explicit_solve(fields, phi_psi, psi_out, b_phi_psi)
+
+    def vec_min(self, x, y, out):
+        """out = min(x, y) element by element, out may alias either (mi_vec_min): minOp over the two sides of a cyclic pair"""
+        _chk(lib().mi_vec_min(self.addr.ctx.h, C.c_int64(x.numel()), _ptr(x), _ptr(y), _ptr(out)))
 
     def lust_weights(self, cd_weights, face_flux, w_out):
         """LUST weights 0.75*cd_weights + 0.25*pos(faceFlux) (LUST.H:104-110)"""

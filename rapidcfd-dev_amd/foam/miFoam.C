@@ -1523,6 +1523,76 @@ void fvc::reconstruct(vectorgpuField* const out[], const reconstructData& rc, la
     miCheck(mi_fvc_reconstruct(rc.handle(), (int32_t)n, s, bssf ? b : nullptr, o), "fvc::reconstruct");
 }
 
+// ---- explicit MULES ---------------------------------------------------------------------------------------------------------------------
+mulesData::mulesData(const lduAddressing& a, const gradBoundary* b, const std::vector<bool>& wedge)
+    : h_(nullptr), nFaces_((label)a.lowerAddrHost().size()), nBFaces_(0)
+{
+    std::vector<int32_t> w(wedge.begin(), wedge.end());
+    miCheck(mi_mules_create(a.handle(), b ? b->handle() : nullptr, w.empty() ? nullptr : w.data(), &h_), "mulesData::New");
+}
+mulesData::~mulesData() { if (h_) mi_mules_destroy(h_); }
+scalargpuField& mulesData::work(int i) const
+{
+    if (!work_[i]) work_[i].reset(new scalargpuField(i % 2 == 0 ? nFaces_ : nBFaces_));
+    return *work_[i];
+}
+namespace {
+mi_mules_fields mulesFields(const MULES::rDeltaTType& rDeltaT, const MULES::rhoType& rho, const MULES::volField& psi, const scalargpuField* Sp,
+                            const scalargpuField* Su, const scalargpuField& V, scalar psiMax, scalar psiMin)
+{
+    mi_mules_fields f{};
+    f.r_delta_t = rDeltaT.value; f.r_delta_t_dev = rDeltaT.field ? rDeltaT.field->data() : nullptr;
+    f.rho_dev = rho.field ? rho.field->data() : nullptr; f.rho_old_dev = rho.oldTime ? rho.oldTime->data() : nullptr;
+    f.sp_dev = Sp ? Sp->data() : nullptr; f.su_dev = Su ? Su->data() : nullptr;
+    f.vol_dev = V.data(); f.psi_dev = psi.field ? psi.field->data() : nullptr; f.psi_old_dev = psi.oldTime ? psi.oldTime->data() : nullptr;
+    f.b_psi_dev = psi.boundary ? psi.boundary->data() : nullptr;
+    f.psi_max = psiMax; f.psi_min = psiMin;
+    return f;
+}
+double* dataOf(scalargpuField* f) { return f ? f->data() : nullptr; }
+}
+void MULES::limiter(const mulesData& m, surfaceField allLambda, const rDeltaTType& rDeltaT, const rhoType& rho, const volField& psi,
+                    const surfaceField& phiBD, const surfaceField& phiCorr, const scalargpuField* Sp, const scalargpuField* Su, const scalargpuField& V,
+                    scalar psiMax, scalar psiMin, label nLimiterIter)
+{
+    const mi_mules_fields f = mulesFields(rDeltaT, rho, psi, Sp, Su, V, psiMax, psiMin);
+    mi_mules_flux x{};
+    x.phi_bd_dev = dataOf(phiBD.field); x.b_phi_bd_dev = dataOf(phiBD.boundary);
+    x.phi_corr_dev = dataOf(phiCorr.field); x.b_phi_corr_dev = dataOf(phiCorr.boundary);
+    x.lambda_dev = dataOf(allLambda.field); x.b_lambda_dev = dataOf(allLambda.boundary);
+    miCheck(mi_mules_limiter(m.handle(), (int32_t)nLimiterIter, &f, &x), "MULES::limiter");
+}
+void MULES::limit(const mulesData& m, const rDeltaTType& rDeltaT, const rhoType& rho, const volField& psi, const surfaceField& phi, surfaceField phiPsi,
+                  const scalargpuField* Sp, const scalargpuField* Su, const scalargpuField& V, scalar psiMax, scalar psiMin, label nLimiterIter,
+                  bool returnCorr)
+{
+    const mi_mules_fields f = mulesFields(rDeltaT, rho, psi, Sp, Su, V, psiMax, psiMin);
+    const bool hasB = phiPsi.boundary != nullptr;
+    mi_mules_flux x{};
+    x.phi_dev = dataOf(phi.field); x.b_phi_dev = dataOf(phi.boundary);
+    x.phi_psi_dev = dataOf(phiPsi.field); x.b_phi_psi_dev = dataOf(phiPsi.boundary);
+    x.phi_bd_dev = m.work(0).data(); x.phi_corr_dev = m.work(2).data(); x.lambda_dev = m.work(4).data();
+    if (hasB) {
+        const label nb = phiPsi.boundary->size();
+        for (int i = 1; i < 6; i += 2) if (m.work(i).size() != nb) m.work(i) = scalargpuField(nb);
+        x.b_phi_bd_dev = m.work(1).data(); x.b_phi_corr_dev = m.work(3).data(); x.b_lambda_dev = m.work(5).data();
+    }
+    x.out_dev = dataOf(phiPsi.field); x.b_out_dev = dataOf(phiPsi.boundary);    // the reference overwrites phiPsi
+    miCheck(mi_mules_limit(m.handle(), (int32_t)nLimiterIter, returnCorr ? 1 : 0, &f, &x), "MULES::limit");
+}
+void MULES::explicitSolve(const mulesData& m, const rDeltaTType& rDeltaT, const rhoType& rho, const volField& psi, const surfaceField& phiPsi,
+                          const scalargpuField* Sp, const scalargpuField* Su, const scalargpuField& V)
+{
+    const mi_mules_fields f = mulesFields(rDeltaT, rho, psi, Sp, Su, V, 0, 0);
+    miCheck(mi_mules_explicit_solve(m.handle(), &f, dataOf(phiPsi.field), dataOf(phiPsi.boundary), dataOf(psi.field)), "MULES::explicitSolve");
+}
+void MULES::explicitSolve(const mulesData& m, const rDeltaTType& rDeltaT, const rhoType& rho, const volField& psi, const surfaceField& phi,
+                          surfaceField phiPsi, const scalargpuField* Sp, const scalargpuField* Su, const scalargpuField& V, scalar psiMax, scalar psiMin)
+{
+    limit(m, rDeltaT, rho, psi, phi, phiPsi, Sp, Su, V, psiMax, psiMin, 3, false);
+    explicitSolve(m, rDeltaT, rho, psi, phiPsi, Sp, Su, V);
+}
+
 // ---- steadyState, localEuler, CoEuler and the bounded convection scheme ----
 namespace {
 mi_ddt_local_scheme parseLocal(const std::string& scheme, int kind, const char* name)
