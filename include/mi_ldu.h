@@ -732,8 +732,7 @@ int mi_vec_axpby(mi_ctx_t ctx, int64_t n, double a, const double *x_dev, double 
  *   arrays while the boundary has faces, an array not aligned for a double, an output that aliases an input or another output, rho
  *   without rho_old (or the reverse), n < 0, iterate or apply before begin, an unknown form, and -- on a boundary with coupled patches --
  *   iterate with n > 1, mi_mules_limiter and mi_mules_limit.  Zero cells: MI_OK.  Zero internal faces is legal (the face arrays may be NULL).
- * Out of scope: CMULES (correct, limiterCorr -- it can reuse the iteration's two kernels), IMULES, limitSum, moving meshes (Vsc0), the
- *   minOp sync across ranks, interfaceCompression. */
+ * Out of scope: IMULES, limitSum, moving meshes (Vsc0), the minOp sync across ranks.  CMULES and interfaceCompression: below. */
 typedef struct mi_mules_s *mi_mules_t;
 enum { MI_MULES_LIMITER, MI_MULES_LIMIT };
 typedef struct mi_mules_fields {
@@ -764,6 +763,57 @@ int mi_mules_limit(mi_mules_t mules, int32_t n_limiter_iter, int32_t return_corr
 int mi_mules_explicit_solve(mi_mules_t mules, const mi_mules_fields *fields, const double *phi_psi_dev, const double *b_phi_psi_dev,
                             double *psi_out_dev);
 int mi_vec_min(mi_ctx_t ctx, int64_t n, const double *x_dev, const double *y_dev, double *out_dev);
+/* ---- semi-implicit MULES: limiterCorr, limitCorr and correct (CMULESTemplates.C:35-758, MULESFunctors.H) ----
+ * What interFoam's alphaEqn.H runs with `MULESCorr yes`: MULES::correct(alpha1, phiAlphaUn, phiAlphaCorr, 1, 0) is mi_mules_limit_corr then
+ * mi_mules_correct.  The handle, the fields, the flux arrays, the order of a cell's faces and the rounding rules are explicit MULES'; what
+ * differs from it:
+ * mi_mules_begin_corr: reads phi_corr, b_phi_corr, psi, b_psi, vol, rho, sp, su and rDeltaT; psi_old_dev, rho_old_dev, phi_bd and phi_psi
+ *   are not looked at and may be NULL (rho without rho_old is legal here).  psiMaxn / psiMinn start from psi_min / psi_max and run over the
+ *   NEIGHBOUR cells' psi and the boundary psiPf (the cell's own value is not among them); sumPhip / mSumPhim from VSMALL, `phiCorr > 0.0`
+ *   picks the branch; there is no phiBD.  Clamp: psiMaxn = min(psiMaxn + e, psi_max), psiMinn = max(psiMinn - e, psi_min) with
+ *   e = extrema_coeff*(psi_max - psi_min) formed once on the host; the addition is performed even when e is 0.0 (-0.0 + 0.0 = +0.0).  Then
+ *   psiMaxn = V*((rho*rDeltaT - Sp)*psiMaxn - Su - rho*psi*rDeltaT), psiMinn = V*(Su - (rho*rDeltaT - Sp)*psiMinn + rho*psi*rDeltaT), one
+ *   rounding per written operator left to right, the old-value term (rho*psi)*rDeltaT of the CURRENT psi and rho.  Form
+ *   MI_MULES_CORR_LIMIT also writes lambda = 1; MI_MULES_CORR_LIMITER leaves lambda as given.
+ * The handle remembers which begin opened it.  After mi_mules_begin_corr, mi_mules_iterate limits a face of a patch that is neither
+ *   coupled nor wedge where the BOUNDARY VALUE OF phi (b_phi_dev) is > SMALL*SMALL (patchLambdaPfCMULESFunctor), not phiBD + phiCorr; it
+ *   reads phi_corr, b_phi_corr and b_phi and never phi_dev or phi_bd.  mi_mules_apply then takes return_corr = 1 only (there is no phiBD)
+ *   and accepts out_dev == phi_corr_dev and b_out_dev == b_phi_corr_dev (limitCorr's phiCorr *= lambda).  mi_mules_work is unchanged.
+ * mi_mules_limiter_corr = begin_corr(MI_MULES_CORR_LIMITER) + iterate(n); mi_mules_limit_corr = begin_corr(MI_MULES_CORR_LIMIT) +
+ *   iterate(n) + the product into phi_corr / b_phi_corr in place (out_dev / b_out_dev are not looked at).
+ * mi_mules_correct: psi = (rho*psi*rDeltaT + Su - surfaceIntegrate(phi_corr))/(rho*rDeltaT - Sp) in place in psi_inout_dev; needs no begin;
+ *   the fields' psi_dev, psi_old_dev, rho_old_dev and b_psi_dev are not looked at (each may be NULL).  psi_inout is the one permitted alias.
+ * Refused as explicit MULES refuses, and: extrema_coeff negative or not finite, an unknown form, b_phi_dev NULL while the boundary has a
+ *   face on a patch that is neither coupled nor wedge, return_corr = 0 after begin_corr.  Coupled patches: iterate(n > 1) and the two
+ *   conveniences are refused, the minOp sync is the caller's.  No call allocates; no atomics; the same bits on every run. */
+enum { MI_MULES_CORR_LIMITER, MI_MULES_CORR_LIMIT };
+int mi_mules_begin_corr(mi_mules_t mules, int32_t form, double extrema_coeff, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_limiter_corr(mi_mules_t mules, int32_t n_limiter_iter, double extrema_coeff, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_limit_corr(mi_mules_t mules, int32_t n_limiter_iter, double extrema_coeff, const mi_mules_fields *fields, const mi_mules_flux *flux);
+int mi_mules_correct(mi_mules_t mules, const mi_mules_fields *fields, const double *phi_corr_dev, const double *b_phi_corr_dev, double *psi_inout_dev);
+/* ---- the interfaceCompression scheme and alphaEqn.H's compression flux (interfaceCompression.H:58-77, PhiScheme.C:52-197) ----
+ * mi_interface_compression_parse: MI_OK for exactly "interfaceCompression" (PhiScheme takes no coefficient).
+ * mi_interface_compression_weights: limiter = min(max(1 - max(sqr(1 - 4*aP*(1 - aP)), sqr(1 - 4*aN*(1 - aN))), 0), 1) from the two cell
+ *   values alone, weights = limiter*cdw + (1 - limiter)*pos(faceFlux), the blend of mi_limited_weights; one face pass, no gradient and no
+ *   centres.  Rounding (the device-functor rule of mi_limited_weights): 1 - (4*a)*(1 - a) is fma(-(4*a), 1 - a, 1), sqr a plain product,
+ *   max / min the ternaries, the weights fma(limiter, cdw, (1 - limiter)*pos).  The flux is the volumetric one (the rho-weighted branch of
+ *   PhiScheme.C:87-94 is the caller's).  Non-coupled patches take limiter 1: no call.  The patch form is for a COUPLED patch: alpha_dev the
+ *   cell field (patchInternalField through the patch's faceCells), nbr_alpha_dev the patchNeighbourField.
+ * mi_alpha_compression_flux: out = fvc::flux(-fvc::flux(-phir, alpha2, interfaceCompression), alpha1, interfaceCompression) with
+ *   alpha2 = 1.0 - alpha1 per cell, in one face pass, with the bits of the unfused sequence: n = -phir; w2 = weights(cdw, n, alpha2);
+ *   g = n*interpolate(w2, alpha2); m = -g; w1 = weights(cdw, m, alpha1); out = m*interpolate(w1, alpha1); interpolate the rule of
+ *   mi_face_interpolate, on a coupled patch w*P + (1 - w)*N with every operator rounded.
+ * Refused: missing arrays, an output that aliases an input or the other output, face arrays not aligned to 16 bytes (patch arrays and
+ *   cell arrays: 8). */
+int mi_interface_compression_parse(const char *scheme);
+int mi_interface_compression_weights(mi_addr_t addr, const double *cd_weights_dev, const double *face_flux_dev, const double *alpha_dev,
+                                     double *weights_out_dev, double *limiter_out_dev_or_null);
+int mi_patch_interface_compression_weights(mi_patch_t patch, const double *patch_cd_weights_dev, const double *patch_flux_dev,
+                                           const double *alpha_dev, const double *nbr_alpha_dev,
+                                           double *weights_out_dev, double *limiter_out_dev_or_null);
+int mi_alpha_compression_flux(mi_addr_t addr, const double *cd_weights_dev, const double *phir_dev, const double *alpha1_dev, double *out_dev);
+int mi_patch_alpha_compression_flux(mi_patch_t patch, const double *patch_cd_weights_dev, const double *patch_phir_dev,
+                                    const double *alpha1_dev, const double *nbr_alpha1_dev, double *out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

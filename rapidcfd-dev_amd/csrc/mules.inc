@@ -1,4 +1,5 @@
-// mules.inc -- explicit MULES: limiter, limit and explicitSolve (included by engine.hip after reconstruct.inc; DESIGN 3.5l).
+// mules.inc -- explicit MULES: limiter, limit and explicitSolve (included by engine.hip after reconstruct.inc; DESIGN 3.5l), and below them
+// semi-implicit MULES (limiterCorr, limitCorr, correct) and the interfaceCompression scheme with the compression flux (DESIGN 3.5m).
 //
 //   limiter        MULESTemplates.C:381-745 with MULESFunctors.H: per cell the bounds over the NEIGHBOUR values (the cell's own value is not
 //                  among them) and the boundary psiPf, sumPhiBD, sumPhip / mSumPhim from VSMALL with `phiCorr > 0.0` choosing the branch, the
@@ -30,6 +31,7 @@ struct MuRow {
 struct MuCells {
     const double *rdtField, *rho, *rhoOld, *sp, *su, *vol, *psi, *psiOld, *bpsi;
     double rdt, psiMax, psiMin;
+    double ec;                                        // CMULES: extremaCoeff*(psiMax - psiMin), formed once on the host
     double *maxn, *minn, *sumPhip, *mSumPhim, *lambdap, *lambdam;
     const uint8_t* bKind;
     const int32_t* bCell;
@@ -179,7 +181,10 @@ __global__ __launch_bounds__(BS) void k_mules_sums(const MuArgs a)
 }
 
 // one limiter iteration's face pass (lambdaIfMULESFunctor and the three patch branches of :672-741), lambda in place: the internal faces
-// in XCD-aware chunks as k_limited_weights, then the boundary faces grid-stride in the same launch
+// in XCD-aware chunks as k_limited_weights, then the boundary faces grid-stride in the same launch.  CORR: the one rule CMULES changes
+// (patchLambdaPfCMULESFunctor, CMULESTemplates.C:345-371): a face of a patch that is neither coupled nor wedge is limited where the boundary
+// value of phi is > SMALL*SMALL, not phiBD + phiCorr; phiBD is then never read
+template <bool CORR>
 __global__ __launch_bounds__(256) void k_mules_lambda(const MuArgs a)
 {
     const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
@@ -193,13 +198,61 @@ __global__ __launch_bounds__(256) void k_mules_lambda(const MuArgs a)
         const int kind = q.bKind[i];
         if (kind == MU_WEDGE) { x.blambda[i] = 0.0; continue; }
         const double corr = x.bphiCorr[i];
-        if (kind != MU_COUPLED && !((x.bphiBD[i] + corr) > MU_SMALL * MU_SMALL)) continue;   // limit outlet faces only
+        if (kind != MU_COUPLED && !((CORR ? x.bphi[i] : x.bphiBD[i] + corr) > MU_SMALL * MU_SMALL)) continue;   // limit outlet faces only
         const int c = q.bCell[i];
         x.blambda[i] = mu_min(x.blambda[i], corr > 0.0 ? q.lambdap[c] : q.lambdam[c]);
     }
 }
 
-// phiBD + lambda*phiCorr, or lambda*phiCorr with returnCorr: internal and boundary faces in one launch
+// the opening row pass of limiterCorr (limiterCMULESFunctor, patchMinMaxCMULESFunctor, CMULESTemplates.C:160-343, :441-517): one staged
+// array, phiCorr.  As the explicit pass the bounds run over the NEIGHBOUR cells' psi and the boundary psiPf from the global psiMin / psiMax
+// (the cell's own value is not among them) and sumPhip / mSumPhim from VSMALL; there is no phiBD.  The clamp adds q.ec even when it is 0.0
+// (-0.0 + 0.0 = +0.0), and the old-value term is (rho*psi)*rDeltaT of the CURRENT psi and rho.  ONES (limitCorr): lambda = 1 as well, the
+// owner side writes its own faces and a cell its boundary faces.
+template <int BS, bool ONES, bool LTS>
+__global__ __launch_bounds__(BS) void k_mules_corr_bounds(const MuArgs a)
+{
+    const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
+    const double* const src[1] = {x.phiCorr};
+    double hi = q.psiMin, lo = q.psiMax, sp = MU_VSMALL, sm = MU_VSMALL;
+    mu_rows<BS, 1>(r, src, [](int) {},
+        [&](int, int f, const double (&v)[1]) {
+            const double pn = q.psi[r.up[f]];
+            if (ONES) x.lambda[f] = 1.0;
+            hi = mu_max(hi, pn); lo = mu_min(lo, pn);
+            if (v[0] > 0.0) sp = sp + v[0]; else sm = sm - v[0];
+        },
+        [&](int, int f, const double (&v)[1]) {
+            const double po = q.psi[r.lo[f]];
+            hi = mu_max(hi, po); lo = mu_min(lo, po);
+            if (v[0] > 0.0) sm = sm + v[0]; else sp = sp - v[0];     // :246-254
+        },
+        [&](int, int bf) {
+            const double pf = q.bpsi[bf], corr = x.bphiCorr[bf];
+            if (ONES) x.blambda[bf] = 1.0;
+            hi = mu_max(hi, pf); lo = mu_min(lo, pf);
+            if (corr > 0.0) sp = sp + corr; else sm = sm - corr;
+        },
+        [&](int c) {
+            hi = mu_min(hi + q.ec, q.psiMax); lo = mu_max(lo - q.ec, q.psiMin);   // :496-497
+            const double rdt = LTS ? q.rdtField[c] : q.rdt, psiC = q.psi[c];
+            double coef = q.rho ? q.rho[c] * rdt : rdt;
+            if (q.sp) coef = coef - q.sp[c];
+            const double old = (q.rho ? q.rho[c] * psiC : psiC) * rdt, V = q.vol[c];
+            double up = coef * hi;                    // :503-509
+            if (q.su) up = up - q.su[c];
+            up = up - old;
+            q.maxn[c] = V * up;
+            double dn = coef * lo;                    // :511-517
+            dn = q.su ? q.su[c] - dn : -dn;
+            dn = dn + old;
+            q.minn[c] = V * dn;
+            q.sumPhip[c] = sp; q.mSumPhim[c] = sm;
+        });
+}
+
+// phiBD + lambda*phiCorr, or lambda*phiCorr with returnCorr: internal and boundary faces in one launch.  out may be phiCorr itself
+// (limitCorr's phiCorr *= lambda): a face reads and writes its own element only
 __global__ __launch_bounds__(256) void k_mules_apply(const MuFlux x)
 {
     const int64_t step = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -207,7 +260,9 @@ __global__ __launch_bounds__(256) void k_mules_apply(const MuFlux x)
     for (int64_t i = t0; i < x.nb; i += step) { const double p = x.blambda[i] * x.bphiCorr[i]; x.bout[i] = x.returnCorr ? p : x.bphiBD[i] + p; }
 }
 
-// explicitSolve: surfaceIntegrate(x.phiPsi) and the final expression; x.out is the new psi, a cell array
+// explicitSolve: surfaceIntegrate(x.phiPsi) and the final expression; x.out is the new psi, a cell array.  MULES::correct
+// (CMULESTemplates.C:35-74) is the same expression with rho and psi in the places of rho0 and psi0, x.out psi itself: a cell reads its own
+// psi before it writes it and no other cell's
 template <int BS, bool LTS>
 __global__ __launch_bounds__(BS) void k_mules_solve(const MuArgs a)
 {
@@ -252,6 +307,8 @@ struct mi_mules_s {
     mi_grad_boundary_s* boundary = nullptr;
     int32_t nCells = 0, nFaces = 0, nBFaces = 0;
     bool coupled = false, begun = false;
+    bool corr = false;                                // the last begin was mi_mules_begin_corr: the iteration takes the CMULES patch rule
+    bool hasOther = false;                            // a face on a patch that is neither coupled nor wedge: the CMULES rule reads b_phi there
     DevBuf<double> work[6];                           // psiMaxn, psiMinn (transformed), sumPhip, mSumPhim, lambdap, lambdam
     DevBuf<uint8_t> bKind;
     DevBuf<int32_t> bCell;
@@ -264,22 +321,28 @@ struct MuCall {                                       // one checked call: the k
     bool lts = false;
 };
 // the checks every staged entry shares: the handle, the fields, the listed flux arrays (in: read, out: written); fills c
+// mode: which cell fields the call reads.  MU_EXPLICIT: all of them.  MU_CORR (semi-implicit MULES): psi and rho are the current ones,
+// psi_old_dev and rho_old_dev are not looked at.  MU_CORRECT (mi_mules_correct): psi is the output array, psi_dev is not looked at either.
+enum { MU_EXPLICIT, MU_CORR, MU_CORRECT };
 int mu_check(const std::string& who, mi_mules_s* h, const mi_mules_fields* fl, const double* const* in, const int* inKind, int nIn,
-             double* const* out, const int* outKind, int nOut, MuCall& c)
+             double* const* out, const int* outKind, int nOut, MuCall& c, int mode = MU_EXPLICIT)
 {
     mi_addr_s* a = h->addr;
     if (h->nCells != a->L.nCells || h->nFaces != a->L.nFaces || (h->boundary && h->boundary->addr != a))
         return fail(MI_ERR_ARG, who + ": the handle was built for another addressing");
     if (!fl) return fail(MI_ERR_ARG, who + ": the fields are missing");
-    if (!fl->vol_dev || !fl->psi_dev || !fl->psi_old_dev) return fail(MI_ERR_ARG, who + ": a cell array is missing");
-    if ((fl->rho_dev != nullptr) != (fl->rho_old_dev != nullptr)) return fail(MI_ERR_ARG, who + ": rho and rho_old come together or not at all");
+    const bool old = mode == MU_EXPLICIT;
+    const double* psi = mode == MU_CORRECT ? nullptr : fl->psi_dev;
+    if (!fl->vol_dev || (mode != MU_CORRECT && !psi) || (old && !fl->psi_old_dev)) return fail(MI_ERR_ARG, who + ": a cell array is missing");
+    if (old && (fl->rho_dev != nullptr) != (fl->rho_old_dev != nullptr)) return fail(MI_ERR_ARG, who + ": rho and rho_old come together or not at all");
     const bool hasF = h->nFaces > 0, hasB = h->nBFaces > 0;
     auto present = [&](int kind) { return kind == MU_CELL || (kind == MU_FACE ? hasF : hasB); };   // an empty array may be NULL and is never read
-    if (hasB && !fl->b_psi_dev) return fail(MI_ERR_ARG, who + ": the boundary has faces: boundary psi needed");
+    const double* bpsi = (hasB && mode != MU_CORRECT) ? fl->b_psi_dev : nullptr;     // correct reads no boundary psi
+    if (hasB && mode != MU_CORRECT && !bpsi) return fail(MI_ERR_ARG, who + ": the boundary has faces: boundary psi needed");
     const double* all[40];
     int m = 0;
-    const double* cells[9] = {fl->r_delta_t_dev, fl->rho_dev, fl->rho_old_dev, fl->sp_dev, fl->su_dev, fl->vol_dev, fl->psi_dev, fl->psi_old_dev,
-                              hasB ? fl->b_psi_dev : nullptr};
+    const double* cells[9] = {fl->r_delta_t_dev, fl->rho_dev, old ? fl->rho_old_dev : nullptr, fl->sp_dev, fl->su_dev, fl->vol_dev, psi,
+                              old ? fl->psi_old_dev : nullptr, bpsi};
     for (const double* p : cells) if (p) all[m++] = p;
     for (int i = 0; i < nIn; ++i) {
         if (!present(inKind[i])) continue;
@@ -305,8 +368,8 @@ int mu_check(const std::string& who, mi_mules_s* h, const mi_mules_fields* fl, c
     if (hasB) { r.bStart = h->boundary->allStart.p; r.bFace = h->boundary->all.p; }
     r.n = a->L.nCells; r.xcd = a->ctx->xcdRows;
     MuCells& q = c.a.q;
-    q.rdtField = fl->r_delta_t_dev; q.rdt = fl->r_delta_t; q.rho = fl->rho_dev; q.rhoOld = fl->rho_old_dev; q.sp = fl->sp_dev; q.su = fl->su_dev;
-    q.vol = fl->vol_dev; q.psi = fl->psi_dev; q.psiOld = fl->psi_old_dev; q.bpsi = fl->b_psi_dev; q.psiMax = fl->psi_max; q.psiMin = fl->psi_min;
+    q.rdtField = fl->r_delta_t_dev; q.rdt = fl->r_delta_t; q.rho = fl->rho_dev; q.rhoOld = old ? fl->rho_old_dev : fl->rho_dev; q.sp = fl->sp_dev; q.su = fl->su_dev;
+    q.vol = fl->vol_dev; q.psi = psi; q.psiOld = old ? fl->psi_old_dev : psi; q.bpsi = bpsi; q.psiMax = fl->psi_max; q.psiMin = fl->psi_min;
     q.maxn = h->work[0].p; q.minn = h->work[1].p; q.sumPhip = h->work[2].p; q.mSumPhim = h->work[3].p; q.lambdap = h->work[4].p; q.lambdam = h->work[5].p;
     q.bKind = h->bKind.p; q.bCell = h->bCell.p;
     c.lts = fl->r_delta_t_dev != nullptr;
@@ -347,26 +410,73 @@ void mu_flux(const mi_mules_flux* fx, MuFlux& x)
 }
 int mu_launch_begin(mi_mules_s* h, int form, MuCall& c)
 {
-    if (h->nCells == 0) { h->begun = true; return MI_OK; }
+    if (h->nCells == 0) { h->begun = true; h->corr = false; return MI_OK; }
     mi_addr_s* a = h->addr;
     int r;
     if (form == MI_MULES_LIMIT) r = c.lts ? mu_row_launch(a, 2, MU_BS(k_mules_bounds, true, true), c.a) : mu_row_launch(a, 2, MU_BS(k_mules_bounds, true, false), c.a);
     else r = c.lts ? mu_row_launch(a, 2, MU_BS(k_mules_bounds, false, true), c.a) : mu_row_launch(a, 2, MU_BS(k_mules_bounds, false, false), c.a);
-    if (r == MI_OK) h->begun = true;
+    if (r == MI_OK) { h->begun = true; h->corr = false; }
     return r;
 }
-int mu_check_iterate(const std::string& who, mi_mules_s* h, int n, const mi_mules_fields* fl, const mi_mules_flux* fx, MuCall& c, bool begunByCaller)
+// the CMULES patch rule reads the boundary value of phi on every face of a patch that is neither coupled nor wedge
+int mu_needs_bphi(const std::string& who, const mi_mules_s* h, const mi_mules_flux* fx)
+{
+    if (h->hasOther && !fx->b_phi_dev)
+        return fail(MI_ERR_ARG, who + ": the boundary has a patch that is neither coupled nor wedge: b_phi_dev needed");
+    return MI_OK;
+}
+// the opening of limiterCorr: phi_corr (and, on the patches the rule reads it, b_phi) as given; lambda written (CORR_LIMIT) or as given
+int mu_begin_corr(const std::string& who, mi_mules_s* h, int form, double extremaCoeff, const mi_mules_fields* fl, const mi_mules_flux* fx, MuCall& c)
+{
+    if (form != MI_MULES_CORR_LIMITER && form != MI_MULES_CORR_LIMIT)
+        return fail(MI_ERR_ARG, who + ": form must be MI_MULES_CORR_LIMITER or MI_MULES_CORR_LIMIT");
+    if (!std::isfinite(extremaCoeff) || extremaCoeff < 0) return fail(MI_ERR_ARG, who + ": extrema_coeff must be a finite number and not negative");
+    if (!fx) return fail(MI_ERR_ARG, who + ": the flux arrays are missing");
+    MICHK(mu_needs_bphi(who, h, fx));
+    const int kind[5] = {MU_FACE, MU_BFACE, MU_BFACE, MU_FACE, MU_BFACE};
+    const double* in[5] = {fx->phi_corr_dev, fx->b_phi_corr_dev, fx->b_phi_dev, fx->lambda_dev, fx->b_lambda_dev};
+    double* out[2] = {fx->lambda_dev, fx->b_lambda_dev};
+    const int nIn = h->hasOther ? 3 : 2;
+    if (form == MI_MULES_CORR_LIMIT) {
+        MICHK(mu_check(who, h, fl, in, kind, nIn, out, kMuFB, 2, c, MU_CORR));
+    } else {
+        const double* given[5] = {in[0], in[1], in[3], in[4], in[2]};
+        const int givenKind[5] = {MU_FACE, MU_BFACE, MU_FACE, MU_BFACE, MU_BFACE};
+        MICHK(mu_check(who, h, fl, given, givenKind, nIn + 2, nullptr, nullptr, 0, c, MU_CORR));
+    }
+    c.a.q.ec = extremaCoeff * (fl->psi_max - fl->psi_min);
+    return MI_OK;
+}
+int mu_launch_begin_corr(mi_mules_s* h, int form, MuCall& c)
+{
+    int r = MI_OK;
+    if (h->nCells > 0) {
+        mi_addr_s* a = h->addr;
+        if (form == MI_MULES_CORR_LIMIT) r = c.lts ? mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, true, true), c.a) : mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, true, false), c.a);
+        else r = c.lts ? mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, false, true), c.a) : mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, false, false), c.a);
+    }
+    if (r == MI_OK) { h->begun = true; h->corr = true; }
+    return r;
+}
+// corr: the state the iteration runs in (the handle's, or the one the convenience is about to open)
+int mu_check_iterate(const std::string& who, mi_mules_s* h, int n, const mi_mules_fields* fl, const mi_mules_flux* fx, MuCall& c, bool begunByCaller, bool corr)
 {
     if (n < 0) return fail(MI_ERR_ARG, who + ": n must not be negative");
     if (!begunByCaller && !h->begun) return fail(MI_ERR_ARG, who + ": called before mi_mules_begin");
     if (n > 1 && h->coupled)
         return fail(MI_ERR_ARG, who + ": the boundary has coupled patches: the minOp sync between iterations is the caller's, iterate one at a time");
     if (!fx) return fail(MI_ERR_ARG, who + ": the flux arrays are missing");
-    const double* in[4] = {fx->phi_bd_dev, fx->b_phi_bd_dev, fx->phi_corr_dev, fx->b_phi_corr_dev};
     double* out[2] = {fx->lambda_dev, fx->b_lambda_dev};
+    if (corr) {
+        MICHK(mu_needs_bphi(who, h, fx));
+        const int kind[3] = {MU_FACE, MU_BFACE, MU_BFACE};
+        const double* in[3] = {fx->phi_corr_dev, fx->b_phi_corr_dev, fx->b_phi_dev};
+        return mu_check(who, h, fl, in, kind, h->hasOther ? 3 : 2, out, kMuFB, 2, c, MU_CORR);
+    }
+    const double* in[4] = {fx->phi_bd_dev, fx->b_phi_bd_dev, fx->phi_corr_dev, fx->b_phi_corr_dev};
     return mu_check(who, h, fl, in, kMuFB, 4, out, kMuFB, 2, c);
 }
-int mu_launch_iterate(mi_mules_s* h, int n, MuCall& c)
+int mu_launch_iterate(mi_mules_s* h, int n, MuCall& c, bool corr)
 {
     if (h->nCells == 0) return MI_OK;
     mi_addr_s* a = h->addr;
@@ -374,18 +484,33 @@ int mu_launch_iterate(mi_mules_s* h, int n, MuCall& c)
     for (int j = 0; j < n; ++j) {
         MICHK(mu_row_launch(a, 2, k_mules_sums<256>, k_mules_sums<512>, k_mules_sums<1024>, c.a));
         if (faces > 0) {
-            k_mules_lambda<<<grid_for(a->ctx, (int)faces), 256, 0, a->ctx->stream>>>(c.a);
+            if (corr) k_mules_lambda<true><<<grid_for(a->ctx, (int)faces), 256, 0, a->ctx->stream>>>(c.a);
+            else k_mules_lambda<false><<<grid_for(a->ctx, (int)faces), 256, 0, a->ctx->stream>>>(c.a);
             HIPCHK(hipGetLastError());
         }
     }
     return MI_OK;
 }
-int mu_check_apply(const std::string& who, mi_mules_s* h, const mi_mules_fields* fl, const mi_mules_flux* fx, MuCall& c, bool begunByCaller)
+int mu_check_apply(const std::string& who, mi_mules_s* h, int returnCorr, const mi_mules_fields* fl, const mi_mules_flux* fx, MuCall& c, bool begunByCaller,
+                   bool corr)
 {
     if (!begunByCaller && !h->begun) return fail(MI_ERR_ARG, who + ": called before mi_mules_begin");
     if (!fx) return fail(MI_ERR_ARG, who + ": the flux arrays are missing");
-    const double* in[6] = {fx->phi_bd_dev, fx->b_phi_bd_dev, fx->phi_corr_dev, fx->b_phi_corr_dev, fx->lambda_dev, fx->b_lambda_dev};
     double* out[2] = {fx->out_dev, fx->b_out_dev};
+    if (corr) {                                       // phiCorr *= lambda: there is no phiBD; out may be phi_corr, b_out b_phi_corr
+        if (!returnCorr) return fail(MI_ERR_ARG, who + ": after mi_mules_begin_corr there is no phi_bd: return_corr must be 1");
+        if ((h->nFaces > 0 && !fx->phi_corr_dev) || (h->nBFaces > 0 && !fx->b_phi_corr_dev))
+            return fail(MI_ERR_ARG, who + (h->nFaces > 0 && !fx->phi_corr_dev ? ": an input array is missing" : ": the boundary has faces: boundary flux arrays needed"));
+        const double* in[4] = {fx->lambda_dev, fx->b_lambda_dev, nullptr, nullptr};
+        int n = 2;
+        int k[4] = {MU_FACE, MU_BFACE, 0, 0};
+        if (fx->out_dev != fx->phi_corr_dev) { in[n] = fx->phi_corr_dev; k[n++] = MU_FACE; }
+        if (fx->b_out_dev != fx->b_phi_corr_dev) { in[n] = fx->b_phi_corr_dev; k[n++] = MU_BFACE; }
+        const double* pa[2] = {fx->phi_corr_dev, fx->b_phi_corr_dev};     // an aliased one is an output to the checks below: aligned like them
+        MICHK(rc_aligned(who, (const void* const*)pa, 2));
+        return mu_check(who, h, fl, in, k, n, out, kMuFB, 2, c, MU_CORR);
+    }
+    const double* in[6] = {fx->phi_bd_dev, fx->b_phi_bd_dev, fx->phi_corr_dev, fx->b_phi_corr_dev, fx->lambda_dev, fx->b_lambda_dev};
     return mu_check(who, h, fl, in, kMuFB, 6, out, kMuFB, 2, c);
 }
 int mu_launch_apply(mi_mules_s* h, int returnCorr, MuCall& c)
@@ -423,6 +548,7 @@ extern "C" int mi_mules_create(mi_addr_t a, mi_grad_boundary_t b, const int32_t*
             const bool wedge = patch_is_wedge_host_or_null && patch_is_wedge_host_or_null[p] != 0;
             const bool cpl = b->patchKinds[p] == MI_GRAD_PATCH_COUPLED;
             if (cpl && !wedge && b->patchSizes[p] > 0) h->coupled = true;
+            if (!cpl && !wedge && b->patchSizes[p] > 0) h->hasOther = true;
             for (int32_t i = 0; i < b->patchSizes[p]; ++i) kind[off++] = wedge ? MU_WEDGE : cpl ? MU_COUPLED : MU_OTHER;
         }
         hipStream_t s = a->ctx->stream;
@@ -468,9 +594,9 @@ extern "C" int mi_mules_iterate(mi_mules_t h, int32_t n, const mi_mules_fields* 
     const std::string who = "mi_mules_iterate";
     if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
     MuCall c;
-    MICHK(mu_check_iterate(who, h, n, fields, flux, c, false));
+    MICHK(mu_check_iterate(who, h, n, fields, flux, c, false, h->corr));
     mu_flux(flux, c.a.x);
-    return mu_launch_iterate(h, n, c);
+    return mu_launch_iterate(h, n, c, h->corr);
 }
 
 extern "C" int mi_mules_apply(mi_mules_t h, int32_t return_corr, const mi_mules_fields* fields, const mi_mules_flux* flux)
@@ -478,7 +604,7 @@ extern "C" int mi_mules_apply(mi_mules_t h, int32_t return_corr, const mi_mules_
     const std::string who = "mi_mules_apply";
     if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
     MuCall c;
-    MICHK(mu_check_apply(who, h, fields, flux, c, false));
+    MICHK(mu_check_apply(who, h, return_corr, fields, flux, c, false, h->corr));
     mu_flux(flux, c.a.x);
     return mu_launch_apply(h, return_corr, c);
 }
@@ -490,10 +616,10 @@ extern "C" int mi_mules_limiter(mi_mules_t h, int32_t n_limiter_iter, const mi_m
     MICHK(mu_no_couples(who, h));
     MuCall c, ci;                                     // every check before the first launch
     MICHK(mu_begin(who, h, MI_MULES_LIMITER, fields, flux, c));
-    MICHK(mu_check_iterate(who, h, n_limiter_iter, fields, flux, ci, true));
+    MICHK(mu_check_iterate(who, h, n_limiter_iter, fields, flux, ci, true, false));
     mu_flux(flux, c.a.x); mu_flux(flux, ci.a.x);
     MICHK(mu_launch_begin(h, MI_MULES_LIMITER, c));
-    return mu_launch_iterate(h, n_limiter_iter, ci);
+    return mu_launch_iterate(h, n_limiter_iter, ci, false);
 }
 
 extern "C" int mi_mules_limit(mi_mules_t h, int32_t n_limiter_iter, int32_t return_corr, const mi_mules_fields* fields, const mi_mules_flux* flux)
@@ -503,12 +629,71 @@ extern "C" int mi_mules_limit(mi_mules_t h, int32_t n_limiter_iter, int32_t retu
     MICHK(mu_no_couples(who, h));
     MuCall c, ci, ca;
     MICHK(mu_begin(who, h, MI_MULES_LIMIT, fields, flux, c));
-    MICHK(mu_check_iterate(who, h, n_limiter_iter, fields, flux, ci, true));
-    MICHK(mu_check_apply(who, h, fields, flux, ca, true));
+    MICHK(mu_check_iterate(who, h, n_limiter_iter, fields, flux, ci, true, false));
+    MICHK(mu_check_apply(who, h, return_corr, fields, flux, ca, true, false));
     mu_flux(flux, c.a.x); mu_flux(flux, ci.a.x); mu_flux(flux, ca.a.x);
     MICHK(mu_launch_begin(h, MI_MULES_LIMIT, c));
-    MICHK(mu_launch_iterate(h, n_limiter_iter, ci));
+    MICHK(mu_launch_iterate(h, n_limiter_iter, ci, false));
     return mu_launch_apply(h, return_corr, ca);
+}
+
+// ---- semi-implicit MULES (CMULESTemplates.C:35-758; DESIGN 3.5m) -----------------------------------------------------------------------
+extern "C" int mi_mules_begin_corr(mi_mules_t h, int32_t form, double extrema_coeff, const mi_mules_fields* fields, const mi_mules_flux* flux)
+{
+    const std::string who = "mi_mules_begin_corr";
+    if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
+    MuCall c;
+    MICHK(mu_begin_corr(who, h, form, extrema_coeff, fields, flux, c));
+    mu_flux(flux, c.a.x);
+    return mu_launch_begin_corr(h, form, c);
+}
+
+extern "C" int mi_mules_limiter_corr(mi_mules_t h, int32_t n_limiter_iter, double extrema_coeff, const mi_mules_fields* fields, const mi_mules_flux* flux)
+{
+    const std::string who = "mi_mules_limiter_corr";
+    if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
+    MICHK(mu_no_couples(who, h));
+    MuCall c, ci;                                     // every check before the first launch
+    MICHK(mu_begin_corr(who, h, MI_MULES_CORR_LIMITER, extrema_coeff, fields, flux, c));
+    MICHK(mu_check_iterate(who, h, n_limiter_iter, fields, flux, ci, true, true));
+    mu_flux(flux, c.a.x); mu_flux(flux, ci.a.x);
+    MICHK(mu_launch_begin_corr(h, MI_MULES_CORR_LIMITER, c));
+    return mu_launch_iterate(h, n_limiter_iter, ci, true);
+}
+
+// limitCorr (:706-758): lambda = 1, limiterCorr, phiCorr *= lambda in place
+extern "C" int mi_mules_limit_corr(mi_mules_t h, int32_t n_limiter_iter, double extrema_coeff, const mi_mules_fields* fields, const mi_mules_flux* flux)
+{
+    const std::string who = "mi_mules_limit_corr";
+    if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
+    MICHK(mu_no_couples(who, h));
+    MuCall c, ci, ca;
+    MICHK(mu_begin_corr(who, h, MI_MULES_CORR_LIMIT, extrema_coeff, fields, flux, c));
+    MICHK(mu_check_iterate(who, h, n_limiter_iter, fields, flux, ci, true, true));
+    mi_mules_flux inPlace = *flux;
+    inPlace.out_dev = flux->phi_corr_dev; inPlace.b_out_dev = flux->b_phi_corr_dev;
+    MICHK(mu_check_apply(who, h, 1, fields, &inPlace, ca, true, true));
+    mu_flux(flux, c.a.x); mu_flux(flux, ci.a.x); mu_flux(&inPlace, ca.a.x);
+    MICHK(mu_launch_begin_corr(h, MI_MULES_CORR_LIMIT, c));
+    MICHK(mu_launch_iterate(h, n_limiter_iter, ci, true));
+    return mu_launch_apply(h, 1, ca);
+}
+
+// MULES::correct (:35-74): psi = (rho*psi*rDeltaT + Su - surfaceIntegrate(phiCorr))/(rho*rDeltaT - Sp) in place, on k_mules_solve
+extern "C" int mi_mules_correct(mi_mules_t h, const mi_mules_fields* fields, const double* phi_corr_dev, const double* b_phi_corr_dev, double* psi_inout_dev)
+{
+    const std::string who = "mi_mules_correct";
+    if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
+    if (h->nCells == 0) return MI_OK;
+    MuCall c;
+    const double* in[2] = {phi_corr_dev, b_phi_corr_dev};
+    double* out[1] = {psi_inout_dev};
+    const int cellOut[1] = {MU_CELL};
+    MICHK(mu_check(who, h, fields, in, kMuFB, 2, out, cellOut, 1, c, MU_CORRECT));
+    c.a.q.psiOld = psi_inout_dev;                     // rhoOld is rho already
+    c.a.x.phiPsi = phi_corr_dev; c.a.x.bphiPsi = b_phi_corr_dev; c.a.x.out = psi_inout_dev;
+    mi_addr_s* a = h->addr;
+    return c.lts ? mu_row_launch(a, 1, MU_BS(k_mules_solve, true), c.a) : mu_row_launch(a, 1, MU_BS(k_mules_solve, false), c.a);
 }
 
 extern "C" int mi_mules_explicit_solve(mi_mules_t h, const mi_mules_fields* fields, const double* phi_psi_dev, const double* b_phi_psi_dev,
@@ -536,4 +721,143 @@ extern "C" int mi_vec_min(mi_ctx_t c, int64_t n, const double* x_dev, const doub
     if (!al8(x_dev) || !al8(y_dev) || !al8(out_dev)) return fail(MI_ERR_ARG, "mi_vec_min: arrays must be aligned to 8 bytes");
     if (n == 0) return MI_OK;
     return cell_launch(c, k_vmin, x_dev, y_dev, out_dev, n);
+}
+
+// ---- the interfaceCompression scheme and the compression flux of alphaEqn.H (DESIGN 3.5m) ------------------------------------------------
+// interfaceCompression.H:58-77 inside PhiScheme.C:52-197: the limiter reads the two cell values only; the weights are
+// limitedSurfaceInterpolationScheme's blend, as k_limited_weights forms it.  A device functor, so the rule of 3.5a / 3.5b: 4*x is exact and
+// 1 - (4*x)*(1 - x) one product under a sum, hence one fma; sqr a plain product; max / min the reference's ternaries.
+namespace mi {
+
+__device__ __forceinline__ double ic_limiter(double P, double N)
+{
+    const double a = fma(-(4.0 * P), 1.0 - P, 1.0), b = fma(-(4.0 * N), 1.0 - N, 1.0);
+    return rmin(rmax(1.0 - rmax(a * a, b * b), 0.0), 1.0);
+}
+__device__ __forceinline__ double ic_weight(double lim, double cdw, double fl) { return fma(lim, cdw, (1.0 - lim) * (fl >= 0 ? 1.0 : 0.0)); }
+
+// fvc::flux(-fvc::flux(-phir, alpha2, interfaceCompression), alpha1, interfaceCompression) on one face, alpha2 = 1.0 - alpha1 per cell: the
+// unfused sequence operation for operation.  PATCH: a coupled patch face interpolates as surfaceInterpolationScheme.C:361-366 does,
+// w*P + (1 - w)*N with every operator rounded; an internal face as mi_face_interpolate does (:273-279, one fma)
+template <bool PATCH>
+__device__ __forceinline__ double ic_compression_flux(double cdw, double phir, double a1P, double a1N)
+{
+    auto interpolate = [](double w, double P, double N) { return PATCH ? w * P + (1.0 - w) * N : fma(w, P - N, N); };
+    const double a2P = 1.0 - a1P, a2N = 1.0 - a1N;
+    const double n = -phir;
+    const double g = n * interpolate(ic_weight(ic_limiter(a2P, a2N), cdw, n), a2P, a2N);
+    const double m = -g;
+    return m * interpolate(ic_weight(ic_limiter(a1P, a1N), cdw, m), a1P, a1N);
+}
+
+struct IcArgs {
+    const int32_t *lo, *up;                           // internal faces; the patch form: lo = faceCells, nbr the patchNeighbourField
+    const double *cdw, *flux, *alpha, *nbr;
+    double *w, *limOut;                               // the flux form writes w only
+    int nf, xcd;
+};
+// the internal faces: XCD-aware chunks as k_limited_weights; cdw and the flux streamed, alpha gathered twice
+template <bool FLUX>
+__global__ __launch_bounds__(256) void k_interface_compression(const IcArgs a)
+{
+    int f0, f1; block_chunk(a.nf, a.xcd, f0, f1);
+    for (int f = f0 + threadIdx.x; f < f1; f += blockDim.x) {
+        const double P = a.alpha[a.lo[f]], N = a.alpha[a.up[f]], fl = a.flux[f], cdw = a.cdw[f];
+        if (FLUX) a.w[f] = ic_compression_flux<false>(cdw, fl, P, N);
+        else {
+            const double lim = ic_limiter(P, N);
+            if (a.limOut) a.limOut[f] = lim;
+            a.w[f] = ic_weight(lim, cdw, fl);
+        }
+    }
+}
+// one COUPLED patch (PhiScheme.C:145-189): patchInternalField through faceCells, patchNeighbourField the caller's
+template <bool FLUX>
+__global__ __launch_bounds__(256) void k_patch_interface_compression(const IcArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nf) return;
+    const double P = a.alpha[a.lo[i]], N = a.nbr[i], fl = a.flux[i], cdw = a.cdw[i];
+    if (FLUX) a.w[i] = ic_compression_flux<true>(cdw, fl, P, N);
+    else {
+        const double lim = ic_limiter(P, N);
+        if (a.limOut) a.limOut[i] = lim;
+        a.w[i] = ic_weight(lim, cdw, fl);
+    }
+}
+
+} // namespace mi
+
+namespace {
+template <bool FLUX>
+int ic_internal(const char* who, mi_addr_s* a, const double* cdw, const double* flux, const double* alpha, double* out, double* limOut)
+{
+    if (!a) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (!alpha) return fail(MI_ERR_ARG, std::string(who) + ": input arrays missing");
+    HIPCHK(hipSetDevice(a->ctx->device));
+    MICHK(ensure_caller_tables(a));
+    if (a->L.nFaces == 0) return MI_OK;
+    const double* in[3] = {cdw, flux, alpha};
+    MICHK(lim_outputs(who, in, 3, out, limOut));
+    if (!al16(cdw) || !al16(flux) || !al16(out) || (limOut && !al16(limOut)) || !al8(alpha))
+        return fail(MI_ERR_ARG, std::string(who) + ": face fields must be 16-byte aligned, the cell field to 8 bytes");
+    IcArgs q{};
+    q.lo = a->lowerAddr.p; q.up = a->upperAddr.p; q.cdw = cdw; q.flux = flux; q.alpha = alpha; q.w = out; q.limOut = limOut;
+    q.nf = a->L.nFaces; q.xcd = a->ctx->xcdRows;
+    k_interface_compression<FLUX><<<grid_for(a->ctx, a->L.nFaces), 256, 0, a->ctx->stream>>>(q);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+template <bool FLUX>
+int ic_patch(const char* who, mi_patch_s* p, const double* cdw, const double* flux, const double* alpha, const double* nbr, double* out, double* limOut)
+{
+    if (!p) return fail(MI_ERR_ARG, std::string(who) + ": bad argument");
+    if (p->nFaces == 0) return MI_OK;
+    const double* in[4] = {cdw, flux, alpha, nbr};
+    MICHK(lim_outputs(who, in, 4, out, limOut));
+    const void* al[6] = {cdw, flux, alpha, nbr, out, limOut};
+    MICHK(rc_aligned(who, al, 6));
+    HIPCHK(hipSetDevice(p->ctx->device));
+    IcArgs q{};
+    q.lo = p->faceCells.p; q.cdw = cdw; q.flux = flux; q.alpha = alpha; q.nbr = nbr; q.w = out; q.limOut = limOut; q.nf = p->nFaces;
+    k_patch_interface_compression<FLUX><<<(p->nFaces + 255) / 256, 256, 0, p->ctx->stream>>>(q);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+} // namespace
+
+// PhiScheme registers the bare word: `Gauss interfaceCompression` takes no coefficient
+extern "C" int mi_interface_compression_parse(const char* scheme)
+{
+    if (!scheme) return fail(MI_ERR_ARG, "mi_interface_compression_parse: bad argument");
+    const std::vector<std::string> tok = scheme_words(scheme);
+    if (tok.empty()) return fail(MI_ERR_ARG, "mi_interface_compression_parse: empty scheme");
+    if (tok[0] != "interfaceCompression") return fail(MI_ERR_ARG, "mi_interface_compression_parse: '" + tok[0] + "' is not interfaceCompression");
+    if (tok.size() > 1) return fail(MI_ERR_ARG, "mi_interface_compression_parse: interfaceCompression takes no coefficient: extra '" + tok[1] + "'");
+    return MI_OK;
+}
+
+extern "C" int mi_interface_compression_weights(mi_addr_t a, const double* cd_weights_dev, const double* face_flux_dev, const double* alpha_dev,
+                                                double* weights_out_dev, double* limiter_out_dev_or_null)
+{
+    return ic_internal<false>("mi_interface_compression_weights", a, cd_weights_dev, face_flux_dev, alpha_dev, weights_out_dev, limiter_out_dev_or_null);
+}
+
+extern "C" int mi_patch_interface_compression_weights(mi_patch_t p, const double* patch_cd_weights_dev, const double* patch_flux_dev,
+                                                      const double* alpha_dev, const double* nbr_alpha_dev, double* weights_out_dev,
+                                                      double* limiter_out_dev_or_null)
+{
+    return ic_patch<false>("mi_patch_interface_compression_weights", p, patch_cd_weights_dev, patch_flux_dev, alpha_dev, nbr_alpha_dev, weights_out_dev,
+                           limiter_out_dev_or_null);
+}
+
+extern "C" int mi_alpha_compression_flux(mi_addr_t a, const double* cd_weights_dev, const double* phir_dev, const double* alpha1_dev, double* out_dev)
+{
+    return ic_internal<true>("mi_alpha_compression_flux", a, cd_weights_dev, phir_dev, alpha1_dev, out_dev, nullptr);
+}
+
+extern "C" int mi_patch_alpha_compression_flux(mi_patch_t p, const double* patch_cd_weights_dev, const double* patch_phir_dev, const double* alpha1_dev,
+                                               const double* nbr_alpha1_dev, double* out_dev)
+{
+    return ic_patch<true>("mi_patch_alpha_compression_flux", p, patch_cd_weights_dev, patch_phir_dev, alpha1_dev, nbr_alpha1_dev, out_dev, nullptr);
 }

@@ -83,6 +83,9 @@ SYMBOLS = [
     "mi_surface_sum", "mi_reconstruct_create", "mi_reconstruct_destroy", "mi_reconstruct_fields", "mi_fvc_reconstruct",
     "mi_mules_create", "mi_mules_destroy", "mi_mules_work", "mi_mules_begin", "mi_mules_iterate", "mi_mules_apply", "mi_mules_limiter", "mi_mules_limit",
     "mi_mules_explicit_solve", "mi_vec_min",
+    "mi_mules_begin_corr", "mi_mules_limiter_corr", "mi_mules_limit_corr", "mi_mules_correct",
+    "mi_interface_compression_parse", "mi_interface_compression_weights", "mi_patch_interface_compression_weights",
+    "mi_alpha_compression_flux", "mi_patch_alpha_compression_flux",
 ]
 
 
@@ -940,6 +943,16 @@ class Patch:
         _chk(lib().mi_patch_filtered_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), pv(phi), pv(nbr_phi), pv(grad),
                                              pv(nbr_grad), pv(patch_delta), _ptr(w_out), _ptr(limiter_out)))
 
+    def interface_compression_weights(self, patch_cd_weights, patch_flux, alpha, nbr_alpha, w_out, limiter_out=None):
+        """the interfaceCompression scheme's weights on a COUPLED patch (PhiScheme.C:145-189): alpha the cell field, nbr_alpha its
+        patchNeighbourField"""
+        _chk(lib().mi_patch_interface_compression_weights(self.h, _ptr(patch_cd_weights), _ptr(patch_flux), _ptr(alpha), _ptr(nbr_alpha), _ptr(w_out),
+                                                          _ptr(limiter_out)))
+
+    def alpha_compression_flux(self, patch_cd_weights, patch_phir, alpha1, nbr_alpha1, out):
+        """alphaEqn.H's compression flux on a COUPLED patch (mi_patch_alpha_compression_flux)"""
+        _chk(lib().mi_patch_alpha_compression_flux(self.h, _ptr(patch_cd_weights), _ptr(patch_phir), _ptr(alpha1), _ptr(nbr_alpha1), _ptr(out)))
+
     def cubic_correction(self, geo, vf, nbr_vf, grad, nbr_grad, out, patch_flux=None):
         """[patchFlux *] correction(vf) of cubic on a COUPLED patch (mi_patch_cubic_correction): geo a CubicGeometry of the patch's arrays, vf /
         nbr_vf one array per component (cell field, its patchNeighbourField), grad / nbr_grad one [gx, gy, gz] per component, out one patch
@@ -1119,6 +1132,11 @@ def filtered(scheme: str) -> FilteredLimiter:
     return out
 
 
+def interface_compression(scheme: str) -> None:
+    """mi_interface_compression_parse: raises unless the scheme is exactly "interfaceCompression" (host only, no GPU)"""
+    _chk(lib().mi_interface_compression_parse(scheme.encode()))
+
+
 class CubicGeometry(C.Structure):
     """mi_cubic_geometry (include/mi_ldu.h)"""
     _fields_ = [("lambda_dev", C.c_void_p), ("sf_dev", C.c_void_p * 3), ("mag_sf_dev", C.c_void_p), ("delta_coeffs_dev", C.c_void_p)]
@@ -1291,6 +1309,7 @@ class MulesFlux(C.Structure):
 
 
 MULES_FORMS = ("limiter", "limit")      # MI_MULES_LIMITER, MI_MULES_LIMIT
+MULES_CORR_FORMS = ("limiter", "limit")  # MI_MULES_CORR_LIMITER, MI_MULES_CORR_LIMIT
 
 
 def mules_fields(vol, psi, psi_old, r_delta_t=1.0, b_psi=None, psi_max=1.0, psi_min=0.0, rho=None, rho_old=None, sp=None, su=None):
@@ -1355,6 +1374,25 @@ class Mules:
     def explicit_solve(self, fields, phi_psi, psi_out, b_phi_psi=None):
         """MULES::explicitSolve(rDeltaT, rho, psi, phiPsi, Sp, Su): the new psi into psi_out"""
         _chk(lib().mi_mules_explicit_solve(self.h, C.byref(fields) if fields is not None else None, _ptr(phi_psi), _ptr(b_phi_psi), _ptr(psi_out)))
+
+    def begin_corr(self, form, fields, flux, extrema_coeff=0.0):
+        f = MULES_CORR_FORMS.index(form) if form in MULES_CORR_FORMS else int(form)
+        _chk(lib().mi_mules_begin_corr(self.h, C.c_int32(f), C.c_double(extrema_coeff), C.byref(fields) if fields is not None else None,
+                                       C.byref(flux) if flux is not None else None))
+
+    def limiter_corr(self, fields, flux, n_limiter_iter=3, extrema_coeff=0.0):
+        """MULES::limiterCorr: begin_corr("limiter") + iterate(n_limiter_iter)"""
+        _chk(lib().mi_mules_limiter_corr(self.h, C.c_int32(n_limiter_iter), C.c_double(extrema_coeff), C.byref(fields) if fields is not None else None,
+                                         C.byref(flux) if flux is not None else None))
+
+    def limit_corr(self, fields, flux, n_limiter_iter=3, extrema_coeff=0.0):
+        """MULES::limitCorr: begin_corr("limit") + iterate(n_limiter_iter) + phi_corr *= lambda in place"""
+        _chk(lib().mi_mules_limit_corr(self.h, C.c_int32(n_limiter_iter), C.c_double(extrema_coeff), C.byref(fields) if fields is not None else None,
+                                       C.byref(flux) if flux is not None else None))
+
+    def correct(self, fields, phi_corr, psi_inout, b_phi_corr=None):
+        """MULES::correct(rDeltaT, rho, psi, phi, phiCorr, Sp, Su): psi_inout updated in place"""
+        _chk(lib().mi_mules_correct(self.h, C.byref(fields) if fields is not None else None, _ptr(phi_corr), _ptr(b_phi_corr), _ptr(psi_inout)))
 
     def close(self):
         if self.h:
@@ -1601,6 +1639,31 @@ class Assembly:
 
     def mules_explicit_solve(self, mu, fields, phi_psi, psi_out, b_phi_psi=None):
         self._mules(mu).explicit_solve(fields, phi_psi, psi_out, b_phi_psi)
+
+    def mules_begin_corr(self, mu, form, fields, flux, extrema_coeff=0.0):
+        """opens semi-implicit MULES' limiter (mi_mules_begin_corr): form "limiter" (lambda as given) or "limit" (lambda = 1); reads phi_corr,
+        b_phi_corr and the current psi / rho; mules_iterate then takes the CMULES patch rule (it reads b_phi) and mules_apply(return_corr=True)
+        may write phi_corr in place"""
+        self._mules(mu).begin_corr(form, fields, flux, extrema_coeff)
+
+    def mules_limiter_corr(self, mu, fields, flux, n_limiter_iter=3, extrema_coeff=0.0):
+        self._mules(mu).limiter_corr(fields, flux, n_limiter_iter, extrema_coeff)
+
+    def mules_limit_corr(self, mu, fields, flux, n_limiter_iter=3, extrema_coeff=0.0):
+        self._mules(mu).limit_corr(fields, flux, n_limiter_iter, extrema_coeff)
+
+    def mules_correct(self, mu, fields, phi_corr, psi_inout, b_phi_corr=None):
+        self._mules(mu).correct(fields, phi_corr, psi_inout, b_phi_corr)
+
+    def interface_compression_weights(self, cd_weights, face_flux, alpha, w_out, limiter_out=None):
+        """the interfaceCompression scheme's weights on the internal faces in one face pass (mi_interface_compression_weights): the limiter
+        from the two cell values of alpha, no gradient and no centres"""
+        _chk(lib().mi_interface_compression_weights(self.addr.h, _ptr(cd_weights), _ptr(face_flux), _ptr(alpha), _ptr(w_out), _ptr(limiter_out)))
+
+    def alpha_compression_flux(self, cd_weights, phir, alpha1, out):
+        """fvc::flux(-fvc::flux(-phir, 1 - alpha1, interfaceCompression), alpha1, interfaceCompression) on the internal faces in one face pass
+        (mi_alpha_compression_flux), the bits of the unfused sequence"""
+        _chk(lib().mi_alpha_compression_flux(self.addr.h, _ptr(cd_weights), _ptr(phir), _ptr(alpha1), _ptr(out)))
 
     def vec_min(self, x, y, out):
         """out = min(x, y) element by element, out may alias either (mi_vec_min): minOp over the two sides of a cyclic pair"""

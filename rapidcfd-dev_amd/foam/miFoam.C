@@ -1193,6 +1193,35 @@ void patchFilteredWeights(scalargpuField& w, const fvPatchCells& p, const filter
     patchFilteredCall(w, p, s, pCdWeights, pFaceFlux, limitedArrays(vf, gradVf), limitedArrays(nbrVf, nbrGradVf), pDelta, limiter);
 }
 
+interfaceCompressionScheme interfaceCompressionScheme::New(const std::string& scheme)
+{
+    miCheck(mi_interface_compression_parse(scheme.c_str()), "limitedSurfaceInterpolationScheme::New");
+    return interfaceCompressionScheme();
+}
+void interfaceCompressionWeights(scalargpuField& w, const lduAddressing& a, const interfaceCompressionScheme&, const scalargpuField& cdWeights,
+                                 const scalargpuField& faceFlux, const scalargpuField& vf, scalargpuField* limiter)
+{
+    miCheck(mi_interface_compression_weights(a.handle(), cdWeights.data(), faceFlux.data(), vf.data(), w.data(), limiter ? limiter->data() : nullptr),
+            "PhiScheme::weights");
+}
+void patchInterfaceCompressionWeights(scalargpuField& w, const fvPatchCells& p, const interfaceCompressionScheme&, const scalargpuField& pCdWeights,
+                                      const scalargpuField& pFaceFlux, const scalargpuField& vf, const scalargpuField& nbrVf, scalargpuField* limiter)
+{
+    miCheck(mi_patch_interface_compression_weights(p.handle(), pCdWeights.data(), pFaceFlux.data(), vf.data(), nbrVf.data(), w.data(),
+                                                   limiter ? limiter->data() : nullptr), "PhiScheme::weights (coupled patch)");
+}
+void alphaCompressionFlux(scalargpuField& flux, const lduAddressing& a, const interfaceCompressionScheme&, const scalargpuField& cdWeights,
+                          const scalargpuField& phir, const scalargpuField& alpha1)
+{
+    miCheck(mi_alpha_compression_flux(a.handle(), cdWeights.data(), phir.data(), alpha1.data(), flux.data()), "alphaCompressionFlux");
+}
+void patchAlphaCompressionFlux(scalargpuField& flux, const fvPatchCells& p, const interfaceCompressionScheme&, const scalargpuField& pCdWeights,
+                               const scalargpuField& pPhir, const scalargpuField& alpha1, const scalargpuField& nbrAlpha1)
+{
+    miCheck(mi_patch_alpha_compression_flux(p.handle(), pCdWeights.data(), pPhir.data(), alpha1.data(), nbrAlpha1.data(), flux.data()),
+            "alphaCompressionFlux (coupled patch)");
+}
+
 // ---- Pstream: the parallel run as this path sees it -------------------------------------------------------------
 namespace {
 struct PstreamState { bool par = false; int rank = 0, n = 1; mi_comm_t red = nullptr, halo = nullptr; };
@@ -1591,6 +1620,47 @@ void MULES::explicitSolve(const mulesData& m, const rDeltaTType& rDeltaT, const 
 {
     limit(m, rDeltaT, rho, psi, phi, phiPsi, Sp, Su, V, psiMax, psiMin, 3, false);
     explicitSolve(m, rDeltaT, rho, psi, phiPsi, Sp, Su, V);
+}
+// ---- semi-implicit MULES ----
+void MULES::limiterCorr(const mulesData& m, surfaceField allLambda, const rDeltaTType& rDeltaT, const rhoType& rho, const volField& psi,
+                        const surfaceField& phi, const surfaceField& phiCorr, const scalargpuField* Sp, const scalargpuField* Su, const scalargpuField& V,
+                        scalar psiMax, scalar psiMin, label nLimiterIter, scalar extremaCoeff)
+{
+    const mi_mules_fields f = mulesFields(rDeltaT, rho, psi, Sp, Su, V, psiMax, psiMin);
+    mi_mules_flux x{};
+    x.b_phi_dev = dataOf(phi.boundary);
+    x.phi_corr_dev = dataOf(phiCorr.field); x.b_phi_corr_dev = dataOf(phiCorr.boundary);
+    x.lambda_dev = dataOf(allLambda.field); x.b_lambda_dev = dataOf(allLambda.boundary);
+    miCheck(mi_mules_limiter_corr(m.handle(), (int32_t)nLimiterIter, extremaCoeff, &f, &x), "MULES::limiterCorr");
+}
+void MULES::limitCorr(const mulesData& m, const rDeltaTType& rDeltaT, const rhoType& rho, const volField& psi, const surfaceField& phi, surfaceField phiCorr,
+                      const scalargpuField* Sp, const scalargpuField* Su, const scalargpuField& V, scalar psiMax, scalar psiMin, label nLimiterIter,
+                      scalar extremaCoeff)
+{
+    const mi_mules_fields f = mulesFields(rDeltaT, rho, psi, Sp, Su, V, psiMax, psiMin);
+    mi_mules_flux x{};
+    x.b_phi_dev = dataOf(phi.boundary);
+    x.phi_corr_dev = dataOf(phiCorr.field); x.b_phi_corr_dev = dataOf(phiCorr.boundary);
+    x.lambda_dev = m.work(4).data();
+    if (phiCorr.boundary) {
+        const label nb = phiCorr.boundary->size();
+        if (m.work(5).size() != nb) m.work(5) = scalargpuField(nb);
+        x.b_lambda_dev = m.work(5).data();
+    }
+    miCheck(mi_mules_limit_corr(m.handle(), (int32_t)nLimiterIter, extremaCoeff, &f, &x), "MULES::limitCorr");
+}
+void MULES::correct(const mulesData& m, const rDeltaTType& rDeltaT, const rhoType& rho, const volField& psi, const surfaceField&, const surfaceField& phiCorr,
+                    const scalargpuField* Sp, const scalargpuField* Su, const scalargpuField& V)
+{
+    const mi_mules_fields f = mulesFields(rDeltaT, rho, psi, Sp, Su, V, 0, 0);
+    miCheck(mi_mules_correct(m.handle(), &f, dataOf(phiCorr.field), dataOf(phiCorr.boundary), dataOf(psi.field)), "MULES::correct");
+}
+void MULES::correct(const mulesData& m, const rhoType& rho, const volField& psi, const surfaceField& phi, surfaceField phiCorr, const scalargpuField* Sp,
+                    const scalargpuField* Su, const scalargpuField& V, scalar psiMax, scalar psiMin, const rDeltaTType& rDeltaT, label nLimiterIter,
+                    scalar extremaCoeff)
+{
+    limitCorr(m, rDeltaT, rho, psi, phi, phiCorr, Sp, Su, V, psiMax, psiMin, nLimiterIter, extremaCoeff);
+    correct(m, rDeltaT, rho, psi, phi, phiCorr, Sp, Su, V);
 }
 
 // ---- steadyState, localEuler, CoEuler and the bounded convection scheme ----
