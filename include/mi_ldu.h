@@ -814,6 +814,67 @@ int mi_patch_interface_compression_weights(mi_patch_t patch, const double *patch
 int mi_alpha_compression_flux(mi_addr_t addr, const double *cd_weights_dev, const double *phir_dev, const double *alpha1_dev, double *out_dev);
 int mi_patch_alpha_compression_flux(mi_patch_t patch, const double *patch_cd_weights_dev, const double *patch_phir_dev,
                                     const double *alpha1_dev, const double *nbr_alpha1_dev, double *out_dev);
+/* ---- interFoam's interfaceProperties: nHatf, curvature and surface tension force (transportModels/interfaceProperties/
+ *      interfaceProperties.C:58-159, :220-231) ----
+ * What calculateK() and surfaceTensionForce() run as about twenty field passes with vector temporaries is two face passes and one row pass
+ * here.  Every operator is rounded on its own except the fma written below; division and square root are the correctly rounded IEEE ones.
+ * mi_interface_nhatf (internal faces; :127, :134, :143): with P = lower[f], N = upper[f], per component k
+ *     g_k = fma(lambda, gP_k - gN_k, gN_k)                     (the rule of mi_face_interpolate)
+ *     m = sqrt(fma(g_z, g_z, fma(g_x, g_x, g_y*g_y)))          (mag of a vector, the contraction of 3.5a: an assumption, see DESIGN)
+ *     d = m + delta_n;  n_k = g_k/d                            (three divisions, no reciprocal)
+ *     nHatf = fma(n_z, Sf_z, fma(n_x, Sf_x, n_y*Sf_y))
+ *   grad_dev: the three cell arrays of a gradient entry; sf_dev: three face arrays; nhatfv_out_dev_or_null: three face arrays for n, or NULL.
+ *   A zero gradient gives exactly 0/(0 + delta_n) = 0.  delta_n is the caller's (1e-8/cbrt(average(V)): a device reduction's order could
+ *   not be the reference's).
+ * mi_patch_interface_nhatf: one patch, three forms by what mi_patch_nhatf holds.
+ *   patch_weights_dev given (a COUPLED patch): g_k = w*gP_k + (1 - w)*gNbr_k, every operator rounded; grad_dev the cell gradient (read
+ *     through the patch's faceCells), nbr_grad_dev its patchNeighbourField.
+ *   patch_weights_dev NULL: grad_dev holds the BOUNDARY VALUE of gradAlpha per patch face (mi_patch_gauss_grad_correct); no cell is read.
+ *   theta_deg_dev given (a contact-angle patch; patch_weights_dev NULL only; patch_magsf_dev required): after n_k = g_k/d,
+ *     correctContactAngle :83-111: theta = (pi/180.0)*theta_deg; nf_k = Sf_k/magSf; a12 = n & nf (the fma chain); b1 = cos(theta);
+ *     b2 = cos(acos(a12) - theta); det = 1.0 - a12*a12; a = (b1 - a12*b2)/det; b = (b2 - a12*b1)/det; n_k = a*nf_k + b*n_k (two products
+ *     and a sum, no fma); n_k /= (mag(n) + delta_n); gradient_out = (nf & n)*mag(g) when given.  |a12| >= 1 has no special case: NaN comes
+ *     out as it does in the reference.  b1_out_dev / b2_out_dev (both or neither): the device's own cos / acos results, for tests.  The
+ *     angle models' theta(U, nHat) and acap.evaluate() are the caller's.
+ *   Then nHatf = n & Sf with the patch's Sf; nhatfv_out_dev all three or all NULL.
+ * mi_interface_create / mi_interface_destroy: the handle of the curvature's row pass on one mesh, from a mi_grad_boundary_t (NULL: no
+ *   boundary faces), which must outlive it.  mi_interface_curvature (:146): K = -fvc::div(nHatf) in one launch: per cell the sum over its
+ *   own faces ascending (+), its neighbour-side faces in losort order (-), its boundary faces patch by patch (+, b_nhatf_dev patch-ordered
+ *   as b_phi_psi_dev of mi_mules_explicit_solve), then /V, then a true sign flip: a cell without flux gives -0.0.  No atomics.
+ * mi_surface_tension_force (:223): sP = sigma*K[P], sN = sigma*K[N] (sigmaK() is a cell product before the interpolate);
+ *   i = fma(lambda, sP - sN, sN); sn = deltaCoeffs*(alpha[N] - alpha[P]), + sngrad_corr[f] when given (the explicit part of a corrected /
+ *   limited snGrad: mi_sngrad_*correction_flux with a gammaMagSf of ones); out = i*sn.  mi_patch_surface_tension_force (a COUPLED patch):
+ *   i = w*sP + (1 - w)*(sigma*nbrK), sn = pDeltaCoeffs*(nbrAlpha - alpha[faceCells]) [+ corr], the product.
+ * mi_near_interface (:230): out = pos(alpha - 0.01)*pos(0.99 - alpha), pos(x) = (x >= 0) ? 1 : 0; out may be alpha.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): delta_n not finite or <= 0; missing arrays; an output that aliases an input
+ *   or another output; internal-face arrays not 16-byte aligned, cell and patch arrays not 8-byte aligned; theta_deg with patch_weights;
+ *   the contact-angle form without patch_magsf; gradient_out / b1_out / b2_out without theta_deg; a handle of another addressing.
+ *   Zero faces: MI_OK. */
+typedef struct mi_patch_nhatf {
+    const double *patch_weights_dev;          /* coupled patch, or NULL */
+    const double *grad_dev[3];                /* coupled: the cell gradient; otherwise the boundary value of gradAlpha per patch face */
+    const double *nbr_grad_dev[3];            /* coupled only */
+    const double *patch_sf_dev[3];
+    const double *patch_magsf_dev;            /* contact-angle form */
+    const double *theta_deg_dev;              /* contact-angle form, degrees per face; NULL otherwise */
+    double *nhatf_out_dev;
+    double *nhatfv_out_dev[3];                /* all three or all NULL */
+    double *gradient_out_dev;                 /* contact-angle form, or NULL */
+    double *b1_out_dev, *b2_out_dev;          /* contact-angle form, both or neither */
+} mi_patch_nhatf;
+typedef struct mi_interface_s *mi_interface_t;
+int mi_interface_nhatf(mi_addr_t addr, double delta_n, const double *lambda_dev, const double *const *sf_dev, const double *const *grad_dev,
+                       double *nhatf_out_dev, double *const *nhatfv_out_dev_or_null);
+int mi_patch_interface_nhatf(mi_patch_t patch, double delta_n, const mi_patch_nhatf *arrays);
+int mi_interface_create(mi_addr_t addr, mi_grad_boundary_t boundary_or_null, mi_interface_t *out);
+int mi_interface_destroy(mi_interface_t iface);
+int mi_interface_curvature(mi_interface_t iface, const double *nhatf_dev, const double *b_nhatf_dev, const double *vol_dev, double *k_out_dev);
+int mi_surface_tension_force(mi_addr_t addr, double sigma, const double *lambda_dev, const double *delta_coeffs_dev, const double *k_dev,
+                             const double *alpha_dev, const double *sngrad_corr_dev_or_null, double *out_dev);
+int mi_patch_surface_tension_force(mi_patch_t patch, double sigma, const double *patch_weights_dev, const double *patch_delta_coeffs_dev,
+                                   const double *k_dev, const double *nbr_k_dev, const double *alpha_dev, const double *nbr_alpha_dev,
+                                   const double *patch_sngrad_corr_dev_or_null, double *out_dev);
+int mi_near_interface(mi_ctx_t ctx, int64_t n, const double *alpha_dev, double *out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

@@ -2505,6 +2505,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "least_squares.inc"
 #include "reconstruct.inc"
 #include "mules.inc"
+#include "interface.inc"
 
 mi_matrix_s::~mi_matrix_s()
 {

@@ -86,6 +86,8 @@ SYMBOLS = [
     "mi_mules_begin_corr", "mi_mules_limiter_corr", "mi_mules_limit_corr", "mi_mules_correct",
     "mi_interface_compression_parse", "mi_interface_compression_weights", "mi_patch_interface_compression_weights",
     "mi_alpha_compression_flux", "mi_patch_alpha_compression_flux",
+    "mi_interface_nhatf", "mi_patch_interface_nhatf", "mi_interface_create", "mi_interface_destroy", "mi_interface_curvature",
+    "mi_surface_tension_force", "mi_patch_surface_tension_force", "mi_near_interface",
 ]
 
 
@@ -891,6 +893,13 @@ def gamg_host_hierarchy(n_cells, lower_addr, upper_addr, face_weights, n_cells_i
     return out
 
 
+class PatchNhatf(C.Structure):
+    """mi_patch_nhatf (include/mi_ldu.h)"""
+    _fields_ = [("patch_weights_dev", C.c_void_p), ("grad_dev", C.c_void_p * 3), ("nbr_grad_dev", C.c_void_p * 3), ("patch_sf_dev", C.c_void_p * 3),
+                ("patch_magsf_dev", C.c_void_p), ("theta_deg_dev", C.c_void_p), ("nhatf_out_dev", C.c_void_p), ("nhatfv_out_dev", C.c_void_p * 3),
+                ("gradient_out_dev", C.c_void_p), ("b1_out_dev", C.c_void_p), ("b2_out_dev", C.c_void_p)]
+
+
 class Patch:
     """A boundary patch (its faceCells) for the assembly sweeps."""
 
@@ -952,6 +961,26 @@ class Patch:
     def alpha_compression_flux(self, patch_cd_weights, patch_phir, alpha1, nbr_alpha1, out):
         """alphaEqn.H's compression flux on a COUPLED patch (mi_patch_alpha_compression_flux)"""
         _chk(lib().mi_patch_alpha_compression_flux(self.h, _ptr(patch_cd_weights), _ptr(patch_phir), _ptr(alpha1), _ptr(nbr_alpha1), _ptr(out)))
+
+    def interface_nhatf(self, delta_n, grad, patch_sf, nhatf_out, patch_weights=None, nbr_grad=None, nhatfv_out=None, patch_magsf=None,
+                        theta_deg=None, gradient_out=None, b12_out=None):
+        """nHatf on this patch (mi_patch_interface_nhatf).  patch_weights given: a COUPLED patch, grad the cell gradient [gx, gy, gz], nbr_grad
+        its patchNeighbourField.  patch_weights None: grad the boundary value of gradAlpha per patch face.  theta_deg given (with patch_magsf):
+        a contact-angle patch, correctContactAngle between the unit normal and the flux; gradient_out the gradient of the alphaContactAngle
+        patch field, b12_out = (b1, b2) the device's own cos(theta) and cos(acos(a12) - theta)"""
+        x = PatchNhatf()
+        x.patch_weights_dev = _ptr(patch_weights)
+        vec3 = lambda xs: (C.c_void_p * 3)(*[_ptr(v) for v in (xs if xs is not None else (None, None, None))])
+        x.grad_dev, x.nbr_grad_dev, x.patch_sf_dev, x.nhatfv_out_dev = vec3(grad), vec3(nbr_grad), vec3(patch_sf), vec3(nhatfv_out)
+        x.patch_magsf_dev, x.theta_deg_dev, x.nhatf_out_dev, x.gradient_out_dev = _ptr(patch_magsf), _ptr(theta_deg), _ptr(nhatf_out), _ptr(gradient_out)
+        x.b1_out_dev, x.b2_out_dev = (_ptr(b12_out[0]), _ptr(b12_out[1])) if b12_out is not None else (None, None)
+        _chk(lib().mi_patch_interface_nhatf(self.h, C.c_double(delta_n), C.byref(x)))
+
+    def surface_tension_force(self, sigma, patch_weights, patch_delta_coeffs, K, nbr_K, alpha, nbr_alpha, out, sngrad_corr=None):
+        """interpolate(sigma*K)*snGrad(alpha) on a COUPLED patch (mi_patch_surface_tension_force): K / alpha the cell fields, nbr_* their
+        patchNeighbourFields"""
+        _chk(lib().mi_patch_surface_tension_force(self.h, C.c_double(sigma), _ptr(patch_weights), _ptr(patch_delta_coeffs), _ptr(K), _ptr(nbr_K), _ptr(alpha),
+                                                  _ptr(nbr_alpha), _ptr(sngrad_corr), _ptr(out)))
 
     def cubic_correction(self, geo, vf, nbr_vf, grad, nbr_grad, out, patch_flux=None):
         """[patchFlux *] correction(vf) of cubic on a COUPLED patch (mi_patch_cubic_correction): geo a CubicGeometry of the patch's arrays, vf /
@@ -1400,6 +1429,25 @@ class Mules:
             self.h = C.c_void_p()
 
 
+class Interface:
+    """The curvature's row pass on one mesh (mi_interface_create): boundary a GradBoundary or None (no boundary faces); it must stay open as
+    long as the handle is used."""
+
+    def __init__(self, addr: Addressing, boundary=None):
+        self.addr, self.boundary = addr, boundary
+        self.h = C.c_void_p()
+        _chk(lib().mi_interface_create(addr.h, boundary.h if boundary is not None else None, C.byref(self.h)))
+
+    def curvature(self, nhatf, vol, K_out, b_nhatf=None):
+        """K = -fvc::div(nHatf) in one launch (mi_interface_curvature): b_nhatf the patch-ordered boundary faces"""
+        _chk(lib().mi_interface_curvature(self.h, _ptr(nhatf), _ptr(b_nhatf), _ptr(vol), _ptr(K_out)))
+
+    def close(self):
+        if self.h:
+            lib().mi_interface_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Assembly:
     """fvm::div / fvm::laplacian / negSumDiag / relax ... on caller-order arrays of an Addressing."""
 
@@ -1664,6 +1712,26 @@ class Assembly:
         """fvc::flux(-fvc::flux(-phir, 1 - alpha1, interfaceCompression), alpha1, interfaceCompression) on the internal faces in one face pass
         (mi_alpha_compression_flux), the bits of the unfused sequence"""
         _chk(lib().mi_alpha_compression_flux(self.addr.h, _ptr(cd_weights), _ptr(phir), _ptr(alpha1), _ptr(out)))
+
+    def interface_nhatf(self, delta_n, lam, sf, grad, nhatf_out, nhatfv_out=None):
+        """the face unit interface normal flux on the internal faces in one face pass (mi_interface_nhatf): sf [x, y, z] face arrays, grad the
+        cell gradient of alpha [gx, gy, gz], nhatfv_out three face arrays for the normal itself or None"""
+        pv = lambda xs: None if xs is None else (C.c_void_p * 3)(*[_ptr(x) for x in xs])
+        _chk(lib().mi_interface_nhatf(self.addr.h, C.c_double(delta_n), _ptr(lam), pv(sf), pv(grad), _ptr(nhatf_out), pv(nhatfv_out)))
+
+    def interface_curvature(self, interface, nhatf, vol, K_out, b_nhatf=None):
+        """K = -fvc::div(nHatf) over an Interface handle of this addressing (mi_interface_curvature)"""
+        interface.curvature(nhatf, vol, K_out, b_nhatf)
+
+    def surface_tension_force(self, sigma, lam, delta_coeffs, K, alpha, out, sngrad_corr=None):
+        """fvc::interpolate(sigma*K)*fvc::snGrad(alpha) on the internal faces in one face pass (mi_surface_tension_force); sngrad_corr the
+        explicit part of a corrected / limited snGrad or None"""
+        _chk(lib().mi_surface_tension_force(self.addr.h, C.c_double(sigma), _ptr(lam), _ptr(delta_coeffs), _ptr(K), _ptr(alpha), _ptr(sngrad_corr), _ptr(out)))
+
+    def near_interface(self, alpha, out):
+        """out = pos(alpha - 0.01)*pos(0.99 - alpha) (mi_near_interface)"""
+        n = (alpha if alpha is not None else out).numel()
+        _chk(lib().mi_near_interface(self.addr.ctx.h, C.c_int64(n), _ptr(alpha), _ptr(out)))
 
     def vec_min(self, x, y, out):
         """out = min(x, y) element by element, out may alias either (mi_vec_min): minOp over the two sides of a cyclic pair"""

@@ -1222,6 +1222,82 @@ void patchAlphaCompressionFlux(scalargpuField& flux, const fvPatchCells& p, cons
             "alphaCompressionFlux (coupled patch)");
 }
 
+// ---- interfaceProperties (interfaceProperties.C:58-231) ---------------------------------------------------------
+namespace {
+label interfaceBoundaryFaces(const std::vector<interfaceProperties::patchData>& patches)
+{
+    label n = 0;
+    for (const auto& p : patches) n += p.cells->size();
+    return n;
+}
+}
+interfaceProperties::interfaceProperties(const meshData& mesh, const std::vector<patchData>& patches, scalar cAlpha, scalar sigma)
+    : mesh_(mesh), patches_(patches), cAlpha_(cAlpha), sigma_(sigma), deltaN_(0), h_(nullptr),
+      nHatf_((label)mesh.addr->lowerAddrHost().size()), nHatfb_(interfaceBoundaryFaces(patches)), K_(mesh.V->size())
+{
+    // deltaN_("deltaN", 1e-8/pow(average(alpha1.mesh().V()), 1.0/3.0)) (:181-185): the sum on the host in cell order
+    const std::vector<scalar> V = mesh.V->asHost();
+    scalar s = 0;
+    for (scalar v : V) s += v;
+    deltaN_ = 1e-8 / std::pow(s / (scalar)V.size(), 1.0 / 3.0);
+    miCheck(mi_interface_create(mesh.addr->handle(), mesh.boundary ? mesh.boundary->handle() : nullptr, &h_), "interfaceProperties::New");
+}
+interfaceProperties::~interfaceProperties() { if (h_) mi_interface_destroy(h_); }
+void interfaceProperties::sigmaK(scalargpuField& out) const { fieldAxpby(out, sigma_, K_, 0.0, K_); }
+void interfaceProperties::surfaceTensionForce(scalargpuField& out, const scalargpuField& alpha1, const scalargpuField* snGradCorr) const
+{
+    miCheck(mi_surface_tension_force(mesh_.addr->handle(), sigma_, mesh_.weights->data(), mesh_.deltaCoeffs->data(), K_.data(), alpha1.data(),
+                                     snGradCorr ? snGradCorr->data() : nullptr, out.data()), "interfaceProperties::surfaceTensionForce");
+}
+void interfaceProperties::patchSurfaceTensionForce(scalargpuField& out, label patchi, const scalargpuField& pDeltaCoeffs, const scalargpuField& nbrK,
+                                                   const scalargpuField& alpha1, const scalargpuField& nbrAlpha1, const scalargpuField* pSnGradCorr) const
+{
+    const patchData& p = patches_[(size_t)patchi];
+    if (!p.weights) FatalErrorIn("interfaceProperties::surfaceTensionForce", "the patch is not coupled: the product of two boundary fields is the caller's");
+    miCheck(mi_patch_surface_tension_force(p.cells->handle(), sigma_, p.weights->data(), pDeltaCoeffs.data(), K_.data(), nbrK.data(), alpha1.data(),
+                                           nbrAlpha1.data(), pSnGradCorr ? pSnGradCorr->data() : nullptr, out.data()),
+            "interfaceProperties::surfaceTensionForce (coupled patch)");
+}
+void interfaceProperties::nearInterface(scalargpuField& out, const scalargpuField& alpha1) const
+{
+    miCheck(mi_near_interface(miEngine::New().ctx, alpha1.size(), alpha1.data(), out.data()), "interfaceProperties::nearInterface");
+}
+void interfaceProperties::calculateK(const vectorgpuField& gradAlpha, const std::vector<const vectorgpuField*>& bGradAlpha,
+                                     const std::vector<scalargpuField*>& gradientOut)
+{
+    if (bGradAlpha.size() != patches_.size()) FatalErrorIn("interfaceProperties::calculateK", "one boundary gradient per patch");
+    const auto sf = cmptData(*mesh_.Sf);
+    const auto g = cmptData(gradAlpha);
+    miCheck(mi_interface_nhatf(mesh_.addr->handle(), deltaN_, mesh_.weights->data(), sf, g, nHatf_.data(), nullptr), "interfaceProperties::calculateK");
+    label off = 0;
+    for (size_t i = 0; i < patches_.size(); ++i) {
+        const patchData& p = patches_[i];
+        mi_patch_nhatf x{};
+        const auto ps = cmptData(*p.Sf);
+        const auto bg = cmptData(*bGradAlpha[i]);
+        for (int d = 0; d < 3; ++d) {
+            x.patch_sf_dev[d] = ps[d];
+            x.grad_dev[d] = p.weights ? g[d] : bg[d];
+            x.nbr_grad_dev[d] = p.weights ? bg[d] : nullptr;
+        }
+        x.patch_weights_dev = p.weights ? p.weights->data() : nullptr;
+        if (p.thetaDeg) {                             // correctContactAngle (:69-114)
+            x.theta_deg_dev = p.thetaDeg->data();
+            x.patch_magsf_dev = p.magSf ? p.magSf->data() : nullptr;
+            if (i < gradientOut.size() && gradientOut[i]) x.gradient_out_dev = gradientOut[i]->data();
+        }
+        x.nhatf_out_dev = nHatfb_.data() + off;
+        miCheck(mi_patch_interface_nhatf(p.cells->handle(), deltaN_, &x), "interfaceProperties::calculateK (patch)");
+        off += p.cells->size();
+    }
+    miCheck(mi_interface_curvature(h_, nHatf_.data(), nHatfb_.data(), mesh_.V->data(), K_.data()), "interfaceProperties::calculateK (K)");
+}
+void interfaceProperties::correct(const vectorgpuField& gradAlpha, const std::vector<const vectorgpuField*>& bGradAlpha,
+                                  const std::vector<scalargpuField*>& gradientOut)
+{
+    calculateK(gradAlpha, bGradAlpha, gradientOut);
+}
+
 // ---- Pstream: the parallel run as this path sees it -------------------------------------------------------------
 namespace {
 struct PstreamState { bool par = false; int rank = 0, n = 1; mi_comm_t red = nullptr, halo = nullptr; };
