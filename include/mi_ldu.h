@@ -681,8 +681,8 @@ int mi_ls_grad(mi_ls_vectors_t lsv, int32_t n_comp, const double *const *vf_dev,
  * Refused (MI_ERR_ARG, nothing launched, nothing written): n_rhs outside 1..4, a mode other than the two, a missing array or one not
  *   aligned for a double, a boundary built for another addressing, NULL boundary arrays while the boundary has faces, an output that aliases
  *   an input or another output.  Zero cells: MI_OK, nothing written.  Zero internal faces is legal (the face arrays may be NULL).
- * Out of scope: reconstruct of a surfaceVectorField (tensor result), fvc::reconstructMag, fvc::average, fvc::curl, a Courant-number entry
- *   (it needs a max reduction), moving meshes. */
+ * Out of scope: reconstruct of a surfaceVectorField (tensor result), fvc::reconstructMag, fvc::curl, a Courant-number entry (its max
+ *   is mi_min_max below), moving meshes. */
 typedef struct mi_reconstruct_s *mi_reconstruct_t;
 enum { MI_SURFACE_SUM, MI_SURFACE_SUM_MAG };
 int mi_surface_sum(mi_addr_t addr, int32_t mode, const double *ssf_dev, double *out_dev);
@@ -875,6 +875,109 @@ int mi_patch_surface_tension_force(mi_patch_t patch, double sigma, const double 
                                    const double *k_dev, const double *nbr_k_dev, const double *alpha_dev, const double *nbr_alpha_dev,
                                    const double *patch_sngrad_corr_dev_or_null, double *out_dev);
 int mi_near_interface(mi_ctx_t ctx, int64_t n, const double *alpha_dev, double *out_dev);
+/* ---- the kEpsilon turbulence model: G, the wall functions, bound and nut (turbulenceModels/incompressible/RAS/kEpsilon/kEpsilon.C:132-136,
+ *      :229-280; epsilonWallFunctionFvPatchScalarField.C:116-396, :540-589; nutkWallFunctionFvPatchScalarField.C:60-77; bound.C:32-60;
+ *      fvcAverage.C:71-74) ----
+ * What incompressible::RASModels::kEpsilon::correct() runs as about forty field passes is eight kernels of this block, four mi_min_max
+ * reductions for the two bound decisions and three launches per bound that has to act, beside the assembly, relaxation, setValues, solve
+ * and boundary evaluation of every transport equation (DESIGN 3.5o counts them).  All values are fp64, all labels int32.  Every operator is rounded on its own except the fma written below; division and
+ * square root are the correctly rounded IEEE ones; max(a, b) = (a > b) ? a : b and pos(x) = (x >= 0) ? 1 : 0 throughout.  A cell meets its
+ * faces in the order of mi_surface_sum / mi_interface_curvature: own faces ascending, neighbour-side faces in losort order, boundary faces
+ * patch by patch.  Restated in tests/turbulence_support.py, not pinned by a compiled reference.
+ * mi_ke_coeffs_init (host only, no GPU): Cmu25 = sqrt(sqrt(Cmu)) (pow025), Cmu75 = pow(Cmu, 0.75), yPlusLam = ten iterations of
+ *   ypl = log(max(E*ypl, 1))/kappa from 11.0 (nutWallFunctionFvPatchScalarField.C:154-167) with the host's libm.  The reference's defaults are
+ *   0.09, 1.44, 1.92, 1.3, 0.41, 9.8.  An entry that takes a mi_ke_coeffs refuses one with a non-finite or non-positive member.
+ * mi_min_max: the smallest and the largest of n values to the host (either output may be NULL): what bound's test (bound.C:35-37) and a
+ *   Courant number need.  Order-independent, hence exact; n == 0 gives +inf / -inf.  The inputs are assumed finite: the result for a NaN
+ *   among them is unspecified, and so is the sign of a zero result when both zeros occur.  Synchronises the context's stream.
+ * mi_vec_max_value: out = max(x, value); out may be x.  The boundary line of bound (:56).
+ * mi_average_create / mi_average_destroy: the handle of fvc::average on one mesh: it keeps surfaceSum(magSf) per cell and one scratch cell
+ *   array.  boundary NULL: no boundary faces; otherwise it must outlive the handle.  mag_sf_dev: internal faces; b_mag_sf_dev: the
+ *   patch-ordered boundary faces of `boundary`.  After mesh motion: destroy and create.
+ * mi_fvc_average: out = surfaceSum(magSf*ssf)/surfaceSum(magSf): each product rounded, then added in the order above; one division per
+ *   cell; one row pass.  A cell without faces gives 0/0.
+ * mi_bound: bound.C:45-54 for the internal field in ONE row pass that writes no face field.  Per face, with m = max(v, lb) on both sides,
+ *   i = fma(lambda, mP - mN, mN) (the rule of mi_face_interpolate); avg as mi_fvc_average forms it, the boundary faces taking b_face_dev;
+ *   then v = max(max(v, avg*pos(-v)), lb).  b_face_dev: the patch-ordered boundary values of linearInterpolate(max(vsf, lb)), the caller's:
+ *   mi_vec_max_value on the boundary values, and on coupled patches w*mP + (1 - w)*mNbr.  A cell reads its neighbours' OLD values: the pass
+ *   writes the handle's scratch array and copies it back, so the result has the bits of the out-of-place sequence mi_vec_max_value +
+ *   mi_face_interpolate + mi_fvc_average + the cell algebra.  Whether to bound at all (min(vsf) < lb, :35-37) is the caller's decision, made
+ *   with mi_min_max on the internal and the boundary values.
+ * mi_ke_production (:238): G = (nut*2)*magSqr(symm(gradU)) in one cell pass over grad_dev[3*j + k] = d(U_j)/dx_k, the nine arrays of
+ *   mi_limited_grad's layout.  symm: xy = 0.5*(g_xy + g_yx), likewise xz and yz.  magSqr (SymmTensorI.H:276-284), left to right:
+ *     s = fma(xx, xx, 2*(xy*xy)); s = fma(2, xz*xz, s); s = fma(yy, yy, s); s = fma(2, yz*yz, s); s = fma(zz, zz, s)
+ *   -- the squares of the diagonal contracted into the running sum, the doubled squares rounded first (doubling is exact, so fma(2, q, s)
+ *   is s + 2*q): an ASSUMPTION, see DESIGN 3.5o.  (nut*2)*s equals nut*(2*s): doubling is exact.
+ * mi_ke_create / mi_ke_destroy: the wall cells of one mesh, built once on the host from `boundary` and patch_is_wall[p] != 0 per patch: the
+ *   union of the cells of the flagged patches, ascending; per such cell its wall faces by patch, then by face; cornerWeight =
+ *   1.0/(wall faces of the cell) (epsilonWallFunctionFvPatchScalarField.C:146-200).  The boundary must outlive the handle.
+ * mi_ke_wall_cells (:241): epsilon.boundaryField().updateCoeffs() for ALL wall patches in ONE launch, no atomics.  Every b_* array of
+ *   mi_ke_wall is patch-ordered over `boundary`; only wall faces are read or written.  Per unique wall cell c, Gc and ec start at 0.0 and its
+ *   wall faces are visited in (patch, face) order:
+ *     sn_k = dc*(Uw_k - U_k[c]);  mgu = sqrt(fma(sn_z, sn_z, fma(sn_x, sn_x, sn_y*sn_y)))     (mag: the contraction of 3.5a, an assumption)
+ *     ec += ((w*Cmu75)*pow(k[c], 1.5))/(kappa*y)
+ *     Gc += ((((w*(nutw + nuw))*mgu)*Cmu25)*sqrt(k[c]))/(kappa*y)
+ *   then g_inout[c] = Gc, eps_inout[c] = ec and b_eps_out[face] = ec for each of the cell's wall faces (the zero-gradient assignment
+ *   :245-253).  Cells that are not wall cells keep their G and epsilon.  pow is the device library's fp64 pow, evaluated once per cell;
+ *   b_pow_out_dev, when given, receives it per wall face (for tests).
+ * mi_ke_wall_cell_labels: the unique wall cells on the device, ascending; boundaryManipulate (:255) is mi_fvm_set_values with them and with
+ *   the values mi_ke_wall_values gathers (values_out[i] = eps[label[i]]).
+ * mi_ke_epsilon_terms (:250-251, DepsilonEff): su = ((C1*G)*eps)/k, sp = (C2*eps)/k, deps = nut/sigmaEps + nu in one cell pass; nu a cell
+ *   array, or nu_value when nu_dev_or_null is NULL.  mi_ke_k_terms (:269, DkEff): sp = eps/k, dk = nut + nu.  su and sp are what
+ *   mi_fvm_assemble takes as su_dev and sp_dev; deps / dk go through mi_face_interpolate into mi_fvm_laplacian's gammaMagSf; G itself is
+ *   the su of the k equation.
+ * mi_ke_nut (:135, :278): nut = (Cmu*(k*k))/eps.  mi_ke_nut_wall: nutkWallFunction::calcNut on every wall face in one launch:
+ *   yPlus = ((Cmu25*y)*sqrt(k[c]))/nuw; yPlus > yPlusLam: nutw = nuw*(((yPlus*kappa)/log(E*yPlus)) - 1.0); otherwise exactly 0.
+ *   b_log_out_dev_or_null receives the device library's log where the branch is taken and is not written elsewhere (for tests).
+ *   kqRWallFunction is zero-gradient: mi_patch_internal_field.
+ * The cell passes take two cells per thread with 16-byte accesses when every array is 16-byte aligned, one by one otherwise; they and the
+ *   wall passes run under the context's launch-grid cap (MI_FACE_GRID).
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): missing arrays; an output that aliases an input or another output (except
+ *   mi_vec_max_value's out and mi_bound's vsf_inout); an array not aligned for a double; a handle or boundary of another addressing; NULL
+ *   boundary arrays while the boundary has faces; patch_is_wall flagging a coupled patch; a coefficient that is not finite or not above zero;
+ *   a lower bound that is not a number.
+ *   mi_min_max during a PCG session: MI_ERR_STATE.  Zero cells, zero wall faces and zero wall patches: MI_OK.
+ * Out of scope: kOmegaSST and every model that needs the wall-distance field (wallDist / meshWave); the low-Re and rough wall functions;
+ *   the nutU* wall functions; the weighted (weights) forms of the epsilon wall function; compressible kEpsilon (rho-weighted); LES models;
+ *   a pisoFoam / simpleFoam application; moving meshes; nearWallDist (y is the caller's patch array). */
+typedef struct mi_ke_coeffs {
+    double Cmu, C1, C2, sigmaEps, kappa, E;
+    double Cmu25, Cmu75, yPlusLam;            /* derived: mi_ke_coeffs_init */
+} mi_ke_coeffs;
+typedef struct mi_ke_wall {
+    const double *k_dev;
+    const double *u_dev[3];
+    const double *b_uw_dev[3];                /* the boundary face values of U */
+    const double *b_delta_coeffs_dev, *b_y_dev, *b_nuw_dev, *b_nutw_dev;
+    double *g_inout_dev, *eps_inout_dev;      /* cell fields: the wall cells are overwritten */
+    double *b_eps_out_dev;
+    double *b_pow_out_dev;                    /* or NULL */
+} mi_ke_wall;
+typedef struct mi_average_s *mi_average_t;
+typedef struct mi_ke_s *mi_ke_t;
+int mi_ke_coeffs_init(double Cmu, double C1, double C2, double sigmaEps, double kappa, double E, mi_ke_coeffs *out);
+int mi_min_max(mi_ctx_t ctx, int64_t n, const double *x_dev, double *min_out_host, double *max_out_host);
+int mi_vec_max_value(mi_ctx_t ctx, int64_t n, const double *x_dev, double value, double *out_dev);
+int mi_average_create(mi_addr_t addr, mi_grad_boundary_t boundary_or_null, const double *mag_sf_dev, const double *b_mag_sf_dev, mi_average_t *out);
+int mi_average_destroy(mi_average_t average);
+int mi_fvc_average(mi_average_t average, const double *mag_sf_dev, const double *b_mag_sf_dev, const double *ssf_dev, const double *b_ssf_dev,
+                   double *out_dev);
+int mi_bound(mi_average_t average, double lower_bound, const double *lambda_dev, const double *mag_sf_dev, const double *b_mag_sf_dev,
+             const double *b_face_dev, double *vsf_inout_dev);
+int mi_ke_production(mi_ctx_t ctx, int64_t n, const double *nut_dev, const double *const *grad_dev, double *g_out_dev);
+int mi_ke_create(mi_addr_t addr, mi_grad_boundary_t boundary, const int32_t *patch_is_wall, mi_ke_t *out);
+int mi_ke_destroy(mi_ke_t ke);
+int mi_ke_wall_cells(mi_ke_t ke, const mi_ke_coeffs *coeffs, const mi_ke_wall *arrays);
+int mi_ke_wall_cell_labels(mi_ke_t ke, int32_t *n_out, const int32_t **labels_dev_out);
+int mi_ke_wall_values(mi_ke_t ke, const double *eps_dev, double *values_out_dev);
+int mi_ke_epsilon_terms(mi_ctx_t ctx, int64_t n, const mi_ke_coeffs *coeffs, const double *g_dev, const double *eps_dev, const double *k_dev,
+                        const double *nut_dev, const double *nu_dev_or_null, double nu_value, double *su_out_dev, double *sp_out_dev,
+                        double *deps_out_dev);
+int mi_ke_k_terms(mi_ctx_t ctx, int64_t n, const double *eps_dev, const double *k_dev, const double *nut_dev, const double *nu_dev_or_null,
+                  double nu_value, double *sp_out_dev, double *dk_out_dev);
+int mi_ke_nut(mi_ctx_t ctx, int64_t n, double Cmu, const double *k_dev, const double *eps_dev, double *nut_out_dev);
+int mi_ke_nut_wall(mi_ke_t ke, const mi_ke_coeffs *coeffs, const double *k_dev, const double *b_y_dev, const double *b_nuw_dev,
+                   double *b_nutw_out_dev, double *b_log_out_dev_or_null);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

@@ -17,6 +17,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <set>
 #include <mutex>
 #include <string>
@@ -2506,6 +2507,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "reconstruct.inc"
 #include "mules.inc"
 #include "interface.inc"
+#include "turbulence.inc"
 
 mi_matrix_s::~mi_matrix_s()
 {

@@ -379,8 +379,8 @@ int mu_check(const std::string& who, mi_mules_s* h, const mi_mules_fields* fl, c
 const int kMuFB[8] = {MU_FACE, MU_BFACE, MU_FACE, MU_BFACE, MU_FACE, MU_BFACE, MU_FACE, MU_BFACE};
 
 // a row pass of `arrays` staged face arrays on the gradient's plan
-template <class K>
-int mu_row_launch(mi_addr_s* a, int arrays, K k256, K k512, K k1024, MuArgs& q)
+template <class K, class A>
+int mu_row_launch(mi_addr_s* a, int arrays, K k256, K k512, K k1024, A& q)
 {
     const mi_addr_s::RowPlan& rp = a->rowPlan[1];
     q.r.cap = row_cap(rp, arrays);

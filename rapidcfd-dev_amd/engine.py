@@ -88,6 +88,9 @@ SYMBOLS = [
     "mi_alpha_compression_flux", "mi_patch_alpha_compression_flux",
     "mi_interface_nhatf", "mi_patch_interface_nhatf", "mi_interface_create", "mi_interface_destroy", "mi_interface_curvature",
     "mi_surface_tension_force", "mi_patch_surface_tension_force", "mi_near_interface",
+    "mi_ke_coeffs_init", "mi_min_max", "mi_vec_max_value", "mi_average_create", "mi_average_destroy", "mi_fvc_average", "mi_bound",
+    "mi_ke_production", "mi_ke_create", "mi_ke_destroy", "mi_ke_wall_cells", "mi_ke_wall_cell_labels", "mi_ke_wall_values",
+    "mi_ke_epsilon_terms", "mi_ke_k_terms", "mi_ke_nut", "mi_ke_nut_wall",
 ]
 
 
@@ -1448,6 +1451,110 @@ class Interface:
             self.h = C.c_void_p()
 
 
+class KeCoeffs(C.Structure):
+    """mi_ke_coeffs (include/mi_ldu.h)"""
+    _fields_ = [(name, C.c_double) for name in ("Cmu", "C1", "C2", "sigmaEps", "kappa", "E", "Cmu25", "Cmu75", "yPlusLam")]
+
+
+def ke_coeffs(Cmu=0.09, C1=1.44, C2=1.92, sigmaEps=1.3, kappa=0.41, E=9.8) -> KeCoeffs:
+    """mi_ke_coeffs_init: kEpsilon's coefficients with Cmu25, Cmu75 and yPlusLam derived (host only, no GPU)"""
+    out = KeCoeffs()
+    _chk(lib().mi_ke_coeffs_init(C.c_double(Cmu), C.c_double(C1), C.c_double(C2), C.c_double(sigmaEps), C.c_double(kappa), C.c_double(E), C.byref(out)))
+    return out
+
+
+class KeWall(C.Structure):
+    """mi_ke_wall (include/mi_ldu.h)"""
+    _fields_ = [("k_dev", C.c_void_p), ("u_dev", C.c_void_p * 3), ("b_uw_dev", C.c_void_p * 3), ("b_delta_coeffs_dev", C.c_void_p),
+                ("b_y_dev", C.c_void_p), ("b_nuw_dev", C.c_void_p), ("b_nutw_dev", C.c_void_p), ("g_inout_dev", C.c_void_p),
+                ("eps_inout_dev", C.c_void_p), ("b_eps_out_dev", C.c_void_p), ("b_pow_out_dev", C.c_void_p)]
+
+
+class Average:
+    """fvc::average on one mesh (mi_average_create): keeps surfaceSum(magSf) per cell.  boundary a GradBoundary or None (no boundary faces); it
+    must stay open as long as the handle is used.  mag_sf internal faces, b_mag_sf the patch-ordered boundary faces."""
+
+    def __init__(self, addr: Addressing, boundary, mag_sf, b_mag_sf=None):
+        self.addr, self.boundary = addr, boundary
+        self.h = C.c_void_p()
+        _chk(lib().mi_average_create(addr.h, boundary.h if boundary is not None else None, _ptr(mag_sf), _ptr(b_mag_sf), C.byref(self.h)))
+
+    def fvc_average(self, mag_sf, ssf, out, b_mag_sf=None, b_ssf=None):
+        """out = surfaceSum(magSf*ssf)/surfaceSum(magSf) in one row pass (mi_fvc_average)"""
+        _chk(lib().mi_fvc_average(self.h, _ptr(mag_sf), _ptr(b_mag_sf), _ptr(ssf), _ptr(b_ssf), _ptr(out)))
+
+    def bound(self, lower_bound, lam, mag_sf, vsf_inout, b_mag_sf=None, b_face=None):
+        """bound.C:45-54 on the internal field in one row pass (mi_bound): b_face the boundary values of linearInterpolate(max(vsf, lb))"""
+        _chk(lib().mi_bound(self.h, C.c_double(lower_bound), _ptr(lam), _ptr(mag_sf), _ptr(b_mag_sf), _ptr(b_face), _ptr(vsf_inout)))
+
+    def close(self):
+        if self.h:
+            lib().mi_average_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class DeviceLabels:
+    """int32 labels on the device that a handle owns, in the shape Assembly.set_values takes its cell_labels"""
+
+    def __init__(self, n, address, owner):
+        self.n, self.address, self.owner = int(n), int(address or 0), owner
+
+    def numel(self):
+        return self.n
+
+    def data_ptr(self):
+        return self.address
+
+    def is_contiguous(self):
+        return True
+
+    def element_size(self):
+        return 4
+
+
+class KEpsilon:
+    """The wall cells of one mesh (mi_ke_create): boundary a GradBoundary, patch_is_wall one flag per patch (a coupled patch is refused).
+    The boundary must stay open as long as the handle is used."""
+
+    def __init__(self, addr: Addressing, boundary, patch_is_wall: Sequence):
+        self.addr, self.boundary = addr, boundary
+        flags = (C.c_int32 * max(len(patch_is_wall), 1))(*[int(bool(x)) for x in patch_is_wall])
+        self.h = C.c_void_p()
+        _chk(lib().mi_ke_create(addr.h, boundary.h if boundary is not None else None, flags, C.byref(self.h)))
+
+    def wall_cell_labels(self):
+        """-> the labels of the unique wall cells, ascending, on the device and owned by the handle (mi_ke_wall_cell_labels): what
+        Assembly.set_values takes for boundaryManipulate"""
+        n, p = C.c_int32(0), C.c_void_p()
+        _chk(lib().mi_ke_wall_cell_labels(self.h, C.byref(n), C.byref(p)))
+        return DeviceLabels(n.value, p.value, self)
+
+    def wall_cells(self, coeffs: KeCoeffs, k, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw, g_inout, eps_inout, b_eps_out, b_pow_out=None):
+        """epsilon.boundaryField().updateCoeffs() for every wall patch in one launch (mi_ke_wall_cells): u / b_uw [x, y, z], every b_* array
+        patch-ordered over the boundary"""
+        x = KeWall()
+        x.k_dev = _ptr(k).value
+        for d in range(3):
+            x.u_dev[d] = _ptr(None if u is None else u[d]).value
+            x.b_uw_dev[d] = _ptr(None if b_uw is None else b_uw[d]).value
+        x.b_delta_coeffs_dev, x.b_y_dev, x.b_nuw_dev, x.b_nutw_dev = (_ptr(t).value for t in (b_delta_coeffs, b_y, b_nuw, b_nutw))
+        x.g_inout_dev, x.eps_inout_dev, x.b_eps_out_dev, x.b_pow_out_dev = (_ptr(t).value for t in (g_inout, eps_inout, b_eps_out, b_pow_out))
+        _chk(lib().mi_ke_wall_cells(self.h, C.byref(coeffs) if coeffs is not None else None, C.byref(x)))
+
+    def wall_values(self, eps, values_out):
+        """values_out[i] = eps[label[i]] (mi_ke_wall_values): the values of boundaryManipulate's setValues"""
+        _chk(lib().mi_ke_wall_values(self.h, _ptr(eps), _ptr(values_out)))
+
+    def nut_wall(self, coeffs: KeCoeffs, k, b_y, b_nuw, b_nutw_out, b_log_out=None):
+        """nutkWallFunction::calcNut on every wall face in one launch (mi_ke_nut_wall)"""
+        _chk(lib().mi_ke_nut_wall(self.h, C.byref(coeffs) if coeffs is not None else None, _ptr(k), _ptr(b_y), _ptr(b_nuw), _ptr(b_nutw_out), _ptr(b_log_out)))
+
+    def close(self):
+        if self.h:
+            lib().mi_ke_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Assembly:
     """fvm::div / fvm::laplacian / negSumDiag / relax ... on caller-order arrays of an Addressing."""
 
@@ -1732,6 +1839,57 @@ class Assembly:
         """out = pos(alpha - 0.01)*pos(0.99 - alpha) (mi_near_interface)"""
         n = (alpha if alpha is not None else out).numel()
         _chk(lib().mi_near_interface(self.addr.ctx.h, C.c_int64(n), _ptr(alpha), _ptr(out)))
+
+    def min_max(self, x):
+        """-> (min, max) of a device array on the host (mi_min_max); an empty array gives (+inf, -inf)"""
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        _chk(lib().mi_min_max(self.addr.ctx.h, C.c_int64(0 if x is None else x.numel()), _ptr(x), C.byref(lo), C.byref(hi)))
+        return float(lo.value), float(hi.value)
+
+    def vec_max_value(self, x, value, out):
+        """out = max(x, value), out may be x (mi_vec_max_value): the boundary line of bound"""
+        n = (x if x is not None else out).numel()
+        _chk(lib().mi_vec_max_value(self.addr.ctx.h, C.c_int64(n), _ptr(x), C.c_double(value), _ptr(out)))
+
+    def fvc_average(self, average, mag_sf, ssf, out, b_mag_sf=None, b_ssf=None):
+        """fvc::average(ssf) over an Average handle of this addressing (mi_fvc_average)"""
+        average.fvc_average(mag_sf, ssf, out, b_mag_sf, b_ssf)
+
+    def bound(self, average, lower_bound, lam, mag_sf, vsf_inout, b_mag_sf=None, b_face=None):
+        """bound.C:45-54 on the internal field over an Average handle of this addressing (mi_bound)"""
+        average.bound(lower_bound, lam, mag_sf, vsf_inout, b_mag_sf, b_face)
+
+    def ke_production(self, nut, grad, g_out):
+        """G = (nut*2)*magSqr(symm(gradU)) in one cell pass (mi_ke_production): grad the nine cell arrays d(U_j)/dx_k at 3*j + k"""
+        pv = None if grad is None else (C.c_void_p * 9)(*[_ptr(x) for x in grad])
+        n = (nut if nut is not None else g_out).numel()
+        _chk(lib().mi_ke_production(self.addr.ctx.h, C.c_int64(n), _ptr(nut), pv, _ptr(g_out)))
+
+    def ke_wall_cells(self, ke, coeffs, k, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw, g_inout, eps_inout, b_eps_out, b_pow_out=None):
+        """the epsilon wall function on every wall patch over a KEpsilon handle of this addressing (mi_ke_wall_cells)"""
+        ke.wall_cells(coeffs, k, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw, g_inout, eps_inout, b_eps_out, b_pow_out)
+
+    def ke_epsilon_terms(self, coeffs, g, eps, k, nut, nu, su_out, sp_out, deps_out):
+        """su = C1*G*eps/k, sp = C2*eps/k, deps = nut/sigmaEps + nu in one cell pass (mi_ke_epsilon_terms); nu a cell array or a number"""
+        nu_dev, nu_value = (None, float(nu)) if isinstance(nu, (int, float)) else (nu, 0.0)
+        n = (k if k is not None else su_out).numel()
+        _chk(lib().mi_ke_epsilon_terms(self.addr.ctx.h, C.c_int64(n), C.byref(coeffs) if coeffs is not None else None, _ptr(g), _ptr(eps), _ptr(k),
+                                       _ptr(nut), _ptr(nu_dev), C.c_double(nu_value), _ptr(su_out), _ptr(sp_out), _ptr(deps_out)))
+
+    def ke_k_terms(self, eps, k, nut, nu, sp_out, dk_out):
+        """sp = eps/k, dk = nut + nu in one cell pass (mi_ke_k_terms); nu a cell array or a number"""
+        nu_dev, nu_value = (None, float(nu)) if isinstance(nu, (int, float)) else (nu, 0.0)
+        n = (k if k is not None else sp_out).numel()
+        _chk(lib().mi_ke_k_terms(self.addr.ctx.h, C.c_int64(n), _ptr(eps), _ptr(k), _ptr(nut), _ptr(nu_dev), C.c_double(nu_value), _ptr(sp_out), _ptr(dk_out)))
+
+    def ke_nut(self, Cmu, k, eps, nut_out):
+        """nut = Cmu*sqr(k)/eps (mi_ke_nut)"""
+        n = (k if k is not None else nut_out).numel()
+        _chk(lib().mi_ke_nut(self.addr.ctx.h, C.c_int64(n), C.c_double(Cmu), _ptr(k), _ptr(eps), _ptr(nut_out)))
+
+    def ke_nut_wall(self, ke, coeffs, k, b_y, b_nuw, b_nutw_out, b_log_out=None):
+        """nutkWallFunction on every wall face over a KEpsilon handle of this addressing (mi_ke_nut_wall)"""
+        ke.nut_wall(coeffs, k, b_y, b_nuw, b_nutw_out, b_log_out)
 
     def vec_min(self, x, y, out):
         """out = min(x, y) element by element, out may alias either (mi_vec_min): minOp over the two sides of a cyclic pair"""

@@ -1243,6 +1243,182 @@ interfaceProperties::interfaceProperties(const meshData& mesh, const std::vector
     miCheck(mi_interface_create(mesh.addr->handle(), mesh.boundary ? mesh.boundary->handle() : nullptr, &h_), "interfaceProperties::New");
 }
 interfaceProperties::~interfaceProperties() { if (h_) mi_interface_destroy(h_); }
+averageData::averageData(const lduAddressing& a, const gradBoundary* b, const scalargpuField& magSf, const scalargpuField* bMagSf)
+    : h_(nullptr), magSf_(&magSf), bMagSf_(bMagSf)
+{
+    miCheck(mi_average_create(a.handle(), b ? b->handle() : nullptr, magSf.data(), bMagSf ? bMagSf->data() : nullptr, &h_), "averageData::New");
+}
+averageData::~averageData() { if (h_) mi_average_destroy(h_); }
+void fvc::average(scalargpuField& out, const averageData& av, const scalargpuField& ssf, const scalargpuField* bssf)
+{
+    miCheck(mi_fvc_average(av.handle(), av.magSf().data(), av.bMagSf() ? av.bMagSf()->data() : nullptr, ssf.data(), bssf ? bssf->data() : nullptr,
+                           out.data()), "fvc::average");
+}
+bool bound(scalargpuField& vsf, scalargpuField* bvsf, const averageData& av, const scalargpuField& weights, scalar lowerBound)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    scalar minVsf = 0, minB = 0;
+    miCheck(mi_min_max(ctx, vsf.size(), vsf.data(), &minVsf, nullptr), "bound");
+    miCheck(mi_min_max(ctx, bvsf ? bvsf->size() : 0, bvsf ? bvsf->data() : nullptr, &minB, nullptr), "bound");   // no faces: +inf
+    if (!(std::min(minVsf, minB) < lowerBound)) return false;
+    if (bvsf) miCheck(mi_vec_max_value(ctx, bvsf->size(), bvsf->data(), lowerBound, bvsf->data()), "bound");
+    miCheck(mi_bound(av.handle(), lowerBound, weights.data(), av.magSf().data(), av.bMagSf() ? av.bMagSf()->data() : nullptr,
+                     bvsf ? bvsf->data() : nullptr, vsf.data()), "bound");
+    return true;
+}
+
+// ---- incompressible::RASModels::kEpsilon ------------------------------------------------------------------------------------------------
+namespace incompressible
+{
+namespace RASModels
+{
+kEpsilon::kEpsilon(const meshData& mesh, scalar nu, const scalargpuField& k, const scalargpuField& bk, const scalargpuField& epsilon,
+                   const scalargpuField& bepsilon, const dictionary& coeffDict, scalar kMin, scalar epsilonMin)
+    : mesh_(mesh), nu_(nu), kMin_(kMin), epsilonMin_(epsilonMin), h_(nullptr), nb_(bk.size()), k_(k), epsilon_(epsilon), nut_(k.size()), bk_(bk),
+      bepsilon_(bepsilon), bnut_(bk.size()), bnu_(std::vector<scalar>((std::size_t)bk.size(), nu))
+{
+    const char* who = "kEpsilon::New";
+    if (!mesh.addr || !mesh.boundary || !mesh.average) FatalErrorIn(who, "the addressing, the boundary and the averageData are needed");
+    if (mesh.patchTypes.size() != mesh.patchFaceCells.size()) FatalErrorIn(who, "one type per patch");
+    scalar Cmu = 0.09, C1 = 1.44, C2 = 1.92, sigmaEps = 1.3, kappa = 0.41, E = 9.8;      // kEpsilon.C:50-86, nutWallFunction's kappa and E
+    coeffDict.readIfPresent("Cmu", Cmu); coeffDict.readIfPresent("C1", C1); coeffDict.readIfPresent("C2", C2);
+    coeffDict.readIfPresent("sigmaEps", sigmaEps); coeffDict.readIfPresent("kappa", kappa); coeffDict.readIfPresent("E", E);
+    miCheck(mi_ke_coeffs_init(Cmu, C1, C2, sigmaEps, kappa, E, &coeffs_), who);
+    std::vector<int32_t> wall;
+    label off = 0;
+    for (std::size_t p = 0; p < mesh.patchFaceCells.size(); ++p) {
+        wall.push_back(mesh.patchTypes[p] == wallFunction ? 1 : 0);
+        start_.push_back(off);
+        patches_.emplace_back(new fvPatchCells(mesh.addr->size(), mesh.patchFaceCells[p]));
+        off += (label)mesh.patchFaceCells[p].size();
+    }
+    start_.push_back(off);
+    if (off != nb_ || bepsilon.size() != nb_) FatalErrorIn(who, "the boundary fields do not have one value per boundary face");
+    miCheck(mi_ke_create(mesh.addr->handle(), mesh.boundary->handle(), wall.data(), &h_), who);
+    int32_t nWall = 0; const int32_t* labels = nullptr;
+    miCheck(mi_ke_wall_cell_labels(h_, &nWall, &labels), who);
+    labelgpuList cells(nWall);
+    if (nWall) miCopyD2D(cells.data(), labels, sizeof(label) * (std::size_t)nWall);
+    wallCells_.swap(cells);
+    bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);                  // :132
+    bound(epsilon_, &bepsilon_, *mesh_.average, *mesh_.weights, epsilonMin_); // :133
+    correctNut();                                                            // :135-136
+}
+kEpsilon::~kEpsilon() { if (h_) mi_ke_destroy(h_); }
+void kEpsilon::correctNut()
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    miCheck(mi_ke_nut(ctx, k_.size(), coeffs_.Cmu, k_.data(), epsilon_.data(), nut_.data()), "kEpsilon: nut");
+    miCheck(mi_ke_nut(ctx, nb_, coeffs_.Cmu, bk_.data(), bepsilon_.data(), bnut_.data()), "kEpsilon: nut");
+    miCheck(mi_ke_nut_wall(h_, &coeffs_, k_.data(), mesh_.y->data(), bnu_.data(), bnut_.data(), nullptr), "nutkWallFunction::calcNut");
+}
+void kEpsilon::evaluateBoundary(const scalargpuField& vf, scalargpuField& bvf) const
+{
+    for (std::size_t p = 0; p < patches_.size(); ++p)
+        if (mesh_.patchTypes[p] != fixedValue && patches_[p]->size() > 0)
+            miCheck(mi_patch_internal_field(patches_[p]->handle(), vf.data(), bvf.data() + start_[p]), "fvPatchField::evaluate");
+}
+void kEpsilon::nuEff(scalargpuField& out) const { DkEff(out); }
+void kEpsilon::DkEff(scalargpuField& out) const
+{
+    scalargpuField sp(k_.size());
+    miCheck(mi_ke_k_terms(miEngine::New().ctx, k_.size(), epsilon_.data(), k_.data(), nut_.data(), nullptr, nu_, sp.data(), out.data()), "kEpsilon::DkEff");
+}
+void kEpsilon::DepsilonEff(scalargpuField& out) const
+{
+    scalargpuField su(k_.size()), sp(k_.size());
+    miCheck(mi_ke_epsilon_terms(miEngine::New().ctx, k_.size(), &coeffs_, nut_.data(), epsilon_.data(), k_.data(), nut_.data(), nullptr, nu_, su.data(),
+                                sp.data(), out.data()), "kEpsilon::DepsilonEff");
+}
+void kEpsilon::divDevReff(fvVectorMatrix& UEqn, const vectorgpuField& Sf, const vectorgpuField* const gradU[3],
+                          const std::vector<fvc::devTGradPatch>& patches) const
+{
+    scalargpuField visc(k_.size());
+    nuEff(visc);
+    vectorgpuField div(k_.size());
+    fvc::divDevTGrad(div, *mesh_.addr, fvc::DEV, *mesh_.weights, Sf, visc, gradU, patches, *mesh_.V);
+    UEqn.subtractField(div, *mesh_.V);
+}
+solverPerformance kEpsilon::solveEquation(const word& name, scalargpuField& psi, const scalargpuField& bpsi, const scalargpuField& psiOld,
+                                          const scalargpuField& su, const scalargpuField& sp, const scalargpuField& gamma, scalar bGammaDivisor,
+                                          const flowData& flow, scalar rDeltaT, scalar alpha, bool manipulate, const dictionary& solverControls)
+{
+#pragma clang fp contract(off)
+    const lduAddressing& a = *mesh_.addr;
+    const label nf = mesh_.magSf->size();
+    // gammaMagSf = fvc::interpolate(gamma)*magSf: 0 - f*magSf, then the exact negation
+    scalargpuField f(nf), gammaMagSf(nf);
+    fvc::interpolate(f, a, *mesh_.weights, gamma);
+    fieldSubMul(gammaMagSf, f, *mesh_.magSf);
+    fieldAxpby(gammaMagSf, -1.0, gammaMagSf, 0.0, gammaMagSf);
+    std::vector<bool> coupled(mesh_.patchFaceCells.size(), false);
+    fvScalarMatrix M(name, a, mesh_.patchFaceCells, coupled);
+    mi_fvm_terms t{};
+    const double* po[1] = {psiOld.data()}; const double* sd[1] = {su.data()}; const double sg[1] = {-1.0}; double* so[1] = {M.source().data()};
+    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = 1.0; t.vol_dev = mesh_.V->data();
+    t.div_flux_dev = flow.phi->data(); t.div_weights_dev = (flow.divWeights ? flow.divWeights : mesh_.weights)->data();
+    t.lap_delta_coeffs_dev = mesh_.deltaCoeffs->data(); t.lap_gamma_magsf_dev = gammaMagSf.data();
+    t.sp_dev = sp.data(); t.sp_sign = 1.0;                  // == ... - fvm::Sp(sp, psi): diag += V*sp
+    t.n_rhs = 1; t.psi_old_dev = po; t.n_su = 1; t.su_dev = sd; t.su_sign = sg;   // == su: source += V*su
+    miCheck(mi_fvm_assemble(a.handle(), &t, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "kEpsilon: fvm::assemble");
+    // the patches: fixedValue: the diffusion coefficient and (diff - phi)*value; zeroGradient and the wall functions: the flux and nothing.
+    // The boundary value of gamma is nut/divisor + nu
+    const std::vector<scalar> bnut = bnut_.asHost(), bms = mesh_.bMagSf->asHost(), bdc = mesh_.bDeltaCoeffs->asHost(), bphi = flow.bPhi->asHost(),
+                              bval = bpsi.asHost();
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        const label m = start_[p + 1] - start_[p];
+        std::vector<scalar> ic((std::size_t)m), bc((std::size_t)m);
+        for (label i = 0; i < m; ++i) {
+            const std::size_t j = (std::size_t)(start_[p] + i);
+            if (mesh_.patchTypes[p] == fixedValue) {
+                const scalar q = bnut[j] / bGammaDivisor, g = q + nu_, gm = g * bms[j], diff = gm * bdc[j];
+                const scalar x = diff * bval[j], y = bphi[j] * bval[j];
+                ic[(std::size_t)i] = diff; bc[(std::size_t)i] = x - y;
+            } else { ic[(std::size_t)i] = bphi[j]; bc[(std::size_t)i] = 0.0; }
+        }
+        M.internalCoeffs()[p] = ic; M.boundaryCoeffs()[p] = bc;
+    }
+    M.relax(alpha, psi);
+    if (manipulate && wallCells_.size() > 0) {               // boundaryManipulate: epsilonWallFunction::manipulateMatrix
+        scalargpuField values(wallCells_.size());
+        miCheck(mi_ke_wall_values(h_, psi.data(), values.data()), "epsilonWallFunction::manipulateMatrix");
+        M.setValues(wallCells_, values, psi);
+    }
+    return M.solve(psi, solverControls);
+}
+void kEpsilon::correct(const flowData& flow, scalar rDeltaT, const dictionary& epsilonSolver, const dictionary& kSolver, scalar epsilonRelax,
+                       scalar kRelax)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const label n = k_.size();
+    // volScalarField G(GName(), nut_*2*magSqr(symm(fvc::grad(U_))))  (:238)
+    scalargpuField G(n);
+    const double* grad[9];
+    for (int j = 0; j < 3; ++j) for (int d = 0; d < 3; ++d) grad[3 * j + d] = flow.gradU[j]->component(d).data();
+    miCheck(mi_ke_production(ctx, n, nut_.data(), grad, G.data()), "kEpsilon::correct: G");
+    // epsilon_.boundaryField().updateCoeffs()  (:241)
+    const scalargpuField epsilonOld(epsilon_), kOld(k_);
+    mi_ke_wall w{};
+    w.k_dev = k_.data(); w.b_delta_coeffs_dev = mesh_.bDeltaCoeffs->data(); w.b_y_dev = mesh_.y->data(); w.b_nuw_dev = bnu_.data();
+    w.b_nutw_dev = bnut_.data(); w.g_inout_dev = G.data(); w.eps_inout_dev = epsilon_.data(); w.b_eps_out_dev = bepsilon_.data();
+    for (int d = 0; d < 3; ++d) { w.u_dev[d] = flow.U->component(d).data(); w.b_uw_dev[d] = flow.bU->component(d).data(); }
+    miCheck(mi_ke_wall_cells(h_, &coeffs_, &w), "epsilonWallFunction::updateCoeffs");
+    // the dissipation equation (:244-258)
+    scalargpuField su(n), sp(n), gamma(n);
+    miCheck(mi_ke_epsilon_terms(ctx, n, &coeffs_, G.data(), epsilon_.data(), k_.data(), nut_.data(), nullptr, nu_, su.data(), sp.data(), gamma.data()),
+            "kEpsilon::correct: epsEqn");
+    solveEquation("epsilon", epsilon_, bepsilon_, epsilonOld, su, sp, gamma, coeffs_.sigmaEps, flow, rDeltaT, epsilonRelax, true, epsilonSolver);
+    evaluateBoundary(epsilon_, bepsilon_);
+    bound(epsilon_, &bepsilon_, *mesh_.average, *mesh_.weights, epsilonMin_);
+    // the turbulent kinetic energy equation (:262-274)
+    miCheck(mi_ke_k_terms(ctx, n, epsilon_.data(), k_.data(), nut_.data(), nullptr, nu_, sp.data(), gamma.data()), "kEpsilon::correct: kEqn");
+    solveEquation("k", k_, bk_, kOld, G, sp, gamma, 1.0, flow, rDeltaT, kRelax, false, kSolver);
+    evaluateBoundary(k_, bk_);
+    bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);
+    correctNut();                                           // :278-279
+}
+}
+}
 void interfaceProperties::sigmaK(scalargpuField& out) const { fieldAxpby(out, sigma_, K_, 0.0, K_); }
 void interfaceProperties::surfaceTensionForce(scalargpuField& out, const scalargpuField& alpha1, const scalargpuField* snGradCorr) const
 {
