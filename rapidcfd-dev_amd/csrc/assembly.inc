@@ -1633,6 +1633,7 @@ extern "C" int mi_patch_flux(mi_patch_t p, const double* internal_coeffs_dev, co
 }
 
 namespace {
+bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }    // the checks of a call's arrays are in row_entry.inc
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // a streaming pass on the fixed RG x RB grid, on the context's stream
 template <class K, class... A>
@@ -2108,7 +2109,6 @@ extern "C" int mi_sngrad_parse(const char* text, mi_sngrad_scheme* out)
     return MI_OK;
 }
 namespace {
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 // the checks both limited passes share; fills the argument block.  in[]: every input array, for the aliasing test
 template <int NCOMP>
 int sngrad_limited_args(const std::string& who, double k, const double* cvx, const double* cvy, const double* cvz, const double* w, const double* dc,

@@ -2502,6 +2502,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "pcg_fused.inc"
 #include "gamg_engine.inc"
 #include "assembly.inc"
+#include "row_entry.inc"
 #include "limited_grad.inc"
 #include "least_squares.inc"
 #include "reconstruct.inc"

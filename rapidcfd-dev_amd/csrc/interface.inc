@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_patch_interface_nhatf(const NhArgs a)
 template <int BS>
 __global__ __launch_bounds__(BS) void k_interface_curvature(const MuArgs a)
 {
-    const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
+    const RowTables& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
     const double* const src[1] = {x.phiPsi};
     double s = 0.0;
     mu_rows<BS, 1>(r, src, [](int) {},
@@ -162,20 +162,9 @@ __global__ __launch_bounds__(RB) void k_near_interface(const double* alpha, doub
 } // namespace mi
 
 // the curvature's row pass on one mesh: the addressing's row tables and the boundary's per-cell face lists (the lists the MULES handle walks)
-struct mi_interface_s {
-    mi_ctx_s* ctx = nullptr;
-    mi_addr_s* addr = nullptr;
-    mi_grad_boundary_s* boundary = nullptr;
-    int32_t nCells = 0, nFaces = 0, nBFaces = 0;
-};
+struct mi_interface_s : RowHandle {};
 
 namespace {
-// every array of `in` present; every output present, distinct from every input and from the other outputs (ls_outputs)
-int if_outputs(const std::string& who, const double* const* in, int nIn, double* const* out, int nOut)
-{
-    for (int i = 0; i < nIn; ++i) if (!in[i]) return fail(MI_ERR_ARG, who + ": input arrays missing");
-    return ls_outputs(who, in, nIn, out, nOut);
-}
 int if_delta_n(const std::string& who, double deltaN)
 {
     if (!std::isfinite(deltaN) || !(deltaN > 0)) return fail(MI_ERR_ARG, who + ": delta_n must be a finite number above zero");
@@ -198,7 +187,8 @@ extern "C" int mi_interface_nhatf(mi_addr_t a, double delta_n, const double* lam
     double* out[4] = {nhatf_out_dev, nullptr, nullptr, nullptr};
     int nOut = 1;
     if (nhatfv_out_dev_or_null) for (int k = 0; k < 3; ++k) out[nOut++] = nhatfv_out_dev_or_null[k];
-    MICHK(if_outputs(who, in, 7, out, nOut));
+    MICHK(arrays_present(who, in, 7));
+    MICHK(outputs_distinct(who, in, 7, out, nOut));
     bool ok = true;
     for (int i = 0; i < 4; ++i) ok = ok && al16(in[i]);
     for (int i = 4; i < 7; ++i) ok = ok && al8(in[i]);
@@ -239,9 +229,10 @@ extern "C" int mi_patch_interface_nhatf(mi_patch_t p, double delta_n, const mi_p
     if (vec) for (int k = 0; k < 3; ++k) out[nOut++] = x->nhatfv_out_dev[k];
     if (x->gradient_out_dev) out[nOut++] = x->gradient_out_dev;
     if (x->b1_out_dev) { out[nOut++] = x->b1_out_dev; out[nOut++] = x->b2_out_dev; }
-    MICHK(if_outputs(who, in, nIn, out, nOut));
-    MICHK(rc_aligned(who, (const void* const*)in, nIn));
-    MICHK(rc_aligned(who, (const void* const*)out, nOut));
+    MICHK(arrays_present(who, in, nIn));
+    MICHK(outputs_distinct(who, in, nIn, out, nOut));
+    MICHK(arrays_aligned8(who, (const void* const*)in, nIn));
+    MICHK(arrays_aligned8(who, (const void* const*)out, nOut));
     HIPCHK(hipSetDevice(p->ctx->device));
     NhArgs q{};
     q.lo = p->faceCells.p; q.lambda = x->patch_weights_dev; q.magSf = x->patch_magsf_dev; q.theta = x->theta_deg_dev;
@@ -259,13 +250,11 @@ extern "C" int mi_patch_interface_nhatf(mi_patch_t p, double delta_n, const mi_p
 extern "C" int mi_interface_create(mi_addr_t a, mi_grad_boundary_t b, mi_interface_t* out)
 {
     const std::string who = "mi_interface_create";
-    if (!a || !out) return fail(MI_ERR_ARG, who + ": bad argument");
-    if (b && (b->addr != a || b->nCells != a->L.nCells)) return fail(MI_ERR_ARG, who + ": the boundary was built for another addressing");
+    std::unique_ptr<mi_interface_s> h(new mi_interface_s());
+    MICHK(row_handle_open(who, a, b, out, *h));
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    mi_interface_s* h = new mi_interface_s();
-    h->ctx = a->ctx; h->addr = a; h->boundary = b; h->nCells = a->L.nCells; h->nFaces = a->L.nFaces; h->nBFaces = b ? b->nFaces : 0;
-    *out = h;
+    *out = h.release();
     return MI_OK;
 }
 extern "C" int mi_interface_destroy(mi_interface_t h) { delete h; return MI_OK; }
@@ -273,10 +262,8 @@ extern "C" int mi_interface_destroy(mi_interface_t h) { delete h; return MI_OK; 
 extern "C" int mi_interface_curvature(mi_interface_t h, const double* nhatf_dev, const double* b_nhatf_dev, const double* vol_dev, double* k_out_dev)
 {
     const std::string who = "mi_interface_curvature";
-    if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
+    MICHK(row_handle_check(who, h));
     mi_addr_s* a = h->addr;
-    if (h->nCells != a->L.nCells || h->nFaces != a->L.nFaces || (h->boundary && h->boundary->addr != a))
-        return fail(MI_ERR_ARG, who + ": the handle was built for another addressing");
     if (h->nCells == 0) return MI_OK;
     if (!vol_dev) return fail(MI_ERR_ARG, who + ": a cell array is missing");
     if (h->nFaces > 0 && !nhatf_dev) return fail(MI_ERR_ARG, who + ": an input array is missing");
@@ -286,19 +273,16 @@ extern "C" int mi_interface_curvature(mi_interface_t h, const double* nhatf_dev,
     if (h->nFaces > 0) in[nIn++] = nhatf_dev;
     if (h->nBFaces > 0) in[nIn++] = b_nhatf_dev;
     double* out[1] = {k_out_dev};
-    MICHK(if_outputs(who, in, nIn, out, 1));
-    MICHK(rc_aligned(who, (const void* const*)in, nIn));
-    MICHK(rc_aligned(who, (const void* const*)out, 1));
+    MICHK(arrays_present(who, in, nIn));
+    MICHK(outputs_distinct(who, in, nIn, out, 1));
+    MICHK(arrays_aligned8(who, (const void* const*)in, nIn));
+    MICHK(arrays_aligned8(who, (const void* const*)out, 1));
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     MuArgs q{};
-    MuRow& r = q.r;
-    r.os = a->ownerStartC.p; r.ls = a->losortStartC.p; r.losort = a->losortC.p; r.lo = a->lowerAddr.p; r.up = a->upperAddr.p;
-    r.blockStart = a->rowPlan[1].tiles ? a->tileCellStart.p : nullptr;
-    if (h->nBFaces > 0) { r.bStart = h->boundary->allStart.p; r.bFace = h->boundary->all.p; }
-    r.n = a->L.nCells; r.xcd = a->ctx->xcdRows;
+    q.r = row_tables(a, h->boundary);
     q.q.vol = vol_dev; q.x.phiPsi = nhatf_dev; q.x.bphiPsi = b_nhatf_dev; q.x.out = k_out_dev;
-    return mu_row_launch(a, 1, k_interface_curvature<256>, k_interface_curvature<512>, k_interface_curvature<1024>, q);
+    return row_launch_bs(a, 1, ROW_BS(k_interface_curvature), q);
 }
 
 extern "C" int mi_surface_tension_force(mi_addr_t a, double sigma, const double* lambda_dev, const double* delta_coeffs_dev, const double* k_dev,
@@ -312,7 +296,8 @@ extern "C" int mi_surface_tension_force(mi_addr_t a, double sigma, const double*
     if (a->L.nFaces == 0) return MI_OK;
     const double* in[5] = {lambda_dev, delta_coeffs_dev, k_dev, alpha_dev, sngrad_corr_dev_or_null};
     double* out[1] = {out_dev};
-    MICHK(if_outputs(who, in, sngrad_corr_dev_or_null ? 5 : 4, out, 1));
+    MICHK(arrays_present(who, in, sngrad_corr_dev_or_null ? 5 : 4));
+    MICHK(outputs_distinct(who, in, sngrad_corr_dev_or_null ? 5 : 4, out, 1));
     if (!al16(lambda_dev) || !al16(delta_coeffs_dev) || !al16(sngrad_corr_dev_or_null) || !al16(out_dev) || !al8(k_dev) || !al8(alpha_dev))
         return fail(MI_ERR_ARG, who + ": face fields must be 16-byte aligned, the cell fields to 8 bytes");
     StArgs q{};
@@ -334,9 +319,10 @@ extern "C" int mi_patch_surface_tension_force(mi_patch_t p, double sigma, const 
     const double* in[7] = {patch_weights_dev, patch_delta_coeffs_dev, k_dev, nbr_k_dev, alpha_dev, nbr_alpha_dev, patch_sngrad_corr_dev_or_null};
     double* out[1] = {out_dev};
     const int nIn = patch_sngrad_corr_dev_or_null ? 7 : 6;
-    MICHK(if_outputs(who, in, nIn, out, 1));
-    MICHK(rc_aligned(who, (const void* const*)in, nIn));
-    MICHK(rc_aligned(who, (const void* const*)out, 1));
+    MICHK(arrays_present(who, in, nIn));
+    MICHK(outputs_distinct(who, in, nIn, out, 1));
+    MICHK(arrays_aligned8(who, (const void* const*)in, nIn));
+    MICHK(arrays_aligned8(who, (const void* const*)out, 1));
     HIPCHK(hipSetDevice(p->ctx->device));
     StArgs q{};
     q.lo = p->faceCells.p; q.lambda = patch_weights_dev; q.dc = patch_delta_coeffs_dev; q.K = k_dev; q.nbrK = nbr_k_dev; q.alpha = alpha_dev;

@@ -24,8 +24,7 @@ __device__ __forceinline__ void ls_wdd(double s, double dx, double dy, double dz
 __device__ __forceinline__ double ls_magsqr(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
 
 struct LsBuildArgs {
-    const int32_t *os, *ls, *losort, *lo, *up;
-    const int32_t *bStart, *bFace;                    // per-cell boundary faces (mi_grad_boundary_s::allStart / all)
+    RowTables r;
     const uint8_t* bCoupled;                          // per boundary face: 1 on a coupled patch
     const double *cc[3], *w, *magSf, *bw, *bMagSf, *bd[3];
     double* dd[6];                                    // xx xy xz yy yz zz; inverted in place by k_ls_invert
@@ -33,34 +32,34 @@ struct LsBuildArgs {
     double *p[3], *nv[3], *bp[3];
     double add[6];                                    // removeCmpts as the tensor added before and subtracted after the inversion
     int removes;
-    int n, nf;
+    int nf;
 };
 
 // dd per cell (leastSquaresVectors.C:123-170): a thread owns a cell and adds its faces' terms in the loops' order
 __global__ __launch_bounds__(256) void k_ls_dd(const LsBuildArgs a)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.n) return;
+    if (c >= a.r.n) return;
     const double cx = a.cc[0][c], cy = a.cc[1][c], cz = a.cc[2][c];
     double dd[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, t[6];
-    for (int j = a.ls[c]; j < a.ls[c + 1]; ++j) {              // c is the neighbour: d = C[c] - C[own], dd[nei] += w*wdd
-        const int f = a.losort[j], o = a.lo[f];
+    for (int j = a.r.ls[c]; j < a.r.ls[c + 1]; ++j) {              // c is the neighbour: d = C[c] - C[own], dd[nei] += w*wdd
+        const int f = a.r.losort[j], o = a.r.lo[f];
         const double dx = cx - a.cc[0][o], dy = cy - a.cc[1][o], dz = cz - a.cc[2][o];
         ls_wdd(a.magSf[f] / ls_magsqr(dx, dy, dz), dx, dy, dz, t);
         const double w = a.w[f];
 #pragma unroll
         for (int i = 0; i < 6; ++i) dd[i] = dd[i] + w * t[i];
     }
-    for (int f = a.os[c]; f < a.os[c + 1]; ++f) {              // c is the owner: d = C[nei] - C[c], dd[own] += (1 - w)*wdd
-        const int u = a.up[f];
+    for (int f = a.r.os[c]; f < a.r.os[c + 1]; ++f) {              // c is the owner: d = C[nei] - C[c], dd[own] += (1 - w)*wdd
+        const int u = a.r.up[f];
         const double dx = a.cc[0][u] - cx, dy = a.cc[1][u] - cy, dz = a.cc[2][u] - cz;
         ls_wdd(a.magSf[f] / ls_magsqr(dx, dy, dz), dx, dy, dz, t);
         const double w1 = 1.0 - a.w[f];
 #pragma unroll
         for (int i = 0; i < 6; ++i) dd[i] = dd[i] + w1 * t[i];
     }
-    if (a.bStart) for (int j = a.bStart[c]; j < a.bStart[c + 1]; ++j) {
-        const int bf = a.bFace[j];
+    if (a.r.bStart) for (int j = a.r.bStart[c]; j < a.r.bStart[c + 1]; ++j) {
+        const int bf = a.r.bFace[j];
         const double dx = a.bd[0][bf], dy = a.bd[1][bf], dz = a.bd[2][bf];
         const double m = ls_magsqr(dx, dy, dz);
         // coupled: ((1 - pw)*pMagSf/magSqr(d))*sqr(d) (:156-157); the others: (pMagSf/magSqr(d))*sqr(d) (:166-167)
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(256) void k_ls_dd(const LsBuildArgs a)
 __global__ __launch_bounds__(256) void k_ls_invert(const LsBuildArgs a)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.n) return;
+    if (c >= a.r.n) return;
     double xx = a.dd[0][c], xy = a.dd[1][c], xz = a.dd[2][c], yy = a.dd[3][c], yz = a.dd[4][c], zz = a.dd[5][c];
     if (a.removes) { xx = xx + a.add[0]; xy = xy + a.add[1]; xz = xz + a.add[2]; yy = yy + a.add[3]; yz = yz + a.add[4]; zz = zz + a.add[5]; }
     const double det = xx * yy * zz + xy * yz * xz + xz * xy * yz - xx * yz * yz - xy * xy * zz - xz * yy * xz;
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(256) void k_ls_face_vectors(const LsBuildArgs a)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= a.nf) return;
-    const int o = a.lo[f], u = a.up[f];
+    const int o = a.r.lo[f], u = a.r.up[f];
     const double dx = a.cc[0][u] - a.cc[0][o], dy = a.cc[1][u] - a.cc[1][o], dz = a.cc[2][u] - a.cc[2][o];
     const double m = a.magSf[f] / ls_magsqr(dx, dy, dz), w = a.w[f];
     const double sp = (1.0 - w) * m, sn = -w * m;
@@ -120,9 +119,9 @@ __global__ __launch_bounds__(256) void k_ls_face_vectors(const LsBuildArgs a)
 __global__ __launch_bounds__(256) void k_ls_boundary_vectors(const LsBuildArgs a)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.n) return;
-    for (int j = a.bStart[c]; j < a.bStart[c + 1]; ++j) {
-        const int bf = a.bFace[j];
+    if (c >= a.r.n) return;
+    for (int j = a.r.bStart[c]; j < a.r.bStart[c + 1]; ++j) {
+        const int bf = a.r.bFace[j];
         const double dx = a.bd[0][bf], dy = a.bd[1][bf], dz = a.bd[2][bf];
         const double m = ls_magsqr(dx, dy, dz);
         const double s = a.bCoupled[bf] ? (1.0 - a.bw[bf]) * a.bMagSf[bf] / m : a.bMagSf[bf] * (1.0 / m);
@@ -134,11 +133,9 @@ __global__ __launch_bounds__(256) void k_ls_boundary_vectors(const LsBuildArgs a
 }
 
 struct LsGradArgs {
-    const int32_t *os, *ls, *losort, *blockStart, *lo, *up;
-    const int32_t *bStart, *bFace;
+    RowTables r;
     const double *p[3], *nv[3], *bp[3], *vf[3], *bv[3];
     double* g[9];                                     // g[3*j + k] = d(vf_j)/dx_k
-    int n, cap, xcd;
 };
 // the gradient: k_gauss_grad's skeleton with the block's own-face pVectors staged, nVectors and the owner's vf gathered for the
 // neighbour-side faces (the first four before the barrier), the boundary faces through the per-cell lists
@@ -146,24 +143,24 @@ template <int NC, int BS>
 __global__ __launch_bounds__(BS) void k_ls_grad(const LsGradArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double rp_smem[];
-    double *sx = rp_smem, *sy = sx + a.cap, *sz = sy + a.cap;
-    const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
+    double *sx = rp_smem, *sy = sx + a.r.cap, *sz = sy + a.r.cap;
+    const int lb = a.r.xcd ? xcd_block() : (int)blockIdx.x;
     int c0, cEnd;
-    if (a.blockStart) { c0 = a.blockStart[lb]; cEnd = a.blockStart[lb + 1]; }
-    else { c0 = lb * BS; cEnd = min(c0 + BS, a.n); }
+    if (a.r.blockStart) { c0 = a.r.blockStart[lb]; cEnd = a.r.blockStart[lb + 1]; }
+    else { c0 = lb * BS; cEnd = min(c0 + BS, a.r.n); }
     const int tid = threadIdx.x, c = c0 + tid;
     const bool live = c < cEnd;
-    const int f0 = a.os[c0], nf = a.os[cEnd] - f0;
-    const bool staged = nf <= a.cap;
+    const int f0 = a.r.os[c0], nf = a.r.os[cEnd] - f0;
+    const bool staged = nf <= a.r.cap;
     if (staged) { stage_dma8<BS>(a.p[0] + f0, sx, nf, tid); stage_dma8<BS>(a.p[1] + f0, sy, nf, tid); stage_dma8<BS>(a.p[2] + f0, sz, nf, tid); }
     int nb = 0, ne = 0;
-    if (live) { nb = a.ls[c]; ne = a.ls[c + 1]; }
+    if (live) { nb = a.r.ls[c]; ne = a.r.ls[c + 1]; }
     const int cnt = ne - nb;
     double nx[4], ny[4], nz[4], no[4][NC];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (k < cnt) {
-            const int f = a.losort[nb + k], o = a.lo[f];
+            const int f = a.r.losort[nb + k], o = a.r.lo[f];
             nx[k] = a.nv[0][f]; ny[k] = a.nv[1][f]; nz[k] = a.nv[2][f];
 #pragma unroll
             for (int j = 0; j < NC; ++j) no[k][j] = a.vf[j][o];
@@ -190,7 +187,7 @@ __global__ __launch_bounds__(BS) void k_ls_grad(const LsGradArgs a)
         }
     }
     for (int i = nb + 4; i < ne; ++i) {
-        const int f = a.losort[i], o = a.lo[f];
+        const int f = a.r.losort[i], o = a.r.lo[f];
         const double lx = a.nv[0][f], ly = a.nv[1][f], lz = a.nv[2][f];
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
@@ -199,12 +196,12 @@ __global__ __launch_bounds__(BS) void k_ls_grad(const LsGradArgs a)
         }
     }
     // lsGrad[own] += ownLs*(vsf[nei] - vsf[own])
-    const int ob = a.os[c], oe = a.os[c + 1];
+    const int ob = a.r.os[c], oe = a.r.os[c + 1];
     for (int f = ob; f < oe; ++f) {
         double lx, ly, lz;
         if (staged) { lx = sx[f - f0]; ly = sy[f - f0]; lz = sz[f - f0]; }
         else { lx = a.p[0][f]; ly = a.p[1][f]; lz = a.p[2][f]; }
-        const int u = a.up[f];
+        const int u = a.r.up[f];
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
             const double d = a.vf[j][u] - v[j];
@@ -212,8 +209,8 @@ __global__ __launch_bounds__(BS) void k_ls_grad(const LsGradArgs a)
         }
     }
     // the patches: lsGrad[faceCells] += patchOwnLs*(neiVsf | patchVsf - vsf[faceCells])
-    if (a.bStart) for (int i = a.bStart[c]; i < a.bStart[c + 1]; ++i) {
-        const int bf = a.bFace[i];
+    if (a.r.bStart) for (int i = a.r.bStart[c]; i < a.r.bStart[c + 1]; ++i) {
+        const int bf = a.r.bFace[i];
         const double lx = a.bp[0][bf], ly = a.bp[1][bf], lz = a.bp[2][bf];
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
@@ -228,11 +225,7 @@ __global__ __launch_bounds__(BS) void k_ls_grad(const LsGradArgs a)
 } // namespace mi
 
 // the least-squares vectors of one mesh: pVectors / nVectors on the internal faces, pVectors on the boundary faces, caller's face order
-struct mi_ls_vectors_s {
-    mi_ctx_s* ctx = nullptr;
-    mi_addr_s* addr = nullptr;
-    mi_grad_boundary_s* boundary = nullptr;
-    int32_t nCells = 0, nFaces = 0, nBFaces = 0;
+struct mi_ls_vectors_s : RowHandle {
     DevBuf<double> p[3], nv[3], bp[3];
 };
 
@@ -273,32 +266,17 @@ extern "C" int mi_grad_scheme_parse(const char* scheme, mi_grad_scheme* out)
 }
 
 namespace {
-// no output among the inputs or twice
-int ls_outputs(const std::string& who, const double* const* in, int nIn, double* const* out, int nOut)
-{
-    for (int o = 0; o < nOut; ++o) {
-        if (!out[o]) return fail(MI_ERR_ARG, who + ": output arrays missing");
-        for (int i = 0; i < nIn; ++i) if (out[o] == in[i]) return fail(MI_ERR_ARG, who + ": an output must not alias an input");
-        for (int q = 0; q < o; ++q) if (out[o] == out[q]) return fail(MI_ERR_ARG, who + ": the outputs must differ");
-    }
-    return MI_OK;
-}
 template <int NC>
-int ls_grad_launch(mi_addr_s* a, const mi_addr_s::RowPlan& rp, const LsGradArgs& q, size_t lds)
-{
-    if (rp.bs == 256) return row_launch(a, rp, k_ls_grad<NC, 256>, q, lds);
-    if (rp.bs == 512) return row_launch(a, rp, k_ls_grad<NC, 512>, q, lds);
-    return row_launch(a, rp, k_ls_grad<NC, 1024>, q, lds);
-}
+int ls_grad_launch(mi_addr_s* a, LsGradArgs& q) { return row_launch_bs(a, 3, k_ls_grad<NC, 256>, k_ls_grad<NC, 512>, k_ls_grad<NC, 1024>, q); }
 } // namespace
 
 extern "C" int mi_ls_vectors_create(mi_addr_t a, mi_grad_boundary_t b, const double* const* c_dev, const double* weights_dev, const double* mag_sf_dev,
                                     const double* b_weights_dev, const double* b_mag_sf_dev, const double* const* b_delta_dev, mi_ls_vectors_t* out)
 {
     const std::string who = "mi_ls_vectors_create";
-    if (!a || !out) return fail(MI_ERR_ARG, who + ": bad argument");
-    if (b && (b->addr != a || b->nCells != a->L.nCells)) return fail(MI_ERR_ARG, who + ": the boundary was built for another addressing");
-    const int32_t n = a->L.nCells, nf = a->L.nFaces, nb = b ? b->nFaces : 0;
+    std::unique_ptr<mi_ls_vectors_s> v(new mi_ls_vectors_s());
+    MICHK(row_handle_open(who, a, b, out, *v));
+    const int32_t n = v->nCells, nf = v->nFaces, nb = v->nBFaces;
     if (n > 0 && (!c_dev || !c_dev[0] || !c_dev[1] || !c_dev[2])) return fail(MI_ERR_ARG, who + ": the cell centres are missing");
     if (nf > 0 && (!weights_dev || !mag_sf_dev)) return fail(MI_ERR_ARG, who + ": the face weights and magSf are missing");
     int64_t nCoupled = 0;
@@ -308,8 +286,6 @@ extern "C" int mi_ls_vectors_create(mi_addr_t a, mi_grad_boundary_t b, const dou
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     hipStream_t s = a->ctx->stream;
-    std::unique_ptr<mi_ls_vectors_s> v(new mi_ls_vectors_s());
-    v->ctx = a->ctx; v->addr = a; v->boundary = b; v->nCells = n; v->nFaces = nf; v->nBFaces = nb;
     for (int k = 0; k < 3; ++k) {
         if (nf > 0) { MICHK(v->p[k].alloc((size_t)nf)); MICHK(v->nv[k].alloc((size_t)nf)); }
         if (nb > 0) MICHK(v->bp[k].alloc((size_t)nb));
@@ -319,7 +295,7 @@ extern "C" int mi_ls_vectors_create(mi_addr_t a, mi_grad_boundary_t b, const dou
     DevBuf<uint8_t> coupled;
     MICHK(dd.alloc((size_t)6 * n + 6));
     LsBuildArgs q{};
-    q.os = a->ownerStartC.p; q.ls = a->losortStartC.p; q.losort = a->losortC.p; q.lo = a->lowerAddr.p; q.up = a->upperAddr.p;
+    q.r = row_tables(a, b);
     if (nb > 0) {
         MICHK(coupled.alloc((size_t)nb));
         HIPCHK(hipMemsetAsync(coupled.p, 0, (size_t)nb, s));
@@ -328,7 +304,7 @@ extern "C" int mi_ls_vectors_create(mi_addr_t a, mi_grad_boundary_t b, const dou
             if (b->patchKinds[p] == MI_GRAD_PATCH_COUPLED && b->patchSizes[p] > 0) HIPCHK(hipMemsetAsync(coupled.p + off, 1, (size_t)b->patchSizes[p], s));
             off += (size_t)b->patchSizes[p];
         }
-        q.bStart = b->allStart.p; q.bFace = b->all.p; q.bCoupled = coupled.p;
+        q.bCoupled = coupled.p;
         q.bw = b_weights_dev; q.bMagSf = b_mag_sf_dev;
         for (int k = 0; k < 3; ++k) { q.bd[k] = b_delta_dev[k]; q.bp[k] = v->bp[k].p; }
     }
@@ -336,7 +312,7 @@ extern "C" int mi_ls_vectors_create(mi_addr_t a, mi_grad_boundary_t b, const dou
     for (int k = 0; k < 3; ++k) { q.cc[k] = c_dev[k]; q.p[k] = v->p[k].p; q.nv[k] = v->nv[k].p; }
     for (int i = 0; i < 6; ++i) q.dd[i] = dd.p + (size_t)i * n;
     q.dd0 = dd.p + (size_t)6 * n;
-    q.n = n; q.nf = nf;
+    q.nf = nf;
     const int cellBlocks = (n + 255) / 256;
     k_ls_dd<<<cellBlocks, 256, 0, s>>>(q);
     HIPCHK(hipGetLastError());
@@ -373,7 +349,7 @@ extern "C" int mi_ls_vectors_fields(mi_ls_vectors_t v, double* const* p_out_dev,
     }
     if (v->nFaces > 0) for (int k = 0; k < 3; ++k) { outs[nOut++] = p_out_dev[k]; outs[nOut++] = n_out_dev[k]; }
     if (v->nBFaces > 0) for (int k = 0; k < 3; ++k) outs[nOut++] = bp_out_dev_or_null[k];
-    MICHK(ls_outputs(who, in, nIn, outs, nOut));
+    MICHK(outputs_distinct(who, in, nIn, outs, nOut));
     HIPCHK(hipSetDevice(v->ctx->device));
     hipStream_t s = v->ctx->stream;
     for (int k = 0; k < 3; ++k) {
@@ -392,32 +368,26 @@ extern "C" int mi_ls_grad(mi_ls_vectors_t v, int32_t n_comp, const double* const
     if (!v) return fail(MI_ERR_ARG, who + ": bad argument");
     if (n_comp != 1 && n_comp != 3) return fail(MI_ERR_ARG, who + ": n_comp must be 1 or 3");
     mi_addr_s* a = v->addr;
-    if (v->nCells != a->L.nCells || v->nFaces != a->L.nFaces || (v->boundary && v->boundary->addr != a))
-        return fail(MI_ERR_ARG, who + ": the vectors were built for another addressing");
+    MICHK(row_handle_check(who, v, "the vectors were"));
     if (!vf_dev || !grad_out_dev) return fail(MI_ERR_ARG, who + ": input arrays missing");
     const bool hasB = v->nBFaces > 0;
     if (hasB && !bvalue_dev_or_null) return fail(MI_ERR_ARG, who + ": the boundary has faces: boundary values needed");
     const double* in[15];
     int nIn = 0;
     for (int j = 0; j < n_comp; ++j) { in[nIn++] = vf_dev[j]; if (hasB) in[nIn++] = bvalue_dev_or_null[j]; }
-    for (int i = 0; i < nIn; ++i) if (!in[i]) return fail(MI_ERR_ARG, who + ": input arrays missing");
+    MICHK(arrays_present(who, in, nIn));
     for (int k = 0; k < 3; ++k) {
         if (v->nFaces > 0) { in[nIn++] = v->p[k].p; in[nIn++] = v->nv[k].p; }
         if (hasB) in[nIn++] = v->bp[k].p;
     }
-    MICHK(ls_outputs(who, in, nIn, grad_out_dev, 3 * n_comp));
+    MICHK(outputs_distinct(who, in, nIn, grad_out_dev, 3 * n_comp));
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nCells == 0) return MI_OK;
     LsGradArgs q{};
-    const mi_addr_s::RowPlan& rp = a->rowPlan[1];
-    q.os = a->ownerStartC.p; q.ls = a->losortStartC.p; q.losort = a->losortC.p; q.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
-    q.lo = a->lowerAddr.p; q.up = a->upperAddr.p;
-    if (hasB) { q.bStart = v->boundary->allStart.p; q.bFace = v->boundary->all.p; }
+    q.r = row_tables(a, v->boundary);
     for (int k = 0; k < 3; ++k) { q.p[k] = v->p[k].p; q.nv[k] = v->nv[k].p; q.bp[k] = v->bp[k].p; }
     for (int j = 0; j < n_comp; ++j) { q.vf[j] = vf_dev[j]; if (hasB) q.bv[j] = bvalue_dev_or_null[j]; }
     for (int i = 0; i < 3 * n_comp; ++i) q.g[i] = grad_out_dev[i];
-    q.n = a->L.nCells; q.cap = row_cap(rp, 3); q.xcd = a->ctx->xcdRows;
-    const size_t lds = (size_t)3 * q.cap * sizeof(double);
-    return n_comp == 1 ? ls_grad_launch<1>(a, rp, q, lds) : ls_grad_launch<3>(a, rp, q, lds);
+    return n_comp == 1 ? ls_grad_launch<1>(a, q) : ls_grad_launch<3>(a, q);
 }

@@ -1,5 +1,5 @@
 // limited_grad.inc -- the limited gradient schemes cellLimited / cellMDLimited / faceLimited / faceMDLimited (included by engine.hip after
-// assembly.inc).
+// row_entry.inc).
 //
 // The reference limits `Gauss linear` gradients with host loops over owner / neighbour that scatter to both cells of every face
 // (finiteVolume/gradSchemes/limitedGradSchemes/*/*Grads.C).  Here it is ONE row pass on the skeleton of k_gauss_grad: a thread owns a
@@ -11,13 +11,11 @@ namespace mi {
 
 enum { LG_CELL = 0, LG_CELL_MD = 1, LG_FACE = 2, LG_FACE_MD = 3 };   // MI_GRAD_CELL_LIMITED ... MI_GRAD_FACE_MD_LIMITED
 struct LGradArgs {
-    const int32_t *os, *ls, *losort, *blockStart, *lo, *up;
-    const int32_t *bStart, *bFace;                    // per-cell boundary faces (mi_grad_boundary_s), indices into the patch-ordered faces
+    RowTables r;                                      // the boundary lists: all faces for the cell kinds, the limited ones for the face kinds
     const double *cf[3], *cc[3], *bcf[3], *vf[3], *bv[3];
     double *g[9], *limOut[3];                         // g[3*j + k] = d(vf_j)/dx_k, in place
     double rk;                                        // 1.0/k - 1.0
     int expand;                                       // k < 1: the cell kinds' and faceMDLimited's expansion of the bounds
-    int n, cap, xcd;
 };
 // Foam::max / Foam::min (the first argument wins a tie: signed zeros keep the reference's order)
 __device__ __forceinline__ double lg_max(double a, double b) { return a > b ? a : b; }
@@ -46,25 +44,25 @@ template <int KIND, int NC, int BS>
 __global__ __launch_bounds__(BS) void k_limited_grad(const LGradArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double rp_smem[];
-    double *sx = rp_smem, *sy = sx + a.cap, *sz = sy + a.cap;
-    const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
+    double *sx = rp_smem, *sy = sx + a.r.cap, *sz = sy + a.r.cap;
+    const int lb = a.r.xcd ? xcd_block() : (int)blockIdx.x;
     int c0, cEnd;
-    if (a.blockStart) { c0 = a.blockStart[lb]; cEnd = a.blockStart[lb + 1]; }
-    else { c0 = lb * BS; cEnd = min(c0 + BS, a.n); }
+    if (a.r.blockStart) { c0 = a.r.blockStart[lb]; cEnd = a.r.blockStart[lb + 1]; }
+    else { c0 = lb * BS; cEnd = min(c0 + BS, a.r.n); }
     const int tid = threadIdx.x, c = c0 + tid;
     const bool live = c < cEnd;
-    const int f0 = a.os[c0], nf = a.os[cEnd] - f0;
-    const bool staged = nf <= a.cap;
+    const int f0 = a.r.os[c0], nf = a.r.os[cEnd] - f0;
+    const bool staged = nf <= a.r.cap;
     if (staged) { stage_dma8<BS>(a.cf[0] + f0, sx, nf, tid); stage_dma8<BS>(a.cf[1] + f0, sy, nf, tid); stage_dma8<BS>(a.cf[2] + f0, sz, nf, tid); }
     int nb = 0, ne = 0;
-    if (live) { nb = a.ls[c]; ne = a.ls[c + 1]; }
+    if (live) { nb = a.r.ls[c]; ne = a.r.ls[c + 1]; }
     const int cnt = ne - nb;
     // the first four neighbour-side faces, their owners and -- when they are not in the block's staged range -- their centres
     int nfk[4], nok[4]; double nx[4], ny[4], nz[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        nfk[k] = (k < cnt) ? a.losort[nb + k] : 0;
-        nok[k] = (k < cnt) ? a.lo[nfk[k]] : 0;
+        nfk[k] = (k < cnt) ? a.r.losort[nb + k] : 0;
+        nok[k] = (k < cnt) ? a.r.lo[nfk[k]] : 0;
         if (k < cnt && (!staged || nfk[k] < f0)) { const int f = nfk[k]; nx[k] = a.cf[0][f]; ny[k] = a.cf[1][f]; nz[k] = a.cf[2][f]; }
         else { nx[k] = ny[k] = nz[k] = 0.0; }
     }
@@ -76,8 +74,8 @@ __global__ __launch_bounds__(BS) void k_limited_grad(const LGradArgs a)
     for (int j = 0; j < NC; ++j) v[j] = a.vf[j][c];
 #pragma unroll
     for (int i = 0; i < 3 * NC; ++i) g[i] = a.g[i][c];
-    const int ob = a.os[c], oe = a.os[c + 1];
-    const int bb = a.bStart ? a.bStart[c] : 0, be = a.bStart ? a.bStart[c + 1] : 0;
+    const int ob = a.r.os[c], oe = a.r.os[c + 1];
+    const int bb = a.r.bStart ? a.r.bStart[c] : 0, be = a.r.bStart ? a.r.bStart[c + 1] : 0;
     // every face of the cell in the reference's order: fn(dcf = Cf - C[c] per component, the value across the face is o[j][i], c owns the face)
     auto walk = [&](auto&& fn) {
 #pragma unroll
@@ -87,20 +85,20 @@ __global__ __launch_bounds__(BS) void k_limited_grad(const LGradArgs a)
             fn(fx - cx, fy - cy, fz - cz, a.vf, nok[k], false);
         }
         for (int j = nb + 4; j < ne; ++j) {
-            const int f = a.losort[j];
+            const int f = a.r.losort[j];
             double fx, fy, fz;
             if (staged && f >= f0) { fx = sx[f - f0]; fy = sy[f - f0]; fz = sz[f - f0]; }
             else { fx = a.cf[0][f]; fy = a.cf[1][f]; fz = a.cf[2][f]; }
-            fn(fx - cx, fy - cy, fz - cz, a.vf, a.lo[f], false);
+            fn(fx - cx, fy - cy, fz - cz, a.vf, a.r.lo[f], false);
         }
         for (int f = ob; f < oe; ++f) {
             double fx, fy, fz;
             if (staged) { fx = sx[f - f0]; fy = sy[f - f0]; fz = sz[f - f0]; }
             else { fx = a.cf[0][f]; fy = a.cf[1][f]; fz = a.cf[2][f]; }
-            fn(fx - cx, fy - cy, fz - cz, a.vf, a.up[f], true);
+            fn(fx - cx, fy - cy, fz - cz, a.vf, a.r.up[f], true);
         }
         for (int j = bb; j < be; ++j) {
-            const int bf = a.bFace[j];
+            const int bf = a.r.bFace[j];
             fn(a.bcf[0][bf] - cx, a.bcf[1][bf] - cy, a.bcf[2][bf] - cz, a.bv, bf, true);
         }
     };
@@ -176,29 +174,14 @@ __global__ __launch_bounds__(BS) void k_limited_grad(const LGradArgs a)
 
 } // namespace mi
 
-// the boundary of a limited gradient: every boundary face's cell, in patch order, as a per-cell list; the face kinds read only the coupled
-// and fixesValue patches (faceLimitedGrads.C:119-163), so they get a list of their own
-struct mi_grad_boundary_s {
-    mi_ctx_s* ctx = nullptr;
-    mi_addr_s* addr = nullptr;
-    int32_t nCells = 0, nFaces = 0, nLimited = 0;
-    DevBuf<int32_t> allStart, all, limStart, lim;
-    std::vector<int32_t> patchSizes, patchKinds;      // the patches as given (least_squares.inc marks the coupled faces from them)
-};
-
 namespace {
 template <int KIND, int NC>
-int lg_launch(mi_addr_s* a, const mi_addr_s::RowPlan& rp, const LGradArgs& q, size_t lds)
+int lg_launch(mi_addr_s* a, LGradArgs& q)
 {
-    if (rp.bs == 256) return row_launch(a, rp, k_limited_grad<KIND, NC, 256>, q, lds);
-    if (rp.bs == 512) return row_launch(a, rp, k_limited_grad<KIND, NC, 512>, q, lds);
-    return row_launch(a, rp, k_limited_grad<KIND, NC, 1024>, q, lds);
+    return row_launch_bs(a, 3, k_limited_grad<KIND, NC, 256>, k_limited_grad<KIND, NC, 512>, k_limited_grad<KIND, NC, 1024>, q);
 }
 template <int KIND>
-int lg_launch_kind(mi_addr_s* a, const mi_addr_s::RowPlan& rp, const LGradArgs& q, size_t lds, int nc)
-{
-    return nc == 1 ? lg_launch<KIND, 1>(a, rp, q, lds) : lg_launch<KIND, 3>(a, rp, q, lds);
-}
+int lg_launch_kind(mi_addr_s* a, LGradArgs& q, int nc) { return nc == 1 ? lg_launch<KIND, 1>(a, q) : lg_launch<KIND, 3>(a, q); }
 const char* const kGradLimNames[] = {"cellLimited", "cellMDLimited", "faceLimited", "faceMDLimited"};
 // the constructors' check (cellLimitedGrad.H:94-107 and its siblings) on a caller-filled mi_grad_limiter
 int grad_lim_check(const char* who, const mi_grad_limiter* l)
@@ -302,7 +285,7 @@ extern "C" int mi_limited_grad(mi_addr_t a, const mi_grad_limiter* lim, mi_grad_
     if (n_comp != 1 && n_comp != 3) return fail(MI_ERR_ARG, std::string(who) + ": n_comp must be 1 or 3");
     const bool md = lim->kind == MI_GRAD_CELL_MD_LIMITED || lim->kind == MI_GRAD_FACE_MD_LIMITED;
     if (md && limiter_out_dev_or_null) return fail(MI_ERR_ARG, std::string(who) + ": the MD kinds have no limiter field: limiter_out must be NULL");
-    if (b && (b->addr != a || b->nCells != a->L.nCells)) return fail(MI_ERR_ARG, std::string(who) + ": the boundary was built for another addressing");
+    MICHK(boundary_matches(who, a, b));
     if (!vf_dev || !c_dev || !cf_dev || !grad_inout_dev) return fail(MI_ERR_ARG, std::string(who) + ": input arrays missing");
     const bool hasB = b && b->nFaces > 0;
     if (hasB && (!bvalue_dev || !bcf_dev)) return fail(MI_ERR_ARG, std::string(who) + ": the boundary has faces: boundary values and face centres needed");
@@ -316,36 +299,25 @@ extern "C" int mi_limited_grad(mi_addr_t a, const mi_grad_limiter* lim, mi_grad_
     int no = 0;
     for (int i = 0; i < 3 * n_comp; ++i) outs[no++] = grad_inout_dev[i];
     for (int j = 0; j < nLim && limiter_out_dev_or_null; ++j) outs[no++] = limiter_out_dev_or_null[j];
-    for (int i = 0; i < m; ++i) if (!in[i]) return fail(MI_ERR_ARG, std::string(who) + ": input arrays missing");
-    for (int i = 0; i < no; ++i) {
-        if (!outs[i]) return fail(MI_ERR_ARG, std::string(who) + ": output arrays missing");
-        for (int k = 0; k < m; ++k) if (outs[i] == in[k]) return fail(MI_ERR_ARG, std::string(who) + ": an output must not alias an input");
-        for (int k = 0; k < i; ++k) if (outs[i] == outs[k]) return fail(MI_ERR_ARG, std::string(who) + ": the outputs must differ");
-    }
+    MICHK(arrays_present(who, in, m));
+    MICHK(outputs_distinct(who, in, m, outs, no));
     if (lim->identity) return MI_OK;                      // k < SMALL: the basic scheme's gradient unchanged (cellLimitedGrads.C:59-62)
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     if (a->L.nCells == 0) return MI_OK;
     LGradArgs q{};
-    const mi_addr_s::RowPlan& rp = a->rowPlan[1];
-    q.os = a->ownerStartC.p; q.ls = a->losortStartC.p; q.losort = a->losortC.p; q.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
-    q.lo = a->lowerAddr.p; q.up = a->upperAddr.p;
     const bool faceKind = lim->kind == MI_GRAD_FACE_LIMITED || lim->kind == MI_GRAD_FACE_MD_LIMITED;
-    if (hasB && (faceKind ? b->nLimited : b->nFaces) > 0) {
-        q.bStart = faceKind ? b->limStart.p : b->allStart.p; q.bFace = faceKind ? b->lim.p : b->all.p;
-    }
+    q.r = faceKind ? row_tables(a, b ? b->limStart.p : nullptr, b ? b->lim.p : nullptr) : row_tables(a, b);   // no limited face: no list
     for (int d = 0; d < 3; ++d) { q.cc[d] = c_dev[d]; q.cf[d] = cf_dev[d]; if (hasB) q.bcf[d] = bcf_dev[d]; }
     for (int j = 0; j < n_comp; ++j) { q.vf[j] = vf_dev[j]; if (hasB) q.bv[j] = bvalue_dev[j]; }
     for (int i = 0; i < 3 * n_comp; ++i) q.g[i] = grad_inout_dev[i];
     for (int j = 0; j < nLim && limiter_out_dev_or_null; ++j) q.limOut[j] = limiter_out_dev_or_null[j];
     q.rk = 1.0 / lim->k - 1.0;
     q.expand = lim->k < 1.0 ? 1 : 0;
-    q.n = a->L.nCells; q.cap = row_cap(rp, 3); q.xcd = a->ctx->xcdRows;
-    const size_t lds = (size_t)3 * q.cap * sizeof(double);
     switch (lim->kind) {
-    case MI_GRAD_CELL_LIMITED: return lg_launch_kind<LG_CELL>(a, rp, q, lds, n_comp);
-    case MI_GRAD_CELL_MD_LIMITED: return lg_launch_kind<LG_CELL_MD>(a, rp, q, lds, n_comp);
-    case MI_GRAD_FACE_LIMITED: return lg_launch_kind<LG_FACE>(a, rp, q, lds, n_comp);
-    default: return lg_launch_kind<LG_FACE_MD>(a, rp, q, lds, n_comp);
+    case MI_GRAD_CELL_LIMITED: return lg_launch_kind<LG_CELL>(a, q, n_comp);
+    case MI_GRAD_CELL_MD_LIMITED: return lg_launch_kind<LG_CELL_MD>(a, q, n_comp);
+    case MI_GRAD_FACE_LIMITED: return lg_launch_kind<LG_FACE>(a, q, n_comp);
+    default: return lg_launch_kind<LG_FACE_MD>(a, q, n_comp);
     }
 }

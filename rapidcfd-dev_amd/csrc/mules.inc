@@ -21,12 +21,6 @@ enum { MU_OTHER = 0, MU_COUPLED = 1, MU_WEDGE = 2 };            // the kind of a
 __device__ __forceinline__ double mu_max(double a, double b) { return (a > b) ? a : b; }
 __device__ __forceinline__ double mu_min(double a, double b) { return (a < b) ? a : b; }
 
-// what every row pass of this file walks: the caller-order row tables, the block mapping and the per-cell boundary lists
-struct MuRow {
-    const int32_t *os, *ls, *losort, *blockStart, *lo, *up;
-    const int32_t *bStart, *bFace;
-    int n, cap, xcd;
-};
 // the cell fields of mi_mules_fields and the handle's work arrays
 struct MuCells {
     const double *rdtField, *rho, *rhoOld, *sp, *su, *vol, *psi, *psiOld, *bpsi;
@@ -42,13 +36,13 @@ struct MuFlux {
     double *out, *bout;
     int nf, nb, xcd, returnCorr;
 };
-struct MuArgs { MuRow r; MuCells q; MuFlux x; };      // one kernel argument, as row_launch passes it
+struct MuArgs { RowTables r; MuCells q; MuFlux x; };  // one kernel argument, as row_launch passes it
 
 // k_gauss_grad's / k_reconstruct's skeleton for NA staged face arrays: the block's own faces of src[0..NA) through LDS, the first four
 // neighbour-side faces in registers before the one barrier, then per live cell own(f, v) for its own faces ascending, nei(f, v) for its
 // neighbour-side faces in losort order, bnd(bf) for its boundary faces, done(); init(c) comes first
 template <int BS, int NA, class Init, class Own, class Nei, class Bnd, class Done>
-__device__ __forceinline__ void mu_rows(const MuRow& r, const double* const (&src)[NA], Init init, Own own, Nei nei, Bnd bnd, Done done)
+__device__ __forceinline__ void mu_rows(const RowTables& r, const double* const (&src)[NA], Init init, Own own, Nei nei, Bnd bnd, Done done)
 {
     extern __shared__ __attribute__((aligned(16))) double mu_smem[];
     const int lb = r.xcd ? xcd_block() : (int)blockIdx.x;
@@ -102,7 +96,7 @@ __device__ __forceinline__ void mu_rows(const MuRow& r, const double* const (&sr
 template <int BS, bool FORM_BD, bool LTS>
 __global__ __launch_bounds__(BS) void k_mules_bounds(const MuArgs a)
 {
-    const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
+    const RowTables& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
     const double* const src[2] = {FORM_BD ? x.phi : x.phiBD, FORM_BD ? x.phiPsi : x.phiCorr};
     double psiC = 0.0, hi = q.psiMin, lo = q.psiMax, sumBD = 0.0, sp = MU_VSMALL, sm = MU_VSMALL;
     // phiBD and phiCorr of a face between P (owner) and N from phi and phiPsi: upwind weights 0 or 1, so a contracted w*(P - N) + N
@@ -167,7 +161,7 @@ __global__ __launch_bounds__(BS) void k_mules_bounds(const MuArgs a)
 template <int BS>
 __global__ __launch_bounds__(BS) void k_mules_sums(const MuArgs a)
 {
-    const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
+    const RowTables& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
     const double* const src[2] = {x.lambda, x.phiCorr};
     double slp = 0.0, mslm = 0.0;
     mu_rows<BS, 2>(r, src, [](int) {},
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(BS) void k_mules_sums(const MuArgs a)
 template <bool CORR>
 __global__ __launch_bounds__(256) void k_mules_lambda(const MuArgs a)
 {
-    const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
+    const RowTables& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
     int f0, f1; block_chunk(x.nf, x.xcd, f0, f1);
     for (int f = f0 + threadIdx.x; f < f1; f += blockDim.x) {
         const int P = r.lo[f], N = r.up[f];
@@ -212,7 +206,7 @@ __global__ __launch_bounds__(256) void k_mules_lambda(const MuArgs a)
 template <int BS, bool ONES, bool LTS>
 __global__ __launch_bounds__(BS) void k_mules_corr_bounds(const MuArgs a)
 {
-    const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
+    const RowTables& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
     const double* const src[1] = {x.phiCorr};
     double hi = q.psiMin, lo = q.psiMax, sp = MU_VSMALL, sm = MU_VSMALL;
     mu_rows<BS, 1>(r, src, [](int) {},
@@ -266,7 +260,7 @@ __global__ __launch_bounds__(256) void k_mules_apply(const MuFlux x)
 template <int BS, bool LTS>
 __global__ __launch_bounds__(BS) void k_mules_solve(const MuArgs a)
 {
-    const MuRow& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
+    const RowTables& r = a.r; const MuCells& q = a.q; const MuFlux& x = a.x;
     const double* const src[1] = {x.phiPsi};
     double s = 0.0;
     mu_rows<BS, 1>(r, src, [](int) {},
@@ -301,11 +295,7 @@ __global__ __launch_bounds__(RB) void k_vmin(const double* x, const double* y, d
 } // namespace mi
 
 // explicit MULES on one mesh: the six cell work arrays and the boundary faces' kinds and cells
-struct mi_mules_s {
-    mi_ctx_s* ctx = nullptr;
-    mi_addr_s* addr = nullptr;
-    mi_grad_boundary_s* boundary = nullptr;
-    int32_t nCells = 0, nFaces = 0, nBFaces = 0;
+struct mi_mules_s : RowHandle {
     bool coupled = false, begun = false;
     bool corr = false;                                // the last begin was mi_mules_begin_corr: the iteration takes the CMULES patch rule
     bool hasOther = false;                            // a face on a patch that is neither coupled nor wedge: the CMULES rule reads b_phi there
@@ -328,8 +318,7 @@ int mu_check(const std::string& who, mi_mules_s* h, const mi_mules_fields* fl, c
              double* const* out, const int* outKind, int nOut, MuCall& c, int mode = MU_EXPLICIT)
 {
     mi_addr_s* a = h->addr;
-    if (h->nCells != a->L.nCells || h->nFaces != a->L.nFaces || (h->boundary && h->boundary->addr != a))
-        return fail(MI_ERR_ARG, who + ": the handle was built for another addressing");
+    MICHK(row_handle_check(who, h));
     if (!fl) return fail(MI_ERR_ARG, who + ": the fields are missing");
     const bool old = mode == MU_EXPLICIT;
     const double* psi = mode == MU_CORRECT ? nullptr : fl->psi_dev;
@@ -357,16 +346,12 @@ int mu_check(const std::string& who, mi_mules_s* h, const mi_mules_fields* fl, c
         if (!out[i]) return fail(MI_ERR_ARG, who + (outKind[i] != MU_BFACE ? ": an output array is missing" : ": the boundary has faces: boundary flux arrays needed"));
         outs[mo++] = out[i];
     }
-    MICHK(rc_aligned(who, (const void* const*)all, m));
-    MICHK(rc_aligned(who, (const void* const*)outs, mo));
-    MICHK(ls_outputs(who, all, m, outs, mo));
+    MICHK(arrays_aligned8(who, (const void* const*)all, m));
+    MICHK(arrays_aligned8(who, (const void* const*)outs, mo));
+    MICHK(outputs_distinct(who, all, m, outs, mo));
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    MuRow& r = c.a.r;
-    r.os = a->ownerStartC.p; r.ls = a->losortStartC.p; r.losort = a->losortC.p; r.lo = a->lowerAddr.p; r.up = a->upperAddr.p;
-    r.blockStart = a->rowPlan[1].tiles ? a->tileCellStart.p : nullptr;
-    if (hasB) { r.bStart = h->boundary->allStart.p; r.bFace = h->boundary->all.p; }
-    r.n = a->L.nCells; r.xcd = a->ctx->xcdRows;
+    c.a.r = row_tables(a, h->boundary);
     MuCells& q = c.a.q;
     q.rdtField = fl->r_delta_t_dev; q.rdt = fl->r_delta_t; q.rho = fl->rho_dev; q.rhoOld = old ? fl->rho_old_dev : fl->rho_dev; q.sp = fl->sp_dev; q.su = fl->su_dev;
     q.vol = fl->vol_dev; q.psi = psi; q.psiOld = old ? fl->psi_old_dev : psi; q.bpsi = bpsi; q.psiMax = fl->psi_max; q.psiMin = fl->psi_min;
@@ -377,16 +362,6 @@ int mu_check(const std::string& who, mi_mules_s* h, const mi_mules_fields* fl, c
     return MI_OK;
 }
 const int kMuFB[8] = {MU_FACE, MU_BFACE, MU_FACE, MU_BFACE, MU_FACE, MU_BFACE, MU_FACE, MU_BFACE};
-
-// a row pass of `arrays` staged face arrays on the gradient's plan
-template <class K, class A>
-int mu_row_launch(mi_addr_s* a, int arrays, K k256, K k512, K k1024, A& q)
-{
-    const mi_addr_s::RowPlan& rp = a->rowPlan[1];
-    q.r.cap = row_cap(rp, arrays);
-    return row_launch(a, rp, rp.bs == 256 ? k256 : rp.bs == 512 ? k512 : k1024, q, (size_t)arrays * q.r.cap * sizeof(double));
-}
-#define MU_BS(K, ...) K<256, __VA_ARGS__>, K<512, __VA_ARGS__>, K<1024, __VA_ARGS__>
 
 int mu_begin(const std::string& who, mi_mules_s* h, int form, const mi_mules_fields* fl, const mi_mules_flux* fx, MuCall& c)
 {
@@ -413,8 +388,8 @@ int mu_launch_begin(mi_mules_s* h, int form, MuCall& c)
     if (h->nCells == 0) { h->begun = true; h->corr = false; return MI_OK; }
     mi_addr_s* a = h->addr;
     int r;
-    if (form == MI_MULES_LIMIT) r = c.lts ? mu_row_launch(a, 2, MU_BS(k_mules_bounds, true, true), c.a) : mu_row_launch(a, 2, MU_BS(k_mules_bounds, true, false), c.a);
-    else r = c.lts ? mu_row_launch(a, 2, MU_BS(k_mules_bounds, false, true), c.a) : mu_row_launch(a, 2, MU_BS(k_mules_bounds, false, false), c.a);
+    if (form == MI_MULES_LIMIT) r = c.lts ? row_launch_bs(a, 2, ROW_BS(k_mules_bounds, true, true), c.a) : row_launch_bs(a, 2, ROW_BS(k_mules_bounds, true, false), c.a);
+    else r = c.lts ? row_launch_bs(a, 2, ROW_BS(k_mules_bounds, false, true), c.a) : row_launch_bs(a, 2, ROW_BS(k_mules_bounds, false, false), c.a);
     if (r == MI_OK) { h->begun = true; h->corr = false; }
     return r;
 }
@@ -452,8 +427,8 @@ int mu_launch_begin_corr(mi_mules_s* h, int form, MuCall& c)
     int r = MI_OK;
     if (h->nCells > 0) {
         mi_addr_s* a = h->addr;
-        if (form == MI_MULES_CORR_LIMIT) r = c.lts ? mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, true, true), c.a) : mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, true, false), c.a);
-        else r = c.lts ? mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, false, true), c.a) : mu_row_launch(a, 1, MU_BS(k_mules_corr_bounds, false, false), c.a);
+        if (form == MI_MULES_CORR_LIMIT) r = c.lts ? row_launch_bs(a, 1, ROW_BS(k_mules_corr_bounds, true, true), c.a) : row_launch_bs(a, 1, ROW_BS(k_mules_corr_bounds, true, false), c.a);
+        else r = c.lts ? row_launch_bs(a, 1, ROW_BS(k_mules_corr_bounds, false, true), c.a) : row_launch_bs(a, 1, ROW_BS(k_mules_corr_bounds, false, false), c.a);
     }
     if (r == MI_OK) { h->begun = true; h->corr = true; }
     return r;
@@ -482,7 +457,7 @@ int mu_launch_iterate(mi_mules_s* h, int n, MuCall& c, bool corr)
     mi_addr_s* a = h->addr;
     const int64_t faces = std::max<int64_t>(h->nFaces, h->nBFaces);
     for (int j = 0; j < n; ++j) {
-        MICHK(mu_row_launch(a, 2, k_mules_sums<256>, k_mules_sums<512>, k_mules_sums<1024>, c.a));
+        MICHK(row_launch_bs(a, 2, ROW_BS(k_mules_sums), c.a));
         if (faces > 0) {
             if (corr) k_mules_lambda<true><<<grid_for(a->ctx, (int)faces), 256, 0, a->ctx->stream>>>(c.a);
             else k_mules_lambda<false><<<grid_for(a->ctx, (int)faces), 256, 0, a->ctx->stream>>>(c.a);
@@ -507,7 +482,7 @@ int mu_check_apply(const std::string& who, mi_mules_s* h, int returnCorr, const 
         if (fx->out_dev != fx->phi_corr_dev) { in[n] = fx->phi_corr_dev; k[n++] = MU_FACE; }
         if (fx->b_out_dev != fx->b_phi_corr_dev) { in[n] = fx->b_phi_corr_dev; k[n++] = MU_BFACE; }
         const double* pa[2] = {fx->phi_corr_dev, fx->b_phi_corr_dev};     // an aliased one is an output to the checks below: aligned like them
-        MICHK(rc_aligned(who, (const void* const*)pa, 2));
+        MICHK(arrays_aligned8(who, (const void* const*)pa, 2));
         return mu_check(who, h, fl, in, k, n, out, kMuFB, 2, c, MU_CORR);
     }
     const double* in[6] = {fx->phi_bd_dev, fx->b_phi_bd_dev, fx->phi_corr_dev, fx->b_phi_corr_dev, fx->lambda_dev, fx->b_lambda_dev};
@@ -533,12 +508,10 @@ int mu_no_couples(const std::string& who, const mi_mules_s* h)
 extern "C" int mi_mules_create(mi_addr_t a, mi_grad_boundary_t b, const int32_t* patch_is_wedge_host_or_null, mi_mules_t* out)
 {
     const std::string who = "mi_mules_create";
-    if (!a || !out) return fail(MI_ERR_ARG, who + ": bad argument");
-    if (b && (b->addr != a || b->nCells != a->L.nCells)) return fail(MI_ERR_ARG, who + ": the boundary was built for another addressing");
+    std::unique_ptr<mi_mules_s> h(new mi_mules_s());
+    MICHK(row_handle_open(who, a, b, out, *h));
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    std::unique_ptr<mi_mules_s> h(new mi_mules_s());
-    h->ctx = a->ctx; h->addr = a; h->boundary = b; h->nCells = a->L.nCells; h->nFaces = a->L.nFaces; h->nBFaces = b ? b->nFaces : 0;
     if (h->nCells == 0) { *out = h.release(); return MI_OK; }
     for (int i = 0; i < 6; ++i) MICHK(h->work[i].alloc((size_t)h->nCells));
     if (h->nBFaces > 0) {
@@ -571,8 +544,8 @@ extern "C" int mi_mules_work(mi_mules_t h, double* const* out_dev)
     if (!out_dev) return fail(MI_ERR_ARG, who + ": output arrays missing");
     const double* in[6];
     for (int i = 0; i < 6; ++i) in[i] = h->work[i].p;
-    MICHK(ls_outputs(who, in, 6, out_dev, 6));
-    MICHK(rc_aligned(who, (const void* const*)out_dev, 6));
+    MICHK(outputs_distinct(who, in, 6, out_dev, 6));
+    MICHK(arrays_aligned8(who, (const void* const*)out_dev, 6));
     HIPCHK(hipSetDevice(h->ctx->device));
     for (int i = 0; i < 6; ++i)
         HIPCHK(hipMemcpyAsync(out_dev[i], h->work[i].p, (size_t)h->nCells * sizeof(double), hipMemcpyDeviceToDevice, h->ctx->stream));
@@ -693,7 +666,7 @@ extern "C" int mi_mules_correct(mi_mules_t h, const mi_mules_fields* fields, con
     c.a.q.psiOld = psi_inout_dev;                     // rhoOld is rho already
     c.a.x.phiPsi = phi_corr_dev; c.a.x.bphiPsi = b_phi_corr_dev; c.a.x.out = psi_inout_dev;
     mi_addr_s* a = h->addr;
-    return c.lts ? mu_row_launch(a, 1, MU_BS(k_mules_solve, true), c.a) : mu_row_launch(a, 1, MU_BS(k_mules_solve, false), c.a);
+    return c.lts ? row_launch_bs(a, 1, ROW_BS(k_mules_solve, true), c.a) : row_launch_bs(a, 1, ROW_BS(k_mules_solve, false), c.a);
 }
 
 extern "C" int mi_mules_explicit_solve(mi_mules_t h, const mi_mules_fields* fields, const double* phi_psi_dev, const double* b_phi_psi_dev,
@@ -712,7 +685,7 @@ extern "C" int mi_mules_explicit_solve(mi_mules_t h, const mi_mules_fields* fiel
     MICHK(mu_check(who, h, fields, in, kMuFB, 2, out, cellOut, 1, c));
     c.a.x.phiPsi = phi_psi_dev; c.a.x.bphiPsi = b_phi_psi_dev; c.a.x.out = psi_out_dev;
     mi_addr_s* a = h->addr;
-    return c.lts ? mu_row_launch(a, 1, MU_BS(k_mules_solve, true), c.a) : mu_row_launch(a, 1, MU_BS(k_mules_solve, false), c.a);
+    return c.lts ? row_launch_bs(a, 1, ROW_BS(k_mules_solve, true), c.a) : row_launch_bs(a, 1, ROW_BS(k_mules_solve, false), c.a);
 }
 
 extern "C" int mi_vec_min(mi_ctx_t c, int64_t n, const double* x_dev, const double* y_dev, double* out_dev)
@@ -816,7 +789,7 @@ int ic_patch(const char* who, mi_patch_s* p, const double* cdw, const double* fl
     const double* in[4] = {cdw, flux, alpha, nbr};
     MICHK(lim_outputs(who, in, 4, out, limOut));
     const void* al[6] = {cdw, flux, alpha, nbr, out, limOut};
-    MICHK(rc_aligned(who, al, 6));
+    MICHK(arrays_aligned8(who, al, 6));
     HIPCHK(hipSetDevice(p->ctx->device));
     IcArgs q{};
     q.lo = p->faceCells.p; q.cdw = cdw; q.flux = flux; q.alpha = alpha; q.nbr = nbr; q.w = out; q.limOut = limOut; q.nf = p->nFaces;

@@ -17,15 +17,14 @@
 namespace mi {
 
 struct RcBuildArgs {
-    const int32_t *os, *ls, *losort;
-    const int32_t *bStart, *bFace;                    // per-cell boundary faces (mi_grad_boundary_s::allStart / all)
+    RowTables r;
     const double *sf[3], *magSf, *bsf[3], *bMagSf;
     double *hat[3], *bhat[3];                         // SfHat, internal and boundary faces
     double* T[9];                                     // xx xy xz yx yy yz zx zy zz; inverted in place by k_rc_invert
     double* T0;                                       // caller cell 0's tensor, nine values (the read-back for removeCmpts)
     double add[9];                                    // removeCmpts as the tensor added before and subtracted after the inversion
     int removes;
-    int n, nf, nb;
+    int nf, nb;
 };
 
 // SfHat = Sf/magSf on the internal faces [0, nf) and the boundary faces [nf, nf + nb), one thread a face
@@ -49,7 +48,7 @@ __global__ __launch_bounds__(256) void k_rc_hat(const RcBuildArgs a)
 __global__ __launch_bounds__(256) void k_rc_tensor(const RcBuildArgs a)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.n) return;
+    if (c >= a.r.n) return;
     double T[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     auto add = [&](const double* const* hat, const double* const* sf, int f) {
         const double h[3] = {hat[0][f], hat[1][f], hat[2][f]}, s[3] = {sf[0][f], sf[1][f], sf[2][f]};
@@ -58,9 +57,9 @@ __global__ __launch_bounds__(256) void k_rc_tensor(const RcBuildArgs a)
 #pragma unroll
             for (int j = 0; j < 3; ++j) { const double p = h[i] * s[j]; T[3 * i + j] = T[3 * i + j] + p; }
     };
-    for (int f = a.os[c]; f < a.os[c + 1]; ++f) add(a.hat, a.sf, f);
-    for (int j = a.ls[c]; j < a.ls[c + 1]; ++j) add(a.hat, a.sf, a.losort[j]);
-    if (a.bStart) for (int j = a.bStart[c]; j < a.bStart[c + 1]; ++j) add(a.bhat, a.bsf, a.bFace[j]);
+    for (int f = a.r.os[c]; f < a.r.os[c + 1]; ++f) add(a.hat, a.sf, f);
+    for (int j = a.r.ls[c]; j < a.r.ls[c + 1]; ++j) add(a.hat, a.sf, a.r.losort[j]);
+    if (a.r.bStart) for (int j = a.r.bStart[c]; j < a.r.bStart[c + 1]; ++j) add(a.bhat, a.bsf, a.r.bFace[j]);
 #pragma unroll
     for (int i = 0; i < 9; ++i) a.T[i][c] = T[i];
     if (c == 0) {
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(256) void k_rc_tensor(const RcBuildArgs a)
 __global__ __launch_bounds__(256) void k_rc_invert(const RcBuildArgs a)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.n) return;
+    if (c >= a.r.n) return;
     double t[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) { t[i] = a.T[i][c]; if (a.removes) t[i] = t[i] + a.add[i]; }
@@ -89,12 +88,10 @@ __global__ __launch_bounds__(256) void k_rc_invert(const RcBuildArgs a)
 }
 
 struct RcArgs {
-    const int32_t *os, *ls, *losort, *blockStart;
-    const int32_t *bStart, *bFace;
+    RowTables r;
     const double *hat[3], *bhat[3], *ssf[4], *bssf[4], *inv[9];
     double* out[12];                                  // out[3*r + k]
-    int n, cap, xcd;
-    int nst;                                          // the first nst fluxes are staged beside SfHat; the others are read from global memory
+    int nst;                                         // the first nst fluxes are staged beside SfHat; the others are read from global memory
 };
 // the evaluation: k_gauss_grad's skeleton with 3 + nst staged face arrays (SfHat and the fluxes of the block's own faces; nst = NRHS unless
 // the largest block's faces do not fit the LDS budget with all of them), the first four neighbour-side faces in registers before the
@@ -105,27 +102,27 @@ __global__ __launch_bounds__(BS) void k_reconstruct(const RcArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double rp_smem[];
     double* sh = rp_smem;                             // sh + k*cap: SfHat_k (k < 3), flux k - 3
-    const int lb = a.xcd ? xcd_block() : (int)blockIdx.x;
+    const int lb = a.r.xcd ? xcd_block() : (int)blockIdx.x;
     int c0, cEnd;
-    if (a.blockStart) { c0 = a.blockStart[lb]; cEnd = a.blockStart[lb + 1]; }
-    else { c0 = lb * BS; cEnd = min(c0 + BS, a.n); }
+    if (a.r.blockStart) { c0 = a.r.blockStart[lb]; cEnd = a.r.blockStart[lb + 1]; }
+    else { c0 = lb * BS; cEnd = min(c0 + BS, a.r.n); }
     const int tid = threadIdx.x, c = c0 + tid;
     const bool live = c < cEnd;
-    const int f0 = a.os[c0], nf = a.os[cEnd] - f0;
-    const bool staged = nf <= a.cap;
+    const int f0 = a.r.os[c0], nf = a.r.os[cEnd] - f0;
+    const bool staged = nf <= a.r.cap;
     if (staged) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) stage_dma8<BS>(a.hat[k] + f0, sh + k * a.cap, nf, tid);
+        for (int k = 0; k < 3; ++k) stage_dma8<BS>(a.hat[k] + f0, sh + k * a.r.cap, nf, tid);
 #pragma unroll
-        for (int r = 0; r < NRHS; ++r) if (r < a.nst) stage_dma8<BS>(a.ssf[r] + f0, sh + (3 + r) * a.cap, nf, tid);
+        for (int r = 0; r < NRHS; ++r) if (r < a.nst) stage_dma8<BS>(a.ssf[r] + f0, sh + (3 + r) * a.r.cap, nf, tid);
     }
     int nb = 0, ne = 0;
-    if (live) { nb = a.ls[c]; ne = a.ls[c + 1]; }
+    if (live) { nb = a.r.ls[c]; ne = a.r.ls[c + 1]; }
     const int cnt = ne - nb;
     int nfk[4]; double nh[4][3], nv[4][NRHS];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {                     // before the barrier: what LDS will not hold -- cut faces, and the fluxes past nst
-        nfk[k] = (k < cnt) ? a.losort[nb + k] : 0;
+        nfk[k] = (k < cnt) ? a.r.losort[nb + k] : 0;
         const int f = nfk[k];
         const bool cut = k < cnt && (!staged || f < f0);
 #pragma unroll
@@ -148,9 +145,9 @@ __global__ __launch_bounds__(BS) void k_reconstruct(const RcArgs a)
         double h[3], v[NRHS];
         if (staged && f >= f0) {
 #pragma unroll
-            for (int d = 0; d < 3; ++d) h[d] = sh[d * a.cap + (f - f0)];
+            for (int d = 0; d < 3; ++d) h[d] = sh[d * a.r.cap + (f - f0)];
 #pragma unroll
-            for (int r = 0; r < NRHS; ++r) v[r] = r < a.nst ? sh[(3 + r) * a.cap + (f - f0)] : a.ssf[r][f];
+            for (int r = 0; r < NRHS; ++r) v[r] = r < a.nst ? sh[(3 + r) * a.r.cap + (f - f0)] : a.ssf[r][f];
         } else {
 #pragma unroll
             for (int d = 0; d < 3; ++d) h[d] = a.hat[d][f];
@@ -159,22 +156,22 @@ __global__ __launch_bounds__(BS) void k_reconstruct(const RcArgs a)
         }
         term(h, v);
     };
-    const int ob = a.os[c], oe = a.os[c + 1];
+    const int ob = a.r.os[c], oe = a.r.os[c + 1];
     for (int f = ob; f < oe; ++f) face(f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) if (k < cnt) {
         if (staged && nfk[k] >= f0) {
             const int j = nfk[k] - f0;
 #pragma unroll
-            for (int d = 0; d < 3; ++d) nh[k][d] = sh[d * a.cap + j];
+            for (int d = 0; d < 3; ++d) nh[k][d] = sh[d * a.r.cap + j];
 #pragma unroll
-            for (int r = 0; r < NRHS; ++r) if (r < a.nst) nv[k][r] = sh[(3 + r) * a.cap + j];
+            for (int r = 0; r < NRHS; ++r) if (r < a.nst) nv[k][r] = sh[(3 + r) * a.r.cap + j];
         }
         term(nh[k], nv[k]);
     }
-    for (int j = nb + 4; j < ne; ++j) face(a.losort[j]);
-    if (a.bStart) for (int j = a.bStart[c]; j < a.bStart[c + 1]; ++j) {
-        const int bf = a.bFace[j];
+    for (int j = nb + 4; j < ne; ++j) face(a.r.losort[j]);
+    if (a.r.bStart) for (int j = a.r.bStart[c]; j < a.r.bStart[c + 1]; ++j) {
+        const int bf = a.r.bFace[j];
         double h[3], v[NRHS];
 #pragma unroll
         for (int d = 0; d < 3; ++d) h[d] = a.bhat[d][bf];
@@ -195,29 +192,10 @@ __global__ __launch_bounds__(BS) void k_reconstruct(const RcArgs a)
 } // namespace mi
 
 // the reconstruction data of one mesh: inv(surfaceSum(SfHat*Sf)) per cell and SfHat per internal and boundary face, caller's order
-struct mi_reconstruct_s {
-    mi_ctx_s* ctx = nullptr;
-    mi_addr_s* addr = nullptr;
-    mi_grad_boundary_s* boundary = nullptr;
-    int32_t nCells = 0, nFaces = 0, nBFaces = 0;
+struct mi_reconstruct_s : RowHandle {
     int32_t removed[3] = {0, 0, 0};
     DevBuf<double> hat[3], bhat[3], inv[9];
 };
-
-namespace {
-template <int NRHS>
-int rc_launch(mi_addr_s* a, const mi_addr_s::RowPlan& rp, const RcArgs& q, size_t lds)
-{
-    if (rp.bs == 256) return row_launch(a, rp, k_reconstruct<256, NRHS>, q, lds);
-    if (rp.bs == 512) return row_launch(a, rp, k_reconstruct<512, NRHS>, q, lds);
-    return row_launch(a, rp, k_reconstruct<1024, NRHS>, q, lds);
-}
-int rc_aligned(const std::string& who, const void* const* p, int n)
-{
-    for (int i = 0; i < n; ++i) if (!al8(p[i])) return fail(MI_ERR_ARG, who + ": arrays must be aligned to 8 bytes");
-    return MI_OK;
-}
-} // namespace
 
 extern "C" int mi_surface_sum(mi_addr_t a, int32_t mode, const double* ssf_dev, double* out_dev)
 {
@@ -227,7 +205,7 @@ extern "C" int mi_surface_sum(mi_addr_t a, int32_t mode, const double* ssf_dev, 
     if (a->L.nCells == 0) return MI_OK;
     if (!out_dev || (!ssf_dev && !faceless(a))) return fail(MI_ERR_ARG, who + ": an array is missing");
     const void* p[2] = {ssf_dev, out_dev};
-    MICHK(rc_aligned(who, p, 2));
+    MICHK(arrays_aligned8(who, p, 2));
     if (out_dev == ssf_dev) return fail(MI_ERR_ARG, who + ": the output must not alias the input");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
@@ -240,9 +218,9 @@ extern "C" int mi_reconstruct_create(mi_addr_t a, mi_grad_boundary_t b, const do
                                      const double* const* b_sf_dev, const double* b_mag_sf_dev, mi_reconstruct_t* out)
 {
     const std::string who = "mi_reconstruct_create";
-    if (!a || !out) return fail(MI_ERR_ARG, who + ": bad argument");
-    if (b && (b->addr != a || b->nCells != a->L.nCells)) return fail(MI_ERR_ARG, who + ": the boundary was built for another addressing");
-    const int32_t n = a->L.nCells, nf = a->L.nFaces, nb = b ? b->nFaces : 0;
+    std::unique_ptr<mi_reconstruct_s> v(new mi_reconstruct_s());
+    MICHK(row_handle_open(who, a, b, out, *v));
+    const int32_t n = v->nCells, nf = v->nFaces, nb = v->nBFaces;
     const void* in[8];
     int nIn = 0;
     if (nf > 0) {
@@ -256,12 +234,10 @@ extern "C" int mi_reconstruct_create(mi_addr_t a, mi_grad_boundary_t b, const do
         for (int k = 0; k < 3; ++k) in[nIn++] = b_sf_dev[k];
         in[nIn++] = b_mag_sf_dev;
     }
-    MICHK(rc_aligned(who, in, nIn));
+    MICHK(arrays_aligned8(who, in, nIn));
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     hipStream_t s = a->ctx->stream;
-    std::unique_ptr<mi_reconstruct_s> v(new mi_reconstruct_s());
-    v->ctx = a->ctx; v->addr = a; v->boundary = b; v->nCells = n; v->nFaces = nf; v->nBFaces = nb;
     if (n == 0) { *out = v.release(); return MI_OK; }
     for (int k = 0; k < 3; ++k) {
         if (nf > 0) MICHK(v->hat[k].alloc((size_t)nf));
@@ -271,15 +247,15 @@ extern "C" int mi_reconstruct_create(mi_addr_t a, mi_grad_boundary_t b, const do
     DevBuf<double> t0;                                // caller cell 0's nine values
     MICHK(t0.alloc(9));
     RcBuildArgs q{};
-    q.os = a->ownerStartC.p; q.ls = a->losortStartC.p; q.losort = a->losortC.p;
+    q.r = row_tables(a, b);
     if (nf > 0) { for (int k = 0; k < 3; ++k) { q.sf[k] = sf_dev[k]; q.hat[k] = v->hat[k].p; } q.magSf = mag_sf_dev; }
     if (nb > 0) {
-        q.bStart = b->allStart.p; q.bFace = b->all.p; q.bMagSf = b_mag_sf_dev;
+        q.bMagSf = b_mag_sf_dev;
         for (int k = 0; k < 3; ++k) { q.bsf[k] = b_sf_dev[k]; q.bhat[k] = v->bhat[k].p; }
     }
     for (int i = 0; i < 9; ++i) q.T[i] = v->inv[i].p;
     q.T0 = t0.p;
-    q.n = n; q.nf = nf; q.nb = nb;
+    q.nf = nf; q.nb = nb;
     const int cellBlocks = (n + 255) / 256;
     const int64_t faces = (int64_t)nf + nb;
     if (faces > 0) { k_rc_hat<<<(unsigned)((faces + 255) / 256), 256, 0, s>>>(q); HIPCHK(hipGetLastError()); }
@@ -310,8 +286,8 @@ extern "C" int mi_reconstruct_fields(mi_reconstruct_t rc, double* const* inv_out
         if (!inv_out_dev) return fail(MI_ERR_ARG, who + ": output arrays missing");
         const double* in[9];
         for (int i = 0; i < 9; ++i) in[i] = rc->inv[i].p;
-        MICHK(ls_outputs(who, in, 9, inv_out_dev, 9));
-        MICHK(rc_aligned(who, (const void* const*)inv_out_dev, 9));
+        MICHK(outputs_distinct(who, in, 9, inv_out_dev, 9));
+        MICHK(arrays_aligned8(who, (const void* const*)inv_out_dev, 9));
         HIPCHK(hipSetDevice(rc->ctx->device));
         for (int i = 0; i < 9; ++i)
             HIPCHK(hipMemcpyAsync(inv_out_dev[i], rc->inv[i].p, (size_t)rc->nCells * sizeof(double), hipMemcpyDeviceToDevice, rc->ctx->stream));
@@ -327,8 +303,7 @@ extern "C" int mi_fvc_reconstruct(mi_reconstruct_t rc, int32_t n_rhs, const doub
     if (!rc) return fail(MI_ERR_ARG, who + ": bad argument");
     if (n_rhs < 1 || n_rhs > 4) return fail(MI_ERR_ARG, who + ": n_rhs must be 1 to 4");
     mi_addr_s* a = rc->addr;
-    if (rc->nCells != a->L.nCells || rc->nFaces != a->L.nFaces || (rc->boundary && rc->boundary->addr != a))
-        return fail(MI_ERR_ARG, who + ": the handle was built for another addressing");
+    MICHK(row_handle_check(who, rc));
     if (rc->nCells == 0) return MI_OK;
     if (!out_dev) return fail(MI_ERR_ARG, who + ": output arrays missing");
     const bool hasF = rc->nFaces > 0, hasB = rc->nBFaces > 0;
@@ -337,18 +312,17 @@ extern "C" int mi_fvc_reconstruct(mi_reconstruct_t rc, int32_t n_rhs, const doub
     const double* in[23];
     int nIn = 0;
     for (int r = 0; r < n_rhs; ++r) { if (hasF) in[nIn++] = ssf_dev[r]; if (hasB) in[nIn++] = b_ssf_dev_or_null[r]; }
-    for (int i = 0; i < nIn; ++i) if (!in[i]) return fail(MI_ERR_ARG, who + ": input arrays missing");
-    MICHK(rc_aligned(who, (const void* const*)in, nIn));
+    MICHK(arrays_present(who, in, nIn));
+    MICHK(arrays_aligned8(who, (const void* const*)in, nIn));
     for (int k = 0; k < 3; ++k) { if (hasF) in[nIn++] = rc->hat[k].p; if (hasB) in[nIn++] = rc->bhat[k].p; }
     for (int i = 0; i < 9; ++i) in[nIn++] = rc->inv[i].p;
-    MICHK(ls_outputs(who, in, nIn, out_dev, 3 * n_rhs));
-    MICHK(rc_aligned(who, (const void* const*)out_dev, 3 * n_rhs));
+    MICHK(outputs_distinct(who, in, nIn, out_dev, 3 * n_rhs));
+    MICHK(arrays_aligned8(who, (const void* const*)out_dev, 3 * n_rhs));
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     RcArgs q{};
     const mi_addr_s::RowPlan& rp = a->rowPlan[1];     // the gradient's plan
-    q.os = a->ownerStartC.p; q.ls = a->losortStartC.p; q.losort = a->losortC.p; q.blockStart = rp.tiles ? a->tileCellStart.p : nullptr;
-    if (hasB) { q.bStart = rc->boundary->allStart.p; q.bFace = rc->boundary->all.p; }
+    q.r = row_tables(a, rc->boundary);
     for (int k = 0; k < 3; ++k) { q.hat[k] = rc->hat[k].p; q.bhat[k] = rc->bhat[k].p; }
     for (int r = 0; r < n_rhs; ++r) { if (hasF) q.ssf[r] = ssf_dev[r]; if (hasB) q.bssf[r] = b_ssf_dev_or_null[r]; }
     for (int i = 0; i < 9; ++i) q.inv[i] = rc->inv[i].p;
@@ -362,12 +336,10 @@ extern "C" int mi_fvc_reconstruct(mi_reconstruct_t rc, int32_t n_rhs, const doub
         if (row_cap(rp, 3 + nst) < want) nst = n_rhs;  // not even SfHat alone: the blocks that fit stage everything, the others nothing
     }
     q.nst = nst;
-    q.n = a->L.nCells; q.cap = row_cap(rp, 3 + nst); q.xcd = a->ctx->xcdRows;
-    const size_t lds = (size_t)(3 + nst) * q.cap * sizeof(double);
     switch (n_rhs) {
-    case 1: return rc_launch<1>(a, rp, q, lds);
-    case 2: return rc_launch<2>(a, rp, q, lds);
-    case 3: return rc_launch<3>(a, rp, q, lds);
-    default: return rc_launch<4>(a, rp, q, lds);
+    case 1: return row_launch_bs(a, 3 + nst, ROW_BS(k_reconstruct, 1), q);
+    case 2: return row_launch_bs(a, 3 + nst, ROW_BS(k_reconstruct, 2), q);
+    case 3: return row_launch_bs(a, 3 + nst, ROW_BS(k_reconstruct, 3), q);
+    default: return row_launch_bs(a, 3 + nst, ROW_BS(k_reconstruct, 4), q);
     }
 }

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void k_min_max_final(const double* __restrict_
 
 // ---- fvc::average and bound: row passes on mu_rows (the walk of k_mules_solve / k_interface_curvature) ------------------------------------
 struct AvArgs {
-    MuRow r;
+    RowTables r;
     const double *magSf, *bMagSf;                     // the weights, internal and boundary faces
     const double *x, *bx;                             // fvc_average: the face field; bound: lambda and the boundary face values
     const double *sum, *v;                            // surfaceSum(magSf) of the handle; bound: the cell field
@@ -247,19 +247,12 @@ __global__ __launch_bounds__(256) void k_ke_wall_values(const int32_t* __restric
 
 // fvc::average on one mesh: the row tables of the addressing, the boundary's per-cell face lists and surfaceSum(magSf); scratch is what
 // mi_bound writes before it copies back
-struct mi_average_s {
-    mi_ctx_s* ctx = nullptr;
-    mi_addr_s* addr = nullptr;
-    mi_grad_boundary_s* boundary = nullptr;
-    int32_t nCells = 0, nFaces = 0, nBFaces = 0;
+struct mi_average_s : RowHandle {
     DevBuf<double> sum, scratch;
 };
 // the wall cells of one mesh
-struct mi_ke_s {
-    mi_ctx_s* ctx = nullptr;
-    mi_addr_s* addr = nullptr;
-    mi_grad_boundary_s* boundary = nullptr;
-    int32_t nCells = 0, nBFaces = 0, nWallCells = 0, nWallFaces = 0;
+struct mi_ke_s : RowHandle {
+    int32_t nWallCells = 0, nWallFaces = 0;
     DevBuf<int32_t> cells, start, faces, faceCell;
     DevBuf<double> weight;
 };
@@ -273,13 +266,6 @@ int ke_coeffs_check(const std::string& who, const mi_ke_coeffs* k)
     for (double x : v) if (!ke_positive(x)) return fail(MI_ERR_ARG, who + ": every coefficient must be a finite number above zero (mi_ke_coeffs_init)");
     return MI_OK;
 }
-bool ke_all16(const double* const* in, int nIn, double* const* out, int nOut)
-{
-    bool v = true;
-    for (int i = 0; i < nIn; ++i) v = v && al16(in[i]);
-    for (int i = 0; i < nOut; ++i) v = v && al16(out[i]);
-    return v;
-}
 // the checks of a cell pass (missing, aliased, not aligned for a double), then the launch under the face-grid cap
 template <class K>
 int ke_cell_pass(const std::string& who, mi_ctx_s* c, int64_t n, K kernel, mi::KeCell& q, const double* const* in, int nIn, double* const* out, int nOut,
@@ -289,33 +275,17 @@ int ke_cell_pass(const std::string& who, mi_ctx_s* c, int64_t n, K kernel, mi::K
     if (n > INT32_MAX) return fail(MI_ERR_ARG, who + ": too many cells");
     if (n == 0) return MI_OK;
     if (inPlace) { if (!in[0] || !out[0]) return fail(MI_ERR_ARG, who + ": arrays missing"); }
-    else MICHK(if_outputs(who, in, nIn, out, nOut));
-    MICHK(rc_aligned(who, (const void* const*)in, nIn));
-    MICHK(rc_aligned(who, (const void* const*)out, nOut));
+    else { MICHK(arrays_present(who, in, nIn)); MICHK(outputs_distinct(who, in, nIn, out, nOut)); }
+    MICHK(arrays_aligned8(who, (const void* const*)in, nIn));
+    MICHK(arrays_aligned8(who, (const void* const*)out, nOut));
     for (int i = 0; i < nIn; ++i) q.in[i] = in[i];
     for (int i = 0; i < nOut; ++i) q.out[i] = out[i];
-    q.n = n; q.vec = ke_all16(in, nIn, out, nOut) ? 1 : 0;
+    q.n = n; q.vec = all_aligned16(in, nIn, out, nOut) ? 1 : 0;
     HIPCHK(hipSetDevice(c->device));
     kernel<<<grid_for(c, (int)((n + 1) / 2)), 256, 0, c->stream>>>(q);
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
-int av_check(const std::string& who, mi_average_s* h)
-{
-    if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
-    mi_addr_s* a = h->addr;
-    if (h->nCells != a->L.nCells || h->nFaces != a->L.nFaces || (h->boundary && (h->boundary->addr != a || h->boundary->nFaces != h->nBFaces)))
-        return fail(MI_ERR_ARG, who + ": the handle was built for another addressing");
-    return MI_OK;
-}
-void av_rows(mi_addr_s* a, mi_grad_boundary_s* b, MuRow& r)
-{
-    r.os = a->ownerStartC.p; r.ls = a->losortStartC.p; r.losort = a->losortC.p; r.lo = a->lowerAddr.p; r.up = a->upperAddr.p;
-    r.blockStart = a->rowPlan[1].tiles ? a->tileCellStart.p : nullptr;
-    if (b && b->nFaces > 0) { r.bStart = b->allStart.p; r.bFace = b->all.p; }
-    r.n = a->L.nCells; r.xcd = a->ctx->xcdRows;
-}
-#define AV_BS(K) K<256>, K<512>, K<1024>
 } // namespace
 
 extern "C" int mi_ke_coeffs_init(double Cmu, double C1, double C2, double sigmaEps, double kappa, double E, mi_ke_coeffs* out)
@@ -372,23 +342,21 @@ extern "C" int mi_vec_max_value(mi_ctx_t c, int64_t n, const double* x_dev, doub
 extern "C" int mi_average_create(mi_addr_t a, mi_grad_boundary_t b, const double* mag_sf_dev, const double* b_mag_sf_dev, mi_average_t* out)
 {
     const std::string who = "mi_average_create";
-    if (!a || !out) return fail(MI_ERR_ARG, who + ": bad argument");
-    if (b && (b->addr != a || b->nCells != a->L.nCells)) return fail(MI_ERR_ARG, who + ": the boundary was built for another addressing");
-    const int32_t nb = b ? b->nFaces : 0;
+    std::unique_ptr<mi_average_s> h(new mi_average_s());
+    MICHK(row_handle_open(who, a, b, out, *h));
+    const int32_t nb = h->nBFaces;
     if (a->L.nCells > 0 && a->L.nFaces > 0 && !mag_sf_dev) return fail(MI_ERR_ARG, who + ": an input array is missing");
     if (a->L.nCells > 0 && nb > 0 && !b_mag_sf_dev) return fail(MI_ERR_ARG, who + ": the boundary has faces: boundary face areas needed");
     if (!al8(mag_sf_dev) || !al8(b_mag_sf_dev)) return fail(MI_ERR_ARG, who + ": arrays must be aligned to 8 bytes");
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
-    std::unique_ptr<mi_average_s> h(new mi_average_s());
-    h->ctx = a->ctx; h->addr = a; h->boundary = b; h->nCells = a->L.nCells; h->nFaces = a->L.nFaces; h->nBFaces = nb;
     MICHK(h->sum.alloc((size_t)h->nCells));
     MICHK(h->scratch.alloc((size_t)h->nCells));
     if (h->nCells > 0) {
         AvArgs q{};
-        av_rows(a, b, q.r);
+        q.r = row_tables(a, b);
         q.magSf = mag_sf_dev; q.bMagSf = b_mag_sf_dev; q.out = h->sum.p;
-        MICHK(mu_row_launch(a, 1, AV_BS(k_average_sum), q));
+        MICHK(row_launch_bs(a, 1, ROW_BS(k_average_sum), q));
         HIPCHK(hipStreamSynchronize(a->ctx->stream));
     }
     *out = h.release();
@@ -400,7 +368,7 @@ extern "C" int mi_fvc_average(mi_average_t h, const double* mag_sf_dev, const do
                               double* out_dev)
 {
     const std::string who = "mi_fvc_average";
-    MICHK(av_check(who, h));
+    MICHK(row_handle_check(who, h));
     if (h->nCells == 0) return MI_OK;
     if (h->nFaces > 0 && (!mag_sf_dev || !ssf_dev)) return fail(MI_ERR_ARG, who + ": an input array is missing");
     if (h->nBFaces > 0 && (!b_mag_sf_dev || !b_ssf_dev)) return fail(MI_ERR_ARG, who + ": the boundary has faces: boundary arrays needed");
@@ -409,23 +377,24 @@ extern "C" int mi_fvc_average(mi_average_t h, const double* mag_sf_dev, const do
     if (h->nFaces > 0) { in[nIn++] = mag_sf_dev; in[nIn++] = ssf_dev; }
     if (h->nBFaces > 0) { in[nIn++] = b_mag_sf_dev; in[nIn++] = b_ssf_dev; }
     double* out[1] = {out_dev};
-    MICHK(if_outputs(who, in, nIn, out, 1));
-    MICHK(rc_aligned(who, (const void* const*)in, nIn));
-    MICHK(rc_aligned(who, (const void* const*)out, 1));
+    MICHK(arrays_present(who, in, nIn));
+    MICHK(outputs_distinct(who, in, nIn, out, 1));
+    MICHK(arrays_aligned8(who, (const void* const*)in, nIn));
+    MICHK(arrays_aligned8(who, (const void* const*)out, 1));
     mi_addr_s* a = h->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     AvArgs q{};
-    av_rows(a, h->boundary, q.r);
+    q.r = row_tables(a, h->boundary);
     q.magSf = mag_sf_dev; q.bMagSf = b_mag_sf_dev; q.x = ssf_dev; q.bx = b_ssf_dev; q.sum = h->sum.p; q.out = out_dev;
-    return mu_row_launch(a, 2, AV_BS(k_fvc_average), q);
+    return row_launch_bs(a, 2, ROW_BS(k_fvc_average), q);
 }
 
 extern "C" int mi_bound(mi_average_t h, double lower_bound, const double* lambda_dev, const double* mag_sf_dev, const double* b_mag_sf_dev,
                         const double* b_face_dev, double* vsf_inout_dev)
 {
     const std::string who = "mi_bound";
-    MICHK(av_check(who, h));
+    MICHK(row_handle_check(who, h));
     if (std::isnan(lower_bound)) return fail(MI_ERR_ARG, who + ": lower_bound is not a number");
     if (h->nCells == 0) return MI_OK;
     if (h->nFaces > 0 && (!mag_sf_dev || !lambda_dev)) return fail(MI_ERR_ARG, who + ": an input array is missing");
@@ -435,17 +404,18 @@ extern "C" int mi_bound(mi_average_t h, double lower_bound, const double* lambda
     if (h->nFaces > 0) { in[nIn++] = mag_sf_dev; in[nIn++] = lambda_dev; }
     if (h->nBFaces > 0) { in[nIn++] = b_mag_sf_dev; in[nIn++] = b_face_dev; }
     double* out[1] = {vsf_inout_dev};
-    MICHK(if_outputs(who, in, nIn, out, 1));
-    MICHK(rc_aligned(who, (const void* const*)in, nIn));
-    MICHK(rc_aligned(who, (const void* const*)out, 1));
+    MICHK(arrays_present(who, in, nIn));
+    MICHK(outputs_distinct(who, in, nIn, out, 1));
+    MICHK(arrays_aligned8(who, (const void* const*)in, nIn));
+    MICHK(arrays_aligned8(who, (const void* const*)out, 1));
     mi_addr_s* a = h->addr;
     HIPCHK(hipSetDevice(a->ctx->device));
     MICHK(ensure_caller_tables(a));
     AvArgs q{};
-    av_rows(a, h->boundary, q.r);
+    q.r = row_tables(a, h->boundary);
     q.magSf = mag_sf_dev; q.bMagSf = b_mag_sf_dev; q.x = lambda_dev; q.bx = b_face_dev; q.sum = h->sum.p; q.v = vsf_inout_dev; q.lb = lower_bound;
     q.out = h->scratch.p;
-    MICHK(mu_row_launch(a, 2, AV_BS(k_bound), q));
+    MICHK(row_launch_bs(a, 2, ROW_BS(k_bound), q));
     HIPCHK(hipMemcpyAsync(vsf_inout_dev, h->scratch.p, (size_t)h->nCells * sizeof(double), hipMemcpyDeviceToDevice, a->ctx->stream));
     return MI_OK;
 }
@@ -501,8 +471,9 @@ extern "C" int mi_ke_nut(mi_ctx_t c, int64_t n, double Cmu, const double* k_dev,
 extern "C" int mi_ke_create(mi_addr_t a, mi_grad_boundary_t b, const int32_t* patch_is_wall, mi_ke_t* out)
 {
     const std::string who = "mi_ke_create";
-    if (!a || !b || !out) return fail(MI_ERR_ARG, who + ": bad argument");
-    if (b->addr != a || b->nCells != a->L.nCells) return fail(MI_ERR_ARG, who + ": the boundary was built for another addressing");
+    if (!b) return fail(MI_ERR_ARG, who + ": bad argument");   // the wall cells are the boundary's
+    std::unique_ptr<mi_ke_s> h(new mi_ke_s());
+    MICHK(row_handle_open(who, a, b, out, *h));
     const int32_t nP = (int32_t)b->patchSizes.size(), n = b->nCells, nb = b->nFaces;
     if (nP > 0 && !patch_is_wall) return fail(MI_ERR_ARG, who + ": patch_is_wall is missing");
     std::vector<uint8_t> wall((size_t)nb, 0);         // per boundary face: on a wall patch
@@ -514,7 +485,7 @@ extern "C" int mi_ke_create(mi_addr_t a, mi_grad_boundary_t b, const int32_t* pa
             off += b->patchSizes[p];
         }
     }
-    HIPCHK(hipSetDevice(a->ctx->device));
+    HIPCHK(hipSetDevice(a->ctx->device));               // no caller-order tables: the wall kernels walk the handle's own lists
     // the boundary's per-cell face lists hold every cell's boundary faces by patch, then by face: the wall faces among them, in that order
     std::vector<int32_t> allStart((size_t)n + 1, 0), all((size_t)nb);
     if (nb > 0) {
@@ -532,8 +503,6 @@ extern "C" int mi_ke_create(mi_addr_t a, mi_grad_boundary_t b, const int32_t* pa
         }
     }
     start.push_back((int32_t)faces.size());
-    std::unique_ptr<mi_ke_s> h(new mi_ke_s());
-    h->ctx = a->ctx; h->addr = a; h->boundary = b; h->nCells = n; h->nBFaces = nb;
     h->nWallCells = (int32_t)cells.size(); h->nWallFaces = (int32_t)faces.size();
     hipStream_t s = a->ctx->stream;
     MICHK(h->cells.upload(cells, s)); MICHK(h->start.upload(start, s)); MICHK(h->faces.upload(faces, s)); MICHK(h->faceCell.upload(faceCell, s));
@@ -545,13 +514,6 @@ extern "C" int mi_ke_create(mi_addr_t a, mi_grad_boundary_t b, const int32_t* pa
 extern "C" int mi_ke_destroy(mi_ke_t h) { delete h; return MI_OK; }
 
 namespace {
-int ke_handle(const std::string& who, mi_ke_s* h)
-{
-    if (!h) return fail(MI_ERR_ARG, who + ": bad argument");
-    if (h->nCells != h->addr->L.nCells || h->boundary->addr != h->addr || h->boundary->nFaces != h->nBFaces)
-        return fail(MI_ERR_ARG, who + ": the handle was built for another addressing");
-    return MI_OK;
-}
 void ke_wall_tables(const mi_ke_s* h, const mi_ke_coeffs* k, KeWallArgs& q)
 {
     q.cells = h->cells.p; q.start = h->start.p; q.faces = h->faces.p; q.faceCell = h->faceCell.p; q.weight = h->weight.p;
@@ -563,7 +525,7 @@ void ke_wall_tables(const mi_ke_s* h, const mi_ke_coeffs* k, KeWallArgs& q)
 extern "C" int mi_ke_wall_cells(mi_ke_t h, const mi_ke_coeffs* coeffs, const mi_ke_wall* x)
 {
     const std::string who = "mi_ke_wall_cells";
-    MICHK(ke_handle(who, h));
+    MICHK(row_handle_check(who, h));
     MICHK(ke_coeffs_check(who, coeffs));
     if (!x) return fail(MI_ERR_ARG, who + ": the arrays are missing");
     if (h->nWallFaces == 0) return MI_OK;
@@ -571,9 +533,10 @@ extern "C" int mi_ke_wall_cells(mi_ke_t h, const mi_ke_coeffs* coeffs, const mi_
                             x->b_delta_coeffs_dev, x->b_y_dev, x->b_nuw_dev, x->b_nutw_dev};
     double* out[4] = {x->g_inout_dev, x->eps_inout_dev, x->b_eps_out_dev, x->b_pow_out_dev};
     const int nOut = x->b_pow_out_dev ? 4 : 3;
-    MICHK(if_outputs(who, in, 11, out, nOut));
-    MICHK(rc_aligned(who, (const void* const*)in, 11));
-    MICHK(rc_aligned(who, (const void* const*)out, nOut));
+    MICHK(arrays_present(who, in, 11));
+    MICHK(outputs_distinct(who, in, 11, out, nOut));
+    MICHK(arrays_aligned8(who, (const void* const*)in, 11));
+    MICHK(arrays_aligned8(who, (const void* const*)out, nOut));
     HIPCHK(hipSetDevice(h->ctx->device));
     KeWallArgs q{};
     ke_wall_tables(h, coeffs, q);
@@ -589,15 +552,16 @@ extern "C" int mi_ke_nut_wall(mi_ke_t h, const mi_ke_coeffs* coeffs, const doubl
                               double* b_nutw_out_dev, double* b_log_out_dev_or_null)
 {
     const std::string who = "mi_ke_nut_wall";
-    MICHK(ke_handle(who, h));
+    MICHK(row_handle_check(who, h));
     MICHK(ke_coeffs_check(who, coeffs));
     if (h->nWallFaces == 0) return MI_OK;
     const double* in[3] = {k_dev, b_y_dev, b_nuw_dev};
     double* out[2] = {b_nutw_out_dev, b_log_out_dev_or_null};
     const int nOut = b_log_out_dev_or_null ? 2 : 1;
-    MICHK(if_outputs(who, in, 3, out, nOut));
-    MICHK(rc_aligned(who, (const void* const*)in, 3));
-    MICHK(rc_aligned(who, (const void* const*)out, nOut));
+    MICHK(arrays_present(who, in, 3));
+    MICHK(outputs_distinct(who, in, 3, out, nOut));
+    MICHK(arrays_aligned8(who, (const void* const*)in, 3));
+    MICHK(arrays_aligned8(who, (const void* const*)out, nOut));
     HIPCHK(hipSetDevice(h->ctx->device));
     KeWallArgs q{};
     ke_wall_tables(h, coeffs, q);
@@ -609,7 +573,7 @@ extern "C" int mi_ke_nut_wall(mi_ke_t h, const mi_ke_coeffs* coeffs, const doubl
 
 extern "C" int mi_ke_wall_cell_labels(mi_ke_t h, int32_t* n_out, const int32_t** labels_dev_out)
 {
-    MICHK(ke_handle("mi_ke_wall_cell_labels", h));
+    MICHK(row_handle_check("mi_ke_wall_cell_labels", h));
     if (!n_out || !labels_dev_out) return fail(MI_ERR_ARG, "mi_ke_wall_cell_labels: bad argument");
     *n_out = h->nWallCells;
     *labels_dev_out = h->cells.p;
@@ -619,13 +583,14 @@ extern "C" int mi_ke_wall_cell_labels(mi_ke_t h, int32_t* n_out, const int32_t**
 extern "C" int mi_ke_wall_values(mi_ke_t h, const double* eps_dev, double* values_out_dev)
 {
     const std::string who = "mi_ke_wall_values";
-    MICHK(ke_handle(who, h));
+    MICHK(row_handle_check(who, h));
     if (h->nWallCells == 0) return MI_OK;
     const double* in[1] = {eps_dev};
     double* out[1] = {values_out_dev};
-    MICHK(if_outputs(who, in, 1, out, 1));
-    MICHK(rc_aligned(who, (const void* const*)in, 1));
-    MICHK(rc_aligned(who, (const void* const*)out, 1));
+    MICHK(arrays_present(who, in, 1));
+    MICHK(outputs_distinct(who, in, 1, out, 1));
+    MICHK(arrays_aligned8(who, (const void* const*)in, 1));
+    MICHK(arrays_aligned8(who, (const void* const*)out, 1));
     HIPCHK(hipSetDevice(h->ctx->device));
     k_ke_wall_values<<<grid_for(h->ctx, h->nWallCells), 256, 0, h->ctx->stream>>>(h->cells.p, eps_dev, values_out_dev, h->nWallCells);
     HIPCHK(hipGetLastError());

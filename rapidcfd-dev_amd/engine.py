@@ -235,6 +235,11 @@ def _ptr(t) -> C.c_void_p:
     return C.c_void_p(t.data_ptr())
 
 
+def _ptrs(xs, least=1):
+    """The device pointers of a list of tensors as a C array of at least `least` entries, NULL past the list (or None for None)."""
+    return None if xs is None else (C.c_void_p * max(len(xs), least))(*[_ptr(x) for x in xs])
+
+
 class Context:
     def __init__(self, device: int = 0, stream_handle: Optional[int] = None):
         self.h = C.c_void_p()
@@ -935,25 +940,22 @@ class Patch:
         """patchFlux*correction(vf) of linearUpwind (scale 1) / LUST (scale 0.25) on a COUPLED patch (linearUpwind.C:49-62): grad and nbr_grad one
         [gx, gy, gz] per component (cell gradients / their patchNeighbourField), out one patch array per component"""
         n = len(out)
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_patch_linear_upwind_correction(self.h, C.c_double(scale), C.c_int32(n), _ptr(patch_flux), pv(patch_cf), pv(c), pv(patch_delta),
-                                                     pv([g for gr in grad for g in gr]), pv([g for gr in nbr_grad for g in gr]), pv(out)))
+        _chk(lib().mi_patch_linear_upwind_correction(self.h, C.c_double(scale), C.c_int32(n), _ptr(patch_flux), _ptrs(patch_cf), _ptrs(c), _ptrs(patch_delta),
+                                                     _ptrs([g for gr in grad for g in gr]), _ptrs([g for gr in nbr_grad for g in gr]), _ptrs(out)))
 
     def limited_weights(self, lim, patch_cd_weights, patch_flux, phi, nbr_phi, grad, nbr_grad, patch_delta, w_out, limiter_out=None):
         """a limited scheme's weights on a COUPLED patch (LimitedScheme.C:145-195): phi / nbr_phi 1 or 3 arrays (cell field, its
         patchNeighbourField), grad / nbr_grad 3 or 9 (grad[3*j + k] = d(phi_j)/dx_k), patch_delta [x, y, z]; lim a Limiter or a scheme name"""
         lim = limiter(lim) if isinstance(lim, str) else lim
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_patch_limited_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), pv(phi), pv(nbr_phi), pv(grad),
-                                            pv(nbr_grad), pv(patch_delta), _ptr(w_out), _ptr(limiter_out)))
+        _chk(lib().mi_patch_limited_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), _ptrs(phi), _ptrs(nbr_phi), _ptrs(grad),
+                                            _ptrs(nbr_grad), _ptrs(patch_delta), _ptr(w_out), _ptr(limiter_out)))
 
     def filtered_weights(self, lim, patch_cd_weights, patch_flux, phi, nbr_phi, grad, nbr_grad, patch_delta, w_out, limiter_out=None):
         """a filtered scheme's weights on a COUPLED patch (mi_patch_filtered_weights): the arguments of limited_weights; lim a FilteredLimiter
         or a scheme name"""
         lim = filtered(lim) if isinstance(lim, str) else lim
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_patch_filtered_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), pv(phi), pv(nbr_phi), pv(grad),
-                                             pv(nbr_grad), pv(patch_delta), _ptr(w_out), _ptr(limiter_out)))
+        _chk(lib().mi_patch_filtered_weights(self.h, C.byref(lim), _ptr(patch_cd_weights), _ptr(patch_flux), _ptrs(phi), _ptrs(nbr_phi), _ptrs(grad),
+                                             _ptrs(nbr_grad), _ptrs(patch_delta), _ptr(w_out), _ptr(limiter_out)))
 
     def interface_compression_weights(self, patch_cd_weights, patch_flux, alpha, nbr_alpha, w_out, limiter_out=None):
         """the interfaceCompression scheme's weights on a COUPLED patch (PhiScheme.C:145-189): alpha the cell field, nbr_alpha its
@@ -989,9 +991,8 @@ class Patch:
         """[patchFlux *] correction(vf) of cubic on a COUPLED patch (mi_patch_cubic_correction): geo a CubicGeometry of the patch's arrays, vf /
         nbr_vf one array per component (cell field, its patchNeighbourField), grad / nbr_grad one [gx, gy, gz] per component, out one patch
         array per component"""
-        pv = lambda xs: (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_patch_cubic_correction(self.h, C.byref(geo), C.c_int32(len(out)), pv(vf), pv(nbr_vf), pv([g for gr in grad for g in gr]),
-                                             pv([g for gr in nbr_grad for g in gr]), _ptr(patch_flux), pv(out)))
+        _chk(lib().mi_patch_cubic_correction(self.h, C.byref(geo), C.c_int32(len(out)), _ptrs(vf), _ptrs(nbr_vf), _ptrs([g for gr in grad for g in gr]),
+                                             _ptrs([g for gr in nbr_grad for g in gr]), _ptr(patch_flux), _ptrs(out)))
 
     def sngrad_correction_flux(self, corr_vecs, weights, grad, nbr_grad, gamma_magsf, out):
         """non-orthogonal correction flux on a COUPLED patch (gaussLaplacianSchemes.C:64-90 + surfaceInterpolationScheme.C:360-365)"""
@@ -1002,25 +1003,22 @@ class Patch:
     def sngrad_limited_correction_flux(self, limit_coeff, corr_vecs, weights, delta_coeffs, vf, nbr_vf, grad, nbr_grad, gamma_magsf, out, limiter_out=None):
         """the `limited` snGrad scheme's correction flux on a COUPLED patch (limitedSnGrad.C:58-84): vf / nbr_vf 1 or 3 arrays (cell field, its
         patchNeighbourField), grad / nbr_grad 3 or 9 (grad[3*j + d] = d(vf_j)/dx_d), out one patch array per component"""
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
         _chk(lib().mi_patch_sngrad_limited_correction_flux(self.h, C.c_int32(len(vf)), C.c_double(limit_coeff), _ptr(corr_vecs[0]), _ptr(corr_vecs[1]),
-                                                           _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), pv(vf), pv(nbr_vf), pv(grad), pv(nbr_grad),
-                                                           _ptr(gamma_magsf), pv(out), _ptr(limiter_out)))
+                                                           _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), _ptrs(vf), _ptrs(nbr_vf), _ptrs(grad), _ptrs(nbr_grad),
+                                                           _ptr(gamma_magsf), _ptrs(out), _ptr(limiter_out)))
 
     def gauss_grad_correct(self, sf, magsf, sngrad, grad, out):
         """the boundary values of a Gauss gradient on a patch that is NOT coupled (gaussGrad.C:277-303; mi_patch_gauss_grad_correct): sf [x, y, z]
         and magsf patch arrays, sngrad 1 or 3 patch arrays (the field's snGrad on the patch: zeros for zeroGradient), grad 3 or 9 CELL arrays
         (grad[3*j + k] = d(vf_j)/dx_k), out 3 or 9 patch arrays"""
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_patch_gauss_grad_correct(self.h, C.c_int32(len(sngrad)), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(magsf), pv(sngrad), pv(grad), pv(out)))
+        _chk(lib().mi_patch_gauss_grad_correct(self.h, C.c_int32(len(sngrad)), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(magsf), _ptrs(sngrad), _ptrs(grad), _ptrs(out)))
 
     def dev_tgrad_flux(self, kind, sf, visc, grad, out, weights=None, nbr_visc=None, nbr_grad=None):
         """Sf_b & (visc*dev[2](T(grad))) on the patch's faces, three components (mi_patch_dev_tgrad_flux); kind "dev" | "dev2".  weights None -- a patch
         that is not coupled: visc and grad[9] are the patch's own boundary values (patch arrays).  weights given -- a coupled patch without
         rotation: visc and grad[9] are the CELL arrays, nbr_visc / nbr_grad[9] their patchNeighbourFields"""
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs]) if xs is not None else None
-        _chk(lib().mi_patch_dev_tgrad_flux(self.h, C.c_int32(_dev_kind(kind)), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(weights), _ptr(visc), pv(grad),
-                                           _ptr(nbr_visc), pv(nbr_grad), pv(out)))
+        _chk(lib().mi_patch_dev_tgrad_flux(self.h, C.c_int32(_dev_kind(kind)), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(weights), _ptr(visc), _ptrs(grad),
+                                           _ptr(nbr_visc), _ptrs(nbr_grad), _ptrs(out)))
 
     def close(self):
         if self.h:
@@ -1270,16 +1268,14 @@ class LsVectors:
     None; b_weights is read on coupled patches only).  The boundary must stay open as long as the vectors are used."""
 
     def __init__(self, addr: Addressing, boundary, centres, weights, mag_sf, b_weights=None, b_mag_sf=None, b_delta=None):
-        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
         self.addr, self.boundary = addr, boundary
         self.h = C.c_void_p()
-        _chk(lib().mi_ls_vectors_create(addr.h, boundary.h if boundary is not None else None, pv(centres), _ptr(weights), _ptr(mag_sf),
-                                        _ptr(b_weights), _ptr(b_mag_sf), pv(b_delta), C.byref(self.h)))
+        _chk(lib().mi_ls_vectors_create(addr.h, boundary.h if boundary is not None else None, _ptrs(centres), _ptr(weights), _ptr(mag_sf),
+                                        _ptr(b_weights), _ptr(b_mag_sf), _ptrs(b_delta), C.byref(self.h)))
 
     def fields(self, p_out, n_out, bp_out=None):
         """copies pVectors, nVectors (internal faces) and the boundary pVectors into three arrays each (mi_ls_vectors_fields)"""
-        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_ls_vectors_fields(self.h, pv(p_out), pv(n_out), pv(bp_out)))
+        _chk(lib().mi_ls_vectors_fields(self.h, _ptrs(p_out), _ptrs(n_out), _ptrs(bp_out)))
 
     def close(self):
         if self.h:
@@ -1296,17 +1292,15 @@ class Reconstruct:
     the inverse geometric tensor; the boundary must stay open as long as it is used.  After mesh motion: close and build again."""
 
     def __init__(self, addr: Addressing, boundary, sf, mag_sf, b_sf=None, b_mag_sf=None):
-        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
         self.addr, self.boundary = addr, boundary
         self.h = C.c_void_p()
-        _chk(lib().mi_reconstruct_create(addr.h, boundary.h if boundary is not None else None, pv(sf), _ptr(mag_sf), pv(b_sf), _ptr(b_mag_sf),
+        _chk(lib().mi_reconstruct_create(addr.h, boundary.h if boundary is not None else None, _ptrs(sf), _ptr(mag_sf), _ptrs(b_sf), _ptr(b_mag_sf),
                                          C.byref(self.h)))
 
     def fields(self, inv_out):
         """copies the inverse tensor into nine cell arrays xx xy xz yx yy yz zx zy zz (mi_reconstruct_fields) -> removeCmpts as (x, y, z) of 0 / 1"""
-        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
         removed = (C.c_int32 * 3)(0, 0, 0)
-        _chk(lib().mi_reconstruct_fields(self.h, pv(inv_out), removed))
+        _chk(lib().mi_reconstruct_fields(self.h, _ptrs(inv_out), removed))
         return tuple(int(x) for x in removed)
 
     def close(self):
@@ -1690,18 +1684,16 @@ class Assembly:
     def sngrad_limited_correction_flux(self, limit_coeff, corr_vecs, weights, delta_coeffs, vf, grad, gamma_magsf, out, limiter_out=None):
         """[gammaMagSf *] limiter*correction of the `limited` snGrad scheme on the internal faces in one face pass (limitedSnGrad.C:58-84): vf 1 or
         3 cell arrays, grad 3 or 9 (grad[3*j + d] = d(vf_j)/dx_d), out one face array per component, limiter_out one face array or None"""
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
         _chk(lib().mi_sngrad_limited_correction_flux(self.addr.h, C.c_int32(len(vf)), C.c_double(limit_coeff), _ptr(corr_vecs[0]), _ptr(corr_vecs[1]),
-                                                     _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), pv(vf), pv(grad), _ptr(gamma_magsf), pv(out),
+                                                     _ptr(corr_vecs[2]), _ptr(weights), _ptr(delta_coeffs), _ptrs(vf), _ptrs(grad), _ptr(gamma_magsf), _ptrs(out),
                                                      _ptr(limiter_out)))
 
     def div_dev_tgrad(self, kind, lam, sf, visc, grad, face_out, div_out, vol=None):
         """fvc::div(visc*dev(T(grad))) ("dev": divDevReff) | fvc::div(visc*dev2(T(grad))) ("dev2": divDevRhoReff) on the internal faces in one face
         pass and one row pass (mi_fvc_div_dev_tgrad): grad 9 cell arrays (grad[3*j + k] = d(U_j)/dx_k), face_out 3 face arrays (kept for the
         patch sums and flux()), div_out 3 cell arrays [/ vol]"""
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_fvc_div_dev_tgrad(self.addr.h, C.c_int32(_dev_kind(kind)), _ptr(lam), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(visc), pv(grad),
-                                        _ptr(vol), pv(face_out), pv(div_out)))
+        _chk(lib().mi_fvc_div_dev_tgrad(self.addr.h, C.c_int32(_dev_kind(kind)), _ptr(lam), _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(visc), _ptrs(grad),
+                                        _ptr(vol), _ptrs(face_out), _ptrs(div_out)))
 
     def linear_upwind_correction(self, face_flux, cf, c, grad, out, scale=1.0):
         """faceFlux*correction(vf) of linearUpwind (scale 1) / LUST (scale 0.25) on the internal faces, one face pass for len(out) <= 4 components
@@ -1714,25 +1706,22 @@ class Assembly:
         """a limited scheme's weights on the internal faces in one face pass (mi_limited_weights): lim a Limiter or a scheme name, phi 1 or 3
         cell arrays, grad 3 or 9 (grad[3*j + k] = d(phi_j)/dx_k), centres [x, y, z]"""
         lim = limiter(lim) if isinstance(lim, str) else lim
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_limited_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), pv(phi), pv(grad), pv(centres), _ptr(w_out),
+        _chk(lib().mi_limited_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), _ptrs(phi), _ptrs(grad), _ptrs(centres), _ptr(w_out),
                                       _ptr(limiter_out)))
 
     def filtered_weights(self, lim, cd_weights, face_flux, phi, grad, centres, w_out, limiter_out=None):
         """a filtered scheme's weights on the internal faces in one face pass (mi_filtered_weights): lim a FilteredLimiter or a scheme name
         ("filteredLinear2V 1 0"), the other arguments as limited_weights"""
         lim = filtered(lim) if isinstance(lim, str) else lim
-        pv = lambda xs: (C.c_void_p * len(xs))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_filtered_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), pv(phi), pv(grad), pv(centres), _ptr(w_out),
+        _chk(lib().mi_filtered_weights(self.addr.h, C.byref(lim), _ptr(cd_weights), _ptr(face_flux), _ptrs(phi), _ptrs(grad), _ptrs(centres), _ptr(w_out),
                                        _ptr(limiter_out)))
 
     def cubic_correction(self, geo, vf, grad, out, face_flux=None):
         """[faceFlux *] correction(vf) of cubic on the internal faces, one face pass for len(out) <= 4 components (mi_cubic_correction; cubic.H:111-184):
         geo a CubicGeometry, vf one cell array per component, grad one [gx, gy, gz] (Gauss linear) per component; face_flux None: the bare
         correction field of fvc::interpolate"""
-        pv = lambda xs: (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_cubic_correction(self.addr.h, C.byref(geo), C.c_int32(len(out)), pv(vf), pv([g for gr in grad for g in gr]), _ptr(face_flux),
-                                       pv(out)))
+        _chk(lib().mi_cubic_correction(self.addr.h, C.byref(geo), C.c_int32(len(out)), _ptrs(vf), _ptrs([g for gr in grad for g in gr]), _ptr(face_flux),
+                                       _ptrs(out)))
 
     def limited_grad(self, lim, vf, centres, cf, grad, boundary=None, bvalue=None, bcf=None, limiter_out=None):
         """limits a Gauss linear gradient in place (mi_limited_grad): lim a GradLimiter or a scheme ("cellLimited Gauss linear 1"), vf 1 or 3
@@ -1740,9 +1729,8 @@ class Assembly:
         boundary a GradBoundary (or None), bvalue one boundary-face array per component; limiter_out n_comp arrays (cellLimited), 1
         (faceLimited) or None"""
         lim = grad_limiter(lim) if isinstance(lim, str) else lim
-        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_limited_grad(self.addr.h, C.byref(lim), boundary.h if boundary is not None else None, C.c_int32(len(vf)), pv(vf),
-                                   pv(centres), pv(cf), pv(bvalue), pv(bcf), pv(grad), pv(limiter_out)))
+        _chk(lib().mi_limited_grad(self.addr.h, C.byref(lim), boundary.h if boundary is not None else None, C.c_int32(len(vf)), _ptrs(vf),
+                                   _ptrs(centres), _ptrs(cf), _ptrs(bvalue), _ptrs(bcf), _ptrs(grad), _ptrs(limiter_out)))
 
     def ls_grad(self, lsv, vf, grad_out, bvalue=None):
         """the leastSquares gradient's internal field in one row pass (mi_ls_grad): lsv an LsVectors of this addressing, vf 1 or 3 cell arrays,
@@ -1750,8 +1738,7 @@ class Assembly:
         patches, the boundary value elsewhere)"""
         if lsv.addr is not self.addr:
             raise MiError("ls_grad: the vectors were built for another addressing")
-        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_ls_grad(lsv.h, C.c_int32(len(vf)), pv(vf), pv(bvalue), pv(grad_out)))
+        _chk(lib().mi_ls_grad(lsv.h, C.c_int32(len(vf)), _ptrs(vf), _ptrs(bvalue), _ptrs(grad_out)))
 
     def surface_sum(self, ssf, out, mode="sum"):
         """fvc::surfaceSum over the internal faces, every term added on both sides (mi_surface_sum): mode "sum" | "mag" (the sum of |ssf|, as
@@ -1765,8 +1752,7 @@ class Assembly:
         (out[3*r + k] = component k of flux r's vector)"""
         if rc.addr is not self.addr:
             raise MiError("reconstruct: the handle was built for another addressing")
-        pv = lambda xs: None if xs is None else (C.c_void_p * max(len(xs), 1))(*[_ptr(x) for x in xs])
-        _chk(lib().mi_fvc_reconstruct(rc.h, C.c_int32(len(ssf)), pv(ssf), pv(b_ssf), pv(out)))
+        _chk(lib().mi_fvc_reconstruct(rc.h, C.c_int32(len(ssf)), _ptrs(ssf), _ptrs(b_ssf), _ptrs(out)))
 
     def _mules(self, mu):
         if mu.addr is not self.addr:
@@ -1823,8 +1809,7 @@ class Assembly:
     def interface_nhatf(self, delta_n, lam, sf, grad, nhatf_out, nhatfv_out=None):
         """the face unit interface normal flux on the internal faces in one face pass (mi_interface_nhatf): sf [x, y, z] face arrays, grad the
         cell gradient of alpha [gx, gy, gz], nhatfv_out three face arrays for the normal itself or None"""
-        pv = lambda xs: None if xs is None else (C.c_void_p * 3)(*[_ptr(x) for x in xs])
-        _chk(lib().mi_interface_nhatf(self.addr.h, C.c_double(delta_n), _ptr(lam), pv(sf), pv(grad), _ptr(nhatf_out), pv(nhatfv_out)))
+        _chk(lib().mi_interface_nhatf(self.addr.h, C.c_double(delta_n), _ptr(lam), _ptrs(sf, 3), _ptrs(grad, 3), _ptr(nhatf_out), _ptrs(nhatfv_out, 3)))
 
     def interface_curvature(self, interface, nhatf, vol, K_out, b_nhatf=None):
         """K = -fvc::div(nHatf) over an Interface handle of this addressing (mi_interface_curvature)"""
