@@ -937,7 +937,7 @@ int mi_near_interface(mi_ctx_t ctx, int64_t n, const double *alpha_dev, double *
  *   boundary arrays while the boundary has faces; patch_is_wall flagging a coupled patch; a coefficient that is not finite or not above zero;
  *   a lower bound that is not a number.
  *   mi_min_max during a PCG session: MI_ERR_STATE.  Zero cells, zero wall faces and zero wall patches: MI_OK.
- * Out of scope: kOmegaSST and every model that needs the wall-distance field (wallDist / meshWave); the low-Re and rough wall functions;
+ * Out of scope: the wall-distance field itself (wallDist / meshWave: kOmegaSST, below, takes y as the caller's cell array); the low-Re and rough wall functions;
  *   the nutU* wall functions; the weighted (weights) forms of the epsilon wall function; compressible kEpsilon (rho-weighted); LES models;
  *   a pisoFoam / simpleFoam application; moving meshes; nearWallDist (y is the caller's patch array). */
 typedef struct mi_ke_coeffs {
@@ -978,6 +978,96 @@ int mi_ke_k_terms(mi_ctx_t ctx, int64_t n, const double *eps_dev, const double *
 int mi_ke_nut(mi_ctx_t ctx, int64_t n, double Cmu, const double *k_dev, const double *eps_dev, double *nut_out_dev);
 int mi_ke_nut_wall(mi_ke_t ke, const mi_ke_coeffs *coeffs, const double *k_dev, const double *b_y_dev, const double *b_nuw_dev,
                    double *b_nutw_out_dev, double *b_log_out_dev_or_null);
+/* ---- the kOmegaSST turbulence model: blending, the omega wall function, sources and nut (turbulenceModels/incompressible/RAS/kOmegaSST/
+ *      kOmegaSST.C:47-111, :127-243, :284-296, :398-468; kOmegaSST.H:164-243; omegaWallFunctionFvPatchScalarField.C:209-239, :241-394,
+ *      :548-596; fvMatrix.C:2208-2216, :2759-2814; fvmSup.C:100-214) ----
+ * What incompressible::RASModels::kOmegaSST::correct() runs as about sixty field passes is six kernels of this block and two or three of the
+ * kEpsilon block (mi_ke_wall_values, mi_ke_nut_wall, the bound decisions), beside the gradients, the assembly, relaxation, setValues, solve
+ * and boundary evaluation of both transport equations (DESIGN 3.5p counts them).  The rules of the kEpsilon block hold: fp64 values, int32
+ * labels, every operator rounded on its own except the fma written below, correctly rounded division and square root,
+ * max(a, b) = (a > b) ? a : b, min(a, b) = (a < b) ? a : b (doubleFloat.H), pow4(s) = sqr(sqr(s)) (Scalar.H:189).  tanh is the device
+ * library's and NOT the reference's bits: F1 and F23 are outputs, and everything formed from them is exact given them.  y, the distance of
+ * every cell centre to the nearest wall (wallDist, :245, :409), is the caller's cell array; b_y of the wall faces (nearWallDist) the caller's
+ * patch array, as for kEpsilon.  Restated in tests/komegasst_support.py, not pinned by a compiled reference.
+ * mi_sst_coeffs_init (host only, no GPU): model_or_null = {alphaK1, alphaK2, alphaOmega1, alphaOmega2, gamma1, gamma2, beta1, beta2, betaStar,
+ *   a1, b1, c1}, NULL for the reference's defaults 0.85, 1.0, 0.5, 0.856, 5.0/9.0, 0.44, 0.075, 0.0828, 0.09, 0.31, 1.0, 10.0 (:127-243);
+ *   wall_or_null = {Cmu, kappa, E, beta1} of the omega wall function, NULL for 0.09, 0.41, 9.8, 0.075 (:406-409).  The products of
+ *   dimensionedScalars are formed once, in the reference's order: twoAlphaOmega2 = 2*alphaOmega2 (:420), fourAlphaOmega2 = 4*alphaOmega2 (:64),
+ *   invBetaStar = 1/betaStar (:61), twoInvBetaStar = 2/betaStar (:80), c1a1BetaStar = (c1/a1)*betaStar (:433), c1BetaStar = c1*betaStar (:456),
+ *   d<X> = X1 - X2 of blend (kOmegaSST.H:171); Cmu25 and yPlusLam as mi_ke_coeffs_init forms them.  An entry that takes a mi_sst_coeffs refuses
+ *   one whose members are not all finite and (the differences apart) above zero.
+ * mi_sst_production (:412-413): S2 = 2*magSqr(symm(gradU)), G = nut*S2 in one cell pass; magSqr(symm) is mi_ke_production's (one device
+ *   function), so G has the bits of mi_ke_production's (nut*2)*magSqr.  mag_out_dev_or_null receives mag(symm(gradU)) = sqrt(magSqr) for the
+ *   constructor's form of nut (:287-295).
+ * mi_sst_wall_cells (:416): omega.boundaryField().updateCoeffs() for ALL wall patches in ONE launch on a mi_ke_t, no atomics, as
+ *   mi_ke_wall_cells: per unique wall cell c, from 0.0, its wall faces in (patch, face) order (calculateTurbulenceFields :209-239):
+ *     omegaVis = (6.0*nuw)/(beta1*sqr(y));  omegaLog = sqrt(k[c])/((Cmu25*kappa)*y)                  (OmegaCalculateOmegaFunctor :270-279)
+ *     oc += w*sqrt(fma(omegaVis, omegaVis, omegaLog*omegaLog))      (the first square contracted into the sum: an ASSUMPTION)
+ *     Gc += ((((w*(nutw + nuw))*mgu)*Cmu25)*sqrt(k[c]))/(kappa*y)   (OmegaCalculateGFunctor :315-325; mgu as in mi_ke_wall_cells)
+ *   then g_inout[c] = Gc, omega_inout[c] = oc (:580-586) and b_omega_out[face] = oc (:227-237).  No transcendental: the reference's bits.
+ *   boundaryManipulate (:444) is mi_fvm_set_values with mi_ke_wall_cell_labels and mi_ke_wall_values.
+ * mi_sst_blend (:418-439, F1 :47-70, F23 :73-111, blend / DkEff / DomegaEff kOmegaSST.H:164-243): one cell pass.
+ *     CDkOmega = (twoAlphaOmega2*fma(gKz, gOz, fma(gKx, gOx, gKy*gOy)))/omega                        (the dot product of 3.5a)
+ *     arg1 = min(min(max((invBetaStar*sqrt(k))/(omega*y), (500*nu)/(sqr(y)*omega)), (fourAlphaOmega2*k)/(max(CDkOmega, 1e-10)*sqr(y))), 10)
+ *     F1 = tanh(pow4(arg1));  arg2 = min(max((twoInvBetaStar*sqrt(k))/(omega*y), (500*nu)/(sqr(y)*omega)), 100);  F2 = tanh(sqr(arg2))
+ *     f3 != 0: arg3 = min((150*nu)/(omega*sqr(y)), 10), F23 = F2*(1 - tanh(pow4(arg3))); otherwise F23 = F2
+ *     blend(X) = F1*dX + X2
+ *     su = blend(gamma)*min(S2, (c1a1BetaStar*omega)*max(a1*omega, (b1*F23)*sqrt(S2)));  sp = blend(beta)*omega
+ *     susp = ((F1 - 1)*CDkOmega)/omega;  DomegaEff = blend(alphaOmega)*nut + nu;  DkEff = blend(alphaK)*nut + nu
+ *   nu a cell array, or nu_value when nu_dev_or_null is NULL.  The optional outputs (for tests) are CDkOmega and arg1 -- the reference's
+ *   bits, no transcendental comes before them -- F23 and tanh(pow4(arg3)) (0 when f3 == 0).
+ * mi_sst_omega_sources (:432-439): the right-hand side su - fvm::Sp(sp, omega) - fvm::SuSp(susp, omega) is a matrix of its own in the
+ *   reference, built as (su - Sp) - SuSp -- operator-(su, A) negates A and subtracts V*su from its source (fvMatrix.C:2759-2814), operator-=
+ *   subtracts diagonals and sources (:1787-1795), SuSp is diag = V*max(susp, 0), source = 0 - (V*min(susp, 0))*omega (fvmSup.C:194-214) --
+ *   and operator== subtracts it from the left side (:2208-2216).  In place on what mi_fvm_assemble wrote for ddt + div - laplacian:
+ *     diag   = diag   - ((-(V*sp)) - V*max(susp, 0))
+ *     source = source - ((-(V*su)) - (0 - (V*min(susp, 0))*omega))
+ *   The two implicit parts meet each other BEFORE the left side's diagonal: not the bits of mi_fvm_sp followed by mi_fvm_susp.
+ * mi_sst_k_terms (:456-457): su = min(G, (c1BetaStar*k)*omega), sp = betaStar*omega with the NEW omega; they go into mi_fvm_assemble as
+ *   su_dev and sp_dev, which gives the bits of the reference's su - fvm::Sp for a single implicit part.
+ * mi_sst_nut (:466; constructor_form != 0: :287-295): nut = (a1*k)/max(a1*omega, (b1*F23)*sqrt(S2)) with F23 recomputed in the pass from k,
+ *   omega, y and nu; the constructor's form takes s_dev = mag(symm(gradU)) and forms ((b1*F23)*sqrt(2.0))*s.  On the boundary values of
+ *   non-wall patches the same entry on boundary arrays; wall patches are mi_ke_nut_wall.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): as in the kEpsilon block -- missing arrays, an output that aliases an input or
+ *   another output (mi_sst_omega_sources's diag and source are in-out), an array not aligned for a double, a handle of another addressing,
+ *   coefficients that are not finite or not above zero, a nu_value that is not.  Zero cells and zero wall faces: MI_OK.
+ * Out of scope: wallDist / meshWave; the weighted (weights) omega wall function; the low-Re, rough and nutU* wall functions; kOmega,
+ *   kOmegaSSTSAS; compressible kOmegaSST; coupled wall patches; moving meshes; a simpleFoam / pisoFoam application. */
+typedef struct mi_sst_coeffs {
+    double alphaK1, alphaK2, alphaOmega1, alphaOmega2, gamma1, gamma2, beta1, beta2, betaStar, a1, b1, c1;
+    double Cmu, kappa, E, wallBeta1;          /* the omega wall function's */
+    double twoAlphaOmega2, fourAlphaOmega2, invBetaStar, twoInvBetaStar, c1a1BetaStar, c1BetaStar;   /* derived: mi_sst_coeffs_init */
+    double dAlphaK, dAlphaOmega, dBeta, dGamma;
+    double Cmu25, yPlusLam;
+} mi_sst_coeffs;
+typedef struct mi_sst_wall {
+    const double *k_dev;
+    const double *u_dev[3];
+    const double *b_uw_dev[3];                /* the boundary face values of U */
+    const double *b_delta_coeffs_dev, *b_y_dev, *b_nuw_dev, *b_nutw_dev;
+    double *g_inout_dev, *omega_inout_dev;    /* cell fields: the wall cells are overwritten */
+    double *b_omega_out_dev;
+} mi_sst_wall;
+typedef struct mi_sst_blend_arrays {
+    const double *grad_k_dev[3], *grad_omega_dev[3];
+    const double *k_dev, *omega_dev, *y_dev, *nut_dev, *s2_dev;
+    const double *nu_dev_or_null;
+    double nu_value;
+    double *f1_out_dev, *su_out_dev, *sp_out_dev, *susp_out_dev, *domega_out_dev, *dk_out_dev;
+    double *cdkomega_out_dev_or_null, *arg1_out_dev_or_null, *f23_out_dev_or_null, *tanh3_out_dev_or_null;
+} mi_sst_blend_arrays;
+int mi_sst_coeffs_init(const double *model_or_null, const double *wall_or_null, mi_sst_coeffs *out);
+int mi_sst_production(mi_ctx_t ctx, int64_t n, const double *nut_dev, const double *const *grad_dev, double *s2_out_dev, double *g_out_dev,
+                      double *mag_out_dev_or_null);
+int mi_sst_wall_cells(mi_ke_t ke, const mi_sst_coeffs *coeffs, const mi_sst_wall *arrays);
+int mi_sst_blend(mi_ctx_t ctx, int64_t n, const mi_sst_coeffs *coeffs, int f3, const mi_sst_blend_arrays *arrays);
+int mi_sst_omega_sources(mi_ctx_t ctx, int64_t n, const double *vol_dev, const double *su_dev, const double *sp_dev, const double *susp_dev,
+                         const double *omega_dev, double *diag_inout_dev, double *source_inout_dev);
+int mi_sst_k_terms(mi_ctx_t ctx, int64_t n, const mi_sst_coeffs *coeffs, const double *g_dev, const double *k_dev, const double *omega_dev,
+                   double *su_out_dev, double *sp_out_dev);
+int mi_sst_nut(mi_ctx_t ctx, int64_t n, const mi_sst_coeffs *coeffs, int f3, int constructor_form, const double *k_dev, const double *omega_dev,
+               const double *y_dev, const double *s_dev, const double *nu_dev_or_null, double nu_value, double *nut_out_dev,
+               double *f23_out_dev_or_null);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

@@ -91,6 +91,7 @@ SYMBOLS = [
     "mi_ke_coeffs_init", "mi_min_max", "mi_vec_max_value", "mi_average_create", "mi_average_destroy", "mi_fvc_average", "mi_bound",
     "mi_ke_production", "mi_ke_create", "mi_ke_destroy", "mi_ke_wall_cells", "mi_ke_wall_cell_labels", "mi_ke_wall_values",
     "mi_ke_epsilon_terms", "mi_ke_k_terms", "mi_ke_nut", "mi_ke_nut_wall",
+    "mi_sst_coeffs_init", "mi_sst_production", "mi_sst_wall_cells", "mi_sst_blend", "mi_sst_omega_sources", "mi_sst_k_terms", "mi_sst_nut",
 ]
 
 
@@ -1543,10 +1544,63 @@ class KEpsilon:
         """nutkWallFunction::calcNut on every wall face in one launch (mi_ke_nut_wall)"""
         _chk(lib().mi_ke_nut_wall(self.h, C.byref(coeffs) if coeffs is not None else None, _ptr(k), _ptr(b_y), _ptr(b_nuw), _ptr(b_nutw_out), _ptr(b_log_out)))
 
+    def sst_wall_cells(self, coeffs: "SstCoeffs", k, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw, g_inout, omega_inout, b_omega_out):
+        """omega.boundaryField().updateCoeffs() (omegaWallFunction) for every wall patch in one launch (mi_sst_wall_cells): the arrays of
+        wall_cells"""
+        x = SstWall()
+        x.k_dev = _ptr(k).value
+        for d in range(3):
+            x.u_dev[d] = _ptr(None if u is None else u[d]).value
+            x.b_uw_dev[d] = _ptr(None if b_uw is None else b_uw[d]).value
+        x.b_delta_coeffs_dev, x.b_y_dev, x.b_nuw_dev, x.b_nutw_dev = (_ptr(t).value for t in (b_delta_coeffs, b_y, b_nuw, b_nutw))
+        x.g_inout_dev, x.omega_inout_dev, x.b_omega_out_dev = (_ptr(t).value for t in (g_inout, omega_inout, b_omega_out))
+        _chk(lib().mi_sst_wall_cells(self.h, C.byref(coeffs) if coeffs is not None else None, C.byref(x)))
+
     def close(self):
         if self.h:
             lib().mi_ke_destroy(self.h)
             self.h = C.c_void_p()
+
+
+SST_MODEL = ("alphaK1", "alphaK2", "alphaOmega1", "alphaOmega2", "gamma1", "gamma2", "beta1", "beta2", "betaStar", "a1", "b1", "c1")
+SST_WALL = ("Cmu", "kappa", "E", "wallBeta1")
+
+
+class SstCoeffs(C.Structure):
+    """mi_sst_coeffs (include/mi_ldu.h)"""
+    _fields_ = [(name, C.c_double) for name in SST_MODEL + SST_WALL + ("twoAlphaOmega2", "fourAlphaOmega2", "invBetaStar", "twoInvBetaStar",
+                                                                       "c1a1BetaStar", "c1BetaStar", "dAlphaK", "dAlphaOmega", "dBeta", "dGamma",
+                                                                       "Cmu25", "yPlusLam")]
+
+
+def sst_coeffs(**given) -> SstCoeffs:
+    """mi_sst_coeffs_init: kOmegaSST's coefficients (SST_MODEL) and its wall function's (SST_WALL) by name, the reference's defaults for the
+    rest, with the host-formed products derived (host only, no GPU)"""
+    unknown = set(given) - set(SST_MODEL) - set(SST_WALL)
+    if unknown:
+        raise TypeError("sst_coeffs: unknown coefficient " + ", ".join(sorted(unknown)))
+    base = SstCoeffs()
+    _chk(lib().mi_sst_coeffs_init(None, None, C.byref(base)))
+    model = (C.c_double * 12)(*[float(given.get(name, getattr(base, name))) for name in SST_MODEL])
+    wall = (C.c_double * 4)(*[float(given.get(name, getattr(base, name))) for name in SST_WALL])
+    out = SstCoeffs()
+    _chk(lib().mi_sst_coeffs_init(model, wall, C.byref(out)))
+    return out
+
+
+class SstWall(C.Structure):
+    """mi_sst_wall (include/mi_ldu.h)"""
+    _fields_ = [("k_dev", C.c_void_p), ("u_dev", C.c_void_p * 3), ("b_uw_dev", C.c_void_p * 3), ("b_delta_coeffs_dev", C.c_void_p),
+                ("b_y_dev", C.c_void_p), ("b_nuw_dev", C.c_void_p), ("b_nutw_dev", C.c_void_p), ("g_inout_dev", C.c_void_p),
+                ("omega_inout_dev", C.c_void_p), ("b_omega_out_dev", C.c_void_p)]
+
+
+class SstBlendArrays(C.Structure):
+    """mi_sst_blend_arrays (include/mi_ldu.h)"""
+    _fields_ = [("grad_k_dev", C.c_void_p * 3), ("grad_omega_dev", C.c_void_p * 3)] + \
+               [(name, C.c_void_p) for name in ("k_dev", "omega_dev", "y_dev", "nut_dev", "s2_dev", "nu_dev_or_null")] + [("nu_value", C.c_double)] + \
+               [(name, C.c_void_p) for name in ("f1_out_dev", "su_out_dev", "sp_out_dev", "susp_out_dev", "domega_out_dev", "dk_out_dev",
+                                                "cdkomega_out_dev_or_null", "arg1_out_dev_or_null", "f23_out_dev_or_null", "tanh3_out_dev_or_null")]
 
 
 class Assembly:
@@ -1875,6 +1929,55 @@ class Assembly:
     def ke_nut_wall(self, ke, coeffs, k, b_y, b_nuw, b_nutw_out, b_log_out=None):
         """nutkWallFunction on every wall face over a KEpsilon handle of this addressing (mi_ke_nut_wall)"""
         ke.nut_wall(coeffs, k, b_y, b_nuw, b_nutw_out, b_log_out)
+
+    def sst_production(self, nut, grad, s2_out, g_out, mag_out=None):
+        """S2 = 2*magSqr(symm(gradU)), G = nut*S2 and optionally mag(symm(gradU)) in one cell pass (mi_sst_production): grad as ke_production's"""
+        pv = None if grad is None else (C.c_void_p * 9)(*[_ptr(x) for x in grad])
+        n = (nut if nut is not None else g_out).numel()
+        _chk(lib().mi_sst_production(self.addr.ctx.h, C.c_int64(n), _ptr(nut), pv, _ptr(s2_out), _ptr(g_out), _ptr(mag_out)))
+
+    def sst_wall_cells(self, ke, coeffs, k, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw, g_inout, omega_inout, b_omega_out):
+        """the omega wall function on every wall patch over a KEpsilon handle of this addressing (mi_sst_wall_cells)"""
+        ke.sst_wall_cells(coeffs, k, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw, g_inout, omega_inout, b_omega_out)
+
+    def sst_blend(self, coeffs, f3, grad_k, grad_omega, k, omega, y, nut, s2, nu, f1_out, su_out, sp_out, susp_out, domega_out, dk_out,
+                  cdkomega_out=None, arg1_out=None, f23_out=None, tanh3_out=None):
+        """CDkOmega, F1, F23, the blended coefficients, the omega equation's su / sp / susp, DomegaEff and DkEff in one cell pass
+        (mi_sst_blend); nu a cell array or a number; f3 the model's F3 switch"""
+        x = SstBlendArrays()
+        for d in range(3):
+            x.grad_k_dev[d] = _ptr(None if grad_k is None else grad_k[d]).value
+            x.grad_omega_dev[d] = _ptr(None if grad_omega is None else grad_omega[d]).value
+        nu_dev, x.nu_value = (None, float(nu)) if isinstance(nu, (int, float)) else (nu, 0.0)
+        x.k_dev, x.omega_dev, x.y_dev, x.nut_dev, x.s2_dev, x.nu_dev_or_null = (_ptr(t).value for t in (k, omega, y, nut, s2, nu_dev))
+        x.f1_out_dev, x.su_out_dev, x.sp_out_dev, x.susp_out_dev, x.domega_out_dev, x.dk_out_dev = \
+            (_ptr(t).value for t in (f1_out, su_out, sp_out, susp_out, domega_out, dk_out))
+        x.cdkomega_out_dev_or_null, x.arg1_out_dev_or_null, x.f23_out_dev_or_null, x.tanh3_out_dev_or_null = \
+            (_ptr(t).value for t in (cdkomega_out, arg1_out, f23_out, tanh3_out))
+        n = (k if k is not None else f1_out).numel()
+        _chk(lib().mi_sst_blend(self.addr.ctx.h, C.c_int64(n), C.byref(coeffs) if coeffs is not None else None, C.c_int(int(bool(f3))), C.byref(x)))
+
+    def sst_omega_sources(self, vol, su, sp, susp, omega, diag_inout, source_inout):
+        """the omega equation's == su - fvm::Sp(sp, omega) - fvm::SuSp(susp, omega) in the reference's grouping, in place on the assembled
+        diagonal and source (mi_sst_omega_sources)"""
+        n = (omega if omega is not None else diag_inout).numel()
+        _chk(lib().mi_sst_omega_sources(self.addr.ctx.h, C.c_int64(n), _ptr(vol), _ptr(su), _ptr(sp), _ptr(susp), _ptr(omega), _ptr(diag_inout),
+                                        _ptr(source_inout)))
+
+    def sst_k_terms(self, coeffs, g, k, omega, su_out, sp_out):
+        """su = min(G, c1*betaStar*k*omega), sp = betaStar*omega in one cell pass (mi_sst_k_terms)"""
+        n = (k if k is not None else su_out).numel()
+        _chk(lib().mi_sst_k_terms(self.addr.ctx.h, C.c_int64(n), C.byref(coeffs) if coeffs is not None else None, _ptr(g), _ptr(k), _ptr(omega),
+                                  _ptr(su_out), _ptr(sp_out)))
+
+    def sst_nut(self, coeffs, f3, k, omega, y, s, nu, nut_out, f23_out=None, constructor_form=False):
+        """nut = a1*k/max(a1*omega, b1*F23*sqrt(S2)) with F23 recomputed in the pass (mi_sst_nut); constructor_form: s is mag(symm(gradU)) and
+        the strain term b1*F23*sqrt(2.0)*s; nu a cell array or a number"""
+        nu_dev, nu_value = (None, float(nu)) if isinstance(nu, (int, float)) else (nu, 0.0)
+        n = (k if k is not None else nut_out).numel()
+        _chk(lib().mi_sst_nut(self.addr.ctx.h, C.c_int64(n), C.byref(coeffs) if coeffs is not None else None, C.c_int(int(bool(f3))),
+                              C.c_int(int(bool(constructor_form))), _ptr(k), _ptr(omega), _ptr(y), _ptr(s), _ptr(nu_dev), C.c_double(nu_value),
+                              _ptr(nut_out), _ptr(f23_out)))
 
     def vec_min(self, x, y, out):
         """out = min(x, y) element by element, out may alias either (mi_vec_min): minOp over the two sides of a cyclic pair"""

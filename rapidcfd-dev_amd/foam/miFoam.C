@@ -1417,6 +1417,253 @@ void kEpsilon::correct(const flowData& flow, scalar rDeltaT, const dictionary& e
     bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);
     correctNut();                                           // :278-279
 }
+
+// ---- incompressible::RASModels::kOmegaSST -----------------------------------------------------------------------------------------------
+kOmegaSST::kOmegaSST(const meshData& mesh, const flowData& flow, scalar nu, const scalargpuField& k, const scalargpuField& bk, const scalargpuField& omega,
+                     const scalargpuField& bomega, const dictionary& coeffDict, scalar kMin, scalar omegaMin)
+    : mesh_(mesh), nu_(nu), kMin_(kMin), omegaMin_(omegaMin), F3_(false), h_(nullptr), nb_(bk.size()), k_(k), omega_(omega), nut_(k.size()), bk_(bk),
+      bomega_(bomega), bnut_(bk.size()), bnu_(std::vector<scalar>((std::size_t)bk.size(), nu)), F1_(k.size()), F23_(k.size()),
+      ones_(std::vector<scalar>((std::size_t)k.size(), 1.0)), bOnes_(std::vector<scalar>((std::size_t)bk.size(), 1.0))
+{
+    const char* who = "kOmegaSST::New";
+    if (!mesh.addr || !mesh.boundary || !mesh.average || !mesh.y || !mesh.bY || !mesh.Sf || !mesh.bSf)
+        FatalErrorIn(who, "the addressing, the boundary, the averageData, the wall distance and the face area vectors are needed");
+    if (mesh.patchTypes.size() != mesh.patchFaceCells.size()) FatalErrorIn(who, "one type per patch");
+    // kOmegaSST.C:127-243 and the omega wall function's Cmu, kappa, E, beta1 (:406-409)
+    const char* names[12] = {"alphaK1", "alphaK2", "alphaOmega1", "alphaOmega2", "gamma1", "gamma2", "beta1", "beta2", "betaStar", "a1", "b1", "c1"};
+    mi_sst_coeffs d{};
+    miCheck(mi_sst_coeffs_init(nullptr, nullptr, &d), who);
+    scalar model[12] = {d.alphaK1, d.alphaK2, d.alphaOmega1, d.alphaOmega2, d.gamma1, d.gamma2, d.beta1, d.beta2, d.betaStar, d.a1, d.b1, d.c1};
+    for (int i = 0; i < 12; ++i) coeffDict.readIfPresent(names[i], model[i]);
+    scalar wall[4] = {d.Cmu, d.kappa, d.E, d.wallBeta1};
+    coeffDict.readIfPresent("Cmu", wall[0]); coeffDict.readIfPresent("kappa", wall[1]); coeffDict.readIfPresent("E", wall[2]);
+    coeffDict.readIfPresent("wallBeta1", wall[3]);
+    scalar f3 = 0;
+    coeffDict.readIfPresent("F3", f3);
+    F3_ = f3 != 0;
+    miCheck(mi_sst_coeffs_init(model, wall, &coeffs_), who);
+    miCheck(mi_ke_coeffs_init(coeffs_.Cmu, 1.44, 1.92, 1.3, coeffs_.kappa, coeffs_.E, &wallCoeffs_), who);   // nutkWallFunction reads Cmu25, kappa, E, yPlusLam
+    std::vector<int32_t> isWall;
+    label off = 0;
+    for (std::size_t p = 0; p < mesh.patchFaceCells.size(); ++p) {
+        isWall.push_back(mesh.patchTypes[p] == wallFunction ? 1 : 0);
+        start_.push_back(off);
+        patches_.emplace_back(new fvPatchCells(mesh.addr->size(), mesh.patchFaceCells[p]));
+        off += (label)mesh.patchFaceCells[p].size();
+    }
+    start_.push_back(off);
+    if (off != nb_ || bomega.size() != nb_ || mesh.bY->size() != nb_) FatalErrorIn(who, "the boundary fields do not have one value per boundary face");
+    miCheck(mi_ke_create(mesh.addr->handle(), mesh.boundary->handle(), isWall.data(), &h_), who);
+    int32_t nWall = 0; const int32_t* labels = nullptr;
+    miCheck(mi_ke_wall_cell_labels(h_, &nWall, &labels), who);
+    labelgpuList cells(nWall);
+    if (nWall) miCopyD2D(cells.data(), labels, sizeof(label) * (std::size_t)nWall);
+    wallCells_.swap(cells);
+    bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);             // :284
+    bound(omega_, &bomega_, *mesh_.average, *mesh_.weights, omegaMin_); // :285
+    // nut_ = a1_*k_/max(a1_*omega_, b1_*F23()*sqrt(2.0)*mag(symm(fvc::grad(U_)))); nut_.correctBoundaryConditions()  (:287-296)
+    scalargpuField S2(k_.size()), G(k_.size()), mag(k_.size()), bS2(nb_), bG(nb_), bmag(nb_);
+    production(S2, G, &mag, ones_, flow.gradU);
+    production(bS2, bG, &bmag, bOnes_, flow.bGradU);
+    correctNut(mag, bmag, true);
+}
+kOmegaSST::~kOmegaSST() { if (h_) mi_ke_destroy(h_); }
+void kOmegaSST::production(scalargpuField& S2, scalargpuField& G, scalargpuField* mag, const scalargpuField& nut, const vectorgpuField* const* gradU) const
+{
+    const double* g[9];
+    for (int j = 0; j < 3; ++j) for (int d = 0; d < 3; ++d) g[3 * j + d] = gradU[j]->component(d).data();
+    miCheck(mi_sst_production(miEngine::New().ctx, nut.size(), nut.data(), g, S2.data(), G.data(), mag ? mag->data() : nullptr), "kOmegaSST: S2, G");
+}
+void kOmegaSST::correctNut(const scalargpuField& s, const scalargpuField& bs, bool constructorForm)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    miCheck(mi_sst_nut(ctx, k_.size(), &coeffs_, F3_, constructorForm, k_.data(), omega_.data(), mesh_.y->data(), s.data(), nullptr, nu_, nut_.data(),
+                       nullptr), "kOmegaSST: nut");
+    miCheck(mi_sst_nut(ctx, nb_, &coeffs_, F3_, constructorForm, bk_.data(), bomega_.data(), mesh_.bY->data(), bs.data(), nullptr, nu_, bnut_.data(),
+                       nullptr), "kOmegaSST: nut");
+    miCheck(mi_ke_nut_wall(h_, &wallCoeffs_, k_.data(), mesh_.bY->data(), bnu_.data(), bnut_.data(), nullptr), "nutkWallFunction::calcNut");
+}
+void kOmegaSST::evaluateBoundary(const scalargpuField& vf, scalargpuField& bvf) const
+{
+    for (std::size_t p = 0; p < patches_.size(); ++p)
+        if (mesh_.patchTypes[p] != fixedValue && patches_[p]->size() > 0)
+            miCheck(mi_patch_internal_field(patches_[p]->handle(), vf.data(), bvf.data() + start_[p]), "fvPatchField::evaluate");
+}
+void kOmegaSST::grad(vectorgpuField& g, vectorgpuField& bg, const scalargpuField& vf, const scalargpuField& bvf) const
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const lduAddressing& a = *mesh_.addr;
+    const label n = a.size();
+    scalargpuField ssf(mesh_.magSf->size());
+    miCheck(mi_face_interpolate(a.handle(), mesh_.weights->data(), vf.data(), ssf.data()), "linear::interpolate");
+    miCheck(mi_gauss_grad(a.handle(), mesh_.Sf->component(0).data(), mesh_.Sf->component(1).data(), mesh_.Sf->component(2).data(), ssf.data(), nullptr,
+                          g.component(0).data(), g.component(1).data(), g.component(2).data()), "gaussGrad::gradf");
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        if (patches_[p]->size() == 0) continue;
+        for (direction d = 0; d < 3; ++d)
+            miCheck(mi_patch_add_product(patches_[p]->handle(), mesh_.bSf->component(d).data() + start_[p], bvf.data() + start_[p], g.component(d).data(), 0),
+                    "gaussGrad::gradf (patch)");
+    }
+    for (direction d = 0; d < 3; ++d) miCheck(mi_vec_div(ctx, n, g.component(d).data(), mesh_.V->data(), g.component(d).data()), "gaussGrad /= V");
+    // gaussGrad::correctBoundaryConditions: snGrad = deltaCoeffs*(value - cell value) on every patch (zero where the value is the cell's)
+    scalargpuField pif(nb_), diff(nb_), sn(std::vector<scalar>((std::size_t)nb_, 0.0));
+    for (std::size_t p = 0; p < patches_.size(); ++p)
+        if (patches_[p]->size() > 0) miCheck(mi_patch_internal_field(patches_[p]->handle(), vf.data(), pif.data() + start_[p]), "patchInternalField");
+    fieldAxpby(diff, 1.0, bvf, -1.0, pif);
+    fieldSubMul(sn, *mesh_.bDeltaCoeffs, diff);            // 0 - dc*diff, then the exact negation
+    fieldAxpby(sn, -1.0, sn, 0.0, sn);
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        if (patches_[p]->size() == 0) continue;
+        const label s = start_[p];
+        const double* snp[1] = {sn.data() + s};
+        const double* gc[3] = {g.component(0).data(), g.component(1).data(), g.component(2).data()};
+        double* out[3] = {bg.component(0).data() + s, bg.component(1).data() + s, bg.component(2).data() + s};
+        miCheck(mi_patch_gauss_grad_correct(patches_[p]->handle(), 1, mesh_.bSf->component(0).data() + s, mesh_.bSf->component(1).data() + s,
+                                            mesh_.bSf->component(2).data() + s, mesh_.bMagSf->data() + s, snp, gc, out), "gaussGrad::correctBoundaryConditions");
+    }
+}
+void kOmegaSST::F23(scalargpuField& out) const
+{
+    scalargpuField nut(k_.size());
+    miCheck(mi_sst_nut(miEngine::New().ctx, k_.size(), &coeffs_, F3_, 0, k_.data(), omega_.data(), mesh_.y->data(), ones_.data(), nullptr, nu_, nut.data(),
+                       out.data()), "kOmegaSST::F23");
+}
+void kOmegaSST::F2(scalargpuField& out) const
+{
+    scalargpuField nut(k_.size());
+    miCheck(mi_sst_nut(miEngine::New().ctx, k_.size(), &coeffs_, 0, 0, k_.data(), omega_.data(), mesh_.y->data(), ones_.data(), nullptr, nu_, nut.data(),
+                       out.data()), "kOmegaSST::F2");
+}
+void kOmegaSST::F3(scalargpuField& out) const
+{
+    // 1 - tanh(pow4(arg3)): the optional output of the blending pass, which reads no gradient for it
+    const label n = k_.size();
+    scalargpuField zero(std::vector<scalar>((std::size_t)n, 0.0)), t[6] = {scalargpuField(n), scalargpuField(n), scalargpuField(n), scalargpuField(n),
+                                                                            scalargpuField(n), scalargpuField(n)}, t3(n);
+    mi_sst_blend_arrays x{};
+    for (int d = 0; d < 3; ++d) { x.grad_k_dev[d] = zero.data(); x.grad_omega_dev[d] = zero.data(); }
+    x.k_dev = k_.data(); x.omega_dev = omega_.data(); x.y_dev = mesh_.y->data(); x.nut_dev = nut_.data(); x.s2_dev = ones_.data(); x.nu_value = nu_;
+    x.f1_out_dev = t[0].data(); x.su_out_dev = t[1].data(); x.sp_out_dev = t[2].data(); x.susp_out_dev = t[3].data(); x.domega_out_dev = t[4].data();
+    x.dk_out_dev = t[5].data(); x.tanh3_out_dev_or_null = t3.data();
+    miCheck(mi_sst_blend(miEngine::New().ctx, n, &coeffs_, 1, &x), "kOmegaSST::F3");
+    fieldAxpby(out, 1.0, ones_, -1.0, t3);
+}
+void kOmegaSST::blend(scalargpuField& out, const scalargpuField& F1, scalar psi1, scalar psi2) const
+{
+#pragma clang fp contract(off)
+    const scalar d = psi1 - psi2;
+    fieldAxpby(out, d, F1, psi2, F1.size() == nb_ && nb_ != k_.size() ? bOnes_ : ones_);   // F1*(psi1 - psi2) + psi2: psi2*1 is exact
+}
+void kOmegaSST::DkEff(scalargpuField& out, const scalargpuField& F1) const
+{
+    const bool onBoundary = F1.size() == nb_ && nb_ != k_.size();
+    scalargpuField a(F1.size()), m(std::vector<scalar>((std::size_t)F1.size(), 0.0));
+    alphaK(a, F1);
+    fieldSubMul(m, a, onBoundary ? bnut_ : nut_);          // 0 - alphaK*nut
+    fieldAxpby(out, -1.0, m, nu_, onBoundary ? bOnes_ : ones_);
+}
+void kOmegaSST::DomegaEff(scalargpuField& out, const scalargpuField& F1) const
+{
+    const bool onBoundary = F1.size() == nb_ && nb_ != k_.size();
+    scalargpuField a(F1.size()), m(std::vector<scalar>((std::size_t)F1.size(), 0.0));
+    alphaOmega(a, F1);
+    fieldSubMul(m, a, onBoundary ? bnut_ : nut_);
+    fieldAxpby(out, -1.0, m, nu_, onBoundary ? bOnes_ : ones_);
+}
+solverPerformance kOmegaSST::solveEquation(const word& name, scalargpuField& psi, const scalargpuField& bpsi, const scalargpuField& psiOld,
+                                           const scalargpuField& su, const scalargpuField& sp, const scalargpuField* susp, const scalargpuField& gamma,
+                                           const scalargpuField& bGamma, const flowData& flow, scalar rDeltaT, scalar alpha, const dictionary& solverControls)
+{
+#pragma clang fp contract(off)
+    const lduAddressing& a = *mesh_.addr;
+    const label nf = mesh_.magSf->size();
+    scalargpuField f(nf), gammaMagSf(std::vector<scalar>((std::size_t)nf, 0.0));
+    fvc::interpolate(f, a, *mesh_.weights, gamma);
+    fieldSubMul(gammaMagSf, f, *mesh_.magSf);               // 0 - f*magSf, then the exact negation
+    fieldAxpby(gammaMagSf, -1.0, gammaMagSf, 0.0, gammaMagSf);
+    std::vector<bool> coupled(mesh_.patchFaceCells.size(), false);
+    fvScalarMatrix M(name, a, mesh_.patchFaceCells, coupled);
+    mi_fvm_terms t{};
+    const double* po[1] = {psiOld.data()}; const double* sd[1] = {su.data()}; const double sg[1] = {-1.0}; double* so[1] = {M.source().data()};
+    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = 1.0; t.vol_dev = mesh_.V->data();
+    t.div_flux_dev = flow.phi->data(); t.div_weights_dev = (flow.divWeights ? flow.divWeights : mesh_.weights)->data();
+    t.lap_delta_coeffs_dev = mesh_.deltaCoeffs->data(); t.lap_gamma_magsf_dev = gammaMagSf.data();
+    t.n_rhs = 1; t.psi_old_dev = po;
+    if (!susp) {                                            // == su - fvm::Sp(sp, psi): one implicit part, inside the assembly
+        t.sp_dev = sp.data(); t.sp_sign = 1.0;
+        t.n_su = 1; t.su_dev = sd; t.su_sign = sg;
+    }
+    miCheck(mi_fvm_assemble(a.handle(), &t, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "kOmegaSST: fvm::assemble");
+    if (susp)                                               // == su - fvm::Sp(sp, psi) - fvm::SuSp(susp, psi): the reference's grouping
+        miCheck(mi_sst_omega_sources(miEngine::New().ctx, psi.size(), mesh_.V->data(), su.data(), sp.data(), susp->data(), psi.data(), M.diag().data(),
+                                     M.source().data()), "kOmegaSST: omegaEqn sources");
+    const std::vector<scalar> bg = bGamma.asHost(), bms = mesh_.bMagSf->asHost(), bdc = mesh_.bDeltaCoeffs->asHost(), bphi = flow.bPhi->asHost(),
+                              bval = bpsi.asHost();
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        const label m = start_[p + 1] - start_[p];
+        std::vector<scalar> ic((std::size_t)m), bc((std::size_t)m);
+        for (label i = 0; i < m; ++i) {
+            const std::size_t j = (std::size_t)(start_[p] + i);
+            if (mesh_.patchTypes[p] == fixedValue) {
+                const scalar gm = bg[j] * bms[j], diff = gm * bdc[j];
+                const scalar x = diff * bval[j], y = bphi[j] * bval[j];
+                ic[(std::size_t)i] = diff; bc[(std::size_t)i] = x - y;
+            } else { ic[(std::size_t)i] = bphi[j]; bc[(std::size_t)i] = 0.0; }
+        }
+        M.internalCoeffs()[p] = ic; M.boundaryCoeffs()[p] = bc;
+    }
+    M.relax(alpha, psi);
+    if (susp && wallCells_.size() > 0) {                    // boundaryManipulate: omegaWallFunction::manipulateMatrix
+        scalargpuField values(wallCells_.size());
+        miCheck(mi_ke_wall_values(h_, psi.data(), values.data()), "omegaWallFunction::manipulateMatrix");
+        M.setValues(wallCells_, values, psi);
+    }
+    return M.solve(psi, solverControls);
+}
+void kOmegaSST::correct(const flowData& flow, scalar rDeltaT, const dictionary& omegaSolver, const dictionary& kSolver, scalar omegaRelax, scalar kRelax)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const label n = k_.size();
+    // const volScalarField S2(2*magSqr(symm(fvc::grad(U_)))); volScalarField G(GName(), nut_*S2)  (:412-413)
+    scalargpuField S2(n), G(n), bS2(nb_), bG(nb_);
+    production(S2, G, nullptr, nut_, flow.gradU);
+    production(bS2, bG, nullptr, bnut_, flow.bGradU);
+    // omega_.boundaryField().updateCoeffs()  (:416)
+    const scalargpuField omegaOld(omega_), kOld(k_);
+    mi_sst_wall w{};
+    w.k_dev = k_.data(); w.b_delta_coeffs_dev = mesh_.bDeltaCoeffs->data(); w.b_y_dev = mesh_.bY->data(); w.b_nuw_dev = bnu_.data();
+    w.b_nutw_dev = bnut_.data(); w.g_inout_dev = G.data(); w.omega_inout_dev = omega_.data(); w.b_omega_out_dev = bomega_.data();
+    for (int d = 0; d < 3; ++d) { w.u_dev[d] = flow.U->component(d).data(); w.b_uw_dev[d] = flow.bU->component(d).data(); }
+    miCheck(mi_sst_wall_cells(h_, &coeffs_, &w), "omegaWallFunction::updateCoeffs");
+    // CDkOmega, F1 and everything blended with it (:418-439), on the cells and on the boundary faces
+    vectorgpuField gradK(n), gradOmega(n), bGradK(nb_), bGradOmega(nb_);
+    grad(gradK, bGradK, k_, bk_);
+    grad(gradOmega, bGradOmega, omega_, bomega_);
+    scalargpuField su(n), sp(n), susp(n), DomegaEff(n), DkEff(n);
+    scalargpuField bF1(nb_), bF23(nb_), bsu(nb_), bsp(nb_), bsusp(nb_), bDomegaEff(nb_), bDkEff(nb_);
+    auto blendPass = [&](label m, const vectorgpuField& gk, const vectorgpuField& go, const scalargpuField& k, const scalargpuField& omega, const scalargpuField& y,
+                         const scalargpuField& nut, const scalargpuField& s2, scalargpuField& F1, scalargpuField& F23, scalargpuField& a, scalargpuField& b,
+                         scalargpuField& c, scalargpuField& dO, scalargpuField& dK) {
+        mi_sst_blend_arrays x{};
+        for (int d = 0; d < 3; ++d) { x.grad_k_dev[d] = gk.component(d).data(); x.grad_omega_dev[d] = go.component(d).data(); }
+        x.k_dev = k.data(); x.omega_dev = omega.data(); x.y_dev = y.data(); x.nut_dev = nut.data(); x.s2_dev = s2.data(); x.nu_value = nu_;
+        x.f1_out_dev = F1.data(); x.su_out_dev = a.data(); x.sp_out_dev = b.data(); x.susp_out_dev = c.data(); x.domega_out_dev = dO.data();
+        x.dk_out_dev = dK.data(); x.f23_out_dev_or_null = F23.data();
+        miCheck(mi_sst_blend(ctx, m, &coeffs_, F3_, &x), "kOmegaSST::correct: F1");
+    };
+    blendPass(n, gradK, gradOmega, k_, omega_, *mesh_.y, nut_, S2, F1_, F23_, su, sp, susp, DomegaEff, DkEff);
+    blendPass(nb_, bGradK, bGradOmega, bk_, bomega_, *mesh_.bY, bnut_, bS2, bF1, bF23, bsu, bsp, bsusp, bDomegaEff, bDkEff);
+    // the turbulent frequency equation (:426-447)
+    solveEquation("omega", omega_, bomega_, omegaOld, su, sp, &susp, DomegaEff, bDomegaEff, flow, rDeltaT, omegaRelax, omegaSolver);
+    evaluateBoundary(omega_, bomega_);
+    bound(omega_, &bomega_, *mesh_.average, *mesh_.weights, omegaMin_);
+    // the turbulent kinetic energy equation (:450-462)
+    miCheck(mi_sst_k_terms(ctx, n, &coeffs_, G.data(), k_.data(), omega_.data(), su.data(), sp.data()), "kOmegaSST::correct: kEqn");
+    solveEquation("k", k_, bk_, kOld, su, sp, nullptr, DkEff, bDkEff, flow, rDeltaT, kRelax, kSolver);
+    evaluateBoundary(k_, bk_);
+    bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);
+    correctNut(S2, bS2, false);                             // :466-467
+}
 }
 }
 void interfaceProperties::sigmaK(scalargpuField& out) const { fieldAxpby(out, sigma_, K_, 0.0, K_); }
