@@ -1068,6 +1068,102 @@ int mi_sst_k_terms(mi_ctx_t ctx, int64_t n, const mi_sst_coeffs *coeffs, const d
 int mi_sst_nut(mi_ctx_t ctx, int64_t n, const mi_sst_coeffs *coeffs, int f3, int constructor_form, const double *k_dev, const double *omega_dev,
                const double *y_dev, const double *s_dev, const double *nu_dev_or_null, double nu_value, double *nut_out_dev,
                double *f23_out_dev_or_null);
+/* ---- the thermo update of rhoPimpleFoam: T from he, psi, mu, alpha, rho (thermophysicalModels/basic/psiThermo/hePsiThermo.C:31-171,
+ *      rhoThermo/heRhoThermo.C:31-177, heThermo/heThermo.C:131-145, :397-760, :875-960; specie/thermo/thermo/thermoI.H:42-90 and below;
+ *      hConst/hConstThermoI.H:93-140, eConst/eConstThermoI.H:94-143, janaf/janafThermoI.H:58-71, :119-141, :188-241, janafThermo.C:31-53;
+ *      equationOfState/perfectGas/perfectGasI.H:80-106; transport/const/constTransportI.H:98-128, sutherland/sutherlandTransportI.H:133-164;
+ *      DESIGN 3.5q) ----
+ * thermo.correct() (rhoPimpleFoam/EEqn.H:31) is hePsiThermo::calculate(): per cell and per patch face a Newton iteration for T from he and
+ * p, then psi, mu and alpha; heRhoThermo::calculate() adds rho.  One pure mixture of one thermoType:
+ *   energy         sensibleEnthalpy (he = Hs, Cpv = Cp, THE = THs) | sensibleInternalEnergy (he = Es, Cpv = Cv, THE = TEs)
+ *   thermodynamics hConst {Cp, Hf} | eConst {Cv, Hf} | janaf {Tlow, Thigh, Tcommon, highCpCoeffs[7], lowCpCoeffs[7]}
+ *   equation of state  perfectGas {W}: rho = p/(R*T), psi = 1.0/(R*T), cpMcv = 8314.4621, R = 8314.4621/W
+ *   transport      const {mu, Pr} | sutherland {As, Ts}
+ * The rules of the kEpsilon block hold: fp64 values, int32 labels, every operator rounded on its own except the fma written below, correctly
+ * rounded division and square root, max(a, b) = (a > b) ? a : b, min(a, b) = (a < b) ? a : b (doubleFloat.H), mag = fabs.  No transcendental
+ * function is called, so given the contraction below every output is the reference's bit for bit.  Restated in tests/thermo_support.py, not
+ * pinned by a compiled reference.
+ * mi_thermo_model_init (host only, no GPU): thermo_values = {Cp, Hf} | {Cv, Hf} | {Tlow, Thigh, Tcommon, high[7], low[7]} and
+ *   transport_values = {mu, Pr} | {As, Ts}, the dictionary's per-mass numbers.  Formed once, in the constructors' order: R = 8314.4621/W,
+ *   CpW = Cp*W, CvW = Cv*W, HfW = Hf*W (hConstThermo.C:40-41, eConstThermo.C likewise; janafThermo.C scales nothing), cpE = CvW + cpMcv
+ *   (eConstThermoI.H:111), rPr = 1.0/Pr (constTransport.C:47); for janaf the quotients {a1/2.0, a2/3.0, a3/4.0, a4/5.0} of each set
+ *   (highH, lowH) and hc = 8314.4621*fma(fma(fma(fma(fma(l4/5, Tstd, l3/4), Tstd, l2/3), Tstd, l1/2), Tstd, l0), Tstd, l5), Tstd = 298.15, of
+ *   the LOW set (janafThermoI.H:230-241).  Refused: a member that is not finite, or not above zero -- Hf and the janaf coefficients may
+ *   have any finite sign -- and what janafThermo::checkInputData refuses: Tlow >= Thigh, Tcommon <= Tlow, Tcommon > Thigh.  Members of the
+ *   parts not chosen stay 0 and are not looked at.  An entry that takes a model refuses one that init would refuse.
+ * The formulas (cp, hs per kmol; W the molecular weight):
+ *     hConst: cp = CpW, hs = CpW*T.   eConst: cp = cpE, hs = cpE*T.
+ *     janaf: a = (T < Tcommon) ? low : high at EVERY evaluation;  cp = 8314.4621*fma(fma(fma(fma(a4, T, a3), T, a2), T, a1), T, a0);
+ *            hs = ha - hc = fma(8314.4621, fma(fma(fma(fma(fma(a4/5.0, T, a3/4.0), T, a2/3.0), T, a1/2.0), T, a0), T, a5), -hc)
+ *     Hs = hs/W;  Cp = cp/W;  Cv = cv/W with cv = cp - cpMcv, for janaf cv = fma(8314.4621, chain of cp, -cpMcv): cp's product has this one
+ *            use and contracts with the subtraction (the Newton divisor of the internal energy, sutherland's Cv_, the Cv / Cpv / kappa
+ *            properties all take it);  Es = es/W with q = (p*W)/rho(p, T) and
+ *            es = fma(CpW, T, -q) (hConst) | fma(cpE, T, -q) (eConst) | hs - q (janaf: hs ends in an fma already)
+ *     gamma = cp/(cp - cpMcv) with cp ROUNDED, janaf included: the product has two uses there (thermoI.H:148-149) and stays a product;
+ *            CpByCpv = 1 (enthalpy) | gamma (internal energy)
+ *     const: mu = mu_, alphah = mu_*rPr, kappa = (Cpv*mu_)*rPr.
+ *     sutherland: mu = (As*sqrt(T))/(1.0 + Ts/T), kappa = (mu*Cv_)*(1.32 + (1.77*R)/Cv_) with Cv_ = Cv(p, T), alphah = kappa/Cpv
+ *   Rounded first, NOT contracted: Cv_ + cpMcv, 1.32 + (1.77*R)/Cv_, the Newton update (a division stands before each sum), hConst's and
+ *   eConst's hs of the enthalpy form.  The fma above are what the x86 compiler's contraction (-ffp-contract=fast) makes of the reference's
+ *   expressions, taken for nvcc's: an ASSUMPTION.
+ * The Newton iteration is thermo::T (thermoI.H:42-90): Ttol = T0*1.0e-4; do { Test = Tnew; Tnew = limit(Test - (F(p, Test) - f)/dFdT(p, Test));
+ *   if (iter++ > 100) return NaN; } while (mag(Tnew - Test) > Ttol) -- the NaN of the reference's device branch (0.0/0.0), on the 102nd
+ *   evaluation.  F / dFdT = Hs / Cp or Es / Cv.  limit is the identity for hConst / eConst and, for janaf, min(max(T, Tlow), Thigh) when
+ *   T < Tlow || T > Thigh (janafThermoI.H:119-141).
+ * mi_thermo_calculate: hePsiThermoCalculateFunctor / heRhoThermoCalculateFunctor on n elements in one launch: T = THE(he, p, T0), psi, mu,
+ *   alpha at the new T; 24 bytes in, 32 out, 40 with rho.  rho_form 0: no rho; 1: rho = p/(R*T), heRhoThermo's mixture.rho; 2: rho = psi*p,
+ *   psiThermo::rho(), what rhoPimpleFoam assigns after correct().  t_out may be t0 itself (the normal in-place use) or he itself (fault 1
+ *   below); every element is read before it is written; any other overlap of an output with an input or an output is refused.
+ *   iters_out_or_null (int32, for the tests) receives the number of evaluations of the Newton step.  Two cells per thread with 16-byte
+ *   accesses when every double array is 16-byte aligned, one by one otherwise; under the context's launch-grid cap (MI_FACE_GRID).  The
+ *   model travels by value in the kernel arguments; janaf's coefficient sets (and the boundary pass's run table) are staged in LDS.
+ * mi_thermo_calculate_boundary: the patch loop of hePsiThermo.C:109-171 / heRhoThermo.C:111-177 for ALL patches in ONE launch (one per 16 runs
+ *   of consecutive patches of one kind) over the patch-ordered boundary arrays of a mi_grad_boundary_t.  patch_kind[p] = 0: skip (empty);
+ *   1: fixesValue(): b_he = HE(p, T), the properties at the given T; 2: b_t_out = THE(he, p, T), the properties at the new T.
+ * mi_thermo_he: he = HE(p, T) on n elements: heThermo::init() on the cells, and he(p, T, patchi) on a patch -- the caller passes the patch's
+ *   slice of its boundary arrays (no patch mask).
+ * mi_thermo_property: one of MI_THERMO_CP / CV / GAMMA / CPV / CPBYCPV / KAPPA from p and T, cells or a patch slice: the mixture's members that
+ *   heThermo.C:397-760 transforms over.  MI_THERMO_KAPPA is the TRANSPORT model's kappa(p, T) (constTransportI.H:110-117,
+ *   sutherlandTransportI.H:145-152), NOT heThermo::kappa(): that one is Cp()*alpha_ (heThermo.C:875-896), kappaEff is Cp*alphaEff(alphat) and
+ *   alphaEff is CpByCpv*(alpha_ + alphat) (:901-962) -- products of fields: MI_THERMO_CP or MI_THERMO_CPBYCPV, then the caller's field
+ *   product with alpha or with alpha + alphat (mi_vec_axpby forms the sum).
+ * Two faults of the reference, decided here:
+ *   1. On a patch that does not fix T the reference's transform writes the new temperature into the he patch field -- its output tuple starts
+ *      with ph.begin() (hePsiThermo.C:161-169, heRhoThermo.C:166-175) -- and pT stays as it was; the loop it replaced, still in the comment
+ *      above it, assigns pT[facei].  Here the outputs are the caller's pointers: b_t_out = b_t is OpenFOAM's meaning (the default of the Python
+ *      binding and the mirror), b_t_out = b_he reproduces the reference's transform.
+ *   2. On a fixesValue patch heRhoThermo's functor returns psi in the rho slot (heRhoThermo.C:57-61).  Here rho(p, T) is written (by
+ *      rho_form).  A caller who wants the reference's bits runs rho_form 0 on those patches' behalf and copies b_psi.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): a missing array; an array not aligned for a double, iters not for an int32; an
+ *   overlap other than the two allowed; an unknown energy form, thermodynamics, transport, rho_form, property kind or patch kind; a boundary
+ *   of another addressing; NULL boundary arrays while a patch of kind 1 or 2 has faces; a model init would refuse; rho_form != 0 with no rho
+ *   array.  Zero elements, zero patches and patches all of kind 0: MI_OK without a launch.
+ * Out of scope: mixtures of several species, reacting thermo, the other equations of state, hPolynomial / polynomialTransport /
+ *   hExponential, absolute enthalpy / internal energy, heBoundaryCorrection, psi.oldTime(), compressible turbulence, moving meshes. */
+enum { MI_THERMO_ENTHALPY = 0, MI_THERMO_INTERNAL_ENERGY = 1 };
+enum { MI_THERMO_HCONST = 0, MI_THERMO_ECONST = 1, MI_THERMO_JANAF = 2 };
+enum { MI_THERMO_CONST = 0, MI_THERMO_SUTHERLAND = 1 };
+enum { MI_THERMO_CP = 0, MI_THERMO_CV = 1, MI_THERMO_GAMMA = 2, MI_THERMO_CPV = 3, MI_THERMO_CPBYCPV = 4, MI_THERMO_KAPPA = 5 };
+typedef struct mi_thermo_model {
+    int32_t energy, thermo, transport, reserved;
+    double W;
+    double Cp, Cv, Hf;                        /* hConst: Cp, Hf; eConst: Cv, Hf (per mass, as given) */
+    double Tlow, Thigh, Tcommon, highCpCoeffs[7], lowCpCoeffs[7];   /* janaf */
+    double mu, Pr, As, Ts;                    /* const: mu, Pr; sutherland: As, Ts */
+    double R, cpMcv, CpW, CvW, HfW, cpE, rPr; /* derived: mi_thermo_model_init */
+    double highH[4], lowH[4], hc;
+} mi_thermo_model;
+int mi_thermo_model_init(int energy, int thermo, int transport, double W, const double *thermo_values, const double *transport_values,
+                         mi_thermo_model *out);
+int mi_thermo_calculate(mi_ctx_t ctx, const mi_thermo_model *model, int rho_form, int64_t n, const double *he_dev, const double *p_dev,
+                        const double *t0_dev, double *t_out_dev, double *psi_out_dev, double *mu_out_dev, double *alpha_out_dev,
+                        double *rho_out_dev_or_null, int32_t *iters_out_or_null);
+int mi_thermo_calculate_boundary(mi_addr_t addr, mi_grad_boundary_t boundary, const mi_thermo_model *model, const int32_t *patch_kind,
+                                 int rho_form, double *b_he_inout_dev, const double *b_p_dev, const double *b_t_dev, double *b_t_out_dev,
+                                 double *b_psi_out_dev, double *b_mu_out_dev, double *b_alpha_out_dev, double *b_rho_out_dev_or_null);
+int mi_thermo_he(mi_ctx_t ctx, const mi_thermo_model *model, int64_t n, const double *p_dev, const double *t_dev, double *he_out_dev);
+int mi_thermo_property(mi_ctx_t ctx, const mi_thermo_model *model, int kind, int64_t n, const double *p_dev, const double *t_dev,
+                       double *out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

@@ -92,6 +92,7 @@ SYMBOLS = [
     "mi_ke_production", "mi_ke_create", "mi_ke_destroy", "mi_ke_wall_cells", "mi_ke_wall_cell_labels", "mi_ke_wall_values",
     "mi_ke_epsilon_terms", "mi_ke_k_terms", "mi_ke_nut", "mi_ke_nut_wall",
     "mi_sst_coeffs_init", "mi_sst_production", "mi_sst_wall_cells", "mi_sst_blend", "mi_sst_omega_sources", "mi_sst_k_terms", "mi_sst_nut",
+    "mi_thermo_model_init", "mi_thermo_calculate", "mi_thermo_calculate_boundary", "mi_thermo_he", "mi_thermo_property",
 ]
 
 
@@ -1588,6 +1589,53 @@ def sst_coeffs(**given) -> SstCoeffs:
     return out
 
 
+class ThermoModel(C.Structure):
+    """mi_thermo_model (include/mi_ldu.h)"""
+    _fields_ = [(name, C.c_int32) for name in ("energy", "thermo", "transport", "reserved")] + \
+               [(name, C.c_double) for name in ("W", "Cp", "Cv", "Hf", "Tlow", "Thigh", "Tcommon")] + \
+               [("highCpCoeffs", C.c_double * 7), ("lowCpCoeffs", C.c_double * 7)] + \
+               [(name, C.c_double) for name in ("mu", "Pr", "As", "Ts", "R", "cpMcv", "CpW", "CvW", "HfW", "cpE", "rPr")] + \
+               [("highH", C.c_double * 4), ("lowH", C.c_double * 4), ("hc", C.c_double)]
+
+
+THERMO_ENERGY = {"sensibleEnthalpy": 0, "h": 0, "sensibleInternalEnergy": 1, "e": 1}
+THERMO_THERMO = {"hConst": 0, "eConst": 1, "janaf": 2}
+THERMO_TRANSPORT = {"const": 0, "sutherland": 1}
+THERMO_PROPERTIES = {"Cp": 0, "Cv": 1, "gamma": 2, "Cpv": 3, "CpByCpv": 4, "kappa": 5}
+# air: the defaults of thermo_model (the janaf set is the two-range fit of the thermophysicalProperties of the combustion tutorials)
+THERMO_DEFAULTS = dict(
+    energy="sensibleEnthalpy", thermo="hConst", transport="const", W=28.9, Cp=1007.0, Cv=719.3, Hf=0.0, mu=1.84e-05, Pr=0.7, As=1.4792e-06, Ts=116.0,
+    Tlow=200.0, Thigh=6000.0, Tcommon=1000.0,
+    highCpCoeffs=(3.08792717, 0.00124597184, -4.23718945e-07, 6.74774789e-11, -3.97076972e-15, -995.262755, 5.9596093),
+    lowCpCoeffs=(3.5683962, -0.000678729429, 1.55371476e-06, -3.2993706e-12, -4.66395387e-13, -1062.34659, 3.71582965))
+
+
+def thermo_model(**given) -> ThermoModel:
+    """mi_thermo_model_init: one pure-mixture thermoType by name -- energy ("sensibleEnthalpy" / "h", "sensibleInternalEnergy" / "e"), thermo
+    ("hConst", "eConst", "janaf"), transport ("const", "sutherland"), W and the dictionary's per-mass numbers of the chosen parts, air's
+    (THERMO_DEFAULTS) for the rest -- with the host-formed members derived (host only, no GPU)"""
+    unknown = set(given) - set(THERMO_DEFAULTS)
+    if unknown:
+        raise TypeError("thermo_model: unknown name " + ", ".join(sorted(unknown)))
+    g = dict(THERMO_DEFAULTS, **given)
+    for name, table in (("energy", THERMO_ENERGY), ("thermo", THERMO_THERMO), ("transport", THERMO_TRANSPORT)):
+        if not isinstance(g[name], int) and g[name] not in table:
+            raise MiError(f"thermo_model: unknown {name} {g[name]!r}")
+    e, th, tr = [g[name] if isinstance(g[name], int) else table[g[name]]
+                 for name, table in (("energy", THERMO_ENERGY), ("thermo", THERMO_THERMO), ("transport", THERMO_TRANSPORT))]
+    if th == 2:
+        if len(g["highCpCoeffs"]) != 7 or len(g["lowCpCoeffs"]) != 7:
+            raise MiError("thermo_model: janaf takes seven high and seven low coefficients")
+        tv = [g["Tlow"], g["Thigh"], g["Tcommon"], *g["highCpCoeffs"], *g["lowCpCoeffs"]]
+    else:
+        tv = [g["Cv"] if th == 1 else g["Cp"], g["Hf"]]
+    xv = [g["As"], g["Ts"]] if tr == 1 else [g["mu"], g["Pr"]]
+    out = ThermoModel()
+    _chk(lib().mi_thermo_model_init(C.c_int(e), C.c_int(th), C.c_int(tr), C.c_double(g["W"]), (C.c_double * len(tv))(*[float(v) for v in tv]),
+                                    (C.c_double * 2)(*[float(v) for v in xv]), C.byref(out)))
+    return out
+
+
 class SstWall(C.Structure):
     """mi_sst_wall (include/mi_ldu.h)"""
     _fields_ = [("k_dev", C.c_void_p), ("u_dev", C.c_void_p * 3), ("b_uw_dev", C.c_void_p * 3), ("b_delta_coeffs_dev", C.c_void_p),
@@ -1978,6 +2026,38 @@ class Assembly:
         _chk(lib().mi_sst_nut(self.addr.ctx.h, C.c_int64(n), C.byref(coeffs) if coeffs is not None else None, C.c_int(int(bool(f3))),
                               C.c_int(int(bool(constructor_form))), _ptr(k), _ptr(omega), _ptr(y), _ptr(s), _ptr(nu_dev), C.c_double(nu_value),
                               _ptr(nut_out), _ptr(f23_out)))
+
+    def thermo_calculate(self, model, he, p, t0, t_out, psi_out, mu_out, alpha_out, rho_out=None, rho_form=0, iters_out=None):
+        """T = THE(he, p, t0) by the reference's Newton iteration, then psi, mu, alpha and (rho_form 1: p/(R*T), 2: psi*p) rho at the new T in one
+        cell pass (mi_thermo_calculate); t_out may be t0 or he; iters_out an int32 tensor for the evaluation counts or None"""
+        n = (he if he is not None else t_out).numel()
+        it = None
+        if iters_out is not None:
+            assert iters_out.is_contiguous() and iters_out.element_size() == 4
+            it = C.c_void_p(iters_out.data_ptr())
+        _chk(lib().mi_thermo_calculate(self.addr.ctx.h, C.byref(model) if model is not None else None, C.c_int(int(rho_form)), C.c_int64(n), _ptr(he),
+                                       _ptr(p), _ptr(t0), _ptr(t_out), _ptr(psi_out), _ptr(mu_out), _ptr(alpha_out), _ptr(rho_out), it))
+
+    def thermo_calculate_boundary(self, boundary, model, patch_kind, b_he, b_p, b_t, b_psi_out, b_mu_out, b_alpha_out, b_rho_out=None, rho_form=0,
+                                  b_t_out=None):
+        """the patch loop of hePsiThermo / heRhoThermo ::calculate() on every patch in one launch (mi_thermo_calculate_boundary): patch_kind per
+        patch 0 skip, 1 fixesValue (b_he = HE(p, T)), 2 otherwise (T = THE(he, p, T)); the new temperature of kind 2 goes to b_t_out, b_t itself
+        when None (OpenFOAM's meaning; b_t_out=b_he is the reference's transform)"""
+        pk = None if patch_kind is None else (C.c_int32 * max(len(patch_kind), 1))(*[int(k) for k in patch_kind])
+        _chk(lib().mi_thermo_calculate_boundary(self.addr.h, boundary.h if boundary is not None else None, C.byref(model) if model is not None else None,
+                                                pk, C.c_int(int(rho_form)), _ptr(b_he), _ptr(b_p), _ptr(b_t), _ptr(b_t if b_t_out is None else b_t_out),
+                                                _ptr(b_psi_out), _ptr(b_mu_out), _ptr(b_alpha_out), _ptr(b_rho_out)))
+
+    def thermo_he(self, model, p, t, he_out):
+        """he = HE(p, T) (mi_thermo_he): heThermo::init on the cells, or on a patch's slice of the boundary arrays"""
+        n = (p if p is not None else he_out).numel()
+        _chk(lib().mi_thermo_he(self.addr.ctx.h, C.byref(model) if model is not None else None, C.c_int64(n), _ptr(p), _ptr(t), _ptr(he_out)))
+
+    def thermo_property(self, model, kind, p, t, out):
+        """one of Cp, Cv, gamma, Cpv, CpByCpv, kappa (THERMO_PROPERTIES) from p and T (mi_thermo_property), cells or a patch slice"""
+        n = (p if p is not None else out).numel()
+        k = THERMO_PROPERTIES[kind] if isinstance(kind, str) else int(kind)
+        _chk(lib().mi_thermo_property(self.addr.ctx.h, C.byref(model) if model is not None else None, C.c_int(k), C.c_int64(n), _ptr(p), _ptr(t), _ptr(out)))
 
     def vec_min(self, x, y, out):
         """out = min(x, y) element by element, out may alias either (mi_vec_min): minOp over the two sides of a cyclic pair"""

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <ctime>
+#include <limits>
 
 namespace Foam
 {
@@ -2344,6 +2345,44 @@ void fvc::divBounded(scalargpuField& out, const lduAddressing& a, const scalargp
     scalargpuField face(faceFlux.size());
     miCheck(mi_fvc_div(a.handle(), faceFlux.data(), weights ? weights->data() : nullptr, vf.data(), V.data(), face.data(), out.data()), "fvc::div (bounded)");
     fieldSubMul(out, divPhi, vf);                     // - (divPhi*vf): the product rounded first
+}
+
+// ---- hePsiThermo / heRhoThermo ---------------------------------------------------------------------------------------------------------------
+hePsiThermo::hePsiThermo(const lduAddressing& addr, const gradBoundary& boundary, const std::vector<label>& patchSizes,
+                         const std::vector<patchType>& TPatchTypes, const mi_thermo_model& model, const scalargpuField& p, const scalargpuField& bp,
+                         const scalargpuField& T, const scalargpuField& bT, bool rhoThermo)
+    : addr_(addr), boundary_(boundary), model_(model), patchSizes_(patchSizes), rhoForm_(rhoThermo ? 1 : 2), p_(p), bp_(bp), T_(T), bT_(bT)
+{
+    if (patchSizes.size() != TPatchTypes.size()) FatalErrorIn("hePsiThermo::hePsiThermo", "one type per patch");
+    label nb = 0;
+    for (std::size_t i = 0; i < patchSizes.size(); ++i) { kinds_.push_back((int32_t)TPatchTypes[i]); nb += patchSizes[i]; }
+    if (p.size() != T.size() || bp.size() != nb || bT.size() != nb) FatalErrorIn("hePsiThermo::hePsiThermo", "field sizes do not match the mesh");
+    const std::vector<scalar> seed((std::size_t)nb, std::numeric_limits<scalar>::quiet_NaN());
+    he_ = scalargpuField(T.size()); psi_ = scalargpuField(T.size()); mu_ = scalargpuField(T.size()); alpha_ = scalargpuField(T.size());
+    rho_ = scalargpuField(T.size());
+    bhe_ = seed; bpsi_ = seed; bmu_ = seed; balpha_ = seed; brho_ = seed;
+    init();
+    calculate();
+}
+void hePsiThermo::init()
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    miCheck(mi_thermo_he(ctx, &model_, T_.size(), p_.data(), T_.data(), he_.data()), "heThermo::init");
+    label off = 0;
+    for (std::size_t i = 0; i < patchSizes_.size(); ++i) {                // he(p, T, patchi) on the patch's slice
+        if (kinds_[i] != empty && patchSizes_[i] > 0)
+            miCheck(mi_thermo_he(ctx, &model_, patchSizes_[i], bp_.data() + off, bT_.data() + off, bhe_.data() + off), "heThermo::init");
+        off += patchSizes_[i];
+    }
+}
+void hePsiThermo::correct() { calculate(); }
+void hePsiThermo::calculate()
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    miCheck(mi_thermo_calculate(ctx, &model_, rhoForm_, T_.size(), he_.data(), p_.data(), T_.data(), T_.data(), psi_.data(), mu_.data(), alpha_.data(),
+                                rho_.data(), nullptr), "hePsiThermo::calculate");
+    miCheck(mi_thermo_calculate_boundary(addr_.handle(), boundary_.handle(), &model_, kinds_.data(), rhoForm_, bhe_.data(), bp_.data(), bT_.data(),
+                                         bT_.data(), bpsi_.data(), bmu_.data(), balpha_.data(), brho_.data()), "hePsiThermo::calculate");
 }
 
 } // namespace Foam
