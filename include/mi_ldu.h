@@ -1164,6 +1164,80 @@ int mi_thermo_calculate_boundary(mi_addr_t addr, mi_grad_boundary_t boundary, co
 int mi_thermo_he(mi_ctx_t ctx, const mi_thermo_model *model, int64_t n, const double *p_dev, const double *t_dev, double *he_out_dev);
 int mi_thermo_property(mi_ctx_t ctx, const mi_thermo_model *model, int kind, int64_t n, const double *p_dev, const double *t_dev,
                        double *out_dev);
+/* ---- rhoCentralFoam's Kurganov and Tadmor face fluxes (applications/solvers/compressible/rhoCentralFoam/rhoCentralFoam.C:60-185,
+ *      readFluxScheme.H, createFields.H:76-98, compressibleCourantNo.H:35-47) ----
+ * What the top of rhoCentralFoam's time loop runs as ten limited interpolations and about forty-five face-field operators (some seventy
+ * passes with face-sized temporaries) is ONE face pass here, with a patch form, one cell pass and one reduction beside it.
+ * mi_central_scheme_parse: host only.  flux_scheme "Kurganov" | "Tadmor" (readFluxScheme.H), anything else MI_ERR_ARG.  The three
+ *   reconstruct(...) entries go through mi_limiter_parse unchanged: every TVD/NVD name it accepts is accepted.  reconstruct(rho) and
+ *   reconstruct(T) limit scalars (the bounded forms allowed, a V form refused); reconstruct(U) may be a V form, limited on rhoU itself, or a
+ *   scalar form, limited on the caller's magSqr(rhoU) and its gradient (LimitFuncs.C:39-54, as mi_limited_weights).  Refused with *out
+ *   untouched: the filtered names and whatever mi_limiter_parse refuses.
+ * mi_central_flux (internal faces; :62-185): with P = lower[f], N = upper[f], d = C[N] - C[P], per field v of rho, rhoU, rPsi, e, c (under
+ *   reconstruct(rho), (U), (T), (T), (T)) and per direction, pos with faceFlux fl = +1.0 and neg with fl = -1.0 (createFields.H:76-98):
+ *     lim = the limiter of mi_limited_weights at that faceFlux;  w = fma(lim, cdw, (1.0 - lim)*(fl >= 0 ? 1.0 : 0.0))
+ *     v_dir = fma(w, vP - vN, vN)                               (the rule of mi_face_interpolate; rhoU per component with one w)
+ *   then, every operator a field operator of the reference and rounded on its own, dir = pos, neg:
+ *     U_dir,k = rhoU_dir,k/rho_dir                              (:107-108, three divisions, no reciprocal)
+ *     p_dir = rho_dir*rPsi_dir                                  (:110-111)
+ *     phiv_dir = fma(U_z, Sf_z, fma(U_x, Sf_x, U_y*Sf_y))       (:113-114, the dot product of DESIGN 3.5a)
+ *     cSf_dir = c_dir*magSf                                     (:117-126)
+ *     ap = max(max(phiv_pos + cSf_pos, phiv_neg + cSf_neg), 0.0);  am = min(min(phiv_pos - cSf_pos, phiv_neg - cSf_neg), 0.0)
+ *                                                               (:128-137; max(a, b) = (a > b) ? a : b, so max(-0.0, 0.0) = +0.0)
+ *     a_pos = ap/(ap - am);  amaxSf = max(|am|, |ap|);  aSf = am*a_pos                      (:139-143)
+ *     Tadmor: aSf = -0.5*amaxSf;  a_pos = 0.5                                               (:145-149)
+ *     a_neg = 1.0 - a_pos;  phiv_pos = phiv_pos*a_pos;  phiv_neg = phiv_neg*a_neg           (:151-154)
+ *     aphiv_pos = phiv_pos - aSf;  aphiv_neg = phiv_neg + aSf;  amaxSf = max(|aphiv_pos|, |aphiv_neg|)   (:156-161, the amaxSf written)
+ *     phi = aphiv_pos*rho_pos + aphiv_neg*rho_neg                                           (:171, two products and a sum)
+ *     phiUp_k = (aphiv_pos*rhoU_pos,k + aphiv_neg*rhoU_neg,k) + (a_pos*p_pos + a_neg*p_neg)*Sf_k         (:173-177)
+ *     phiEp = ((aphiv_pos*(rho_pos*(e_pos + 0.5*magSqr(U_pos)) + p_pos) + aphiv_neg*(rho_neg*(e_neg + 0.5*magSqr(U_neg)) + p_neg))
+ *              + aSf*p_pos) - aSf*p_neg                                                     (:179-185, left to right as written)
+ *     magSqr(U) = fma(U_z, U_z, fma(U_x, U_x, U_y*U_y)): magSqr contracts as the dot product does -- an ASSUMPTION
+ *     a_pos_out, au_out (all four or none): a_pos and aU_k = a_pos*U_pos,k + a_neg*U_neg,k (what sigmaDotU, :216-224, reads)
+ *   ap - am == 0 (it needs c == 0) has no special case: the reference's NaN comes out.  One launch, one thread per face, no atomics, the
+ *   same bits on every run; under the context's launch-grid cap (MI_FACE_GRID).
+ * mi_patch_central_flux: one patch.  patch_weights NULL (any patch that is not coupled): `values` holds the seven BOUNDARY VALUE arrays
+ *   (rho, rhoU[3], rPsi, e, c per patch face; no gradient is read), which are the face values of both directions
+ *   (surfaceInterpolationScheme.C:261-264); the algebra above runs operation for operation, nothing simplified.  patch_weights given (a
+ *   COUPLED patch): `values` the cell arrays (read through the patch's faceCells), `nbr` their patchNeighbourFields, d = patch_delta, the
+ *   limiter as mi_patch_limited_weights', v_dir = w*vP + (1.0 - w)*vNbr with every operator rounded (surfaceInterpolationScheme.C:361-366).
+ * mi_central_sound_speed (:84, :116): rPsi = 1.0/psi;  c = sqrt((Cp/Cv)*rPsi) in that order, IEEE / and sqrt.
+ * mi_central_courant (compressibleCourantNo.H:35-47): max over the internal AND the boundary faces of (deltaCoeffs*amaxSf)/magSf
+ *   (max(GeometricField) includes the boundary, GeometricFieldFunctions.C:478-506) and sum over the INTERNAL faces of deltaCoeffs*amaxSf
+ *   (sum(GeometricField) does not, :511-538), to the host; the caller multiplies by deltaT and divides by its own sum(magSf).  The product
+ *   is formed on load in the reduction trees of mi_sum and mi_min_max: the sum is mi_sum's over the stored product bit for bit, the max
+ *   mi_min_max's.  No internal faces: 0 and 0, no launch.  During a PCG session: MI_ERR_STATE.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): an invalid mi_central_scheme; a missing array; internal-face arrays not 16-byte
+ *   aligned, cell and patch arrays not 8-byte aligned; an output that aliases an input or another output; a_pos_out / au_out given in
+ *   part; a scalar reconstruct(U) without lim_u and its gradient.  A mesh without internal faces, a patch without faces: MI_OK, no launch.
+ * Out of scope: the viscous branch and sigmaDotU (apart from aU), rhoCentralDyMFoam's mesh-flux terms, the slip and jump boundary
+ *   conditions of rhoCentralFoam/BCs, rotated coupled patches. */
+enum { MI_CENTRAL_KURGANOV = 0, MI_CENTRAL_TADMOR = 1 };
+typedef struct mi_central_scheme {
+    int32_t flux_scheme, reserved;            /* MI_CENTRAL_* */
+    mi_limiter rho, U, T;                     /* reconstruct(rho), reconstruct(U), reconstruct(T) */
+} mi_central_scheme;
+typedef struct mi_central_cells {             /* one side's fields: cell arrays, patchNeighbourFields, or a plain patch's boundary values */
+    const double *rho_dev, *rhou_dev[3], *rpsi_dev, *e_dev, *c_dev;
+    const double *grad_rho_dev[3], *grad_rhou_dev[9], *grad_rpsi_dev[3], *grad_e_dev[3], *grad_c_dev[3];   /* grad_rhou[3*j + k] = d(rhoU_j)/dx_k: a V reconstruct(U) only */
+    const double *lim_u_dev, *grad_lim_u_dev[3];   /* a scalar reconstruct(U) only: magSqr(rhoU) and its gradient */
+} mi_central_cells;
+typedef struct mi_central_out {
+    double *phi_out_dev, *phiup_out_dev[3], *phiep_out_dev, *amaxsf_out_dev;
+    double *a_pos_out_dev, *au_out_dev[3];    /* all four or all NULL */
+} mi_central_out;
+int mi_central_scheme_parse(const char *flux_scheme, const char *reconstruct_rho, const char *reconstruct_U, const char *reconstruct_T,
+                            mi_central_scheme *out);
+int mi_central_flux(mi_addr_t addr, const mi_central_scheme *scheme, const double *cd_weights_dev, const double *const *sf_dev,
+                    const double *mag_sf_dev, const mi_central_cells *cells, const double *const *c_dev, const mi_central_out *out);
+int mi_patch_central_flux(mi_patch_t patch, const mi_central_scheme *scheme, const double *patch_weights_dev_or_null,
+                          const double *const *patch_sf_dev, const double *patch_mag_sf_dev, const mi_central_cells *values,
+                          const mi_central_cells *nbr_or_null, const double *const *patch_delta_dev_or_null, const mi_central_out *out);
+int mi_central_sound_speed(mi_ctx_t ctx, int64_t n, const double *cp_dev, const double *cv_dev, const double *psi_dev,
+                           double *rpsi_out_dev, double *c_out_dev);
+int mi_central_courant(mi_addr_t addr, const double *delta_coeffs_dev, const double *mag_sf_dev, const double *amaxsf_dev,
+                       int64_t n_boundary, const double *b_delta_coeffs_dev, const double *b_mag_sf_dev, const double *b_amaxsf_dev,
+                       double *max_out_host, double *sum_out_host);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

@@ -2510,6 +2510,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "interface.inc"
 #include "turbulence.inc"
 #include "thermo.inc"
+#include "central.inc"
 
 mi_matrix_s::~mi_matrix_s()
 {

@@ -93,6 +93,7 @@ SYMBOLS = [
     "mi_ke_epsilon_terms", "mi_ke_k_terms", "mi_ke_nut", "mi_ke_nut_wall",
     "mi_sst_coeffs_init", "mi_sst_production", "mi_sst_wall_cells", "mi_sst_blend", "mi_sst_omega_sources", "mi_sst_k_terms", "mi_sst_nut",
     "mi_thermo_model_init", "mi_thermo_calculate", "mi_thermo_calculate_boundary", "mi_thermo_he", "mi_thermo_property",
+    "mi_central_scheme_parse", "mi_central_flux", "mi_patch_central_flux", "mi_central_sound_speed", "mi_central_courant",
 ]
 
 
@@ -983,6 +984,13 @@ class Patch:
         x.b1_out_dev, x.b2_out_dev = (_ptr(b12_out[0]), _ptr(b12_out[1])) if b12_out is not None else (None, None)
         _chk(lib().mi_patch_interface_nhatf(self.h, C.c_double(delta_n), C.byref(x)))
 
+    def central_flux(self, scheme, patch_sf, patch_mag_sf, values, out, patch_weights=None, nbr=None, patch_delta=None):
+        """rhoCentralFoam's fluxes on this patch (mi_patch_central_flux).  patch_weights None: values a CentralCells of the seven boundary value
+        arrays.  patch_weights given: a COUPLED patch, values the cell arrays, nbr their patchNeighbourFields, patch_delta [x, y, z]"""
+        _chk(lib().mi_patch_central_flux(self.h, C.byref(scheme) if scheme is not None else None, _ptr(patch_weights), _ptrs(patch_sf, 3), _ptr(patch_mag_sf),
+                                         C.byref(values) if values is not None else None, C.byref(nbr) if nbr is not None else None,
+                                         _ptrs(patch_delta, 3), C.byref(out) if out is not None else None))
+
     def surface_tension_force(self, sigma, patch_weights, patch_delta_coeffs, K, nbr_K, alpha, nbr_alpha, out, sngrad_corr=None):
         """interpolate(sigma*K)*snGrad(alpha) on a COUPLED patch (mi_patch_surface_tension_force): K / alpha the cell fields, nbr_* their
         patchNeighbourFields"""
@@ -1146,6 +1154,58 @@ def limiter(scheme: str) -> Limiter:
     out = Limiter()
     _chk(lib().mi_limiter_parse(scheme.encode(), C.byref(out)))
     return out
+
+
+class CentralScheme(C.Structure):
+    """mi_central_scheme (include/mi_ldu.h)"""
+    _fields_ = [("flux_scheme", C.c_int32), ("reserved", C.c_int32), ("rho", Limiter), ("U", Limiter), ("T", Limiter)]
+
+
+class CentralCells(C.Structure):
+    """mi_central_cells (include/mi_ldu.h)"""
+    _fields_ = [("rho_dev", C.c_void_p), ("rhou_dev", C.c_void_p * 3), ("rpsi_dev", C.c_void_p), ("e_dev", C.c_void_p), ("c_dev", C.c_void_p),
+                ("grad_rho_dev", C.c_void_p * 3), ("grad_rhou_dev", C.c_void_p * 9), ("grad_rpsi_dev", C.c_void_p * 3), ("grad_e_dev", C.c_void_p * 3),
+                ("grad_c_dev", C.c_void_p * 3), ("lim_u_dev", C.c_void_p), ("grad_lim_u_dev", C.c_void_p * 3)]
+
+
+class CentralOut(C.Structure):
+    """mi_central_out (include/mi_ldu.h)"""
+    _fields_ = [("phi_out_dev", C.c_void_p), ("phiup_out_dev", C.c_void_p * 3), ("phiep_out_dev", C.c_void_p), ("amaxsf_out_dev", C.c_void_p),
+                ("a_pos_out_dev", C.c_void_p), ("au_out_dev", C.c_void_p * 3)]
+
+
+def central_scheme(flux_scheme: str, reconstruct_rho: str, reconstruct_U: str, reconstruct_T: str) -> CentralScheme:
+    """mi_central_scheme_parse: "Kurganov" | "Tadmor" and the three reconstruct(...) entries of fvSchemes, each a limited scheme as
+    limiter() reads it; reconstruct(U) a V form or a scalar form (host only, no GPU)"""
+    out = CentralScheme()
+    _chk(lib().mi_central_scheme_parse(flux_scheme.encode(), reconstruct_rho.encode(), reconstruct_U.encode(), reconstruct_T.encode(), C.byref(out)))
+    return out
+
+
+def _pvec(xs, n):
+    """n device pointers of a list that may be None or hold None"""
+    xs = list(xs) if xs is not None else []
+    return (C.c_void_p * n)(*[_ptr(x) for x in xs + [None] * (n - len(xs))])
+
+
+def central_cells(rho=None, rhoU=None, rPsi=None, e=None, c=None, grad_rho=None, grad_rhoU=None, grad_rPsi=None, grad_e=None, grad_c=None,
+                  lim_U=None, grad_lim_U=None) -> CentralCells:
+    """one side's fields of the central flux passes: cell arrays, patchNeighbourFields or a plain patch's boundary values; rhoU three arrays,
+    every gradient three, grad_rhoU nine (grad_rhoU[3*j + k] = d(rhoU_j)/dx_k); lim_U / grad_lim_U for a scalar reconstruct(U).  The
+    structure holds device addresses, not tensors: the caller keeps the tensors alive until the call has been made"""
+    x = CentralCells()
+    x.rho_dev, x.rpsi_dev, x.e_dev, x.c_dev, x.lim_u_dev = _ptr(rho), _ptr(rPsi), _ptr(e), _ptr(c), _ptr(lim_U)
+    x.rhou_dev, x.grad_rho_dev, x.grad_rpsi_dev, x.grad_e_dev, x.grad_c_dev = _pvec(rhoU, 3), _pvec(grad_rho, 3), _pvec(grad_rPsi, 3), _pvec(grad_e, 3), _pvec(grad_c, 3)
+    x.grad_rhou_dev, x.grad_lim_u_dev = _pvec(grad_rhoU, 9), _pvec(grad_lim_U, 3)
+    return x
+
+
+def central_out(phi=None, phiUp=None, phiEp=None, amaxSf=None, a_pos=None, aU=None) -> CentralOut:
+    """the outputs of the central flux passes: phiUp three arrays; a_pos and aU (three arrays) together or not at all"""
+    x = CentralOut()
+    x.phi_out_dev, x.phiep_out_dev, x.amaxsf_out_dev, x.a_pos_out_dev = _ptr(phi), _ptr(phiEp), _ptr(amaxSf), _ptr(a_pos)
+    x.phiup_out_dev, x.au_out_dev = _pvec(phiUp, 3), _pvec(aU, 3)
+    return x
 
 
 class FilteredLimiter(C.Structure):
@@ -2058,6 +2118,30 @@ class Assembly:
         n = (p if p is not None else out).numel()
         k = THERMO_PROPERTIES[kind] if isinstance(kind, str) else int(kind)
         _chk(lib().mi_thermo_property(self.addr.ctx.h, C.byref(model) if model is not None else None, C.c_int(k), C.c_int64(n), _ptr(p), _ptr(t), _ptr(out)))
+
+    def central_flux(self, scheme, cd_weights, sf, mag_sf, cells, c, out):
+        """rhoCentralFoam.C:62-185 on the internal faces in one face pass (mi_central_flux): scheme a CentralScheme (central_scheme), sf
+        [x, y, z] face arrays, cells a CentralCells (central_cells), c the cell centres [x, y, z], out a CentralOut (central_out)"""
+        _chk(lib().mi_central_flux(self.addr.h, C.byref(scheme) if scheme is not None else None, _ptr(cd_weights), _ptrs(sf, 3), _ptr(mag_sf),
+                                   C.byref(cells) if cells is not None else None, _ptrs(c, 3), C.byref(out) if out is not None else None))
+
+    def central_sound_speed(self, cp, cv, psi, rpsi_out, c_out):
+        """rPsi = 1.0/psi and c = sqrt((Cp/Cv)*rPsi) in one cell pass (mi_central_sound_speed)"""
+        n = (psi if psi is not None else rpsi_out).numel()
+        _chk(lib().mi_central_sound_speed(self.addr.ctx.h, C.c_int64(n), _ptr(cp), _ptr(cv), _ptr(psi), _ptr(rpsi_out), _ptr(c_out)))
+
+    def vec_div(self, x, y, out):
+        """out = x/y element by element, out may alias either (mi_vec_div)"""
+        _chk(lib().mi_vec_div(self.addr.ctx.h, C.c_int64(x.numel()), _ptr(x), _ptr(y), _ptr(out)))
+
+    def central_courant(self, delta_coeffs, mag_sf, amaxsf, b_delta_coeffs=None, b_mag_sf=None, b_amaxsf=None):
+        """-> (max over internal and boundary faces of (deltaCoeffs*amaxSf)/magSf, sum over the internal faces of deltaCoeffs*amaxSf) on the
+        host (mi_central_courant, compressibleCourantNo.H:35-47); a mesh without internal faces gives (0.0, 0.0)"""
+        mx, sm = C.c_double(0.0), C.c_double(0.0)
+        nb = 0 if b_amaxsf is None else b_amaxsf.numel()
+        _chk(lib().mi_central_courant(self.addr.h, _ptr(delta_coeffs), _ptr(mag_sf), _ptr(amaxsf), C.c_int64(nb), _ptr(b_delta_coeffs), _ptr(b_mag_sf),
+                                      _ptr(b_amaxsf), C.byref(mx), C.byref(sm)))
+        return float(mx.value), float(sm.value)
 
     def vec_min(self, x, y, out):
         """out = min(x, y) element by element, out may alias either (mi_vec_min): minOp over the two sides of a cyclic pair"""

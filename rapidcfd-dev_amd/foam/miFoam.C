@@ -2384,5 +2384,107 @@ void hePsiThermo::calculate()
     miCheck(mi_thermo_calculate_boundary(addr_.handle(), boundary_.handle(), &model_, kinds_.data(), rhoForm_, bhe_.data(), bp_.data(), bT_.data(),
                                          bT_.data(), bpsi_.data(), bmu_.data(), balpha_.data(), brho_.data()), "hePsiThermo::calculate");
 }
+static void thermoProperty(const mi_thermo_model& m, int kind, const scalargpuField& p, const scalargpuField& T, scalargpuField& out)
+{
+    if (out.size() != T.size()) FatalErrorIn("heThermo::Cp", "field sizes do not match");
+    miCheck(mi_thermo_property(miEngine::New().ctx, &m, kind, T.size(), p.data(), T.data(), out.data()), "heThermo::Cp");
+}
+void hePsiThermo::Cp(scalargpuField& cells, scalargpuField& boundary) const
+{
+    thermoProperty(model_, MI_THERMO_CP, p_, T_, cells); thermoProperty(model_, MI_THERMO_CP, bp_, bT_, boundary);
+}
+void hePsiThermo::Cv(scalargpuField& cells, scalargpuField& boundary) const
+{
+    thermoProperty(model_, MI_THERMO_CV, p_, T_, cells); thermoProperty(model_, MI_THERMO_CV, bp_, bT_, boundary);
+}
+
+// ---- rhoCentralFoam's flux evaluation (rhoCentralFoam.C:60-185) ------------------------------------------------------------------------
+centralFluxes::centralFluxes(const lduAddressing& addr, const std::vector<labelList>& patchFaceCells, const word& fluxScheme, const word& reconstructRho,
+                             const word& reconstructU, const word& reconstructT, const geometry& g)
+    : addr_(addr), g_(g), rPsi_(addr.size()), c_(addr.size()), brPsi_(g.bMagSf.size()), bc_(g.bMagSf.size()), ssf_(g.magSf.size()),
+      gradRho_(addr.size()), gradRPsi_(addr.size()), gradE_(addr.size()), gradC_(addr.size()), gradRhoU0_(addr.size()), gradRhoU1_(addr.size()),
+      gradRhoU2_(addr.size()), phi_(g.magSf.size()), phiEp_(g.magSf.size()), amaxSf_(g.magSf.size()), bphi_(g.bMagSf.size()), bphiEp_(g.bMagSf.size()),
+      bamaxSf_(g.bMagSf.size()), phiUp_(g.magSf.size()), bphiUp_(g.bMagSf.size())
+{
+    miCheck(mi_central_scheme_parse(fluxScheme.c_str(), reconstructRho.c_str(), reconstructU.c_str(), reconstructT.c_str(), &scheme_), "readFluxScheme.H");
+    if (!scheme_.U.vector_form) FatalErrorIn("centralFluxes::centralFluxes", "reconstruct(U) must be a V scheme here: a scalar scheme limits on magSqr(rhoU), the caller's field");
+    label nb = 0;
+    for (const labelList& fc : patchFaceCells) { patches_.emplace_back(new fvPatchCells(addr.size(), fc)); nb += (label)fc.size(); }
+    if (nb != g.bMagSf.size() || g.bSf.size() != nb || g.bDeltaCoeffs.size() != nb) FatalErrorIn("centralFluxes::centralFluxes", "the boundary geometry does not match the patches");
+}
+// fvc::grad, Gauss linear: the boundary faces add Sf_b*vf_b to their cells patch by patch before the division by V (gaussGrad.C:143-250)
+void centralFluxes::grad(vectorgpuField& g, const scalargpuField& vf, const scalargpuField& bvf)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    miCheck(mi_face_interpolate(addr_.handle(), g_.weights.data(), vf.data(), ssf_.data()), "fvc::interpolate");
+    miCheck(mi_gauss_grad(addr_.handle(), g_.Sf.c[0].data(), g_.Sf.c[1].data(), g_.Sf.c[2].data(), ssf_.data(), nullptr, g.c[0].data(), g.c[1].data(),
+                          g.c[2].data()), "fvc::grad");
+    for (direction d = 0; d < 3; ++d) {
+        label off = 0;
+        for (const auto& p : patches_) {
+            if (p->size()) miCheck(mi_patch_add_product(p->handle(), g_.bSf.c[d].data() + off, bvf.data() + off, g.c[d].data(), 0), "fvc::grad");
+            off += p->size();
+        }
+        miCheck(mi_vec_div(ctx, g.size(), g.c[d].data(), g_.V.data(), g.c[d].data()), "fvc::grad");
+    }
+}
+void centralFluxes::update(const volFields& v, const volFields& b)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const label n = addr_.size(), nb = g_.bMagSf.size();
+    miCheck(mi_central_sound_speed(ctx, n, v.Cp.data(), v.Cv.data(), v.psi.data(), rPsi_.data(), c_.data()), "rhoCentralFoam.C:84,116");
+    if (nb) miCheck(mi_central_sound_speed(ctx, nb, b.Cp.data(), b.Cv.data(), b.psi.data(), brPsi_.data(), bc_.data()), "rhoCentralFoam.C:84,116");
+    grad(gradRho_, v.rho, b.rho); grad(gradRPsi_, rPsi_, brPsi_); grad(gradE_, v.e, b.e); grad(gradC_, c_, bc_);
+    vectorgpuField* const gU[3] = {&gradRhoU0_, &gradRhoU1_, &gradRhoU2_};
+    for (direction d = 0; d < 3; ++d) grad(*gU[d], v.rhoU.c[d], b.rhoU.c[d]);
+    mi_central_cells cells{};
+    cells.rho_dev = v.rho.data(); cells.rpsi_dev = rPsi_.data(); cells.e_dev = v.e.data(); cells.c_dev = c_.data();
+    for (int k = 0; k < 3; ++k) {
+        cells.rhou_dev[k] = v.rhoU.c[k].data(); cells.grad_rho_dev[k] = gradRho_.c[k].data(); cells.grad_rpsi_dev[k] = gradRPsi_.c[k].data();
+        cells.grad_e_dev[k] = gradE_.c[k].data(); cells.grad_c_dev[k] = gradC_.c[k].data();
+        for (int j = 0; j < 3; ++j) cells.grad_rhou_dev[3 * j + k] = gU[j]->c[k].data();
+    }
+    mi_central_out out{};
+    out.phi_out_dev = phi_.data(); out.phiep_out_dev = phiEp_.data(); out.amaxsf_out_dev = amaxSf_.data();
+    for (int k = 0; k < 3; ++k) out.phiup_out_dev[k] = phiUp_.c[k].data();
+    const double* const sf[3] = {g_.Sf.c[0].data(), g_.Sf.c[1].data(), g_.Sf.c[2].data()};
+    const double* const cc[3] = {g_.C.c[0].data(), g_.C.c[1].data(), g_.C.c[2].data()};
+    miCheck(mi_central_flux(addr_.handle(), &scheme_, g_.weights.data(), sf, g_.magSf.data(), &cells, cc, &out), "rhoCentralFoam.C:62-185");
+    label off = 0;
+    for (const auto& p : patches_) {                          // the boundary value is the face value of both directions
+        mi_central_cells vals{};
+        vals.rho_dev = b.rho.data() + off; vals.rpsi_dev = brPsi_.data() + off; vals.e_dev = b.e.data() + off; vals.c_dev = bc_.data() + off;
+        mi_central_out po{};
+        po.phi_out_dev = bphi_.data() + off; po.phiep_out_dev = bphiEp_.data() + off; po.amaxsf_out_dev = bamaxSf_.data() + off;
+        const double* psf[3];
+        for (int k = 0; k < 3; ++k) { vals.rhou_dev[k] = b.rhoU.c[k].data() + off; po.phiup_out_dev[k] = bphiUp_.c[k].data() + off; psf[k] = g_.bSf.c[k].data() + off; }
+        miCheck(mi_patch_central_flux(p->handle(), &scheme_, nullptr, psf, g_.bMagSf.data() + off, &vals, nullptr, nullptr, &po), "rhoCentralFoam.C:62-185");
+        off += p->size();
+    }
+}
+void centralFluxes::CourantNo(scalar deltaT, scalar sumMagSf, scalar& CoNum, scalar& meanCoNum) const
+{
+    scalar mx = 0.0, sm = 0.0;
+    miCheck(mi_central_courant(addr_.handle(), g_.deltaCoeffs.data(), g_.magSf.data(), amaxSf_.data(), g_.bMagSf.size(), g_.bDeltaCoeffs.data(),
+                               g_.bMagSf.data(), bamaxSf_.data(), &mx, &sm), "compressibleCourantNo.H");
+    CoNum = 0.5 * mx * deltaT;
+    meanCoNum = 0.5 * (sm / sumMagSf) * deltaT;
+}
+void centralFluxes::solveDdtDiv(scalargpuField& vf, scalar rDeltaT, const scalargpuField& flux, const scalargpuField& bflux)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const label n = addr_.size();
+    scalargpuField diag(n), source(n), dv(n);
+    miCheck(mi_fvm_ddt_euler(ctx, n, rDeltaT, 1.0, g_.V.data(), vf.data(), diag.data(), source.data()), "fvm::ddt");
+    miCheck(mi_surface_integrate(addr_.handle(), flux.data(), nullptr, dv.data()), "fvc::div");
+    label off = 0;
+    for (const auto& p : patches_) {
+        if (p->size()) miCheck(mi_patch_add(p->handle(), bflux.data() + off, dv.data(), 0), "fvc::div");
+        off += p->size();
+    }
+    miCheck(mi_vec_div(ctx, n, dv.data(), g_.V.data(), dv.data()), "fvc::div");
+    miCheck(mi_vec_submul(ctx, n, g_.V.data(), dv.data(), source.data()), "fvMatrix + volField");
+    miCheck(mi_vec_div(ctx, n, source.data(), diag.data(), vf.data()), "fvMatrix::solve");
+}
 
 } // namespace Foam
