@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- PCG iterations/s + HBM GB/s on the 10M-cell lduMatrix (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one full PCG iteration of the reference's loop (PCG.C:133-204: precondition,
 gSumProd, p update, Amul, gSumProd, psi/r update, gSumMag) on the 216^3 hex-box pressure
@@ -11,7 +11,12 @@ one process per GPU, halo exchange + global sums on RCCL).
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel, lduMatrix::Amul
 (tile_kernel<OP_AMUL>): algorithmic bytes 24N+16F per launch / its average launch duration,
-measured with HIP events on the engine's stream inside the timed region.  `cpu_baseline` is
+measured with HIP events on the engine's stream inside the timed region.
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds every measurement that takes runs of its own, beside `value` and never part of it: `cpu_baseline`, the Amul alone
+over rotating buffers, `config.supplements` (configs 3 and 4/5), the weak-scaling supplement of N > 1, and in `--solver gamg`
+the solve to convergence.  --no-cpu / --no-supplements take single legs out of a --full run.  `cpu_baseline` is
 upstream OpenFOAM's CPU lduMatrix path as it runs on the node (one rank per host core over a slab decomposition,
 face-loop Amul, diagonal PCG; oracle/baseline_oracle.c) timed on a bounded sample of the same workload.
 """
@@ -160,9 +165,12 @@ def bench_gamg(args, eng, syn, ctx, dev, json_fd):
     levels = [(G.level_sizes(l)["n_coarse"], G.level_sizes(l)["n_coarse_faces"]) for l in range(G.n_levels)]
     ctl = dict(nPostSweeps=2, postSweepsLevelMultiplier=1, maxPostSweeps=4, nFinestSweeps=2)
     alg = gamg_cycle_bytes(levels, N, F, ctl)
-    # to convergence, next to diagonal PCG (what the multigrid buys)
-    psi.zero_(); torch.cuda.synchronize(); t0 = time.perf_counter()
-    pc = G.solve(mat, psi, src, tolerance=1e-6, maxIter=200); torch.cuda.synchronize(); t_conv = time.perf_counter() - t0
+    to_conv = None
+    if args.full:                         # to convergence, next to diagonal PCG (what the multigrid buys)
+        psi.zero_(); torch.cuda.synchronize(); t0 = time.perf_counter()
+        pc = G.solve(mat, psi, src, tolerance=1e-6, maxIter=200); torch.cuda.synchronize(); t_conv = time.perf_counter() - t0
+        to_conv = {"cycles": pc["nIterations"], "seconds": t_conv}
+    traffic = gamg_traffic_from_profile(nx, ny, nz)
     out = {
         "metric": "PCG iterations/s + HBM GB/s on 10M-cell lduMatrix at 1/2/4/8 MI355X",
         "value": K / elapsed, "unit": "V-cycles/s", "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K,
@@ -173,12 +181,12 @@ def bench_gamg(args, eng, syn, ctx, dev, json_fd):
                    "solver": "GAMG", "cells": N, "faces": F, "levels": [n for n, _ in levels],
                    "timing": f"median of {R} repeats of mi_gamg_solve with {K} V-cycles each (tolerance 0; the solve's prologue -- Amul, normFactor -- is inside the clock)",
                    "repeat_ms_per_step": [1e3 * x / K for x in rep_s],
-                   "solve_to_1e-6": {"cycles": pc["nIterations"], "seconds": t_conv}},
+                   "solve_to_1e-6": to_conv},
         "roofline": {"kernel": "whole V-cycle (tile_kernel<OP_JACOBI> / <OP_AMUL> on every level + transfer and scaling passes)", "bound": "hbm",
                      "achieved": alg / (elapsed / K) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg / (elapsed / K) / 1e9 / HBM_PEAK_GBS,
-                     "algorithmic_bytes_per_cycle": alg, "traffic": gamg_traffic_from_profile(nx, ny, nz),
+                     "algorithmic_bytes_per_cycle": alg, "traffic": traffic,
                      "traffic_unit": "bytes per V-cycle (rocprofv3 PMC: FETCH_SIZE x 2 + WRITE_SIZE over all dispatches, 25-cycle minus 5-cycle solve; profiles/r03_g_gamg_cycle_traffic.json)"
-                                     if gamg_traffic_from_profile(nx, ny, nz) is not None else "not measured for this configuration"},
+                                     if traffic is not None else "not measured for this configuration"},
     }
     os.write(json_fd, (json.dumps(out) + "\n").encode())
 
@@ -222,7 +230,7 @@ def negotiate_peer_path(solver, make_solver, trial, persist_launches, all_ok, an
     return solver, note
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -230,14 +238,22 @@ def main():
     ap.add_argument("--dims", type=int, nargs=3, default=[216, 216, 216])
     ap.add_argument("--precond", default="diagonal")
     ap.add_argument("--cpu-iters", type=int, default=int(os.environ.get("MI_BENCH_CPU_ITERS", "0")))  # 0: about 10 s
-    ap.add_argument("--no-cpu", action="store_true")
+    # everything the benchmark measures besides the headline figure (module docstring); off: a plain run is set-up, warm-up, timed steps, line
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true")            # with --full: without the cpu_baseline leg
     ap.add_argument("--repeats", type=int, default=5)   # median of 5 repeats of the timed region
     ap.add_argument("--solver", choices=["pcg", "gamg"], default="pcg")   # gamg: BASELINE config 3 (a second mode, 1 GPU; a step = one V-cycle)
-    ap.add_argument("--no-supplements", action="store_true")   # skip config.supplements (configs 3 and 4/5 on the same box, N = 1 only)
+    ap.add_argument("--no-supplements", action="store_true")   # with --full: without config.supplements (configs 3 and 4/5 on the same box)
     # after the timed steps: the solution (a fixed sample of its cells past 2^21) and the residual history the timed solve produced,
     # as DIR/<name>.npy (float64, < 64 MB); the ranks of a decomposed run write their sub-domain's solution as psi_rank<r>
     ap.add_argument("--dump-outputs", metavar="DIR", default=None)
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = make_parser().parse_args()
+    want_cpu = args.full and not args.no_cpu
+    want_supplements = args.full and not args.no_supplements and not os.environ.get("MI_BENCH_NO_SUPPLEMENTS")
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: become the launcher (one rank per GPU, as the driver's
     # `python -m torch.distributed.run --nproc-per-node N ... bench.py` does) instead of silently measuring one GPU
@@ -299,7 +315,7 @@ def main():
     force_dist = bool(os.environ.get("MI_BENCH_FORCE_DIST"))  # exercise the N>1 code path on one GPU
     single = world == 1 and not force_dist
     # N = 1: the whole case (the CPU baseline needs it too); N > 1: every rank builds only its own sub-domain
-    case = syn.box_case(nx, ny, nz) if (single or (rank == 0 and not args.no_cpu and world == 1)) else None
+    case = syn.box_case(nx, ny, nz) if (single or (rank == 0 and want_cpu and world == 1)) else None
     if rank == 0:
         log(f"[bench] case {nx}x{ny}x{nz}: N={N} F={F} built in {time.perf_counter() - t0:.1f}s")
 
@@ -356,26 +372,27 @@ def main():
             path_taken = "single-gpu pipeline, fused residual / direction update (csrc/pcg_fused.inc)"
         assert np.all(np.isfinite(perf["history"])) and perf["history"][-1] < perf["history"][0]
         n_amul_cells, n_amul_faces = N, F
-        # Amul alone, out of the solver loop: rotating vectors (4 input/output pairs = 645 MB > the 256 MiB Infinity Cache),
-        # so that no sample finds its vectors on-die; kernel-bracketing events on the engine's stream
-        nrot, nl = 4, 40
-        xs = [torch.full((N,), 1.0 + 0.1 * i, dtype=torch.float64, device=dev) for i in range(nrot)]
-        ys = [torch.empty(N, dtype=torch.float64, device=dev) for _ in range(nrot)]
-        for i in range(nrot):
-            mat.amul_engine(xs[i], ys[i])
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        samples = []
-        for _ in range(R):
-            torch.cuda.synchronize(); e0.record()
-            for i in range(nl):
-                mat.amul_engine(xs[i % nrot], ys[i % nrot])
-            e1.record(); torch.cuda.synchronize()
-            samples.append(e0.elapsed_time(e1) * 1e3 / nl)
-        amul_alone_us = float(np.median(samples))
-        del xs, ys
-        # BASELINE configs 3 and 4/5 on the same box, reported beside `value` (never part of it): the driver's record then carries
+        if args.full:
+            # Amul alone, out of the solver loop: rotating vectors (4 input/output pairs = 645 MB > the 256 MiB Infinity Cache),
+            # so that no sample finds its vectors on-die; kernel-bracketing events on the engine's stream
+            nrot, nl = 4, 40
+            xs = [torch.full((N,), 1.0 + 0.1 * i, dtype=torch.float64, device=dev) for i in range(nrot)]
+            ys = [torch.empty(N, dtype=torch.float64, device=dev) for _ in range(nrot)]
+            for i in range(nrot):
+                mat.amul_engine(xs[i], ys[i])
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            samples = []
+            for _ in range(R):
+                torch.cuda.synchronize(); e0.record()
+                for i in range(nl):
+                    mat.amul_engine(xs[i % nrot], ys[i % nrot])
+                e1.record(); torch.cuda.synchronize()
+                samples.append(e0.elapsed_time(e1) * 1e3 / nl)
+            amul_alone_us = float(np.median(samples))
+            del xs, ys
+        # BASELINE configs 3 and 4/5 on the same box, reported beside `value` (never part of it): a --full record then carries
         # the GAMG cycle rate and the cost of a whole time step as well (VERDICT r02 "missing" 3, 6)
-        if not args.no_supplements and not os.environ.get("MI_BENCH_NO_SUPPLEMENTS"):
+        if want_supplements:
             try:
                 t0 = time.perf_counter()
                 sup_gamg, G = workloads.gamg_supplement(eng, case, addr, mat, dev)
@@ -490,7 +507,7 @@ def main():
         # supplement (not `value`): the same solver with the per-GPU work held at the N = 1 size (weak scaling;
         # at 8 GPUs this is the 80 M-cell box of BASELINE config 5), so that the latency-bound strong-scaling number
         # above can be read beside the regime the halo/all-reduce overlap is designed for
-        if world > 1 or os.environ.get("MI_BENCH_WEAK"):
+        if args.full and (world > 1 or os.environ.get("MI_BENCH_WEAK")):
             px, py, pz = parts_for(world)
             del solver
             wsub = syn.box_subdomain((nx * px, ny * py, nz * pz), (px, py, pz), rank)
@@ -517,7 +534,7 @@ def main():
             # configs 3 / 4 / 5 as decomposed workloads (round 4): GAMG V-cycles and a whole time step per rank, attached
             # matrices, on the weak sub-domain (216^3 per rank: at 8 GPUs the 80 M-cell box of config 5) and GAMG also on the
             # strong share of the 10 M-cell box.  Never part of `value`.
-            if not args.no_supplements and not os.environ.get("MI_BENCH_NO_SUPPLEMENTS") and ws.comms is not None:
+            if want_supplements and ws.comms is not None:
                 def rmax(v):
                     if world == 1:
                         return float(v)
@@ -588,7 +605,7 @@ def main():
         },
     }
     if rank == 0:
-        if not args.no_cpu and world == 1:
+        if want_cpu and world == 1:
             if case is None:
                 case = syn.box_case(nx, ny, nz)
             v, n_it, dt, cores = cpu_baseline(case, syn, args.cpu_iters)

@@ -20,9 +20,9 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _check(line, n):
+def _check(line, n, full=True):
     d = json.loads(line)
-    assert KEYS - ({"cpu_baseline"} if n > 1 else set()) <= set(d), set(d) ^ KEYS      # the CPU leg runs at N = 1 only
+    assert KEYS - ({"cpu_baseline"} if n > 1 or not full else set()) <= set(d), set(d) ^ KEYS      # the CPU leg runs at N = 1 only, under --full
     assert d["n_gpus"] == n and d["steps"] == 12 and d["warmup"] == 3 and d["value"] > 0 and d["higher_is_better"] is True
     assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3
     assert d["dtype"] == "f64" and d["data"] == "synthetic" and "workload" in d["config"]
@@ -40,14 +40,31 @@ def _run_with_port(make_cmd, env, attempts=4):
             return out
 
 
+def test_plain_single_gpu_line():
+    """without --full: set-up, warm-up, the timed steps and the line -- the same headline keys, none of the measurements that take
+    runs of their own (CPU leg, Amul alone, supplements)"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--dims", "40", "32", "24"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout                       # ONE JSON line on stdout, everything else on stderr
+    d = _check(lines[0], 1, full=False)
+    assert d["metric"].startswith("PCG iterations/s") and d["unit"] == "iterations/s"
+    assert d["config"]["timing"].startswith("median of 5 repeats") and len(d["config"]["repeat_ms_per_step"]) == 5
+    assert d["roofline"]["avg_launch_us"] > 0                # the Amul events of the timed region stay
+    assert "cpu_baseline" not in d and d["config"]["supplements"] is None and d["config"]["weak_scaling_supplement"] is None
+    assert d["config"]["amul_alone_us_rotating_buffers"] is None and d["config"]["amul_alone_frac_of_peak"] is None
+
+
 def test_single_gpu_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--dims", "40", "32", "24", "--cpu-iters", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "3", "--dims", "40", "32", "24", "--cpu-iters", "5"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout                       # ONE JSON line on stdout, everything else on stderr
     d = _check(lines[0], 1)
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["cores"] >= 1
+    assert d["config"]["amul_alone_us_rotating_buffers"] > 0 and 0 < d["config"]["amul_alone_frac_of_peak"] < 1
     # configs 3 and 4/5 ride in the same line as supplements (never in `value`)
     sup = d["config"]["supplements"]
     assert "error" not in sup, sup
@@ -80,7 +97,7 @@ def test_gamg_mode_line():
 def test_multi_rank_rehearsal_over_gloo(n):
     env = dict(os.environ, MI_BENCH_BACKEND="gloo", MI_BENCH_DECOMP_CYCLES="3", MI_BENCH_DECOMP_STEPS="1")   # (ranks share ONE GPU here: short supplements)
     make = lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "12", "--warmup", "3",
+                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", "12", "--warmup", "3",
            "--dims", "40", "32", "24", "--no-cpu"]
     out = _run_with_port(make, env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -99,7 +116,7 @@ def test_two_rank_rehearsal_with_peer_windows_and_the_persistent_kernel():
     env = dict(os.environ, MI_BENCH_BACKEND="gloo", MI_DPCG_DRIVER="native", MI_COMM_TRANSPORT="host", MI_PERSIST_SHARED="1", MI_PERSIST_GRID="96", MI_PEER_POLLS="3000000",
                MI_BENCH_DECOMP_CYCLES="3", MI_BENCH_DECOMP_STEPS="1")     # (two processes on one GPU: a scheduling quantum per exchange -- short supplements)
     make = lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3",
+                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "12", "--warmup", "3",
            "--dims", "96", "64", "48", "--no-cpu"]
     out = _run_with_port(make, env)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -29,6 +29,17 @@ def test_field_sample_is_fixed_and_within_budget(tmp_path):
     assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
 
 
+def test_full_is_an_option_and_off_by_default():
+    """a plain `--gpus 1 --steps N --warmup W` run asks for none of the extra measurements; --full asks for them, and the options
+    that take single legs out of a --full run are still understood"""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.make_parser().parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup, plain.repeats, plain.dump_outputs) == (1, 20, 5, 5, None)
+    full = bench.make_parser().parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--no-supplements"])
+    assert full.full is True and full.no_cpu and full.no_supplements and (full.steps, full.warmup, full.repeats) == (20, 5, 5)
+
+
 @pytest.mark.gpu
 def test_dump_outputs_repeat_bit_for_bit(tmp_path):
     steps, warmup, repeats = 7, 2, 3

@@ -1,5 +1,5 @@
 """One PISO-like time step on the 216^3 box, the per-rank workload of BASELINE configs 4 / 5 on ONE MI355X (tools/workloads.py:
-timestep_supplement; bench.py reports the same measurement as config.supplements.timestep_216).
+timestep_supplement; bench.py --full reports the same measurement as config.supplements.timestep_216).
    DIMS=216,216,216 STEPS=5 [MI_TIMESTEP_SEGREGATED=1] python tools/bench_timestep.py"""
 import json, os, sys
 import torch

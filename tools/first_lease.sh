@@ -41,7 +41,7 @@ echo "[first_lease] window tests, one device per rank: rc=$? ($(tail -n 1 $O/tes
 run_bench() {  # N path env...
   local N=$1 P=$2; shift 2
   env "$@" timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29700 + N)) \
-      bench.py --gpus $N --steps 200 --warmup 10 > $O/bench_${N}_${P}.json 2> $O/bench_${N}_${P}.err
+      bench.py --full --gpus $N --steps 200 --warmup 10 > $O/bench_${N}_${P}.json 2> $O/bench_${N}_${P}.err
   echo "[first_lease] bench --gpus $N path=$P rc=$?" | tee -a $O/selftests.log
 }
 for N in 2 4 8; do

@@ -1,4 +1,4 @@
-"""The BASELINE workloads beyond config 2 as callable measurements (bench.py appends them to its JSON line as
+"""The BASELINE workloads beyond config 2 as callable measurements (bench.py --full appends them to its JSON line as
 `config.supplements`; tools/bench_timestep.py and tools/bench_gamg.py print them on their own):
 
   gamg_supplement      config 3: GAMG pressure solve on the 10 M-cell box (V-cycles/s, fraction of the HBM roofline on the
