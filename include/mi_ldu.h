@@ -938,7 +938,7 @@ int mi_near_interface(mi_ctx_t ctx, int64_t n, const double *alpha_dev, double *
  *   a lower bound that is not a number.
  *   mi_min_max during a PCG session: MI_ERR_STATE.  Zero cells, zero wall faces and zero wall patches: MI_OK.
  * Out of scope: the wall-distance field itself (wallDist / meshWave: kOmegaSST, below, takes y as the caller's cell array); the low-Re and rough wall functions;
- *   the nutU* wall functions; the weighted (weights) forms of the epsilon wall function; compressible kEpsilon (rho-weighted); LES models;
+ *   the nutU* wall functions; the weighted (weights) forms of the epsilon wall function; compressible kEpsilon (rho-weighted);
  *   a pisoFoam / simpleFoam application; moving meshes; nearWallDist (y is the caller's patch array). */
 typedef struct mi_ke_coeffs {
     double Cmu, C1, C2, sigmaEps, kappa, E;
@@ -1238,6 +1238,87 @@ int mi_central_sound_speed(mi_ctx_t ctx, int64_t n, const double *cp_dev, const 
 int mi_central_courant(mi_addr_t addr, const double *delta_coeffs_dev, const double *mag_sf_dev, const double *amaxsf_dev,
                        int64_t n_boundary, const double *b_delta_coeffs_dev, const double *b_mag_sf_dev, const double *b_amaxsf_dev,
                        double *max_out_host, double *sum_out_host);
+/* ---- the LES models Smagorinsky, oneEqEddy and dynOneEqEddy with cubeRootVolDelta and the simpleFilter
+ *      (turbulenceModels/incompressible/LES/Smagorinsky/Smagorinsky.C:45-49, Smagorinsky.H:117-120; oneEqEddy/oneEqEddy.C:46-50, :100-122,
+ *      oneEqEddy.H:132; dynOneEqEddy/dynOneEqEddy.C:45-100, :134-137, :145-172; GenEddyVisc/GenEddyVisc.C:61;
+ *      turbulenceModels/LES/LESfilters/simpleFilter/simpleFilter.C:64-125; LES/LESdeltas/cubeRootVolDelta/cubeRootVolDelta.C:42-76;
+ *      LES/LESdeltas/LESdelta/LESdelta.C:53) ----
+ * One correct() of dynOneEqEddy calls an LESfilter thirteen times inside about thirty field operators, roughly a hundred field passes; here it
+ * is four cell passes and five row passes, beside the k equation's assembly, relaxation, solve and mi_bound.  The rules of the kEpsilon block
+ * hold: fp64 values, int32 labels, every operator rounded on its own except the fma written below, IEEE / and sqrt, max(a, b) = (a > b) ? a : b,
+ * mag = fabs, the face order of mi_fvc_average.  A symmetric tensor is six arrays in the order xx, xy, xz, yy, yz, zz; grad_dev is
+ * mi_ke_production's layout.  SMALL = 1e-15, VSMALL = 1e-300.  Field operators of the reference are separate passes over stored fields, so
+ * nothing is contracted ACROSS them (fSqrU - sqr(fU) is a rounded product, then a subtraction); inside one primitive operator:
+ *   dev(st)   (SymmTensorI.H:326-329): t = (1.0/3.0)*((xx + yy) + zz); xx - t, yy - t, zz - t: no fma (the product has three uses)
+ *   a && b    (SymmTensorI.H:233-241): s = fma(a.xx, b.xx, (2*a.xy)*b.xy); s = fma(2*a.xz, b.xz, s); s = fma(a.yy, b.yy, s);
+ *             s = fma(2*a.yz, b.yz, s); s = fma(a.zz, b.zz, s)
+ *   magSqr(v) (VectorSpaceI.H:336-344): fma(v.z, v.z, fma(v.x, v.x, v.y*v.y))
+ *   magSqr(st): the chain stated for mi_ke_production
+ *   read from LLVM's contraction of these expressions (an ASSUMPTION for the device compiler).
+ * mi_les_simple_filter (simpleFilter.C:64-125) on a mi_average_t: out_k = surfaceSum(magSf*interpolate(vf_k))/surfaceSum(magSf) for
+ *   k < n_cmpt, 1 <= n_cmpt <= 9 (nine: a volTensorField), in ONE row pass that writes no face field.  Per face, for component k:
+ *     i = fma(lambda, P_k - N_k, N_k);  p = magSf*i (rounded);  s_k = s_k + p
+ *   own faces ascending, neighbour-side faces in losort order, then the boundary faces patch by patch with p = b_magSf*b_face_k;
+ *   out_k[c] = s_k/sum[c]: ONE DIVISION PER COMPONENT -- VectorSpace's operator/(vs, scalar) (VectorSpaceI.H:621-630) applies divideOp3,
+ *   `x / y` (ops.H:208), to every component; it does not multiply by a reciprocal.  A cell without faces gives 0/0.  b_face_dev[k]: the
+ *   patch-ordered boundary face values of the UNFILTERED field, the caller's: its boundary values on a non-coupled patch,
+ *   w*P + (1 - w)*Nbr on a coupled one.  The filtered field's own boundary values are zero-gradient (fvcSurfaceIntegrate.C:285):
+ *   mi_patch_internal_field.  Only the first n_cmpt pointers of vf_dev, b_face_dev and out_dev are read.
+ * mi_les_delta_cube_root_vol (cubeRootVolDelta.C:48, :68): thickness_or_0 == 0: out = deltaCoeff*pow(V, 1.0/3.0), the device library's pow,
+ *   not cbrt; thickness_or_0 > 0 (a 2-D case): out = deltaCoeff*sqrt(V/thickness).  pow_out_dev_or_null receives the root (for tests).
+ *   delta's BOUNDARY values stay the constructor's SMALL (LESdelta.C:53: calculated patches, calcDelta sets the internal field only): the
+ *   boundary array is the caller's, filled with SMALL.
+ * mi_les_coeffs_init (host only): ck and ce, the reference's defaults 0.094 (Smagorinsky.C:72, oneEqEddy.C:86) and 1.048 (GenEddyVisc.C:61);
+ *   a non-finite or non-positive member is refused, here and by every entry that takes a mi_les_coeffs.
+ * mi_les_smagorinsky (Smagorinsky.H:119, Smagorinsky.C:47): k = (((2.0*ck)/ce)*(delta*delta))*magSqr(dev(symm(gradU))), (2.0*ck)/ce formed on
+ *   the host; nuSgs = (ck*delta)*sqrt(k).
+ * mi_les_k_terms (oneEqEddy.C:104-113, dynOneEqEddy.C:154-163, oneEqEddy.H:132): G = (2.0*nuSgs)*magSqr(symm(gradU)) through the device
+ *   function of mi_ke_production, hence with its bits for nut = nuSgs; sp = (ce*sqrt(k))/delta with ce the number, or per cell when
+ *   ce_dev_or_null is given (the dynamic model); dk = nuSgs + nu, nu a cell array or nu_value.  G and sp are mi_fvm_assemble's su_dev and sp_dev.
+ * mi_les_nusgs (oneEqEddy.C:48, dynOneEqEddy.C:51): out = (ck*sqrt(k))*delta, ck the number or per cell.
+ * The dynamic procedure (dynOneEqEddy.C:56-100, :136, :151-152).  Every cell pass is a per-element map without neighbour access: run over
+ *   the patch-ordered boundary arrays it gives the boundary values of its outputs on non-coupled patches, as the reference's field algebra
+ *   forms them.  With delta_b = SMALL, MM_b all but vanishes and ce_den_b is enormous: the reference's result, replicated.
+ *   mi_les_dyn_moments: sqr(U) (SymmTensorI.H:546-554), magSqr(U), D = symm(gradU) (0.5*(a + b) off the diagonal), magSqr(D).
+ *   level 1 (filter_): U (3), sqr(U) (6), magSqr(U), D (6), magSqr(D): 17 components in two mi_les_simple_filter launches (9 + 8).
+ *   mi_les_dyn_level1: KK = 0.5*(fMagSqrU - magSqr(fU)), with clip != 0 then KK = max(KK, SMALL) (correct() :152 clips, the constructor :136
+ *     does not); LL = dev(a) with a_ij = fSqrU_ij - fU_i*fU_j; MM = ((-2.0*delta)*sqrt(KK))*fD; ce_num = nuEff*(fMagSqrD - magSqr(fD));
+ *     ce_den = pow(KK, 1.5)/(2.0*delta), the device library's pow evaluated once; pow_out_dev_or_null receives it (for tests).
+ *   level 2 (simpleFilter_): LL, MM, ce_num, ce_den: 14 components in two launches.
+ *   mi_les_dyn_level2: lm = 0.5*(fLL && fMM); mmmm = magSqr(fMM).   level 3: lm and mmmm, one launch of 2 components.
+ *   mi_les_dyn_coeffs (:72-99): c = f_lm/(f_mmmm + VSMALL), ck = 0.5*(mag(c) + c); e = f_ce_num/f_ce_den, ce = 0.5*(mag(e) + e).
+ * The cell passes take two cells per thread with 16-byte accesses when every array is 16-byte aligned, one by one otherwise, under the
+ *   context's launch-grid cap (MI_FACE_GRID).
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): n_cmpt outside 1..9; a missing array; an output that aliases an input or another
+ *   output (reported before alignment, as mi_fvc_average does); an array not aligned for a double; NULL boundary arrays while the boundary
+ *   has faces; a handle of another addressing; a coefficient that is not finite or not above zero.  Zero cells: MI_OK.
+ * Out of scope: laplaceFilter and anisotropicFilter; vanDriestDelta, smoothDelta, maxDeltaxyz and PrandtlDelta (they need the wall distance
+ *   or face geometry); the homogeneous dynamic models (their average() fixes a reduction order); the Spalart-Allmaras DES family; the nuSgs
+ *   wall functions; compressible LES; a pisoFoam application; moving meshes. */
+typedef struct mi_les_coeffs {
+    double ck, ce;
+} mi_les_coeffs;
+int mi_les_coeffs_init(double ck, double ce, mi_les_coeffs *out);
+int mi_les_simple_filter(mi_average_t average, int n_cmpt, const double *lambda_dev, const double *mag_sf_dev, const double *b_mag_sf_dev,
+                         const double *const *vf_dev, const double *const *b_face_dev, double *const *out_dev);
+int mi_les_delta_cube_root_vol(mi_ctx_t ctx, int64_t n, double delta_coeff, double thickness_or_0, const double *v_dev, double *out_dev,
+                               double *pow_out_dev_or_null);
+int mi_les_smagorinsky(mi_ctx_t ctx, int64_t n, const mi_les_coeffs *coeffs, const double *delta_dev, const double *const *grad_dev,
+                       double *k_out_dev_or_null, double *nusgs_out_dev);
+int mi_les_k_terms(mi_ctx_t ctx, int64_t n, double ce, const double *ce_dev_or_null, const double *nusgs_dev, const double *const *grad_dev,
+                   const double *k_dev, const double *delta_dev, const double *nu_dev_or_null, double nu_value, double *g_out_dev,
+                   double *sp_out_dev, double *dk_out_dev);
+int mi_les_nusgs(mi_ctx_t ctx, int64_t n, double ck, const double *ck_dev_or_null, const double *k_dev, const double *delta_dev, double *out_dev);
+int mi_les_dyn_moments(mi_ctx_t ctx, int64_t n, const double *const *u_dev, const double *const *grad_dev, double *const *sqr_u_out_dev,
+                       double *magsqr_u_out_dev, double *const *d_out_dev, double *magsqr_d_out_dev);
+int mi_les_dyn_level1(mi_ctx_t ctx, int64_t n, int clip, const double *delta_dev, const double *nueff_dev, const double *const *f_u_dev,
+                      const double *const *f_sqr_u_dev, const double *f_magsqr_u_dev, const double *const *f_d_dev,
+                      const double *f_magsqr_d_dev, double *kk_out_dev, double *const *ll_out_dev, double *const *mm_out_dev,
+                      double *ce_num_out_dev, double *ce_den_out_dev, double *pow_out_dev_or_null);
+int mi_les_dyn_level2(mi_ctx_t ctx, int64_t n, const double *const *f_ll_dev, const double *const *f_mm_dev, double *lm_out_dev,
+                      double *mmmm_out_dev);
+int mi_les_dyn_coeffs(mi_ctx_t ctx, int64_t n, const double *f_lm_dev, const double *f_mmmm_dev, const double *f_ce_num_dev,
+                      const double *f_ce_den_dev, double *ck_out_dev, double *ce_out_dev);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

@@ -2511,6 +2511,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "turbulence.inc"
 #include "thermo.inc"
 #include "central.inc"
+#include "les.inc"
 
 mi_matrix_s::~mi_matrix_s()
 {

@@ -94,6 +94,8 @@ SYMBOLS = [
     "mi_sst_coeffs_init", "mi_sst_production", "mi_sst_wall_cells", "mi_sst_blend", "mi_sst_omega_sources", "mi_sst_k_terms", "mi_sst_nut",
     "mi_thermo_model_init", "mi_thermo_calculate", "mi_thermo_calculate_boundary", "mi_thermo_he", "mi_thermo_property",
     "mi_central_scheme_parse", "mi_central_flux", "mi_patch_central_flux", "mi_central_sound_speed", "mi_central_courant",
+    "mi_les_coeffs_init", "mi_les_simple_filter", "mi_les_delta_cube_root_vol", "mi_les_smagorinsky", "mi_les_k_terms", "mi_les_nusgs",
+    "mi_les_dyn_moments", "mi_les_dyn_level1", "mi_les_dyn_level2", "mi_les_dyn_coeffs",
 ]
 
 
@@ -1519,6 +1521,18 @@ def ke_coeffs(Cmu=0.09, C1=1.44, C2=1.92, sigmaEps=1.3, kappa=0.41, E=9.8) -> Ke
     return out
 
 
+class LesCoeffs(C.Structure):
+    """mi_les_coeffs (include/mi_ldu.h)"""
+    _fields_ = [("ck", C.c_double), ("ce", C.c_double)]
+
+
+def les_coeffs(ck=0.094, ce=1.048) -> LesCoeffs:
+    """mi_les_coeffs_init: ck and ce of Smagorinsky / oneEqEddy (host only, no GPU)"""
+    out = LesCoeffs()
+    _chk(lib().mi_les_coeffs_init(C.c_double(ck), C.c_double(ce), C.byref(out)))
+    return out
+
+
 class KeWall(C.Structure):
     """mi_ke_wall (include/mi_ldu.h)"""
     _fields_ = [("k_dev", C.c_void_p), ("u_dev", C.c_void_p * 3), ("b_uw_dev", C.c_void_p * 3), ("b_delta_coeffs_dev", C.c_void_p),
@@ -1542,6 +1556,12 @@ class Average:
     def bound(self, lower_bound, lam, mag_sf, vsf_inout, b_mag_sf=None, b_face=None):
         """bound.C:45-54 on the internal field in one row pass (mi_bound): b_face the boundary values of linearInterpolate(max(vsf, lb))"""
         _chk(lib().mi_bound(self.h, C.c_double(lower_bound), _ptr(lam), _ptr(mag_sf), _ptr(b_mag_sf), _ptr(b_face), _ptr(vsf_inout)))
+
+    def les_simple_filter(self, lam, mag_sf, vf, out, b_mag_sf=None, b_face=None, n_cmpt=None):
+        """out[k] = surfaceSum(magSf*interpolate(vf[k]))/surfaceSum(magSf) for up to nine components in one row pass (mi_les_simple_filter):
+        vf, out and b_face lists of arrays (b_face the boundary face values of the unfiltered components); n_cmpt defaults to len(vf)"""
+        nc = next((len(x) for x in (vf, out, b_face) if x is not None), 0) if n_cmpt is None else n_cmpt
+        _chk(lib().mi_les_simple_filter(self.h, C.c_int(nc), _ptr(lam), _ptr(mag_sf), _ptr(b_mag_sf), _ptrs(vf, 9), _ptrs(b_face, 9), _ptrs(out, 9)))
 
     def close(self):
         if self.h:
@@ -2037,6 +2057,63 @@ class Assembly:
     def ke_nut_wall(self, ke, coeffs, k, b_y, b_nuw, b_nutw_out, b_log_out=None):
         """nutkWallFunction on every wall face over a KEpsilon handle of this addressing (mi_ke_nut_wall)"""
         ke.nut_wall(coeffs, k, b_y, b_nuw, b_nutw_out, b_log_out)
+
+    def les_simple_filter(self, average, lam, mag_sf, vf, out, b_mag_sf=None, b_face=None, n_cmpt=None):
+        """the simple filter of up to nine components over an Average handle of this addressing (mi_les_simple_filter)"""
+        average.les_simple_filter(lam, mag_sf, vf, out, b_mag_sf, b_face, n_cmpt)
+
+    def _les_n(self, *xs):
+        for x in xs:
+            if x is not None and not isinstance(x, (list, tuple)):
+                return x.numel()
+        for x in xs:
+            if isinstance(x, (list, tuple)):
+                for y in x:
+                    if y is not None:
+                        return y.numel()
+        return 0
+
+    def les_delta_cube_root_vol(self, delta_coeff, thickness, vol, out, pow_out=None):
+        """delta = deltaCoeff*pow(V, 1/3), or deltaCoeff*sqrt(V/thickness) with thickness > 0 (mi_les_delta_cube_root_vol)"""
+        _chk(lib().mi_les_delta_cube_root_vol(self.addr.ctx.h, C.c_int64(self._les_n(vol, out)), C.c_double(delta_coeff), C.c_double(thickness), _ptr(vol),
+                                              _ptr(out), _ptr(pow_out)))
+
+    def les_smagorinsky(self, coeffs, delta, grad, nusgs_out, k_out=None):
+        """Smagorinsky's k = (2ck/ce)*sqr(delta)*magSqr(dev(symm(gradU))) and nuSgs = ck*delta*sqrt(k) in one cell pass (mi_les_smagorinsky)"""
+        _chk(lib().mi_les_smagorinsky(self.addr.ctx.h, C.c_int64(self._les_n(delta, nusgs_out)), C.byref(coeffs) if coeffs is not None else None, _ptr(delta),
+                                      _ptrs(grad, 9), _ptr(k_out), _ptr(nusgs_out)))
+
+    def les_k_terms(self, ce, nusgs, grad, k, delta, nu, g_out, sp_out, dk_out):
+        """G = 2*nuSgs*magSqr(symm(gradU)), sp = ce*sqrt(k)/delta, dk = nuSgs + nu in one cell pass (mi_les_k_terms); ce and nu numbers or cell arrays"""
+        ce_dev, ce_value = (None, float(ce)) if isinstance(ce, (int, float)) else (ce, 0.0)
+        nu_dev, nu_value = (None, float(nu)) if isinstance(nu, (int, float)) else (nu, 0.0)
+        _chk(lib().mi_les_k_terms(self.addr.ctx.h, C.c_int64(self._les_n(k, nusgs, g_out)), C.c_double(ce_value), _ptr(ce_dev), _ptr(nusgs), _ptrs(grad, 9),
+                                  _ptr(k), _ptr(delta), _ptr(nu_dev), C.c_double(nu_value), _ptr(g_out), _ptr(sp_out), _ptr(dk_out)))
+
+    def les_nusgs(self, ck, k, delta, out):
+        """nuSgs = ck*sqrt(k)*delta (mi_les_nusgs); ck a number or a cell array"""
+        ck_dev, ck_value = (None, float(ck)) if isinstance(ck, (int, float)) else (ck, 0.0)
+        _chk(lib().mi_les_nusgs(self.addr.ctx.h, C.c_int64(self._les_n(k, delta, out)), C.c_double(ck_value), _ptr(ck_dev), _ptr(k), _ptr(delta), _ptr(out)))
+
+    def les_dyn_moments(self, u, grad, sqr_u_out, magsqr_u_out, d_out, magsqr_d_out):
+        """sqr(U), magSqr(U), D = symm(gradU) and magSqr(D) in one cell pass (mi_les_dyn_moments)"""
+        _chk(lib().mi_les_dyn_moments(self.addr.ctx.h, C.c_int64(self._les_n(magsqr_u_out, magsqr_d_out, u)), _ptrs(u, 3), _ptrs(grad, 9), _ptrs(sqr_u_out, 6),
+                                      _ptr(magsqr_u_out), _ptrs(d_out, 6), _ptr(magsqr_d_out)))
+
+    def les_dyn_level1(self, clip, delta, nueff, f_u, f_sqr_u, f_magsqr_u, f_d, f_magsqr_d, kk_out, ll_out, mm_out, ce_num_out, ce_den_out, pow_out=None):
+        """KK, LL, MM and the two fields of ce between the first and the second filter level (mi_les_dyn_level1)"""
+        _chk(lib().mi_les_dyn_level1(self.addr.ctx.h, C.c_int64(self._les_n(delta, nueff, kk_out)), C.c_int(1 if clip else 0), _ptr(delta), _ptr(nueff),
+                                     _ptrs(f_u, 3), _ptrs(f_sqr_u, 6), _ptr(f_magsqr_u), _ptrs(f_d, 6), _ptr(f_magsqr_d), _ptr(kk_out), _ptrs(ll_out, 6),
+                                     _ptrs(mm_out, 6), _ptr(ce_num_out), _ptr(ce_den_out), _ptr(pow_out)))
+
+    def les_dyn_level2(self, f_ll, f_mm, lm_out, mmmm_out):
+        """lm = 0.5*(fLL && fMM), mmmm = magSqr(fMM) (mi_les_dyn_level2)"""
+        _chk(lib().mi_les_dyn_level2(self.addr.ctx.h, C.c_int64(self._les_n(lm_out, mmmm_out, f_ll)), _ptrs(f_ll, 6), _ptrs(f_mm, 6), _ptr(lm_out), _ptr(mmmm_out)))
+
+    def les_dyn_coeffs(self, f_lm, f_mmmm, f_ce_num, f_ce_den, ck_out, ce_out):
+        """ck = 0.5*(mag(c) + c) with c = f_lm/(f_mmmm + VSMALL); ce likewise from f_ce_num/f_ce_den (mi_les_dyn_coeffs)"""
+        _chk(lib().mi_les_dyn_coeffs(self.addr.ctx.h, C.c_int64(self._les_n(f_lm, ck_out)), _ptr(f_lm), _ptr(f_mmmm), _ptr(f_ce_num), _ptr(f_ce_den),
+                                     _ptr(ck_out), _ptr(ce_out)))
 
     def sst_production(self, nut, grad, s2_out, g_out, mag_out=None):
         """S2 = 2*magSqr(symm(gradU)), G = nut*S2 and optionally mag(symm(gradU)) in one cell pass (mi_sst_production): grad as ke_production's"""

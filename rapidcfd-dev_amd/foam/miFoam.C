@@ -2,6 +2,8 @@
 // the C ABI (include/mi_ldu.h).  Compiled with hipcc only because device memory is managed here.
 #include "miFoam.H"
 
+#include <array>
+
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -1664,6 +1666,266 @@ void kOmegaSST::correct(const flowData& flow, scalar rDeltaT, const dictionary& 
     evaluateBoundary(k_, bk_);
     bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);
     correctNut(S2, bS2, false);                             // :466-467
+}
+}
+}
+// ---- LESdelta, simpleFilter and incompressible::LESModels -------------------------------------------------------------------
+LESdelta::LESdelta(label nCells, label nBoundaryFaces)
+    : delta_(std::vector<scalar>((std::size_t)nCells, 1e-15)), bdelta_(std::vector<scalar>((std::size_t)nBoundaryFaces, 1e-15)) {}   // LESdelta.C:53
+LESdelta::~LESdelta() {}
+cubeRootVolDelta::cubeRootVolDelta(const scalargpuField& V, label nBoundaryFaces, scalar deltaCoeff, scalar thickness)
+    : LESdelta(V.size(), nBoundaryFaces), deltaCoeff_(deltaCoeff), thickness_(thickness)
+{
+    calcDelta(V);
+}
+void cubeRootVolDelta::calcDelta(const scalargpuField& V)
+{
+    miCheck(mi_les_delta_cube_root_vol(miEngine::New().ctx, V.size(), deltaCoeff_, thickness_, V.data(), delta_.data(), nullptr), "cubeRootVolDelta::calcDelta");
+}
+simpleFilter::simpleFilter(const averageData& av, const scalargpuField& weights) : av_(&av), weights_(&weights) {}
+void simpleFilter::operator()(const std::vector<const scalargpuField*>& vf, const std::vector<const scalargpuField*>& bvf,
+                              const std::vector<scalargpuField*>& out) const
+{
+    if (vf.empty() || vf.size() > 9 || out.size() != vf.size() || (!bvf.empty() && bvf.size() != vf.size()))
+        FatalErrorIn("simpleFilter::operator()", "one to nine components, as many outputs and boundary fields");
+    const double* v[9] = {}; const double* b[9] = {}; double* o[9] = {};
+    for (std::size_t i = 0; i < vf.size(); ++i) { v[i] = vf[i]->data(); o[i] = out[i]->data(); if (!bvf.empty()) b[i] = bvf[i]->data(); }
+    miCheck(mi_les_simple_filter(av_->handle(), (int)vf.size(), weights_->data(), av_->magSf().data(), av_->bMagSf() ? av_->bMagSf()->data() : nullptr,
+                                 v, bvf.empty() ? nullptr : b, o), "simpleFilter::operator()");
+}
+namespace incompressible
+{
+namespace LESModels
+{
+namespace
+{
+std::vector<const scalargpuField*> cptrs(const std::vector<scalargpuField>& v, std::size_t a, std::size_t b)
+{
+    std::vector<const scalargpuField*> p;
+    for (std::size_t i = a; i < b; ++i) p.push_back(&v[i]);
+    return p;
+}
+std::vector<scalargpuField*> mptrs(std::vector<scalargpuField>& v, std::size_t a, std::size_t b)
+{
+    std::vector<scalargpuField*> p;
+    for (std::size_t i = a; i < b; ++i) p.push_back(&v[i]);
+    return p;
+}
+void dataOf(const std::vector<scalargpuField>& v, std::size_t a, const double** out, int n) { for (int i = 0; i < n; ++i) out[i] = v[a + (std::size_t)i].data(); }
+void dataOf(std::vector<scalargpuField>& v, std::size_t a, double** out, int n) { for (int i = 0; i < n; ++i) out[i] = v[a + (std::size_t)i].data(); }
+}
+GenEddyVisc::GenEddyVisc(const meshData& mesh, scalar nu, const scalargpuField& k, const scalargpuField& bk, const dictionary& coeffDict, scalar kMin)
+    : mesh_(mesh), nu_(nu), kMin_(kMin), nb_(bk.size()), delta_(*mesh.V, bk.size(), coeffDict.lookupOrDefault<scalar>("deltaCoeff", 1.0)), k_(k), bk_(bk),
+      nuSgs_(k.size()), bnuSgs_(bk.size())
+{
+    const char* who = "GenEddyVisc::New";
+    if (!mesh.addr || !mesh.boundary || !mesh.average) FatalErrorIn(who, "the addressing, the boundary and the averageData are needed");
+    if (mesh.patchTypes.size() != mesh.patchFaceCells.size()) FatalErrorIn(who, "one type per patch");
+    scalar ck = 0.094, ce = 1.048;
+    coeffDict.readIfPresent("ck", ck); coeffDict.readIfPresent("ce", ce);
+    miCheck(mi_les_coeffs_init(ck, ce, &coeffs_), who);
+    label off = 0;
+    for (std::size_t p = 0; p < mesh.patchFaceCells.size(); ++p) {
+        start_.push_back(off);
+        patches_.emplace_back(new fvPatchCells(mesh.addr->size(), mesh.patchFaceCells[p]));
+        off += (label)mesh.patchFaceCells[p].size();
+    }
+    start_.push_back(off);
+    if (off != nb_) FatalErrorIn(who, "the boundary fields do not have one value per boundary face");
+}
+GenEddyVisc::~GenEddyVisc() {}
+void GenEddyVisc::evaluateBoundary(const scalargpuField& vf, scalargpuField& bvf, bool keepFixed) const
+{
+    for (std::size_t p = 0; p < patches_.size(); ++p)
+        if (!(keepFixed && mesh_.patchTypes[p] == fixedValue) && patches_[p]->size() > 0)
+            miCheck(mi_patch_internal_field(patches_[p]->handle(), vf.data(), bvf.data() + start_[p]), "fvPatchField::evaluate");
+}
+void GenEddyVisc::gradArrays(const vectorgpuField* const* g, const double* out[9])
+{
+    for (int j = 0; j < 3; ++j) for (int d = 0; d < 3; ++d) out[3 * j + d] = g[j]->component((direction)d).data();
+}
+void GenEddyVisc::nuEff(scalargpuField& out) const { DkEff(out); }
+void GenEddyVisc::DkEff(scalargpuField& out) const
+{
+    scalargpuField sp(nuSgs_.size());                       // mi_ke_k_terms' dk = nut + nu; its sp is not used
+    miCheck(mi_ke_k_terms(miEngine::New().ctx, nuSgs_.size(), k_.data(), k_.data(), nuSgs_.data(), nullptr, nu_, sp.data(), out.data()), "GenEddyVisc::DkEff");
+}
+void GenEddyVisc::divDevReff(fvVectorMatrix& UEqn, const vectorgpuField& Sf, const vectorgpuField* const gradU[3],
+                             const std::vector<fvc::devTGradPatch>& patches) const
+{
+    scalargpuField visc(k_.size());
+    nuEff(visc);
+    vectorgpuField div(k_.size());
+    fvc::divDevTGrad(div, *mesh_.addr, fvc::DEV, *mesh_.weights, Sf, visc, gradU, patches, *mesh_.V);
+    UEqn.subtractField(div, *mesh_.V);
+}
+void GenEddyVisc::solveK(const scalargpuField& G, const scalargpuField& sp, const scalargpuField& gamma, const flowData& flow, scalar rDeltaT, scalar alpha,
+                         const dictionary& solverControls)
+{
+#pragma clang fp contract(off)
+    const lduAddressing& a = *mesh_.addr;
+    const label nf = mesh_.magSf->size();
+    const scalargpuField kOld(k_);
+    scalargpuField f(nf), gammaMagSf(nf);
+    fvc::interpolate(f, a, *mesh_.weights, gamma);
+    fieldSubMul(gammaMagSf, f, *mesh_.magSf);               // 0 - f*magSf, then the exact negation
+    fieldAxpby(gammaMagSf, -1.0, gammaMagSf, 0.0, gammaMagSf);
+    std::vector<bool> coupled(mesh_.patchFaceCells.size(), false);
+    fvScalarMatrix M("k", a, mesh_.patchFaceCells, coupled);
+    mi_fvm_terms t{};
+    const double* po[1] = {kOld.data()}; const double* sd[1] = {G.data()}; const double sg[1] = {-1.0}; double* so[1] = {M.source().data()};
+    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = 1.0; t.vol_dev = mesh_.V->data();
+    t.div_flux_dev = flow.phi->data(); t.div_weights_dev = (flow.divWeights ? flow.divWeights : mesh_.weights)->data();
+    t.lap_delta_coeffs_dev = mesh_.deltaCoeffs->data(); t.lap_gamma_magsf_dev = gammaMagSf.data();
+    t.sp_dev = sp.data(); t.sp_sign = 1.0;
+    t.n_rhs = 1; t.psi_old_dev = po; t.n_su = 1; t.su_dev = sd; t.su_sign = sg;
+    miCheck(mi_fvm_assemble(a.handle(), &t, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "GenEddyVisc: fvm::assemble");
+    // fixedValue: the diffusion coefficient and (diff - phi)*value with the boundary DkEff = nuSgs_b + nu; zeroGradient: the flux and nothing
+    const std::vector<scalar> bnut = bnuSgs_.asHost(), bms = mesh_.bMagSf->asHost(), bdc = mesh_.bDeltaCoeffs->asHost(), bphi = flow.bPhi->asHost(),
+                              bval = bk_.asHost();
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        const label m = start_[p + 1] - start_[p];
+        std::vector<scalar> ic((std::size_t)m), bc((std::size_t)m);
+        for (label i = 0; i < m; ++i) {
+            const std::size_t j = (std::size_t)(start_[p] + i);
+            if (mesh_.patchTypes[p] == fixedValue) {
+                const scalar g = bnut[j] + nu_, gm = g * bms[j], diff = gm * bdc[j];
+                const scalar x = diff * bval[j], y = bphi[j] * bval[j];
+                ic[(std::size_t)i] = diff; bc[(std::size_t)i] = x - y;
+            } else { ic[(std::size_t)i] = bphi[j]; bc[(std::size_t)i] = 0.0; }
+        }
+        M.internalCoeffs()[p] = ic; M.boundaryCoeffs()[p] = bc;
+    }
+    M.relax(alpha, k_);
+    M.solve(k_, solverControls);
+    evaluateBoundary(k_, bk_, true);
+    bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);
+}
+
+Smagorinsky::Smagorinsky(const meshData& mesh, const flowData& flow, scalar nu, const dictionary& coeffDict)
+    : GenEddyVisc(mesh, nu, scalargpuField(mesh.V->size()), scalargpuField(mesh.bMagSf->size()), coeffDict, 1e-15)
+{
+    updateSubGridScaleFields(flow);                         // Smagorinsky.C:76
+}
+void Smagorinsky::updateSubGridScaleFields(const flowData& flow)
+{
+    const double* grad[9];
+    gradArrays(flow.gradU, grad);
+    miCheck(mi_les_smagorinsky(miEngine::New().ctx, k_.size(), &coeffs_, delta_().data(), grad, k_.data(), nuSgs_.data()), "Smagorinsky::updateSubGridScaleFields");
+    evaluateBoundary(nuSgs_, bnuSgs_, false);
+    evaluateBoundary(k_, bk_, false);
+}
+void Smagorinsky::correct(const flowData& flow, scalar, const dictionary&, scalar) { updateSubGridScaleFields(flow); }   // Smagorinsky.C:84-89
+
+oneEqEddy::oneEqEddy(const meshData& mesh, scalar nu, const scalargpuField& k, const scalargpuField& bk, const dictionary& coeffDict, scalar kMin)
+    : GenEddyVisc(mesh, nu, k, bk, coeffDict, kMin)
+{
+    bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);   // oneEqEddy.C:90
+    updateSubGridScaleFields();
+}
+void oneEqEddy::updateSubGridScaleFields()
+{
+    miCheck(mi_les_nusgs(miEngine::New().ctx, k_.size(), coeffs_.ck, nullptr, k_.data(), delta_().data(), nuSgs_.data()), "oneEqEddy::updateSubGridScaleFields");
+    evaluateBoundary(nuSgs_, bnuSgs_, false);
+}
+void oneEqEddy::correct(const flowData& flow, scalar rDeltaT, const dictionary& kSolver, scalar kRelax)
+{
+    const label n = k_.size();
+    scalargpuField G(n), sp(n), dk(n);
+    const double* grad[9];
+    gradArrays(flow.gradU, grad);
+    miCheck(mi_les_k_terms(miEngine::New().ctx, n, coeffs_.ce, nullptr, nuSgs_.data(), grad, k_.data(), delta_().data(), nullptr, nu_, G.data(), sp.data(),
+                           dk.data()), "oneEqEddy::correct");
+    solveK(G, sp, dk, flow, rDeltaT, kRelax, kSolver);      // :106-119
+    updateSubGridScaleFields();
+}
+
+dynOneEqEddy::dynOneEqEddy(const meshData& mesh, const flowData& flow, scalar nu, const scalargpuField& k, const scalargpuField& bk,
+                           const dictionary& coeffDict, scalar kMin)
+    : GenEddyVisc(mesh, nu, k, bk, coeffDict, kMin), simpleFilter_(*mesh.average, *mesh.weights), filter_(simpleFilter_)
+{
+    bound(k_, &bk_, *mesh_.average, *mesh_.weights, kMin_);   // dynOneEqEddy.C:134
+    scalargpuField ck(k_.size()), ce(k_.size());
+    coefficients(flow, false, ck, ce);                      // :136-137: KK is not clipped here
+    updateSubGridScaleFields(ck);
+}
+void dynOneEqEddy::updateSubGridScaleFields(const scalargpuField& ck)
+{
+    miCheck(mi_les_nusgs(miEngine::New().ctx, k_.size(), 0.0, ck.data(), k_.data(), delta_().data(), nuSgs_.data()), "dynOneEqEddy::updateSubGridScaleFields");
+    evaluateBoundary(nuSgs_, bnuSgs_, false);
+}
+void dynOneEqEddy::coefficients(const flowData& flow, bool clip, scalargpuField& ck, scalargpuField& ce) const
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const label n = k_.size(), nb = nb_;
+    const char* who = "dynOneEqEddy::ck";
+    // a field with its boundary: [0] the cells, [1] the patch-ordered boundary values
+    auto fields = [&](int m) { return std::array<std::vector<scalargpuField>, 2>{std::vector<scalargpuField>((std::size_t)m, scalargpuField(n)),
+                                                                                  std::vector<scalargpuField>((std::size_t)m, scalargpuField(nb))}; };
+    // sqr(U) 0-5, magSqr(U) 6, D 7-12, magSqr(D) 13 (mi_les_dyn_moments), on the cells and on the boundary values
+    auto mom = fields(14);
+    for (int s = 0; s < 2; ++s) {
+        const vectorgpuField& U = s ? *flow.bU : *flow.U;
+        const double* u[3] = {U.component(0).data(), U.component(1).data(), U.component(2).data()};
+        const double* grad[9];
+        gradArrays(s ? flow.bGradU : flow.gradU, grad);
+        double *sq[6], *D[6];
+        dataOf(mom[s], 0, sq, 6); dataOf(mom[s], 7, D, 6);
+        miCheck(mi_les_dyn_moments(ctx, s ? nb : n, u, grad, sq, mom[s][6].data(), D, mom[s][13].data()), who);
+    }
+    // filter_ : U 0-2, sqr(U) 3-8, magSqr(U) 9, D 10-15, magSqr(D) 16 -- each filtered field once, two launches
+    auto f1 = fields(17);
+    {
+        std::vector<const scalargpuField*> in, bin;
+        for (int s = 0; s < 2; ++s) {
+            const vectorgpuField& U = s ? *flow.bU : *flow.U;
+            std::vector<const scalargpuField*>& v = s ? bin : in;
+            for (int d = 0; d < 3; ++d) v.push_back(&U.component((direction)d));
+            for (const scalargpuField* x : cptrs(mom[s], 0, 6)) v.push_back(x);
+        }
+        filter_(in, bin, mptrs(f1[0], 0, 9));
+        filter_(cptrs(mom[0], 6, 14), cptrs(mom[1], 6, 14), mptrs(f1[0], 9, 17));
+    }
+    for (int i = 0; i < 17; ++i) evaluateBoundary(f1[0][(std::size_t)i], f1[1][(std::size_t)i], false);
+    // KK 0, LL 1-6, MM 7-12, ce_num 13, ce_den 14 (mi_les_dyn_level1); nuEff = nuSgs + nu, delta_b = SMALL
+    auto lv = fields(15);
+    scalargpuField nuEffC(n), nuEffB(nb), spC(n), spB(nb);
+    miCheck(mi_ke_k_terms(ctx, n, k_.data(), k_.data(), nuSgs_.data(), nullptr, nu_, spC.data(), nuEffC.data()), who);
+    miCheck(mi_ke_k_terms(ctx, nb, bk_.data(), bk_.data(), bnuSgs_.data(), nullptr, nu_, spB.data(), nuEffB.data()), who);
+    for (int s = 0; s < 2; ++s) {
+        const double *fU[3], *fS[6], *fD[6];
+        dataOf(f1[s], 0, fU, 3); dataOf(f1[s], 3, fS, 6); dataOf(f1[s], 10, fD, 6);
+        double *LL[6], *MM[6];
+        dataOf(lv[s], 1, LL, 6); dataOf(lv[s], 7, MM, 6);
+        miCheck(mi_les_dyn_level1(ctx, s ? nb : n, clip ? 1 : 0, (s ? delta_.boundaryField() : delta_()).data(), (s ? nuEffB : nuEffC).data(), fU, fS,
+                                  f1[s][9].data(), fD, f1[s][16].data(), lv[s][0].data(), LL, MM, lv[s][13].data(), lv[s][14].data(), nullptr), who);
+    }
+    // simpleFilter_ : LL 0-5, MM 6-11, ce_num 12, ce_den 13
+    auto f2 = fields(14);
+    simpleFilter_(cptrs(lv[0], 1, 10), cptrs(lv[1], 1, 10), mptrs(f2[0], 0, 9));
+    simpleFilter_(cptrs(lv[0], 10, 15), cptrs(lv[1], 10, 15), mptrs(f2[0], 9, 14));
+    for (int i = 0; i < 12; ++i) evaluateBoundary(f2[0][(std::size_t)i], f2[1][(std::size_t)i], false);
+    auto lm = fields(2);
+    for (int s = 0; s < 2; ++s) {
+        const double *fLL[6], *fMM[6];
+        dataOf(f2[s], 0, fLL, 6); dataOf(f2[s], 6, fMM, 6);
+        miCheck(mi_les_dyn_level2(ctx, s ? nb : n, fLL, fMM, lm[s][0].data(), lm[s][1].data()), who);
+    }
+    auto f3 = fields(2);
+    simpleFilter_(cptrs(lm[0], 0, 2), cptrs(lm[1], 0, 2), mptrs(f3[0], 0, 2));
+    miCheck(mi_les_dyn_coeffs(ctx, n, f3[0][0].data(), f3[0][1].data(), f2[0][12].data(), f2[0][13].data(), ck.data(), ce.data()), who);
+}
+void dynOneEqEddy::correct(const flowData& flow, scalar rDeltaT, const dictionary& kSolver, scalar kRelax)
+{
+    const label n = k_.size();
+    scalargpuField ck(n), ce(n), P(n), sp(n), dk(n);
+    coefficients(flow, true, ck, ce);                       // :151-152 and the ck / ce of :163, :171
+    const double* grad[9];
+    gradArrays(flow.gradU, grad);
+    miCheck(mi_les_k_terms(miEngine::New().ctx, n, 0.0, ce.data(), nuSgs_.data(), grad, k_.data(), delta_().data(), nullptr, nu_, P.data(), sp.data(), dk.data()),
+            "dynOneEqEddy::correct");
+    solveK(P, sp, dk, flow, rDeltaT, kRelax, kSolver);      // :154-169
+    updateSubGridScaleFields(ck);
 }
 }
 }
