@@ -938,7 +938,7 @@ int mi_near_interface(mi_ctx_t ctx, int64_t n, const double *alpha_dev, double *
  *   a lower bound that is not a number.
  *   mi_min_max during a PCG session: MI_ERR_STATE.  Zero cells, zero wall faces and zero wall patches: MI_OK.
  * Out of scope: the wall-distance field itself (wallDist / meshWave: kOmegaSST, below, takes y as the caller's cell array); the low-Re and rough wall functions;
- *   the nutU* wall functions; the weighted (weights) forms of the epsilon wall function; compressible kEpsilon (rho-weighted);
+ *   the nutU* wall functions (nutUSpalding: the Spalart-Allmaras block); the weighted (weights) forms of the epsilon wall function; compressible kEpsilon (rho-weighted);
  *   a pisoFoam / simpleFoam application; moving meshes; nearWallDist (y is the caller's patch array). */
 typedef struct mi_ke_coeffs {
     double Cmu, C1, C2, sigmaEps, kappa, E;
@@ -1031,7 +1031,7 @@ int mi_ke_nut_wall(mi_ke_t ke, const mi_ke_coeffs *coeffs, const double *k_dev, 
  * Refused (MI_ERR_ARG, nothing launched, nothing written): as in the kEpsilon block -- missing arrays, an output that aliases an input or
  *   another output (mi_sst_omega_sources's diag and source are in-out), an array not aligned for a double, a handle of another addressing,
  *   coefficients that are not finite or not above zero, a nu_value that is not.  Zero cells and zero wall faces: MI_OK.
- * Out of scope: wallDist / meshWave; the weighted (weights) omega wall function; the low-Re, rough and nutU* wall functions; kOmega,
+ * Out of scope: wallDist / meshWave; the weighted (weights) omega wall function; the low-Re, rough and nutU* wall functions (nutUSpalding: the Spalart-Allmaras block); kOmega,
  *   kOmegaSSTSAS; compressible kOmegaSST; coupled wall patches; moving meshes; a simpleFoam / pisoFoam application. */
 typedef struct mi_sst_coeffs {
     double alphaK1, alphaK2, alphaOmega1, alphaOmega2, gamma1, gamma2, beta1, beta2, betaStar, a1, b1, c1;
@@ -1293,7 +1293,7 @@ int mi_central_courant(mi_addr_t addr, const double *delta_coeffs_dev, const dou
  *   output (reported before alignment, as mi_fvc_average does); an array not aligned for a double; NULL boundary arrays while the boundary
  *   has faces; a handle of another addressing; a coefficient that is not finite or not above zero.  Zero cells: MI_OK.
  * Out of scope: laplaceFilter and anisotropicFilter; vanDriestDelta, smoothDelta, maxDeltaxyz and PrandtlDelta (they need the wall distance
- *   or face geometry); the homogeneous dynamic models (their average() fixes a reduction order); the Spalart-Allmaras DES family; the nuSgs
+ *   or face geometry); the homogeneous dynamic models (their average() fixes a reduction order); the Spalart-Allmaras DES family (the block below); the nuSgs
  *   wall functions; compressible LES; a pisoFoam application; moving meshes. */
 typedef struct mi_les_coeffs {
     double ck, ce;
@@ -1319,6 +1319,118 @@ int mi_les_dyn_level2(mi_ctx_t ctx, int64_t n, const double *const *f_ll_dev, co
                       double *mmmm_out_dev);
 int mi_les_dyn_coeffs(mi_ctx_t ctx, int64_t n, const double *f_lm_dev, const double *f_mmmm_dev, const double *f_ce_num_dev,
                       const double *f_ce_den_dev, double *ck_out_dev, double *ce_out_dev);
+/* ---- the Spalart-Allmaras model: RAS, DES, DDES, IDDES and the nutUSpalding wall function
+ *      (turbulenceModels/incompressible/RAS/SpalartAllmaras/SpalartAllmaras.C:45-137, :190, :269-275, :437-464;
+ *      LES/SpalartAllmaras/SpalartAllmaras.C:45-172, :260, :331-357; LES/SpalartAllmarasDDES/SpalartAllmarasDDES.C:45-93;
+ *      LES/SpalartAllmarasIDDES/SpalartAllmarasIDDES.C:45-140; RAS/derivedFvPatchFields/wallFunctions/nutWallFunctions/
+ *      nutUSpaldingWallFunction/nutUSpaldingWallFunctionFvPatchScalarField.C:39-110; fvMatrix.C:2208-2216, :2731-2756, :2773-2800; fvmSup.C:100-131;
+ *      primitives/Scalar/Scalar.H:183-204) ----
+ * correct() of the RAS class is about 30 one-operator field passes between the gradients and the matrix, of IDDES well over 80; here it is ONE
+ * cell pass, mi_sa_terms, beside the gradients, mi_fvm_assemble, mi_relax, the solve, mi_bound and mi_sa_nut.  The rules of the kEpsilon and
+ * LES blocks hold: fp64 values, int32 labels, every field operator rounded on its own except the fma written below, IEEE / and sqrt,
+ * max(a, b) = (a > b) ? a : b, min(a, b) = (a < b) ? a : b, pos(x) = x >= 0, neg(x) = x < 0, pow3(s) = s*sqr(s), pow6(s) = pow3(sqr(s))
+ * (Scalar.H:183-204), SMALL = 1e-15, ROOTVSMALL = 1e-150.  grad_dev is mi_ke_production's layout, g[3*j + k] = d(U_j)/dx_k.  y (wallDist),
+ * delta (LESdelta / IDDESDelta) and hmax (maxDeltaxyz) are the CALLER's cell arrays.  pow, tanh and exp are the device library's and NOT the
+ * reference's bits: each is evaluated once per cell and can be returned, and everything formed from them is exact given them.  A per-element
+ * map has no neighbour access: run over the patch-ordered boundary arrays it gives the boundary values (the rule of the LES block).
+ *   magSqr(v)  of grad(nuTilda): fma(v.z, v.z, fma(v.x, v.x, v.y*v.y))                                          (stated in the LES block)
+ *   mag(symm(gradU)): sqrt of the chain stated for mi_ke_production
+ *   mag(skew(gradU)) (TensorI.H:511-519, VectorSpaceI.H:336-355): magSqr of the nine components t0..t8 is s = fma(t0, t0, t1*t1), then
+ *     s = fma(tk, tk, s) for k = 2..8; skew's diagonal is 0.0, so with xy = 0.5*(g1 - g3), xz = 0.5*(g2 - g6), yx = 0.5*(g3 - g1),
+ *     yz = 0.5*(g5 - g7), zx = 0.5*(g6 - g2), zy = 0.5*(g7 - g5):  s = xy*xy, then fma(xz, xz, s), fma(yx, yx, s), fma(yz, yz, s),
+ *     fma(zx, zx, s), fma(zy, zy, s); mag = sqrt(s)                                             (an ASSUMPTION)
+ * mi_sa_coeffs_init (host only, no GPU): model_or_null = {sigmaNut, kappa, Cb1, Cb2, Cw2, Cw3, Cv1, Cv2, CDES, ck, fwStar, cl, ct}, NULL for
+ *   the reference's defaults 0.66666, 0.41, 0.1355, 0.622, 0.3, 2.0, 7.1, 5.0, 0.65, 0.07, 0.424, 3.55, 1.63; wall_or_null = {kappa, E} of the
+ *   wall function, NULL for 0.41, 9.8.  The products of dimensionedScalars are formed once, in the reference's operand order:
+ *   Cw1 = Cb1/sqr(kappa) + (1.0 + Cb2)/sigmaNut, Cb2BySigmaNut = Cb2/sigmaNut, Cv1_3 = pow3(Cv1), Cw3_6 = pow6(Cw3), onePlusCw3_6 = 1 + Cw3_6,
+ *   invCv2 = 1/Cv2, ct2 = sqr(ct), cl2 = sqr(cl), psiDen = (Cw1*sqr(kappa))*fwStar, psiCoeff = Cb1/psiDen, invE = 1/E, sqrt2 = sqrt(2.0).
+ *   Every member must be finite and above zero, here and in every entry that takes a mi_sa_coeffs.
+ * mi_sa_terms: kind = MI_SA_RAS | MI_SA_DES | MI_SA_DDES | MI_SA_IDDES, ashford != 0: ashfordCorrection.  With nt = nuTilda:
+ *     chi = nt/nu;  chi3 = pow3(chi);  fv1 = chi3/(chi3 + Cv1_3)                                                  (RAS :51-55, LES :54-58)
+ *     S = sqrt2*mag(skew(gradU)); for MI_SA_DDES sqrt2*mag(symm(gradU)) -- SpalartAllmarasDDES::S overrides the virtual (DDES.C:78-81),
+ *       SpalartAllmarasIDDES does not
+ *     Ashford, RAS (:66, :83-89):  fv2 = 1.0/pow3(1 + chi/Cv2);          c = invCv2*chi
+ *     Ashford, LES (:65, :79-86):  fv2 = 1/pow3(1 + nt/(Cv2*nu));        c = chi/Cv2
+ *              both:               fv3 = (((1 + chi*fv1)*invCv2)*(3*(1 + c) + sqr(c)))/pow3(1 + c)
+ *     without Ashford:             fv2 = 1.0 - chi/(1.0 + chi*fv1);      fv3 = 1
+ *     dTilda   RAS: y.   DES (:169-172): min(CDES*delta, y).
+ *              rd(visc) = min(visc/(max(S, SMALL)*sqr(kappa*y) + ROOTVSMALL), 10)                               (DDES :45-69, IDDES :73-97)
+ *              DDES (:72-93): fd = 1 - tanh(pow3(8*rd(nuSgs + nu)));  dTilda = max(y - fd*max(y - CDES*delta, 0), SMALL)
+ *              IDDES (:45-140): alpha = max(0.25 - y/hmax, -5);  e = exp(sqr(alpha));  p1 = pow(e, -11.09);  p2 = pow(e, -9.0)
+ *                fHill = 2*(pos(alpha)*p1 + neg(alpha)*p2);  fStep = min(2*p2, 1);  fd as DDES;  fHyb = max(1 - fd, fStep)
+ *                ft = tanh(pow3(ct2*rd(nuSgs)));  fl = tanh(pow(cl2*rd(nu), 10));  fAmp = 1 - max(ft, fl)
+ *                fRestore = max(fHill - 1, 0)*fAmp;  Psi = sqrt(min(100, (1 - psiCoeff*fv2)/max(SMALL, fv1)))
+ *                dTilda = max(SMALL, (fHyb*(1 + fRestore*Psi))*y + (((1 - fHyb)*CDES)*Psi)*delta)
+ *     STilda   RAS (:440-444): (fv3*sqrt2)*mag(skew(gradU)) + (fv2*nt)/sqr(kappa*y)    -- sqrt(2.0) meets fv3 BEFORE the magnitude
+ *              LES (:123):     fv3*S + (fv2*nt)/sqr(kappa*dTilda)
+ *     r        RAS (:116-131): min(nt/(max(STilda, SMALL)*sqr(kappa*y)), 10)           -- no ROOTVSMALL
+ *              LES (:127-153): min(nt/(max(STilda, SMALL)*sqr(kappa*dTilda) + ROOTVSMALL), 10)
+ *     g = r + Cw2*(pow6(r) - r);  fw = g*pow(onePlusCw3_6/(pow6(g) + Cw3_6), 1.0/6.0)                              (RAS :134-136, LES :163-165)
+ *     su_grad = Cb2BySigmaNut*magSqr(grad(nt));  su_prod = (Cb1*STilda)*nt;  sp = ((Cw1*fw)*nt)/sqr(dTilda);  dnu = (nt + nu)/sigmaNut
+ *   nu a cell array, or nu_value when nu_dev_or_null is NULL.  delta is read by the DES kinds, nuSgs by DDES and IDDES, hmax by IDDES; an
+ *   array a kind does not read may be NULL.  Optional outputs (NULL: not written): S, dTilda, STilda and pow of fw for every kind; tanh of fd
+ *   for DDES and IDDES; e, p1, p2, ft, pow(., 10) and fl for IDDES.  One that the kind does not form is refused.
+ *   The equation (RAS :446-455, LES :335-349): ddt + div - laplacian - su_grad == su_prod - fvm::Sp(sp, nt).  operator-(tmp<fvMatrix>,
+ *   tmp<volScalarField>) adds V*su_grad to the left side's source (fvMatrix.C:2731-2756: `tC().source() += V*su`);
+ *   operator-(tmp<volScalarField>, fvMatrix) negates the Sp matrix and subtracts V*su_prod from ITS source (:2773-2800); operator== subtracts that
+ *   matrix: diag = diagL + V*sp, source = (sourceL + V*su_grad) + V*su_prod -- two additions in this order, not V*(su_grad + su_prod).  That
+ *   is mi_fvm_assemble with sp_sign > 0, n_su = 2, su = {su_grad, su_prod} and both su_sign < 0; no entry of its own.
+ * mi_sa_nut: recompute_fv1 == 0 (RAS :463): nut = fv1*nt with fv1_dev_or_null the array mi_sa_terms wrote BEFORE the solve;
+ *   recompute_fv1 != 0 (updateSubGridScaleFields, LES :45-49, and the constructor): fv1 recomputed from nt and nu, optionally returned.
+ * mi_sa_nut_spalding_wall (nutUSpalding :93-110 with calcUTau's functor :39-89): every wall face of ALL wall patches in ONE launch on a
+ *   mi_ke_t, one thread per face, no atomics.  Per face with cell c (mag as in mi_ke_wall_cells):
+ *     magUp = mag(U[c] - Uw);  magGradU = mag(dc*(Uw - U[c]));  ut = sqrt((nutw + nuw)*magGradU)
+ *     ut <= ROOTVSMALL: uTau = 0.  Otherwise at most ten times:
+ *       kUu = min((kappa*magUp)/ut, 50);  e = exp(kUu);  fkUu = fma(-kUu, fma(kUu, 0.5, 1.0), e - 1)
+ *       f = fma(invE, fma(-(1.0/6.0)*kUu, sqr(kUu), fkUu), magUp/ut - (ut*y)/nuw)
+ *       df = (magUp/sqr(ut) + y/nuw) + ((invE*kUu)*fkUu)/ut;  new = ut + f/df;  err = mag((ut - new)/ut);  ut = new
+ *     while ut > ROOTVSMALL && err > 0.01 && ++iter < 10;  uTau = max(0.0, ut)     (the contraction: an ASSUMPTION)
+ *     nutw = max(0, sqr(uTau)/(magGradU + ROOTVSMALL) - nuw)
+ *   b_nutw_inout_dev holds the patch-ordered boundary values of nut: a wall face reads its own value and writes the new one, other faces are
+ *   untouched.  b_exp_out_dev_or_null (10 per BOUNDARY face, [10*face + step]) receives e of every step taken, b_iter_out_dev_or_null (int32
+ *   per boundary face) the number of steps; faces that are not on a wall and steps not taken are not written.
+ * Refused (MI_ERR_ARG, nothing launched, nothing written): as in the LES block -- missing arrays (delta for the DES kinds, nuSgs for DDES and
+ *   IDDES, hmax for IDDES), an output that aliases an input or another output, an array not aligned for a double, a handle of another
+ *   addressing, coefficients that are not finite or not above zero, a nu_value that is not, an unknown kind.  Zero cells, zero wall faces: MI_OK.
+ * Out of scope: wallDist / meshWave, maxDeltaxyz and IDDESDelta (y, hmax and delta are the caller's arrays); nuSgsUSpaldingWallFunction and the
+ *   other wall functions; k(), epsilon(), B(), LESRegion() beyond the dTilda output; the compressible forms; moving meshes; a simpleFoam /
+ *   pisoFoam application; the wiring into tools/workloads.py. */
+#define MI_SA_RAS 0
+#define MI_SA_DES 1
+#define MI_SA_DDES 2
+#define MI_SA_IDDES 3
+typedef struct mi_sa_coeffs {
+    double sigmaNut, kappa, Cb1, Cb2, Cw2, Cw3, Cv1, Cv2, CDES, ck, fwStar, cl, ct;
+    double wallKappa, E;                      /* the wall function's */
+    double Cw1, Cb2BySigmaNut, Cv1_3, Cw3_6, onePlusCw3_6, invCv2, ct2, cl2, psiDen, psiCoeff, invE, sqrt2;   /* derived: mi_sa_coeffs_init */
+} mi_sa_coeffs;
+typedef struct mi_sa_cells {
+    const double *nutilda_dev;
+    const double *grad_dev[9];
+    const double *grad_nutilda_dev[3];
+    const double *y_dev;
+    const double *nu_dev_or_null;
+    double nu_value;
+    const double *delta_dev, *nusgs_dev, *hmax_dev;
+    double *su_grad_out_dev, *su_prod_out_dev, *sp_out_dev, *dnu_out_dev, *fv1_out_dev;
+    double *s_out_dev_or_null, *dtilda_out_dev_or_null, *stilda_out_dev_or_null, *pow_fw_out_dev_or_null;
+    double *tanh_fd_out_dev_or_null;
+    double *exp_out_dev_or_null, *pow_hill_pos_out_dev_or_null, *pow_hill_neg_out_dev_or_null, *tanh_ft_out_dev_or_null, *pow_fl_out_dev_or_null,
+           *tanh_fl_out_dev_or_null;
+} mi_sa_cells;
+typedef struct mi_sa_wall {
+    const double *u_dev[3];
+    const double *b_uw_dev[3];                /* the boundary face values of U */
+    const double *b_delta_coeffs_dev, *b_y_dev, *b_nuw_dev;
+    double *b_nutw_inout_dev;
+    double *b_exp_out_dev_or_null;
+    int32_t *b_iter_out_dev_or_null;
+} mi_sa_wall;
+int mi_sa_coeffs_init(const double *model_or_null, const double *wall_or_null, mi_sa_coeffs *out);
+int mi_sa_terms(mi_ctx_t ctx, int64_t n, const mi_sa_coeffs *coeffs, int kind, int ashford, const mi_sa_cells *arrays);
+int mi_sa_nut(mi_ctx_t ctx, int64_t n, const mi_sa_coeffs *coeffs, int recompute_fv1, const double *nutilda_dev, const double *fv1_dev_or_null,
+              const double *nu_dev_or_null, double nu_value, double *nut_out_dev, double *fv1_out_dev_or_null);
+int mi_sa_nut_spalding_wall(mi_ke_t ke, const mi_sa_coeffs *coeffs, const mi_sa_wall *arrays);
 /* ---- the compressible operators of rhoPimpleFoam (BASELINE config 5; round 5) ----
  * mi_fvm_ddt_euler_rho: fvm::ddt(rho, vf) with a density FIELD -- EulerDdtScheme<Type>::fvmDdt(const volScalarField& rho, vf),
  *   src/finiteVolume/finiteVolume/ddtSchemes/EulerDdtScheme/EulerDdtScheme.C:403-440:

@@ -2512,6 +2512,7 @@ extern "C" int mi_event_elapsed_ms(mi_matrix_t m, int32_t idx0, int32_t idx1, fl
 #include "thermo.inc"
 #include "central.inc"
 #include "les.inc"
+#include "spalart.inc"
 
 mi_matrix_s::~mi_matrix_s()
 {

@@ -96,6 +96,7 @@ SYMBOLS = [
     "mi_central_scheme_parse", "mi_central_flux", "mi_patch_central_flux", "mi_central_sound_speed", "mi_central_courant",
     "mi_les_coeffs_init", "mi_les_simple_filter", "mi_les_delta_cube_root_vol", "mi_les_smagorinsky", "mi_les_k_terms", "mi_les_nusgs",
     "mi_les_dyn_moments", "mi_les_dyn_level1", "mi_les_dyn_level2", "mi_les_dyn_coeffs",
+    "mi_sa_coeffs_init", "mi_sa_terms", "mi_sa_nut", "mi_sa_nut_spalding_wall",
 ]
 
 
@@ -1637,6 +1638,21 @@ class KEpsilon:
         x.g_inout_dev, x.omega_inout_dev, x.b_omega_out_dev = (_ptr(t).value for t in (g_inout, omega_inout, b_omega_out))
         _chk(lib().mi_sst_wall_cells(self.h, C.byref(coeffs) if coeffs is not None else None, C.byref(x)))
 
+    def sa_nut_spalding_wall(self, coeffs: "SaCoeffs", u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw_inout, b_exp_out=None, b_iter_out=None):
+        """nutUSpaldingWallFunction::calcNut with calcUTau's Newton loop on every wall face in one launch (mi_sa_nut_spalding_wall):
+        b_nutw_inout the boundary values of nut (the wall faces are read and rewritten), b_exp_out 10 doubles per boundary face for the exp of
+        every step taken, b_iter_out an int32 tensor per boundary face for the number of steps"""
+        x = SaWall()
+        for d in range(3):
+            x.u_dev[d] = _ptr(None if u is None else u[d]).value
+            x.b_uw_dev[d] = _ptr(None if b_uw is None else b_uw[d]).value
+        x.b_delta_coeffs_dev, x.b_y_dev, x.b_nuw_dev, x.b_nutw_inout_dev, x.b_exp_out_dev_or_null = \
+            (_ptr(t).value for t in (b_delta_coeffs, b_y, b_nuw, b_nutw_inout, b_exp_out))
+        if b_iter_out is not None:
+            assert b_iter_out.is_contiguous() and b_iter_out.element_size() == 4
+            x.b_iter_out_dev_or_null = b_iter_out.data_ptr()
+        _chk(lib().mi_sa_nut_spalding_wall(self.h, C.byref(coeffs) if coeffs is not None else None, C.byref(x)))
+
     def close(self):
         if self.h:
             lib().mi_ke_destroy(self.h)
@@ -1729,6 +1745,47 @@ class SstBlendArrays(C.Structure):
                [(name, C.c_void_p) for name in ("k_dev", "omega_dev", "y_dev", "nut_dev", "s2_dev", "nu_dev_or_null")] + [("nu_value", C.c_double)] + \
                [(name, C.c_void_p) for name in ("f1_out_dev", "su_out_dev", "sp_out_dev", "susp_out_dev", "domega_out_dev", "dk_out_dev",
                                                 "cdkomega_out_dev_or_null", "arg1_out_dev_or_null", "f23_out_dev_or_null", "tanh3_out_dev_or_null")]
+
+
+SA_MODEL = ("sigmaNut", "kappa", "Cb1", "Cb2", "Cw2", "Cw3", "Cv1", "Cv2", "CDES", "ck", "fwStar", "cl", "ct")
+SA_WALL = ("wallKappa", "E")
+SA_DERIVED = ("Cw1", "Cb2BySigmaNut", "Cv1_3", "Cw3_6", "onePlusCw3_6", "invCv2", "ct2", "cl2", "psiDen", "psiCoeff", "invE", "sqrt2")
+SA_KINDS = {"RAS": 0, "DES": 1, "DDES": 2, "IDDES": 3}
+SA_OPTIONAL = ("s", "dtilda", "stilda", "pow_fw", "tanh_fd", "exp", "pow_hill_pos", "pow_hill_neg", "tanh_ft", "pow_fl", "tanh_fl")
+
+
+class SaCoeffs(C.Structure):
+    """mi_sa_coeffs (include/mi_ldu.h)"""
+    _fields_ = [(name, C.c_double) for name in SA_MODEL + SA_WALL + SA_DERIVED]
+
+
+def sa_coeffs(**given) -> SaCoeffs:
+    """mi_sa_coeffs_init: the Spalart-Allmaras coefficients (SA_MODEL) and the wall function's (SA_WALL) by name, the reference's defaults for
+    the rest, with the host-formed products derived (host only, no GPU)"""
+    unknown = set(given) - set(SA_MODEL) - set(SA_WALL)
+    if unknown:
+        raise TypeError("sa_coeffs: unknown coefficient " + ", ".join(sorted(unknown)))
+    base = SaCoeffs()
+    _chk(lib().mi_sa_coeffs_init(None, None, C.byref(base)))
+    model = (C.c_double * 13)(*[float(given.get(name, getattr(base, name))) for name in SA_MODEL])
+    wall = (C.c_double * 2)(*[float(given.get(name, getattr(base, name))) for name in SA_WALL])
+    out = SaCoeffs()
+    _chk(lib().mi_sa_coeffs_init(model, wall, C.byref(out)))
+    return out
+
+
+class SaCells(C.Structure):
+    """mi_sa_cells (include/mi_ldu.h)"""
+    _fields_ = [("nutilda_dev", C.c_void_p), ("grad_dev", C.c_void_p * 9), ("grad_nutilda_dev", C.c_void_p * 3), ("y_dev", C.c_void_p),
+                ("nu_dev_or_null", C.c_void_p), ("nu_value", C.c_double), ("delta_dev", C.c_void_p), ("nusgs_dev", C.c_void_p), ("hmax_dev", C.c_void_p)] + \
+               [(name, C.c_void_p) for name in ("su_grad_out_dev", "su_prod_out_dev", "sp_out_dev", "dnu_out_dev", "fv1_out_dev")] + \
+               [(name + "_out_dev_or_null", C.c_void_p) for name in SA_OPTIONAL]
+
+
+class SaWall(C.Structure):
+    """mi_sa_wall (include/mi_ldu.h)"""
+    _fields_ = [("u_dev", C.c_void_p * 3), ("b_uw_dev", C.c_void_p * 3), ("b_delta_coeffs_dev", C.c_void_p), ("b_y_dev", C.c_void_p),
+                ("b_nuw_dev", C.c_void_p), ("b_nutw_inout_dev", C.c_void_p), ("b_exp_out_dev_or_null", C.c_void_p), ("b_iter_out_dev_or_null", C.c_void_p)]
 
 
 class Assembly:
@@ -2163,6 +2220,42 @@ class Assembly:
         _chk(lib().mi_sst_nut(self.addr.ctx.h, C.c_int64(n), C.byref(coeffs) if coeffs is not None else None, C.c_int(int(bool(f3))),
                               C.c_int(int(bool(constructor_form))), _ptr(k), _ptr(omega), _ptr(y), _ptr(s), _ptr(nu_dev), C.c_double(nu_value),
                               _ptr(nut_out), _ptr(f23_out)))
+
+    def sa_terms(self, coeffs, kind, ashford, nutilda, grad, grad_nutilda, y, nu, su_grad_out, su_prod_out, sp_out, dnu_out, fv1_out, delta=None,
+                 nusgs=None, hmax=None, **optional):
+        """The Spalart-Allmaras model's cell pass (mi_sa_terms): kind "RAS" | "DES" | "DDES" | "IDDES" (or MI_SA_*), ashford the ashfordCorrection
+        switch; nu a cell array or a number; delta for the DES kinds, nusgs for DDES and IDDES, hmax for IDDES; optional outputs by the names
+        of SA_OPTIONAL"""
+        unknown = set(optional) - set(SA_OPTIONAL)
+        if unknown:
+            raise TypeError("sa_terms: unknown output " + ", ".join(sorted(unknown)))
+        x = SaCells()
+        x.nutilda_dev = _ptr(nutilda).value
+        for i in range(9):
+            x.grad_dev[i] = _ptr(None if grad is None else grad[i]).value
+        for i in range(3):
+            x.grad_nutilda_dev[i] = _ptr(None if grad_nutilda is None else grad_nutilda[i]).value
+        nu_dev, x.nu_value = (None, float(nu)) if isinstance(nu, (int, float)) else (nu, 0.0)
+        x.y_dev, x.nu_dev_or_null, x.delta_dev, x.nusgs_dev, x.hmax_dev = (_ptr(t).value for t in (y, nu_dev, delta, nusgs, hmax))
+        x.su_grad_out_dev, x.su_prod_out_dev, x.sp_out_dev, x.dnu_out_dev, x.fv1_out_dev = \
+            (_ptr(t).value for t in (su_grad_out, su_prod_out, sp_out, dnu_out, fv1_out))
+        for name in SA_OPTIONAL:
+            setattr(x, name + "_out_dev_or_null", _ptr(optional.get(name)).value)
+        n = self._les_n(nutilda, y, fv1_out)
+        _chk(lib().mi_sa_terms(self.addr.ctx.h, C.c_int64(n), C.byref(coeffs) if coeffs is not None else None, C.c_int(SA_KINDS.get(kind, kind)),
+                               C.c_int(int(bool(ashford))), C.byref(x)))
+
+    def sa_nut(self, coeffs, nutilda, nut_out, fv1=None, nu=None, fv1_out=None):
+        """nut = fv1*nuTilda (mi_sa_nut): with fv1 the array sa_terms wrote before the solve (the RAS correct()), or with nu (a cell array or a
+        number) fv1 recomputed from nuTilda, as updateSubGridScaleFields() of the LES classes does"""
+        recompute = fv1 is None
+        nu_dev, nu_value = (None, float(nu)) if isinstance(nu, (int, float)) else (nu, 0.0)
+        _chk(lib().mi_sa_nut(self.addr.ctx.h, C.c_int64(self._les_n(nutilda, nut_out)), C.byref(coeffs) if coeffs is not None else None,
+                             C.c_int(int(recompute)), _ptr(nutilda), _ptr(fv1), _ptr(nu_dev), C.c_double(nu_value), _ptr(nut_out), _ptr(fv1_out)))
+
+    def sa_nut_spalding_wall(self, ke, coeffs, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw_inout, b_exp_out=None, b_iter_out=None):
+        """nutUSpaldingWallFunction on every wall face over a KEpsilon handle of this addressing (mi_sa_nut_spalding_wall)"""
+        ke.sa_nut_spalding_wall(coeffs, u, b_uw, b_delta_coeffs, b_y, b_nuw, b_nutw_inout, b_exp_out, b_iter_out)
 
     def thermo_calculate(self, model, he, p, t0, t_out, psi_out, mu_out, alpha_out, rho_out=None, rho_form=0, iters_out=None):
         """T = THE(he, p, t0) by the reference's Newton iteration, then psi, mu, alpha and (rho_form 1: p/(R*T), 2: psi*p) rho at the new T in one

@@ -1669,6 +1669,240 @@ void kOmegaSST::correct(const flowData& flow, scalar rDeltaT, const dictionary& 
 }
 }
 }
+// ---- the Spalart-Allmaras model: RAS, DES, DDES, IDDES ---------------------------------------------------------------------
+namespace incompressible
+{
+struct SpalartAllmarasBase::termFields
+{
+    scalargpuField suGrad, suProd, sp, dnu, fv1;
+    scalargpuField *S, *dTilda, *tanhFd;                    // optional
+    explicit termFields(label m) : suGrad(m), suProd(m), sp(m), dnu(m), fv1(m), S(nullptr), dTilda(nullptr), tanhFd(nullptr) {}
+};
+SpalartAllmarasBase::SpalartAllmarasBase(const meshData& mesh, scalar nu, const scalargpuField& nuTilda, const scalargpuField& bnuTilda,
+                                         const dictionary& coeffDict)
+    : mesh_(mesh), nu_(nu), ashfordCorrection_(true), h_(nullptr), nb_(bnuTilda.size()), nuTilda_(nuTilda), bnuTilda_(bnuTilda), nut_(nuTilda.size()),
+      bnut_(std::vector<scalar>((std::size_t)bnuTilda.size(), 0.0)), bnu_(std::vector<scalar>((std::size_t)bnuTilda.size(), nu))
+{
+    const char* who = "SpalartAllmaras::New";
+    if (!mesh.addr || !mesh.boundary || !mesh.average || !mesh.y || !mesh.bY || !mesh.Sf || !mesh.bSf)
+        FatalErrorIn(who, "the addressing, the boundary, the averageData, the wall distance and the face area vectors are needed");
+    if (mesh.patchTypes.size() != mesh.patchFaceCells.size()) FatalErrorIn(who, "one type per patch");
+    const char* names[13] = {"sigmaNut", "kappa", "Cb1", "Cb2", "Cw2", "Cw3", "Cv1", "Cv2", "CDES", "ck", "fwStar", "cl", "ct"};
+    mi_sa_coeffs d{};
+    miCheck(mi_sa_coeffs_init(nullptr, nullptr, &d), who);
+    scalar model[13] = {d.sigmaNut, d.kappa, d.Cb1, d.Cb2, d.Cw2, d.Cw3, d.Cv1, d.Cv2, d.CDES, d.ck, d.fwStar, d.cl, d.ct};
+    for (int i = 0; i < 13; ++i) coeffDict.readIfPresent(names[i], model[i]);
+    scalar wall[2] = {d.wallKappa, d.E};                    // the wall function's own kappa and E
+    coeffDict.readIfPresent("wallKappa", wall[0]); coeffDict.readIfPresent("E", wall[1]);
+    scalar ash = 1;
+    coeffDict.readIfPresent("ashfordCorrection", ash);
+    ashfordCorrection_ = ash != 0;
+    miCheck(mi_sa_coeffs_init(model, wall, &coeffs_), who);
+    sigmaNut_ = coeffs_.sigmaNut; kappa_ = coeffs_.kappa; Cb1_ = coeffs_.Cb1; Cb2_ = coeffs_.Cb2; Cw1_ = coeffs_.Cw1; Cw2_ = coeffs_.Cw2; Cw3_ = coeffs_.Cw3;
+    Cv1_ = coeffs_.Cv1; Cv2_ = coeffs_.Cv2; CDES_ = coeffs_.CDES; ck_ = coeffs_.ck; fwStar_ = coeffs_.fwStar; cl_ = coeffs_.cl; ct_ = coeffs_.ct;
+    std::vector<int32_t> isWall;
+    label off = 0;
+    for (std::size_t p = 0; p < mesh.patchFaceCells.size(); ++p) {
+        isWall.push_back(mesh.patchTypes[p] == wallFunction ? 1 : 0);
+        start_.push_back(off);
+        patches_.emplace_back(new fvPatchCells(mesh.addr->size(), mesh.patchFaceCells[p]));
+        off += (label)mesh.patchFaceCells[p].size();
+    }
+    start_.push_back(off);
+    if (off != nb_ || mesh.bY->size() != nb_) FatalErrorIn(who, "the boundary fields do not have one value per boundary face");
+    miCheck(mi_ke_create(mesh.addr->handle(), mesh.boundary->handle(), isWall.data(), &h_), who);
+}
+SpalartAllmarasBase::~SpalartAllmarasBase() { if (h_) mi_ke_destroy(h_); }
+void SpalartAllmarasBase::evaluateBoundary(const scalargpuField& vf, scalargpuField& bvf) const
+{
+    for (std::size_t p = 0; p < patches_.size(); ++p)
+        if (mesh_.patchTypes[p] != fixedValue && patches_[p]->size() > 0)
+            miCheck(mi_patch_internal_field(patches_[p]->handle(), vf.data(), bvf.data() + start_[p]), "fvPatchField::evaluate");
+}
+void SpalartAllmarasBase::grad(vectorgpuField& g, vectorgpuField& bg, const scalargpuField& vf, const scalargpuField& bvf) const
+{
+    // kOmegaSST::grad: fvc::grad with `Gauss linear` and gaussGrad::correctBoundaryConditions
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const lduAddressing& a = *mesh_.addr;
+    const label n = a.size();
+    scalargpuField ssf(mesh_.magSf->size());
+    miCheck(mi_face_interpolate(a.handle(), mesh_.weights->data(), vf.data(), ssf.data()), "linear::interpolate");
+    miCheck(mi_gauss_grad(a.handle(), mesh_.Sf->component(0).data(), mesh_.Sf->component(1).data(), mesh_.Sf->component(2).data(), ssf.data(), nullptr,
+                          g.component(0).data(), g.component(1).data(), g.component(2).data()), "gaussGrad::gradf");
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        if (patches_[p]->size() == 0) continue;
+        for (direction d = 0; d < 3; ++d)
+            miCheck(mi_patch_add_product(patches_[p]->handle(), mesh_.bSf->component(d).data() + start_[p], bvf.data() + start_[p], g.component(d).data(), 0),
+                    "gaussGrad::gradf (patch)");
+    }
+    for (direction d = 0; d < 3; ++d) miCheck(mi_vec_div(ctx, n, g.component(d).data(), mesh_.V->data(), g.component(d).data()), "gaussGrad /= V");
+    scalargpuField pif(nb_), diff(nb_), sn(std::vector<scalar>((std::size_t)nb_, 0.0));
+    for (std::size_t p = 0; p < patches_.size(); ++p)
+        if (patches_[p]->size() > 0) miCheck(mi_patch_internal_field(patches_[p]->handle(), vf.data(), pif.data() + start_[p]), "patchInternalField");
+    fieldAxpby(diff, 1.0, bvf, -1.0, pif);
+    fieldSubMul(sn, *mesh_.bDeltaCoeffs, diff);            // 0 - dc*diff, then the exact negation
+    fieldAxpby(sn, -1.0, sn, 0.0, sn);
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        if (patches_[p]->size() == 0) continue;
+        const label s = start_[p];
+        const double* snp[1] = {sn.data() + s};
+        const double* gc[3] = {g.component(0).data(), g.component(1).data(), g.component(2).data()};
+        double* out[3] = {bg.component(0).data() + s, bg.component(1).data() + s, bg.component(2).data() + s};
+        miCheck(mi_patch_gauss_grad_correct(patches_[p]->handle(), 1, mesh_.bSf->component(0).data() + s, mesh_.bSf->component(1).data() + s,
+                                            mesh_.bSf->component(2).data() + s, mesh_.bMagSf->data() + s, snp, gc, out), "gaussGrad::correctBoundaryConditions");
+    }
+}
+void SpalartAllmarasBase::terms(int kind, bool onBoundary, const flowData& flow, const vectorgpuField& gradNuTilda, termFields& o) const
+{
+    const char* who = "SpalartAllmaras: mi_sa_terms";
+    if (kind >= MI_SA_DES && (!mesh_.delta || !mesh_.bDelta)) FatalErrorIn(who, "the DES kinds need meshData::delta and bDelta");
+    if (kind == MI_SA_IDDES && (!mesh_.hmax || !mesh_.bHmax)) FatalErrorIn(who, "IDDES needs meshData::hmax and bHmax");
+    const vectorgpuField* const* g = onBoundary ? flow.bGradU : flow.gradU;
+    mi_sa_cells x{};
+    x.nutilda_dev = (onBoundary ? bnuTilda_ : nuTilda_).data();
+    for (int j = 0; j < 3; ++j) for (int d = 0; d < 3; ++d) x.grad_dev[3 * j + d] = g[j]->component(d).data();
+    for (int d = 0; d < 3; ++d) x.grad_nutilda_dev[d] = gradNuTilda.component(d).data();
+    x.y_dev = (onBoundary ? mesh_.bY : mesh_.y)->data();
+    x.nu_value = nu_;
+    if (kind >= MI_SA_DES) x.delta_dev = (onBoundary ? mesh_.bDelta : mesh_.delta)->data();
+    if (kind >= MI_SA_DDES) x.nusgs_dev = (onBoundary ? bnut_ : nut_).data();
+    if (kind == MI_SA_IDDES) x.hmax_dev = (onBoundary ? mesh_.bHmax : mesh_.hmax)->data();
+    x.su_grad_out_dev = o.suGrad.data(); x.su_prod_out_dev = o.suProd.data(); x.sp_out_dev = o.sp.data(); x.dnu_out_dev = o.dnu.data();
+    x.fv1_out_dev = o.fv1.data();
+    if (o.S) x.s_out_dev_or_null = o.S->data();
+    if (o.dTilda) x.dtilda_out_dev_or_null = o.dTilda->data();
+    if (o.tanhFd) x.tanh_fd_out_dev_or_null = o.tanhFd->data();
+    miCheck(mi_sa_terms(miEngine::New().ctx, o.sp.size(), &coeffs_, kind, ashfordCorrection_ ? 1 : 0, &x), who);
+}
+void SpalartAllmarasBase::field(int kind, int which, scalargpuField& out, const flowData& flow) const
+{
+    const label n = nuTilda_.size();
+    vectorgpuField g(n), bg(nb_);
+    grad(g, bg, nuTilda_, bnuTilda_);
+    termFields o(n);
+    scalargpuField t(n);
+    if (which == 0) o.S = &out; else if (which == 1) o.dTilda = &out; else o.tanhFd = &t;
+    terms(kind, false, flow, g, o);
+    if (which == 2) {                                       // fd = 1 - tanh(...)
+        const scalargpuField ones(std::vector<scalar>((std::size_t)n, 1.0));
+        fieldAxpby(out, 1.0, ones, -1.0, t);
+    }
+}
+void SpalartAllmarasBase::DnuTildaEff(scalargpuField& out) const
+{
+    const scalargpuField nuField(std::vector<scalar>((std::size_t)nuTilda_.size(), nu_));
+    scalargpuField sum(nuTilda_.size());
+    fieldAxpby(sum, 1.0, nuTilda_, 1.0, nuField);
+    const scalargpuField sig(std::vector<scalar>((std::size_t)nuTilda_.size(), sigmaNut_));
+    miCheck(mi_vec_div(miEngine::New().ctx, sum.size(), sum.data(), sig.data(), out.data()), "SpalartAllmaras::DnuTildaEff");
+}
+void SpalartAllmarasBase::correctNut(const flowData& flow, const scalargpuField* fv1, const scalargpuField* bfv1)
+{
+    const mi_ctx_t ctx = miEngine::New().ctx;
+    const char* who = "SpalartAllmaras: nut";
+    scalargpuField bcalc(nb_);
+    miCheck(mi_sa_nut(ctx, nuTilda_.size(), &coeffs_, fv1 ? 0 : 1, nuTilda_.data(), fv1 ? fv1->data() : nullptr, nullptr, nu_, nut_.data(), nullptr), who);
+    miCheck(mi_sa_nut(ctx, nb_, &coeffs_, bfv1 ? 0 : 1, bnuTilda_.data(), bfv1 ? bfv1->data() : nullptr, nullptr, nu_, bcalc.data(), nullptr), who);
+    // a calculated patch takes the formula on its boundary values; a nutUSpaldingWallFunction patch keeps its value, which calcNut reads
+    for (std::size_t p = 0; p < patches_.size(); ++p)
+        if (mesh_.patchTypes[p] != wallFunction && patches_[p]->size() > 0)
+            miCopyD2D(bnut_.data() + start_[p], bcalc.data() + start_[p], sizeof(scalar) * (std::size_t)(start_[p + 1] - start_[p]));
+    mi_sa_wall w{};
+    for (int d = 0; d < 3; ++d) { w.u_dev[d] = flow.U->component(d).data(); w.b_uw_dev[d] = flow.bU->component(d).data(); }
+    w.b_delta_coeffs_dev = mesh_.bDeltaCoeffs->data(); w.b_y_dev = mesh_.bY->data(); w.b_nuw_dev = bnu_.data(); w.b_nutw_inout_dev = bnut_.data();
+    miCheck(mi_sa_nut_spalding_wall(h_, &coeffs_, &w), "nutUSpaldingWallFunction::calcNut");
+}
+void SpalartAllmarasBase::correct(const flowData& flow, scalar rDeltaT, const dictionary& solverControls, scalar alpha)
+{
+#pragma clang fp contract(off)
+    const lduAddressing& a = *mesh_.addr;
+    const label n = nuTilda_.size(), nf = mesh_.magSf->size();
+    vectorgpuField gradNuTilda(n), bGradNuTilda(nb_);
+    grad(gradNuTilda, bGradNuTilda, nuTilda_, bnuTilda_);
+    termFields o(n), b(nb_);
+    terms(kind(), false, flow, gradNuTilda, o);
+    terms(kind(), true, flow, bGradNuTilda, b);
+    // fvm::ddt(nuTilda) + fvm::div(phi, nuTilda) - fvm::laplacian(DnuTildaEff, nuTilda) - Cb2/sigmaNut*magSqr(grad(nuTilda))
+    //  == Cb1*STilda*nuTilda - fvm::Sp(Cw1*fw*nuTilda/sqr(dTilda), nuTilda)   (RAS :446-455, LES :335-349)
+    const scalargpuField nuTildaOld(nuTilda_);
+    scalargpuField f(nf), gammaMagSf(std::vector<scalar>((std::size_t)nf, 0.0));
+    fvc::interpolate(f, a, *mesh_.weights, o.dnu);
+    fieldSubMul(gammaMagSf, f, *mesh_.magSf);               // 0 - f*magSf, then the exact negation
+    fieldAxpby(gammaMagSf, -1.0, gammaMagSf, 0.0, gammaMagSf);
+    std::vector<bool> coupled(mesh_.patchFaceCells.size(), false);
+    fvScalarMatrix M("nuTilda", a, mesh_.patchFaceCells, coupled);
+    mi_fvm_terms t{};
+    const double* po[1] = {nuTildaOld.data()}; const double* sd[2] = {o.suGrad.data(), o.suProd.data()}; const double sg[2] = {-1.0, -1.0};
+    double* so[1] = {M.source().data()};
+    t.ddt = 1; t.r_delta_t = rDeltaT; t.rho_value = 1.0; t.vol_dev = mesh_.V->data();
+    t.div_flux_dev = flow.phi->data(); t.div_weights_dev = (flow.divWeights ? flow.divWeights : mesh_.weights)->data();
+    t.lap_delta_coeffs_dev = mesh_.deltaCoeffs->data(); t.lap_gamma_magsf_dev = gammaMagSf.data();
+    t.n_rhs = 1; t.psi_old_dev = po;
+    t.sp_dev = o.sp.data(); t.sp_sign = 1.0;
+    t.n_su = 2; t.su_dev = sd; t.su_sign = sg;              // (source + V*su_grad) + V*su_prod, the reference's grouping
+    miCheck(mi_fvm_assemble(a.handle(), &t, M.lower().data(), M.upper().data(), M.diag().data(), so, nullptr), "SpalartAllmaras: fvm::assemble");
+    const std::vector<scalar> bg = b.dnu.asHost(), bms = mesh_.bMagSf->asHost(), bdc = mesh_.bDeltaCoeffs->asHost(), bphi = flow.bPhi->asHost(),
+                              bval = bnuTilda_.asHost();
+    for (std::size_t p = 0; p < patches_.size(); ++p) {
+        const label m = start_[p + 1] - start_[p];
+        std::vector<scalar> ic((std::size_t)m), bc((std::size_t)m);
+        for (label i = 0; i < m; ++i) {
+            const std::size_t j = (std::size_t)(start_[p] + i);
+            if (mesh_.patchTypes[p] == fixedValue) {
+                const scalar gm = bg[j] * bms[j], diff = gm * bdc[j];
+                const scalar x = diff * bval[j], y = bphi[j] * bval[j];
+                ic[(std::size_t)i] = diff; bc[(std::size_t)i] = x - y;
+            } else { ic[(std::size_t)i] = bphi[j]; bc[(std::size_t)i] = 0.0; }
+        }
+        M.internalCoeffs()[p] = ic; M.boundaryCoeffs()[p] = bc;
+    }
+    M.relax(alpha, nuTilda_);
+    M.solve(nuTilda_, solverControls);
+    evaluateBoundary(nuTilda_, bnuTilda_);
+    bound(nuTilda_, &bnuTilda_, *mesh_.average, *mesh_.weights, 0.0);
+    if (storedFv1()) correctNut(flow, &o.fv1, &b.fv1); else correctNut(flow, nullptr, nullptr);
+}
+namespace RASModels
+{
+SpalartAllmaras::SpalartAllmaras(const meshData& mesh, const flowData& flow, scalar nu, const scalargpuField& nuTilda, const scalargpuField& bnuTilda,
+                                 const dictionary& coeffDict)
+    : SpalartAllmarasBase(mesh, nu, nuTilda, bnuTilda, coeffDict)
+{
+    correctNut(flow, nullptr, nullptr);                     // nut_ = nuTilda_*fv1(this->chi()) (:426): the reference reads nut; here it is formed
+}
+}
+namespace LESModels
+{
+SpalartAllmaras::SpalartAllmaras(const meshData& mesh, scalar nu, const scalargpuField& nuTilda, const scalargpuField& bnuTilda, const dictionary& coeffDict, bool)
+    : SpalartAllmarasBase(mesh, nu, nuTilda, bnuTilda, coeffDict) {}
+SpalartAllmaras::SpalartAllmaras(const meshData& mesh, const flowData& flow, scalar nu, const scalargpuField& nuTilda, const scalargpuField& bnuTilda,
+                                 const dictionary& coeffDict)
+    : SpalartAllmarasBase(mesh, nu, nuTilda, bnuTilda, coeffDict)
+{
+    updateSubGridScaleFields(flow);                         // :310
+}
+void SpalartAllmaras::updateSubGridScaleFields(const flowData& flow) { correctNut(flow, nullptr, nullptr); }
+void SpalartAllmaras::S(scalargpuField& out, const flowData& flow) const { field(MI_SA_DES, 0, out, flow); }
+void SpalartAllmaras::dTilda(scalargpuField& out, const flowData& flow) const { field(MI_SA_DES, 1, out, flow); }
+SpalartAllmarasDDES::SpalartAllmarasDDES(const meshData& mesh, const flowData& flow, scalar nu, const scalargpuField& nuTilda, const scalargpuField& bnuTilda,
+                                         const dictionary& coeffDict)
+    : SpalartAllmaras(mesh, nu, nuTilda, bnuTilda, coeffDict, true)
+{
+    updateSubGridScaleFields(flow);
+}
+void SpalartAllmarasDDES::fd(scalargpuField& out, const flowData& flow) const { field(MI_SA_DDES, 2, out, flow); }
+void SpalartAllmarasDDES::S(scalargpuField& out, const flowData& flow) const { field(MI_SA_DDES, 0, out, flow); }
+void SpalartAllmarasDDES::dTilda(scalargpuField& out, const flowData& flow) const { field(MI_SA_DDES, 1, out, flow); }
+SpalartAllmarasIDDES::SpalartAllmarasIDDES(const meshData& mesh, const flowData& flow, scalar nu, const scalargpuField& nuTilda, const scalargpuField& bnuTilda,
+                                           const dictionary& coeffDict)
+    : SpalartAllmaras(mesh, nu, nuTilda, bnuTilda, coeffDict, true)
+{
+    updateSubGridScaleFields(flow);
+}
+void SpalartAllmarasIDDES::fd(scalargpuField& out, const flowData& flow) const { field(MI_SA_IDDES, 2, out, flow); }
+void SpalartAllmarasIDDES::dTilda(scalargpuField& out, const flowData& flow) const { field(MI_SA_IDDES, 1, out, flow); }
+}
+}
 // ---- LESdelta, simpleFilter and incompressible::LESModels -------------------------------------------------------------------
 LESdelta::LESdelta(label nCells, label nBoundaryFaces)
     : delta_(std::vector<scalar>((std::size_t)nCells, 1e-15)), bdelta_(std::vector<scalar>((std::size_t)nBoundaryFaces, 1e-15)) {}   // LESdelta.C:53
